@@ -3,7 +3,10 @@
 
 One "step" = one whole tracker step (bilateral / pyramid / maps, 19 ICP iterations, TSDF integrate, TSDF raycast, model
 pyramid) on one synthetic 640x480 depth frame that is already resident in HBM when the timed region starts.  Prints ONE
-JSON line (the task contract) with, beside the contract's keys (SURVEY.md 8(d), row by row):
+JSON line (the task contract).  A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the line: metric, value, unit, ms_per_step, dtype, tracking, frame_ms and the configuration.
+--dump-outputs DIR also writes what the last timed step computed as .npy files (dump_outputs below).  With --full the
+line carries, beside those keys, everything else the benchmark measures (SURVEY.md 8(d), row by row):
 
   roofline        integrate stage vs the HBM roofline: algorithmic bytes = 8 B x V_upd + 2 B x W x H per launch (V_upd
                   counted by the library's own count-only kernels), duration from HIP events on the library's stream over a
@@ -18,7 +21,8 @@ JSON line (the task contract) with, beside the contract's keys (SURVEY.md 8(d), 
   cpu_baseline    the CPU oracle (kind "port") on this box's host cores: all cores and one thread, built -O3 -march=native
   concurrent_rooms_one_gpu   2 and 4 independent rooms scanned at once on the one GPU (BASELINE configs[4] on a single device)
 
-  python bench.py                                   # 1 GPU, 512^3
+  python bench.py                                   # 1 GPU, 512^3: the timed region only
+  python bench.py --full                            # 1 GPU, 512^3: + every block above
   python bench.py --gpus N                          # bare, or under python -m torch.distributed.run --nproc-per-node N
       ONE volume sharded as z-slabs over N GPUs through the C ABI (hsk_group_*), every form on the same frames, each on
       fresh worker processes: "rccl" (two ncclAllReduce composites per frame), "rccl_icp_allreduce" (the north_star's
@@ -41,38 +45,12 @@ import time
 
 import numpy as np
 
-from bench_common import HBM_PEAK_GBS, ROOT, SLAB_FORMS, W, H, check_build, emit, make_frames
+from bench_common import HBM_PEAK_GBS, ROOT, SLAB_FORMS, W, H, check_build, emit, host_cores, make_frames, synth_frames
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # CPU baseline (the only place, with the raycast step count, where bench.py touches oracle/)
 # ---------------------------------------------------------------------------------------------------------------------
-def host_cores():
-    """the CPU cores this process can really use: its affinity mask, cut down to the container's CPU quota (cgroup v2
-    cpu.max / v1 cfs quota) -- 256 OpenMP threads on a 16-core quota run 30 times slower than 16"""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 1
-    quota = None
-    try:
-        q, p = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-        if q != "max":
-            quota = float(q) / float(p)
-    except (OSError, ValueError):
-        try:
-            q = float(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read())
-            p = float(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
-            if q > 0:
-                quota = q / p
-        except (OSError, ValueError):
-            pass
-    if quota is not None:
-        n = max(1, min(n, int(quota + 0.5)))
-    return n
-
-
-
 def cpu_baseline(volume, hsk, budget_s=12.0):
     """Oracle (CPU restatement, kind "port") on a bounded sample of the same workload, all host cores, then one thread."""
     from oracle import oracle as O
@@ -397,6 +375,38 @@ def stream_replay(hsk, n, path, local_rank=0, first=0, count=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE_VOXELS = 1 << 20
+DUMP_SEED = 1234
+
+
+def dump_outputs(path, trk, pose, tracked):
+    """--dump-outputs DIR: what the timed path computed in its last step, as .npy files (float32; the voxel indices
+    float64) -- the pose and tracking flag hsk_wait_frame returned for it, the model vertex / normal maps its raycast
+    left for the next frame (level 0: 2 x 3.7 MB), and the TSDF it left (hsk_download_tsdf, which brings the deferred
+    weights up to date) as a fixed, seeded sample of 2^20 voxel draws: flat index x + X (y + Y z), value and weight.
+    Every array is finite: the maps mark a pixel without a surface by NaN, which the dump writes as 0, with
+    model_valid_l0 (H x W, 1 where every component of both maps is finite) beside them."""
+    os.makedirs(path, exist_ok=True)
+    trk.synchronize()
+    vmap, nmap = trk.download_map(2, 0), trk.download_map(3, 0)
+    valid = np.isfinite(vmap).all(axis=0) & np.isfinite(nmap).all(axis=0)
+    out = {"pose": np.asarray(pose, np.float32), "tracked": np.array([float(tracked)], np.float32),
+           "model_vertex_l0": np.where(np.isfinite(vmap), vmap, np.float32(0)), "model_normal_l0": np.where(np.isfinite(nmap), nmap, np.float32(0)),
+           "model_valid_l0": valid.astype(np.float32)}
+    pairs = trk.download_tsdf().reshape(-1, 2)
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, pairs.shape[0], DUMP_SAMPLE_VOXELS, dtype=np.int64))
+    out["tsdf_sample_index"] = idx.astype(np.float64)
+    out["tsdf_sample_value"] = pairs[idx, 0].astype(np.float32)
+    out["tsdf_sample_weight"] = pairs[idx, 1].astype(np.float32)
+    del pairs
+    bad = [name for name, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit("--dump-outputs: non-finite values in %s" % ", ".join(bad))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def timed_single(hsk, torch, n, K, Wm, ahead, dev_frames, local_rank, graph=0, sync_api=False, init_pose=None, host_frames=None):
     """the timed region at one GPU: warm-up, then K frames through hsk_submit_frame_dev / hsk_wait_frame (frames resident in
     HBM) -- or, host_frames given, the SAME frames as host buffers through hsk_submit_frame / hsk_wait_frame, the call the
@@ -450,6 +460,7 @@ def timed_single(hsk, torch, n, K, Wm, ahead, dev_frames, local_rank, graph=0, s
     elapsed = time.perf_counter() - t0
     if gc_was:
         gc.enable()
+    timed_single.last_tracked = ok   # (the last timed step's tracking flag, for --dump-outputs)
     per = np.diff(np.array([t0] + stamps)) * 1e3
     return trk, pose, lost, elapsed, per
 
@@ -603,16 +614,19 @@ def run_single(args, hsk, torch, local_rank):
     t_wall0 = time.perf_counter()
     K, Wm, n = args.steps, args.warmup, args.volume
     total = 1 + Wm + K
-    poses_gt, frames = make_frames(hsk, 0, total)
-    dev_all = torch.from_numpy(np.stack(frames).view(np.int16)).cuda(local_rank)  # one upload
+    poses_gt, distinct, index = synth_frames(hsk, 0, total)
+    frames = [distinct[j] for j in index]
+    # one upload of the distinct frames, then every step's frame a buffer of its own in HBM, as make_frames' stack gave it
+    dev_all = torch.from_numpy(distinct.view(np.int16)).cuda(local_rank)[torch.from_numpy(index).cuda(local_rank)]
     dev_frames = [dev_all[i] for i in range(total)]
     torch.cuda.synchronize()
     trk, pose, lost, elapsed, per = timed_single(hsk, torch, n, K, Wm, args.ahead, dev_frames, local_rank, args.graph, args.sync_api)
+    tracked = timed_single.last_tracked
     gt = poses_gt[total - 1]
     # the SAME frames through the boundary's own calls: host pointers, pipelined (hsk_submit_frame /
     # hsk_wait_frame: what INTEGRATION.md section 5 binds) and one hsk_process_frame per frame (SURVEY.md 8(d) metric (1))
     api = {}
-    if not args.no_host_frames:
+    if args.full and not args.no_host_frames:
         for key, kw in (("host_frames_pipelined_fps", {}), ("sync_process_frame_fps", {"sync_api": True})):
             t_h, pose_h, lost_h, el_h, per_h = timed_single(hsk, torch, n, K, Wm, args.ahead, dev_frames, local_rank, args.graph, host_frames=frames, **kw)
             t_h.close()
@@ -642,6 +656,12 @@ def run_single(args, hsk, torch, local_rank):
                      "p90": round(float(np.percentile(per, 90)), 4),
                      "note": "host clock between consecutive hsk_wait_frame returns over the timed region"},
     }
+    if not args.full:   # a plain run: the headline and nothing else
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, trk, pose, tracked)
+        trk.close()
+        out["bench_wall_s"] = round(time.perf_counter() - t_wall0, 1)
+        return out
     # ---- stage times + roofline of the dominant kernel group (integrate) ----
     rep, ms, nf, icp_ms, v_mean, _ = replay_with_events(hsk, n, K, Wm, frames, dev_frames, local_rank, pose)
     traffic, tinfo, ray_pmc = (None, "skipped (--no-traffic)", None)
@@ -688,6 +708,8 @@ def run_single(args, hsk, torch, local_rank):
         out["roofline"]["flush_note"] = ("only hsk_download_tsdf flushes (it hands the weights out; %.1f ms by itself at this size); clouds and meshes "
                                          "do not: a host that takes a product per frame pays the product, not the flush" % out["readout_ms"].get("download_tsdf_ms", 0.0))
         out["roofline"]["frac_with_flush_every_frame"] = round(out["roofline"]["algorithmic_bytes_per_launch"] / ((out["stage_us"]["integrate"] + fl) * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)
+    if args.dump_outputs:   # (after the read-outs: they change no output, and their first-call timings stay first calls)
+        dump_outputs(args.dump_outputs, trk, pose, tracked)
     trk.close()
     if not args.no_noise:
         # the room scan (camera INSIDE the volume: what HouseScan's rooms are made with), holes as a sensor makes them, and
@@ -758,6 +780,13 @@ def main():
     ap.add_argument("--no-rooms", action="store_true", help="skip the concurrent-room blocks (N = 1: 2 and 4 rooms at once on the one GPU; N > 1, --mode slab: one room per GPU, a room per GPU pair)")
     ap.add_argument("--no-noise", action="store_true", help="skip the other-stream blocks (the timed region again on the room scan, the sensor-holes stream and the noise run: room_ / holes_ / noise_<volume>)")
     ap.add_argument("--quick", action="store_true", help="all of the above")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: besides the timed region, everything else the benchmark measures (stage times, roofline, counters, host-pointer "
+                         "figures, read-outs, other streams, rooms, 1024^3, CPU baseline; the --no-* options above leave parts out).  Without it "
+                         "a run does only what its headline needs.  (N > 1: the launcher's line is the same either way)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: after the timed steps, write what the last of them computed to DIR/<name>.npy (pose, tracking flag, model "
+                         "maps, a seeded sample of the TSDF; --stream: the poses of the replay)")
     ap.add_argument("--ahead", type=int, default=1, help="frames submitted ahead of the one being waited for (1 or 2)")
     ap.add_argument("--graph", type=int, default=0, help="synchronous frames replayed from a hipGraph (default: eager, through the ring)")
     ap.add_argument("--sync-api", action="store_true", help="time hsk_process_frame_dev (one host sync per frame) instead of submit/wait")
@@ -803,6 +832,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     multi = args.gpus > 1 or world > 1 or bool(os.environ.get("HSK_BENCH_FORCE_MULTI"))  # (the variable: the N > 1 flow on one rank, for the tests)
+    if multi and args.dump_outputs and not args.stream:
+        raise SystemExit("--dump-outputs: the single-GPU line only (--gpus 1)")
     if multi and not args.stream and not (args.engine == "torch" and args.mode == "slab"):
         import bench_launcher   # (no GPU call, no torch import in THIS process: its workers are fresh processes, never an exec)
         return bench_launcher.launch(args)
@@ -819,7 +850,13 @@ def main():
     if args.stream:
         if not os.path.exists(args.stream):
             record_synthetic(hsk, args.stream, 300)
-        rep, _ = stream_replay(hsk, args.volume, args.stream, local_rank)
+        rep, poses = stream_replay(hsk, args.volume, args.stream, local_rank)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            poses = np.asarray(poses, np.float32)
+            if not np.isfinite(poses).all():
+                raise SystemExit("--dump-outputs: non-finite values in poses")
+            np.save(os.path.join(args.dump_outputs, "poses.npy"), poses)
         out = {"metric": "frames/sec fused (640x480 into %d^3 TSDF): integrate+ICP+raycast" % args.volume,
                "value": rep["frames_per_s_file_and_pcie_inclusive"], "unit": "frames/s", "n_gpus": 1, "steps": rep["frames"], "warmup": 0,
                "ms_per_step": round(1e3 / rep["frames_per_s_file_and_pcie_inclusive"], 4), "higher_is_better": True, "scaling": "weak",

@@ -12,9 +12,56 @@ W, H = 640, 480
 SLAB_FORMS = ("rccl", "rccl_icp_allreduce", "direct")   # the forms of the N > 1 z-slab path (bench_launcher.py)
 
 
-def make_frames(hsk, first, count):
+def host_cores():
+    """the CPU cores this process can really use: its affinity mask, cut down to the container's CPU quota (cgroup v2
+    cpu.max / v1 cfs quota) -- 256 OpenMP threads on a 16-core quota run 30 times slower than 16"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    quota = None
+    try:
+        q, p = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if q != "max":
+            quota = float(q) / float(p)
+    except (OSError, ValueError):
+        try:
+            q = float(open("/sys/fs/cgroup/cpu/cpu.cfs_quota_us").read())
+            p = float(open("/sys/fs/cgroup/cpu/cpu.cfs_period_us").read())
+            if q > 0:
+                quota = q / p
+        except (OSError, ValueError):
+            pass
+    if quota is not None:
+        n = max(1, min(n, int(quota + 0.5)))
+    return n
+
+
+def synth_frames(hsk, first, count):
+    """frames first .. first + count - 1 of the scripted stream, hsk.synth_depth(hsk.synth_pose(k)) bit for bit, in a time
+    that hardly grows with count: a frame is a function of its float32 pose alone and the scripted poses repeat (300
+    distinct ones in the first 300 frames, 825 in the first 20000), so each distinct pose is rendered once, on the host
+    cores this process may use (hsk_synth_render runs outside the GIL).
+    -> (poses, distinct frames [U, H, W] uint16, index [count] of every frame's distinct one)"""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
     poses = [hsk.synth_pose(k) for k in range(first, first + count)]
-    return poses, [hsk.synth_depth(p) for p in poses]
+    slot, distinct = {}, []
+    index = np.empty(count, np.int64)
+    for k, p in enumerate(poses):
+        index[k] = slot.setdefault(p.tobytes(), len(distinct))
+        if index[k] == len(distinct):
+            distinct.append(p)
+    with ThreadPoolExecutor(max_workers=host_cores()) as ex:
+        rendered = np.stack(list(ex.map(hsk.synth_depth, distinct)))
+    return poses, rendered, index
+
+
+def make_frames(hsk, first, count):
+    """(poses, frames) of the scripted stream; repeated frames are views of one read-only array"""
+    poses, distinct, index = synth_frames(hsk, first, count)
+    distinct.flags.writeable = False
+    return poses, [distinct[j] for j in index]
 
 
 def check_build(args):

@@ -1245,7 +1245,7 @@ def test_bench_two_ranks_match_one(tmp_path):
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 
-    one = last_json([sys.executable, "bench.py"] + common)
+    one = last_json([sys.executable, "bench.py", "--full"] + common)
     assert one["tracking"]["lost_frames"] == 0 and one["roofline"]["traffic"] is None and "frame_ms" in one
     for icp in ("replicated", "allreduce"):
         with socket.socket() as s:

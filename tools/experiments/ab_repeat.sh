@@ -19,7 +19,7 @@ n=$i
 for r in $(seq 1 $reps); do
   for i in $(seq 0 $((n-1))); do
     cp /tmp/libhsk_v$i.so housescan_amd/libhskinfu.so
-    python bench.py --allow-exp --quick --steps ${STEPS:-60} --warmup 10 --volume ${VOL:-512} 2>/dev/null | grep -o '{"metric.*' | python -c "
+    python bench.py --full --allow-exp --quick --steps ${STEPS:-60} --warmup 10 --volume ${VOL:-512} 2>/dev/null | grep -o '{"metric.*' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_us']; print('v$i rep $r fps %.0f icp %.1f integrate %.1f raycast %.1f frac %.3f' % (d['value'], s['icp'], s['integrate'], s['raycast'], d['roofline']['frac']))"
   done

@@ -11,7 +11,7 @@ for fl in "" "-DICP_BLOCK=512 -DICP_PX_FINE=3 -DICP_PX_MID=1" "-DICP_BLOCK=512 -
 done
 for r in 1 2 3; do for v in 0 1 2 3 4 5; do
   cp /tmp/libicp_v$v.so housescan_amd/libhskinfu.so
-  python bench.py --allow-exp --quick --steps 60 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
+  python bench.py --full --allow-exp --quick --steps 60 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_us']; print('v$v rep $r fps %.0f icp %.1f per-iter %s' % (d['value'], s['icp'], {k:v for k,v in d['icp_us_per_iter'].items() if k!='note'}))"
 done; done

@@ -9,7 +9,7 @@ for fl in "" "-mllvm -amdgpu-sched-strategy=max-ilp" "-mllvm -amdgpu-sched-strat
 done
 for r in 1 2 3 4; do for i in 0 1 2; do
   cp /tmp/libimg_v$i.so housescan_amd/libhskinfu.so
-  python bench.py --allow-exp --quick --steps 60 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
+  python bench.py --full --allow-exp --quick --steps 60 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_us']; print('v$i rep $r fps %.0f icp %.1f pre %.1f' % (d['value'], s['icp'], s['preprocess']))"
 done; done

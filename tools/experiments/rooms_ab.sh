@@ -15,7 +15,7 @@ n=$i
 for r in $(seq 1 $reps); do
   for i in $(seq 0 $((n-1))); do
     cp /tmp/libhsk_v$i.so housescan_amd/libhskinfu.so
-    python bench.py --allow-exp --no-cpu-baseline --no-traffic --no-1024 --no-host-frames --no-readout --no-trajectory --steps 100 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
+    python bench.py --full --allow-exp --no-cpu-baseline --no-traffic --no-1024 --no-host-frames --no-readout --no-trajectory --steps 100 --warmup 10 2>/dev/null | grep -o '{"metric.*' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['concurrent_rooms_one_gpu']; print('v$i rep $r one room %.0f  two %.0f  four %.0f  icp %.1f' % (d['value'], c['2_rooms']['frames_per_s_in_all'], c['4_rooms']['frames_per_s_in_all'], d['stage_us']['icp']))"
   done

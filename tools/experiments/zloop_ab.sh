@@ -7,7 +7,7 @@ make -s -j8 -C housescan_amd/csrc FLAGS="$BASE -DHSK_PA_ZLOOP -DINTEGRATE_WPE=7 
 cp housescan_amd/libhskinfu.so /tmp/lib_zloop.so
 HSK_PA_ZSPLIT=4 python tools/quick_parity.py 128 256 2>&1 | tail -1
 HSK_PA_ZSPLIT=16 python tools/quick_parity.py 512 2>&1 | tail -1
-run() { python bench.py --allow-exp --quick --steps 60 --warmup 10 --volume $1 2>/dev/null | grep -o '{"metric.*' | python -c "
+run() { python bench.py --full --allow-exp --quick --steps 60 --warmup 10 --volume $1 2>/dev/null | grep -o '{"metric.*' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d['stage_us']; print('$2 vol $1 fps %.0f icp %.1f integrate %.1f raycast %.1f frac %.3f' % (d['value'], s['icp'], s['integrate'], s['raycast'], d['roofline']['frac']))"; }
 for rep in 1 2; do

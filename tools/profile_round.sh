@@ -7,14 +7,14 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/round
 rm -rf $OUT/trace; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --quick > $OUT/bench_profiled.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --quick > $OUT/bench_profiled.log 2>&1
 cp $OUT/trace/*/*_kernel_stats.csv $OUT/kernel_stats.csv
 grep -o '{"metric.*' $OUT/bench_profiled.log > $OUT/bench_profiled.json
 cd $ROOT && tools/pmc.sh gpurun_out/round/pmc > $OUT/pmc_summary.txt 2>&1
 cp $OUT/pmc/integrate_traffic.json $OUT/ 2>/dev/null
 # the same at 1024^3 (the HBM measurement): kernel averages of a 40-frame run
 rm -rf $OUT/trace1024
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1024 -- python3 $ROOT/bench.py --quick --volume 1024 --steps 40 --warmup 5 > $OUT/bench_profiled_1024.log 2>&1)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1024 -- python3 $ROOT/bench.py --full --quick --volume 1024 --steps 40 --warmup 5 > $OUT/bench_profiled_1024.log 2>&1)
 cp $OUT/trace1024/*/*_kernel_stats.csv $OUT/kernel_stats_1024.csv
 grep -o '{"metric.*' $OUT/bench_profiled_1024.log > $OUT/bench_profiled_1024.json
 rm -rf $OUT/trace1024

@@ -9,14 +9,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import housescan_amd as hsk  # noqa: E402
+from bench_common import make_frames  # noqa: E402
 
 
 def stream_frames(hsk, stream, count):
     """(ground-truth poses, frames, init_pose or None) of the named synthetic stream -- the one place that maps a stream's
     name to its frames (bench.py's blocks and their counter passes must see the same frames)"""
     if stream in (None, "", "scripted"):
-        gts = [hsk.synth_pose(k) for k in range(count)]
-        return gts, [hsk.synth_depth(p) for p in gts], None
+        gts, frames = make_frames(hsk, 0, count)   # (each distinct pose rendered once: bench.py --full replays its whole window)
+        return gts, frames, None
     if stream == "noise":      # SURVEY.md 8(d)'s noise run: sigma = 1.2 mm z^2, 2 % independent dropout
         gts, fr = hsk.synth_noisy_frames(count)
         return gts, fr, None
