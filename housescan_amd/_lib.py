@@ -73,6 +73,13 @@ SYMBOLS = {
     "hsk_extract_cloud": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_extract_mesh": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_extract_mesh_cubes": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_enable_color": (C.c_int, [_P, C.c_int, C.c_float]),
+    "hsk_process_frame_rgbd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _F, _I]),
+    "hsk_submit_frame_rgbd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "hsk_integrate_color": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _F]),
+    "hsk_download_color": (C.c_int, [_P, _P]),
+    "hsk_upload_color": (C.c_int, [_P, _P]),
+    "hsk_extract_cloud_attrs": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_mgpu_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_prefetch": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_front": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
@@ -120,10 +127,14 @@ SYMBOLS = {
     "hsk_synth_room_pose": (C.c_int, [C.c_int, C.c_int, C.c_int, _F]),
     "hsk_synth_room_render": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "hsk_synth_render_sensor": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_float, C.c_float, C.c_int, _P, _D]),
+    "hsk_synth_color_at": (C.c_int, [C.c_int, _F, _P]),
+    "hsk_synth_render_rgb": (C.c_int, [C.c_int, _F, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "hsk_write_pcd_xyz": (C.c_int, [C.c_char_p, _P, C.c_size_t]),
     "hsk_write_ply_mesh": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_weld_triangles": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "hsk_voxel_downsample": (C.c_int, [_P, C.c_size_t, C.c_float, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_voxel_downsample_attrs": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_float, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_write_pcd_xyzrgbnormal": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_size_t]),
     "hsk_detect_planes": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _I]),
     "hsk_plane_hull": (C.c_int, [_P, C.c_size_t, _P, C.c_int, _F, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_write_planes_txt": (C.c_int, [C.c_char_p, _P, C.c_int]),

@@ -607,6 +607,156 @@ void launch_extract(hipStream_t s, const void* vol, const VolParams& vp, unsigne
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The cloud with normals and colour (hsk_extract_cloud_attrs): the write pass of the cloud again, in a kernel of its own
+// (k_extract is untouched); the points, their count and order come from the same crossing_count, so xyz is bit-identical.
+//   normal: the raycast's -- central differences of the trilinear TSDF one cell either side, scaled by 1 / |n| -- where
+//           floor(p / cell) lies in (1, dims - 2) on every axis (tests/np_twin.py: the raycast's `deep`), NaN elsewhere
+//   colour: of the crossing's voxel with the smaller |tsdf| (the first on a tie), of the other when that one has colour
+//           weight 0, (0, 0, 0) and one count in n_uncolored when both have
+// ------------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ int attr_vox(float p, float cell) {  // floor(p / cell) of the spec, -1 below 0 or NaN
+  const float q = floorf(p / cell);
+  if (!(q >= 0.0f)) return -1;
+  if (q > 1.0e6f) return 1000000;
+  return (int)q;
+}
+static __device__ __forceinline__ float attr_tsdf(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
+  const int zz = z - vp.zs0;
+  if (zz < 0 || zz >= vp.nzs) return 0.0f;
+  return (float)vol[hsk_vox_index(vp, x, y, zz)].x / 32767.0f;
+}
+// the trilinear TSDF sample of A.6 (raycast.hip: trilinear), written with the plain correctly rounded quotients of the spec
+static __device__ float attr_trilinear(const short2* __restrict__ vol, const VolParams& vp, float px, float py, float pz) {
+  int gx = attr_vox(px, vp.cell[0]), gy = attr_vox(py, vp.cell[1]), gz = attr_vox(pz, vp.cell[2]);
+  if (!(gx > 0 && gx < vp.X - 1 && gy > 0 && gy < vp.Y - 1 && gz > 0 && gz < vp.Z - 1)) return HSK_NANF;
+  if (px < ((float)gx + 0.5f) * vp.cell[0]) gx -= 1;
+  if (py < ((float)gy + 0.5f) * vp.cell[1]) gy -= 1;
+  if (pz < ((float)gz + 0.5f) * vp.cell[2]) gz -= 1;
+  const float a = (px - ((float)gx + 0.5f) * vp.cell[0]) / vp.cell[0];
+  const float b = (py - ((float)gy + 0.5f) * vp.cell[1]) / vp.cell[1];
+  const float c = (pz - ((float)gz + 0.5f) * vp.cell[2]) / vp.cell[2];
+  float res = attr_tsdf(vol, vp, gx, gy, gz) * (1.0f - a) * (1.0f - b) * (1.0f - c);
+  res = res + attr_tsdf(vol, vp, gx, gy, gz + 1) * (1.0f - a) * (1.0f - b) * c;
+  res = res + attr_tsdf(vol, vp, gx, gy + 1, gz) * (1.0f - a) * b * (1.0f - c);
+  res = res + attr_tsdf(vol, vp, gx, gy + 1, gz + 1) * (1.0f - a) * b * c;
+  res = res + attr_tsdf(vol, vp, gx + 1, gy, gz) * a * (1.0f - b) * (1.0f - c);
+  res = res + attr_tsdf(vol, vp, gx + 1, gy, gz + 1) * a * (1.0f - b) * c;
+  res = res + attr_tsdf(vol, vp, gx + 1, gy + 1, gz) * a * b * (1.0f - c);
+  res = res + attr_tsdf(vol, vp, gx + 1, gy + 1, gz + 1) * a * b * c;
+  return res;
+}
+// the axes of the crossings crossing_count finds at (x, y, z), in its order (the same tests)
+static __device__ __forceinline__ int crossing_axes(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z, int* axes) {
+  const short2 c = vol[hsk_vox_index(vp, x, y, z - vp.zs0)];
+  if (c.y == 0 || c.x == HSK_DIVISOR) return 0;
+  int n = 0;
+  for (int k = 0; k < 3; ++k) {
+    const int g = k == 0 ? x : (k == 1 ? y : z);
+    const int dim = k == 0 ? vp.X : (k == 1 ? vp.Y : vp.Z);
+    if (g + 1 >= dim) continue;
+    if (k == 2 && (z + 1 - vp.zs0) >= vp.nzs) continue;
+    const short2 nb = vol[hsk_vox_index(vp, x + (k == 0 ? 1 : 0), y + (k == 1 ? 1 : 0), z - vp.zs0 + (k == 2 ? 1 : 0))];
+    if (nb.y == 0 || nb.x == HSK_DIVISOR) continue;
+    if (!((c.x > 0 && nb.x < 0) || (c.x < 0 && nb.x > 0))) continue;
+    axes[n++] = k;
+  }
+  return n;
+}
+
+__global__ __launch_bounds__(256) void k_extract_attrs(const short2* __restrict__ vol, const unsigned* __restrict__ colv, VolParams vp,
+                                                       const unsigned* __restrict__ row_count,
+                                                       const unsigned long long* __restrict__ row_offset, float* __restrict__ xyz,
+                                                       float* __restrict__ normals, unsigned char* __restrict__ rgb,
+                                                       unsigned long long cap, unsigned long long* __restrict__ n_uncolored,
+                                                       const unsigned* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  const int nrows = vp.Y * (vp.zo1 - vp.zo0);
+  if (row >= nrows) return;
+  const int y = row % vp.Y, z = vp.zo0 + row / vp.Y;
+  if (row_count[row] == 0u) return;  // (the count pass found the row empty)
+  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
+  if (row_mask == 0ull) return;
+  unsigned long long base = row_offset[row];
+  unsigned uncol = 0;
+  for (int xb = 0; xb < vp.X; xb += 64) {
+    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 1))) continue;
+    const int x = xb + lane;
+    float pts[9];
+    int axes[3];
+    int n = 0;
+    if (x < vp.X) {
+      n = crossing_count(vol, vp, x, y, z, pts);
+      (void)crossing_axes(vol, vp, x, y, z, axes);
+    }
+    int scan = n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(scan, o, 64);
+      if (lane >= o) scan += v;
+    }
+    const int wave_total = __shfl(scan, 63, 64);
+    unsigned long long at = base + (unsigned long long)(scan - n);
+    for (int q = 0; q < n; ++q, ++at) {
+      if (at >= cap) continue;
+      const float px = pts[3 * q], py = pts[3 * q + 1], pz = pts[3 * q + 2];
+      xyz[3 * at] = px;
+      xyz[3 * at + 1] = py;
+      xyz[3 * at + 2] = pz;
+      if (normals) {
+        float nx = HSK_NANF, ny = HSK_NANF, nz = HSK_NANF;
+        const float qx = floorf(px / vp.cell[0]), qy = floorf(py / vp.cell[1]), qz = floorf(pz / vp.cell[2]);
+        if (qx > 1.0f && qx < (float)(vp.X - 2) && qy > 1.0f && qy < (float)(vp.Y - 2) && qz > 1.0f && qz < (float)(vp.Z - 2)) {
+          const float gxn = attr_trilinear(vol, vp, px + vp.cell[0], py, pz) - attr_trilinear(vol, vp, px - vp.cell[0], py, pz);
+          const float gyn = attr_trilinear(vol, vp, px, py + vp.cell[1], pz) - attr_trilinear(vol, vp, px, py - vp.cell[1], pz);
+          const float gzn = attr_trilinear(vol, vp, px, py, pz + vp.cell[2]) - attr_trilinear(vol, vp, px, py, pz - vp.cell[2]);
+          const float ninv = 1.0f / sqrtf(hsk_dot3(gxn, gyn, gzn, gxn, gyn, gzn));
+          nx = gxn * ninv;
+          ny = gyn * ninv;
+          nz = gzn * ninv;
+        }
+        normals[3 * at] = nx;
+        normals[3 * at + 1] = ny;
+        normals[3 * at + 2] = nz;
+      }
+      if (rgb) {
+        const int k = axes[q];
+        const int zz = z - vp.zs0;
+        const int bx = x + (k == 0 ? 1 : 0), by = y + (k == 1 ? 1 : 0), bzz = zz + (k == 2 ? 1 : 0);
+        const int ta = vol[hsk_vox_index(vp, x, y, zz)].x, tb = vol[hsk_vox_index(vp, bx, by, bzz)].x;
+        const unsigned ca = colv[((size_t)zz * vp.Y + y) * vp.X + x], cb = colv[((size_t)bzz * vp.Y + by) * vp.X + bx];
+        const bool take_a = (ta < 0 ? -ta : ta) <= (tb < 0 ? -tb : tb);
+        unsigned cw = take_a ? ca : cb;
+        if ((cw >> 24) == 0u) cw = take_a ? cb : ca;
+        if ((cw >> 24) == 0u) {
+          cw = 0u;
+          uncol += 1u;
+        }
+        rgb[3 * at] = (unsigned char)(cw & 255u);
+        rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
+        rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
+      }
+    }
+    base += wave_total;
+  }
+  if (rgb && n_uncolored) {
+    unsigned sum = uncol;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
+  }
+}
+
+// the write pass of the cloud with its attributes, behind launch_extract's count pass (pass 0) on the same volume
+void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const unsigned* row_count,
+                          const unsigned long long* row_offset, float* xyz, float* normals, unsigned char* rgb,
+                          unsigned long long cap, unsigned long long* n_uncolored, const unsigned* flags) {
+  const int nrows = vp.Y * (vp.zo1 - vp.zo0);
+  hipLaunchKernelGGL(k_extract_attrs, dim3((nrows + 3) / 4), dim3(256), 0, s, (const short2*)vol, colv, vp, row_count, row_offset, xyz,
+                     normals, rgb, cap, n_uncolored, flags);
+}
+
 // The code object of this file is loaded when one of its kernels is first used (deferred loading): 0.7 ms that the first
 // product of a process would otherwise pay on whatever thread asks for it.  hsk_prepare_readout asks here instead.
 int extract_warm() {

@@ -43,6 +43,14 @@ void launch_extract(hipStream_t s, const void* vol, const VolParams& vp, unsigne
                     unsigned long long* row_offset, unsigned long long* total, float* xyz, unsigned long long cap,
                     int pass, const unsigned* flags);
 size_t hsk_scan_scratch_entries(int nrows);  // entries of a row_offset buffer for nrows rows (the offsets, then the scan's block sums)
+// the cloud's write pass with normals and colour (either may be null), behind launch_extract's count pass (extract.hip)
+void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const unsigned* row_count,
+                          const unsigned long long* row_offset, float* xyz, float* normals, unsigned char* rgb,
+                          unsigned long long cap, unsigned long long* n_uncolored, const unsigned* flags);
+// colour volume (color.hip): one frame's colour into the row-major (r, g, b, w) words `col`, behind the frame's integrate
+void launch_color_integrate(hipStream_t s, unsigned* col, const TrackState* st, const int* has_color, const float* scaled,
+                            const unsigned char* rgb, const float* tiles, const VolParams& vp, int W, int H, Intr in, float band,
+                            int max_w);
 
 // image
 void launch_bilateral_scale(hipStream_t s, const uint16_t* src, int W, int H, Intr in, const float* ws, const float* wc,

@@ -38,6 +38,7 @@ struct ImgBufs {
   float* d_vcur[HSK_NLEVELS] = {};
   float* d_ncur[HSK_NLEVELS] = {};
   float* d_tmax = nullptr;  // tile tables of the scaled depth (see launch_tile_max)
+  unsigned char* d_rgb = nullptr;  // the frame's colour image (RGB8), only once colour is enabled (hsk_enable_color)
 };
 
 struct hsk_ctx {
@@ -138,6 +139,20 @@ struct hsk_ctx {
   double submit_us[4] = {};
   unsigned long long submit_n = 0;
   uint64_t prof_frames = 0;
+  // colour (hsk_enable_color; all null until then): the (r, g, b, w) volume, row-major; per image-buffer set a device flag "this
+  // frame has colour", written when the frame is submitted (the captured graphs read it, with the set's d_rgb); one pinned
+  // staging image (its upload has completed before a submission returns, as the depth frame's has); the read-out's attribute
+  // buffer (a counter, then the normals and the colours of a cloud)
+  unsigned* d_color = nullptr;
+  size_t color_bytes = 0;
+  int* d_has_color = nullptr;
+  unsigned char* h_rgb_stage = nullptr;
+  const unsigned char* rgb_src = nullptr;  // the colour of the frame being submitted (h_rgb_stage), null: a depth-only frame
+  int color_max_w = 0;
+  bool group_slab = false;  // a slab of a group (hsk_group_create*): no colour
+  float color_band = 0.0f;
+  void* d_attr = nullptr;
+  size_t attr_bytes = 0;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -270,6 +285,11 @@ static void free_all(hsk_ctx* k) {
   F(k->d_rowcnt);
   F(k->d_rowoff);
   F(k->d_out);
+  F(k->d_color);
+  F(k->d_has_color);
+  F(k->d_attr);
+  for (auto& b : k->ib) F(b.d_rgb);
+  if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
   for (auto& p : k->h_pin)
     if (p) (void)hipHostFree(p);
   for (auto& e : k->ev_pin)
@@ -314,6 +334,7 @@ static int do_reset(hsk_ctx* k) {
   HIPCHK(k, hipMemsetAsync(k->d_uni, 1, uniform_lane_bytes(k->vp), k->stream));  // 1: "all 16 voxels never observed"
   // ... and the coarse level behind them: 0, "nothing pending, nothing known" (a never-observed block is not quiet)
   HIPCHK(k, hipMemsetAsync(k->d_uni + uniform_lane_bytes(k->vp), 0, k->uni_bytes - uniform_lane_bytes(k->vp), k->stream));
+  if (k->d_color) HIPCHK(k, hipMemsetAsync(k->d_color, 0, k->color_bytes, k->stream));  // (the colour goes with the TSDF)
   memset(k->h_st, 0, sizeof(TrackState));
   memcpy(k->h_st->R, k->init_R, sizeof(k->init_R));
   memcpy(k->h_st->t, k->init_t, sizeof(k->init_t));
@@ -571,6 +592,15 @@ static void enqueue_integrate(hsk_ctx* k, const IcpFinal* fin = nullptr, bool re
                    k->d_uni, report_early ? &ring : nullptr);
 }
 
+// colour (hsk_enable_color): right behind the frame's integrate -- its pose is final there (the integrate's first kernel does
+// the last solve) -- and before its raycast, whose report into the ring says the buffer set's inputs (the colour image with
+// them) are consumed.  Nothing is launched while colour is off.
+static void enqueue_color(hsk_ctx* k) {
+  if (!k->d_color) return;
+  launch_color_integrate(k->stream, k->d_color, k->d_st, k->d_has_color + k->cur, k->B().d_scaled, k->B().d_rgb, k->B().d_tmax, k->vp,
+                         k->lv[0].W, k->lv[0].H, k->lv[0].in, k->color_band, k->color_max_w);
+}
+
 static void enqueue_raycast_and_resize(hsk_ctx* k, int* keys, bool report = false) {
   hipStream_t s = k->stream;
   // report: the raycast (the frame's last reader of the tracker state) writes it into the pinned ring slot the host
@@ -619,6 +649,7 @@ static void enqueue_tracked_frame(hsk_ctx* k, bool with_events) {
   enqueue_icp(k);
   if (with_events) (void)hipEventRecord(k->ev[2], s);
   enqueue_integrate(k);
+  enqueue_color(k);
   if (with_events) (void)hipEventRecord(k->ev[3], s);
   enqueue_raycast_and_resize(k, nullptr);
   if (with_events) (void)hipEventRecord(k->ev[4], s);
@@ -629,6 +660,7 @@ static void enqueue_tracked_rest(hsk_ctx* k) {
   IcpFinal fin;
   enqueue_icp(k, &fin);  // its first iteration also starts the frame (previous pose <- pose, lost flag)
   enqueue_integrate(k, &fin, true);  // ... and its last solve happens in the first kernel of the integrate, which reports the pose
+  enqueue_color(k);
   enqueue_raycast_and_resize(k, nullptr, true);  // pipelined frames report their state through the ring
 }
 
@@ -639,6 +671,7 @@ static int frame_common(hsk_ctx* k, float pose_out[16], int* tracked) {
   if (k->frame == 0) {
     enqueue_preprocess(k, k->stream);
     enqueue_integrate(k);
+    enqueue_color(k);
     for (int l = 0; l < HSK_NLEVELS; ++l)
       launch_transform_maps(s, k->B().d_vcur[l], k->B().d_ncur[l], k->lv[l].W * k->lv[l].H, k->d_st, k->d_vmod[l], k->d_nmod[l]);
     int r = download_state(k);
@@ -656,7 +689,10 @@ static int frame_common(hsk_ctx* k, float pose_out[16], int* tracked) {
     int r = download_state(k);
     if (r != HSK_OK) return r;
     if (!k->h_st->lost) {
-      if (gate_passes(k->h_st, k->cfg.integrate_move_thresh)) enqueue_integrate(k);
+      if (gate_passes(k->h_st, k->cfg.integrate_move_thresh)) {
+        enqueue_integrate(k);
+        enqueue_color(k);
+      }
       enqueue_raycast_and_resize(k, nullptr);
     }
   } else if (k->prof) {
@@ -725,6 +761,16 @@ static int stage_depth_host(hsk_ctx* k, const uint16_t* depth) {
   return HSK_OK;
 }
 
+// with colour enabled, every frame submission says on `s` whether buffer set `set` holds a colour image for it (and uploads
+// the image from the staging buffer): a depth-only frame leaves the colour volume as it is
+static hipError_t stage_color(hsk_ctx* k, int set, hipStream_t s) {
+  if (!k->d_color) return hipSuccess;
+  hipError_t e = hipSuccess;
+  if (k->rgb_src) e = hipMemcpyAsync(k->ib[set].d_rgb, k->rgb_src, (size_t)k->cfg.width * k->cfg.height * 3, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)(k->d_has_color + set), k->rgb_src ? 1 : 0, 1, s);
+  return e;
+}
+
 // The synchronous calls of a steady-state frame go through the pipelined machinery (submit + wait: eager launches, the
 // preprocessing on the second stream, the pose reported through the pinned ring), which leaves less idle GPU around the
 // frame than a hipGraph launch followed by a copy and a stream synchronisation (2206 -> 2450 frames/s).  use_graph = 1
@@ -748,6 +794,7 @@ extern "C" int hsk_process_frame(hsk_ctx* k, const uint16_t* depth, int w, int h
   leave_slab_bookkeeping(k);
   r = stage_depth_host(k, depth);
   if (r != HSK_OK) return r;
+  HIPCHK(k, stage_color(k, k->cur, k->stream));
   return frame_common(k, pose_out, tracked);
 }
 
@@ -763,6 +810,7 @@ extern "C" int hsk_process_frame_dev(hsk_ctx* k, const void* depth_dev, int w, i
   }
   leave_slab_bookkeeping(k);
   HIPCHK(k, hipMemcpyAsync(k->B().d_raw, depth_dev, (size_t)w * h * 2, hipMemcpyDeviceToDevice, k->stream));
+  HIPCHK(k, stage_color(k, k->cur, k->stream));
   return frame_common(k, pose_out, tracked);
 }
 
@@ -855,6 +903,7 @@ static int submit_frame(hsk_ctx* k, const void* depth_dev, hipMemcpyKind kind, i
       if (r != HSK_OK) return r;
     }
     HIPCHK(k, hipMemcpyAsync(k->B().d_raw, depth_dev, (size_t)w * h * 2, kind, s));
+    HIPCHK(k, stage_color(k, k->cur, s));
     float pose[16];
     int tracked = 0;
     r = frame_common(k, pose, &tracked);
@@ -899,6 +948,7 @@ static int submit_frame(hsk_ctx* k, const void* depth_dev, hipMemcpyKind kind, i
   }
   const auto tp0 = std::chrono::steady_clock::now();
   if (e == hipSuccess) e = hipMemcpyAsync(k->B().d_raw, depth_dev, (size_t)w * h * 2, kind, k->pstream);
+  if (e == hipSuccess) e = stage_color(k, set, k->pstream);
   if (e == hipSuccess) {
     enqueue_preprocess(k, k->pstream);
     e = hipEventRecord(k->ev_pre[set], k->pstream);
@@ -1551,6 +1601,191 @@ extern "C" int hsk_extract_mesh_cubes(hsk_ctx* k, float* tri_xyz, size_t cap_tri
       k, 3, 36, tri_xyz, cap_triangles, n_triangles,
       [&]() { launch_extract_mesh_mc(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); },
       [&](float* d, size_t nw) { launch_extract_mesh_mc(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, 1, k->d_flags); });
+}
+
+// ------------------------------------------------------------------------------------------------------
+// colour (RGB-D scans; opt-in: include/hskinfu.h "Colour", DESIGN.md "Colour")
+// ------------------------------------------------------------------------------------------------------
+// (library-internal, not in the C ABI: hsk_group_create* marks the contexts it makes as slabs, whatever planes they own)
+void hsk_mark_group_slab(hsk_ctx* k) {
+  if (k) k->group_slab = true;
+}
+
+// the captured frame chains hold the launches they were captured with: dropped, so that the next frame captures them again
+static void drop_graphs(hsk_ctx* k) {
+  if (k->gexec) (void)hipGraphExecDestroy(k->gexec);
+  if (k->graph) (void)hipGraphDestroy(k->graph);
+  k->gexec = nullptr;
+  k->graph = nullptr;
+  k->graph_ready = false;
+  for (int i = 0; i < 2; ++i) {
+    if (k->pgexec[i]) (void)hipGraphExecDestroy(k->pgexec[i]);
+    if (k->pgraph[i]) (void)hipGraphDestroy(k->pgraph[i]);
+    k->pgexec[i] = nullptr;
+    k->pgraph[i] = nullptr;
+  }
+}
+
+extern "C" int hsk_enable_color(hsk_ctx* k, int max_weight, float band_m) {
+  if (!k) return HSK_ERR_ARG;
+  if (max_weight < 0 || max_weight > 255) return fail(k, HSK_ERR_ARG, "hsk_enable_color: max_weight must lie in 0..255 (0: 64)");
+  if (!(band_m == band_m)) return fail(k, HSK_ERR_ARG, "hsk_enable_color: band_m is NaN");
+  if (k->group_slab)
+    return fail(k, HSK_ERR_STATE, "hsk_enable_color: colour is not available for the slabs of a group");
+  if (k->ring_count > 0) return fail(k, HSK_ERR_STATE, "frames are in flight: collect them with hsk_wait_frame first");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  float m = k->vp.cell[0] > k->vp.cell[1] ? k->vp.cell[0] : k->vp.cell[1];
+  m = m > k->vp.cell[2] ? m : k->vp.cell[2];
+  float band = band_m > 0.0f ? band_m : 2.0f * m;
+  if (band > k->vp.tau) band = k->vp.tau;  // every voxel coloured is one the frame's integrate updates
+  if (!k->d_color) {
+    const size_t P0 = (size_t)k->cfg.width * k->cfg.height;
+    const size_t bytes = (size_t)k->vp.X * k->vp.Y * (size_t)k->vp.nzs * 4;
+    hipError_t e = hipMalloc((void**)&k->d_color, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&k->d_has_color, 2 * sizeof(int));
+    for (auto& b : k->ib)
+      if (e == hipSuccess) e = hipMalloc((void**)&b.d_rgb, P0 * 3);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&k->h_rgb_stage, P0 * 3, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMemsetAsync(k->d_color, 0, bytes, k->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k->d_has_color, 0, 2 * sizeof(int), k->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(k->stream);
+    if (e != hipSuccess) {  // (nothing half made is left behind: colour stays off)
+      auto F = [](void* p) {
+        if (p) (void)hipFree(p);
+      };
+      F(k->d_color);
+      F(k->d_has_color);
+      for (auto& b : k->ib) {
+        F(b.d_rgb);
+        b.d_rgb = nullptr;
+      }
+      if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
+      k->d_color = nullptr;
+      k->d_has_color = nullptr;
+      k->h_rgb_stage = nullptr;
+      HIPCHK(k, e);
+    }
+    k->color_bytes = bytes;
+  }
+  k->color_max_w = max_weight == 0 ? 64 : max_weight;
+  k->color_band = band;
+  drop_graphs(k);
+  return HSK_OK;
+}
+
+static int check_rgb(hsk_ctx* k, const uint8_t* rgb) {
+  if (!k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  if (!rgb) return fail(k, HSK_ERR_ARG, "rgb pointer is null");
+  memcpy(k->h_rgb_stage, rgb, (size_t)k->cfg.width * k->cfg.height * 3);  // (the caller's buffer may be gone when this returns)
+  k->rgb_src = k->h_rgb_stage;
+  return HSK_OK;
+}
+
+extern "C" int hsk_process_frame_rgbd(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h, float pose_out[16], int* tracked) {
+  int r = check_dims(k, depth, w, h);
+  if (r != HSK_OK) return r;
+  if (k->ring_count > 0) return fail(k, HSK_ERR_STATE, "frames are in flight: collect them with hsk_wait_frame first");
+  r = check_rgb(k, rgb);
+  if (r != HSK_OK) return r;
+  r = hsk_process_frame(k, depth, w, h, pose_out, tracked);
+  k->rgb_src = nullptr;
+  return r;
+}
+
+extern "C" int hsk_submit_frame_rgbd(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h) {
+  int r = check_dims(k, depth, w, h);
+  if (r != HSK_OK) return r;
+  if (k->ring_count >= HSK_MAX_IN_FLIGHT) return fail(k, HSK_ERR_STATE, "too many frames in flight: call hsk_wait_frame first");
+  const auto t0 = std::chrono::steady_clock::now();
+  r = check_rgb(k, rgb);
+  if (r != HSK_OK) return r;
+  k->submit_us[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  r = hsk_submit_frame(k, depth, w, h);
+  k->rgb_src = nullptr;
+  return r;
+}
+
+extern "C" int hsk_integrate_color(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h, const float pose[16]) {
+  int r = check_dims(k, depth, w, h);
+  if (r != HSK_OK) return r;
+  if (!pose) return fail(k, HSK_ERR_ARG, "pose is null");
+  if (k->ring_count > 0) return fail(k, HSK_ERR_STATE, "frames are in flight: collect them with hsk_wait_frame first");
+  r = check_rgb(k, rgb);
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  leave_slab_bookkeeping(k);
+  r = set_pose_internal(k, pose);
+  if (r == HSK_OK) r = stage_depth_host(k, depth);
+  if (r != HSK_OK) {
+    k->rgb_src = nullptr;
+    return r;
+  }
+  launch_scale_depth(k->stream, k->B().d_raw, w, h, k->lv[0].in, k->B().d_scaled);
+  launch_tile_max(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  launch_tile_fine(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  const hipError_t e = stage_color(k, k->cur, k->stream);
+  k->rgb_src = nullptr;
+  HIPCHK(k, e);
+  enqueue_color(k);
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  return HSK_OK;
+}
+
+extern "C" int hsk_download_color(hsk_ctx* k, uint8_t* rgbw) {
+  if (!k || !rgbw) return HSK_ERR_ARG;
+  if (!k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  return copy_out(k, rgbw, k->d_color, k->color_bytes);
+}
+
+extern "C" int hsk_upload_color(hsk_ctx* k, const uint8_t* rgbw) {
+  if (!k || !rgbw) return HSK_ERR_ARG;
+  if (!k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  HIPCHK(k, hipMemcpyAsync(k->d_color, rgbw, k->color_bytes, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  return HSK_OK;
+}
+
+// the cloud of hsk_extract_cloud (the same count pass, shared with it: kind 1) with normals and colour from k_extract_attrs
+extern "C" int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, uint8_t* rgb, size_t cap_points, size_t* n_points,
+                                       size_t* n_uncolored) {
+  if (!k || !n_points) return HSK_ERR_ARG;
+  if (rgb && !k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  if (n_uncolored) *n_uncolored = 0;
+  auto count = [&]() { launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); };
+  size_t total = 0;
+  int r = extract_product(k, 1, 12, nullptr, 0, &total, count, [](float*, size_t) {});
+  *n_points = total;
+  if (r != HSK_OK || !xyz || cap_points == 0 || total == 0) return r;
+  const size_t nw = total < cap_points ? total : cap_points;
+  const size_t want = 16 + nw * 12 + nw * 3;  // the uncoloured counter, the normals, the colours
+  if (k->attr_bytes < want) {
+    if (k->d_attr) (void)hipFree(k->d_attr);
+    k->d_attr = nullptr;
+    k->attr_bytes = 0;
+    HIPCHK(k, hipMalloc(&k->d_attr, want + (want >> 2)));
+    k->attr_bytes = want + (want >> 2);
+  }
+  unsigned long long* d_uncol = (unsigned long long*)k->d_attr;
+  float* d_nrm = normals ? (float*)((char*)k->d_attr + 16) : nullptr;
+  unsigned char* d_rgb = rgb ? (unsigned char*)k->d_attr + 16 + nw * 12 : nullptr;
+  HIPCHK(k, hipMemsetAsync(d_uncol, 0, 8, k->stream));
+  r = extract_product(k, 1, 12, xyz, cap_points, &total, count, [&](float* d, size_t n) {
+    launch_extract_attrs(k->stream, k->d_vol, k->d_color, k->vp, k->d_rowcnt, k->d_rowoff, d, d_nrm, d_rgb, n, d_uncol, k->d_flags);
+  });
+  if (r == HSK_OK && normals) r = copy_out(k, normals, d_nrm, nw * 12);
+  if (r == HSK_OK && rgb) r = copy_out(k, rgb, d_rgb, nw * 3);
+  if (r == HSK_OK && rgb && n_uncolored) {
+    unsigned long long u = 0;
+    HIPCHK(k, hipMemcpyAsync(&u, d_uncol, 8, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    *n_uncolored = (size_t)u;
+  }
+  return r;
 }
 
 // ------------------------------------------------------------------------------------------------------

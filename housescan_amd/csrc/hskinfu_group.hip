@@ -30,6 +30,8 @@
 
 #include "../../include/hskinfu.h"
 
+void hsk_mark_group_slab(hsk_ctx* k);  // hskinfu_api.hip (library-internal)
+
 namespace {
 
 struct Rccl {
@@ -484,6 +486,7 @@ static int group_build(const hsk_config* c, int n_total, int first, int n_local,
       g->err = std::string("hsk_group_create: slab ") + std::to_string(s.index) + ": " + hsk_last_error(nullptr);
       return bail(r);
     }
+    hsk_mark_group_slab(s.k);  // (refuses hsk_enable_color: the group's frame loop feeds no colour)
     (void)hipSetDevice(sc.device_id);
     if (hsk_set_stream(s.k, g->devs[s.dev_slot].stream) != HSK_OK || hipMalloc((void**)&s.keys, P * 4) != hipSuccess ||
         hipMalloc((void**)&s.bits, P * 24) != hipSuccess || hipMalloc((void**)&s.sums, 27 * sizeof(double)) != hipSuccess) {

@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/hskinfu.h"
@@ -23,8 +25,43 @@ extern "C" int hsk_write_pcd_xyz(const char* path, const float* xyz, size_t n) {
   return (wrote == n && rc == 0) ? HSK_OK : HSK_ERR_STATE;
 }
 
-// voxel-grid centroid downsample (what produces cloud_downsampled.pcd); output ordered by leaf index
-extern "C" int hsk_voxel_downsample(const float* xyz, size_t n, float leaf, float* out, size_t cap, size_t* n_out) {
+// binary PCD v0.7 with x y z rgb normal_x normal_y normal_z curvature, 32 B per point: the coloured form of HouseScan's cloud
+// loader (Main.hs:1325-1345: XYZ first, then XYZ + RGB + normal).  rgb is PCL's packed colour, the bit pattern 0x00RRGGBB
+// stored in a float field; curvature 0.  (Unverified against pcd-loader's loadXyzRgbNormal itself: it is not available here.)
+extern "C" int hsk_write_pcd_xyzrgbnormal(const char* path, const float* xyz, const uint8_t* rgb, const float* normals, size_t n) {
+  if (!path || (n && (!xyz || !rgb))) return HSK_ERR_ARG;
+  FILE* f = fopen(path, "wb");
+  if (!f) return HSK_ERR_STATE;
+  fprintf(f,
+          "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb normal_x normal_y normal_z curvature\n"
+          "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\n"
+          "WIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n",
+          n, n);
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  std::vector<uint32_t> rec(8 * 4096);
+  size_t wrote = 0;
+  for (size_t i0 = 0; i0 < n; i0 += 4096) {
+    const size_t m = n - i0 < 4096 ? n - i0 : 4096;
+    for (size_t j = 0; j < m; ++j) {
+      const size_t i = i0 + j;
+      uint32_t* r = &rec[8 * j];
+      float nrm[3] = {nan, nan, nan};
+      if (normals) memcpy(nrm, normals + 3 * i, 12);
+      memcpy(r, xyz + 3 * i, 12);
+      r[3] = ((uint32_t)rgb[3 * i] << 16) | ((uint32_t)rgb[3 * i + 1] << 8) | (uint32_t)rgb[3 * i + 2];
+      memcpy(r + 4, nrm, 12);
+      r[7] = 0u;  // curvature 0.0f
+    }
+    wrote += fwrite(rec.data(), 32, m, f);
+  }
+  const int rc = fclose(f);
+  return (wrote == n && rc == 0) ? HSK_OK : HSK_ERR_STATE;
+}
+
+// voxel-grid centroid downsample with attributes: leaves keyed by floor(p / leaf), ordered by key (then by point), the
+// centroid in binary64; the mean colour, rounded half up, and the renormalised mean of the leaf's non-NaN normals
+extern "C" int hsk_voxel_downsample_attrs(const float* xyz, const uint8_t* rgb, const float* normals, size_t n, float leaf, float* out_xyz,
+                                          uint8_t* out_rgb, float* out_normals, size_t cap, size_t* n_out) {
   if (!n_out || (!xyz && n) || !(leaf > 0.0f)) return HSK_ERR_ARG;
   struct Item {
     uint64_t key;
@@ -43,27 +80,66 @@ extern "C" int hsk_voxel_downsample(const float* xyz, size_t n, float leaf, floa
     items.push_back(Item{((uint64_t)iz << 42) | ((uint64_t)iy << 21) | (uint64_t)ix, (uint32_t)i});
   }
   std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.key != b.key ? a.key < b.key : a.idx < b.idx; });
+  const float nan = std::numeric_limits<float>::quiet_NaN();
   size_t m = 0;
   for (size_t i = 0; i < items.size();) {
     size_t j = i;
-    double sx = 0, sy = 0, sz = 0;
+    double sx = 0, sy = 0, sz = 0, nx = 0, ny = 0, nz = 0;
+    uint64_t cr = 0, cg = 0, cb = 0;
+    size_t nn = 0;
     while (j < items.size() && items[j].key == items[i].key) {
-      sx += xyz[3 * (size_t)items[j].idx];
-      sy += xyz[3 * (size_t)items[j].idx + 1];
-      sz += xyz[3 * (size_t)items[j].idx + 2];
+      const size_t q = items[j].idx;
+      sx += xyz[3 * q];
+      sy += xyz[3 * q + 1];
+      sz += xyz[3 * q + 2];
+      if (rgb) {
+        cr += rgb[3 * q];
+        cg += rgb[3 * q + 1];
+        cb += rgb[3 * q + 2];
+      }
+      if (normals) {
+        const float a = normals[3 * q], b = normals[3 * q + 1], c = normals[3 * q + 2];
+        if (a == a && b == b && c == c) {
+          nx += a;
+          ny += b;
+          nz += c;
+          ++nn;
+        }
+      }
       ++j;
     }
     const double c = (double)(j - i);
-    if (out && m < cap) {
-      out[3 * m] = (float)(sx / c);
-      out[3 * m + 1] = (float)(sy / c);
-      out[3 * m + 2] = (float)(sz / c);
+    if (m < cap) {
+      if (out_xyz) {
+        out_xyz[3 * m] = (float)(sx / c);
+        out_xyz[3 * m + 1] = (float)(sy / c);
+        out_xyz[3 * m + 2] = (float)(sz / c);
+      }
+      if (rgb && out_rgb) {
+        const uint64_t cnt = (uint64_t)(j - i);
+        out_rgb[3 * m] = (uint8_t)((cr + cnt / 2) / cnt);
+        out_rgb[3 * m + 1] = (uint8_t)((cg + cnt / 2) / cnt);
+        out_rgb[3 * m + 2] = (uint8_t)((cb + cnt / 2) / cnt);
+      }
+      if (normals && out_normals) {
+        const double len = std::sqrt(nx * nx + ny * ny + nz * nz);
+        const bool ok = nn > 0 && len > 0.0;
+        out_normals[3 * m] = ok ? (float)(nx / len) : nan;
+        out_normals[3 * m + 1] = ok ? (float)(ny / len) : nan;
+        out_normals[3 * m + 2] = ok ? (float)(nz / len) : nan;
+      }
     }
     ++m;
     i = j;
   }
   *n_out = m;
   return HSK_OK;
+}
+
+// voxel-grid centroid downsample (what produces cloud_downsampled.pcd); output ordered by leaf index.  The attribute form's
+// leaves with no attributes: one implementation, so that both give the same xyz by construction
+extern "C" int hsk_voxel_downsample(const float* xyz, size_t n, float leaf, float* out, size_t cap, size_t* n_out) {
+  return hsk_voxel_downsample_attrs(xyz, nullptr, nullptr, n, leaf, out, nullptr, nullptr, cap, n_out);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -530,3 +530,50 @@ extern "C" int hsk_synth_render_sensor(int scene, const float pose[16], int w, i
   delete[] bad;
   return HSK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Synthetic colour for the RGB-D path: a smooth colour of the world position (one sine per channel along its own axis, a
+// period of 1.2 m: at 256^3 the offset between a voxel and the surface point it is coloured from costs a few levels), and
+// camera images of it -- each pixel the colour of the nearest hit of trace_room_n / trace_open_n, which decide the nearest
+// hit exactly as the clean depth renders do, so a pixel is (0, 0, 0) exactly where their depth is 0.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+inline void color_of(const double p[3], uint8_t rgb[3]) {
+  for (int i = 0; i < 3; ++i) rgb[i] = (uint8_t)std::nearbyint(128.0 + 100.0 * std::sin(2.0 * kPi * p[i] / 1.2));
+}
+}  // namespace
+
+extern "C" int hsk_synth_color_at(int scene, const float p[3], uint8_t rgb[3]) {
+  if (!p || !rgb || scene > 3) return HSK_ERR_ARG;
+  const double q[3] = {(double)p[0], (double)p[1], (double)p[2]};
+  color_of(q, rgb);
+  return HSK_OK;
+}
+
+extern "C" int hsk_synth_render_rgb(int scene, const float pose[16], int w, int h, float fx, float fy, float cx, float cy, uint8_t* rgb) {
+  if (!pose || !rgb || w <= 0 || h <= 0 || scene > 3) return HSK_ERR_ARG;
+  double R[9], o[3];
+  for (int i = 0; i < 3; ++i) {
+    R[i * 3] = pose[i * 4];
+    R[i * 3 + 1] = pose[i * 4 + 1];
+    R[i * 3 + 2] = pose[i * 4 + 2];
+    o[i] = pose[i * 4 + 3];
+  }
+  RoomScene room;
+  if (scene >= 0) room = make_room(scene);
+  for (int v = 0; v < h; ++v)
+    for (int u = 0; u < w; ++u) {
+      const double dc[3] = {((double)u - (double)cx) / (double)fx, ((double)v - (double)cy) / (double)fy, 1.0};
+      const double d[3] = {R[0] * dc[0] + R[1] * dc[1] + R[2] * dc[2], R[3] * dc[0] + R[4] * dc[1] + R[5] * dc[2],
+                           R[6] * dc[0] + R[7] * dc[1] + R[8] * dc[2]};
+      const Hit hit = scene >= 0 ? trace_room_n(room, o, d) : trace_open_n(o, d);
+      uint8_t* px = rgb + ((size_t)v * w + u) * 3;
+      px[0] = px[1] = px[2] = 0;
+      if (!(hit.s < 10.0)) continue;
+      const double r = std::nearbyint(hit.s * 1000.0);  // (the depth renders' millimetres: no colour where they have no depth)
+      if (!(r >= 1.0 && r <= 65535.0)) continue;
+      const double p[3] = {o[0] + hit.s * d[0], o[1] + hit.s * d[1], o[2] + hit.s * d[2]};
+      color_of(p, px);
+    }
+  return HSK_OK;
+}

@@ -259,6 +259,62 @@ class KinfuTracker:
             self._ck(fn(self.h, out.ctypes.data, m, C.byref(n)))
         return out, total
 
+    # ---- colour (RGB-D; opt-in) ---------------------------------------------------------------------
+    def _rgb(self, rgb):
+        c = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if c.shape != (self.hgt, self.w, 3):
+            raise KinfuError(f"rgb must be a ({self.hgt}, {self.w}, 3) uint8 array registered to the depth grid")
+        return c
+
+    def enable_color(self, max_weight=0, band_m=0.0):
+        """allocate and zero the colour volume (4 B per stored voxel); max_weight 1..255 (0: 64), band_m <= 0: 2 cells"""
+        self._ck(self.lib.hsk_enable_color(self.h, int(max_weight), C.c_float(band_m)))
+
+    def process_frame_rgbd(self, depth, rgb):
+        d, c = self._depth(depth), self._rgb(rgb)
+        pose = np.empty(16, np.float32)
+        tracked = C.c_int()
+        self._ck(self.lib.hsk_process_frame_rgbd(self.h, d.ctypes.data, c.ctypes.data, d.shape[1], d.shape[0], _fp(pose), C.byref(tracked)))
+        return pose.reshape(4, 4), bool(tracked.value)
+
+    def submit_frame_rgbd(self, depth, rgb):
+        """submit_frame with the frame's colour image (both copied before this returns); collect with wait_frame()"""
+        d, c = self._depth(depth), self._rgb(rgb)
+        self._ck(self.lib.hsk_submit_frame_rgbd(self.h, d.ctypes.data, c.ctypes.data, d.shape[1], d.shape[0]))
+
+    def integrate_color(self, depth, rgb, pose):
+        """stage level: the colour update of one frame at `pose` (the TSDF is untouched)"""
+        d, c = self._depth(depth), self._rgb(rgb)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16)
+        self._ck(self.lib.hsk_integrate_color(self.h, d.ctypes.data, c.ctypes.data, d.shape[1], d.shape[0], _fp(p)))
+
+    def download_color(self):
+        """the colour volume as a row-major [nz, Y, X, 4] uint8 array of (r, g, b, w)"""
+        out = np.empty((self.stored_nz, self.cfg.vol_y, self.cfg.vol_x, 4), np.uint8)
+        self._ck(self.lib.hsk_download_color(self.h, out.ctypes.data))
+        return out
+
+    def upload_color(self, rgbw):
+        a = np.ascontiguousarray(rgbw, np.uint8)
+        if a.size != self.stored_nz * self.cfg.vol_y * self.cfg.vol_x * 4:
+            raise ValueError(f"upload_color: {self.stored_nz * self.cfg.vol_y * self.cfg.vol_x * 4} uint8 elements are needed, got {a.size}")
+        self._ck(self.lib.hsk_upload_color(self.h, a.ctypes.data))
+
+    def extract_cloud_attrs(self, cap=None, normals=True, rgb=True):
+        """extract_cloud with normals [n, 3] float32 (NaN near the volume's rim) and colours [n, 3] uint8 ->
+        (xyz, normals or None, rgb or None, total, n_uncolored)"""
+        n, nu = C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_extract_cloud_attrs(self.h, None, None, None, 0, C.byref(n), None))
+        total = n.value
+        m = total if cap is None else min(cap, total)
+        xyz = np.empty((m, 3), np.float32)
+        nrm = np.empty((m, 3), np.float32) if normals else None
+        col = np.empty((m, 3), np.uint8) if rgb else None
+        if m:
+            self._ck(self.lib.hsk_extract_cloud_attrs(self.h, xyz.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                                      None if col is None else col.ctypes.data, m, C.byref(n), C.byref(nu)))
+        return xyz, nrm, col, total, nu.value
+
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
         return self.lib.hsk_stream(self.h)
@@ -475,6 +531,27 @@ def synth_room_depth(variant, pose, w=640, h=480, fx=525.0, fy=525.0, cx=319.5, 
     if rc != 0:
         raise KinfuError(f"hsk_synth_room_render failed ({rc})")
     return d
+
+
+def synth_rgb(pose, scene=-1, w=640, h=480, fx=525.0, fy=525.0, cx=319.5, cy=239.5):
+    """the colour image registered to synth_depth (scene -1) / synth_room_depth (scene 0..3): (h, w, 3) uint8, (0, 0, 0) exactly
+    where the clean depth render has no depth"""
+    p = np.ascontiguousarray(pose, np.float32).reshape(16)
+    out = np.empty((h, w, 3), np.uint8)
+    rc = _lib.load().hsk_synth_render_rgb(int(scene), _fp(p), w, h, fx, fy, cx, cy, out.ctypes.data)
+    if rc != 0:
+        raise KinfuError(f"hsk_synth_render_rgb failed ({rc})")
+    return out
+
+
+def synth_color_at(p, scene=-1):
+    """the synthetic colour (uint8 r, g, b) of world point p"""
+    q = np.ascontiguousarray(p, np.float32).reshape(3)
+    out = np.empty(3, np.uint8)
+    rc = _lib.load().hsk_synth_color_at(int(scene), _fp(q), out.ctypes.data)
+    if rc != 0:
+        raise KinfuError(f"hsk_synth_color_at failed ({rc})")
+    return out
 
 
 def bilateral_tables():

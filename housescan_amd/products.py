@@ -35,6 +35,44 @@ def write_pcd(path, xyz):
     _ck(lib.hsk_write_pcd_xyz(os.fsencode(path), pts.ctypes.data, len(pts)), "hsk_write_pcd_xyz")
 
 
+def write_pcd_xyzrgbnormal(path, xyz, rgb, normals=None):
+    """binary PCD with x y z rgb normal_x normal_y normal_z curvature (32 B per point; rgb packed as 0x00RRGGBB; NaN normals
+    kept; normals None: NaN)"""
+    lib = _lib.load()
+    pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    if len(col) != len(pts):
+        raise ValueError("write_pcd_xyzrgbnormal: rgb must have one row per point")
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(nrm) != len(pts):
+            raise ValueError("write_pcd_xyzrgbnormal: normals must have one row per point")
+    _ck(lib.hsk_write_pcd_xyzrgbnormal(os.fsencode(path), pts.ctypes.data, col.ctypes.data, None if nrm is None else nrm.ctypes.data, len(pts)),
+        "hsk_write_pcd_xyzrgbnormal")
+
+
+def voxel_downsample_attrs(xyz, leaf, rgb=None, normals=None):
+    """voxel_downsample (the same xyz, bit for bit, in the same order) with the rounded mean colour and the renormalised mean
+    of the non-NaN normals per leaf -> (xyz, rgb or None, normals or None)"""
+    lib = _lib.load()
+    pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    col = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    for a in (col, nrm):
+        if a is not None and len(a) != len(pts):
+            raise ValueError("voxel_downsample_attrs: attributes must have one row per point")
+    out = np.empty_like(pts)
+    out_rgb = None if col is None else np.empty((len(pts), 3), np.uint8)
+    out_nrm = None if nrm is None else np.empty((len(pts), 3), np.float32)
+    n = C.c_size_t()
+    _ck(lib.hsk_voxel_downsample_attrs(pts.ctypes.data, None if col is None else col.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                       len(pts), C.c_float(leaf), out.ctypes.data, None if out_rgb is None else out_rgb.ctypes.data,
+                                       None if out_nrm is None else out_nrm.ctypes.data, len(pts), C.byref(n)), "hsk_voxel_downsample_attrs")
+    m = n.value
+    return out[:m].copy(), None if out_rgb is None else out_rgb[:m].copy(), None if out_nrm is None else out_nrm[:m].copy()
+
+
 def write_ply_mesh(path, triangles):
     """triangle soup [n, 3, 3] -> welded binary .ply mesh; returns (vertices, faces) written"""
     lib = _lib.load()
@@ -80,13 +118,27 @@ def plane_hull(xyz, labels, plane, abcd):
     return hull[:n.value].copy()
 
 
-def write_room_dir(room_dir, cloud_xyz, leaf=0.03, **plane_args):
-    """cloud (full resolution, KinFu frame) -> the files HouseScan's loadRoom expects. Returns (planes, n_downsampled)."""
+def write_room_dir(room_dir, cloud_xyz, leaf=0.03, *, cloud_rgb=None, cloud_normals=None, colored_downsampled=False, **plane_args):
+    """cloud (full resolution, KinFu frame) -> the files HouseScan's loadRoom expects. Returns (planes, n_downsampled).
+    With cloud_rgb (and cloud_normals; KinfuTracker.extract_cloud_attrs) cloud_bin.pcd is written as XYZRGBNormal, the coloured
+    form of HouseScan's cloud loader (Main.hs:1325-1345) -- NaN normals when cloud_normals is None; cloud_downsampled.pcd stays
+    XYZ -- the form loadRoom tries first -- unless colored_downsampled.  Plane detection always runs on the same downsampled xyz.
+    Normals without colour, or colored_downsampled without colour, are refused (ValueError): there is no XYZ + normal form."""
+    if cloud_rgb is None and (cloud_normals is not None or colored_downsampled):
+        raise ValueError("write_room_dir: cloud_normals and colored_downsampled need cloud_rgb (the coloured file carries both)")
     lib = _lib.load()
     os.makedirs(room_dir, exist_ok=True)
-    write_pcd(os.path.join(room_dir, "cloud_bin.pcd"), cloud_xyz)
+    colored = cloud_rgb is not None
+    if colored:
+        write_pcd_xyzrgbnormal(os.path.join(room_dir, "cloud_bin.pcd"), cloud_xyz, cloud_rgb, cloud_normals)
+    else:
+        write_pcd(os.path.join(room_dir, "cloud_bin.pcd"), cloud_xyz)
     down = voxel_downsample(cloud_xyz, leaf)
-    write_pcd(os.path.join(room_dir, "cloud_downsampled.pcd"), down)
+    if colored and colored_downsampled:
+        d_xyz, d_rgb, d_nrm = voxel_downsample_attrs(cloud_xyz, leaf, cloud_rgb, cloud_normals)
+        write_pcd_xyzrgbnormal(os.path.join(room_dir, "cloud_downsampled.pcd"), d_xyz, d_rgb, d_nrm)
+    else:
+        write_pcd(os.path.join(room_dir, "cloud_downsampled.pcd"), down)
     planes, labels = detect_planes(down, **plane_args)
     _ck(lib.hsk_write_planes_txt(os.fsencode(os.path.join(room_dir, "planes.txt")), planes.ctypes.data, len(planes)),
         "hsk_write_planes_txt")

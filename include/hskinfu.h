@@ -146,6 +146,35 @@ int hsk_extract_mesh(hsk_ctx* k, float* tri_xyz, size_t cap_triangles, size_t* n
  * classic table's counts (820 triangles, at most 5 per cube); same validity rule, vertices and order as hsk_extract_mesh */
 int hsk_extract_mesh_cubes(hsk_ctx* k, float* tri_xyz, size_t cap_triangles, size_t* n_triangles);
 
+/* ---- Colour (RGB-D scans; opt-in).  A context that never calls hsk_enable_color runs exactly as without this section.
+ * The colour volume holds one uint8 (r, g, b, w) quadruple per stored voxel -- 4 B per voxel, 512 MiB at 512^3, allocated
+ * and zeroed by hsk_enable_color, nothing before.  Host arrays are row-major like hsk_download_tsdf's:
+ * rgbw[stored_plane][y][x][4].  A frame's colour image is RGB8, 3 bytes per pixel, registered to the depth grid, row-major
+ * (i = y*w + x) with the depth frame's w x h.  Each frame that integrates its TSDF also colours: voxel (x, y, z), projected
+ * with the integrate's own arithmetic onto pixel (u, v) with scaled depth D_s != 0 and -band < D_s - dist < band, takes
+ *     c' = (c w + p + ((w + 1) >> 1)) / (w + 1)  per channel (integers, truncating),  w' = min(w + 1, max_weight).
+ * Lost frames and frames dropped in flight behind one colour nothing; hsk_reset and the reset after a tracking loss zero the
+ * colour volume with the TSDF; frames submitted through the depth-only calls (hsk_process_frame, hsk_submit_frame,
+ * hsk_track_stream, ...) leave colour untouched.  Not for the slabs of a group, nor for the *_dev frame calls. */
+/* max_weight 1..255 (0: 64); band_m <= 0: 2 x the largest cell; the band is clamped to the truncation distance.  No frame may
+ * be in flight.  A second call keeps the volume and changes the parameters.  HSK_ERR_STATE on a slab of a group. */
+int hsk_enable_color(hsk_ctx* k, int max_weight, float band_m);
+/* hsk_process_frame / hsk_submit_frame with the frame's colour image; both images are copied before the call returns.
+ * HSK_ERR_STATE without hsk_enable_color. */
+int hsk_process_frame_rgbd(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h, float pose_out[16], int* tracked);
+int hsk_submit_frame_rgbd(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h);
+/* stage level: the colour update of one frame at `pose` (the TSDF is untouched) */
+int hsk_integrate_color(hsk_ctx* k, const uint16_t* depth, const uint8_t* rgb, int w, int h, const float pose[16]);
+int hsk_download_color(hsk_ctx* k, uint8_t* rgbw /* 4 * X*Y*stored_planes */);
+int hsk_upload_color(hsk_ctx* k, const uint8_t* rgbw);
+/* hsk_extract_cloud with attributes: xyz, the count and the order are bit-identical to hsk_extract_cloud's (same two-call
+ * protocol).  normals (3 floats per point): the raycast's normal at the point (central differences of the trilinear TSDF),
+ * NaN x 3 where floor(p / cell) is not within (1, dims - 2) on every axis.  rgb (3 bytes per point): the colour of the
+ * crossing's voxel with the smaller |tsdf|, or of the other one when that has colour weight 0; (0, 0, 0) when both have,
+ * counted in *n_uncolored.  normals, rgb and n_uncolored may be NULL; rgb != NULL needs hsk_enable_color (HSK_ERR_STATE). */
+int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, uint8_t* rgb, size_t cap_points, size_t* n_points,
+                            size_t* n_uncolored);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
@@ -255,7 +284,7 @@ int hsk_stage_ms(hsk_ctx* k, double sum_ms[HSK_NSTAGES], uint64_t* n_frames, int
 int hsk_icp_level_ms(hsk_ctx* k, double sum_ms[HSK_LEVELS]);
 /* lane-blocks (4 x 1 x 4 voxels) the last integrate's classification pass could not settle and handed to its per-voxel
  * pass (a measure of the classification's slack: bench.py reports it beside V_upd); synchronises the context's stream */
-/* host microseconds the pipelined submissions (hsk_submit_frame[_dev]) have spent so far, by phase: [0] the copy of a host frame
+/* host microseconds the pipelined submissions (hsk_submit_frame[_dev|_rgbd]) have spent so far, by phase: [0] the copy of a host frame
    into the pinned staging ring, [1] enqueueing the upload and the preprocessing on the second stream, [2] waiting for that
    preprocessing, [3] enqueueing the frame's main-stream chain; n_submissions: how many.  reset != 0: counted afresh from now. */
 int hsk_submit_host_us(hsk_ctx* k, double sum_us[4], uint64_t* n_submissions, int reset);
@@ -289,6 +318,12 @@ int hsk_synth_room_render(int variant, const float pose[16], int w, int h, float
    hsk_synth_render; 0..3: closed room `scene`.  hole_fraction (may be NULL): the share of pixels without depth. */
 int hsk_synth_render_sensor(int scene, const float pose[16], int w, int h, float fx, float fy, float cx, float cy, uint64_t seed,
                             float sigma_mm, float range_cut_m, int absorbing, uint16_t* depth, double* hole_fraction);
+/* Synthetic colour for RGB-D tests: hsk_synth_color_at is a smooth colour of the world position (per channel
+ * 128 + 100 sin(2 pi p_i / 1.2 m), rounded: 28..228), the same for every scene.  hsk_synth_render_rgb gives every pixel the
+ * colour of the nearest hit the depth renders use, and (0, 0, 0) exactly where the clean depth render (hsk_synth_render,
+ * hsk_synth_room_render) is 0.  scene < 0: the open scene; 0..3: closed room `scene`.  rgb: 3 * w * h bytes. */
+int hsk_synth_color_at(int scene, const float p[3], uint8_t rgb[3]);
+int hsk_synth_render_rgb(int scene, const float pose[16], int w, int h, float fx, float fy, float cx, float cy, uint8_t* rgb);
 
 /* Products on the file seam (Main.hs:1740, :1320-1345): binary PCD with float32 x y z */
 int hsk_write_pcd_xyz(const char* path, const float* xyz, size_t n_points);
@@ -298,6 +333,16 @@ int hsk_write_ply_mesh(const char* path, const float* tri_xyz, size_t n_triangle
 /* the same welding without a file: indices[3 * n_triangles] into vertices (cap_vertices x 3); degenerate triangles keep index triples with repeats */
 int hsk_weld_triangles(const float* tri_xyz, size_t n_triangles, float* vertices, size_t cap_vertices, size_t* n_vertices, int32_t* indices);
 int hsk_voxel_downsample(const float* xyz, size_t n, float leaf_m, float* out, size_t cap, size_t* n_out);
+/* the same leaves, xyz bit-identical to hsk_voxel_downsample's and in the same order, with the rounded mean colour and the
+ * renormalised mean of the non-NaN normals of each leaf (NaN x 3 when it has none).  rgb / normals (inputs) may be NULL,
+ * and the matching output is then not written. */
+int hsk_voxel_downsample_attrs(const float* xyz, const uint8_t* rgb, const float* normals, size_t n, float leaf_m, float* out_xyz,
+                               uint8_t* out_rgb, float* out_normals, size_t cap, size_t* n_out);
+/* binary PCD v0.7, FIELDS x y z rgb normal_x normal_y normal_z curvature (SIZE 4, TYPE F, COUNT 1 each; 32 B per point):
+ * rgb holds the bit pattern 0x00RRGGBB, curvature is 0, NaN normals are kept (normals may be NULL: NaN).  The form
+ * HouseScan's loader falls back to for a coloured cloud (Main.hs:1325-1345); that pcd-loader's loadXyzRgbNormal accepts
+ * exactly this layout is unverified here. */
+int hsk_write_pcd_xyzrgbnormal(const char* path, const float* xyz, const uint8_t* rgb, const float* normals, size_t n);
 /* Plane products loadRoom reads beside the cloud (Main.hs:1392-1404): planes.txt lines "a b c d" in PCL form
  * ax+by+cz+d=0 (planeEqsFromFile, Main.hs:1379-1389) and cloud_plane_hull<k>.pcd polygons (Main.hs:1395-1400).
  * Deterministic RANSAC + PCA refit; labels[i] = plane index of point i or -1. */

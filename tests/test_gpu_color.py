@@ -1,0 +1,432 @@
+"""RGB-D colour and the cloud with normals and colour, on the GPU: the colour update bit-exact against a numpy restatement
+built on the integrate's projection (tests/np_twin.py), through every frame path; the read-out bit-exact against the
+downloaded volumes; and what a scanned room looks like."""
+import os
+
+import numpy as np
+import pytest
+
+from np_twin import _Grid, _vox, scale_depth, tau_of
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+FX, FY, CX, CY = 525.0, 525.0, 319.5, 239.5
+
+
+def band_of(n, band_m, size=3.0, trunc=0.03):
+    cell = f32(size) / f32(n)
+    b = f32(band_m) if band_m > 0 else f32(2.0) * cell
+    return min(b, tau_of((size,) * 3, (n, n, n), trunc))
+
+
+def np_color(col, scaled, rgb, pose, band, max_w, size=3.0):
+    """one frame's colour update of `col` ([nz, Y, X, 4] uint8, in place): the projection of np_twin._integrate, then
+    -band < sdf < band, c' = (c w + p + ((w + 1) >> 1)) // (w + 1), w' = min(w + 1, max_w)"""
+    nz, Y, X, _ = col.shape
+    H, W = scaled.shape
+    cell = [f32(size) / f32(X), f32(size) / f32(Y), f32(size) / f32(nz)]
+    R = pose[:3, :3].astype(f32)
+    t = pose[:3, 3].astype(f32)
+    Ri = R.T.copy()
+    x = np.arange(X, dtype=f32)[None, None, :]
+    y = np.arange(Y, dtype=f32)[None, :, None]
+    gx = (x + f32(0.5)) * cell[0] - t[0]
+    gy = (y + f32(0.5)) * cell[1] - t[1]
+    for z0 in range(0, nz, 32):
+        z = np.arange(z0, min(z0 + 32, nz)).astype(f32)[:, None, None]
+        gz = (z + f32(0.5)) * cell[2] - t[2]
+        cam = [(Ri[i, 0] * gx + Ri[i, 1] * gy) + Ri[i, 2] * gz for i in range(3)]
+        with np.errstate(all="ignore"):
+            front = cam[2] >= f32(1.17549435e-38)
+            inv_z = f32(1) / cam[2]
+            fu = (cam[0] * f32(FX)) * inv_z + f32(CX)
+            fv = (cam[1] * f32(FY)) * inv_z + f32(CY)
+            ok = front & (fu > f32(-1e6)) & (fu < f32(1e6)) & (fv > f32(-1e6)) & (fv < f32(1e6))
+            u = np.where(ok, np.rint(np.where(ok, fu, 0)), -1).astype(np.int64)
+            v = np.where(ok, np.rint(np.where(ok, fv, 0)), -1).astype(np.int64)
+        ok &= (u >= 0) & (v >= 0) & (u < W) & (v < H)
+        Ds = np.where(ok, scaled[np.clip(v, 0, H - 1), np.clip(u, 0, W - 1)], f32(0))
+        dist = np.sqrt(gz * gz + (gx * gx + gy * gy))
+        sdf = Ds - dist
+        upd = ok & (Ds != 0) & (sdf > -band) & (sdf < band)
+        iz, iy, ix = np.nonzero(upd)
+        if len(iz) == 0:
+            continue
+        p = rgb[v[iz, iy, ix], u[iz, iy, ix]].astype(np.int64)
+        blk = col[z0:z0 + 32]
+        c = blk[iz, iy, ix, :3].astype(np.int64)
+        w = blk[iz, iy, ix, 3].astype(np.int64)
+        w1 = w + 1
+        blk[iz, iy, ix, :3] = ((c * w[:, None] + p + (w1 >> 1)[:, None]) // w1[:, None]).astype(np.uint8)
+        blk[iz, iy, ix, 3] = np.minimum(w1, max_w).astype(np.uint8)
+
+
+def frame_of(hsk, src, k):
+    """(pose, depth, rgb) of frame k of the scripted stream ("synth") or of room 0's scan ("room")"""
+    if src == "synth":
+        pose = hsk.synth_pose(k)
+        return pose, hsk.synth_depth(pose), hsk.synth_rgb(pose)
+    pose = hsk.synth_room_pose(0, k, 720)
+    return pose, hsk.synth_room_depth(0, pose), hsk.synth_rgb(pose, 0)
+
+
+def random_color(rng, n, max_w):
+    col = rng.integers(0, 256, size=(n, n, n, 4), dtype=np.uint8)
+    col[..., 3] = rng.integers(0, max_w + 1, size=(n, n, n))
+    col[..., 3][rng.random((n, n, n)) < 0.1] = max_w  # some already capped
+    return col
+
+
+@pytest.mark.parametrize("n,src,band_m,max_w", [(64, "synth", 0.0, 64), (64, "room", 0.01, 1), (128, "synth", 0.02, 255),
+                                                (128, "room", 0.0, 1), (256, "synth", 0.0, 64)])
+def test_integrate_color_stage_bitexact(hsk, n, src, band_m, max_w):
+    rng = np.random.default_rng(n + max_w)
+    trk = hsk.KinfuTracker(n=n)
+    trk.enable_color(max_w, band_m)
+    col = random_color(rng, n, max_w)
+    trk.upload_color(col)
+    assert np.array_equal(trk.download_color(), col)
+    tsdf0 = trk.download_tsdf()
+    band = band_of(n, band_m)
+    for k in (3, 9):
+        pose, depth, rgb = frame_of(hsk, src, k)
+        trk.integrate_color(depth, rgb, pose)
+        scaled = trk.download_scaled_depth()
+        assert np.array_equal(scaled.view(np.uint32), scale_depth(depth, FX, FY, CX, CY).view(np.uint32))
+        np_color(col, scaled, rgb, pose, band, max_w)
+        got = trk.download_color()
+        bad = np.argwhere((got != col).any(axis=3))
+        assert len(bad) == 0, f"{len(bad)} voxels differ, first {bad[:5].tolist()}"
+    assert np.array_equal(trk.download_tsdf(), tsdf0), "integrate_color must leave the TSDF alone"
+    trk.close()
+
+
+def run_tracker(hsk, n, frames, color=True, use_graph=0, mode="sync", profile=False):
+    trk = hsk.KinfuTracker(n=n, use_graph=use_graph)
+    if color:
+        trk.enable_color()
+    if profile:
+        trk.set_profiling(1)
+    out = []
+    if mode == "sync":
+        for pose, depth, rgb in frames:
+            out.append(trk.process_frame_rgbd(depth, rgb) if color else trk.process_frame(depth))
+    else:
+        for i, (pose, depth, rgb) in enumerate(frames):
+            trk.submit_frame_rgbd(depth, rgb) if color else trk.submit_frame(depth)
+            if i >= 2:
+                out.append(trk.wait_frame())
+        while len(out) < len(frames):
+            out.append(trk.wait_frame())
+    return trk, out
+
+
+def replay(n, frames, results, max_w=64):
+    col = np.zeros((n, n, n, 4), np.uint8)
+    for k, ((_, depth, rgb), (pose, ok)) in enumerate(zip(frames, results)):
+        if ok or k == 0:  # frame 0 integrates at the initial pose; every tracked frame integrates (no gate)
+            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), max_w)
+    return col
+
+
+@pytest.mark.parametrize("n", [128, 256])
+def test_tracker_color_bitexact(hsk, n):
+    frames = [frame_of(hsk, "synth", k) for k in range(30)]
+    trk, res = run_tracker(hsk, n, frames)
+    ref, res0 = run_tracker(hsk, n, frames, color=False)
+    assert all(ok for _, ok in res[1:])
+    for (p, ok), (p0, ok0) in zip(res, res0):
+        assert ok == ok0 and np.array_equal(p.view(np.uint32), p0.view(np.uint32))
+    assert np.array_equal(trk.download_tsdf(), ref.download_tsdf()), "colour must not change the TSDF"
+    got = trk.download_color()
+    want = replay(n, frames, res)
+    bad = np.argwhere((got != want).any(axis=3))
+    assert len(bad) == 0, f"{len(bad)} voxels differ, first {bad[:5].tolist()}"
+    assert (got[..., 3] > 0).sum() > 10000
+    trk.close()
+    ref.close()
+
+
+def test_paths_agree(hsk):
+    n = 128
+    frames = [frame_of(hsk, "synth", k) for k in range(12)]
+    base, res = run_tracker(hsk, n, frames)
+    want = base.download_color()
+    assert np.array_equal(want, replay(n, frames, res))
+    tsdf = base.download_tsdf()
+    for use_graph, mode, prof in [(1, "sync", False), (2, "sync", False), (0, "async", False), (2, "async", False), (0, "sync", True)]:
+        trk, r = run_tracker(hsk, n, frames, use_graph=use_graph, mode=mode, profile=prof)
+        assert [ok for _, ok in r] == [ok for _, ok in res]
+        assert np.array_equal(trk.download_color(), want), (use_graph, mode, prof)
+        assert np.array_equal(trk.download_tsdf(), tsdf), (use_graph, mode, prof)
+        trk.close()
+    base.close()
+
+
+@pytest.mark.parametrize("use_graph", [0, 1, 2])
+def test_depth_only_frames_leave_color(hsk, use_graph):
+    n = 64
+    frames = [frame_of(hsk, "synth", k) for k in range(10)]
+    trk = hsk.KinfuTracker(n=n, use_graph=use_graph)
+    trk.enable_color()
+    results = []
+    for k, (pose, depth, rgb) in enumerate(frames):
+        if k % 3 == 2:
+            before = trk.download_color()
+            results.append((trk.process_frame(depth), False))
+            assert np.array_equal(trk.download_color(), before), f"depth-only frame {k} changed the colour"
+        else:
+            results.append((trk.process_frame_rgbd(depth, rgb), True))
+    # pipelined depth-only frames, then a coloured one
+    before = trk.download_color()
+    trk.submit_frame(frames[-1][1])
+    trk.submit_frame(frames[-1][1])
+    assert trk.wait_frame()[1] and trk.wait_frame()[1]
+    assert np.array_equal(trk.download_color(), before)
+    # the whole run against the rule applied to the coloured frames only
+    col = np.zeros((n, n, n, 4), np.uint8)
+    for k, (((_, depth, rgb)), ((pose, ok), colored)) in enumerate(zip(frames, results)):
+        if colored and (ok or k == 0):
+            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), 64)
+    assert np.array_equal(before, col)
+    trk.close()
+
+
+def test_loss_zeroes_color(hsk):
+    n = 64
+    trk = hsk.KinfuTracker(n=n)
+    trk.enable_color()
+    f = [frame_of(hsk, "synth", k) for k in range(4)]
+    trk.process_frame_rgbd(f[0][1], f[0][2])
+    trk.process_frame_rgbd(f[1][1], f[1][2])
+    assert trk.download_color().any()
+    blank = np.zeros_like(f[0][1])
+    _, tracked = trk.process_frame_rgbd(blank, f[2][2])
+    assert not tracked
+    assert not trk.download_tsdf().any() and not trk.download_color().any()
+    # pipelined: a lost frame, and one dropped in flight behind it.  Both have run on the device before the host collects them
+    # (and resets): the volumes, read in between, show that neither coloured nor integrated -- the kernels' own `lost` test
+    trk.submit_frame_rgbd(f[0][1], f[0][2])
+    trk.submit_frame_rgbd(f[1][1], f[1][2])
+    assert trk.wait_frame()[1] is False and trk.wait_frame()[1] is True
+    col1, tsdf1 = trk.download_color(), trk.download_tsdf()
+    assert col1.any()
+    trk.submit_frame_rgbd(blank, f[2][2])
+    trk.submit_frame_rgbd(f[2][1], f[2][2])
+    trk.synchronize()
+    assert np.array_equal(trk.download_color(), col1), "a lost frame, or one dropped behind it, coloured"
+    assert np.array_equal(trk.download_tsdf(), tsdf1)
+    p1, t1 = trk.wait_frame()
+    p2, t2 = trk.wait_frame()
+    assert not t1 and not t2
+    assert not trk.download_tsdf().any() and not trk.download_color().any()
+    # the restarted scan colours as a fresh one
+    r = [trk.process_frame_rgbd(d, c) for _, d, c in f[:3]]
+    assert np.array_equal(trk.download_color(), replay(n, f[:3], r))
+    # hsk_reset zeroes it as well
+    trk.reset()
+    assert not trk.download_color().any()
+    trk.close()
+
+
+def np_attrs(tsdf, col, xyz, size=3.0):
+    """per point of the cloud (voxel order: plane, row, x, axis): the normal of the raycast on the TSDF and the colour of the
+    selection rule -> (normals, rgb, n_uncolored)"""
+    nz, Y, X, _ = tsdf.shape
+    t = tsdf[..., 0].astype(np.int32)
+    valid = (tsdf[..., 1] != 0) & (t != 32767)
+    M = np.zeros((nz, Y, X, 3), bool)
+    for k, (sa, sb) in enumerate([((slice(None), slice(None), slice(0, -1)), (slice(None), slice(None), slice(1, None))),
+                                   ((slice(None), slice(0, -1), slice(None)), (slice(None), slice(1, None), slice(None))),
+                                   ((slice(0, -1), slice(None), slice(None)), (slice(1, None), slice(None), slice(None)))]):
+        a, b = t[sa], t[sb]
+        M[sa + (k,)] = valid[sa] & valid[sb] & (((a > 0) & (b < 0)) | ((a < 0) & (b > 0)))
+    z, y, x, k = np.nonzero(M)
+    assert len(z) == len(xyz)
+    bz, by, bx = z + (k == 2), y + (k == 1), x + (k == 0)
+    ta, tb = np.abs(t[z, y, x]), np.abs(t[bz, by, bx])
+    ca, cb = col[z, y, x], col[bz, by, bx]
+    take_a = ta <= tb
+    first = np.where(take_a[:, None], ca, cb)
+    other = np.where(take_a[:, None], cb, ca)
+    pick = np.where((first[:, 3] == 0)[:, None], other, first)
+    unc = pick[:, 3] == 0
+    rgb = np.where(unc[:, None], 0, pick[:, :3]).astype(np.uint8)
+    G = _Grid(tsdf, (size,) * 3, nz, 0)
+    p = [xyz[:, i].copy() for i in range(3)]
+    dims = (X, Y, nz)
+    deep = np.ones(len(xyz), bool)
+    for i in range(3):
+        q = _vox(p[i], G.cell[i])
+        deep &= (q > 1) & (q < dims[i] - 2)
+    nrm = np.full((len(xyz), 3), np.nan, np.float32)
+    n = []
+    for i in range(3):
+        hi = [c.copy() for c in p]
+        lo = [c.copy() for c in p]
+        hi[i] = (hi[i] + G.cell[i]).astype(f32)
+        lo[i] = (lo[i] - G.cell[i]).astype(f32)
+        n.append((G.trilinear(hi) - G.trilinear(lo)).astype(f32))
+    with np.errstate(all="ignore"):
+        ninv = f32(1) / np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
+    for i in range(3):
+        nrm[deep, i] = (n[i] * ninv)[deep]
+    return nrm, rgb, int(unc.sum())
+
+
+def test_extract_cloud_attrs_bitexact(hsk, tmp_path):
+    n = 128
+    frames = [frame_of(hsk, "synth", k) for k in range(15)]
+    trk, _ = run_tracker(hsk, n, frames)
+    xyz0, total0 = trk.extract_cloud()
+    xyz, nrm, rgb, total, unc = trk.extract_cloud_attrs()
+    assert total == total0 and total > 1000
+    assert np.array_equal(xyz.view(np.uint32), xyz0.view(np.uint32))
+    tsdf, col = trk.download_tsdf(), trk.download_color()
+    want_n, want_rgb, want_unc = np_attrs(tsdf, col, xyz)
+    assert np.array_equal(np.isnan(nrm), np.isnan(want_n))
+    assert np.array_equal(nrm[~np.isnan(nrm)].view(np.uint32), want_n[~np.isnan(want_n)].view(np.uint32))
+    assert (~np.isnan(nrm[:, 0])).sum() > 0.9 * total
+    assert np.array_equal(rgb, want_rgb) and unc == want_unc
+    # NULL attribute pointers; a capped read; normals without colour on a context without it
+    x2, n2, r2, _, _ = trk.extract_cloud_attrs(normals=False, rgb=False)
+    assert n2 is None and r2 is None and np.array_equal(x2.view(np.uint32), xyz.view(np.uint32))
+    x3, n3, r3, _, _ = trk.extract_cloud_attrs(cap=100)
+    assert np.array_equal(x3, xyz[:100]) and np.array_equal(r3, rgb[:100]) and np.array_equal(n3[~np.isnan(n3)], nrm[:100][~np.isnan(nrm[:100])])
+    plain, _ = run_tracker(hsk, n, frames, color=False)
+    with pytest.raises(hsk.KinfuError):
+        plain.extract_cloud_attrs()
+    xp, npl, _, _, _ = plain.extract_cloud_attrs(rgb=False)
+    assert np.array_equal(xp.view(np.uint32), xyz.view(np.uint32))
+    assert np.array_equal(np.isnan(npl), np.isnan(nrm)) and np.array_equal(npl[~np.isnan(npl)], nrm[~np.isnan(nrm)])
+    for call in (lambda: plain.process_frame_rgbd(frames[0][1], frames[0][2]), lambda: plain.submit_frame_rgbd(frames[0][1], frames[0][2]),
+                 lambda: plain.integrate_color(frames[0][1], frames[0][2], frames[0][0]), plain.download_color):
+        with pytest.raises(hsk.KinfuError):
+            call()
+    # the room directory: cloud_bin.pcd parses back to the extracted arrays
+    from housescan_amd import products
+    from test_color_host import read_pcd_xyzrgbnormal
+    d = str(tmp_path / "room")
+    products.write_room_dir(d, xyz, cloud_rgb=rgb, cloud_normals=nrm)
+    _, xb, bits, nb, _ = read_pcd_xyzrgbnormal(os.path.join(d, "cloud_bin.pcd"))
+    assert np.array_equal(xb.view(np.uint32), xyz.view(np.uint32))
+    assert np.array_equal(bits, (rgb[:, 0].astype(np.uint32) << 16) | (rgb[:, 1].astype(np.uint32) << 8) | rgb[:, 2])
+    assert np.array_equal(nb.view(np.uint32), nrm.view(np.uint32))
+    trk.close()
+    plain.close()
+
+
+def test_room_scan_physical(hsk):
+    """room 0 as a sensor sees it (holes, noise), synthetic colour, 256^3: the colours of the cloud against the colour of the
+    scene at the point, the normals against the walls'.  Wall points near another wall (within 3 cells: corners and edges,
+    where the TSDF's gradient mixes two planes) are left out.  Measured on the first run (150 frames): every coloured point
+    within 16 levels (median 2); of the points within 5 mm of a wall, 90.6 / 96.7 / 97.4 / 97.5 % have their normal within
+    10 deg (median 1.7 .. 2.3 deg).  The rest is geometry, not noise: the same scan without sensor noise leaves 8.7 % of wall
+    0/0's points beyond 10 deg (median 0.5 deg) -- furniture standing against the wall puts points of its own faces, and of
+    the junction the TSDF rounds off, within 5 mm of the wall's plane.  So the wall test asks for 88 % within 10 deg and a
+    median under 3 deg, not for every point (DESIGN.md "Colour")."""
+    n, scan, count = 256, 720, 150
+    poses, frames = hsk.synth_sensor_frames(count, room=0, scan=scan)
+    trk = hsk.KinfuTracker(n=n, init_pose=poses[0])
+    trk.enable_color()
+    tracked = []
+    trk.submit_frame_rgbd(frames[0], hsk.synth_rgb(poses[0], 0))
+    for k in range(1, count):
+        trk.submit_frame_rgbd(frames[k], hsk.synth_rgb(poses[k], 0))
+        tracked.append(trk.wait_frame()[1])
+    tracked.append(trk.wait_frame()[1])
+    assert all(tracked[1:]), "the room scan must stay tracked"
+    xyz, nrm, rgb, total, unc = trk.extract_cloud_attrs()
+    colored = (rgb != 0).any(axis=1)
+    assert colored.sum() > 0.9 * total, (colored.sum(), total, unc)
+    want = np.rint(128.0 + 100.0 * np.sin(2.0 * np.pi * xyz.astype(np.float64) / 1.2))
+    err = np.abs(rgb.astype(np.float64) - want).max(axis=1)[colored]
+    share = (err <= 16).mean()
+    assert share >= 0.98, f"only {share:.4f} of the coloured points within 16 levels (median error {np.median(err)})"
+    e = hsk.synth_room_extents(0)
+    cell = 3.0 / n
+    checked = 0
+    for ax in range(3):
+        for side, into in ((0, 1.0), (1, -1.0)):
+            plane = e[2 * ax + side]
+            near = np.abs(xyz[:, ax] - plane) < 0.005
+            for other in range(3):
+                if other != ax:
+                    near &= (np.abs(xyz[:, other] - e[2 * other]) > 3 * cell) & (np.abs(xyz[:, other] - e[2 * other + 1]) > 3 * cell)
+            near &= ~np.isnan(nrm[:, 0])
+            if near.sum() < 50:
+                continue
+            ang = np.degrees(np.arccos(np.clip(nrm[near, ax] * into, -1.0, 1.0)))
+            good = (ang <= 10.0).mean()
+            assert good >= 0.88, f"wall {ax}/{side}: {good:.4f} of {near.sum()} normals within 10 deg"
+            assert np.median(ang) < 3.0, f"wall {ax}/{side}: median angle {np.median(ang):.2f} deg"
+            checked += 1
+    assert checked >= 3
+    trk.close()
+
+
+@pytest.mark.parametrize("devices", [(0, 0), (0,)])
+def test_slab_refuses_color(hsk, devices):
+    """a slab of a group refuses colour -- also the one slab of a one-slab group, which owns the whole volume"""
+    g = hsk.KinfuGroup(n=64, device_ids=devices)
+    for i in range(g.n_slabs()):
+        with pytest.raises(hsk.KinfuError):
+            g.slab(i).enable_color()
+    g.close()
+
+
+def test_gated_frames_color_when_they_integrate(hsk):
+    """integrate_move_thresh > 0: the host's gate decides per frame, and colour follows the integrate.  Repeated frames barely
+    move, so the gate skips them; which frames integrated is read off the TSDF (it changes exactly when one does)"""
+    n = 64
+    seq = [0, 1, 2, 2, 2, 3, 4, 4, 5, 6, 6, 6, 7]
+    frames = [frame_of(hsk, "synth", k) for k in seq]
+    trk = hsk.KinfuTracker(n=n, integrate_move_thresh=0.002)
+    trk.enable_color()
+    col = np.zeros((n, n, n, 4), np.uint8)
+    prev = trk.download_tsdf()
+    integrated = []
+    for k, (_, depth, rgb) in enumerate(frames):
+        pose, ok = trk.process_frame_rgbd(depth, rgb)
+        assert ok or k == 0
+        cur = trk.download_tsdf()
+        did = not np.array_equal(cur, prev)
+        integrated.append(did)
+        prev = cur
+        if did:
+            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), 64)
+        assert np.array_equal(trk.download_color(), col), f"frame {k} (integrated: {did})"
+    assert integrated[0] and any(integrated[1:]) and not all(integrated), integrated
+    trk.close()
+
+
+@pytest.mark.parametrize("use_graph,mode", [(1, "sync"), (2, "async"), (2, "sync")])
+def test_enable_after_graph_capture(hsk, use_graph, mode):
+    """colour enabled after the frame chain was captured without it: the graphs are captured again, with the colour launch"""
+    n = 64
+    frames = [frame_of(hsk, "synth", k) for k in range(10)]
+    trk = hsk.KinfuTracker(n=n, use_graph=use_graph)
+    for _, depth, _ in frames[:4]:
+        if mode == "sync":
+            assert trk.process_frame(depth)[1] or depth is frames[0][1]
+        else:
+            trk.submit_frame(depth)
+            trk.wait_frame()
+    trk.enable_color()
+    assert not trk.download_color().any()
+    res = []
+    rest = frames[4:]
+    if mode == "sync":
+        res = [trk.process_frame_rgbd(d, c) for _, d, c in rest]
+    else:
+        for i, (_, d, c) in enumerate(rest):
+            trk.submit_frame_rgbd(d, c)
+            if i >= 1:
+                res.append(trk.wait_frame())
+        res.append(trk.wait_frame())
+    assert all(ok for _, ok in res)
+    col = np.zeros((n, n, n, 4), np.uint8)
+    for (_, d, c), (pose, _) in zip(rest, res):
+        np_color(col, scale_depth(d, FX, FY, CX, CY), c, pose, band_of(n, 0.0), 64)
+    assert np.array_equal(trk.download_color(), col)
+    trk.close()
