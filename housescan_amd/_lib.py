@@ -80,6 +80,8 @@ SYMBOLS = {
     "hsk_download_color": (C.c_int, [_P, _P]),
     "hsk_upload_color": (C.c_int, [_P, _P]),
     "hsk_extract_cloud_attrs": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "hsk_extract_mesh_indexed": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                            C.POINTER(C.c_size_t)]),
     "hsk_mgpu_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_prefetch": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_front": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
@@ -132,6 +134,7 @@ SYMBOLS = {
     "hsk_write_pcd_xyz": (C.c_int, [C.c_char_p, _P, C.c_size_t]),
     "hsk_write_ply_mesh": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_weld_triangles": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
+    "hsk_write_ply_indexed": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
     "hsk_voxel_downsample": (C.c_int, [_P, C.c_size_t, C.c_float, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_voxel_downsample_attrs": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_float, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_write_pcd_xyzrgbnormal": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_size_t]),
@@ -141,6 +144,7 @@ SYMBOLS = {
     "hsk_write_xf": (C.c_int, [C.c_char_p, _F]),
     "hsk_read_xf": (C.c_int, [C.c_char_p, _F]),
     "hsk_transform_cloud": (C.c_int, [_P, C.c_size_t, _F, _P]),
+    "hsk_transform_normals": (C.c_int, [_P, C.c_size_t, _F, _P]),
     "hsk_stream_create": (_P, [C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float]),
     "hsk_stream_open": (_P, [C.c_char_p, _I, _I, _I, _F]),
     "hsk_stream_write": (C.c_int, [_P, _P]),

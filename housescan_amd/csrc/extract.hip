@@ -646,6 +646,36 @@ static __device__ float attr_trilinear(const short2* __restrict__ vol, const Vol
   res = res + attr_tsdf(vol, vp, gx + 1, gy + 1, gz + 1) * a * b * c;
   return res;
 }
+// the normal rule at p: NaN x 3 outside the (1, dims - 2) interior (shared by the cloud's and the indexed mesh's attributes)
+static __device__ __forceinline__ void attr_normal(const short2* __restrict__ vol, const VolParams& vp, float px, float py, float pz,
+                                                   float* nx, float* ny, float* nz) {
+  *nx = HSK_NANF, *ny = HSK_NANF, *nz = HSK_NANF;
+  const float qx = floorf(px / vp.cell[0]), qy = floorf(py / vp.cell[1]), qz = floorf(pz / vp.cell[2]);
+  if (qx > 1.0f && qx < (float)(vp.X - 2) && qy > 1.0f && qy < (float)(vp.Y - 2) && qz > 1.0f && qz < (float)(vp.Z - 2)) {
+    const float gxn = attr_trilinear(vol, vp, px + vp.cell[0], py, pz) - attr_trilinear(vol, vp, px - vp.cell[0], py, pz);
+    const float gyn = attr_trilinear(vol, vp, px, py + vp.cell[1], pz) - attr_trilinear(vol, vp, px, py - vp.cell[1], pz);
+    const float gzn = attr_trilinear(vol, vp, px, py, pz + vp.cell[2]) - attr_trilinear(vol, vp, px, py, pz - vp.cell[2]);
+    const float ninv = 1.0f / sqrtf(hsk_dot3(gxn, gyn, gzn, gxn, gyn, gzn));
+    *nx = gxn * ninv;
+    *ny = gyn * ninv;
+    *nz = gzn * ninv;
+  }
+}
+// the colour rule of the edge between voxel a = (x, y, zz) and its neighbour b (stored planes): the (r, g, b, w) word chosen,
+// 0 with one count in *uncol when neither voxel has colour weight
+static __device__ __forceinline__ unsigned attr_color(const short2* __restrict__ vol, const unsigned* __restrict__ colv, const VolParams& vp,
+                                                      int x, int y, int zz, int bx, int by, int bzz, unsigned* uncol) {
+  const int ta = vol[hsk_vox_index(vp, x, y, zz)].x, tb = vol[hsk_vox_index(vp, bx, by, bzz)].x;
+  const unsigned ca = colv[((size_t)zz * vp.Y + y) * vp.X + x], cb = colv[((size_t)bzz * vp.Y + by) * vp.X + bx];
+  const bool take_a = (ta < 0 ? -ta : ta) <= (tb < 0 ? -tb : tb);
+  unsigned cw = take_a ? ca : cb;
+  if ((cw >> 24) == 0u) cw = take_a ? cb : ca;
+  if ((cw >> 24) == 0u) {
+    cw = 0u;
+    *uncol += 1u;
+  }
+  return cw;
+}
 // the axes of the crossings crossing_count finds at (x, y, z), in its order (the same tests)
 static __device__ __forceinline__ int crossing_axes(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z, int* axes) {
   const short2 c = vol[hsk_vox_index(vp, x, y, z - vp.zs0)];
@@ -705,17 +735,8 @@ __global__ __launch_bounds__(256) void k_extract_attrs(const short2* __restrict_
       xyz[3 * at + 1] = py;
       xyz[3 * at + 2] = pz;
       if (normals) {
-        float nx = HSK_NANF, ny = HSK_NANF, nz = HSK_NANF;
-        const float qx = floorf(px / vp.cell[0]), qy = floorf(py / vp.cell[1]), qz = floorf(pz / vp.cell[2]);
-        if (qx > 1.0f && qx < (float)(vp.X - 2) && qy > 1.0f && qy < (float)(vp.Y - 2) && qz > 1.0f && qz < (float)(vp.Z - 2)) {
-          const float gxn = attr_trilinear(vol, vp, px + vp.cell[0], py, pz) - attr_trilinear(vol, vp, px - vp.cell[0], py, pz);
-          const float gyn = attr_trilinear(vol, vp, px, py + vp.cell[1], pz) - attr_trilinear(vol, vp, px, py - vp.cell[1], pz);
-          const float gzn = attr_trilinear(vol, vp, px, py, pz + vp.cell[2]) - attr_trilinear(vol, vp, px, py, pz - vp.cell[2]);
-          const float ninv = 1.0f / sqrtf(hsk_dot3(gxn, gyn, gzn, gxn, gyn, gzn));
-          nx = gxn * ninv;
-          ny = gyn * ninv;
-          nz = gzn * ninv;
-        }
+        float nx, ny, nz;
+        attr_normal(vol, vp, px, py, pz, &nx, &ny, &nz);
         normals[3 * at] = nx;
         normals[3 * at + 1] = ny;
         normals[3 * at + 2] = nz;
@@ -724,15 +745,7 @@ __global__ __launch_bounds__(256) void k_extract_attrs(const short2* __restrict_
         const int k = axes[q];
         const int zz = z - vp.zs0;
         const int bx = x + (k == 0 ? 1 : 0), by = y + (k == 1 ? 1 : 0), bzz = zz + (k == 2 ? 1 : 0);
-        const int ta = vol[hsk_vox_index(vp, x, y, zz)].x, tb = vol[hsk_vox_index(vp, bx, by, bzz)].x;
-        const unsigned ca = colv[((size_t)zz * vp.Y + y) * vp.X + x], cb = colv[((size_t)bzz * vp.Y + by) * vp.X + bx];
-        const bool take_a = (ta < 0 ? -ta : ta) <= (tb < 0 ? -tb : tb);
-        unsigned cw = take_a ? ca : cb;
-        if ((cw >> 24) == 0u) cw = take_a ? cb : ca;
-        if ((cw >> 24) == 0u) {
-          cw = 0u;
-          uncol += 1u;
-        }
+        const unsigned cw = attr_color(vol, colv, vp, x, y, zz, bx, by, bzz, &uncol);
         rgb[3 * at] = (unsigned char)(cw & 255u);
         rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
         rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
@@ -755,6 +768,270 @@ void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, 
   const int nrows = vp.Y * (vp.zo1 - vp.zo0);
   hipLaunchKernelGGL(k_extract_attrs, dim3((nrows + 3) / 4), dim3(256), 0, s, (const short2*)vol, colv, vp, row_count, row_offset, xyz,
                      normals, rgb, cap, n_uncolored, flags);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The marching-cubes surface as an INDEXED mesh (hsk_extract_mesh_indexed), welded by edge identity: a vertex is computed
+// from its edge's lower corner, so every cube that shares an edge produces the same bits, and the edge names the vertex.
+// A GRID ROW (y, z) holds the edges whose lower corner lies on it, bit 3 x + axis, in segments of 64 voxels (3 words):
+//   mark     (a wave per cube row, k_extract_mesh_mc's walk): each valid, cut cube ORs the bits of its cut edges into the
+//            four grid rows its edges start on, and the row's triangles are counted (the faces' row offsets)
+//   rows     (a wave per grid row): its vertex count, and per segment the count of the segments before it
+//   (both row counts scanned by launch_scan_rows: the vertex order is the bits' order -- plane, row, x, axis)
+//   vertices (a wave per grid row, a lane per voxel): the soup's arithmetic, the cloud's normal and colour rules
+//   faces    (k_extract_mesh_mc<true>'s walk): each corner's index is its edge's rank, at most three popcounts
+// ------------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ unsigned mi_case(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
+  // the cube's inside mask when it is valid and cut, 0 otherwise (cube_triangles_mc's tests)
+  bool ok = true;
+  unsigned m8 = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const short2 v = vol[hsk_vox_index(vp, x + (c & 1), y + ((c >> 1) & 1), z + (c >> 2) - vp.zs0)];
+    ok = ok && v.y != 0;
+    m8 |= (v.x < 0 ? 1u : 0u) << c;
+  }
+  return (!ok || m8 == 255u) ? 0u : m8;
+}
+// set bits below bit o (0 .. 191) of a segment's three words
+static __device__ __forceinline__ unsigned mi_rank(unsigned long long w0, unsigned long long w1, unsigned long long w2, int o) {
+  const unsigned long long m0 = o >= 64 ? ~0ull : ((1ull << o) - 1ull);
+  const unsigned long long m1 = o >= 128 ? ~0ull : (o <= 64 ? 0ull : ((1ull << (o - 64)) - 1ull));
+  const unsigned long long m2 = o <= 128 ? 0ull : ((1ull << (o - 128)) - 1ull);
+  return (unsigned)(__popcll(w0 & m0) + __popcll(w1 & m1) + __popcll(w2 & m2));
+}
+
+size_t mesh_index_layout(const VolParams& vp, void* base, MeshIndexBufs* b) {
+  const int z_end = hsk_mesh_z_end(vp);
+  const int rows = z_end > vp.zo0 ? vp.Y * (z_end - vp.zo0 + 1) : 0;
+  const int nseg = (vp.X + 63) / 64;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? (char*)base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  MeshIndexBufs m;
+  m.rows = rows;
+  m.nseg = nseg;
+  m.totals = (unsigned long long*)take(32);
+  m.bits = (unsigned long long*)take((size_t)rows * 3 * nseg * 8);
+  m.voff = (unsigned long long*)take(hsk_scan_scratch_entries(rows) * 8);
+  m.vcount = (unsigned*)take((size_t)rows * 4);
+  m.segbase = (unsigned short*)take((size_t)rows * nseg * 2);
+  if (b) *b = m;
+  return off;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_index_mark(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
+                                                         unsigned* __restrict__ row_count, unsigned* __restrict__ bits, int nseg, int z_end,
+                                                         const unsigned* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  const int ny = vp.Y - 1;
+  const int nrows = ny * (z_end - vp.zo0);
+  if (row >= nrows) return;
+  const int y = row % ny, zr = row / ny, z = vp.zo0 + zr;
+  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
+  if (row_mask == 0ull) {
+    if (lane == 0) row_count[row] = 0u;
+    return;
+  }
+  const size_t row_words = (size_t)nseg * 6;  // (32-bit words of a grid row)
+  unsigned total = 0;
+  for (int xb = 0; xb < vp.X - 1; xb += 64) {
+    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
+    const int x = xb + lane;
+    const unsigned m8 = x < vp.X - 1 ? mi_case(vol, vp, x, y, z) : 0u;
+    int n = 0;
+    if (m8 != 0u) {
+      n = ct->ntri[m8];
+      // the cut edges by the grid row they start on (dy, dz), as bits 0 .. 5 above bit 3 x: the x edge of the row's corner
+      // (bit 0), and on the lower rows the y edges (bits 1, 4) or z edges (bits 2, 5) of the corners x and x + 1
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int dy = r & 1, dz = r >> 1;
+        const int c0 = dy * 2 + dz * 4;
+        unsigned m = ((m8 >> c0) ^ (m8 >> (c0 + 1))) & 1u;
+        if (dy == 0)
+          m |= ((((m8 >> c0) ^ (m8 >> (c0 + 2))) & 1u) << 1) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 3))) & 1u) << 4);
+        if (dz == 0)
+          m |= ((((m8 >> c0) ^ (m8 >> (c0 + 4))) & 1u) << 2) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 5))) & 1u) << 5);
+        if (m == 0u) continue;
+        const int bit = 3 * x;
+        unsigned* w = bits + (size_t)((zr + dz) * vp.Y + y + dy) * row_words + (bit >> 5);
+        const int sh = bit & 31;
+        atomicOr(w, m << sh);
+        if (sh > 26 && (m >> (32 - sh)) != 0u) atomicOr(w + 1, m >> (32 - sh));
+      }
+    }
+    int sum = n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    total += sum;
+  }
+  if (lane == 0) row_count[row] = total;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_index_rows(const unsigned long long* __restrict__ bits, int rows, int nseg,
+                                                         unsigned* __restrict__ vcount, unsigned short* __restrict__ segbase) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (row >= rows) return;
+  const unsigned long long* w = bits + (size_t)row * 3 * nseg;
+  unsigned carry = 0;
+  for (int j0 = 0; j0 < 3 * nseg; j0 += 64) {  // a lane per word
+    const int j = j0 + lane;
+    const unsigned c = j < 3 * nseg ? (unsigned)__popcll(w[j]) : 0u;
+    unsigned incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (j < 3 * nseg && j % 3 == 0) segbase[(size_t)row * nseg + j / 3] = (unsigned short)(carry + incl - c);
+    carry += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) vcount[row] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_index_verts(const short2* __restrict__ vol, const unsigned* __restrict__ colv, VolParams vp,
+                                                          MeshIndexBufs mb, float* __restrict__ xyz, float* __restrict__ normals,
+                                                          unsigned char* __restrict__ rgb, unsigned long long* __restrict__ n_uncolored) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (row >= mb.rows) return;
+  if (mb.vcount[row] == 0u) return;
+  const int y = row % vp.Y, z = vp.zo0 + row / vp.Y, zz = z - vp.zs0;
+  const unsigned long long* w = mb.bits + (size_t)row * 3 * mb.nseg;
+  const unsigned long long row_base = mb.voff[row];
+  unsigned uncol = 0;
+  for (int s = 0; s < mb.nseg; ++s) {
+    const unsigned long long w0 = w[3 * s], w1 = w[3 * s + 1], w2 = w[3 * s + 2];
+    if ((w0 | w1 | w2) == 0ull) continue;
+    const int o = 3 * lane, j = o >> 6, sh = o & 63;
+    const unsigned long long lo = j == 0 ? w0 : (j == 1 ? w1 : w2), hi = j == 0 ? w1 : w2;
+    const unsigned b3 = ((unsigned)(lo >> sh) | (sh > 61 ? (unsigned)(hi << (64 - sh)) : 0u)) & 7u;
+    if (b3 == 0u) continue;
+    const int x = 64 * s + lane;
+    unsigned long long at = row_base + mb.segbase[(size_t)row * mb.nseg + s] + mi_rank(w0, w1, w2, o);
+    const short fa = vol[hsk_vox_index(vp, x, y, zz)].x;
+    for (int k = 0; k < 3; ++k) {
+      if (!((b3 >> k) & 1u)) continue;
+      const int bx = x + (k == 0 ? 1 : 0), by = y + (k == 1 ? 1 : 0), bzz = zz + (k == 2 ? 1 : 0);
+      const short fb = vol[hsk_vox_index(vp, bx, by, bzz)].x;
+      // (cube_triangles_mc's arithmetic on every axis: a, the lower corner, and b)
+      const float Fa = (float)fa / 32767.0f, Fb = (float)fb / 32767.0f;
+      const float wt = Fa / (Fa - Fb);
+      const int ga[3] = {x, y, z};
+      const int gb[3] = {bx, by, z + (k == 2 ? 1 : 0)};
+      float p[3];
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        const float pa = ((float)ga[ax] + 0.5f) * vp.cell[ax];
+        const float pb = ((float)gb[ax] + 0.5f) * vp.cell[ax];
+        p[ax] = pa + wt * (pb - pa);
+      }
+      if (xyz) {
+        xyz[3 * at] = p[0];
+        xyz[3 * at + 1] = p[1];
+        xyz[3 * at + 2] = p[2];
+      }
+      if (normals) {
+        float nx, ny, nz;
+        attr_normal(vol, vp, p[0], p[1], p[2], &nx, &ny, &nz);
+        normals[3 * at] = nx;
+        normals[3 * at + 1] = ny;
+        normals[3 * at + 2] = nz;
+      }
+      if (rgb) {
+        const unsigned cw = attr_color(vol, colv, vp, x, y, zz, bx, by, bzz, &uncol);
+        rgb[3 * at] = (unsigned char)(cw & 255u);
+        rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
+        rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
+      }
+      ++at;
+    }
+  }
+  if (rgb && n_uncolored) {
+    unsigned sum = uncol;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_index_faces(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
+                                                          const unsigned* __restrict__ row_count, const unsigned long long* __restrict__ row_offset,
+                                                          MeshIndexBufs mb, int* __restrict__ faces, int z_end, const unsigned* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  const int ny = vp.Y - 1;
+  const int nrows = ny * (z_end - vp.zo0);
+  if (row >= nrows) return;
+  const int y = row % ny, zr = row / ny, z = vp.zo0 + zr;
+  if (row_count[row] == 0u) return;  // (the mark pass found the row empty)
+  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
+  if (row_mask == 0ull) return;
+  unsigned long long base = row_offset[row];
+  for (int xb = 0; xb < vp.X - 1; xb += 64) {
+    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
+    const int x = xb + lane;
+    const unsigned m8 = x < vp.X - 1 ? mi_case(vol, vp, x, y, z) : 0u;
+    const int n = m8 ? (int)ct->ntri[m8] : 0;
+    int scan = n;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(scan, o, 64);
+      if (lane >= o) scan += u;
+    }
+    const int wave_total = __shfl(scan, 63, 64);
+    const unsigned long long at = base + (unsigned long long)(scan - n);
+    for (int t = 0; t < n; ++t)
+      for (int q = 0; q < 3; ++q) {
+        const unsigned code = ct->edge[m8][t][q];
+        const int a = (int)(code & 15u), ab = (int)((code >> 4) ^ code) & 7;  // (b ^ a: the edge's axis as 1, 2 or 4)
+        const int axis = ab == 1 ? 0 : (ab == 2 ? 1 : 2);
+        const int gx = x + (a & 1), g = (zr + (a >> 2)) * vp.Y + y + ((a >> 1) & 1);
+        const int s = gx >> 6;
+        const unsigned long long* w = mb.bits + ((size_t)g * mb.nseg + s) * 3;
+        const unsigned long long idx = mb.voff[g] + mb.segbase[(size_t)g * mb.nseg + s] + mi_rank(w[0], w[1], w[2], 3 * (gx & 63) + axis);
+        faces[3 * (at + t) + q] = (int)idx;
+      }
+    base += wave_total;
+  }
+}
+
+// the count pass: zeroed edge bits, marked, the grid rows' counts; both row scans (totals[0] vertices, totals[1] faces)
+void launch_mesh_index_count(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
+                             unsigned long long* row_offset, const MeshIndexBufs& mb, const unsigned* flags) {
+  const int z_end = hsk_mesh_z_end(vp);
+  const int nrows = (vp.Y - 1) * (z_end - vp.zo0);
+  if (nrows <= 0 || mb.rows <= 0) {
+    (void)hipMemsetAsync(mb.totals, 0, 16, s);
+    return;
+  }
+  (void)hipMemsetAsync(mb.bits, 0, (size_t)mb.rows * 3 * mb.nseg * 8, s);
+  hipLaunchKernelGGL(k_mesh_index_mark, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s, (const short2*)vol, vp, ct_dev, row_count,
+                     (unsigned*)mb.bits, mb.nseg, z_end, flags);
+  hipLaunchKernelGGL(k_mesh_index_rows, dim3((unsigned)((mb.rows + 3) / 4)), dim3(256), 0, s, (const unsigned long long*)mb.bits, mb.rows,
+                     mb.nseg, mb.vcount, mb.segbase);
+  launch_scan_rows(s, mb.vcount, mb.voff, mb.rows, mb.totals);
+  launch_scan_rows(s, row_count, row_offset, nrows, mb.totals + 1);
+}
+// the write passes behind it: the vertices (any of xyz / normals / rgb; rgb needs colv), the faces (when non-null)
+void launch_mesh_index_write(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const CubeTable* ct_dev,
+                             const unsigned* row_count, const unsigned long long* row_offset, const MeshIndexBufs& mb, float* xyz,
+                             float* normals, unsigned char* rgb, unsigned long long* n_uncolored, int* faces, const unsigned* flags) {
+  const int z_end = hsk_mesh_z_end(vp);
+  const int nrows = (vp.Y - 1) * (z_end - vp.zo0);
+  if (nrows <= 0 || mb.rows <= 0) return;
+  if (xyz || normals || rgb)
+    hipLaunchKernelGGL(k_mesh_index_verts, dim3((unsigned)((mb.rows + 3) / 4)), dim3(256), 0, s, (const short2*)vol, colv, vp, mb, xyz,
+                       normals, rgb, n_uncolored);
+  if (faces)
+    hipLaunchKernelGGL(k_mesh_index_faces, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s, (const short2*)vol, vp, ct_dev, row_count,
+                       row_offset, mb, faces, z_end, flags);
 }
 
 // The code object of this file is loaded when one of its kernels is first used (deferred loading): 0.7 ms that the first

@@ -87,3 +87,20 @@ void launch_extract_mesh(hipStream_t s, const void* vol, const VolParams& vp, co
                          unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags);
 void launch_extract_mesh_mc(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
                             unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags);
+// the indexed marching-cubes mesh (extract.hip): its scratch, carved out of one device buffer by mesh_index_layout
+struct MeshIndexBufs {
+  int rows;                     // grid rows: Y x (hsk_mesh_z_end - zo0 + 1) planes (0 when the context emits no cube)
+  int nseg;                     // 64-voxel segments per row; a row's edge bits are 3 nseg words
+  unsigned long long* totals;   // [0] vertices, [1] faces, [2] uncoloured vertices
+  unsigned long long* bits;     // rows x 3 nseg words: bit 3 x + axis of row (y, z) = the edge from (x, y, z) has a vertex
+  unsigned long long* voff;     // rows (+ the scan's block sums): the rows' first vertex
+  unsigned* vcount;             // rows: vertices per row
+  unsigned short* segbase;      // rows x nseg: vertices of the row before each segment
+};
+size_t mesh_index_layout(const VolParams& vp, void* base /* null: the size only */, MeshIndexBufs* b);
+// count pass (faces' row counts into row_count / row_offset, as launch_extract_mesh_mc's pass 0), then the write passes
+void launch_mesh_index_count(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
+                             unsigned long long* row_offset, const MeshIndexBufs& mb, const unsigned* flags);
+void launch_mesh_index_write(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const CubeTable* ct_dev,
+                             const unsigned* row_count, const unsigned long long* row_offset, const MeshIndexBufs& mb, float* xyz,
+                             float* normals, unsigned char* rgb, unsigned long long* n_uncolored, int* faces, const unsigned* flags);

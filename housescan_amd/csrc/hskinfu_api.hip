@@ -82,7 +82,7 @@ struct hsk_ctx {
   // finds the rows' counts and offsets in place), a grow-only device buffer for the product, and two pinned staging
   // buffers through which products and the volume reach the caller's pageable memory (lazily allocated)
   uint64_t vol_epoch = 1;       // counted up by everything that changes the volume
-  int ro_kind = 0;              // 1 cloud, 2 tetrahedra mesh, 3 cubes mesh: whose counts d_rowcnt / d_rowoff hold
+  int ro_kind = 0;              // 1 cloud, 2 tetrahedra mesh, 3 cubes mesh, 4 indexed mesh: whose counts d_rowcnt / d_rowoff hold
   uint64_t ro_epoch = 0;
   unsigned long long ro_total = 0;
   void* d_out = nullptr;
@@ -153,6 +153,11 @@ struct hsk_ctx {
   float color_band = 0.0f;
   void* d_attr = nullptr;
   size_t attr_bytes = 0;
+  // the indexed mesh's scratch (hsk_extract_mesh_indexed: edge bits, per-row tables; extract.hip mesh_index_layout), made on
+  // first use; its counts belong to ro_kind 4, whose faces are ro_total
+  void* d_mi = nullptr;
+  size_t mi_bytes = 0;
+  unsigned long long mi_vertices = 0;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -288,6 +293,7 @@ static void free_all(hsk_ctx* k) {
   F(k->d_color);
   F(k->d_has_color);
   F(k->d_attr);
+  F(k->d_mi);
   for (auto& b : k->ib) F(b.d_rgb);
   if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
   for (auto& p : k->h_pin)
@@ -1782,6 +1788,74 @@ extern "C" int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, u
   if (r == HSK_OK && rgb && n_uncolored) {
     unsigned long long u = 0;
     HIPCHK(k, hipMemcpyAsync(&u, d_uncol, 8, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    *n_uncolored = (size_t)u;
+  }
+  return r;
+}
+
+// hsk_extract_mesh_cubes' surface as an indexed mesh, welded on the device by edge identity (extract.hip: k_mesh_index_*).
+// The count pass (edge bits, both row scans) is cached as kind 4; the faces' row tables are the shared d_rowcnt / d_rowoff.
+extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* normals, uint8_t* rgb, size_t cap_vertices, size_t* n_vertices,
+                                        int32_t* faces, size_t cap_faces, size_t* n_faces, size_t* n_uncolored) {
+  if (!k || !n_vertices || !n_faces) return HSK_ERR_ARG;
+  if (rgb && !k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  if (n_uncolored) *n_uncolored = 0;
+  int r = ensure_cube_table(k);
+  if (r == HSK_OK) r = ensure_row_tables(k);
+  if (r != HSK_OK) return r;
+  MeshIndexBufs mb;
+  if (!k->d_mi) {
+    const size_t bytes = mesh_index_layout(k->vp, nullptr, nullptr);
+    HIPCHK(k, hipMalloc(&k->d_mi, bytes));
+    k->mi_bytes = bytes;
+  }
+  (void)mesh_index_layout(k->vp, k->d_mi, &mb);
+  // (no flush of the deferred weights: extract_product says why)
+  if (!(k->ro_kind == 4 && k->ro_epoch == k->vol_epoch)) {
+    k->ro_kind = 0;
+    launch_mesh_index_count(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, mb, k->d_flags);
+    unsigned long long tot[2] = {0, 0};
+    HIPCHK(k, hipMemcpyAsync(tot, mb.totals, 16, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    k->ro_kind = 4;
+    k->ro_epoch = k->vol_epoch;
+    k->ro_total = tot[1];
+    k->mi_vertices = tot[0];
+  }
+  const size_t nv = (size_t)k->mi_vertices, nf = (size_t)k->ro_total;
+  *n_vertices = nv;
+  *n_faces = nf;
+  if (nv > (size_t)INT32_MAX) return fail(k, HSK_ERR_STATE, "hsk_extract_mesh_indexed: more vertices than an int32 index reaches");
+  const bool want_v = vertices || normals || rgb;
+  if ((want_v && cap_vertices < nv) || (faces && cap_faces < nf))
+    return fail(k, HSK_ERR_ARG, "hsk_extract_mesh_indexed: a capacity below the total (the arrays are written whole or not at all)");
+  if (!(want_v && nv) && !(faces && nf)) return HSK_OK;
+  // one product buffer: vertices, normals, colours, faces (each 256-B aligned)
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_nrm = al(vertices ? nv * 12 : 0), o_rgb = o_nrm + al(normals ? nv * 12 : 0), o_fc = o_rgb + al(rgb ? nv * 3 : 0);
+  const size_t want = o_fc + (faces ? nf * 12 : 0);
+  if (k->out_bytes < want) {
+    r = ensure_product_bytes(k, want + (want >> 2));
+    if (r != HSK_OK) return r;
+  }
+  char* d = (char*)k->d_out;
+  float* d_xyz = vertices ? (float*)d : nullptr;
+  float* d_nrm = normals ? (float*)(d + o_nrm) : nullptr;
+  unsigned char* d_rgb = rgb ? (unsigned char*)(d + o_rgb) : nullptr;
+  int* d_fc = faces ? (int*)(d + o_fc) : nullptr;
+  if (rgb) HIPCHK(k, hipMemsetAsync(mb.totals + 2, 0, 8, k->stream));
+  launch_mesh_index_write(k->stream, k->d_vol, k->d_color, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, mb, nv ? d_xyz : nullptr,
+                          nv ? d_nrm : nullptr, nv ? d_rgb : nullptr, mb.totals + 2, nf ? d_fc : nullptr, k->d_flags);
+  HIPCHK(k, hipGetLastError());
+  if (vertices && nv) r = copy_out(k, vertices, d_xyz, nv * 12);
+  if (r == HSK_OK && normals && nv) r = copy_out(k, normals, d_nrm, nv * 12);
+  if (r == HSK_OK && rgb && nv) r = copy_out(k, rgb, d_rgb, nv * 3);
+  if (r == HSK_OK && faces && nf) r = copy_out(k, faces, d_fc, nf * 12);
+  if (r == HSK_OK && rgb && n_uncolored) {
+    unsigned long long u = 0;
+    HIPCHK(k, hipMemcpyAsync(&u, mb.totals + 2, 8, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
     *n_uncolored = (size_t)u;
   }

@@ -563,3 +563,67 @@ extern "C" int hsk_write_ply_mesh(const char* path, const float* tri_xyz, size_t
   if (n_faces_out) *n_faces_out = faces;
   return (ok && rc == 0) ? HSK_OK : HSK_ERR_STATE;
 }
+
+// binary little-endian PLY 1.0 of an indexed mesh: per vertex x y z [nx ny nz] [red green blue], interleaved and unpadded (NaN
+// normal components written as 0); per face a uchar 3 and three int indices, every face as given.  The indices are checked
+// before the file is created.
+extern "C" int hsk_write_ply_indexed(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
+                                     const int32_t* faces, size_t n_faces) {
+  if (!path || (n_vertices && !vertices) || (n_faces && !faces)) return HSK_ERR_ARG;
+  for (size_t i = 0; i < 3 * n_faces; ++i)
+    if (faces[i] < 0 || (size_t)faces[i] >= n_vertices) return HSK_ERR_ARG;
+  FILE* f = fopen(path, "wb");
+  if (!f) return HSK_ERR_STATE;
+  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n", n_vertices);
+  if (normals) fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
+  if (rgb) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+  fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", n_faces);
+  const size_t rec = 12 + (normals ? 12 : 0) + (rgb ? 3 : 0), batch = 8192;
+  std::vector<unsigned char> buf(batch * (rec > 13 ? rec : 13));
+  bool ok = true;
+  for (size_t i0 = 0; i0 < n_vertices && ok; i0 += batch) {
+    const size_t m = n_vertices - i0 < batch ? n_vertices - i0 : batch;
+    unsigned char* p = buf.data();
+    for (size_t j = 0; j < m; ++j) {
+      const size_t i = i0 + j;
+      memcpy(p, vertices + 3 * i, 12);
+      p += 12;
+      if (normals) {
+        for (int c = 0; c < 3; ++c) {
+          const float v = normals[3 * i + c];
+          const float w = v == v ? v : 0.0f;
+          memcpy(p + 4 * c, &w, 4);
+        }
+        p += 12;
+      }
+      if (rgb) {
+        memcpy(p, rgb + 3 * i, 3);
+        p += 3;
+      }
+    }
+    ok = fwrite(buf.data(), rec, m, f) == m;
+  }
+  for (size_t t0 = 0; t0 < n_faces && ok; t0 += batch) {
+    const size_t m = n_faces - t0 < batch ? n_faces - t0 : batch;
+    for (size_t j = 0; j < m; ++j) {
+      buf[13 * j] = 3;
+      memcpy(&buf[13 * j + 1], faces + 3 * (t0 + j), 12);
+    }
+    ok = fwrite(buf.data(), 13, m, f) == m;
+  }
+  const int rc = fclose(f);
+  return (ok && rc == 0) ? HSK_OK : HSK_ERR_STATE;
+}
+
+// n' = R n with R the rotation part of a row-major .xf matrix: hsk_transform_cloud's arithmetic without the translation, no
+// renormalisation (in place allowed)
+extern "C" int hsk_transform_normals(const float* n, size_t count, const float m[16], float* out) {
+  if ((!n && count) || !m || (!out && count)) return HSK_ERR_ARG;
+  for (size_t i = 0; i < count; ++i) {
+    const float x = n[3 * i], y = n[3 * i + 1], z = n[3 * i + 2];
+    out[3 * i] = m[0] * x + m[1] * y + m[2] * z;
+    out[3 * i + 1] = m[4] * x + m[5] * y + m[6] * z;
+    out[3 * i + 2] = m[8] * x + m[9] * y + m[10] * z;
+  }
+  return HSK_OK;
+}

@@ -315,6 +315,23 @@ class KinfuTracker:
                                                       None if col is None else col.ctypes.data, m, C.byref(n), C.byref(nu)))
         return xyz, nrm, col, total, nu.value
 
+    def extract_mesh_indexed(self, normals=True, rgb=True):
+        """extract_mesh(cubes=True)'s surface as an indexed mesh welded on the device by edge identity ->
+        (vertices [n, 3] float32, faces [m, 3] int32, normals [n, 3] float32 or None, rgb [n, 3] uint8 or None, n_uncolored);
+        vertices[faces] is the triangle soup bit for bit.  rgb=True needs enable_color()."""
+        nv, nf, nu = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_extract_mesh_indexed(self.h, None, None, None, 0, C.byref(nv), None, 0, C.byref(nf), None))
+        verts = np.empty((nv.value, 3), np.float32)
+        faces = np.empty((nf.value, 3), np.int32)
+        nrm = np.empty((nv.value, 3), np.float32) if normals else None
+        col = np.empty((nv.value, 3), np.uint8) if rgb else None
+        self._ck(self.lib.hsk_extract_mesh_indexed(self.h, verts.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                                   None if col is None else col.ctypes.data, len(verts), C.byref(nv),
+                                                   faces.ctypes.data, len(faces), C.byref(nf), C.byref(nu)))
+        if (nv.value, nf.value) != (len(verts), len(faces)):
+            raise KinfuError("extract_mesh_indexed: the counts changed between the two calls")
+        return verts, faces, nrm, col, nu.value
+
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
         return self.lib.hsk_stream(self.h)

@@ -147,6 +147,21 @@ def write_room_dir(room_dir, cloud_xyz, leaf=0.03, *, cloud_rgb=None, cloud_norm
     return planes, len(down)
 
 
+def write_ply_indexed(path, vertices, faces, normals=None, rgb=None):
+    """indexed mesh -> binary little-endian .ply: x y z [nx ny nz] [red green blue] per vertex (NaN normals written as 0),
+    every face as given; an index outside [0, n) raises and writes no file"""
+    lib = _lib.load()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    col = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    for a in (nrm, col):
+        if a is not None and len(a) != len(v):
+            raise ValueError("write_ply_indexed: attributes must have one row per vertex")
+    _ck(lib.hsk_write_ply_indexed(os.fsencode(path), v.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                  None if col is None else col.ctypes.data, len(v), f.ctypes.data, len(f)), "hsk_write_ply_indexed")
+
+
 def write_xf(path, m):
     lib = _lib.load()
     a = np.ascontiguousarray(m, np.float32).reshape(16)
@@ -166,6 +181,16 @@ def transform_cloud(xyz, m):
     a = np.ascontiguousarray(m, np.float32).reshape(16)
     out = np.empty_like(pts)
     _ck(lib.hsk_transform_cloud(pts.ctypes.data, len(pts), a.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data), "hsk_transform_cloud")
+    return out
+
+
+def transform_normals(normals, m):
+    """normals by the rotation part of a row-major .xf matrix (no translation, no renormalisation; NaN stays NaN)"""
+    lib = _lib.load()
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    a = np.ascontiguousarray(m, np.float32).reshape(16)
+    out = np.empty_like(n)
+    _ck(lib.hsk_transform_normals(n.ctypes.data, len(n), a.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data), "hsk_transform_normals")
     return out
 
 

@@ -174,6 +174,32 @@ int hsk_upload_color(hsk_ctx* k, const uint8_t* rgbw);
  * counted in *n_uncolored.  normals, rgb and n_uncolored may be NULL; rgb != NULL needs hsk_enable_color (HSK_ERR_STATE). */
 int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, uint8_t* rgb, size_t cap_points, size_t* n_points,
                             size_t* n_uncolored);
+/* hsk_extract_mesh_cubes' surface as an indexed mesh, welded on the device by edge identity.
+ *   faces: one per triangle of hsk_extract_mesh_cubes on the same context, in its order (cube voxel order, then table order),
+ *     corners in the soup's order: vertices[faces] equals the soup bit for bit, and the winding (normals towards free space) stays.
+ *   vertices: one per cube edge that a face uses -- an edge that is cut (one end < 0, the other >= 0) and lies on at least one
+ *     valid cube (all 8 weights non-zero) that this context emits.  Ordered by the edge's lower corner in voxel order (plane, row,
+ *     x), then by axis (x, y, z); at pa + (Fa / (Fa - Fb)) (pb - pa), a the lower corner (the soup's arithmetic).  Distinct edges
+ *     stay distinct vertices even where their coordinates coincide: on a grid point whose stored TSDF is exactly 0, and (at fine
+ *     cells, 1024^3) where an extreme ratio of the two TSDF values moves a vertex by less than half an ulp from its end.  So
+ *     *n_vertices >= hsk_weld_triangles' count on the soup, equal when neither occurs.
+ *   normals (3 floats per vertex, may be NULL): hsk_extract_cloud_attrs' rule at the vertex -- central differences of the
+ *     trilinear TSDF, one cell either side, scaled by 1 / |n|; NaN x 3 outside the (1, dims - 2) interior.
+ *   rgb (3 bytes per vertex, may be NULL): hsk_extract_cloud_attrs' selection rule on the edge's two voxels -- the smaller |tsdf|
+ *     (the lower corner on a tie), the other when that has colour weight 0, (0, 0, 0) and one count in *n_uncolored when both
+ *     have.  Needs hsk_enable_color (HSK_ERR_STATE), so not on the slabs of a group.  n_uncolored may be NULL (0 without rgb).
+ *   protocol: with every array NULL only the counts (the count pass is kept for the next call while the volume is unchanged).
+ *     Any subset of the arrays may be asked for; each is written whole or not at all: a cap below its total (cap_vertices for
+ *     vertices, normals and rgb) returns HSK_ERR_ARG with the counts set and nothing written.  More than INT32_MAX vertices:
+ *     HSK_ERR_STATE.  No flush of the deferred weights is needed (as for the other products).  On a slab of a group: the cubes
+ *     hsk_extract_mesh_cubes covers there; vertices on a plane two slabs share appear in both slabs' meshes.
+ *   memory, made on first use and kept: R = Y x (planes of the emitted cubes + 1) grid rows, S = ceil(X / 64) segments per row:
+ *     24 S + 2 S + 12 B per row (edge bits: 3 bits per voxel; per-segment bases; count and offset) + 8 B per 1024 rows + at
+ *     most 1.3 KiB of alignment; at 512^3 55.0 MiB.  The arrays come back through the product buffer (12 B per vertex for each of vertices and normals,
+ *     3 for rgb, 12 per face; it only grows), the faces' row tables are the ones every product shares. */
+int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices /* 3 per vertex */, float* normals /* 3 per vertex, may be NULL */,
+                             uint8_t* rgb /* 3 per vertex, may be NULL */, size_t cap_vertices, size_t* n_vertices,
+                             int32_t* faces /* 3 per face */, size_t cap_faces, size_t* n_faces, size_t* n_uncolored);
 
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
@@ -332,6 +358,13 @@ int hsk_write_pcd_xyz(const char* path, const float* xyz, size_t n_points);
 int hsk_write_ply_mesh(const char* path, const float* tri_xyz, size_t n_triangles, size_t* n_vertices_out, size_t* n_faces_out);
 /* the same welding without a file: indices[3 * n_triangles] into vertices (cap_vertices x 3); degenerate triangles keep index triples with repeats */
 int hsk_weld_triangles(const float* tri_xyz, size_t n_triangles, float* vertices, size_t cap_vertices, size_t* n_vertices, int32_t* indices);
+/* binary little-endian PLY 1.0 of an indexed mesh (hsk_extract_mesh_indexed): element vertex with float x y z, then float nx ny
+ * nz when normals != NULL, then uchar red green blue when rgb != NULL, interleaved per vertex without padding (NaN normal
+ * components written as 0); element face with property list uchar int vertex_indices, 13 B per face, every face as given.
+ * The property names are the ones Meshlab reads; whether plyxform carries the normals through is unverified.  An index
+ * outside [0, n_vertices): HSK_ERR_ARG and no file; an I/O failure: HSK_ERR_STATE; an empty mesh is valid. */
+int hsk_write_ply_indexed(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
+                          const int32_t* faces, size_t n_faces);
 int hsk_voxel_downsample(const float* xyz, size_t n, float leaf_m, float* out, size_t cap, size_t* n_out);
 /* the same leaves, xyz bit-identical to hsk_voxel_downsample's and in the same order, with the rounded mean colour and the
  * renormalised mean of the non-NaN normals of each leaf (NaN x 3 when it has none).  rgb / normals (inputs) may be NULL,
@@ -357,6 +390,9 @@ int hsk_write_planes_txt(const char* path, const float* planes_abcd, int n_plane
 int hsk_write_xf(const char* path, const float m[16]);
 int hsk_read_xf(const char* path, float m[16]);              /* accepts both layouts */
 int hsk_transform_cloud(const float* xyz, size_t n, const float m[16], float* out /* may alias xyz */);
+/* normals by the rotation part of the same matrix (no translation, no renormalisation; hsk_transform_cloud's operation order
+ * without the m[3] / m[7] / m[11] term; NaN stays NaN): a room's mesh moved by its .xf keeps correct normals */
+int hsk_transform_normals(const float* n, size_t count, const float m[16], float* out /* may alias n */);
 
 /* Recorded depth streams ("HSKD" raw container; frames in the layout of takeDepthSnapshot, HoniHelper.hs:20-36). */
 typedef struct hsk_depth_stream hsk_depth_stream;

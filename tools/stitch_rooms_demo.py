@@ -7,6 +7,10 @@ loads, run the host-side stitching chain on them and export one .xf per room plu
 This is BASELINE configs[0] (two rooms -> cuboid fit + translation optimiser -> export) fed by configs[2]-style
 scans; with --rooms 4 it is the single-GPU form of configs[4].  The "user" who clicks corners in HouseScan is
 emulated: of the suggested corners, the 8 nearest to the true room corners are accepted.
+
+--indexed-mesh: each room's mesh comes off the GPU indexed, with normals (hsk_extract_mesh_indexed), is written as
+<room_dir>/mesh.ply, and house_mesh.ply concatenates the rooms' meshes moved by their .xf (positions by transform_cloud,
+normals by transform_normals, faces offset by each room's vertex base) -- no host weld.
 """
 import argparse
 import json
@@ -20,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False):
+def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=False):
     """the three-turn scan inside room `variant`; returns (cloud, worst translation error [m], lost frames, fps).
     (Round 6: the frames go through the pipelined pair and the clock covers the tracker only -- the poses and the errors are
     computed outside it; the synchronous call with a pose and a norm per frame inside the loop made "2050 frames/s" of a
@@ -40,7 +44,10 @@ def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False):
     lost = sum(1 for k, (_, ok) in enumerate(got) if k > 0 and not ok)   # frame 0 only seeds the model
     worst = max(float(np.linalg.norm(pose[:3, 3] - gt[:3, 3])) for (pose, _), gt in zip(got, gts))
     cloud, total = trk.extract_cloud()
-    mesh = trk.extract_mesh(cubes=True)[0] if with_mesh else None   # marching cubes: the form upstream's .ply export has
+    if with_mesh and indexed:
+        mesh = trk.extract_mesh_indexed(normals=True, rgb=False)[:3]   # (vertices, faces, normals)
+    else:
+        mesh = trk.extract_mesh(cubes=True)[0] if with_mesh else None   # marching cubes: the form upstream's .ply export has
     trk.close()
     if with_mesh:
         return cloud, worst, lost, len(depth) / dt, mesh
@@ -97,6 +104,7 @@ def main():
     ap.add_argument("--volume", type=int, default=256)
     ap.add_argument("--frames", type=int, default=720, help="frames of the three-turn room trajectory")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "stitch"))
+    ap.add_argument("--indexed-mesh", action="store_true", help="rooms' meshes indexed with normals: <room_dir>/mesh.ply, no host weld")
     args = ap.parse_args()
 
     import housescan_amd as hsk
@@ -107,10 +115,12 @@ def main():
     report = {"rooms": []}
     dirs, variants, meshes = [], list(range(args.rooms)), []
     for v in variants:
-        cloud, worst, lost, fps, mesh = scan_room(hsk, v, args.volume, args.frames, with_mesh=True)
+        cloud, worst, lost, fps, mesh = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh)
         meshes.append(mesh)
         d = os.path.join(args.out, f"room{v}", "walls")
         planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, dist_thresh=0.025, min_fraction=0.03)
+        if args.indexed_mesh:
+            P.write_ply_indexed(os.path.join(d, "mesh.ply"), mesh[0], mesh[1], normals=mesh[2])
         print(f"room{v}: {len(cloud)} points, {n_down} downsampled, {len(planes)} planes, worst pose error {worst * 1000:.1f} mm, "
               f"lost {lost}, {fps:.0f} frames/s incl. upload")
         report["rooms"].append({"variant": v, "points": int(len(cloud)), "planes": int(len(planes)), "worst_pose_error_mm": worst * 1000,
@@ -129,8 +139,19 @@ def main():
     merged = np.concatenate(merged)
     H.write_ply_points(os.path.join(args.out, "house.ply"), merged)
     # the README's last step (plyxform on KinFu's mesh): every room's mesh moved by its .xf, one welded .ply
-    moved = [P.transform_cloud(m.reshape(-1, 3), hs.room_projection(rid)).reshape(-1, 3, 3) for m, rid in zip(meshes, rooms)]
-    nv, nf = P.write_ply_mesh(os.path.join(args.out, "house_mesh.ply"), np.concatenate(moved))
+    if args.indexed_mesh:
+        vs, fs, ns, base = [], [], [], 0
+        for (v, f, nrm), rid in zip(meshes, rooms):
+            M = hs.room_projection(rid)
+            vs.append(P.transform_cloud(v, M))
+            ns.append(P.transform_normals(nrm, M))
+            fs.append(f + base)
+            base += len(v)
+        P.write_ply_indexed(os.path.join(args.out, "house_mesh.ply"), np.concatenate(vs), np.concatenate(fs), normals=np.concatenate(ns))
+        nv, nf = base, sum(len(f) for f in fs)
+    else:
+        moved = [P.transform_cloud(m.reshape(-1, 3), hs.room_projection(rid)).reshape(-1, 3, 3) for m, rid in zip(meshes, rooms)]
+        nv, nf = P.write_ply_mesh(os.path.join(args.out, "house_mesh.ply"), np.concatenate(moved))
     report["house_mesh"] = {"vertices": nv, "faces": nf}
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
