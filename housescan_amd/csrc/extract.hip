@@ -3,13 +3,38 @@
 #pragma clang fp contract(off)
 #include "hsk_dev.h"
 #include "hsk_launch.h"
+#include <type_traits>
+
+// inclusive scan and sum of v over the wave's 64 lanes
+static __device__ __forceinline__ int wave_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+static __device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+static __device__ __forceinline__ void store3(float* __restrict__ dst, float a, float b, float c) {
+  dst[0] = a;
+  dst[1] = b;
+  dst[2] = c;
+}
 
 // ------------------------------------------------------------------------------------------------------
 // extractCloud (A.7): a wave per (y,z) row; pass 1 counts, an exclusive scan orders the rows, pass 2 writes
 // the points in voxel order (deterministic, identical to the sequential restatement).
 // ------------------------------------------------------------------------------------------------------
+// the zero crossings from voxel (x, y, z) to its +x, +y, +z neighbours: their count, their points when pts is given, and
+// their axes when axes is (two bits each, the first crossing lowest)
 static __device__ __forceinline__ int crossing_count(const short2* __restrict__ vol, const VolParams& vp, int x, int y,
-                                                     int z, float* pts /* up to 9 floats or null */) {
+                                                     int z, float* pts /* up to 9 floats or null */, unsigned* axes = nullptr) {
+  if (axes) *axes = 0u;
   const short2 c = vol[hsk_vox_index(vp, x, y, z - vp.zs0)];
   if (c.y == 0 || c.x == HSK_DIVISOR) return 0;
   const float F = (float)c.x / 32767.0f;
@@ -35,6 +60,7 @@ static __device__ __forceinline__ int crossing_count(const short2* __restrict__ 
       pts[3 * n + 1] = k == 1 ? pk : V1;
       pts[3 * n + 2] = k == 2 ? pk : V2;
     }
+    if (axes) *axes |= (unsigned)k << (2 * n);
     ++n;
   }
   return n;
@@ -74,51 +100,57 @@ static __device__ __forceinline__ bool segment_may_hold_negative(unsigned long l
   return (row_mask & seg) != 0ull;
 }
 
+// The sweep every product shares: a wave per row (y, z) -- ny rows per plane, nplanes planes from zo0 -- and a lane per cell
+// x < nx, 64 cells at a time.  count(x, y, z, zr) -> the items of the cell (zr = z - zo0).  The count pass (!WRITE) leaves
+// the rows' totals in row_count; the write pass takes a row's first slot from row_offset (launch_scan_rows) and calls
+// write(x, y, z, zr, n, at) for a cell with n > 0 items: they go to slots at .. at + n - 1, in voxel order.  What a cell
+// computes in count and needs again in write, the callers' lambdas keep in a captured local.
+template <bool WRITE, class RowCount, class Count, class Write>
+static __device__ __forceinline__ void sweep_row(const VolParams& vp, const unsigned* __restrict__ flags, int ny, int nplanes, int nx,
+                                                 RowCount* __restrict__ row_count, const unsigned long long* __restrict__ row_offset,
+                                                 Count count, Write write) {
+  const int lane = threadIdx.x & 63;
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (row >= ny * nplanes) return;
+  const int y = row % ny, zr = row / ny, z = vp.zo0 + zr;
+  if (WRITE && row_count[row] == 0u) return;  // (the count pass found the row empty)
+  unsigned long long base = WRITE ? row_offset[row] : 0;  // (asked for before the mask's loads, used after them)
+  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
+  if (row_mask == 0ull) {
+    if constexpr (!WRITE)
+      if (lane == 0) row_count[row] = 0u;
+    return;
+  }
+  unsigned total = 0;
+  for (int xb = 0; xb < nx; xb += 64) {
+    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, nx - 1))) continue;
+    const int x = xb + lane;
+    const int n = x < nx ? count(x, y, z, zr) : 0;
+    if constexpr (WRITE) {
+      const int scan = wave_scan(n);
+      if (n) write(x, y, z, zr, n, base + (unsigned long long)(scan - n));
+      base += __shfl(scan, 63, 64);
+    } else {
+      total += wave_sum((unsigned)n);
+    }
+  }
+  if constexpr (!WRITE)
+    if (lane == 0) row_count[row] = total;
+}
+
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_extract(const short2* __restrict__ vol, VolParams vp,
                                                  unsigned* __restrict__ row_count,
                                                  const unsigned long long* __restrict__ row_offset,
                                                  float* __restrict__ xyz, unsigned long long cap, const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int nrows = vp.Y * (vp.zo1 - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % vp.Y, z = vp.zo0 + row / vp.Y;
-  if (WRITE && row_count[row] == 0u) return;  // (the count pass found the row empty)
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) {
-    if (!WRITE && lane == 0) row_count[row] = 0u;
-    return;
-  }
-  unsigned long long base = WRITE ? row_offset[row] : 0;
-  unsigned total = 0;
-  for (int xb = 0; xb < vp.X; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 1))) continue;
-    const int x = xb + lane;
-    float pts[9];
-    int n = 0;
-    if (x < vp.X) n = crossing_count(vol, vp, x, y, z, WRITE ? pts : nullptr);
-    // inclusive wave scan of n
-    int scan = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(scan, o, 64);
-      if (lane >= o) scan += v;
-    }
-    const int wave_total = __shfl(scan, 63, 64);
-    if (WRITE) {
-      unsigned long long at = base + (unsigned long long)(scan - n);
-      for (int q = 0; q < n; ++q, ++at)
-        if (at < cap) {
-          xyz[3 * at] = pts[3 * q];
-          xyz[3 * at + 1] = pts[3 * q + 1];
-          xyz[3 * at + 2] = pts[3 * q + 2];
-        }
-      base += wave_total;
-    }
-    total += wave_total;
-  }
-  if (!WRITE && lane == 0) row_count[row] = total;
+  float pts[9];
+  sweep_row<WRITE>(
+      vp, flags, vp.Y, vp.zo1 - vp.zo0, vp.X, row_count, row_offset,
+      [&](int x, int y, int z, int) { return crossing_count(vol, vp, x, y, z, WRITE ? pts : nullptr); },
+      [&](int, int, int, int, int n, unsigned long long at) {
+        for (int q = 0; q < n; ++q, ++at)
+          if (at < cap) store3(xyz + 3 * at, pts[3 * q], pts[3 * q + 1], pts[3 * q + 2]);
+      });
 }
 
 // exclusive scan of the row counts (up to a few million rows), three small launches: per block of 1024 rows its sum; the
@@ -377,95 +409,121 @@ int hsk_build_cube_table(CubeTable* ct) {
   return worst;  // 5: the table's row length (checked by the caller)
 }
 
-// triangles of the cube at (x, y, z); when WRITE, stores 9 floats per triangle at tri + 9 * (at + i) while at + i < cap
-template <bool WRITE>
-static __device__ int cube_triangles(const short2* __restrict__ vol, const VolParams& vp, const TetTable& tt, int x, int y, int z,
-                                     float* __restrict__ tri, unsigned long long at, unsigned long long cap) {
+// the cube at (x, y, z): its 8 voxels and the inside mask (a corner is inside when its TSDF is negative) -- 0 when a corner
+// has never been observed or the level set does not cut the cube
+struct Cube {
   short2 v[8];
+  unsigned m8;
+};
+static __device__ __forceinline__ Cube load_cube(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
+  Cube cb;
   bool ok = true;
-  unsigned m8 = 0;
+  cb.m8 = 0;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
-    v[c] = vol[hsk_vox_index(vp, x + (c & 1), y + ((c >> 1) & 1), z + (c >> 2) - vp.zs0)];
-    ok = ok && v[c].y != 0;
-    m8 |= (v[c].x < 0 ? 1u : 0u) << c;
+    cb.v[c] = vol[hsk_vox_index(vp, x + (c & 1), y + ((c >> 1) & 1), z + (c >> 2) - vp.zs0)];
+    ok = ok && cb.v[c].y != 0;
+    cb.m8 |= (cb.v[c].x < 0 ? 1u : 0u) << c;
   }
-  if (!ok || m8 == 0u || m8 == 255u) return 0;
+  if (!ok || cb.m8 == 255u) cb.m8 = 0u;
+  return cb;
+}
+// the vertex of the edge from voxel ga (TSDF fa; the LOWER corner) to voxel gb (TSDF fb)
+static __device__ __forceinline__ void edge_vertex(const VolParams& vp, short fa, short fb, const int* ga, const int* gb, float* p) {
+  const float Fa = (float)fa / 32767.0f, Fb = (float)fb / 32767.0f;
+  const float w = Fa / (Fa - Fb);
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    const float pa = ((float)ga[ax] + 0.5f) * vp.cell[ax];
+    const float pb = ((float)gb[ax] + 0.5f) * vp.cell[ax];
+    p[ax] = pa + w * (pb - pa);
+  }
+}
+// a triangle of the cube at (x, y, z) from its three edge codes (lower corner | upper corner << 4): 9 floats
+static __device__ __forceinline__ void write_triangle(const VolParams& vp, const Cube& cb, int x, int y, int z, const unsigned char* codes,
+                                                      float* __restrict__ out) {
+  for (int q = 0; q < 3; ++q) {
+    const unsigned code = codes[q];
+    const int a = (int)(code & 15u), b = (int)(code >> 4);
+    // dynamic corner selection without a scratch array
+    short fa = 0, fb = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      fa = c == a ? cb.v[c].x : fa;
+      fb = c == b ? cb.v[c].x : fb;
+    }
+    const int ga[3] = {x + (a & 1), y + ((a >> 1) & 1), z + (a >> 2)};
+    const int gb[3] = {x + (b & 1), y + ((b >> 1) & 1), z + (b >> 2)};
+    float p[3];
+    edge_vertex(vp, fa, fb, ga, gb, p);
+    store3(out + 3 * q, p[0], p[1], p[2]);
+  }
+}
+
+// triangles of the cube cb at (x, y, z); when WRITE, stores 9 floats per triangle at tri + 9 * (at + i) while at + i < cap
+// ... by marching tetrahedra
+template <bool WRITE>
+static __device__ int cube_triangles(const VolParams& vp, const TetTable& tt, const Cube& cb, int x, int y, int z, float* __restrict__ tri,
+                                     unsigned long long at, unsigned long long cap) {
+  if (cb.m8 == 0u) return 0;
   const int tet[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
   int n = 0;
   for (int t = 0; t < 6; ++t) {
-    const unsigned m = ((m8 >> tet[t][0]) & 1u) | (((m8 >> tet[t][1]) & 1u) << 1) | (((m8 >> tet[t][2]) & 1u) << 2) |
-                       (((m8 >> tet[t][3]) & 1u) << 3);
+    const unsigned m = ((cb.m8 >> tet[t][0]) & 1u) | (((cb.m8 >> tet[t][1]) & 1u) << 1) | (((cb.m8 >> tet[t][2]) & 1u) << 2) |
+                       (((cb.m8 >> tet[t][3]) & 1u) << 3);
     const int nt = tt.ntri[t][m];
     if (WRITE) {
       for (int k = 0; k < nt; ++k) {
         const unsigned long long slot = at + (unsigned long long)(n + k);
-        if (slot >= cap) continue;
-        for (int q = 0; q < 3; ++q) {
-          const unsigned code = tt.edge[t][m][k][q];
-          const int a = (int)(code & 15u), b = (int)(code >> 4);
-          // dynamic corner selection without a scratch array
-          short fa = 0, fb = 0;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            fa = c == a ? v[c].x : fa;
-            fb = c == b ? v[c].x : fb;
-          }
-          const float Fa = (float)fa / 32767.0f, Fb = (float)fb / 32767.0f;
-          const float w = Fa / (Fa - Fb);
-          const int ga[3] = {x + (a & 1), y + ((a >> 1) & 1), z + (a >> 2)};
-          const int gb[3] = {x + (b & 1), y + ((b >> 1) & 1), z + (b >> 2)};
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) {
-            const float pa = ((float)ga[ax] + 0.5f) * vp.cell[ax];
-            const float pb = ((float)gb[ax] + 0.5f) * vp.cell[ax];
-            tri[9 * slot + 3 * q + ax] = pa + w * (pb - pa);
-          }
-        }
+        if (slot < cap) write_triangle(vp, cb, x, y, z, tt.edge[t][m][k], tri + 9 * slot);
       }
     }
     n += nt;
   }
   return n;
 }
+// ... and by marching cubes: straight from the table (in device memory: 4 KiB)
+template <bool WRITE>
+static __device__ int cube_triangles(const VolParams& vp, const CubeTable* __restrict__ ct, const Cube& cb, int x, int y, int z,
+                                     float* __restrict__ tri, unsigned long long at, unsigned long long cap) {
+  if (cb.m8 == 0u) return 0;
+  const int nt = ct->ntri[cb.m8];
+  if (WRITE) {
+    for (int k = 0; k < nt; ++k) {
+      const unsigned long long slot = at + (unsigned long long)k;
+      if (slot < cap) write_triangle(vp, cb, x, y, z, ct->edge[cb.m8][k], tri + 9 * slot);
+    }
+  }
+  return nt;
+}
 
+// a row of cubes of either soup: Table is TetTable or const CubeTable*
+template <bool WRITE, class Table>
+static __device__ __forceinline__ void soup_row(const short2* __restrict__ vol, const VolParams& vp, const Table& table,
+                                                unsigned* __restrict__ row_count, const unsigned long long* __restrict__ row_offset,
+                                                float* __restrict__ tri, unsigned long long cap, int z_end, const unsigned* __restrict__ flags) {
+  Cube cb;
+  sweep_row<WRITE>(
+      vp, flags, vp.Y - 1, z_end - vp.zo0, vp.X - 1, row_count, row_offset,
+      [&](int x, int y, int z, int) {
+        cb = load_cube(vol, vp, x, y, z);
+        return cube_triangles<false>(vp, table, cb, x, y, z, nullptr, 0, 0);
+      },
+      [&](int x, int y, int z, int, int, unsigned long long at) { cube_triangles<true>(vp, table, cb, x, y, z, tri, at, cap); });
+}
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_extract_mesh(const short2* __restrict__ vol, VolParams vp, TetTable tt,
                                                       unsigned* __restrict__ row_count,
                                                       const unsigned long long* __restrict__ row_offset,
                                                       float* __restrict__ tri, unsigned long long cap, int z_end, const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int ny = vp.Y - 1;
-  const int nrows = ny * (z_end - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % ny, z = vp.zo0 + row / ny;
-  if (WRITE && row_count[row] == 0u) return;  // (the count pass found the row empty)
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) {
-    if (!WRITE && lane == 0) row_count[row] = 0u;
-    return;
-  }
-  unsigned long long base = WRITE ? row_offset[row] : 0;
-  unsigned total = 0;
-  for (int xb = 0; xb < vp.X - 1; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
-    const int x = xb + lane;
-    const int n = x < vp.X - 1 ? cube_triangles<false>(vol, vp, tt, x, y, z, nullptr, 0, 0) : 0;
-    int scan = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(scan, o, 64);
-      if (lane >= o) scan += u;
-    }
-    const int wave_total = __shfl(scan, 63, 64);
-    if (WRITE) {
-      if (n) cube_triangles<true>(vol, vp, tt, x, y, z, tri, base + (unsigned long long)(scan - n), cap);
-      base += wave_total;
-    }
-    total += wave_total;
-  }
-  if (!WRITE && lane == 0) row_count[row] = total;
+  soup_row<WRITE>(vol, vp, tt, row_count, row_offset, tri, cap, z_end, flags);
+}
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_extract_mesh_mc(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
+                                                         unsigned* __restrict__ row_count,
+                                                         const unsigned long long* __restrict__ row_offset,
+                                                         float* __restrict__ tri, unsigned long long cap, int z_end, const unsigned* __restrict__ flags) {
+  soup_row<WRITE>(vol, vp, ct, row_count, row_offset, tri, cap, z_end, flags);
 }
 
 // cubes whose base plane this context owns and whose upper plane is stored
@@ -476,140 +534,50 @@ int hsk_mesh_z_end(const VolParams& vp) {
   return z_end > vp.zo0 ? z_end : vp.zo0;
 }
 
-void launch_extract_mesh(hipStream_t s, const void* vol, const VolParams& vp, const TetTable& tt, unsigned* row_count,
-                         unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags) {
-  const int z_end = hsk_mesh_z_end(vp);
-  const int nrows = (vp.Y - 1) * (z_end - vp.zo0);
+// Both passes of a product over nrows rows, a block per four: without an output buffer the count pass -- launch(false_type,
+// grid) and the rows' scan, whose total is zeroed when there are no rows -- and with one the write pass, launch(true_type, grid).
+template <class Launch>
+static void launch_two_pass(hipStream_t s, int nrows, unsigned* row_count, unsigned long long* row_offset, unsigned long long* total,
+                            bool write, Launch launch) {
   if (nrows <= 0) {
-    if (pass == 0) (void)hipMemsetAsync(total, 0, 8, s);
-    return;
-  }
-  dim3 block(256), grid((nrows + 3) / 4);
-  if (pass == 0) {
-    hipLaunchKernelGGL(k_extract_mesh<false>, grid, block, 0, s, (const short2*)vol, vp, tt, row_count, row_offset, tri, cap, z_end, flags);
-    launch_scan_rows(s, row_count, row_offset, nrows, total);
-  } else {
-    hipLaunchKernelGGL(k_extract_mesh<true>, grid, block, 0, s, (const short2*)vol, vp, tt, row_count, row_offset, tri, cap, z_end, flags);
-  }
-}
-
-// ... and the marching-cubes form: the cube's triangles straight from the table (in device memory: 4 KiB)
-template <bool WRITE>
-static __device__ int cube_triangles_mc(const short2* __restrict__ vol, const VolParams& vp, const CubeTable* __restrict__ ct, int x, int y,
-                                        int z, float* __restrict__ tri, unsigned long long at, unsigned long long cap) {
-  short2 v[8];
-  bool ok = true;
-  unsigned m8 = 0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    v[c] = vol[hsk_vox_index(vp, x + (c & 1), y + ((c >> 1) & 1), z + (c >> 2) - vp.zs0)];
-    ok = ok && v[c].y != 0;
-    m8 |= (v[c].x < 0 ? 1u : 0u) << c;
-  }
-  if (!ok || m8 == 0u || m8 == 255u) return 0;
-  const int nt = ct->ntri[m8];
-  if (WRITE) {
-    for (int k = 0; k < nt; ++k) {
-      const unsigned long long slot = at + (unsigned long long)k;
-      if (slot >= cap) continue;
-      for (int q = 0; q < 3; ++q) {
-        const unsigned code = ct->edge[m8][k][q];
-        const int a = (int)(code & 15u), b = (int)(code >> 4);
-        short fa = 0, fb = 0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          fa = c == a ? v[c].x : fa;
-          fb = c == b ? v[c].x : fb;
-        }
-        const float Fa = (float)fa / 32767.0f, Fb = (float)fb / 32767.0f;
-        const float w = Fa / (Fa - Fb);
-        const int ga[3] = {x + (a & 1), y + ((a >> 1) & 1), z + (a >> 2)};
-        const int gb[3] = {x + (b & 1), y + ((b >> 1) & 1), z + (b >> 2)};
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-          const float pa = ((float)ga[ax] + 0.5f) * vp.cell[ax];
-          const float pb = ((float)gb[ax] + 0.5f) * vp.cell[ax];
-          tri[9 * slot + 3 * q + ax] = pa + w * (pb - pa);
-        }
-      }
-    }
-  }
-  return nt;
-}
-
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_extract_mesh_mc(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
-                                                         unsigned* __restrict__ row_count,
-                                                         const unsigned long long* __restrict__ row_offset,
-                                                         float* __restrict__ tri, unsigned long long cap, int z_end, const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int ny = vp.Y - 1;
-  const int nrows = ny * (z_end - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % ny, z = vp.zo0 + row / ny;
-  if (WRITE && row_count[row] == 0u) return;  // (the count pass found the row empty)
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) {
-    if (!WRITE && lane == 0) row_count[row] = 0u;
-    return;
-  }
-  unsigned long long base = WRITE ? row_offset[row] : 0;
-  unsigned total = 0;
-  for (int xb = 0; xb < vp.X - 1; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
-    const int x = xb + lane;
-    const int n = x < vp.X - 1 ? cube_triangles_mc<false>(vol, vp, ct, x, y, z, nullptr, 0, 0) : 0;
-    int scan = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(scan, o, 64);
-      if (lane >= o) scan += u;
-    }
-    const int wave_total = __shfl(scan, 63, 64);
-    if (WRITE) {
-      if (n) cube_triangles_mc<true>(vol, vp, ct, x, y, z, tri, base + (unsigned long long)(scan - n), cap);
-      base += wave_total;
-    }
-    total += wave_total;
-  }
-  if (!WRITE && lane == 0) row_count[row] = total;
-}
-
-void launch_extract_mesh_mc(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
-                            unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags) {
-  const int z_end = hsk_mesh_z_end(vp);
-  const int nrows = (vp.Y - 1) * (z_end - vp.zo0);
-  if (nrows <= 0) {
-    if (pass == 0) (void)hipMemsetAsync(total, 0, 8, s);
+    if (!write) (void)hipMemsetAsync(total, 0, 8, s);
     return;
   }
   const dim3 grid((unsigned)((nrows + 3) / 4));
-  if (pass == 0) {
-    hipLaunchKernelGGL(k_extract_mesh_mc<false>, grid, dim3(256), 0, s, (const short2*)vol, vp, ct_dev, row_count, (const unsigned long long*)nullptr,
-                       (float*)nullptr, 0ull, z_end, flags);
-    launch_scan_rows(s, row_count, row_offset, nrows, total);
+  if (write) {
+    launch(std::true_type{}, grid);
   } else {
-    hipLaunchKernelGGL(k_extract_mesh_mc<true>, grid, dim3(256), 0, s, (const short2*)vol, vp, ct_dev, row_count, row_offset, tri, cap, z_end, flags);
+    launch(std::false_type{}, grid);
+    launch_scan_rows(s, row_count, row_offset, nrows, total);
   }
 }
-
-void launch_extract(hipStream_t s, const void* vol, const VolParams& vp, unsigned* row_count,
-                    unsigned long long* row_offset, unsigned long long* total, float* xyz, unsigned long long cap,
-                    int pass, const unsigned* flags) {
-  const int nrows = vp.Y * (vp.zo1 - vp.zo0);
-  dim3 block(256), grid((nrows + 3) / 4);
-  if (pass == 0) {
-    hipLaunchKernelGGL(k_extract<false>, grid, block, 0, s, (const short2*)vol, vp, row_count, row_offset, xyz, cap, flags);
-    launch_scan_rows(s, row_count, row_offset, nrows, total);
-  } else {
-    hipLaunchKernelGGL(k_extract<true>, grid, block, 0, s, (const short2*)vol, vp, row_count, row_offset, xyz, cap, flags);
-  }
+void launch_extract(hipStream_t s, const void* vol, const VolParams& vp, unsigned* row_count, unsigned long long* row_offset,
+                    unsigned long long* total, float* xyz, unsigned long long cap, const unsigned* flags) {
+  launch_two_pass(s, vp.Y * (vp.zo1 - vp.zo0), row_count, row_offset, total, xyz != nullptr, [&](auto write, dim3 grid) {
+    hipLaunchKernelGGL(k_extract<decltype(write)::value>, grid, dim3(256), 0, s, (const short2*)vol, vp, row_count,
+                       (const unsigned long long*)row_offset, xyz, cap, flags);
+  });
+}
+void launch_extract_mesh(hipStream_t s, const void* vol, const VolParams& vp, const TetTable& tt, unsigned* row_count,
+                         unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, const unsigned* flags) {
+  const int z_end = hsk_mesh_z_end(vp);
+  launch_two_pass(s, (vp.Y - 1) * (z_end - vp.zo0), row_count, row_offset, total, tri != nullptr, [&](auto write, dim3 grid) {
+    hipLaunchKernelGGL(k_extract_mesh<decltype(write)::value>, grid, dim3(256), 0, s, (const short2*)vol, vp, tt, row_count,
+                       (const unsigned long long*)row_offset, tri, cap, z_end, flags);
+  });
+}
+void launch_extract_mesh_mc(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
+                            unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, const unsigned* flags) {
+  const int z_end = hsk_mesh_z_end(vp);
+  launch_two_pass(s, (vp.Y - 1) * (z_end - vp.zo0), row_count, row_offset, total, tri != nullptr, [&](auto write, dim3 grid) {
+    hipLaunchKernelGGL(k_extract_mesh_mc<decltype(write)::value>, grid, dim3(256), 0, s, (const short2*)vol, vp, ct_dev, row_count,
+                       (const unsigned long long*)row_offset, tri, cap, z_end, flags);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------
-// The cloud with normals and colour (hsk_extract_cloud_attrs): the write pass of the cloud again, in a kernel of its own
-// (k_extract is untouched); the points, their count and order come from the same crossing_count, so xyz is bit-identical.
+// The cloud with normals and colour (hsk_extract_cloud_attrs): the write pass of the cloud again, in a kernel of its own;
+// the points, their count and order come from k_extract's sweep and crossing_count, so xyz is bit-identical.
 //   normal: the raycast's -- central differences of the trilinear TSDF one cell either side, scaled by 1 / |n| -- where
 //           floor(p / cell) lies in (1, dims - 2) on every axis (tests/np_twin.py: the raycast's `deep`), NaN elsewhere
 //   colour: of the crossing's voxel with the smaller |tsdf| (the first on a tie), of the other when that one has colour
@@ -676,22 +644,29 @@ static __device__ __forceinline__ unsigned attr_color(const short2* __restrict__
   }
   return cw;
 }
-// the axes of the crossings crossing_count finds at (x, y, z), in its order (the same tests)
-static __device__ __forceinline__ int crossing_axes(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z, int* axes) {
-  const short2 c = vol[hsk_vox_index(vp, x, y, z - vp.zs0)];
-  if (c.y == 0 || c.x == HSK_DIVISOR) return 0;
-  int n = 0;
-  for (int k = 0; k < 3; ++k) {
-    const int g = k == 0 ? x : (k == 1 ? y : z);
-    const int dim = k == 0 ? vp.X : (k == 1 ? vp.Y : vp.Z);
-    if (g + 1 >= dim) continue;
-    if (k == 2 && (z + 1 - vp.zs0) >= vp.nzs) continue;
-    const short2 nb = vol[hsk_vox_index(vp, x + (k == 0 ? 1 : 0), y + (k == 1 ? 1 : 0), z - vp.zs0 + (k == 2 ? 1 : 0))];
-    if (nb.y == 0 || nb.x == HSK_DIVISOR) continue;
-    if (!((c.x > 0 && nb.x < 0) || (c.x < 0 && nb.x > 0))) continue;
-    axes[n++] = k;
+// the attributes of item `at`, a point p on the edge between voxel (x, y, zz) and its neighbour (bx, by, bzz) (stored planes):
+// the normal rule at p, the colour rule on the edge (either array may be null)
+static __device__ __forceinline__ void write_attrs(const short2* __restrict__ vol, const unsigned* __restrict__ colv, const VolParams& vp,
+                                                   unsigned long long at, const float* p, int x, int y, int zz, int bx, int by, int bzz,
+                                                   float* __restrict__ normals, unsigned char* __restrict__ rgb, unsigned* uncol) {
+  if (normals) {
+    float nx, ny, nz;
+    attr_normal(vol, vp, p[0], p[1], p[2], &nx, &ny, &nz);
+    store3(normals + 3 * at, nx, ny, nz);
   }
-  return n;
+  if (rgb) {
+    const unsigned cw = attr_color(vol, colv, vp, x, y, zz, bx, by, bzz, uncol);
+    rgb[3 * at] = (unsigned char)(cw & 255u);
+    rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
+    rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
+  }
+}
+// ... and, once per wave, the lanes' uncoloured items into the product's counter
+static __device__ __forceinline__ void add_uncolored(unsigned uncol, const unsigned char* rgb, unsigned long long* __restrict__ n_uncolored) {
+  if (rgb && n_uncolored) {
+    const unsigned sum = wave_sum(uncol);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
+  }
 }
 
 __global__ __launch_bounds__(256) void k_extract_attrs(const short2* __restrict__ vol, const unsigned* __restrict__ colv, VolParams vp,
@@ -700,68 +675,24 @@ __global__ __launch_bounds__(256) void k_extract_attrs(const short2* __restrict_
                                                        float* __restrict__ normals, unsigned char* __restrict__ rgb,
                                                        unsigned long long cap, unsigned long long* __restrict__ n_uncolored,
                                                        const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int nrows = vp.Y * (vp.zo1 - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % vp.Y, z = vp.zo0 + row / vp.Y;
-  if (row_count[row] == 0u) return;  // (the count pass found the row empty)
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) return;
-  unsigned long long base = row_offset[row];
-  unsigned uncol = 0;
-  for (int xb = 0; xb < vp.X; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 1))) continue;
-    const int x = xb + lane;
-    float pts[9];
-    int axes[3];
-    int n = 0;
-    if (x < vp.X) {
-      n = crossing_count(vol, vp, x, y, z, pts);
-      (void)crossing_axes(vol, vp, x, y, z, axes);
-    }
-    int scan = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(scan, o, 64);
-      if (lane >= o) scan += v;
-    }
-    const int wave_total = __shfl(scan, 63, 64);
-    unsigned long long at = base + (unsigned long long)(scan - n);
-    for (int q = 0; q < n; ++q, ++at) {
-      if (at >= cap) continue;
-      const float px = pts[3 * q], py = pts[3 * q + 1], pz = pts[3 * q + 2];
-      xyz[3 * at] = px;
-      xyz[3 * at + 1] = py;
-      xyz[3 * at + 2] = pz;
-      if (normals) {
-        float nx, ny, nz;
-        attr_normal(vol, vp, px, py, pz, &nx, &ny, &nz);
-        normals[3 * at] = nx;
-        normals[3 * at + 1] = ny;
-        normals[3 * at + 2] = nz;
-      }
-      if (rgb) {
-        const int k = axes[q];
-        const int zz = z - vp.zs0;
-        const int bx = x + (k == 0 ? 1 : 0), by = y + (k == 1 ? 1 : 0), bzz = zz + (k == 2 ? 1 : 0);
-        const unsigned cw = attr_color(vol, colv, vp, x, y, zz, bx, by, bzz, &uncol);
-        rgb[3 * at] = (unsigned char)(cw & 255u);
-        rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
-        rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
-      }
-    }
-    base += wave_total;
-  }
-  if (rgb && n_uncolored) {
-    unsigned sum = uncol;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
-  }
+  float pts[9];
+  unsigned axes = 0, uncol = 0;
+  sweep_row<true>(
+      vp, flags, vp.Y, vp.zo1 - vp.zo0, vp.X, row_count, row_offset,
+      [&](int x, int y, int z, int) { return crossing_count(vol, vp, x, y, z, pts, &axes); },
+      [&](int x, int y, int z, int, int n, unsigned long long at) {
+        for (int q = 0; q < n; ++q, ++at) {
+          if (at >= cap) continue;
+          store3(xyz + 3 * at, pts[3 * q], pts[3 * q + 1], pts[3 * q + 2]);
+          const int k = (int)((axes >> (2 * q)) & 3u), zz = z - vp.zs0;
+          write_attrs(vol, colv, vp, at, pts + 3 * q, x, y, zz, x + (k == 0 ? 1 : 0), y + (k == 1 ? 1 : 0), zz + (k == 2 ? 1 : 0), normals, rgb,
+                      &uncol);
+        }
+      });
+  add_uncolored(uncol, rgb, n_uncolored);
 }
 
-// the write pass of the cloud with its attributes, behind launch_extract's count pass (pass 0) on the same volume
+// the write pass of the cloud with its attributes, behind launch_extract's count pass on the same volume
 void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const unsigned* row_count,
                           const unsigned long long* row_offset, float* xyz, float* normals, unsigned char* rgb,
                           unsigned long long cap, unsigned long long* n_uncolored, const unsigned* flags) {
@@ -774,25 +705,13 @@ void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, 
 // The marching-cubes surface as an INDEXED mesh (hsk_extract_mesh_indexed), welded by edge identity: a vertex is computed
 // from its edge's lower corner, so every cube that shares an edge produces the same bits, and the edge names the vertex.
 // A GRID ROW (y, z) holds the edges whose lower corner lies on it, bit 3 x + axis, in segments of 64 voxels (3 words):
-//   mark     (a wave per cube row, k_extract_mesh_mc's walk): each valid, cut cube ORs the bits of its cut edges into the
+//   mark     (the cubes' sweep, counting): each valid, cut cube ORs the bits of its cut edges into the
 //            four grid rows its edges start on, and the row's triangles are counted (the faces' row offsets)
 //   rows     (a wave per grid row): its vertex count, and per segment the count of the segments before it
 //   (both row counts scanned by launch_scan_rows: the vertex order is the bits' order -- plane, row, x, axis)
-//   vertices (a wave per grid row, a lane per voxel): the soup's arithmetic, the cloud's normal and colour rules
-//   faces    (k_extract_mesh_mc<true>'s walk): each corner's index is its edge's rank, at most three popcounts
+//   vertices (a wave per grid row, a lane per voxel): the soup's edge_vertex, the cloud's write_attrs
+//   faces    (the cubes' sweep, writing): each corner's index is its edge's rank, at most three popcounts
 // ------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ unsigned mi_case(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
-  // the cube's inside mask when it is valid and cut, 0 otherwise (cube_triangles_mc's tests)
-  bool ok = true;
-  unsigned m8 = 0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const short2 v = vol[hsk_vox_index(vp, x + (c & 1), y + ((c >> 1) & 1), z + (c >> 2) - vp.zs0)];
-    ok = ok && v.y != 0;
-    m8 |= (v.x < 0 ? 1u : 0u) << c;
-  }
-  return (!ok || m8 == 255u) ? 0u : m8;
-}
 // set bits below bit o (0 .. 191) of a segment's three words
 static __device__ __forceinline__ unsigned mi_rank(unsigned long long w0, unsigned long long w1, unsigned long long w2, int o) {
   const unsigned long long m0 = o >= 64 ? ~0ull : ((1ull << o) - 1ull);
@@ -826,51 +745,33 @@ size_t mesh_index_layout(const VolParams& vp, void* base, MeshIndexBufs* b) {
 __global__ __launch_bounds__(256) void k_mesh_index_mark(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
                                                          unsigned* __restrict__ row_count, unsigned* __restrict__ bits, int nseg, int z_end,
                                                          const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int ny = vp.Y - 1;
-  const int nrows = ny * (z_end - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % ny, zr = row / ny, z = vp.zo0 + zr;
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) {
-    if (lane == 0) row_count[row] = 0u;
-    return;
-  }
   const size_t row_words = (size_t)nseg * 6;  // (32-bit words of a grid row)
-  unsigned total = 0;
-  for (int xb = 0; xb < vp.X - 1; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
-    const int x = xb + lane;
-    const unsigned m8 = x < vp.X - 1 ? mi_case(vol, vp, x, y, z) : 0u;
-    int n = 0;
-    if (m8 != 0u) {
-      n = ct->ntri[m8];
-      // the cut edges by the grid row they start on (dy, dz), as bits 0 .. 5 above bit 3 x: the x edge of the row's corner
-      // (bit 0), and on the lower rows the y edges (bits 1, 4) or z edges (bits 2, 5) of the corners x and x + 1
+  sweep_row<false>(
+      vp, flags, vp.Y - 1, z_end - vp.zo0, vp.X - 1, row_count, (const unsigned long long*)nullptr,
+      [&](int x, int y, int z, int zr) {
+        const unsigned m8 = load_cube(vol, vp, x, y, z).m8;
+        if (m8 == 0u) return 0;
+        // the cut edges by the grid row they start on (dy, dz), as bits 0 .. 5 above bit 3 x: the x edge of the row's corner
+        // (bit 0), and on the lower rows the y edges (bits 1, 4) or z edges (bits 2, 5) of the corners x and x + 1
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int dy = r & 1, dz = r >> 1;
-        const int c0 = dy * 2 + dz * 4;
-        unsigned m = ((m8 >> c0) ^ (m8 >> (c0 + 1))) & 1u;
-        if (dy == 0)
-          m |= ((((m8 >> c0) ^ (m8 >> (c0 + 2))) & 1u) << 1) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 3))) & 1u) << 4);
-        if (dz == 0)
-          m |= ((((m8 >> c0) ^ (m8 >> (c0 + 4))) & 1u) << 2) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 5))) & 1u) << 5);
-        if (m == 0u) continue;
-        const int bit = 3 * x;
-        unsigned* w = bits + (size_t)((zr + dz) * vp.Y + y + dy) * row_words + (bit >> 5);
-        const int sh = bit & 31;
-        atomicOr(w, m << sh);
-        if (sh > 26 && (m >> (32 - sh)) != 0u) atomicOr(w + 1, m >> (32 - sh));
-      }
-    }
-    int sum = n;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    total += sum;
-  }
-  if (lane == 0) row_count[row] = total;
+        for (int r = 0; r < 4; ++r) {
+          const int dy = r & 1, dz = r >> 1;
+          const int c0 = dy * 2 + dz * 4;
+          unsigned m = ((m8 >> c0) ^ (m8 >> (c0 + 1))) & 1u;
+          if (dy == 0)
+            m |= ((((m8 >> c0) ^ (m8 >> (c0 + 2))) & 1u) << 1) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 3))) & 1u) << 4);
+          if (dz == 0)
+            m |= ((((m8 >> c0) ^ (m8 >> (c0 + 4))) & 1u) << 2) | ((((m8 >> (c0 + 1)) ^ (m8 >> (c0 + 5))) & 1u) << 5);
+          if (m == 0u) continue;
+          const int bit = 3 * x;
+          unsigned* w = bits + (size_t)((zr + dz) * vp.Y + y + dy) * row_words + (bit >> 5);
+          const int sh = bit & 31;
+          atomicOr(w, m << sh);
+          if (sh > 26 && (m >> (32 - sh)) != 0u) atomicOr(w + 1, m >> (32 - sh));
+        }
+        return (int)ct->ntri[m8];
+      },
+      [](int, int, int, int, int, unsigned long long) {});
 }
 
 __global__ __launch_bounds__(256) void k_mesh_index_rows(const unsigned long long* __restrict__ bits, int rows, int nseg,
@@ -920,86 +821,41 @@ __global__ __launch_bounds__(256) void k_mesh_index_verts(const short2* __restri
       if (!((b3 >> k) & 1u)) continue;
       const int bx = x + (k == 0 ? 1 : 0), by = y + (k == 1 ? 1 : 0), bzz = zz + (k == 2 ? 1 : 0);
       const short fb = vol[hsk_vox_index(vp, bx, by, bzz)].x;
-      // (cube_triangles_mc's arithmetic on every axis: a, the lower corner, and b)
-      const float Fa = (float)fa / 32767.0f, Fb = (float)fb / 32767.0f;
-      const float wt = Fa / (Fa - Fb);
       const int ga[3] = {x, y, z};
       const int gb[3] = {bx, by, z + (k == 2 ? 1 : 0)};
       float p[3];
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        const float pa = ((float)ga[ax] + 0.5f) * vp.cell[ax];
-        const float pb = ((float)gb[ax] + 0.5f) * vp.cell[ax];
-        p[ax] = pa + wt * (pb - pa);
-      }
-      if (xyz) {
-        xyz[3 * at] = p[0];
-        xyz[3 * at + 1] = p[1];
-        xyz[3 * at + 2] = p[2];
-      }
-      if (normals) {
-        float nx, ny, nz;
-        attr_normal(vol, vp, p[0], p[1], p[2], &nx, &ny, &nz);
-        normals[3 * at] = nx;
-        normals[3 * at + 1] = ny;
-        normals[3 * at + 2] = nz;
-      }
-      if (rgb) {
-        const unsigned cw = attr_color(vol, colv, vp, x, y, zz, bx, by, bzz, &uncol);
-        rgb[3 * at] = (unsigned char)(cw & 255u);
-        rgb[3 * at + 1] = (unsigned char)((cw >> 8) & 255u);
-        rgb[3 * at + 2] = (unsigned char)((cw >> 16) & 255u);
-      }
+      edge_vertex(vp, fa, fb, ga, gb, p);
+      if (xyz) store3(xyz + 3 * at, p[0], p[1], p[2]);
+      write_attrs(vol, colv, vp, at, p, x, y, zz, bx, by, bzz, normals, rgb, &uncol);
       ++at;
     }
   }
-  if (rgb && n_uncolored) {
-    unsigned sum = uncol;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
-  }
+  add_uncolored(uncol, rgb, n_uncolored);
 }
 
 __global__ __launch_bounds__(256) void k_mesh_index_faces(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,
                                                           const unsigned* __restrict__ row_count, const unsigned long long* __restrict__ row_offset,
                                                           MeshIndexBufs mb, int* __restrict__ faces, int z_end, const unsigned* __restrict__ flags) {
-  const int lane = threadIdx.x & 63;
-  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int ny = vp.Y - 1;
-  const int nrows = ny * (z_end - vp.zo0);
-  if (row >= nrows) return;
-  const int y = row % ny, zr = row / ny, z = vp.zo0 + zr;
-  if (row_count[row] == 0u) return;  // (the mark pass found the row empty)
-  const unsigned long long row_mask = row_brick_mask(flags, vp, y, z);
-  if (row_mask == 0ull) return;
-  unsigned long long base = row_offset[row];
-  for (int xb = 0; xb < vp.X - 1; xb += 64) {
-    if (!segment_may_hold_negative(row_mask, vp, xb, min(xb + 63, vp.X - 2))) continue;
-    const int x = xb + lane;
-    const unsigned m8 = x < vp.X - 1 ? mi_case(vol, vp, x, y, z) : 0u;
-    const int n = m8 ? (int)ct->ntri[m8] : 0;
-    int scan = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(scan, o, 64);
-      if (lane >= o) scan += u;
-    }
-    const int wave_total = __shfl(scan, 63, 64);
-    const unsigned long long at = base + (unsigned long long)(scan - n);
-    for (int t = 0; t < n; ++t)
-      for (int q = 0; q < 3; ++q) {
-        const unsigned code = ct->edge[m8][t][q];
-        const int a = (int)(code & 15u), ab = (int)((code >> 4) ^ code) & 7;  // (b ^ a: the edge's axis as 1, 2 or 4)
-        const int axis = ab == 1 ? 0 : (ab == 2 ? 1 : 2);
-        const int gx = x + (a & 1), g = (zr + (a >> 2)) * vp.Y + y + ((a >> 1) & 1);
-        const int s = gx >> 6;
-        const unsigned long long* w = mb.bits + ((size_t)g * mb.nseg + s) * 3;
-        const unsigned long long idx = mb.voff[g] + mb.segbase[(size_t)g * mb.nseg + s] + mi_rank(w[0], w[1], w[2], 3 * (gx & 63) + axis);
-        faces[3 * (at + t) + q] = (int)idx;
-      }
-    base += wave_total;
-  }
+  unsigned m8 = 0;
+  sweep_row<true>(
+      vp, flags, vp.Y - 1, z_end - vp.zo0, vp.X - 1, row_count, row_offset,
+      [&](int x, int y, int z, int) {
+        m8 = load_cube(vol, vp, x, y, z).m8;
+        return m8 ? (int)ct->ntri[m8] : 0;
+      },
+      [&](int x, int y, int, int zr, int n, unsigned long long at) {
+        for (int t = 0; t < n; ++t)
+          for (int q = 0; q < 3; ++q) {
+            const unsigned code = ct->edge[m8][t][q];
+            const int a = (int)(code & 15u), ab = (int)((code >> 4) ^ code) & 7;  // (b ^ a: the edge's axis as 1, 2 or 4)
+            const int axis = ab == 1 ? 0 : (ab == 2 ? 1 : 2);
+            const int gx = x + (a & 1), g = (zr + (a >> 2)) * vp.Y + y + ((a >> 1) & 1);
+            const int s = gx >> 6;
+            const unsigned long long* w = mb.bits + ((size_t)g * mb.nseg + s) * 3;
+            const unsigned long long idx = mb.voff[g] + mb.segbase[(size_t)g * mb.nseg + s] + mi_rank(w[0], w[1], w[2], 3 * (gx & 63) + axis);
+            faces[3 * (at + t) + q] = (int)idx;
+          }
+      });
 }
 
 // the count pass: zeroed edge bits, marked, the grid rows' counts; both row scans (totals[0] vertices, totals[1] faces)

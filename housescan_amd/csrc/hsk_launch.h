@@ -39,9 +39,11 @@ void launch_adopt_pyramid(hipStream_t s, const int* keys_min, const int* bits, i
 void launch_resolve_push(hipStream_t s, const int* keys_local, const int* keys_min, const float* vmap, const float* nmap,
                          const PushDests& dst, int P);
 int extract_warm();   // loads extract.hip's code object (hsk_prepare_readout); a hipError_t
+// the products' two passes (extract.hip): without an output buffer the count pass (the rows' counts and offsets, the total),
+// with one the write pass behind it
 void launch_extract(hipStream_t s, const void* vol, const VolParams& vp, unsigned* row_count,
                     unsigned long long* row_offset, unsigned long long* total, float* xyz, unsigned long long cap,
-                    int pass, const unsigned* flags);
+                    const unsigned* flags);
 size_t hsk_scan_scratch_entries(int nrows);  // entries of a row_offset buffer for nrows rows (the offsets, then the scan's block sums)
 // the cloud's write pass with normals and colour (either may be null), behind launch_extract's count pass (extract.hip)
 void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const unsigned* row_count,
@@ -84,9 +86,9 @@ void hsk_build_tet_table(TetTable* tt);
 int hsk_build_cube_table(CubeTable* ct);  // marching cubes; returns the most triangles of a case (HSK_MC_MAXT)
 int hsk_mesh_z_end(const VolParams& vp);
 void launch_extract_mesh(hipStream_t s, const void* vol, const VolParams& vp, const TetTable& tt, unsigned* row_count,
-                         unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags);
+                         unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, const unsigned* flags);
 void launch_extract_mesh_mc(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
-                            unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, int pass, const unsigned* flags);
+                            unsigned long long* row_offset, unsigned long long* total, float* tri, unsigned long long cap, const unsigned* flags);
 // the indexed marching-cubes mesh (extract.hip): its scratch, carved out of one device buffer by mesh_index_layout
 struct MeshIndexBufs {
   int rows;                     // grid rows: Y x (hsk_mesh_z_end - zo0 + 1) planes (0 when the context emits no cube)
@@ -98,7 +100,7 @@ struct MeshIndexBufs {
   unsigned short* segbase;      // rows x nseg: vertices of the row before each segment
 };
 size_t mesh_index_layout(const VolParams& vp, void* base /* null: the size only */, MeshIndexBufs* b);
-// count pass (faces' row counts into row_count / row_offset, as launch_extract_mesh_mc's pass 0), then the write passes
+// count pass (faces' row counts into row_count / row_offset, as launch_extract_mesh_mc's count pass), then the write passes
 void launch_mesh_index_count(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, unsigned* row_count,
                              unsigned long long* row_offset, const MeshIndexBufs& mb, const unsigned* flags);
 void launch_mesh_index_write(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const CubeTable* ct_dev,

@@ -84,7 +84,7 @@ struct hsk_ctx {
   uint64_t vol_epoch = 1;       // counted up by everything that changes the volume
   int ro_kind = 0;              // 1 cloud, 2 tetrahedra mesh, 3 cubes mesh, 4 indexed mesh: whose counts d_rowcnt / d_rowoff hold
   uint64_t ro_epoch = 0;
-  unsigned long long ro_total = 0;
+  unsigned long long ro_totals[2] = {0, 0};  // its items; of the indexed mesh the vertices, then the faces
   void* d_out = nullptr;
   size_t out_bytes = 0;
   void* h_pin[2] = {nullptr, nullptr};
@@ -141,8 +141,7 @@ struct hsk_ctx {
   uint64_t prof_frames = 0;
   // colour (hsk_enable_color; all null until then): the (r, g, b, w) volume, row-major; per image-buffer set a device flag "this
   // frame has colour", written when the frame is submitted (the captured graphs read it, with the set's d_rgb); one pinned
-  // staging image (its upload has completed before a submission returns, as the depth frame's has); the read-out's attribute
-  // buffer (a counter, then the normals and the colours of a cloud)
+  // staging image (its upload has completed before a submission returns, as the depth frame's has)
   unsigned* d_color = nullptr;
   size_t color_bytes = 0;
   int* d_has_color = nullptr;
@@ -151,13 +150,10 @@ struct hsk_ctx {
   int color_max_w = 0;
   bool group_slab = false;  // a slab of a group (hsk_group_create*): no colour
   float color_band = 0.0f;
-  void* d_attr = nullptr;
-  size_t attr_bytes = 0;
   // the indexed mesh's scratch (hsk_extract_mesh_indexed: edge bits, per-row tables; extract.hip mesh_index_layout), made on
-  // first use; its counts belong to ro_kind 4, whose faces are ro_total
+  // first use; its counts belong to ro_kind 4
   void* d_mi = nullptr;
   size_t mi_bytes = 0;
-  unsigned long long mi_vertices = 0;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -292,7 +288,6 @@ static void free_all(hsk_ctx* k) {
   F(k->d_out);
   F(k->d_color);
   F(k->d_has_color);
-  F(k->d_attr);
   F(k->d_mi);
   for (auto& b : k->ib) F(b.d_rgb);
   if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
@@ -1515,8 +1510,11 @@ static int ensure_row_tables(hsk_ctx* k) {
   HIPCHK(k, hipMalloc((void**)&k->d_rowoff, hsk_scan_scratch_entries(nrows) * 8));
   return HSK_OK;
 }
-static int ensure_product_bytes(hsk_ctx* k, size_t want) {
+// the product buffer: grow-only, and when it has to grow a quarter more than asked (a scan grows from call to call) unless
+// the caller names the size itself (hsk_prepare_readout)
+static int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom = true) {
   if (k->out_bytes >= want) return HSK_OK;
+  if (headroom) want += want >> 2;
   if (k->d_out) (void)hipFree(k->d_out);
   k->d_out = nullptr;
   k->out_bytes = 0;
@@ -1524,41 +1522,60 @@ static int ensure_product_bytes(hsk_ctx* k, size_t want) {
   k->out_bytes = want;
   return HSK_OK;
 }
+// ... carved into the arrays of one product, each 256-byte aligned: take() -> the next array's offset
+struct ProductLayout {
+  size_t bytes = 0;
+  size_t take(size_t n) {
+    const size_t at = bytes;
+    bytes += (n + 255) & ~(size_t)255;
+    return at;
+  }
+};
+// n 64-bit words of device memory, once the stream has produced them
+static int read_u64(hsk_ctx* k, unsigned long long* dst, const unsigned long long* src_dev, int n = 1) {
+  HIPCHK(k, hipMemcpyAsync(dst, src_dev, (size_t)n * 8, hipMemcpyDeviceToHost, k->stream));
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  return HSK_OK;
+}
 
 // A product of the volume (cloud, mesh): counted row by row, the rows' offsets scanned, then written in voxel order.  The
 // callers' protocol is a size query (null buffer) followed by the fill: the second call finds the counts and offsets of
 // the first in place when nothing has touched the volume in between (ro_kind / ro_epoch) -- the count sweep ran twice
-// per product before.  The product is written into a device buffer that only ever grows and reaches the caller through
-// the pinned pair (copy_out).
-template <class Count, class Fill>
-static int extract_product(hsk_ctx* k, int kind, size_t elem_bytes, float* out, size_t cap, size_t* n_out, Count count, Fill fill) {
-  {
-    const int r = ensure_row_tables(k);
-    if (r != HSK_OK) return r;
-  }
+// per product before.  This is the one place that says whether d_rowcnt / d_rowoff (for kind 4 also the mesh-index scratch)
+// hold product `kind`'s counts of the volume as it is; if not, count() enqueues the count pass, which leaves the totals
+// (ro_totals: one, of the indexed mesh two) at d_totals.
+template <class Count>
+static int product_counts(hsk_ctx* k, int kind, const unsigned long long* d_totals, Count count) {
+  int r = ensure_row_tables(k);
+  if (r != HSK_OK) return r;
   // (NO flush of the deferred weights here, round 5: the products ask of a weight only whether it is zero, and a weight the
   // summaries hold ahead of the volume's copy is never that -- a block leaves "never observed" with a store of (+1, 1),
   // and every deferred state has all 16 weights >= 1 in the volume itself; the TSDF values are always current.  Only
   // hsk_download_tsdf, which hands the weights out, brings them up to date.  A host that shows a cloud after every
   // frame pays for the cloud, not for rewriting the frustum's free space.)
-  if (!(k->ro_kind == kind && k->ro_epoch == k->vol_epoch)) {
-    k->ro_kind = 0;
-    count();
-    unsigned long long total = 0;
-    HIPCHK(k, hipMemcpyAsync(&total, k->d_counter, 8, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    k->ro_kind = kind;
-    k->ro_epoch = k->vol_epoch;
-    k->ro_total = total;
-  }
-  *n_out = (size_t)k->ro_total;
-  if (!out || cap == 0 || k->ro_total == 0) return HSK_OK;
-  const size_t nw = k->ro_total < cap ? (size_t)k->ro_total : cap;
-  if (k->out_bytes < nw * elem_bytes) {
-    const int r = ensure_product_bytes(k, nw * elem_bytes + (nw * elem_bytes >> 2));  // (a quarter more: a scan grows from call to call)
-    if (r != HSK_OK) return r;
-  }
-  fill((float*)k->d_out, nw);
+  if (k->ro_kind == kind && k->ro_epoch == k->vol_epoch) return HSK_OK;
+  k->ro_kind = 0;
+  count();
+  k->ro_totals[1] = 0;
+  r = read_u64(k, k->ro_totals, d_totals, kind == 4 ? 2 : 1);
+  if (r != HSK_OK) return r;
+  k->ro_kind = kind;
+  k->ro_epoch = k->vol_epoch;
+  return HSK_OK;
+}
+// ... and a product of one array: launch(d, nw) enqueues the count pass when d is null, else writes the first nw items at d.
+// The product is written into the product buffer and reaches the caller through the pinned pair (copy_out).
+template <class Launch>
+static int extract_product(hsk_ctx* k, int kind, size_t elem_bytes, float* out, size_t cap, size_t* n_out, Launch launch) {
+  int r = product_counts(k, kind, k->d_counter, [&]() { launch(nullptr, 0); });
+  if (r != HSK_OK) return r;
+  const unsigned long long total = k->ro_totals[0];
+  *n_out = (size_t)total;
+  if (!out || cap == 0 || total == 0) return HSK_OK;
+  const size_t nw = total < cap ? (size_t)total : cap;
+  r = ensure_product_bytes(k, nw * elem_bytes);
+  if (r != HSK_OK) return r;
+  launch((float*)k->d_out, nw);
   return copy_out(k, out, k->d_out, nw * elem_bytes);
 }
 
@@ -1568,7 +1585,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   int r = ensure_pinned(k);
   if (r == HSK_OK) r = ensure_row_tables(k);
   if (r == HSK_OK) r = ensure_cube_table(k);
-  if (r == HSK_OK) r = ensure_product_bytes(k, product_bytes ? product_bytes : (size_t)48 << 20);
+  if (r == HSK_OK) r = ensure_product_bytes(k, product_bytes ? product_bytes : (size_t)48 << 20, false);
   if (r == HSK_OK) HIPCHK(k, (hipError_t)extract_warm());  // (the read-out kernels' code object: 0.7 ms of a process's first product)
   return r;
 }
@@ -1576,10 +1593,9 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
 extern "C" int hsk_extract_cloud(hsk_ctx* k, float* xyz, size_t cap_points, size_t* n_points) {
   if (!k || !n_points) return HSK_ERR_ARG;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  return extract_product(
-      k, 1, 12, xyz, cap_points, n_points,
-      [&]() { launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); },
-      [&](float* d, size_t nw) { launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, 1, k->d_flags); });
+  return extract_product(k, 1, 12, xyz, cap_points, n_points, [&](float* d, size_t nw) {
+    launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, k->d_flags);
+  });
 }
 
 // Triangle soup (9 floats per triangle) of the TSDF zero level set, marching tetrahedra, voxel order.
@@ -1588,10 +1604,9 @@ extern "C" int hsk_extract_mesh(hsk_ctx* k, float* tri_xyz, size_t cap_triangles
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   TetTable tt;
   hsk_build_tet_table(&tt);
-  return extract_product(
-      k, 2, 36, tri_xyz, cap_triangles, n_triangles,
-      [&]() { launch_extract_mesh(k->stream, k->d_vol, k->vp, tt, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); },
-      [&](float* d, size_t nw) { launch_extract_mesh(k->stream, k->d_vol, k->vp, tt, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, 1, k->d_flags); });
+  return extract_product(k, 2, 36, tri_xyz, cap_triangles, n_triangles, [&](float* d, size_t nw) {
+    launch_extract_mesh(k->stream, k->d_vol, k->vp, tt, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, k->d_flags);
+  });
 }
 
 // The same level set by MARCHING CUBES (the form upstream's .ply export has, README.md:16-17): about half the triangles
@@ -1603,10 +1618,9 @@ extern "C" int hsk_extract_mesh_cubes(hsk_ctx* k, float* tri_xyz, size_t cap_tri
     const int r = ensure_cube_table(k);
     if (r != HSK_OK) return r;
   }
-  return extract_product(
-      k, 3, 36, tri_xyz, cap_triangles, n_triangles,
-      [&]() { launch_extract_mesh_mc(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); },
-      [&](float* d, size_t nw) { launch_extract_mesh_mc(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, 1, k->d_flags); });
+  return extract_product(k, 3, 36, tri_xyz, cap_triangles, n_triangles, [&](float* d, size_t nw) {
+    launch_extract_mesh_mc(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, k->d_counter, d, nw, k->d_flags);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1762,33 +1776,33 @@ extern "C" int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, u
   if (rgb && !k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   if (n_uncolored) *n_uncolored = 0;
-  auto count = [&]() { launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, 0, k->d_flags); };
-  size_t total = 0;
-  int r = extract_product(k, 1, 12, nullptr, 0, &total, count, [](float*, size_t) {});
-  *n_points = total;
-  if (r != HSK_OK || !xyz || cap_points == 0 || total == 0) return r;
-  const size_t nw = total < cap_points ? total : cap_points;
-  const size_t want = 16 + nw * 12 + nw * 3;  // the uncoloured counter, the normals, the colours
-  if (k->attr_bytes < want) {
-    if (k->d_attr) (void)hipFree(k->d_attr);
-    k->d_attr = nullptr;
-    k->attr_bytes = 0;
-    HIPCHK(k, hipMalloc(&k->d_attr, want + (want >> 2)));
-    k->attr_bytes = want + (want >> 2);
-  }
-  unsigned long long* d_uncol = (unsigned long long*)k->d_attr;
-  float* d_nrm = normals ? (float*)((char*)k->d_attr + 16) : nullptr;
-  unsigned char* d_rgb = rgb ? (unsigned char*)k->d_attr + 16 + nw * 12 : nullptr;
-  HIPCHK(k, hipMemsetAsync(d_uncol, 0, 8, k->stream));
-  r = extract_product(k, 1, 12, xyz, cap_points, &total, count, [&](float* d, size_t n) {
-    launch_extract_attrs(k->stream, k->d_vol, k->d_color, k->vp, k->d_rowcnt, k->d_rowoff, d, d_nrm, d_rgb, n, d_uncol, k->d_flags);
+  int r = product_counts(k, 1, k->d_counter, [&]() {
+    launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, k->d_flags);
   });
+  if (r != HSK_OK) return r;
+  const size_t total = (size_t)k->ro_totals[0];
+  *n_points = total;
+  if (!xyz || cap_points == 0 || total == 0) return HSK_OK;
+  const size_t nw = total < cap_points ? total : cap_points;
+  ProductLayout lay;
+  const size_t o_xyz = lay.take(nw * 12), o_nrm = lay.take(normals ? nw * 12 : 0), o_rgb = lay.take(rgb ? nw * 3 : 0);
+  r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  char* d = (char*)k->d_out;
+  float* d_nrm = normals ? (float*)(d + o_nrm) : nullptr;
+  unsigned char* d_rgb = rgb ? (unsigned char*)(d + o_rgb) : nullptr;
+  // (the uncoloured points are counted in d_counter's second word: the totals are its first, and nothing else on the stream
+  // touches it between this memset and the read below)
+  unsigned long long* d_uncol = k->d_counter + 1;
+  HIPCHK(k, hipMemsetAsync(d_uncol, 0, 8, k->stream));
+  launch_extract_attrs(k->stream, k->d_vol, k->d_color, k->vp, k->d_rowcnt, k->d_rowoff, (float*)(d + o_xyz), d_nrm, d_rgb, nw, d_uncol,
+                       k->d_flags);
+  r = copy_out(k, xyz, d + o_xyz, nw * 12);
   if (r == HSK_OK && normals) r = copy_out(k, normals, d_nrm, nw * 12);
   if (r == HSK_OK && rgb) r = copy_out(k, rgb, d_rgb, nw * 3);
   if (r == HSK_OK && rgb && n_uncolored) {
     unsigned long long u = 0;
-    HIPCHK(k, hipMemcpyAsync(&u, d_uncol, 8, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
+    r = read_u64(k, &u, d_uncol);
     *n_uncolored = (size_t)u;
   }
   return r;
@@ -1803,7 +1817,6 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   if (n_uncolored) *n_uncolored = 0;
   int r = ensure_cube_table(k);
-  if (r == HSK_OK) r = ensure_row_tables(k);
   if (r != HSK_OK) return r;
   MeshIndexBufs mb;
   if (!k->d_mi) {
@@ -1812,19 +1825,11 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
     k->mi_bytes = bytes;
   }
   (void)mesh_index_layout(k->vp, k->d_mi, &mb);
-  // (no flush of the deferred weights: extract_product says why)
-  if (!(k->ro_kind == 4 && k->ro_epoch == k->vol_epoch)) {
-    k->ro_kind = 0;
+  r = product_counts(k, 4, mb.totals, [&]() {
     launch_mesh_index_count(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, mb, k->d_flags);
-    unsigned long long tot[2] = {0, 0};
-    HIPCHK(k, hipMemcpyAsync(tot, mb.totals, 16, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    k->ro_kind = 4;
-    k->ro_epoch = k->vol_epoch;
-    k->ro_total = tot[1];
-    k->mi_vertices = tot[0];
-  }
-  const size_t nv = (size_t)k->mi_vertices, nf = (size_t)k->ro_total;
+  });
+  if (r != HSK_OK) return r;
+  const size_t nv = (size_t)k->ro_totals[0], nf = (size_t)k->ro_totals[1];
   *n_vertices = nv;
   *n_faces = nf;
   if (nv > (size_t)INT32_MAX) return fail(k, HSK_ERR_STATE, "hsk_extract_mesh_indexed: more vertices than an int32 index reaches");
@@ -1832,16 +1837,13 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
   if ((want_v && cap_vertices < nv) || (faces && cap_faces < nf))
     return fail(k, HSK_ERR_ARG, "hsk_extract_mesh_indexed: a capacity below the total (the arrays are written whole or not at all)");
   if (!(want_v && nv) && !(faces && nf)) return HSK_OK;
-  // one product buffer: vertices, normals, colours, faces (each 256-B aligned)
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_nrm = al(vertices ? nv * 12 : 0), o_rgb = o_nrm + al(normals ? nv * 12 : 0), o_fc = o_rgb + al(rgb ? nv * 3 : 0);
-  const size_t want = o_fc + (faces ? nf * 12 : 0);
-  if (k->out_bytes < want) {
-    r = ensure_product_bytes(k, want + (want >> 2));
-    if (r != HSK_OK) return r;
-  }
+  ProductLayout lay;
+  const size_t o_xyz = lay.take(vertices ? nv * 12 : 0), o_nrm = lay.take(normals ? nv * 12 : 0), o_rgb = lay.take(rgb ? nv * 3 : 0),
+               o_fc = lay.take(faces ? nf * 12 : 0);
+  r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
   char* d = (char*)k->d_out;
-  float* d_xyz = vertices ? (float*)d : nullptr;
+  float* d_xyz = vertices ? (float*)(d + o_xyz) : nullptr;
   float* d_nrm = normals ? (float*)(d + o_nrm) : nullptr;
   unsigned char* d_rgb = rgb ? (unsigned char*)(d + o_rgb) : nullptr;
   int* d_fc = faces ? (int*)(d + o_fc) : nullptr;
@@ -1855,8 +1857,7 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
   if (r == HSK_OK && faces && nf) r = copy_out(k, faces, d_fc, nf * 12);
   if (r == HSK_OK && rgb && n_uncolored) {
     unsigned long long u = 0;
-    HIPCHK(k, hipMemcpyAsync(&u, mb.totals + 2, 8, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
+    r = read_u64(k, &u, mb.totals + 2);
     *n_uncolored = (size_t)u;
   }
   return r;
