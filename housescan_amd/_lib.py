@@ -36,6 +36,24 @@ class HskConfig(C.Structure):
     ]
 
 
+HSK_VIEW_LAMBERT, HSK_VIEW_NORMALS, HSK_VIEW_COLOR, HSK_VIEW_COLOR_LIT = 0, 1, 2, 3
+
+
+class HskView(C.Structure):
+    """Mirror of `hsk_view` (include/hskinfu.h)."""
+
+    _fields_ = [
+        ("width", C.c_int), ("height", C.c_int),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("pose", C.c_float * 16),
+        ("follow", C.c_int),
+        ("mode", C.c_int),
+        ("light", C.c_float * 3),
+        ("light_in_camera", C.c_int),
+        ("background", C.c_uint8 * 3),
+    ]
+
+
 # every symbol include/hskinfu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -82,6 +100,10 @@ SYMBOLS = {
     "hsk_extract_cloud_attrs": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_extract_mesh_indexed": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t),
                                             C.POINTER(C.c_size_t)]),
+    "hsk_default_view": (None, [_P, C.POINTER(HskView)]),
+    "hsk_render_view": (C.c_int, [_P, C.POINTER(HskView), _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
+    "hsk_write_pgm16": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_prefetch": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_front": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

@@ -31,6 +31,20 @@ void launch_raycast(hipStream_t s, const void* vol, const TrackState* st, const 
                     float* vmap, float* nmap, int* keys, const unsigned* flags, const MapPyramid* pyramid = nullptr,
                     const RingOut* ring = nullptr);
 bool raycast_can_fuse_pyramid(const VolParams& vp, int W, int H);
+// scene views (view.hip).  The camera of a view lives in device memory: a ViewCam block the host fills by a copy -- or the
+// TrackState itself, which begins with the same twelve floats (`follow`: the tracker's pose as the stream has it by then)
+struct ViewCam {
+  float R[9], t[3];   // cam->world
+};
+// one view: the march of launch_raycast for a whole (unsharded) volume from `cam`, shaded by `mode` (HSK_VIEW_*); rgb (3 B per
+// pixel), depth (millimetres), vmap, nmap (3 planes each) may each be null; counts: HSK_VIEW_COUNT_SLOTS slots of 16 words, a wave
+// adds its hits to word 0 and its hits without colour to word 1 of its tile's slot
+#define HSK_VIEW_COUNT_SLOTS 64
+void launch_render_view(hipStream_t s, const void* vol, const unsigned* colv, const ViewCam* cam, const VolParams& vp, int W, int H,
+                        Intr in, const unsigned* flags, int mode, const float light[3], int light_in_camera,
+                        const unsigned char background[3], unsigned char* rgb, unsigned short* depth, float* vmap, float* nmap,
+                        unsigned long long* counts);
+int view_warm();      // loads view.hip's code object (hsk_prepare_readout); a hipError_t
 void launch_resolve(hipStream_t s, const int* keys_local, const int* keys_min, const float* vmap, const float* nmap,
                     int* bits, int P);
 // the end of a z-slab frame in ONE launch: k_adopt + k_resize_maps2 (+ the report into the host ring) fused (kernels_image.hip)

@@ -154,6 +154,10 @@ struct hsk_ctx {
   // first use; its counts belong to ro_kind 4
   void* d_mi = nullptr;
   size_t mi_bytes = 0;
+  // scene views (hsk_render_view), made on first use: the free camera's block and the counter slots in device memory, and their
+  // pinned host side (the camera on its way in, the counts on their way out)
+  void* d_view = nullptr;
+  void* h_view = nullptr;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -289,6 +293,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_color);
   F(k->d_has_color);
   F(k->d_mi);
+  F(k->d_view);
+  if (k->h_view) (void)hipHostFree(k->h_view);
   for (auto& b : k->ib) F(b.d_rgb);
   if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
   for (auto& p : k->h_pin)
@@ -1579,6 +1585,24 @@ static int extract_product(hsk_ctx* k, int kind, size_t elem_bytes, float* out, 
   return copy_out(k, out, k->d_out, nw * elem_bytes);
 }
 
+// a view's small blocks: ViewCam, and 256 B behind it the counter slots, on the device; the same on the pinned host side
+#define HSK_VIEW_COUNTS_AT 256
+#define HSK_VIEW_COUNTS_BYTES ((size_t)HSK_VIEW_COUNT_SLOTS * 128)
+#define HSK_VIEW_BLOCK_BYTES (HSK_VIEW_COUNTS_AT + HSK_VIEW_COUNTS_BYTES)
+static int ensure_view(hsk_ctx* k) {
+  if (k->d_view) return HSK_OK;
+  void* d = nullptr;
+  HIPCHK(k, hipMalloc(&d, HSK_VIEW_BLOCK_BYTES));
+  hipError_t e = hipHostMalloc(&k->h_view, HSK_VIEW_BLOCK_BYTES, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    k->h_view = nullptr;
+    HIPCHK(k, e);
+  }
+  k->d_view = d;
+  return HSK_OK;
+}
+
 extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (!k) return HSK_ERR_ARG;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
@@ -1587,6 +1611,8 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) r = ensure_cube_table(k);
   if (r == HSK_OK) r = ensure_product_bytes(k, product_bytes ? product_bytes : (size_t)48 << 20, false);
   if (r == HSK_OK) HIPCHK(k, (hipError_t)extract_warm());  // (the read-out kernels' code object: 0.7 ms of a process's first product)
+  if (r == HSK_OK) r = ensure_view(k);
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)view_warm());
   return r;
 }
 
@@ -1861,6 +1887,89 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
     *n_uncolored = (size_t)u;
   }
   return r;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// scene views (include/hskinfu.h "Scene views")
+// ------------------------------------------------------------------------------------------------------
+extern "C" void hsk_default_view(const hsk_ctx* k, hsk_view* v) {
+  if (!v) return;
+  hsk_config c;
+  if (k)
+    c = k->cfg;
+  else
+    hsk_default_config(&c, 256);
+  memset(v, 0, sizeof(*v));
+  v->width = c.width;
+  v->height = c.height;
+  v->fx = c.fx;
+  v->fy = c.fy;
+  v->cx = c.cx;
+  v->cy = c.cy;
+  v->pose[0] = v->pose[5] = v->pose[10] = v->pose[15] = 1.0f;
+  v->follow = 1;
+  v->mode = HSK_VIEW_LAMBERT;
+  v->light_in_camera = 1;
+}
+
+// One launch behind whatever the stream holds; everything it writes is the product buffer and the view's own counters.
+extern "C" int hsk_render_view(hsk_ctx* k, const hsk_view* v, uint8_t* rgb, uint16_t* depth_mm, float* vmap, float* nmap, size_t* n_hit,
+                               size_t* n_uncolored) {
+  if (!k) return HSK_ERR_ARG;
+  if (!v) return fail(k, HSK_ERR_ARG, "hsk_render_view: view is null");
+  if (v->width < 1 || v->width > 4096 || v->height < 1 || v->height > 4096)
+    return fail(k, HSK_ERR_ARG, "hsk_render_view: width and height must lie in 1..4096");
+  if (!(std::isfinite(v->fx) && std::isfinite(v->fy) && v->fx > 0.0f && v->fy > 0.0f))
+    return fail(k, HSK_ERR_ARG, "hsk_render_view: fx and fy must be finite and positive");
+  if (v->mode < HSK_VIEW_LAMBERT || v->mode > HSK_VIEW_COLOR_LIT) return fail(k, HSK_ERR_ARG, "hsk_render_view: unknown mode");
+  const bool colour = v->mode == HSK_VIEW_COLOR || v->mode == HSK_VIEW_COLOR_LIT;
+  if (k->group_slab || k->vp.zs0 != 0 || k->vp.nzs != k->vp.Z || k->vp.zo0 != 0 || k->vp.zo1 != k->vp.Z)
+    return fail(k, HSK_ERR_STATE, "hsk_render_view: not for a slab (it owns only its own march steps; views are not composited)");
+  if (colour && !k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  int r = ensure_view(k);
+  if (r != HSK_OK) return r;
+  const size_t P = (size_t)v->width * v->height;
+  ProductLayout lay;
+  const size_t o_rgb = lay.take(rgb ? P * 3 : 0), o_dep = lay.take(depth_mm ? P * 2 : 0), o_v = lay.take(vmap ? P * 12 : 0),
+               o_n = lay.take(nmap ? P * 12 : 0);
+  r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  char* d = (char*)k->d_out;
+  unsigned char* d_rgb = rgb ? (unsigned char*)(d + o_rgb) : nullptr;
+  unsigned short* d_dep = depth_mm ? (unsigned short*)(d + o_dep) : nullptr;
+  float* d_v = vmap ? (float*)(d + o_v) : nullptr;
+  float* d_n = nmap ? (float*)(d + o_n) : nullptr;
+  // the camera: the tracker's own state, read by the kernel where the stream has got to (follow), or the view's block
+  const ViewCam* cam = (const ViewCam*)k->d_st;
+  if (!v->follow) {
+    ViewCam* hc = (ViewCam*)k->h_view;   // (free: every call waits for its own result before it returns)
+    pose16_to_rt(v->pose, hc->R, hc->t);
+    HIPCHK(k, hipMemcpyAsync(k->d_view, hc, sizeof(ViewCam), hipMemcpyHostToDevice, k->stream));
+    cam = (const ViewCam*)k->d_view;
+  }
+  unsigned long long* d_counts = (unsigned long long*)((char*)k->d_view + HSK_VIEW_COUNTS_AT);
+  unsigned long long* h_counts = (unsigned long long*)((char*)k->h_view + HSK_VIEW_COUNTS_AT);
+  HIPCHK(k, hipMemsetAsync(d_counts, 0, HSK_VIEW_COUNTS_BYTES, k->stream));
+  const Intr in = {v->fx, v->fy, v->cx, v->cy};
+  launch_render_view(k->stream, k->d_vol, k->d_color, cam, k->vp, v->width, v->height, in, k->d_flags, v->mode, v->light,
+                     v->light_in_camera, v->background, d_rgb, d_dep, d_v, d_n, d_counts);
+  HIPCHK(k, hipGetLastError());
+  HIPCHK(k, hipMemcpyAsync(h_counts, d_counts, HSK_VIEW_COUNTS_BYTES, hipMemcpyDeviceToHost, k->stream));
+  if (rgb) r = copy_out(k, rgb, d_rgb, P * 3);
+  if (r == HSK_OK && depth_mm) r = copy_out(k, depth_mm, d_dep, P * 2);
+  if (r == HSK_OK && vmap) r = copy_out(k, vmap, d_v, P * 12);
+  if (r == HSK_OK && nmap) r = copy_out(k, nmap, d_n, P * 12);
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  unsigned long long hits = 0, uncolored = 0;
+  for (int i = 0; i < HSK_VIEW_COUNT_SLOTS; ++i) {
+    hits += h_counts[16 * i];
+    uncolored += h_counts[16 * i + 1];
+  }
+  if (n_hit) *n_hit = (size_t)hits;
+  if (n_uncolored) *n_uncolored = (size_t)uncolored;
+  return HSK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------

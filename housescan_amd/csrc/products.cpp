@@ -25,6 +25,37 @@ extern "C" int hsk_write_pcd_xyz(const char* path, const float* xyz, size_t n) {
   return (wrote == n && rc == 0) ? HSK_OK : HSK_ERR_STATE;
 }
 
+// Scene views on the file seam (hsk_render_view): binary PPM (P6, 8-bit RGB) and binary PGM (P5, maxval 65535: 16-bit samples,
+// most significant byte first -- the depth image in millimetres, readable by any Netpbm tool).  Sizes as hsk_render_view's.
+extern "C" int hsk_write_ppm(const char* path, const uint8_t* rgb, int w, int h) {
+  if (!path || !rgb || w < 1 || h < 1 || w > 4096 || h > 4096) return HSK_ERR_ARG;
+  FILE* f = fopen(path, "wb");
+  if (!f) return HSK_ERR_STATE;
+  fprintf(f, "P6\n%d %d\n255\n", w, h);
+  const size_t n = (size_t)w * h;
+  const size_t wrote = fwrite(rgb, 3, n, f);
+  const int rc = fclose(f);
+  return (wrote == n && rc == 0) ? HSK_OK : HSK_ERR_STATE;
+}
+extern "C" int hsk_write_pgm16(const char* path, const uint16_t* depth_mm, int w, int h) {
+  if (!path || !depth_mm || w < 1 || h < 1 || w > 4096 || h > 4096) return HSK_ERR_ARG;
+  FILE* f = fopen(path, "wb");
+  if (!f) return HSK_ERR_STATE;
+  fprintf(f, "P5\n%d %d\n65535\n", w, h);
+  std::vector<uint8_t> row((size_t)w * 2);
+  bool ok = true;
+  for (int y = 0; y < h && ok; ++y) {
+    for (int x = 0; x < w; ++x) {
+      const uint16_t d = depth_mm[(size_t)y * w + x];
+      row[2 * x] = (uint8_t)(d >> 8);
+      row[2 * x + 1] = (uint8_t)(d & 255);
+    }
+    ok = fwrite(row.data(), 2, (size_t)w, f) == (size_t)w;
+  }
+  const int rc = fclose(f);
+  return (ok && rc == 0) ? HSK_OK : HSK_ERR_STATE;
+}
+
 // binary PCD v0.7 with x y z rgb normal_x normal_y normal_z curvature, 32 B per point: the coloured form of HouseScan's cloud
 // loader (Main.hs:1325-1345: XYZ first, then XYZ + RGB + normal).  rgb is PCL's packed colour, the bit pattern 0x00RRGGBB
 // stored in a float field; curvature 0.  (Unverified against pcd-loader's loadXyzRgbNormal itself: it is not available here.)

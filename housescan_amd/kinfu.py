@@ -332,6 +332,50 @@ class KinfuTracker:
             raise KinfuError("extract_mesh_indexed: the counts changed between the two calls")
         return verts, faces, nrm, col, nu.value
 
+    # ---- scene views ----------------------------------------------------------------------------------
+    def default_view(self):
+        """the sensor's camera following the tracker, Lambert, the light at the camera (an `_lib.HskView` to edit and pass on)"""
+        v = _lib.HskView()
+        self.lib.hsk_default_view(self.h, C.byref(v))
+        return v
+
+    def render_view(self, view=None, *, width=None, height=None, fx=None, fy=None, cx=None, cy=None, pose=None, mode=None,
+                    light=None, light_in_camera=None, background=None, rgb=True, depth=True, vmap=False, nmap=False):
+        """what has been fused so far as images from a virtual camera (hsk_render_view), legal with frames in flight.  `view`: an
+        HskView (default: default_view()); the keywords override its fields.  pose: a 4x4 cam->world matrix for a free camera,
+        None (and view.follow) to follow the tracker.  -> dict with the arrays asked for -- rgb (h, w, 3) uint8, depth (h, w)
+        uint16 millimetres, vmap / nmap (3, h, w) float32 with NaN = no hit / no normal -- and n_hit, n_uncolored."""
+        if view is None:
+            view = self.default_view()
+        v = _lib.HskView.from_buffer_copy(view)
+        for name, val in (("width", width), ("height", height), ("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("mode", mode),
+                          ("light_in_camera", light_in_camera)):
+            if val is not None:
+                setattr(v, name, val)
+        if pose is not None:
+            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
+            v.follow = 0
+        if light is not None:
+            v.light[:] = [float(x) for x in light]
+        if background is not None:
+            v.background[:] = [int(x) for x in background]
+        w, h = v.width, v.height
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
+        out = {}
+        if rgb and ok:
+            out["rgb"] = np.empty((h, w, 3), np.uint8)
+        if depth and ok:
+            out["depth"] = np.empty((h, w), np.uint16)
+        if vmap and ok:
+            out["vmap"] = np.empty((3, h, w), np.float32)
+        if nmap and ok:
+            out["nmap"] = np.empty((3, h, w), np.float32)
+        ptr = lambda k: out[k].ctypes.data if k in out else None  # noqa: E731
+        nh, nu = C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_render_view(self.h, C.byref(v), ptr("rgb"), ptr("depth"), ptr("vmap"), ptr("nmap"), C.byref(nh), C.byref(nu)))
+        out["n_hit"], out["n_uncolored"] = nh.value, nu.value
+        return out
+
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
         return self.lib.hsk_stream(self.h)

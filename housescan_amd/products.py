@@ -162,6 +162,22 @@ def write_ply_indexed(path, vertices, faces, normals=None, rgb=None):
                                   None if col is None else col.ctypes.data, len(v), f.ctypes.data, len(f)), "hsk_write_ply_indexed")
 
 
+def write_ppm(path, rgb):
+    """(h, w, 3) uint8 image -> binary PPM (P6): KinfuTracker.render_view's rgb"""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_ppm: an (h, w, 3) uint8 array is needed")
+    _ck(_lib.load().hsk_write_ppm(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]), "hsk_write_ppm")
+
+
+def write_pgm16(path, depth_mm):
+    """(h, w) uint16 image -> binary PGM (P5, maxval 65535, big-endian samples): KinfuTracker.render_view's depth"""
+    a = np.ascontiguousarray(depth_mm, np.uint16)
+    if a.ndim != 2:
+        raise ValueError("write_pgm16: an (h, w) uint16 array is needed")
+    _ck(_lib.load().hsk_write_pgm16(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]), "hsk_write_pgm16")
+
+
 def write_xf(path, m):
     lib = _lib.load()
     a = np.ascontiguousarray(m, np.float32).reshape(16)

@@ -201,6 +201,47 @@ int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices /* 3 per vertex */, flo
                              uint8_t* rgb /* 3 per vertex, may be NULL */, size_t cap_vertices, size_t* n_vertices,
                              int32_t* faces /* 3 per face */, size_t cap_faces, size_t* n_faces, size_t* n_uncolored);
 
+/* ---- Scene views: what has been fused so far, as an image from any camera (upstream's generateImage / generateDepth and its
+ * colour view; DESIGN.md 3.8 the kernel, 8b the rule).  One call marches the TSDF from a virtual pinhole camera, shades the
+ * hits on the device and hands back small images.  It is enqueued on hsk_stream() behind every frame submitted so far and
+ * waits for its own result only: it neither consumes nor delays a hsk_wait_frame result, and it writes NOTHING the tracker
+ * reads (not the tracker state, the model maps, the step keys, the image-buffer sets or the ring), so it is legal in the
+ * middle of a pipelined scan -- unlike hsk_raycast, which overwrites the tracker's pose and model maps.  No flush of the
+ * deferred weights is needed (a march reads TSDF values only).  The images come back through the product buffer and the
+ * pinned staging pair (hsk_prepare_readout covers the first-use costs); nothing is allocated on a later call of the same size. */
+#define HSK_VIEW_LAMBERT   0  /* grey: one point light, upstream's generateImage (ambient 50, diffuse 205, no specular)  */
+#define HSK_VIEW_NORMALS   1  /* the world normal as a colour: (n * 0.5 + 0.5) * 255 per channel; no normal: background  */
+#define HSK_VIEW_COLOR     2  /* the colour volume, unlit (needs hsk_enable_color: HSK_ERR_STATE)                        */
+#define HSK_VIEW_COLOR_LIT 3  /* the colour volume times the Lambert term                                                */
+typedef struct {
+  int width, height;     /* 1..4096 each, any value                                                                    */
+  float fx, fy, cx, cy;  /* fx, fy finite and positive                                                                 */
+  float pose[16];        /* row-major cam->world, as everywhere on this ABI; ignored when follow != 0                  */
+  int follow;            /* 1: the tracker's current pose, read on the device, so the host need not know it: the pose
+                            of the last frame enqueued before this call (after a tracking loss: what hsk_get_pose gives) */
+  int mode;              /* HSK_VIEW_*                                                                                 */
+  float light[3];        /* point light; light_in_camera != 0: in camera coordinates (it moves with the camera)        */
+  int light_in_camera;
+  uint8_t background[3]; /* every pixel without a hit                                                                  */
+} hsk_view;
+/* the context's sensor camera, follow = 1, HSK_VIEW_LAMBERT, the light at the camera ((0, 0, 0) in camera coordinates), black
+ * background, the identity as pose.  k == NULL: the camera of hsk_default_config; v == NULL: nothing */
+void hsk_default_view(const hsk_ctx* k, hsk_view* v);
+/* Every output may be NULL.  rgb: 3 bytes per pixel, row-major; depth_mm: the hit's z along the optical axis in millimetres
+ * (the sensor's own unit: a rendered depth image can be fed back as a frame), 0 without a hit or outside 1..65535; vmap, nmap:
+ * the raycast's world vertex and normal maps for this camera, 3 planes of h*w floats each, NaN = no hit / no normal, bit for
+ * bit what hsk_raycast gives for the same camera and pose; *n_hit: pixels with a hit; *n_uncolored: hits whose voxel has
+ * colour weight 0 (colour modes; they come out (0, 0, 0)).  The colour of a hit is that of the voxel containing the vertex
+ * (nearest voxel, no filtering).  HSK_ERR_ARG: NULL context or view, a size outside 1..4096, fx or fy not finite and
+ * positive, an unknown mode; HSK_ERR_STATE: a colour mode without hsk_enable_color, a slab of a group or any context
+ * that stores part of the volume (a slab owns only its own march steps). */
+int hsk_render_view(hsk_ctx* k, const hsk_view* v, uint8_t* rgb /* 3*w*h */, uint16_t* depth_mm /* w*h */, float* vmap /* 3*h*w SoA */,
+                    float* nmap /* 3*h*w SoA */, size_t* n_hit, size_t* n_uncolored);
+/* binary Netpbm files of a view: P6 (8-bit RGB) and P5 with maxval 65535 (16-bit, most significant byte first).  w, h in
+ * 1..4096; HSK_ERR_ARG for a NULL pointer or a size outside that, HSK_ERR_STATE for an I/O failure */
+int hsk_write_ppm(const char* path, const uint8_t* rgb, int w, int h);
+int hsk_write_pgm16(const char* path, const uint16_t* depth_mm, int w, int h);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
