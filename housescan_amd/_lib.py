@@ -54,6 +54,23 @@ class HskView(C.Structure):
     ]
 
 
+HSK_PROJ_PINHOLE, HSK_PROJ_ORTHO = 0, 1
+HSK_MAX_CLIP = 4
+
+
+class HskSection(C.Structure):
+    """Mirror of `hsk_section` (include/hskinfu.h)."""
+
+    _fields_ = [
+        ("view", HskView),
+        ("projection", C.c_int),
+        ("light_directional", C.c_int),
+        ("n_clip", C.c_int),
+        ("clip", (C.c_float * 4) * HSK_MAX_CLIP),
+        ("cut_rgb", C.c_uint8 * 3),
+    ]
+
+
 # every symbol include/hskinfu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -102,6 +119,11 @@ SYMBOLS = {
                                             C.POINTER(C.c_size_t)]),
     "hsk_default_view": (None, [_P, C.POINTER(HskView)]),
     "hsk_render_view": (C.c_int, [_P, C.POINTER(HskView), _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "hsk_default_section": (None, [_P, C.POINTER(HskSection)]),
+    "hsk_render_section": (C.c_int, [_P, C.POINTER(HskSection), _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_size_t)]),
+    "hsk_section_in_room": (C.c_int, [C.POINTER(HskSection), _F, C.POINTER(HskSection)]),
+    "hsk_composite_views": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, _P, _P, _P, _P]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_write_pgm16": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int]),

@@ -45,6 +45,21 @@ void launch_render_view(hipStream_t s, const void* vol, const unsigned* colv, co
                         const unsigned char background[3], unsigned char* rgb, unsigned short* depth, float* vmap, float* nmap,
                         unsigned long long* counts);
 int view_warm();      // loads view.hip's code object (hsk_prepare_readout); a hipError_t
+// section views (section.hip): launch_render_view's arguments, and what makes a section of a view -- the projection (HSK_PROJ_*),
+// the clip planes (keep a x + b y + c z + d >= 0, world coordinates), the kind of light and the colour of a cut pixel; counts: a
+// wave adds its shown hits to word 0, those without colour to word 1 and its cut pixels to word 2 of its tile's slot
+struct SectionPlane {
+  float a, b, c, d;
+};
+struct SectionClip {
+  int projection, n_clip;
+  SectionPlane plane[4];
+};
+void launch_render_section(hipStream_t s, const void* vol, const unsigned* colv, const ViewCam* cam, const VolParams& vp, int W, int H,
+                           Intr in, const unsigned* flags, int mode, const float light[3], int light_in_camera, int light_directional,
+                           const unsigned char background[3], const unsigned char cut_rgb[3], const SectionClip& clip,
+                           unsigned char* rgb, unsigned short* depth, float* vmap, float* nmap, unsigned long long* counts);
+int section_warm();   // loads section.hip's code object (hsk_prepare_readout); a hipError_t
 void launch_resolve(hipStream_t s, const int* keys_local, const int* keys_min, const float* vmap, const float* nmap,
                     int* bits, int P);
 // the end of a z-slab frame in ONE launch: k_adopt + k_resize_maps2 (+ the report into the host ring) fused (kernels_image.hip)

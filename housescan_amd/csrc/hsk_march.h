@@ -1,8 +1,9 @@
 // hsk_march.h -- what the TSDF march's kernels share (raycast.hip: k_raycast, the tracker's model frame; view.hip:
 // k_render_view, a scene image from any camera): the voxel look-ups, the trilinear sample, the march's constants and its
-// wave-wide minimum.  The march itself is two pieces of function-body text, hsk_march_stage.h and hsk_march_rays.h, that
-// each kernel includes at its place: k_raycast compiles from exactly the tokens it had when the text stood in raycast.hip,
-// so its machine code cannot move when the other kernel changes (tools/isa_compare.py checks it).
+// wave-wide minimum.  The march itself is three pieces of function-body text -- hsk_march_stage.h, hsk_march_rays.h (the pinhole
+// ray) and hsk_march_loop.h -- that each kernel includes at its place: k_raycast compiles from exactly the tokens it had when
+// the text stood in raycast.hip, so its machine code cannot move when another kernel changes (tools/isa_compare.py checks
+// it).  section.hip's k_render_section puts its own ray piece between the stage and the loop.
 #pragma once
 #include "hsk_dev.h"
 // ------------------------------------------------------------------------------------------------------

@@ -1613,6 +1613,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) HIPCHK(k, (hipError_t)extract_warm());  // (the read-out kernels' code object: 0.7 ms of a process's first product)
   if (r == HSK_OK) r = ensure_view(k);
   if (r == HSK_OK) HIPCHK(k, (hipError_t)view_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)section_warm());
   return r;
 }
 
@@ -1968,6 +1969,95 @@ extern "C" int hsk_render_view(hsk_ctx* k, const hsk_view* v, uint8_t* rgb, uint
     uncolored += h_counts[16 * i + 1];
   }
   if (n_hit) *n_hit = (size_t)hits;
+  if (n_uncolored) *n_uncolored = (size_t)uncolored;
+  return HSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// section views (include/hskinfu.h "Section views")
+// ------------------------------------------------------------------------------------------------------
+extern "C" void hsk_default_section(const hsk_ctx* k, hsk_section* s) {
+  if (!s) return;
+  memset(s, 0, sizeof(*s));
+  hsk_default_view(k, &s->view);
+  s->projection = HSK_PROJ_PINHOLE;
+  s->cut_rgb[0] = 255;
+  s->cut_rgb[1] = 96;
+  s->cut_rgb[2] = 0;
+}
+
+// hsk_render_view's call with a section's ray and tail: the same blocks, buffers and order of work on the stream
+extern "C" int hsk_render_section(hsk_ctx* k, const hsk_section* s, uint8_t* rgb, uint16_t* depth_mm, float* vmap, float* nmap,
+                                  size_t* n_hit, size_t* n_cut, size_t* n_uncolored) {
+  if (!k) return HSK_ERR_ARG;
+  if (!s) return fail(k, HSK_ERR_ARG, "hsk_render_section: section is null");
+  const hsk_view* v = &s->view;
+  if (v->width < 1 || v->width > 4096 || v->height < 1 || v->height > 4096)
+    return fail(k, HSK_ERR_ARG, "hsk_render_section: width and height must lie in 1..4096");
+  if (!(std::isfinite(v->fx) && std::isfinite(v->fy) && v->fx > 0.0f && v->fy > 0.0f))
+    return fail(k, HSK_ERR_ARG, "hsk_render_section: fx and fy must be finite and positive");
+  if (v->mode < HSK_VIEW_LAMBERT || v->mode > HSK_VIEW_COLOR_LIT) return fail(k, HSK_ERR_ARG, "hsk_render_section: unknown mode");
+  if (s->projection != HSK_PROJ_PINHOLE && s->projection != HSK_PROJ_ORTHO)
+    return fail(k, HSK_ERR_ARG, "hsk_render_section: unknown projection");
+  if (s->n_clip < 0 || s->n_clip > HSK_MAX_CLIP) return fail(k, HSK_ERR_ARG, "hsk_render_section: n_clip must lie in 0..HSK_MAX_CLIP");
+  SectionClip clip;
+  memset(&clip, 0, sizeof(clip));
+  clip.projection = s->projection;
+  clip.n_clip = s->n_clip;
+  for (int c = 0; c < s->n_clip; ++c) {
+    const float* p = s->clip[c];
+    if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3])))
+      return fail(k, HSK_ERR_ARG, "hsk_render_section: a clip plane has a non-finite number");
+    if (p[0] == 0.0f && p[1] == 0.0f && p[2] == 0.0f) return fail(k, HSK_ERR_ARG, "hsk_render_section: a clip plane has no normal (a = b = c = 0)");
+    clip.plane[c] = {p[0], p[1], p[2], p[3]};
+  }
+  const bool colour = v->mode == HSK_VIEW_COLOR || v->mode == HSK_VIEW_COLOR_LIT;
+  if (k->group_slab || k->vp.zs0 != 0 || k->vp.nzs != k->vp.Z || k->vp.zo0 != 0 || k->vp.zo1 != k->vp.Z)
+    return fail(k, HSK_ERR_STATE, "hsk_render_section: not for a slab (it owns only its own march steps; sections of a group are not composited)");
+  if (colour && !k->d_color) return fail(k, HSK_ERR_STATE, "colour is not enabled (hsk_enable_color)");
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  int r = ensure_view(k);
+  if (r != HSK_OK) return r;
+  const size_t P = (size_t)v->width * v->height;
+  ProductLayout lay;
+  const size_t o_rgb = lay.take(rgb ? P * 3 : 0), o_dep = lay.take(depth_mm ? P * 2 : 0), o_v = lay.take(vmap ? P * 12 : 0),
+               o_n = lay.take(nmap ? P * 12 : 0);
+  r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  char* d = (char*)k->d_out;
+  unsigned char* d_rgb = rgb ? (unsigned char*)(d + o_rgb) : nullptr;
+  unsigned short* d_dep = depth_mm ? (unsigned short*)(d + o_dep) : nullptr;
+  float* d_v = vmap ? (float*)(d + o_v) : nullptr;
+  float* d_n = nmap ? (float*)(d + o_n) : nullptr;
+  const ViewCam* cam = (const ViewCam*)k->d_st;
+  if (!v->follow) {
+    ViewCam* hc = (ViewCam*)k->h_view;   // (free: every call waits for its own result before it returns)
+    pose16_to_rt(v->pose, hc->R, hc->t);
+    HIPCHK(k, hipMemcpyAsync(k->d_view, hc, sizeof(ViewCam), hipMemcpyHostToDevice, k->stream));
+    cam = (const ViewCam*)k->d_view;
+  }
+  unsigned long long* d_counts = (unsigned long long*)((char*)k->d_view + HSK_VIEW_COUNTS_AT);
+  unsigned long long* h_counts = (unsigned long long*)((char*)k->h_view + HSK_VIEW_COUNTS_AT);
+  HIPCHK(k, hipMemsetAsync(d_counts, 0, HSK_VIEW_COUNTS_BYTES, k->stream));
+  const Intr in = {v->fx, v->fy, v->cx, v->cy};
+  launch_render_section(k->stream, k->d_vol, k->d_color, cam, k->vp, v->width, v->height, in, k->d_flags, v->mode, v->light,
+                        v->light_in_camera, s->light_directional != 0, v->background, s->cut_rgb, clip, d_rgb, d_dep, d_v, d_n, d_counts);
+  HIPCHK(k, hipGetLastError());
+  HIPCHK(k, hipMemcpyAsync(h_counts, d_counts, HSK_VIEW_COUNTS_BYTES, hipMemcpyDeviceToHost, k->stream));
+  if (rgb) r = copy_out(k, rgb, d_rgb, P * 3);
+  if (r == HSK_OK && depth_mm) r = copy_out(k, depth_mm, d_dep, P * 2);
+  if (r == HSK_OK && vmap) r = copy_out(k, vmap, d_v, P * 12);
+  if (r == HSK_OK && nmap) r = copy_out(k, nmap, d_n, P * 12);
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  unsigned long long hits = 0, uncolored = 0, cuts = 0;
+  for (int i = 0; i < HSK_VIEW_COUNT_SLOTS; ++i) {
+    hits += h_counts[16 * i];
+    uncolored += h_counts[16 * i + 1];
+    cuts += h_counts[16 * i + 2];
+  }
+  if (n_hit) *n_hit = (size_t)hits;
+  if (n_cut) *n_cut = (size_t)cuts;
   if (n_uncolored) *n_uncolored = (size_t)uncolored;
   return HSK_OK;
 }

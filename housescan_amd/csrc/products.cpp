@@ -658,3 +658,95 @@ extern "C" int hsk_transform_normals(const float* n, size_t count, const float m
   }
   return HSK_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------
+// Section views on the host seam (include/hskinfu.h "Section views"): a house section in a room's frame, and the
+// rooms' images into one.
+// ------------------------------------------------------------------------------------------------------
+// M = room -> house, rigid: M^-1 = (R^T, -R^T t).  Everything in binary64 from the binary32 inputs, one rounding at the end.
+extern "C" int hsk_section_in_room(const hsk_section* house, const float room_xf[16], hsk_section* room) {
+  if (!house || !room_xf || !room) return HSK_ERR_ARG;
+  if (house->view.follow != 0) return HSK_ERR_ARG;
+  if (house->n_clip < 0 || house->n_clip > HSK_MAX_CLIP) return HSK_ERR_ARG;
+  const float* m = room_xf;
+  if (!(m[12] == 0.0f && m[13] == 0.0f && m[14] == 0.0f && m[15] == 1.0f)) return HSK_ERR_ARG;
+  double R[3][3], t[3];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i][j] = (double)m[4 * i + j];
+    t[i] = (double)m[4 * i + 3];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = (R[0][i] * R[0][j] + R[1][i] * R[1][j]) + R[2][i] * R[2][j];
+      if (!(std::fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-4)) return HSK_ERR_ARG;   // (NaN: refused)
+    }
+  hsk_section out = *house;
+  // a point p -> R^T (p - t); a direction v -> R^T v
+  auto point = [&](const double p[3], double q[3]) {
+    const double e0 = p[0] - t[0], e1 = p[1] - t[1], e2 = p[2] - t[2];
+    for (int i = 0; i < 3; ++i) q[i] = (R[0][i] * e0 + R[1][i] * e1) + R[2][i] * e2;
+  };
+  auto direction = [&](const double v[3], double q[3]) {
+    for (int i = 0; i < 3; ++i) q[i] = (R[0][i] * v[0] + R[1][i] * v[1]) + R[2][i] * v[2];
+  };
+  // pose: the columns of its rotation are directions, its translation a point
+  const float* hp = house->view.pose;
+  for (int c = 0; c < 3; ++c) {
+    const double v[3] = {(double)hp[c], (double)hp[4 + c], (double)hp[8 + c]};
+    double q[3];
+    direction(v, q);
+    for (int i = 0; i < 3; ++i) out.view.pose[4 * i + c] = (float)q[i];
+  }
+  {
+    const double p[3] = {(double)hp[3], (double)hp[7], (double)hp[11]};
+    double q[3];
+    point(p, q);
+    for (int i = 0; i < 3; ++i) out.view.pose[4 * i + 3] = (float)q[i];
+  }
+  // planes: (n, d) M = (n R, n . t + d)
+  for (int c = 0; c < house->n_clip; ++c) {
+    const double n[3] = {(double)house->clip[c][0], (double)house->clip[c][1], (double)house->clip[c][2]};
+    for (int j = 0; j < 3; ++j) out.clip[c][j] = (float)((n[0] * R[0][j] + n[1] * R[1][j]) + n[2] * R[2][j]);
+    out.clip[c][3] = (float)(((n[0] * t[0] + n[1] * t[1]) + n[2] * t[2]) + (double)house->clip[c][3]);
+  }
+  if (!house->view.light_in_camera) {
+    const double l[3] = {(double)house->view.light[0], (double)house->view.light[1], (double)house->view.light[2]};
+    double q[3];
+    if (house->light_directional)
+      direction(l, q);
+    else
+      point(l, q);
+    for (int i = 0; i < 3; ++i) out.view.light[i] = (float)q[i];
+  }
+  *room = out;
+  return HSK_OK;
+}
+
+extern "C" int hsk_composite_views(int n, const uint8_t* const* rgb, const uint16_t* const* depth_mm, int w, int h,
+                                   const uint8_t background[3], uint8_t* out_rgb, uint16_t* out_depth_mm, int32_t* out_index) {
+  if (n < 1 || w < 1 || w > 4096 || h < 1 || h > 4096 || !depth_mm) return HSK_ERR_ARG;
+  if (out_rgb && (!rgb || !background)) return HSK_ERR_ARG;
+  for (int v = 0; v < n; ++v)
+    if (!depth_mm[v] || (out_rgb && !rgb[v])) return HSK_ERR_ARG;
+  const size_t P = (size_t)w * h;
+  for (size_t i = 0; i < P; ++i) {
+    int best = -1;
+    unsigned bd = 0;
+    for (int v = 0; v < n; ++v) {
+      const unsigned d = depth_mm[v][i];
+      if (d != 0 && (best < 0 || d < bd)) {
+        best = v;
+        bd = d;
+      }
+    }
+    if (out_rgb) {
+      const uint8_t* src = best < 0 ? background : rgb[best] + 3 * i;
+      out_rgb[3 * i] = src[0];
+      out_rgb[3 * i + 1] = src[1];
+      out_rgb[3 * i + 2] = src[2];
+    }
+    if (out_depth_mm) out_depth_mm[i] = (uint16_t)bd;
+    if (out_index) out_index[i] = best;
+  }
+  return HSK_OK;
+}

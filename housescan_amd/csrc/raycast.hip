@@ -110,6 +110,7 @@ __global__ __launch_bounds__(RC_BLOCK, RC_WPE) void k_raycast(RcArgs a) {
   const bool in_img = x < W && y < H;
   if (st->lost) return;
 #include "hsk_march_rays.h"
+#include "hsk_march_loop.h"
   // the tail of the argument block, fetched now (the empty asm hides where the pointer comes from, so the loads cannot
   // be moved up across the march)
   const RcTail tl = RC_ARG(RcTail, tail);

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(RC_BLOCK, RC_WPE) void k_render_view(ViewArgs a) {
   // (lanes outside the image stay in the wave as ended rays: hsk_march_rays.h)
   const bool in_img = x < W && y < H;
 #include "hsk_march_rays.h"
+#include "hsk_march_loop.h"
   (void)key;
   const ViewTail tl = VW_ARG(ViewTail, tail);
   const ViewCam* __restrict__ cam = VW_ARG(ViewCamPtr, cam);   // (fetched again: the pointer need not live through the march)

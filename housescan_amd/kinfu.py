@@ -376,6 +376,66 @@ class KinfuTracker:
         out["n_hit"], out["n_uncolored"] = nh.value, nu.value
         return out
 
+    # ---- section views ---------------------------------------------------------------------------------
+    def default_section(self):
+        """default_view()'s camera as a section: pinhole, a point light, no clip planes, cut colour (255, 96, 0) (an
+        `_lib.HskSection` to edit and pass on)"""
+        s = _lib.HskSection()
+        self.lib.hsk_default_section(self.h, C.byref(s))
+        return s
+
+    def render_section(self, section=None, *, width=None, height=None, fx=None, fy=None, cx=None, cy=None, pose=None, mode=None,
+                       light=None, light_in_camera=None, background=None, projection=None, light_directional=None, clip=None,
+                       cut_rgb=None, rgb=True, depth=True, vmap=False, nmap=False):
+        """a floor plan, elevation or dollhouse view of what has been fused so far (hsk_render_section), legal with frames in
+        flight.  `section`: an HskSection (default: default_section()); the keywords override its fields, the view's as in
+        render_view.  projection: _lib.HSK_PROJ_PINHOLE or HSK_PROJ_ORTHO (fx, fy are then pixels per metre); clip: up to four
+        planes (a, b, c, d), keep a x + b y + c z + d >= 0 in world coordinates; light_directional: `light` is a direction
+        towards the light.  -> render_view's dict plus n_cut; vmap / nmap are NaN except on shown hits."""
+        if section is None:
+            section = self.default_section()
+        s = _lib.HskSection.from_buffer_copy(section)
+        v = s.view
+        for name, val in (("width", width), ("height", height), ("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("mode", mode),
+                          ("light_in_camera", light_in_camera)):
+            if val is not None:
+                setattr(v, name, val)
+        if pose is not None:
+            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
+            v.follow = 0
+        if light is not None:
+            v.light[:] = [float(x) for x in light]
+        if background is not None:
+            v.background[:] = [int(x) for x in background]
+        if projection is not None:
+            s.projection = int(projection)
+        if light_directional is not None:
+            s.light_directional = int(light_directional)
+        if clip is not None:
+            planes = np.asarray(clip, np.float32).reshape(-1, 4)
+            s.n_clip = len(planes)       # (more than HSK_MAX_CLIP: the call refuses)
+            for c, pl in enumerate(planes[:_lib.HSK_MAX_CLIP]):
+                s.clip[c][:] = [float(x) for x in pl]
+        if cut_rgb is not None:
+            s.cut_rgb[:] = [int(x) for x in cut_rgb]
+        w, h = v.width, v.height
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
+        out = {}
+        if rgb and ok:
+            out["rgb"] = np.empty((h, w, 3), np.uint8)
+        if depth and ok:
+            out["depth"] = np.empty((h, w), np.uint16)
+        if vmap and ok:
+            out["vmap"] = np.empty((3, h, w), np.float32)
+        if nmap and ok:
+            out["nmap"] = np.empty((3, h, w), np.float32)
+        ptr = lambda k: out[k].ctypes.data if k in out else None  # noqa: E731
+        nh, nc, nu = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_render_section(self.h, C.byref(s), ptr("rgb"), ptr("depth"), ptr("vmap"), ptr("nmap"), C.byref(nh),
+                                             C.byref(nc), C.byref(nu)))
+        out["n_hit"], out["n_cut"], out["n_uncolored"] = nh.value, nc.value, nu.value
+        return out
+
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
         return self.lib.hsk_stream(self.h)

@@ -178,6 +178,40 @@ def write_pgm16(path, depth_mm):
     _ck(_lib.load().hsk_write_pgm16(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]), "hsk_write_pgm16")
 
 
+def section_in_room(house, room_xf):
+    """a section given in house coordinates (an `_lib.HskSection`, follow = 0) -> the same section in the frame of the room that
+    the rigid 4x4 room -> house matrix `room_xf` (its .xf) places in the house (hsk_section_in_room)"""
+    m = np.ascontiguousarray(room_xf, np.float32).reshape(16)
+    room = _lib.HskSection()
+    _ck(_lib.load().hsk_section_in_room(C.byref(house), m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(room)), "hsk_section_in_room")
+    return room
+
+
+def composite_views(rgbs, depths, background=(0, 0, 0), *, want_rgb=True):
+    """images of one size, one per room (KinfuTracker.render_section's rgb and depth) -> (rgb, depth, index): per pixel the
+    view with the smallest non-zero depth, the lowest index on a tie; background, 0 and -1 where no view has a depth
+    (hsk_composite_views).  rgbs may be None with want_rgb=False (rgb is then None)"""
+    deps = [np.ascontiguousarray(d, np.uint16) for d in depths]
+    n = len(deps)
+    if n < 1 or any(d.shape != deps[0].shape or d.ndim != 2 for d in deps):
+        raise ValueError("composite_views: at least one (h, w) depth image, all of one size")
+    h, w = deps[0].shape
+    cols = None
+    if want_rgb:
+        cols = [np.ascontiguousarray(c, np.uint8) for c in rgbs]
+        if len(cols) != n or any(c.shape != (h, w, 3) for c in cols):
+            raise ValueError("composite_views: one (h, w, 3) rgb image per depth image")
+    bg = np.asarray(background, np.uint8).reshape(3).copy()
+    out_rgb = np.empty((h, w, 3), np.uint8) if want_rgb else None
+    out_dep = np.empty((h, w), np.uint16)
+    out_idx = np.empty((h, w), np.int32)
+    dp = (C.c_void_p * n)(*[d.ctypes.data for d in deps])
+    cp = (C.c_void_p * n)(*[c.ctypes.data for c in cols]) if want_rgb else None
+    _ck(_lib.load().hsk_composite_views(n, cp, dp, w, h, bg.ctypes.data, None if out_rgb is None else out_rgb.ctypes.data,
+                                        out_dep.ctypes.data, out_idx.ctypes.data), "hsk_composite_views")
+    return out_rgb, out_dep, out_idx
+
+
 def write_xf(path, m):
     lib = _lib.load()
     a = np.ascontiguousarray(m, np.float32).reshape(16)

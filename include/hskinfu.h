@@ -242,6 +242,49 @@ int hsk_render_view(hsk_ctx* k, const hsk_view* v, uint8_t* rgb /* 3*w*h */, uin
 int hsk_write_ppm(const char* path, const uint8_t* rgb, int w, int h);
 int hsk_write_pgm16(const char* path, const uint16_t* depth_mm, int w, int h);
 
+/* ---- Section views: floor plans, elevations and "dollhouse" views (DESIGN.md 3.9 the kernel, 8c the rule).  A room is
+ * scanned from inside, so a camera outside it meets the back of a wall or ceiling first and sees nothing.  A section is a
+ * scene view whose rays may be parallel (an orthographic camera) and start on clip planes inside the volume: what the planes
+ * cut away is not shown, and where a plane cuts through the material of a wall (a negative TSDF) the pixel gets cut_rgb, so
+ * walls show as outlines.  With HSK_PROJ_PINHOLE, no planes and a point light hsk_render_section gives hsk_render_view's
+ * outputs byte for byte. */
+#define HSK_PROJ_PINHOLE 0
+#define HSK_PROJ_ORTHO   1   /* parallel rays along the camera's z axis; view.fx, view.fy are PIXELS PER METRE */
+#define HSK_MAX_CLIP     4
+typedef struct {
+  hsk_view view;                /* size, fx, fy, cx, cy, pose, follow, mode, light, light_in_camera, background: as for hsk_render_view */
+  int projection;               /* HSK_PROJ_* */
+  int light_directional;        /* 0: view.light is a point (8b step 4); 1: a direction TOWARDS the light */
+  int n_clip;                   /* 0..HSK_MAX_CLIP */
+  float clip[HSK_MAX_CLIP][4];  /* keep a x + b y + c z + d >= 0, in the volume's (world) coordinates */
+  uint8_t cut_rgb[3];           /* colour of a pixel whose ray starts on a clip plane inside a negative TSDF */
+} hsk_section;
+/* hsk_default_view's values, HSK_PROJ_PINHOLE, a point light, no planes, cut_rgb (255, 96, 0).  s == NULL: nothing */
+void hsk_default_section(const hsk_ctx* k, hsk_section* s);
+/* Outputs, enqueue and ordering contract as hsk_render_view's (legal between submit and wait of pipelined frames; writes nothing
+ * the tracker reads; no flush; product buffer and pinned pair; nothing allocated on a later call of the same size).  A pixel is
+ * CUT (its ray starts on a clip plane, inside the volume's box, in a voxel with a negative TSDF: cut_rgb, the depth of that
+ * point), else a HIT (the march's vertex, if it satisfies every plane), else background.  An orthographic camera's depth_mm is
+ * the distance from the camera's plane: a top-down depth image is a height map.  vmap, nmap: NaN except on shown hits;
+ * *n_hit, *n_cut: the pixels shown as each; *n_uncolored: as hsk_render_view's, over shown hits.  The march does not stop at a
+ * far-side plane; a hit beyond one is not shown.  HSK_ERR_ARG: what hsk_render_view refuses, an unknown projection, n_clip
+ * outside 0..HSK_MAX_CLIP, a plane with a non-finite number or a = b = c = 0; HSK_ERR_STATE: as hsk_render_view. */
+int hsk_render_section(hsk_ctx* k, const hsk_section* s, uint8_t* rgb /* 3*w*h */, uint16_t* depth_mm /* w*h */,
+                       float* vmap /* 3*h*w SoA */, float* nmap /* 3*h*w SoA */, size_t* n_hit, size_t* n_cut, size_t* n_uncolored);
+/* host only: a section given in HOUSE coordinates, in the frame of a room placed in the house by the rigid .xf matrix
+ * room_xf = M (room -> house, row-major, p_house = M p_room): pose M^-1 pose, each plane (a b c d) M, a world-space point
+ * light M^-1 l, a world-space direction R_M^T l; camera-space lights and everything else copied.  Computed in binary64,
+ * rounded once.  `room` may be `house`.  HSK_ERR_ARG: a NULL pointer, follow != 0, M's last row not (0 0 0 1),
+ * max |R_M^T R_M - I| > 1e-4 (not rigid).  Rigid maps keep the distance from the camera's plane or centre, so the depths of
+ * the rooms' sections made from one house section compare: hsk_composite_views. */
+int hsk_section_in_room(const hsk_section* house, const float room_xf[16], hsk_section* room);
+/* host only: n >= 1 views of one size into one image.  Per pixel the view with the smallest non-zero depth wins (the lowest
+ * index on a tie): its rgb, depth and index are written; a pixel without a depth in any view gets background, 0 and -1.
+ * Every output may be NULL; rgb may be NULL when out_rgb is.  HSK_ERR_ARG: n < 1, w or h outside 1..4096, depth_mm or one
+ * of its entries NULL, rgb (or an entry) or background NULL while out_rgb is given. */
+int hsk_composite_views(int n, const uint8_t* const* rgb, const uint16_t* const* depth_mm, int w, int h,
+                        const uint8_t background[3], uint8_t* out_rgb, uint16_t* out_depth_mm, int32_t* out_index);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */

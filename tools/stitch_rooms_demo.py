@@ -11,12 +11,18 @@ emulated: of the suggested corners, the 8 nearest to the true room corners are a
 --indexed-mesh: each room's mesh comes off the GPU indexed, with normals (hsk_extract_mesh_indexed), is written as
 <room_dir>/mesh.ply, and house_mesh.ply concatenates the rooms' meshes moved by their .xf (positions by transform_cloud,
 normals by transform_normals, faces offset by each room's vertex base) -- no host weld.
+
+--floorplan: behind the stitch, one top-down orthographic section of the whole house, cut at mid height, is taken into every
+room's frame by its .xf (hsk_section_in_room), rendered from the room's volume on the GPU (hsk_render_section) and the rooms'
+images are composited (hsk_composite_views): house_floorplan.ppm (walls as outlines in the cut colour) and house_heights.pgm
+(16-bit millimetres below the camera's plane: a height map).
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -24,14 +30,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=False):
+def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=False, keep=False):
     """the three-turn scan inside room `variant`; returns (cloud, worst translation error [m], lost frames, fps).
     (Round 6: the frames go through the pipelined pair and the clock covers the tracker only -- the poses and the errors are
     computed outside it; the synchronous call with a pose and a norm per frame inside the loop made "2050 frames/s" of a
     scan that runs at 4900.)"""
     gts = [hsk.synth_room_pose(variant, k, frames) for k in range(frames + 1)]
     trk = hsk.KinfuTracker(n=n, init_pose=gts[0], device_id=device_id)
-    depth = [hsk.synth_room_depth(variant, p) for p in gts]
+    with ThreadPoolExecutor(8) as ex:   # (the renderer releases the GIL)
+        depth = list(ex.map(lambda p: hsk.synth_room_depth(variant, p), gts))
     got = []
     t0 = time.perf_counter()
     trk.submit_frame(depth[0])
@@ -48,6 +55,8 @@ def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=Fal
         mesh = trk.extract_mesh_indexed(normals=True, rgb=False)[:3]   # (vertices, faces, normals)
     else:
         mesh = trk.extract_mesh(cubes=True)[0] if with_mesh else None   # marching cubes: the form upstream's .ply export has
+    if keep:   # (the volume stays on the device for --floorplan; the caller closes the tracker)
+        return cloud, worst, lost, len(depth) / dt, mesh, trk
     trk.close()
     if with_mesh:
         return cloud, worst, lost, len(depth) / dt, mesh
@@ -98,6 +107,53 @@ def stitch(hsk, room_dirs, variants, log=print):
     return hs, rooms, rm
 
 
+def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
+    """the house from above: one section in house coordinates, each room's share rendered in the room's own frame"""
+    from housescan_amd import _lib
+    from housescan_amd import products as P
+    t0 = time.perf_counter()
+    Ms = [np.asarray(M, np.float64) for M in Ms]
+    corners = np.concatenate([true_corners(hsk.synth_room_extents(v)) @ M[:3, :3].T + M[:3, 3] for v, M in zip(variants, Ms)])
+    up = Ms[0][:3, :3] @ np.array([0.0, -1.0, 0.0])          # a scan's y axis points down
+    up /= np.linalg.norm(up)
+    z = -up
+    x = np.eye(3)[int(np.argmin(np.abs(up)))]
+    x = x - (x @ z) * z
+    x /= np.linalg.norm(x)
+    y = np.cross(z, x)
+    u, v, h = corners @ x, corners @ y, corners @ up
+    margin = 0.2
+    W = min(4096, int(np.ceil((u.max() - u.min() + 2 * margin) * px_per_m)))
+    H = min(4096, int(np.ceil((v.max() - v.min() + 2 * margin) * px_per_m)))
+    eye = 0.5 * (u.max() + u.min()) * x + 0.5 * (v.max() + v.min()) * y + (h.max() + 0.5) * up
+    house = _lib.HskSection()
+    _lib.load().hsk_default_section(None, house)
+    hv = house.view
+    hv.width, hv.height, hv.fx, hv.fy, hv.cx, hv.cy = W, H, px_per_m, px_per_m, (W - 1) / 2.0, (H - 1) / 2.0
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = x, y, z, eye
+    hv.pose[:] = [float(a) for a in pose.astype(np.float32).reshape(16)]
+    hv.follow, hv.mode, hv.light_in_camera = 0, _lib.HSK_VIEW_LAMBERT, 0
+    light = up + 0.3 * x + 0.2 * y
+    hv.light[:] = [float(a) for a in light]
+    hv.background[:] = [255, 255, 255]
+    house.projection, house.light_directional, house.n_clip = _lib.HSK_PROJ_ORTHO, 1, 1
+    mid = 0.5 * (h.max() + h.min())
+    house.clip[0][:] = [float(-up[0]), float(-up[1]), float(-up[2]), float(mid)]     # keep what lies below mid height
+    rgbs, deps, counts = [], [], []
+    for trk, M in zip(trackers, Ms):
+        r = trk.render_section(P.section_in_room(house, M.astype(np.float32)))
+        rgbs.append(r["rgb"])
+        deps.append(r["depth"])
+        counts.append({"hit": r["n_hit"], "cut": r["n_cut"]})
+    rgb, dep, idx = P.composite_views(rgbs, deps, (255, 255, 255))
+    ms = 1e3 * (time.perf_counter() - t0)
+    P.write_ppm(os.path.join(out, "house_floorplan.ppm"), rgb)
+    P.write_pgm16(os.path.join(out, "house_heights.pgm"), dep)
+    return {"width": W, "height": H, "px_per_m": px_per_m, "rooms": counts, "pixels_per_room": [int((idx == i).sum()) for i in range(len(Ms))],
+            "end_to_end_ms": round(ms, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rooms", type=int, default=2)
@@ -105,6 +161,7 @@ def main():
     ap.add_argument("--frames", type=int, default=720, help="frames of the three-turn room trajectory")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "stitch"))
     ap.add_argument("--indexed-mesh", action="store_true", help="rooms' meshes indexed with normals: <room_dir>/mesh.ply, no host weld")
+    ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
     args = ap.parse_args()
 
     import housescan_amd as hsk
@@ -113,9 +170,12 @@ def main():
 
     os.makedirs(args.out, exist_ok=True)
     report = {"rooms": []}
-    dirs, variants, meshes = [], list(range(args.rooms)), []
+    dirs, variants, meshes, trackers = [], list(range(args.rooms)), [], []
     for v in variants:
-        cloud, worst, lost, fps, mesh = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh)
+        res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh, keep=args.floorplan)
+        cloud, worst, lost, fps, mesh = res[:5]
+        if args.floorplan:
+            trackers.append(res[5])
         meshes.append(mesh)
         d = os.path.join(args.out, f"room{v}", "walls")
         planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, dist_thresh=0.025, min_fraction=0.03)
@@ -153,6 +213,10 @@ def main():
         moved = [P.transform_cloud(m.reshape(-1, 3), hs.room_projection(rid)).reshape(-1, 3, 3) for m, rid in zip(meshes, rooms)]
         nv, nf = P.write_ply_mesh(os.path.join(args.out, "house_mesh.ply"), np.concatenate(moved))
     report["house_mesh"] = {"vertices": nv, "faces": nf}
+    if args.floorplan:
+        report["floorplan"] = floorplan(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out)
+        for trk in trackers:
+            trk.close()
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
     with open(os.path.join(args.out, "report.json"), "w") as f:
