@@ -71,6 +71,16 @@ class HskSection(C.Structure):
     ]
 
 
+class HskFuseStats(C.Structure):
+    """Mirror of `hsk_fuse_stats` (include/hskinfu.h)."""
+
+    _fields_ = [
+        ("n_fused", C.c_uint64), ("n_colored", C.c_uint64),
+        ("chunks_total", C.c_uint64), ("chunks_swept", C.c_uint64),
+        ("box", C.c_int32 * 6),
+    ]
+
+
 # every symbol include/hskinfu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -124,6 +134,9 @@ SYMBOLS = {
                                       C.POINTER(C.c_size_t)]),
     "hsk_section_in_room": (C.c_int, [C.POINTER(HskSection), _F, C.POINTER(HskSection)]),
     "hsk_composite_views": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, _P, _P, _P, _P]),
+    "hsk_fuse_volume": (C.c_int, [_P, _P, _F, C.POINTER(HskFuseStats)]),
+    "hsk_invert_rigid": (C.c_int, [_F, _F]),
+    "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_write_pgm16": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_mgpu_frame_begin": (C.c_int, [_P, _P, C.c_int, C.c_int]),

@@ -82,6 +82,15 @@ void launch_extract_attrs(hipStream_t s, const void* vol, const unsigned* colv, 
 void launch_color_integrate(hipStream_t s, unsigned* col, const TrackState* st, const int* has_color, const float* scaled,
                             const unsigned char* rgb, const float* tiles, const VolParams& vp, int W, int H, Intr in, float band,
                             int max_w);
+// volume fusion (fuse.hip): the source's brick table -- one bit per 8^3 brick, "holds an observed voxel", fuse_table_words
+// words zeroed by the caller -- then the sweep of the destination footprint `box` (x0 x1 y0 y1 z0 z1, half-open, not empty);
+// (A, b) maps destination to source coordinates; colour is merged when both colour volumes are given; counts: [0] voxels
+// fused, [1] voxels coloured, [2] chunks swept (zeroed by the caller); *chunks_total: the chunks of the footprint
+size_t fuse_table_words(const VolParams& sv);
+void launch_fuse_bricks(hipStream_t s, const void* src_vol, const VolParams& sv, unsigned* tab);
+void launch_fuse_sweep(hipStream_t s, const void* src_vol, const unsigned* src_col, void* dst_vol, unsigned* dst_col, const VolParams& sv,
+                       const VolParams& dv, const float A[9], const float b[3], const int box[6], const unsigned* tab, int max_w,
+                       unsigned long long* counts, unsigned long long* chunks_total);
 
 // image
 void launch_bilateral_scale(hipStream_t s, const uint16_t* src, int W, int H, Intr in, const float* ws, const float* wc,

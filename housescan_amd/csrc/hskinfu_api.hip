@@ -158,6 +158,10 @@ struct hsk_ctx {
   // pinned host side (the camera on its way in, the counts on their way out)
   void* d_view = nullptr;
   void* h_view = nullptr;
+  // volume fusion (hsk_fuse_volume), made on first use as a destination and only grown: 64 B of counters, then the source's
+  // brick table (fuse.hip)
+  void* d_fuse = nullptr;
+  size_t fuse_bytes = 0;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -294,6 +298,7 @@ static void free_all(hsk_ctx* k) {
   F(k->d_has_color);
   F(k->d_mi);
   F(k->d_view);
+  F(k->d_fuse);
   if (k->h_view) (void)hipHostFree(k->h_view);
   for (auto& b : k->ib) F(b.d_rgb);
   if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);
@@ -2059,6 +2064,80 @@ extern "C" int hsk_render_section(hsk_ctx* k, const hsk_section* s, uint8_t* rgb
   if (n_hit) *n_hit = (size_t)hits;
   if (n_cut) *n_cut = (size_t)cuts;
   if (n_uncolored) *n_uncolored = (size_t)uncolored;
+  return HSK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// volume fusion (include/hskinfu.h "Volume fusion")
+// ------------------------------------------------------------------------------------------------------
+#define HSK_FUSE_COUNTS_BYTES 64
+static bool stores_whole_volume(const hsk_ctx* k) {
+  return !k->group_slab && k->vp.zs0 == 0 && k->vp.nzs == k->vp.Z && k->vp.zo0 == 0 && k->vp.zo1 == k->vp.Z;
+}
+
+extern "C" int hsk_fuse_volume(hsk_ctx* dst, hsk_ctx* src, const float src_to_dst[16], hsk_fuse_stats* stats) {
+  if (!dst) return HSK_ERR_ARG;
+  if (!src || !src_to_dst) return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: null argument");
+  if (src == dst) return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: source and destination are the same context");
+  float inv[16];
+  if (hsk_invert_rigid(src_to_dst, inv) != HSK_OK)
+    return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: src_to_dst is not rigid (last row 0 0 0 1, |R^T R - I| <= 1e-4)");
+  if (memcmp(&dst->vp.tau, &src->vp.tau, sizeof(float)) != 0)
+    return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: the contexts' effective truncation distances differ (stored TSDF values are in units of it)");
+  if (dst->cfg.device_id != src->cfg.device_id) return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: the contexts are on different devices");
+  if (!stores_whole_volume(dst) || !stores_whole_volume(src))
+    return fail(dst, HSK_ERR_STATE, "hsk_fuse_volume: not for a slab (a context that stores part of its volume)");
+  if (dst->ring_count > 0 || src->ring_count > 0)
+    return fail(dst, HSK_ERR_STATE, "frames are in flight: collect them with hsk_wait_frame first");
+  hsk_fuse_stats st;
+  memset(&st, 0, sizeof(st));
+  const int sdims[3] = {src->vp.X, src->vp.Y, src->vp.Z}, ddims[3] = {dst->vp.X, dst->vp.Y, dst->vp.Z};
+  if (hsk_fuse_footprint(sdims, src->vp.size, ddims, dst->vp.size, src_to_dst, st.box) != HSK_OK)
+    return fail(dst, HSK_ERR_ARG, "hsk_fuse_volume: no footprint for these volumes");
+  if (st.box[1] <= st.box[0]) {  // nothing of the source's interior reaches the destination
+    if (stats) *stats = st;
+    return HSK_OK;
+  }
+  hsk_ctx* k = dst;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  // the source: read only.  The rule reads weights, so its deferred ones are written back first (which changes nothing it
+  // returns); everything its stream holds must have ended before the destination's stream reads the volume
+  flush_weights(src);
+  HIPCHK(k, hipStreamSynchronize(src->stream));
+  flush_weights(k);
+  const size_t tab_bytes = fuse_table_words(src->vp) * 4;
+  if (k->fuse_bytes < HSK_FUSE_COUNTS_BYTES + tab_bytes) {
+    if (k->d_fuse) HIPCHK(k, hipFree(k->d_fuse));
+    k->d_fuse = nullptr;
+    k->fuse_bytes = 0;
+    HIPCHK(k, hipMalloc(&k->d_fuse, HSK_FUSE_COUNTS_BYTES + tab_bytes));
+    k->fuse_bytes = HSK_FUSE_COUNTS_BYTES + tab_bytes;
+  }
+  unsigned long long* d_counts = (unsigned long long*)k->d_fuse;
+  unsigned* d_tab = (unsigned*)((char*)k->d_fuse + HSK_FUSE_COUNTS_BYTES);
+  HIPCHK(k, hipMemsetAsync(k->d_fuse, 0, HSK_FUSE_COUNTS_BYTES + tab_bytes, k->stream));
+  launch_fuse_bricks(k->stream, src->d_vol, src->vp, d_tab);
+  const bool colour = k->d_color && src->d_color;
+  unsigned long long chunks_total = 0;
+  float A[9], b[3];
+  pose16_to_rt(inv, A, b);
+  launch_fuse_sweep(k->stream, src->d_vol, colour ? src->d_color : nullptr, k->d_vol, colour ? k->d_color : nullptr, src->vp, k->vp, A, b,
+                    st.box, d_tab, k->color_max_w, d_counts, &chunks_total);
+  HIPCHK(k, hipGetLastError());
+  // the tail of hsk_upload_tsdf: the brick bitfield and both summary levels from the volume as it now is
+  k->vol_epoch += 1;
+  HIPCHK(k, hipMemsetAsync(k->d_flags, 0, k->flags_bytes, k->stream));
+  launch_rebuild_flags(k->stream, k->d_vol, k->vp, k->d_flags);
+  launch_rebuild_uniform(k->stream, k->d_vol, k->vp, k->d_uni);
+  HIPCHK(k, hipGetLastError());
+  unsigned long long counts[3] = {0, 0, 0};
+  int r = read_u64(k, counts, d_counts, 3);
+  if (r != HSK_OK) return r;
+  st.n_fused = counts[0];
+  st.n_colored = counts[1];
+  st.chunks_swept = counts[2];
+  st.chunks_total = chunks_total;
+  if (stats) *stats = st;
   return HSK_OK;
 }
 

@@ -722,6 +722,79 @@ extern "C" int hsk_section_in_room(const hsk_section* house, const float room_xf
   return HSK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Volume fusion on the host seam (include/hskinfu.h "Volume fusion")
+// ------------------------------------------------------------------------------------------------------
+// hsk_section_in_room's test of a rigid row-major matrix; R, t in binary64
+static bool rigid_parts(const float* m, double R[3][3], double t[3]) {
+  if (!(m[12] == 0.0f && m[13] == 0.0f && m[14] == 0.0f && m[15] == 1.0f)) return false;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i][j] = (double)m[4 * i + j];
+    t[i] = (double)m[4 * i + 3];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double g = (R[0][i] * R[0][j] + R[1][i] * R[1][j]) + R[2][i] * R[2][j];
+      if (!(std::fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-4)) return false;   // (NaN: refused)
+    }
+  return true;
+}
+
+// M^-1 = (R^T, -R^T t): the rotation is a transposition (no rounding), the translation one binary64 expression rounded once
+extern "C" int hsk_invert_rigid(const float m[16], float inv[16]) {
+  if (!m || !inv) return HSK_ERR_ARG;
+  double R[3][3], t[3];
+  if (!rigid_parts(m, R, t)) return HSK_ERR_ARG;
+  float out[16];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) out[4 * i + j] = m[4 * j + i];
+    out[4 * i + 3] = (float)(-((R[0][i] * t[0] + R[1][i] * t[1]) + R[2][i] * t[2]));
+  }
+  out[12] = out[13] = out[14] = 0.0f;
+  out[15] = 1.0f;
+  memcpy(inv, out, sizeof(out));   // (inv may be m)
+  return HSK_OK;
+}
+
+// The source's interior -- the points whose voxel lies in [1, dims - 2] on every axis, where a trilinear sample exists -- is the
+// box [cell, (dims - 1) cell]; its image under M lies in the box of its eight corners' images.  Binary64 from the binary32
+// cells the contexts use (size / dims in binary32).
+extern "C" int hsk_fuse_footprint(const int src_dims[3], const float src_size_m[3], const int dst_dims[3], const float dst_size_m[3],
+                                  const float src_to_dst[16], int32_t box[6]) {
+  if (!src_dims || !src_size_m || !dst_dims || !dst_size_m || !src_to_dst || !box) return HSK_ERR_ARG;
+  double R[3][3], t[3];
+  if (!rigid_parts(src_to_dst, R, t)) return HSK_ERR_ARG;
+  double lo[3], hi[3], cd[3];
+  for (int i = 0; i < 3; ++i) {
+    if (src_dims[i] <= 0 || dst_dims[i] <= 0 || !(src_size_m[i] > 0.0f) || !(dst_size_m[i] > 0.0f)) return HSK_ERR_ARG;
+    const double cs = (double)(src_size_m[i] / (float)src_dims[i]);
+    cd[i] = (double)(dst_size_m[i] / (float)dst_dims[i]);
+    lo[i] = cs;
+    hi[i] = (double)(src_dims[i] - 1) * cs;
+  }
+  double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
+  for (int c = 0; c < 8; ++c) {
+    const double p[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
+    for (int i = 0; i < 3; ++i) {
+      const double q = ((R[i][0] * p[0] + R[i][1] * p[1]) + R[i][2] * p[2]) + t[i];
+      if (q < mn[i]) mn[i] = q;
+      if (q > mx[i]) mx[i] = q;
+    }
+  }
+  bool empty = false;
+  int32_t out[6];
+  for (int i = 0; i < 3; ++i) {
+    double a = std::floor(mn[i] / cd[i]) - 1.0, b = std::floor(mx[i] / cd[i]) + 2.0;
+    if (!(a >= 0.0)) a = 0.0;                        // (also a NaN: an image that is not finite receives nothing)
+    if (!(b <= (double)dst_dims[i])) b = (double)dst_dims[i];
+    if (!(mn[i] <= mx[i]) || !(a < b)) empty = true;
+    out[2 * i] = (int32_t)(a < (double)dst_dims[i] ? a : (double)dst_dims[i]);
+    out[2 * i + 1] = (int32_t)(b > 0.0 ? b : 0.0);
+  }
+  for (int i = 0; i < 6; ++i) box[i] = empty ? 0 : out[i];
+  return HSK_OK;
+}
+
 extern "C" int hsk_composite_views(int n, const uint8_t* const* rgb, const uint16_t* const* depth_mm, int w, int h,
                                    const uint8_t background[3], uint8_t* out_rgb, uint16_t* out_depth_mm, int32_t* out_index) {
   if (n < 1 || w < 1 || w > 4096 || h < 1 || h > 4096 || !depth_mm) return HSK_ERR_ARG;

@@ -436,6 +436,18 @@ class KinfuTracker:
         out["n_hit"], out["n_cut"], out["n_uncolored"] = nh.value, nc.value, nu.value
         return out
 
+    # ---- volume fusion --------------------------------------------------------------------------------
+    def fuse_from(self, src, src_to_dst):
+        """resample the volume (and, when both trackers have colour, the colour) of tracker `src` through the rigid 4x4
+        matrix `src_to_dst` (p_dst = M p_src, e.g. a room's .xf) into this one and merge by weight, on the device
+        (hsk_fuse_volume).  Synchronous; `src` is not changed; this tracker's pose and model maps are not touched (call
+        raycast(pose) before scanning on).  -> dict(n_fused, n_colored, chunks_total, chunks_swept, box)"""
+        m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
+        st = _lib.HskFuseStats()
+        self._ck(self.lib.hsk_fuse_volume(self.h, None if src is None else src.h, _fp(m), C.byref(st)))
+        return {"n_fused": int(st.n_fused), "n_colored": int(st.n_colored), "chunks_total": int(st.chunks_total),
+                "chunks_swept": int(st.chunks_swept), "box": tuple(int(x) for x in st.box)}
+
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
         return self.lib.hsk_stream(self.h)

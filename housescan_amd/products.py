@@ -187,6 +187,30 @@ def section_in_room(house, room_xf):
     return room
 
 
+def invert_rigid(m):
+    """the inverse (R^T, -R^T t) of a rigid row-major 4x4 matrix, computed in binary64 and rounded once (hsk_invert_rigid)"""
+    a = np.ascontiguousarray(m, np.float32).reshape(16)
+    out = np.empty(16, np.float32)
+    fp = C.POINTER(C.c_float)
+    _ck(_lib.load().hsk_invert_rigid(a.ctypes.data_as(fp), out.ctypes.data_as(fp)), "hsk_invert_rigid")
+    return out.reshape(4, 4)
+
+
+def fuse_footprint(src_dims, src_size_m, dst_dims, dst_size_m, src_to_dst):
+    """the half-open destination voxel box (x0, x1, y0, y1, z0, z1) that can receive a sample when a source volume of
+    src_dims voxels over src_size_m metres is fused through `src_to_dst` (hsk_fuse_footprint); all zeros when empty"""
+    sd = np.ascontiguousarray(src_dims, np.int32).reshape(3)
+    dd = np.ascontiguousarray(dst_dims, np.int32).reshape(3)
+    ss = np.ascontiguousarray(src_size_m, np.float32).reshape(3)
+    ds = np.ascontiguousarray(dst_size_m, np.float32).reshape(3)
+    m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
+    box = np.zeros(6, np.int32)
+    ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+    _ck(_lib.load().hsk_fuse_footprint(sd.ctypes.data_as(ip), ss.ctypes.data_as(fp), dd.ctypes.data_as(ip), ds.ctypes.data_as(fp),
+                                       m.ctypes.data_as(fp), box.ctypes.data_as(C.POINTER(C.c_int32))), "hsk_fuse_footprint")
+    return tuple(int(x) for x in box)
+
+
 def composite_views(rgbs, depths, background=(0, 0, 0), *, want_rgb=True):
     """images of one size, one per room (KinfuTracker.render_section's rgb and depth) -> (rgb, depth, index): per pixel the
     view with the smallest non-zero depth, the lowest index on a tie; background, 0 and -1 where no view has a depth

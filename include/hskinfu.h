@@ -285,6 +285,46 @@ int hsk_section_in_room(const hsk_section* house, const float room_xf[16], hsk_s
 int hsk_composite_views(int n, const uint8_t* const* rgb, const uint16_t* const* depth_mm, int w, int h,
                         const uint8_t background[3], uint8_t* out_rgb, uint16_t* out_depth_mm, int32_t* out_index);
 
+/* ---- Volume fusion: one volume resampled through a rigid transform into another and merged by weight, on the device
+ * (DESIGN.md 3.10 the kernels, 8d the rule).  With it a "house" context is an ordinary hsk_ctx -- a larger vol_size_m, non-cubic
+ * dims -- into which every room is fused by its .xf; every product (clouds, meshes, views, sections) and hsk_integrate then
+ * work on the house unchanged, and a second scan session of a room merges into the first. */
+typedef struct {
+  uint64_t n_fused;      /* destination voxels that took a sample (rule step 3)                    */
+  uint64_t n_colored;    /* of those, voxels whose colour was merged (step 4)                       */
+  uint64_t chunks_total; /* destination work units inside the footprint                             */
+  uint64_t chunks_swept; /* ... of which were swept voxel by voxel (the others left on the skip test) */
+  int32_t  box[6];       /* the destination footprint swept: x0 x1 y0 y1 z0 z1, half-open, voxels   */
+} hsk_fuse_stats;
+
+/* dst <- dst (+) resample(src) under src_to_dst (row-major, p_dst = M p_src, rigid).  stats may be NULL.
+ * Destination voxel (x, y, z), centre pd, is sampled at ps = M^-1 pd (hsk_invert_rigid) with the raycast's trilinear sample Fs
+ * and the smallest weight Ws of its eight taps; a sample on the source's outer shell or with Ws == 0 leaves the voxel alone,
+ * else raw' = round((raw_d W_d + q Ws) / (W_d + Ws)) with q = rint(Fs * 32767), W' = min(W_d + Ws, 128); the colour of the
+ * source voxel containing ps is merged likewise, by the colour weights.  Stored TSDF values are in units of the truncation
+ * distance, so the two EFFECTIVE truncation distances (trunc_dist_m after the 2.1-cell clamp) must be bit-equal; cells, dims
+ * and sizes may differ in every other way.
+ * Synchronous: returns when the destination is complete and the counts are on the host.  The source is read only (its deferred
+ * free-space weights are written back first, which changes nothing it returns).  The destination's deferred weights are
+ * written back before the merge; behind it its brick bitfield and summaries are rebuilt (as by hsk_upload_tsdf), so every later
+ * product, integrate or raycast sees a consistent volume.  The destination's tracker pose and model maps are NOT touched: a
+ * host that goes on scanning against the fused volume calls hsk_raycast(dst, pose, ...) first, which sets them.
+ * Colour is merged iff both contexts have called hsk_enable_color; otherwise the destination's colour volume, if any, is
+ * untouched and n_colored = 0.  An empty footprint: HSK_OK, zero counts, nothing launched.
+ * HSK_ERR_ARG: a NULL context, src == dst, a matrix hsk_invert_rigid refuses, unequal truncation distances, contexts on
+ * different devices; HSK_ERR_STATE: a frame in flight in either context, a slab of a group or any context that stores part of
+ * its volume (hsk_render_view's cases). */
+int hsk_fuse_volume(hsk_ctx* dst, hsk_ctx* src, const float src_to_dst[16], hsk_fuse_stats* stats);
+
+/* host only: the inverse of a rigid matrix, computed in binary64 from the binary32 entries and rounded once
+ * (R^T, -R^T t; last row 0 0 0 1).  The rigidity test and HSK_ERR_ARG are hsk_section_in_room's. */
+int hsk_invert_rigid(const float m[16], float inv[16]);
+
+/* host only: the half-open destination voxel box that can receive a sample.  It is the image of the source volume's
+ * interior under M, padded by one destination cell and clipped to the destination.  Empty: x1 <= x0, HSK_OK. */
+int hsk_fuse_footprint(const int src_dims[3], const float src_size_m[3], const int dst_dims[3], const float dst_size_m[3],
+                       const float src_to_dst[16], int32_t box[6]);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */

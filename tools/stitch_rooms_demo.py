@@ -16,6 +16,12 @@ normals by transform_normals, faces offset by each room's vertex base) -- no hos
 room's frame by its .xf (hsk_section_in_room), rendered from the room's volume on the GPU (hsk_render_section) and the rooms'
 images are composited (hsk_composite_views): house_floorplan.ppm (walls as outlines in the cut colour) and house_heights.pgm
 (16-bit millimetres below the camera's plane: a height map).
+
+--fuse-house: behind the stitch, ONE house volume is made on the GPU -- a context sized to the placed rooms' extents at the
+rooms' cell -- and every room's volume is fused into it by T_offset . xf (hsk_fuse_volume; T_offset moves the house into the
+context's positive octant).  house_fused_mesh.ply is one hsk_extract_mesh_indexed of that volume (in house coordinates: where
+rooms overlap there is one surface, not two), house_fused_floorplan.ppm one hsk_render_section of it (--floorplan's camera);
+report.json gets a "fused_house" block with the statistics of every fuse and the milliseconds.
 """
 import argparse
 import json
@@ -107,11 +113,9 @@ def stitch(hsk, room_dirs, variants, log=print):
     return hs, rooms, rm
 
 
-def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
-    """the house from above: one section in house coordinates, each room's share rendered in the room's own frame"""
+def house_section(hsk, variants, Ms, px_per_m):
+    """the top-down orthographic section of the whole house, cut at mid height, in house coordinates -> (section, W, H)"""
     from housescan_amd import _lib
-    from housescan_amd import products as P
-    t0 = time.perf_counter()
     Ms = [np.asarray(M, np.float64) for M in Ms]
     corners = np.concatenate([true_corners(hsk.synth_room_extents(v)) @ M[:3, :3].T + M[:3, 3] for v, M in zip(variants, Ms)])
     up = Ms[0][:3, :3] @ np.array([0.0, -1.0, 0.0])          # a scan's y axis points down
@@ -140,6 +144,15 @@ def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
     house.projection, house.light_directional, house.n_clip = _lib.HSK_PROJ_ORTHO, 1, 1
     mid = 0.5 * (h.max() + h.min())
     house.clip[0][:] = [float(-up[0]), float(-up[1]), float(-up[2]), float(mid)]     # keep what lies below mid height
+    return house, W, H
+
+
+def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
+    """the house from above: one section in house coordinates, each room's share rendered in the room's own frame"""
+    from housescan_amd import products as P
+    t0 = time.perf_counter()
+    house, W, H = house_section(hsk, variants, Ms, px_per_m)
+    Ms = [np.asarray(M, np.float64) for M in Ms]
     rgbs, deps, counts = [], [], []
     for trk, M in zip(trackers, Ms):
         r = trk.render_section(P.section_in_room(house, M.astype(np.float32)))
@@ -154,6 +167,43 @@ def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
             "end_to_end_ms": round(ms, 2)}
 
 
+def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=0.25):
+    """one house volume on the GPU: every room fused into it by its .xf; one mesh and one floor plan of the whole"""
+    from housescan_amd import products as P
+    Ms = [np.asarray(M, np.float64) for M in Ms]
+    cell = 3.0 / volume                                       # the rooms' cell (a room's context is volume^3 over 3 m)
+    corners = np.concatenate([true_corners(hsk.synth_room_extents(v)) @ M[:3, :3].T + M[:3, 3] for v, M in zip(variants, Ms)])
+    lo, hi = corners.min(axis=0) - margin, corners.max(axis=0) + margin
+    dims = [int(-(-(hi[i] - lo[i]) // (64 * cell))) * 64 for i in range(3)]   # (multiples of 64: the brick bitfield's rule)
+    size = [d * cell for d in dims]
+    T = np.eye(4)
+    T[:3, 3] = -lo
+    t0 = time.perf_counter()
+    house = hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size))
+    make_ms = 1e3 * (time.perf_counter() - t0)
+    rooms = []
+    for trk, M in zip(trackers, Ms):
+        t0 = time.perf_counter()
+        st = house.fuse_from(trk, (T @ M).astype(np.float32))
+        st["ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        st["box"] = list(st["box"])
+        rooms.append(st)
+    t0 = time.perf_counter()
+    verts, faces, normals, _, _ = house.extract_mesh_indexed(normals=True, rgb=False)
+    mesh_ms = 1e3 * (time.perf_counter() - t0)
+    P.write_ply_indexed(os.path.join(out, "house_fused_mesh.ply"), P.transform_cloud(verts, np.linalg.inv(T).astype(np.float32)), faces,
+                        normals=normals)
+    t0 = time.perf_counter()
+    sec, W, H = house_section(hsk, variants, Ms, px_per_m)
+    r = house.render_section(P.section_in_room(sec, np.linalg.inv(T).astype(np.float32)), depth=False)   # (the context sits at T^-1 in the house)
+    plan_ms = 1e3 * (time.perf_counter() - t0)
+    P.write_ppm(os.path.join(out, "house_fused_floorplan.ppm"), r["rgb"])
+    house.close()
+    return {"dims": dims, "size_m": [round(x, 6) for x in size], "rooms": rooms, "create_ms": round(make_ms, 2),
+            "mesh": {"vertices": int(len(verts)), "faces": int(len(faces)), "ms": round(mesh_ms, 2)},
+            "floorplan": {"width": W, "height": H, "hit": r["n_hit"], "cut": r["n_cut"], "ms": round(plan_ms, 2)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rooms", type=int, default=2)
@@ -162,6 +212,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "stitch"))
     ap.add_argument("--indexed-mesh", action="store_true", help="rooms' meshes indexed with normals: <room_dir>/mesh.ply, no host weld")
     ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
+    ap.add_argument("--fuse-house", action="store_true", help="house_fused_mesh.ply + house_fused_floorplan.ppm: the rooms' volumes fused into one house volume on the GPU")
     args = ap.parse_args()
 
     import housescan_amd as hsk
@@ -172,9 +223,9 @@ def main():
     report = {"rooms": []}
     dirs, variants, meshes, trackers = [], list(range(args.rooms)), [], []
     for v in variants:
-        res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh, keep=args.floorplan)
+        res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh, keep=args.floorplan or args.fuse_house)
         cloud, worst, lost, fps, mesh = res[:5]
-        if args.floorplan:
+        if args.floorplan or args.fuse_house:
             trackers.append(res[5])
         meshes.append(mesh)
         d = os.path.join(args.out, f"room{v}", "walls")
@@ -215,8 +266,10 @@ def main():
     report["house_mesh"] = {"vertices": nv, "faces": nf}
     if args.floorplan:
         report["floorplan"] = floorplan(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out)
-        for trk in trackers:
-            trk.close()
+    if args.fuse_house:
+        report["fused_house"] = fuse_house(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out, args.volume)
+    for trk in trackers:
+        trk.close()
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
     with open(os.path.join(args.out, "report.json"), "w") as f:
