@@ -81,6 +81,28 @@ class HskFuseStats(C.Structure):
     ]
 
 
+class HskVolumeInfo(C.Structure):
+    """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
+
+    _fields_ = [
+        ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("flags", C.c_uint32),
+        ("dims", C.c_int32 * 3), ("z0", C.c_int32), ("nz", C.c_int32),
+        ("size_m", C.c_float * 3),
+        ("trunc_dist_m", C.c_float), ("trunc_eff_m", C.c_float),
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("pose", C.c_float * 16),
+        ("frame", C.c_int32),
+        ("color_max_weight", C.c_int32), ("color_band_m", C.c_float),
+        ("n_bricks", C.c_uint64),
+        ("tsdf_bricks", C.c_uint64 * 4), ("color_bricks", C.c_uint64 * 2),
+        ("tsdf_table_bytes", C.c_uint64), ("tsdf_payload_bytes", C.c_uint64),
+        ("color_table_bytes", C.c_uint64), ("color_payload_bytes", C.c_uint64),
+        ("total_bytes", C.c_uint64),
+        ("pass_reused", C.c_int32),
+    ]
+
+
 # every symbol include/hskinfu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -135,6 +157,14 @@ SYMBOLS = {
     "hsk_section_in_room": (C.c_int, [C.POINTER(HskSection), _F, C.POINTER(HskSection)]),
     "hsk_composite_views": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, _P, _P, _P, _P]),
     "hsk_fuse_volume": (C.c_int, [_P, _P, _F, C.POINTER(HskFuseStats)]),
+    "hsk_pack_volume": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskVolumeInfo)]),
+    "hsk_unpack_volume": (C.c_int, [_P, _P, C.c_size_t]),
+    "hsk_save_volume": (C.c_int, [_P, C.c_char_p, C.POINTER(HskVolumeInfo)]),
+    "hsk_load_volume": (C.c_int, [_P, C.c_char_p]),
+    "hsk_volume_image_info": (C.c_int, [_P, C.c_size_t, C.POINTER(HskVolumeInfo)]),
+    "hsk_volume_file_info": (C.c_int, [C.c_char_p, C.POINTER(HskVolumeInfo)]),
+    "hsk_config_from_volume": (C.c_int, [C.POINTER(HskVolumeInfo), C.POINTER(HskConfig)]),
+    "hsk_resume_scan": (C.c_int, [_P, _F]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

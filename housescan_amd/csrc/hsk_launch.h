@@ -92,6 +92,22 @@ void launch_fuse_sweep(hipStream_t s, const void* src_vol, const unsigned* src_c
                        const VolParams& dv, const float A[9], const float b[3], const int box[6], const unsigned* tab, int max_w,
                        unsigned long long* counts, unsigned long long* chunks_total);
 
+// sparse volume image (pack.hip): bricks of 8^3 voxels, pack_bricks of them, a class byte and a record size
+// (in 4-byte words) each.  launch_pack_scan turns the sizes into offsets in place (an exclusive scan; bsum: pack_scan_blocks
+// words of scratch) and leaves in counts[0..3] the bricks per class, in counts[4] the payload's length in words (8 words).
+// gather / scatter move the records of every non-ZERO brick between the volume (color: the row-major colour volume) and the
+// payload; the scatter expects a zeroed volume.
+size_t pack_bricks(const VolParams& vp);
+size_t pack_scan_blocks(size_t n_bricks);
+void launch_pack_classify(hipStream_t s, const void* vol, const VolParams& vp, unsigned char* cls, unsigned* size);
+void launch_pack_classify_color(hipStream_t s, const unsigned* col, const VolParams& vp, unsigned char* cls, unsigned* size);
+void launch_pack_sizes(hipStream_t s, const unsigned char* cls, size_t n_bricks, unsigned* size);
+void launch_pack_scan(hipStream_t s, unsigned* size, size_t n_bricks, unsigned* bsum, unsigned* counts);
+void launch_pack_gather(hipStream_t s, const void* vol, bool color, const VolParams& vp, const unsigned char* cls, const unsigned* off,
+                        void* payload);
+void launch_pack_scatter(hipStream_t s, void* vol, bool color, const VolParams& vp, const unsigned char* cls, const unsigned* off,
+                         const void* payload);
+
 // image
 void launch_bilateral_scale(hipStream_t s, const uint16_t* src, int W, int H, Intr in, const float* ws, const float* wc,
                             uint16_t* dst, float* scaled, float* tiles);

@@ -441,12 +441,69 @@ class KinfuTracker:
         """resample the volume (and, when both trackers have colour, the colour) of tracker `src` through the rigid 4x4
         matrix `src_to_dst` (p_dst = M p_src, e.g. a room's .xf) into this one and merge by weight, on the device
         (hsk_fuse_volume).  Synchronous; `src` is not changed; this tracker's pose and model maps are not touched (call
-        raycast(pose) before scanning on).  -> dict(n_fused, n_colored, chunks_total, chunks_swept, box)"""
+        resume_scan(pose) before scanning on).  -> dict(n_fused, n_colored, chunks_total, chunks_swept, box)"""
         m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
         st = _lib.HskFuseStats()
         self._ck(self.lib.hsk_fuse_volume(self.h, None if src is None else src.h, _fp(m), C.byref(st)))
         return {"n_fused": int(st.n_fused), "n_colored": int(st.n_colored), "chunks_total": int(st.chunks_total),
                 "chunks_swept": int(st.chunks_swept), "box": tuple(int(x) for x in st.box)}
+
+    # ---- volume files -----------------------------------------------------------------------------------
+    def pack_volume(self, with_info=False):
+        """the volume (TSDF, and colour once enabled) as a lossless sparse image, packed on the device (hsk_pack_volume)
+        -> bytes, or (bytes, info dict) with with_info"""
+        n, info = C.c_size_t(), _lib.HskVolumeInfo()
+        self._ck(self.lib.hsk_pack_volume(self.h, None, 0, C.byref(n), C.byref(info)))
+        buf = np.empty(n.value, np.uint8)
+        self._ck(self.lib.hsk_pack_volume(self.h, buf.ctypes.data, buf.size, C.byref(n), C.byref(info)))
+        if n.value != buf.size:
+            raise KinfuError("pack_volume: the size changed between the two calls")
+        return (buf.tobytes(), _info_dict(info)) if with_info else buf.tobytes()
+
+    def pack_volume_info(self):
+        """the size query of pack_volume alone: the header and the class counts of the image the volume would make"""
+        n, info = C.c_size_t(), _lib.HskVolumeInfo()
+        self._ck(self.lib.hsk_pack_volume(self.h, None, 0, C.byref(n), C.byref(info)))
+        return _info_dict(info)
+
+    def unpack_volume(self, image):
+        """replace the volume by a sparse image's (hsk_unpack_volume); the tracker pose and model maps are not touched"""
+        a = np.frombuffer(image, np.uint8)
+        self._ck(self.lib.hsk_unpack_volume(self.h, a.ctypes.data if a.size else None, a.size))
+
+    def save_volume(self, path):
+        """the image as a file (written beside itself, then renamed into place) -> info dict"""
+        info = _lib.HskVolumeInfo()
+        self._ck(self.lib.hsk_save_volume(self.h, str(path).encode(), C.byref(info)))
+        return _info_dict(info)
+
+    def load_volume(self, path):
+        self._ck(self.lib.hsk_load_volume(self.h, str(path).encode()))
+
+    def resume_scan(self, pose):
+        """put the tracker where it stands after a tracked frame at `pose`: the model maps are raycast from the volume as it
+        is, so the next frame is tracked by ICP against it (hsk_resume_scan)"""
+        p = np.ascontiguousarray(pose, np.float32).reshape(16)
+        self._ck(self.lib.hsk_resume_scan(self.h, _fp(p)))
+
+    @classmethod
+    def from_volume_file(cls, path, **over):
+        """a tracker made for the volume file at `path` (config_from_volume; keywords override config fields) that holds
+        its volume, with colour enabled when the file has colour.  The tracker stands at the file's pose; call
+        resume_scan(info pose) to scan on."""
+        info = volume_file_info(path)
+        cfg = config_from_volume(info)
+        for k, v in over.items():
+            setattr(cfg, k, v)
+        t = cls(cfg)
+        try:
+            if info["has_color"]:
+                t.enable_color(info["color_max_weight"], info["color_band_m"])
+            t.load_volume(path)
+        except Exception:
+            t.close()
+            raise
+        return t
 
     # ---- streams / profiling -----------------------------------------------------------------------
     def stream(self):
@@ -472,6 +529,52 @@ class KinfuTracker:
         n = C.c_uint64()
         self._ck(self.lib.hsk_stage_ms(self.h, ms, C.byref(n), int(reset)))
         return list(ms), n.value
+
+
+def _info_dict(info):
+    """an `_lib.HskVolumeInfo` as a dict (arrays as numpy; "raw": the structure itself, for config_from_volume)"""
+    d = {}
+    for name, _ in _lib.HskVolumeInfo._fields_:
+        v = getattr(info, name)
+        d[name] = np.array(v[:]) if hasattr(v, "__len__") else v
+    d["pose"] = np.array(info.pose[:], np.float32).reshape(4, 4)
+    d["size_m"] = np.array(info.size_m[:], np.float32)
+    d["has_color"] = bool(info.flags & 1)
+    d["raw"] = _lib.HskVolumeInfo.from_buffer_copy(info)
+    return d
+
+
+def volume_image_info(image):
+    """host only: validate a sparse volume image (bytes) and return its header as a dict; KinfuError when it is refused"""
+    lib = _lib.load()
+    a = np.frombuffer(image, np.uint8)
+    info = _lib.HskVolumeInfo()
+    rc = lib.hsk_volume_image_info(a.ctypes.data if a.size else None, a.size, C.byref(info))
+    if rc != 0:
+        raise KinfuError(f"hsk_volume_image_info failed ({rc}): {lib.hsk_last_error(None).decode()}")
+    return _info_dict(info)
+
+
+def volume_file_info(path):
+    """host only: the same for a volume file (reads the header and the class tables only)"""
+    lib = _lib.load()
+    info = _lib.HskVolumeInfo()
+    rc = lib.hsk_volume_file_info(str(path).encode(), C.byref(info))
+    if rc != 0:
+        raise KinfuError(f"hsk_volume_file_info failed ({rc}): {lib.hsk_last_error(None).decode()}")
+    return _info_dict(info)
+
+
+def config_from_volume(info):
+    """host only: the configuration of a context that accepts the image whose header `info` is (a dict of
+    volume_*_info, or an `_lib.HskVolumeInfo`); the image's pose becomes init_pose"""
+    lib = _lib.load()
+    raw = info["raw"] if isinstance(info, dict) else info
+    cfg = _lib.HskConfig()
+    rc = lib.hsk_config_from_volume(C.byref(raw), C.byref(cfg))
+    if rc != 0:
+        raise KinfuError(f"hsk_config_from_volume failed ({rc}): {lib.hsk_last_error(None).decode()}")
+    return cfg
 
 
 GROUP_FORCE_RCCL = 1

@@ -308,7 +308,8 @@ typedef struct {
  * free-space weights are written back first, which changes nothing it returns).  The destination's deferred weights are
  * written back before the merge; behind it its brick bitfield and summaries are rebuilt (as by hsk_upload_tsdf), so every later
  * product, integrate or raycast sees a consistent volume.  The destination's tracker pose and model maps are NOT touched: a
- * host that goes on scanning against the fused volume calls hsk_raycast(dst, pose, ...) first, which sets them.
+ * host that goes on scanning against the fused volume calls hsk_resume_scan(dst, pose) first, which sets them and makes the next
+ * frame a tracked one (hsk_raycast sets them too, but leaves a context that has seen no frame at its first-frame step).
  * Colour is merged iff both contexts have called hsk_enable_color; otherwise the destination's colour volume, if any, is
  * untouched and n_colored = 0.  An empty footprint: HSK_OK, zero counts, nothing launched.
  * HSK_ERR_ARG: a NULL context, src == dst, a matrix hsk_invert_rigid refuses, unequal truncation distances, contexts on
@@ -324,6 +325,68 @@ int hsk_invert_rigid(const float m[16], float inv[16]);
  * interior under M, padded by one destination cell and clipped to the destination.  Empty: x1 <= x0, HSK_OK. */
 int hsk_fuse_footprint(const int src_dims[3], const float src_size_m[3], const int dst_dims[3], const float dst_size_m[3],
                        const float src_to_dst[16], int32_t box[6]);
+
+/* ---- Volume files: a scanned volume (TSDF + colour) as a lossless sparse image, made and consumed on the device, so that a
+ * room outlives its process: saved behind a scan, loaded later to be fused into a house, merged with a second session or
+ * scanned further (DESIGN.md 3.11 the kernels, 8e the format "HSKV" version 1).  The volume is cut into bricks of 8 x 8 x 8
+ * voxels; a brick is stored as nothing (every word 0), one word (all words equal), its tsdf and 512 weight bytes (free
+ * space: one tsdf, weights below 256) or its 512 words; only the packed bytes cross the host link. */
+typedef struct {
+  uint32_t version, header_bytes;  /* 1, 256                                                                         */
+  uint32_t flags;                  /* bit 0: the image holds colour                                                  */
+  int32_t dims[3];                 /* vol_x, vol_y, vol_z                                                            */
+  int32_t z0, nz;                  /* the stored planes (hsk_stored_planes); whole volumes only: 0, vol_z            */
+  float size_m[3];
+  float trunc_dist_m;              /* as configured                                                                  */
+  float trunc_eff_m;               /* as used: after the 2.1-cell clamp; stored TSDF values are in units of it       */
+  int32_t width, height;           /* the depth camera                                                               */
+  float fx, fy, cx, cy;
+  float pose[16];                  /* the tracker pose when the image was made (hsk_get_pose)                        */
+  int32_t frame;                   /* frames the scan had taken since its (re)start                                  */
+  int32_t color_max_weight;        /* hsk_enable_color's parameters as in effect (0, 0 without colour)               */
+  float color_band_m;
+  uint64_t n_bricks;               /* (vol_x / 8) (vol_y / 8) ceil(nz / 8)                                           */
+  uint64_t tsdf_bricks[4];         /* per class: ZERO, UNIFORM, SPLIT, RAW                                           */
+  uint64_t color_bricks[2];        /* ZERO, RAW (0, 0 without colour)                                                */
+  uint64_t tsdf_table_bytes, tsdf_payload_bytes, color_table_bytes, color_payload_bytes;
+  uint64_t total_bytes;            /* header + the four sections = the image                                         */
+  int32_t pass_reused;             /* hsk_pack_volume only (not in the image): 1 when the call found the class and offset pass
+                                      of an earlier call in place */
+} hsk_volume_info;
+
+/* The image of the context's volume.  Two-call protocol like the products': with buf == NULL only *n_bytes and *info (may be
+ * NULL) are set, and the class and offset pass is kept for the next call while the volume is unchanged; a cap_bytes below the
+ * total returns HSK_ERR_ARG with the counts set and nothing written.  The deferred free-space weights are written back first
+ * (as by hsk_download_tsdf: the image holds weights).  Colour is packed iff the context has called hsk_enable_color.
+ * Synchronous.  The bytes come back through the product buffer and the pinned staging pair; device memory: the packed size
+ * plus 10 bytes per brick of tables, never a second copy of the volume.  HSK_ERR_STATE: a frame in flight, a slab of a group
+ * or any context that stores part of its volume (hsk_render_view's cases). */
+int hsk_pack_volume(hsk_ctx* k, void* buf, size_t cap_bytes, size_t* n_bytes, hsk_volume_info* info);
+/* Replaces the context's volume as a whole by the image's.  The image is validated on the host first (hsk_volume_image_info's
+ * rules: HSK_ERR_ARG and an untouched context); dims, stored planes, size_m and the effective truncation distance must then
+ * equal the context's bit for bit (HSK_ERR_ARG).  The payload goes up in batches through the pinned pair, the bricks are
+ * written on the device, the brick bitfield and the summaries are rebuilt (as by hsk_upload_tsdf).  Colour: image and context
+ * both have it: taken; only the context: its colour volume is zeroed; only the image: skipped.  The tracker pose and the model
+ * maps are NOT touched (hsk_resume_scan does that).  State errors as hsk_pack_volume's. */
+int hsk_unpack_volume(hsk_ctx* k, const void* buf, size_t n_bytes);
+/* the image as a file, byte for byte.  Save writes `path`.tmp and renames it into place; an I/O failure is HSK_ERR_STATE */
+int hsk_save_volume(hsk_ctx* k, const char* path, hsk_volume_info* info /* may be NULL */);
+int hsk_load_volume(hsk_ctx* k, const char* path);
+/* host only: the header of an image, after validating the image: magic, version, header size; a self-consistent header
+ * (dims, planes, brick count, section lengths, total); every class byte legal; the header's brick counts and section lengths
+ * those that follow from the class tables; the total equal to n_bytes.  HSK_ERR_ARG with a message (hsk_last_error(NULL))
+ * otherwise.  There is no payload checksum.  The file form reads the header and the class tables only. */
+int hsk_volume_image_info(const void* buf, size_t n_bytes, hsk_volume_info* info);
+int hsk_volume_file_info(const char* path, hsk_volume_info* info);
+/* host only: hsk_default_config with the image's dims, size_m, configured trunc_dist_m and camera, its pose as init_pose: a
+ * context created from *c accepts the image */
+int hsk_config_from_volume(const hsk_volume_info* info, hsk_config* c);
+/* Puts the tracker where it stands after a tracked frame at `pose`: the pose is set, the model maps of all three levels are
+ * made by the raycast of the volume as it is (hsk_raycast's device work without the downloads), the lost flag and any pending
+ * reset are cleared, and the context counts as having seen a frame -- so the next frame, through any of the frame calls, is
+ * tracked by ICP against the volume, whoever grew it (hsk_unpack_volume, hsk_load_volume, hsk_fuse_volume, hsk_upload_tsdf).
+ * HSK_ERR_STATE: a frame in flight, a slab of a group. */
+int hsk_resume_scan(hsk_ctx* k, const float pose[16]);
 
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */

@@ -22,6 +22,10 @@ rooms' cell -- and every room's volume is fused into it by T_offset . xf (hsk_fu
 context's positive octant).  house_fused_mesh.ply is one hsk_extract_mesh_indexed of that volume (in house coordinates: where
 rooms overlap there is one surface, not two), house_fused_floorplan.ppm one hsk_render_section of it (--floorplan's camera);
 report.json gets a "fused_house" block with the statistics of every fuse and the milliseconds.
+
+--save-volumes: behind each scan the room's volume is written to <room dir>/volume.hskv (hsk_save_volume: a sparse image packed
+on the GPU) and the room's context is closed.  --floorplan and --fuse-house then load one room at a time from its file into a
+single scratch context (hsk_load_volume), so at most two contexts are alive at once however many rooms the house has.
 """
 import argparse
 import json
@@ -67,6 +71,33 @@ def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=Fal
     if with_mesh:
         return cloud, worst, lost, len(depth) / dt, mesh
     return cloud, worst, lost, len(depth) / dt
+
+
+class RoomVolumes:
+    """the rooms' volumes for what follows the stitch, in room order: the scans' own contexts, or (--save-volumes) their
+    volume files, loaded one at a time into a single scratch context when they are iterated over"""
+
+    def __init__(self, hsk):
+        self.hsk, self.items, self.scratch = hsk, [], None
+
+    def add(self, item):            # a KinfuTracker, or the path of a volume file
+        self.items.append(item)
+
+    def __iter__(self):
+        for item in self.items:
+            if not isinstance(item, str):
+                yield item
+            elif self.scratch is None:
+                self.scratch = self.hsk.KinfuTracker.from_volume_file(item)
+                yield self.scratch
+            else:
+                self.scratch.load_volume(item)
+                yield self.scratch
+
+    def close(self):
+        for item in self.items + [self.scratch]:
+            if item is not None and not isinstance(item, str):
+                item.close()
 
 
 def true_corners(extents):
@@ -213,6 +244,7 @@ def main():
     ap.add_argument("--indexed-mesh", action="store_true", help="rooms' meshes indexed with normals: <room_dir>/mesh.ply, no host weld")
     ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
     ap.add_argument("--fuse-house", action="store_true", help="house_fused_mesh.ply + house_fused_floorplan.ppm: the rooms' volumes fused into one house volume on the GPU")
+    ap.add_argument("--save-volumes", action="store_true", help="<room dir>/volume.hskv behind each scan, the room's context closed; --floorplan / --fuse-house load them one at a time")
     args = ap.parse_args()
 
     import housescan_amd as hsk
@@ -221,12 +253,24 @@ def main():
 
     os.makedirs(args.out, exist_ok=True)
     report = {"rooms": []}
-    dirs, variants, meshes, trackers = [], list(range(args.rooms)), [], []
+    dirs, variants, meshes, trackers = [], list(range(args.rooms)), [], RoomVolumes(hsk)
     for v in variants:
-        res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh, keep=args.floorplan or args.fuse_house)
+        res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh,
+                        keep=args.floorplan or args.fuse_house or args.save_volumes)
         cloud, worst, lost, fps, mesh = res[:5]
-        if args.floorplan or args.fuse_house:
-            trackers.append(res[5])
+        if args.save_volumes:
+            os.makedirs(os.path.join(args.out, f"room{v}"), exist_ok=True)
+            path = os.path.join(args.out, f"room{v}", "volume.hskv")
+            t0 = time.perf_counter()
+            info = res[5].save_volume(path)
+            res[5].close()
+            trackers.add(path)
+            report.setdefault("volumes", []).append({"path": os.path.relpath(path, args.out), "bytes": int(info["total_bytes"]),
+                                                     "share_of_raw": info["total_bytes"] / (4.0 * args.volume ** 3),
+                                                     "tsdf_bricks": [int(x) for x in info["tsdf_bricks"]],
+                                                     "save_ms": round(1e3 * (time.perf_counter() - t0), 2)})
+        elif args.floorplan or args.fuse_house:
+            trackers.add(res[5])
         meshes.append(mesh)
         d = os.path.join(args.out, f"room{v}", "walls")
         planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, dist_thresh=0.025, min_fraction=0.03)
@@ -268,8 +312,7 @@ def main():
         report["floorplan"] = floorplan(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out)
     if args.fuse_house:
         report["fused_house"] = fuse_house(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out, args.volume)
-    for trk in trackers:
-        trk.close()
+    trackers.close()
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
     with open(os.path.join(args.out, "report.json"), "w") as f:
