@@ -1,0 +1,202 @@
+// hsk_ctx.h -- library-internal, not installed: the context behind the C ABI (include/hskinfu.h) and the host helpers that the
+// ABI's three files share -- hskinfu_api.hip (context, frames), api_readout.hip (what reaches the caller), api_volume.hip (what
+// replaces or serialises the volume).  hskinfu_group.hip takes hsk_mark_group_slab from here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+#include "../../include/hskinfu.h"
+#include "hsk_dev.h"
+#include "hsk_launch.h"
+#include "hsk_volume_image.h"
+
+// image-space buffers of one frame; two sets so that the asynchronous path can preprocess frame k+1 on a second
+// stream while frame k is still being tracked / fused / raycast
+struct ImgBufs {
+  uint16_t* d_raw = nullptr;
+  uint16_t* d_dep[HSK_NLEVELS] = {};
+  float* d_scaled = nullptr;
+  float* d_vcur[HSK_NLEVELS] = {};
+  float* d_ncur[HSK_NLEVELS] = {};
+  float* d_tmax = nullptr;  // tile tables of the scaled depth (see launch_tile_max)
+  unsigned char* d_rgb = nullptr;  // the frame's colour image (RGB8), only once colour is enabled (hsk_enable_color)
+};
+
+struct hsk_ctx {
+  hsk_config cfg;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  VolParams vp;
+  ImgLevel lv[HSK_NLEVELS];
+  float init_R[9], init_t[3];
+  // device memory (all sized once at create; nothing is allocated on the frame path)
+  void* d_vol = nullptr;
+  size_t vol_bytes = 0;
+  ImgBufs ib[2];
+  int cur = 0;  // set the enqueue_* helpers work on (0 everywhere except inside the overlapped async submission)
+  ImgBufs& B() { return ib[cur]; }
+  float* d_vmod[HSK_NLEVELS] = {};
+  float* d_nmod[HSK_NLEVELS] = {};
+  TrackState* d_st = nullptr;
+  TrackState* h_st = nullptr;  // pinned
+  double* d_partials = nullptr;
+  double* d_partials2 = nullptr;  // ping-pong partner of d_partials (fused ICP iterations)
+  void* d_icp_pose = nullptr;     // two IcpPose slots
+  double* d_sums = nullptr;
+  float h_ws[169] = {};  // bilateral spatial weights (host copy: passed to the kernel by value)
+  float* d_wc = nullptr;
+  int* d_keys = nullptr;
+  unsigned* d_flags = nullptr;       // bitfield, one bit per brick: ever held a negative TSDF
+  unsigned char* d_uni = nullptr;    // lane-block summaries (integrate.hip: hsk_uniform_code), one byte per 4x1x4 voxels
+  size_t uni_bytes = 0;
+  bool weights_pending = false;      // an integrate has been enqueued since the summaries' weights were last written back
+  size_t flags_bytes = 0;
+  unsigned* d_queue = nullptr;       // integrate pass A -> pass B: count (4 words) + uncertain lane-block ids
+  CubeTable* d_cube_tab = nullptr;   // marching-cubes table (hsk_extract_mesh_cubes; filled on first use)
+  int2* d_zint = nullptr;            // per lane column: stored-plane range inside the padded frustum
+  uint16_t* h_stage = nullptr;  // pinned staging for the incoming depth frame (HSK_MAX_IN_FLIGHT + 1 frames, used in turn)
+  unsigned stage_turn = 0;
+  unsigned long long* d_counter = nullptr;
+  unsigned* d_rowcnt = nullptr;
+  unsigned long long* d_rowoff = nullptr;
+  // read-out (round 5): what the volume looked like when a product was last counted (a size query followed by the fill
+  // finds the rows' counts and offsets in place), a grow-only device buffer for the product, and two pinned staging
+  // buffers through which products and the volume reach the caller's pageable memory (lazily allocated)
+  uint64_t vol_epoch = 1;       // counted up by everything that changes the volume
+  int ro_kind = 0;              // 1 cloud, 2 tetrahedra mesh, 3 cubes mesh, 4 indexed mesh: whose counts d_rowcnt / d_rowoff hold
+  uint64_t ro_epoch = 0;
+  unsigned long long ro_totals[2] = {0, 0};  // its items; of the indexed mesh the vertices, then the faces
+  void* d_out = nullptr;
+  size_t out_bytes = 0;
+  void* h_pin[2] = {nullptr, nullptr};
+  size_t pin_bytes = 0;
+  hipEvent_t ev_pin[2] = {};
+  int frame = 0;
+  std::string err;
+  // asynchronous submission ring (hsk_submit_frame_dev / hsk_wait_frame)
+  TrackState* h_ring = nullptr;  // pinned, HSK_MAX_IN_FLIGHT + 1 slots
+  int* h_slot_fifo = nullptr;    // pinned: ring slot of each pipelined frame, read by the frame's last kernel (RingOut)
+  unsigned* d_ring_seq = nullptr;  // device: pipelined frames that have reported
+  unsigned ring_seq = 0;         // host mirror: pipelined frames submitted
+  unsigned ring_expect[HSK_MAX_IN_FLIGHT + 1] = {};  // mark the frame in each slot will write
+  unsigned set_expect[2] = {0, 0};                     // ... and the one that last used each image buffer set
+  int set_slot[2] = {-1, -1};
+  TrackState* d_ring_view = nullptr;  // device-side addresses of h_ring / h_slot_fifo
+  int* d_fifo_view = nullptr;
+  hipEvent_t ring_ev[HSK_MAX_IN_FLIGHT + 1] = {};
+  int ring_kind[HSK_MAX_IN_FLIGHT + 1] = {};  // 0 tracked-frame candidate, 1 first frame (already complete)
+  int ring_head = 0, ring_count = 0;
+  bool pending_reset = false;
+  // overlapped preprocessing: stream, per-set events (preprocess done / set free again), per-set graphs of the rest
+  hipStream_t pstream = nullptr;
+  hipEvent_t ev_pre[2] = {}, ev_free[2] = {};
+  hipEvent_t ev_src = nullptr;  // orders the second stream behind the caller's (adopted) stream before a depth copy
+
+  bool set_used[2] = {false, false};
+  int async_set = 1;
+  const void* pf_ptr = nullptr;   // hsk_mgpu_prefetch: depth pointer whose preprocessing is already enqueued ...
+  int pf_set = -1;                // ... into this buffer set (on pstream, ev_pre[pf_set] recorded)
+  int mgpu_set = 0;               // buffer set of the slab frame in progress
+  hipGraph_t sgraph[2] = {};       // slab frame front (ICP + integrate + local raycast) per buffer set
+  hipGraphExec_t sgexec[2] = {};
+  void* sgraph_keys = nullptr;     // the keys buffer baked into those graphs
+  // hipGraph of the steady-state frame
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t gexec = nullptr;
+  bool graph_ready = false;
+  // use_graph = 2: the main-stream chain of a PIPELINED frame (19 ICP launches + 3 integrate + raycast) as one graph per
+  // image-buffer set -- the host's cost of a frame is then one launch where it was 23 (what limits several rooms on one GPU)
+  hipGraph_t pgraph[2] = {};
+  hipGraphExec_t pgexec[2] = {};
+  // profiling
+  bool prof = false;
+  bool prof_levels = false;  // profiling level 2: also an event at every ICP level (they cost about 4 us each)
+  hipEvent_t ev[HSK_NSTAGES + 1] = {};
+  hipEvent_t ev_icp[HSK_NLEVELS + 1] = {};  // profiling: start of each ICP level (coarsest first) and the end of the last
+  double icp_level_ms[HSK_NLEVELS] = {};    // ... summed per level, index = level (0 = finest)
+  double stage_ms[HSK_NSTAGES] = {};
+  // host time of the pipelined submissions, by phase (hsk_submit_host_us): staging copy, copy + preprocessing enqueue, the
+  // wait for the preprocessing, the main-stream chain's enqueue; and the submissions counted
+  double submit_us[4] = {};
+  unsigned long long submit_n = 0;
+  uint64_t prof_frames = 0;
+  // colour (hsk_enable_color; all null until then): the (r, g, b, w) volume, row-major; per image-buffer set a device flag "this
+  // frame has colour", written when the frame is submitted (the captured graphs read it, with the set's d_rgb); one pinned
+  // staging image (its upload has completed before a submission returns, as the depth frame's has)
+  unsigned* d_color = nullptr;
+  size_t color_bytes = 0;
+  int* d_has_color = nullptr;
+  unsigned char* h_rgb_stage = nullptr;
+  const unsigned char* rgb_src = nullptr;  // the colour of the frame being submitted (h_rgb_stage), null: a depth-only frame
+  int color_max_w = 0;
+  bool group_slab = false;  // a slab of a group (hsk_group_create*): no colour
+  float color_band = 0.0f;
+  // the indexed mesh's scratch (hsk_extract_mesh_indexed: edge bits, per-row tables; extract.hip mesh_index_layout), made on
+  // first use; its counts belong to ro_kind 4
+  void* d_mi = nullptr;
+  size_t mi_bytes = 0;
+  // scene views (hsk_render_view), made on first use: the free camera's block and the counter slots in device memory, and their
+  // pinned host side (the camera on its way in, the counts on their way out)
+  void* d_view = nullptr;
+  void* h_view = nullptr;
+  // volume fusion (hsk_fuse_volume), made on first use as a destination and only grown: 64 B of counters, then the source's
+  // brick table (fuse.hip)
+  void* d_fuse = nullptr;
+  size_t fuse_bytes = 0;
+  // volume images (hsk_pack_volume / hsk_unpack_volume), made on first use: 64 B of counters, the two class tables, the two
+  // size / offset tables and the scan's block sums (pack.hip); what the tables hold is the class and offset pass of the
+  // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
+  void* d_pack = nullptr;
+  uint64_t pk_epoch = 0;
+  bool pk_color = false;
+  unsigned pk_counts[16] = {};
+};
+
+#define HIPCHK(k, call)                                                                        \
+  do {                                                                                         \
+    hipError_t e_ = (call);                                                                    \
+    if (e_ != hipSuccess) {                                                                    \
+      char buf_[512];                                                                          \
+      snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+      (k)->err = buf_;                                                                         \
+      return HSK_ERR_HIP;                                                                      \
+    }                                                                                          \
+  } while (0)
+
+// ---- hskinfu_api.hip ----
+std::string& create_error();  // the thread's message of the calls that have no context (hsk_last_error(NULL))
+int fail(hsk_ctx* k, int code, const char* msg);
+void pose16_to_rt(const float m[16], float R[9], float t[3]);
+void rt_to_pose16(const float R[9], const float t[3], float m[16]);
+void flush_weights(hsk_ctx* k);
+int upload_state(hsk_ctx* k);
+int download_state(hsk_ctx* k);
+void leave_slab_bookkeeping(hsk_ctx* k);
+int set_pose_internal(hsk_ctx* k, const float pose[16]);
+void enqueue_raycast_and_resize(hsk_ctx* k, int* keys, bool report = false);
+void hsk_mark_group_slab(hsk_ctx* k);  // hsk_group_create* marks the contexts it makes as slabs, whatever planes they own
+// the state a call needs, or its refusal (HSK_ERR_STATE): no frame in flight; colour enabled; a context that stores its whole
+// volume ("<who>: not for a slab (<sentence>)").  `errs` takes the message: hsk_fuse_volume asks of its source, too, and reports
+// in its destination.
+int require_idle(const hsk_ctx* k, hsk_ctx* errs);
+inline int require_idle(hsk_ctx* k) { return require_idle(k, k); }
+int require_color(hsk_ctx* k);
+int require_whole_volume(const hsk_ctx* k, hsk_ctx* errs, const char* who, const char* sentence = "a context that stores part of its volume");
+// ---- api_readout.hip ----
+int ensure_pinned(hsk_ctx* k);
+void parallel_memcpy(void* dst, const void* src, size_t bytes);
+int copy_out(hsk_ctx* k, void* dst, const void* src_dev, size_t bytes);
+int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom = true);
+int read_u64(hsk_ctx* k, unsigned long long* dst, const unsigned long long* src_dev, int n = 1);
+// the product buffer carved into the arrays of one product, each 256-byte aligned: take() -> the next array's offset
+struct ProductLayout {
+  size_t bytes = 0;
+  size_t take(size_t n) {
+    const size_t at = bytes;
+    bytes += (n + 255) & ~(size_t)255;
+    return at;
+  }
+};

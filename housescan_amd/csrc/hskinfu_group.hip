@@ -28,9 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/hskinfu.h"
-
-void hsk_mark_group_slab(hsk_ctx* k);  // hskinfu_api.hip (library-internal)
+#include "hsk_ctx.h"  // (hsk_mark_group_slab)
 
 namespace {
 

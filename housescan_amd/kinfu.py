@@ -36,6 +36,30 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _apply_view_fields(v, width, height, fx, fy, cx, cy, pose, mode, light, light_in_camera, background):
+    """render_view's / render_section's keywords into the HskView `v`: those that are not None override its fields"""
+    for name, val in (("width", width), ("height", height), ("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("mode", mode),
+                      ("light_in_camera", light_in_camera)):
+        if val is not None:
+            setattr(v, name, val)
+    if pose is not None:
+        v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
+        v.follow = 0
+    if light is not None:
+        v.light[:] = [float(x) for x in light]
+    if background is not None:
+        v.background[:] = [int(x) for x in background]
+
+
+def _image_arrays(w, h, rgb, depth, vmap, nmap):
+    """the images asked for -> (dict of empty arrays, ptr(key): an array's address or None)"""
+    shapes = (("rgb", rgb, (h, w, 3), np.uint8), ("depth", depth, (h, w), np.uint16), ("vmap", vmap, (3, h, w), np.float32),
+              ("nmap", nmap, (3, h, w), np.float32))
+    ok = 1 <= w <= 4096 and 1 <= h <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
+    out = {key: np.empty(shape, dt) for key, want, shape, dt in shapes if want and ok}
+    return out, lambda k: out[k].ctypes.data if k in out else None
+
+
 class KinfuTracker:
     """One TSDF volume + tracker on one MI355X (one `hsk_ctx`)."""
 
@@ -348,29 +372,8 @@ class KinfuTracker:
         if view is None:
             view = self.default_view()
         v = _lib.HskView.from_buffer_copy(view)
-        for name, val in (("width", width), ("height", height), ("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("mode", mode),
-                          ("light_in_camera", light_in_camera)):
-            if val is not None:
-                setattr(v, name, val)
-        if pose is not None:
-            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
-            v.follow = 0
-        if light is not None:
-            v.light[:] = [float(x) for x in light]
-        if background is not None:
-            v.background[:] = [int(x) for x in background]
-        w, h = v.width, v.height
-        ok = 1 <= w <= 4096 and 1 <= h <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
-        out = {}
-        if rgb and ok:
-            out["rgb"] = np.empty((h, w, 3), np.uint8)
-        if depth and ok:
-            out["depth"] = np.empty((h, w), np.uint16)
-        if vmap and ok:
-            out["vmap"] = np.empty((3, h, w), np.float32)
-        if nmap and ok:
-            out["nmap"] = np.empty((3, h, w), np.float32)
-        ptr = lambda k: out[k].ctypes.data if k in out else None  # noqa: E731
+        _apply_view_fields(v, width, height, fx, fy, cx, cy, pose, mode, light, light_in_camera, background)
+        out, ptr = _image_arrays(v.width, v.height, rgb, depth, vmap, nmap)
         nh, nu = C.c_size_t(), C.c_size_t()
         self._ck(self.lib.hsk_render_view(self.h, C.byref(v), ptr("rgb"), ptr("depth"), ptr("vmap"), ptr("nmap"), C.byref(nh), C.byref(nu)))
         out["n_hit"], out["n_uncolored"] = nh.value, nu.value
@@ -396,17 +399,7 @@ class KinfuTracker:
             section = self.default_section()
         s = _lib.HskSection.from_buffer_copy(section)
         v = s.view
-        for name, val in (("width", width), ("height", height), ("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("mode", mode),
-                          ("light_in_camera", light_in_camera)):
-            if val is not None:
-                setattr(v, name, val)
-        if pose is not None:
-            v.pose[:] = [float(x) for x in np.asarray(pose, np.float32).reshape(16)]
-            v.follow = 0
-        if light is not None:
-            v.light[:] = [float(x) for x in light]
-        if background is not None:
-            v.background[:] = [int(x) for x in background]
+        _apply_view_fields(v, width, height, fx, fy, cx, cy, pose, mode, light, light_in_camera, background)
         if projection is not None:
             s.projection = int(projection)
         if light_directional is not None:
@@ -418,18 +411,7 @@ class KinfuTracker:
                 s.clip[c][:] = [float(x) for x in pl]
         if cut_rgb is not None:
             s.cut_rgb[:] = [int(x) for x in cut_rgb]
-        w, h = v.width, v.height
-        ok = 1 <= w <= 4096 and 1 <= h <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
-        out = {}
-        if rgb and ok:
-            out["rgb"] = np.empty((h, w, 3), np.uint8)
-        if depth and ok:
-            out["depth"] = np.empty((h, w), np.uint16)
-        if vmap and ok:
-            out["vmap"] = np.empty((3, h, w), np.float32)
-        if nmap and ok:
-            out["nmap"] = np.empty((3, h, w), np.float32)
-        ptr = lambda k: out[k].ctypes.data if k in out else None  # noqa: E731
+        out, ptr = _image_arrays(v.width, v.height, rgb, depth, vmap, nmap)
         nh, nc, nu = C.c_size_t(), C.c_size_t(), C.c_size_t()
         self._ck(self.lib.hsk_render_section(self.h, C.byref(s), ptr("rgb"), ptr("depth"), ptr("vmap"), ptr("nmap"), C.byref(nh),
                                              C.byref(nc), C.byref(nu)))

@@ -13,9 +13,11 @@ mkdir -p $S
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan -fno-omit-frame-pointer -g"
 FL="-O1 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -Wno-unused-function -Wno-bitwise-instead-of-logical -mllvm -amdgpu-kernarg-preload-count=16 $SAN -fno-gpu-sanitize"
 cd $ROOT/housescan_amd/csrc
-python3 build_id.py --header $S/build/build_id.h 2>/dev/null || { mkdir -p $S/build; python3 build_id.py --header $S/build/build_id.h; }
+mkdir -p $S/build
+python3 build_id.py --header $S/build/build_id.h || exit 1
 OBJ=
-for f in integrate.hip raycast.hip exchange.hip extract.hip kernels_image.hip kernels_selftest.hip hskinfu_api.hip hskinfu_group.hip synth.cpp products.cpp house.cpp; do
+# the Makefile's own source list; "build/build_id.h" is found under $S, the sources' other headers beside them
+for f in $(make -s print-SRC); do
   /opt/rocm/bin/hipcc $FL -I$S -I. -x hip -c $f -o $S/$f.o || exit 1
   OBJ="$OBJ $S/$f.o"
 done
