@@ -81,6 +81,36 @@ class HskFuseStats(C.Structure):
     ]
 
 
+HSK_ALIGN_CONVERGED, HSK_ALIGN_MAX_ITERS, HSK_ALIGN_FEW, HSK_ALIGN_DEGENERATE, HSK_ALIGN_DIVERGED = 0, 1, 2, 3, 4
+HSK_ALIGN_STATUS = ("converged", "max_iters", "few", "degenerate", "diverged")
+HSK_ALIGN_MAX_ITERS_CAP = 64
+HSK_ALIGN_DIRECT = -1
+
+
+class HskAlignParams(C.Structure):
+    """Mirror of `hsk_align_params` (include/hskinfu.h); a 0 in a field means its default."""
+
+    _fields_ = [
+        ("max_iters", C.c_int), ("probes", C.c_int),
+        ("cos_gate", C.c_float),
+        ("max_points", C.c_uint32), ("min_points", C.c_uint32),
+        ("eps_rot", C.c_float), ("eps_trans_m", C.c_float), ("max_rot", C.c_float), ("max_shift_m", C.c_float),
+    ]
+
+
+class HskAlignStats(C.Structure):
+    """Mirror of `hsk_align_stats` (include/hskinfu.h)."""
+
+    _fields_ = [
+        ("status", C.c_int), ("iterations", C.c_int),
+        ("n_points", C.c_uint32), ("stride", C.c_uint32),
+        ("n_used", C.c_uint32 * HSK_ALIGN_MAX_ITERS_CAP),
+        ("rms_m", C.c_float * HSK_ALIGN_MAX_ITERS_CAP),
+        ("x_last", C.c_float * 6),
+        ("sums_last", C.c_double * 28),
+    ]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -165,6 +195,10 @@ SYMBOLS = {
     "hsk_volume_file_info": (C.c_int, [C.c_char_p, C.POINTER(HskVolumeInfo)]),
     "hsk_config_from_volume": (C.c_int, [C.POINTER(HskVolumeInfo), C.POINTER(HskConfig)]),
     "hsk_resume_scan": (C.c_int, [_P, _F]),
+    "hsk_default_align_params": (None, [_P, C.POINTER(HskAlignParams)]),
+    "hsk_align_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _F, C.POINTER(HskAlignParams), _F, C.POINTER(HskAlignStats)]),
+    "hsk_align_volume": (C.c_int, [_P, _P, _F, C.POINTER(HskAlignParams), _F, C.POINTER(HskAlignStats)]),
+    "hsk_align_step": (C.c_int, [_D, _F, _F, _F, _F, _I]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

@@ -1,6 +1,7 @@
 // hsk_ctx.h -- library-internal, not installed: the context behind the C ABI (include/hskinfu.h) and the host helpers that the
-// ABI's three files share -- hskinfu_api.hip (context, frames), api_readout.hip (what reaches the caller), api_volume.hip (what
-// replaces or serialises the volume).  hskinfu_group.hip takes hsk_mark_group_slab from here.
+// ABI's four files share -- hskinfu_api.hip (context, frames), api_readout.hip (what reaches the caller), api_volume.hip (what
+// replaces or serialises the volume), api_align.hip (registration against the volume).  hskinfu_group.hip takes
+// hsk_mark_group_slab from here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -149,6 +150,11 @@ struct hsk_ctx {
   // volume images (hsk_pack_volume / hsk_unpack_volume), made on first use: 64 B of counters, the two class tables, the two
   // size / offset tables and the scan's block sums (pack.hip); what the tables hold is the class and offset pass of the
   // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
+  // volume alignment (hsk_align_cloud), made on first use as a destination and only grown: the accumulators (align.hip:
+  // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes; h_align: the accumulators' pinned host side
+  void* d_align = nullptr;
+  size_t align_bytes = 0;
+  unsigned long long* h_align = nullptr;
   void* d_pack = nullptr;
   uint64_t pk_epoch = 0;
   bool pk_color = false;

@@ -92,6 +92,18 @@ void launch_fuse_sweep(hipStream_t s, const void* src_vol, const unsigned* src_c
                        const VolParams& dv, const float A[9], const float b[3], const int box[6], const unsigned* tab, int max_w,
                        unsigned long long* counts, unsigned long long* chunks_total);
 
+// volume alignment (align.hip): one iteration's sums over n points -- six planes of `pitch` floats each at
+// `soa` (x, y, z, nx, ny, nz in source coordinates) -- moved by (R, t) and probed in the destination volume.  acc:
+// HSK_ALIGN_ACC_WORDS 64-bit words zeroed by the caller: HSK_ALIGN_SHARDS rows of 32, in each the 28 sums as integers in
+// units of 2^-26 (two's complement) and, in word 28, the contributing points
+#define HSK_ALIGN_SHARDS 16
+#define HSK_ALIGN_ACC_WORDS (HSK_ALIGN_SHARDS * 32)
+struct AlignPose {
+  float R[9], t[3];
+};
+void launch_align_iter(hipStream_t s, const void* dst_vol, const VolParams& dv, const float* soa, unsigned n, unsigned pitch,
+                       const AlignPose& m, int probes, float cos_gate, unsigned long long* acc);
+
 // sparse volume image (pack.hip): bricks of 8^3 voxels, pack_bricks of them, a class byte and a record size
 // (in 4-byte words) each.  launch_pack_scan turns the sizes into offsets in place (an exclusive scan; bsum: pack_scan_blocks
 // words of scratch) and leaves in counts[0..3] the bricks per class, in counts[4] the payload's length in words (8 words).

@@ -154,6 +154,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_view);
   F(k->d_fuse);
   F(k->d_pack);
+  F(k->d_align);
+  if (k->h_align) (void)hipHostFree(k->h_align);
   if (k->h_view) (void)hipHostFree(k->h_view);
   for (auto& b : k->ib) F(b.d_rgb);
   if (k->h_rgb_stage) (void)hipHostFree(k->h_rgb_stage);

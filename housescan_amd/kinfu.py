@@ -430,6 +430,62 @@ class KinfuTracker:
         return {"n_fused": int(st.n_fused), "n_colored": int(st.n_colored), "chunks_total": int(st.chunks_total),
                 "chunks_swept": int(st.chunks_swept), "box": tuple(int(x) for x in st.box)}
 
+    # ---- volume alignment -----------------------------------------------------------------------------
+    def default_align_params(self):
+        """the defaults of align_cloud / align_from as values (an `_lib.HskAlignParams`)"""
+        p = _lib.HskAlignParams()
+        self.lib.hsk_default_align_params(self.h, C.byref(p))
+        return p
+
+    @staticmethod
+    def _align_params(probes, over):
+        """the keywords into an HskAlignParams (a field left out is 0: its default); probes: to either side, 0 = the point
+        itself only (the C field's HSK_ALIGN_DIRECT), None = the default"""
+        p = _lib.HskAlignParams()
+        if probes is not None:
+            p.probes = _lib.HSK_ALIGN_DIRECT if int(probes) == 0 else int(probes)
+        for name, val in over.items():
+            if not hasattr(p, name) or name == "probes":
+                raise TypeError(f"unknown alignment parameter {name!r}")
+            setattr(p, name, val)
+        return p
+
+    @staticmethod
+    def _align_result(out, st):
+        n = max(0, min(int(st.iterations), _lib.HSK_ALIGN_MAX_ITERS_CAP))
+        return out.reshape(4, 4), {"status": _lib.HSK_ALIGN_STATUS[st.status], "iterations": int(st.iterations), "n_points": int(st.n_points),
+                                   "stride": int(st.stride), "n_used": [int(v) for v in st.n_used[:n]],
+                                   "rms_m": np.array(st.rms_m[:n], np.float32), "x_last": np.array(st.x_last[:], np.float32),
+                                   "sums_last": np.array(st.sums_last[:], np.float64)}
+
+    def align_cloud(self, xyz, normals, src_to_dst, probes=None, **params):
+        """refine the rigid 4x4 matrix `src_to_dst` (p_dst = M p_src) so that the points xyz [n, 3] with unit normals [n, 3]
+        towards free space (e.g. another tracker's extract_cloud_attrs) lie on this volume's surface (hsk_align_cloud).
+        probes: TSDF look-ups to either side along the normal, in steps of the truncation distance (None: 3; 0: none);
+        params: the other fields of hsk_align_params (max_iters, cos_gate, max_points, min_points, eps_rot, eps_trans_m,
+        max_rot, max_shift_m).  Synchronous; this tracker's volume, pose and model maps are not touched.
+        -> (matrix [4, 4] float32, dict(status, iterations, n_points, stride, n_used, rms_m, x_last, sums_last)); the status
+        "max_iters" means: do not trust the matrix; "diverged" hands src_to_dst back."""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(pts) != len(nrm):
+            raise ValueError(f"align_cloud: {len(pts)} points but {len(nrm)} normals")
+        m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
+        out, st = np.zeros(16, np.float32), _lib.HskAlignStats()
+        p = self._align_params(probes, params)
+        self._ck(self.lib.hsk_align_cloud(self.h, pts.ctypes.data if len(pts) else None, nrm.ctypes.data if len(pts) else None, len(pts),
+                                          _fp(m), C.byref(p), _fp(out), C.byref(st)))
+        return self._align_result(out, st)
+
+    def align_from(self, src, src_to_dst, probes=None, **params):
+        """align_cloud with the cloud and normals of tracker `src`'s volume (hsk_align_volume): the matrix to hand to
+        fuse_from(src, .)"""
+        m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
+        out, st = np.zeros(16, np.float32), _lib.HskAlignStats()
+        p = self._align_params(probes, params)
+        self._ck(self.lib.hsk_align_volume(self.h, None if src is None else src.h, _fp(m), C.byref(p), _fp(out), C.byref(st)))
+        return self._align_result(out, st)
+
     # ---- volume files -----------------------------------------------------------------------------------
     def pack_volume(self, with_info=False):
         """the volume (TSDF, and colour once enabled) as a lossless sparse image, packed on the device (hsk_pack_volume)

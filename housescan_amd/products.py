@@ -196,6 +196,19 @@ def invert_rigid(m):
     return out.reshape(4, 4)
 
 
+def align_step(sums27, m, centre):
+    """host only: one alignment iteration's solve and pose update about `centre` (hsk_align_step) -> (m_next [4, 4] float32,
+    x6 float32, ok); a singular system: m_next = m, x6 zeros, ok False"""
+    s = np.ascontiguousarray(sums27, np.float64).reshape(-1)[:27].copy()
+    a = np.ascontiguousarray(m, np.float32).reshape(16)
+    c = np.ascontiguousarray(centre, np.float32).reshape(3)
+    out, x6, ok = np.empty(16, np.float32), np.empty(6, np.float32), C.c_int()
+    fp = C.POINTER(C.c_float)
+    _ck(_lib.load().hsk_align_step(s.ctypes.data_as(C.POINTER(C.c_double)), a.ctypes.data_as(fp), c.ctypes.data_as(fp),
+                                   out.ctypes.data_as(fp), x6.ctypes.data_as(fp), C.byref(ok)), "hsk_align_step")
+    return out.reshape(4, 4), x6, bool(ok.value)
+
+
 def fuse_footprint(src_dims, src_size_m, dst_dims, dst_size_m, src_to_dst):
     """the half-open destination voxel box (x0, x1, y0, y1, z0, z1) that can receive a sample when a source volume of
     src_dims voxels over src_size_m metres is fused through `src_to_dst` (hsk_fuse_footprint); all zeros when empty"""

@@ -388,6 +388,73 @@ int hsk_config_from_volume(const hsk_volume_info* info, hsk_config* c);
  * HSK_ERR_STATE: a frame in flight, a slab of a group. */
 int hsk_resume_scan(hsk_ctx* k, const float pose[16]);
 
+/* ---- Volume alignment: a cloud with normals, or another volume, registered against this volume's TSDF on the device
+ * (DESIGN.md 3.12 the kernel, 8f the rule).  It makes or improves the rigid matrix that hsk_fuse_volume and hsk_resume_scan take:
+ * stitch -> align -> fuse for the rooms of a house, load -> align -> fuse / resume for a second session of a room.
+ * Every source point p (unit normal n towards free space) is moved by the current M and looked up in the destination's TSDF
+ * at p and at `probes` steps of the truncation distance tau to either side along n: a TSDF holds distance only within tau of
+ * a surface, the probes widen the basin to (probes + 1) tau.  The probe with the smallest |F| whose TSDF gradient agrees with
+ * n (cosine >= cos_gate) gives the point its row of a point-to-plane system; the 27 + 1 sums are exact (the ICP's 2^-26
+ * quantisation, integer accumulation), the 6 x 6 solve and the pose update are the tracker's (hsk_icp_solve), taken about
+ * the volume's centre.  Far probes can find OTHER surfaces (a prototype of the rule ended 11 mm off with 5 probes on the scene
+ * of DESIGN.md 8f; the exact rule did not repeat that, it took 5 iterations instead of 4): the default is 3, whose basin of
+ * 4 tau already exceeds the wall stitch's 5 cm at every resolution, at 7 look-ups per point instead of 11.
+ * What the statuses do NOT say: the points of one wall alone do not make the solve fail -- rounding keeps the 6 x 6 system
+ * regular -- and may even end CONVERGED, with the motion along the wall left wherever it was (15 mm off on that scene).  Give it
+ * points whose normals span the three directions. */
+#define HSK_ALIGN_CONVERGED 0   /* the last step was below eps_rot and eps_trans_m: out is the refined matrix              */
+#define HSK_ALIGN_MAX_ITERS 1   /* max_iters steps without that: DO NOT TRUST out                                          */
+#define HSK_ALIGN_FEW 2         /* fewer than min_points points found a valid probe: out is the last matrix formed         */
+#define HSK_ALIGN_DEGENERATE 3  /* the 6 x 6 system was singular: out is the last matrix formed                            */
+#define HSK_ALIGN_DIVERGED 4    /* the steps' sum passed max_rot or max_shift_m: out is src_to_dst, bit for bit            */
+#define HSK_ALIGN_MAX_ITERS_CAP 64
+#define HSK_ALIGN_DIRECT (-1)   /* `probes`: none to either side, the point itself only (0 means the default)              */
+typedef struct {
+  int max_iters;        /* 1..64                                                             default 30             */
+  int probes;           /* to either side, 1..8; HSK_ALIGN_DIRECT: none                      default 3              */
+  float cos_gate;       /* least cosine between n and the TSDF gradient, (0, 1]              default 0.5            */
+  uint32_t max_points;  /* the cloud is taken with the stride ceil(n / max_points); <= 2^20  default 262144         */
+  uint32_t min_points;  /*                                                                   default 256            */
+  float eps_rot;        /* radians: largest |angle| of a step that counts as converged       default 1e-5           */
+  float eps_trans_m;    /* metres, likewise                                                  default 1e-5           */
+  float max_rot;        /* radians: sum over the steps of their largest |angle|              default 0.2            */
+  float max_shift_m;    /* metres, likewise                                                  default 2 (probes + 1) tau */
+} hsk_align_params;     /* a 0 in a field means its default                                                         */
+typedef struct {
+  int status;                                /* HSK_ALIGN_*                                                          */
+  int iterations;                            /* iterations taken, 1..max_iters                                       */
+  uint32_t n_points, stride;                 /* points used (of every `stride` one, from the first)                  */
+  uint32_t n_used[HSK_ALIGN_MAX_ITERS_CAP];  /* per iteration: points with a valid probe                             */
+  float rms_m[HSK_ALIGN_MAX_ITERS_CAP];      /* per iteration: root mean square of their residuals (0 without a point) */
+  float x_last[6];                           /* the last solved step (alpha, beta, gamma, tx, ty, tz)                */
+  double sums_last[28];                      /* the last iteration's sums: the solve's 27, then the residuals' squares */
+} hsk_align_stats;
+
+/* the defaults of the table above, as values (max_shift_m from dst's truncation distance; 0 with dst NULL) */
+void hsk_default_align_params(const hsk_ctx* dst, hsk_align_params* p);
+/* n points xyz (3 floats each) with unit normals towards free space (3 floats each; NaN normals are allowed, such points never
+ * contribute), in source coordinates; src_to_dst the rough matrix (row-major, p_dst = M p_src, rigid); out the refined one.
+ * params NULL: the defaults; stats may be NULL.  Synchronous.  The points go up once, into a scratch buffer that dst owns
+ * (made on first use, only grown); an iteration is one kernel launch on dst's stream and a read-back of 4 KiB.  dst's deferred
+ * free-space weights are written back first (the rule reads weights); nothing else of dst is written: not the volume, the
+ * brick flags, the tracker pose, the model maps or the cached count passes.  Every HSK_ALIGN_* status returns HSK_OK: the
+ * status is a value, like tracked = 0.  n = 0 is not an error (HSK_ALIGN_FEW).
+ * HSK_ERR_ARG (out untouched): a NULL context, xyz (with n > 0), normals (with n > 0) or out; a matrix hsk_invert_rigid refuses;
+ * a parameter outside its range; half the diagonal of dst's box above 8 m or (probes + 1) tau above 8 m (the sums' exactness).
+ * HSK_ERR_STATE (out untouched): a frame in flight, a slab of a group or any context that stores part of its volume
+ * (hsk_render_view's cases). */
+int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* normals, size_t n, const float src_to_dst[16],
+                    const hsk_align_params* params, float out[16], hsk_align_stats* stats);
+/* src's hsk_extract_cloud_attrs product (xyz and normals) handed to hsk_align_cloud: the result is that of making the two
+ * calls yourself, bit for bit.  The cloud passes through host memory.  Only dst's TSDF is sampled, so -- unlike the fuse --
+ * the two truncation distances need not be equal.  Errors as hsk_align_cloud's, the state errors also for src; a NULL src or src == dst:
+ * HSK_ERR_ARG. */
+int hsk_align_volume(hsk_ctx* dst, hsk_ctx* src, const float src_to_dst[16], const hsk_align_params* params, float out[16],
+                     hsk_align_stats* stats);
+/* host only: one iteration's solve and pose update about `centre`: x6 = hsk_icp_solve(sums27); with (R, t) = m the tracker's
+ * pose update is applied to (R, t - centre) and centre added back.  A singular system: *ok = 0, x6 zeros, m_next = m. */
+int hsk_align_step(const double sums27[27], const float m[16], const float centre[3], float m_next[16], float x6[6], int* ok);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */

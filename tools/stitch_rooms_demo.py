@@ -23,6 +23,11 @@ context's positive octant).  house_fused_mesh.ply is one hsk_extract_mesh_indexe
 rooms overlap there is one surface, not two), house_fused_floorplan.ppm one hsk_render_section of it (--floorplan's camera);
 report.json gets a "fused_house" block with the statistics of every fuse and the milliseconds.
 
+--refine (with --fuse-house): every room after the first is first registered against the house volume fused so far, starting
+from its stitched .xf (hsk_align_volume: the room's cloud and normals against the house's TSDF), and fused by the refined matrix,
+which is written as <room>.refined.xf; both matrices and every iteration's n_used / rms are printed.  A registration that does
+not end CONVERGED keeps the stitched matrix.
+
 --save-volumes: behind each scan the room's volume is written to <room dir>/volume.hskv (hsk_save_volume: a sparse image packed
 on the GPU) and the room's context is closed.  --floorplan and --fuse-house then load one room at a time from its file into a
 single scratch context (hsk_load_volume), so at most two contexts are alive at once however many rooms the house has.
@@ -198,8 +203,9 @@ def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
             "end_to_end_ms": round(ms, 2)}
 
 
-def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=0.25):
-    """one house volume on the GPU: every room fused into it by its .xf; one mesh and one floor plan of the whole"""
+def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=0.25, refine=False):
+    """one house volume on the GPU: every room fused into it by its .xf (with `refine`: by the .xf registered against the house
+    so far); one mesh and one floor plan of the whole"""
     from housescan_amd import products as P
     Ms = [np.asarray(M, np.float64) for M in Ms]
     cell = 3.0 / volume                                       # the rooms' cell (a room's context is volume^3 over 3 m)
@@ -213,10 +219,30 @@ def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=
     house = hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size))
     make_ms = 1e3 * (time.perf_counter() - t0)
     rooms = []
-    for trk, M in zip(trackers, Ms):
+    for i, (trk, M) in enumerate(zip(trackers, Ms)):
+        m = (T @ M).astype(np.float32)
+        align = None
+        if refine and i > 0:
+            t0 = time.perf_counter()
+            m_ref, a = house.align_from(trk, m)
+            align = {"status": a["status"], "iterations": a["iterations"], "n_points": a["n_points"], "stride": a["stride"],
+                     "n_used": a["n_used"], "rms_mm": [round(1e3 * float(v), 4) for v in a["rms_m"]],
+                     "ms": round(1e3 * (time.perf_counter() - t0), 3)}
+            xf = (np.linalg.inv(T) @ m_ref.astype(np.float64)).astype(np.float32)       # room -> house, as the stitched .xf is
+            print(f"room{variants[i]}: stitched .xf\n{M.astype(np.float32)}\nrefined ({a['status']}, {a['iterations']} iterations)\n{xf}")
+            for k, (nu, rms) in enumerate(zip(a["n_used"], a["rms_m"])):
+                print(f"  iteration {k}: n_used {nu} of {a['n_points']}, rms {1e3 * float(rms):.3f} mm")
+            if a["status"] == "converged":
+                m = m_ref
+                P.write_xf(os.path.join(out, f"room{variants[i]}.refined.xf"), xf)
+            else:
+                print(f"room{variants[i]}: the registration ended {a['status']}: the stitched matrix is kept")
+            align["used"] = a["status"] == "converged"
         t0 = time.perf_counter()
-        st = house.fuse_from(trk, (T @ M).astype(np.float32))
+        st = house.fuse_from(trk, m)
         st["ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+        if align is not None:
+            st["align"] = align
         st["box"] = list(st["box"])
         rooms.append(st)
     t0 = time.perf_counter()
@@ -244,6 +270,7 @@ def main():
     ap.add_argument("--indexed-mesh", action="store_true", help="rooms' meshes indexed with normals: <room_dir>/mesh.ply, no host weld")
     ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
     ap.add_argument("--fuse-house", action="store_true", help="house_fused_mesh.ply + house_fused_floorplan.ppm: the rooms' volumes fused into one house volume on the GPU")
+    ap.add_argument("--refine", action="store_true", help="with --fuse-house: register every room after the first against the house fused so far (<room>.refined.xf)")
     ap.add_argument("--save-volumes", action="store_true", help="<room dir>/volume.hskv behind each scan, the room's context closed; --floorplan / --fuse-house load them one at a time")
     args = ap.parse_args()
 
@@ -311,7 +338,8 @@ def main():
     if args.floorplan:
         report["floorplan"] = floorplan(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out)
     if args.fuse_house:
-        report["fused_house"] = fuse_house(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out, args.volume)
+        report["fused_house"] = fuse_house(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out, args.volume,
+                                            refine=args.refine)
     trackers.close()
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
