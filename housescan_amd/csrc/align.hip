@@ -3,7 +3,7 @@
 //
 // The rule (tests/align_twin.py restates it in numpy): a source point (x, y, z) with normal n is moved by the
 // current matrix, p_i = ((R[i][0] x + R[i][1] y) + R[i][2] z) + t[i], n likewise without t.  The probes j = 0, +1, -1, .., +J, -J
-// look at a = p + ((float)j tau) n with the raycast's trilinear sample F (fuse.hip's restatement: the same guards, cell choice,
+// look at a = p + ((float)j tau) n with the raycast's trilinear sample F (hsk_sample.h: the same guards, cell choice,
 // fractions and summation order), the smallest weight Ws of its eight taps and the gradient g of the trilinear form from the
 // same eight values, divided by the cells.  A probe is valid when the sample is not the shell's NaN, Ws > 0, |F| < 1, g.g > 0
 // and n . g / |g| >= cos_gate; the valid probe with the smallest |F| (the earliest on a tie) gives the point's row
@@ -23,14 +23,7 @@
 #include "hsk_launch.h"
 #include "hsk_align_point.h"
 
-// the sum of a 64-bit integer over the wave, in every lane
-static __device__ __forceinline__ long long align_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void k_align_iter(const unsigned* __restrict__ vol, const float* __restrict__ soa, AlignVol dv,
+__global__ __launch_bounds__(256) void k_align_iter(const unsigned* __restrict__ vol, const float* __restrict__ soa, SampleVol dv,
                                                     AlignArgs aa, unsigned long long* __restrict__ acc_out) {
   const int lane = threadIdx.x & 63;
   const unsigned n_threads = gridDim.x * 256u;
@@ -51,7 +44,7 @@ __global__ __launch_bounds__(256) void k_align_iter(const unsigned* __restrict__
   long long mine = 0;
 #pragma unroll
   for (int k = 0; k < 29; ++k) {
-    const long long t = align_wave_sum(k < 28 ? (long long)acc[k] : (long long)n_used);
+    const long long t = hsk_wave_sum(k < 28 ? (long long)acc[k] : (long long)n_used);
     mine = lane == k ? t : mine;
   }
   const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -61,14 +54,9 @@ __global__ __launch_bounds__(256) void k_align_iter(const unsigned* __restrict__
 void launch_align_iter(hipStream_t s, const void* dst_vol, const VolParams& dv, const float* soa, unsigned n, unsigned pitch,
                        const AlignPose& m, int probes, float cos_gate, unsigned long long* acc) {
   if (n == 0) return;
-  AlignVol av;
-  av.X = dv.X;
-  av.Y = dv.Y;
-  av.Z = dv.Z;
+  const SampleVol av = hsk_sample_vol(dv);
   AlignArgs aa;
   for (int i = 0; i < 3; ++i) {
-    av.cell[i] = dv.cell[i];
-    av.icell[i] = dv.icell[i];
     aa.t[i] = m.t[i];
     aa.c[i] = dv.size[i] * 0.5f;
   }

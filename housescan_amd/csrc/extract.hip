@@ -3,9 +3,10 @@
 #pragma clang fp contract(off)
 #include "hsk_dev.h"
 #include "hsk_launch.h"
+#include "hsk_march.h"  // (trilinear: the normals are the raycast's)
 #include <type_traits>
 
-// inclusive scan and sum of v over the wave's 64 lanes
+// inclusive scan of v over the wave's 64 lanes
 static __device__ __forceinline__ int wave_scan(int v) {
   const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -13,11 +14,6 @@ static __device__ __forceinline__ int wave_scan(int v) {
     const int u = __shfl_up(v, o, 64);
     if (lane >= o) v += u;
   }
-  return v;
-}
-static __device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 static __device__ __forceinline__ void store3(float* __restrict__ dst, float a, float b, float c) {
@@ -131,7 +127,7 @@ static __device__ __forceinline__ void sweep_row(const VolParams& vp, const unsi
       if (n) write(x, y, z, zr, n, base + (unsigned long long)(scan - n));
       base += __shfl(scan, 63, 64);
     } else {
-      total += wave_sum((unsigned)n);
+      total += hsk_wave_sum((unsigned)n);
     }
   }
   if constexpr (!WRITE)
@@ -583,46 +579,23 @@ void launch_extract_mesh_mc(hipStream_t s, const void* vol, const VolParams& vp,
 //   colour: of the crossing's voxel with the smaller |tsdf| (the first on a tie), of the other when that one has colour
 //           weight 0, (0, 0, 0) and one count in n_uncolored when both have
 // ------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ int attr_vox(float p, float cell) {  // floor(p / cell) of the spec, -1 below 0 or NaN
-  const float q = floorf(p / cell);
-  if (!(q >= 0.0f)) return -1;
-  if (q > 1.0e6f) return 1000000;
-  return (int)q;
-}
-static __device__ __forceinline__ float attr_tsdf(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
-  const int zz = z - vp.zs0;
-  if (zz < 0 || zz >= vp.nzs) return 0.0f;
-  return (float)vol[hsk_vox_index(vp, x, y, zz)].x / 32767.0f;
-}
-// the trilinear TSDF sample of A.6 (raycast.hip: trilinear), written with the plain correctly rounded quotients of the spec
-static __device__ float attr_trilinear(const short2* __restrict__ vol, const VolParams& vp, float px, float py, float pz) {
-  int gx = attr_vox(px, vp.cell[0]), gy = attr_vox(py, vp.cell[1]), gz = attr_vox(pz, vp.cell[2]);
-  if (!(gx > 0 && gx < vp.X - 1 && gy > 0 && gy < vp.Y - 1 && gz > 0 && gz < vp.Z - 1)) return HSK_NANF;
-  if (px < ((float)gx + 0.5f) * vp.cell[0]) gx -= 1;
-  if (py < ((float)gy + 0.5f) * vp.cell[1]) gy -= 1;
-  if (pz < ((float)gz + 0.5f) * vp.cell[2]) gz -= 1;
-  const float a = (px - ((float)gx + 0.5f) * vp.cell[0]) / vp.cell[0];
-  const float b = (py - ((float)gy + 0.5f) * vp.cell[1]) / vp.cell[1];
-  const float c = (pz - ((float)gz + 0.5f) * vp.cell[2]) / vp.cell[2];
-  float res = attr_tsdf(vol, vp, gx, gy, gz) * (1.0f - a) * (1.0f - b) * (1.0f - c);
-  res = res + attr_tsdf(vol, vp, gx, gy, gz + 1) * (1.0f - a) * (1.0f - b) * c;
-  res = res + attr_tsdf(vol, vp, gx, gy + 1, gz) * (1.0f - a) * b * (1.0f - c);
-  res = res + attr_tsdf(vol, vp, gx, gy + 1, gz + 1) * (1.0f - a) * b * c;
-  res = res + attr_tsdf(vol, vp, gx + 1, gy, gz) * a * (1.0f - b) * (1.0f - c);
-  res = res + attr_tsdf(vol, vp, gx + 1, gy, gz + 1) * a * (1.0f - b) * c;
-  res = res + attr_tsdf(vol, vp, gx + 1, gy + 1, gz) * a * b * (1.0f - c);
-  res = res + attr_tsdf(vol, vp, gx + 1, gy + 1, gz + 1) * a * b * c;
-  return res;
-}
 // the normal rule at p: NaN x 3 outside the (1, dims - 2) interior (shared by the cloud's and the indexed mesh's attributes)
 static __device__ __forceinline__ void attr_normal(const short2* __restrict__ vol, const VolParams& vp, float px, float py, float pz,
                                                    float* nx, float* ny, float* nz) {
   *nx = HSK_NANF, *ny = HSK_NANF, *nz = HSK_NANF;
   const float qx = floorf(px / vp.cell[0]), qy = floorf(py / vp.cell[1]), qz = floorf(pz / vp.cell[2]);
   if (qx > 1.0f && qx < (float)(vp.X - 2) && qy > 1.0f && qy < (float)(vp.Y - 2) && qz > 1.0f && qz < (float)(vp.Z - 2)) {
-    const float gxn = attr_trilinear(vol, vp, px + vp.cell[0], py, pz) - attr_trilinear(vol, vp, px - vp.cell[0], py, pz);
-    const float gyn = attr_trilinear(vol, vp, px, py + vp.cell[1], pz) - attr_trilinear(vol, vp, px, py - vp.cell[1], pz);
-    const float gzn = attr_trilinear(vol, vp, px, py, pz + vp.cell[2]) - attr_trilinear(vol, vp, px, py, pz - vp.cell[2]);
+    // (one axis at a time, in a loop that stays a loop: written out, the six branch-free samples keep all 48 taps in flight and
+    // cost both kernels waves -- profiles/r16/refactor_notes.md; p +- 0.0f is p)
+    float gxn = 0.0f, gyn = 0.0f, gzn = 0.0f;
+#pragma nounroll
+    for (int ax = 0; ax < 3; ++ax) {
+      const float ex = ax == 0 ? vp.cell[0] : 0.0f, ey = ax == 1 ? vp.cell[1] : 0.0f, ez = ax == 2 ? vp.cell[2] : 0.0f;
+      const float d = trilinear(vol, vp, px + ex, py + ey, pz + ez) - trilinear(vol, vp, px - ex, py - ey, pz - ez);
+      gxn = ax == 0 ? d : gxn;
+      gyn = ax == 1 ? d : gyn;
+      gzn = ax == 2 ? d : gzn;
+    }
     const float ninv = 1.0f / sqrtf(hsk_dot3(gxn, gyn, gzn, gxn, gyn, gzn));
     *nx = gxn * ninv;
     *ny = gyn * ninv;
@@ -664,7 +637,7 @@ static __device__ __forceinline__ void write_attrs(const short2* __restrict__ vo
 // ... and, once per wave, the lanes' uncoloured items into the product's counter
 static __device__ __forceinline__ void add_uncolored(unsigned uncol, const unsigned char* rgb, unsigned long long* __restrict__ n_uncolored) {
   if (rgb && n_uncolored) {
-    const unsigned sum = wave_sum(uncol);
+    const unsigned sum = hsk_wave_sum(uncol);
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(n_uncolored, (unsigned long long)sum);
   }
 }

@@ -63,85 +63,27 @@ __global__ __launch_bounds__(256) void k_fuse_bricks(const uint4* __restrict__ v
   if ((tab[bit >> 5] & m) == 0u) atomicOr(&tab[bit >> 5], m);
 }
 
-// what the sweep needs of a volume's geometry (VolParams carries three times as much, and the sweep's scalar registers are full)
-struct FuseVol {
-  int X, Y, Z;
-  float cell[3];
-  double icell[3];
-};
-static FuseVol fuse_vol(const VolParams& vp) {
-  FuseVol v;
-  v.X = vp.X;
-  v.Y = vp.Y;
-  v.Z = vp.Z;
-  for (int i = 0; i < 3; ++i) {
-    v.cell[i] = vp.cell[i];
-    v.icell[i] = vp.icell[i];
-  }
-  return v;
-}
-
-// floor of a quotient with the specification's range guards (the oracle's vox_of)
-static __device__ __forceinline__ int fuse_vox_of_q(float quot) {
-  const float q = floorf(quot);
-  if (!(q >= 0.0f)) return -1;
-  if (q > 1.0e6f) return 1000000;
-  return (int)q;
-}
-
-static __device__ __forceinline__ int fuse_raw(unsigned w) { return (int)(short)(w & 0xffffu); }
-static __device__ __forceinline__ int fuse_wgt(unsigned w) { return (int)(short)(w >> 16); }
-
 // One destination voxel: `dw` its (tsdf, weight) pair, (px, py, pz) its source point.  Returns true when the voxel took a
-// sample (dw rewritten); (cx, cy, cz) is then the source voxel that contains the point (the colour rule's voxel).
-static __device__ __forceinline__ bool fuse_sample_merge(const unsigned* __restrict__ src, const FuseVol& sv, float px, float py,
+// sample (dw rewritten); (cx, cy, cz) is then the source voxel that contains the point (the colour rule's voxel).  The sample
+// is hsk_sample.h's: branch-free up to the taps, so the gathers of a lane's four voxels can be in flight together.
+static __device__ __forceinline__ bool fuse_sample_merge(const unsigned* __restrict__ src, const SampleVol& sv, float px, float py,
                                                          float pz, unsigned& dw, int& cx, int& cy, int& cz) {
-  int gx = fuse_vox_of_q(hsk_div_by_const(px, sv.icell[0])), gy = fuse_vox_of_q(hsk_div_by_const(py, sv.icell[1])),
-      gz = fuse_vox_of_q(hsk_div_by_const(pz, sv.icell[2]));
-  // branch-free up to the taps: the indices are clamped for the loads and the NaN of the sample (a point on the outer shell
-  // or outside) is selected behind them, so the gathers of a lane's four voxels can be in flight together
-  const bool ok = gx > 0 && gx < sv.X - 1 && gy > 0 && gy < sv.Y - 1 && gz > 0 && gz < sv.Z - 1;
-  gx = min(max(gx, 1), sv.X - 2);
-  gy = min(max(gy, 1), sv.Y - 2);
-  gz = min(max(gz, 1), sv.Z - 2);
-  cx = gx;
-  cy = gy;
-  cz = gz;
-  if (px < ((float)gx + 0.5f) * sv.cell[0]) gx -= 1;
-  if (py < ((float)gy + 0.5f) * sv.cell[1]) gy -= 1;
-  if (pz < ((float)gz + 0.5f) * sv.cell[2]) gz -= 1;
-  const float a = hsk_div_by_const(px - ((float)gx + 0.5f) * sv.cell[0], sv.icell[0]);
-  const float b = hsk_div_by_const(py - ((float)gy + 0.5f) * sv.cell[1], sv.icell[1]);
-  const float c = hsk_div_by_const(pz - ((float)gz + 0.5f) * sv.cell[2], sv.icell[2]);
-  // word indices (a volume holds fewer than 2^32 words: hsk_create): one term per axis, the upper neighbours by steps -- +1
-  // word in x (or into the next block: +13), one row pitch in y, +4 words in z (or into the next group of planes)
-  const unsigned pitch = (unsigned)((sv.X >> 2) << 4);
-  const unsigned tx0 = (((unsigned)gx >> 2) << 4) + ((unsigned)gx & 3u), tx1 = tx0 + ((gx & 3) == 3 ? 13u : 1u);
-  const unsigned ty0 = (unsigned)gy * pitch, ty1 = ty0 + pitch;
-  const unsigned tz0 = ((unsigned)gz >> 2) * (unsigned)sv.Y * pitch + (((unsigned)gz & 3u) << 2);
-  const unsigned tz1 = tz0 + ((gz & 3) == 3 ? (unsigned)sv.Y * pitch - 12u : 4u);
-  const unsigned w000 = src[tz0 + ty0 + tx0], w100 = src[tz0 + ty0 + tx1], w010 = src[tz0 + ty1 + tx0], w110 = src[tz0 + ty1 + tx1];
-  const unsigned w001 = src[tz1 + ty0 + tx0], w101 = src[tz1 + ty0 + tx1], w011 = src[tz1 + ty1 + tx0], w111 = src[tz1 + ty1 + tx1];
-  const int Ws = min(min(min(fuse_wgt(w000), fuse_wgt(w100)), min(fuse_wgt(w010), fuse_wgt(w110))),
-                     min(min(fuse_wgt(w001), fuse_wgt(w101)), min(fuse_wgt(w011), fuse_wgt(w111))));
-  const bool take = ok && Ws > 0;  // not the NaN of the sample, and no tap never observed
-  const float f000 = hsk_tsdf_unpack(fuse_raw(w000)), f100 = hsk_tsdf_unpack(fuse_raw(w100));
-  const float f010 = hsk_tsdf_unpack(fuse_raw(w010)), f110 = hsk_tsdf_unpack(fuse_raw(w110));
-  const float f001 = hsk_tsdf_unpack(fuse_raw(w001)), f101 = hsk_tsdf_unpack(fuse_raw(w101));
-  const float f011 = hsk_tsdf_unpack(fuse_raw(w011)), f111 = hsk_tsdf_unpack(fuse_raw(w111));
-  float res = f000 * (1.0f - a) * (1.0f - b) * (1.0f - c);
-  res = res + f001 * (1.0f - a) * (1.0f - b) * c;
-  res = res + f010 * (1.0f - a) * b * (1.0f - c);
-  res = res + f011 * (1.0f - a) * b * c;
-  res = res + f100 * a * (1.0f - b) * (1.0f - c);
-  res = res + f101 * a * (1.0f - b) * c;
-  res = res + f110 * a * b * (1.0f - c);
-  res = res + f111 * a * b * c;
+  const SampleCell sc = hsk_sample_cell(sv, px, py, pz);
+  cx = sc.cx;
+  cy = sc.cy;
+  cz = sc.cz;
+  unsigned w[8];
+  float f[8];
+  hsk_sample_words(src, sv, sc, w);
+  const int Ws = hsk_sample_min_weight(w);
+  const bool take = sc.in && Ws > 0;  // not the NaN of the sample, and no tap never observed
+  hsk_sample_values(w, f);
+  const float res = hsk_sample_blend(f, sc.a, sc.b, sc.c);
   // (the merge too is computed for every voxel and selected: a lane's four voxels then share one instruction stream, where a
   // branch per voxel cost the sweep its scalar registers)
   const int q = min(max(__float2int_rn(take ? res * 32767.0f : 0.0f), -32767), 32767);
-  const int Wd = fuse_wgt(dw);
-  const int n = fuse_raw(dw) * Wd + q * Ws, W = max(Wd + Ws, 1);
+  const int Wd = hsk_pair_wgt(dw);
+  const int n = hsk_pair_raw(dw) * Wd + q * Ws, W = max(Wd + Ws, 1);
   const unsigned mag = (2u * (unsigned)abs(n) + (unsigned)W) / (2u * (unsigned)W);
   const int raw = n < 0 ? -(int)mag : (int)mag;
   dw = take ? (((unsigned)raw & 0xffffu) | ((unsigned)min(W, HSK_MAX_WEIGHT) << 16)) : dw;
@@ -165,17 +107,11 @@ struct FuseArgs {
   int max_w;          // the destination's colour max_weight
 };
 
-static __device__ __forceinline__ unsigned long long fuse_wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return (unsigned long long)v;
-}
-
 // counts: [0] voxels fused, [1] voxels coloured, [2] chunks swept.  Persistent waves: a workgroup stages the brick table once
 // (LDS: it fits 64 KiB) and its waves stride over the footprint's chunks; a wave adds its counts once, at its end.
 template <bool LDS, bool COLOR>
 __global__ __launch_bounds__(256) void k_fuse_sweep(const unsigned* __restrict__ src, const unsigned* __restrict__ scol,
-                                                    unsigned* __restrict__ dst, unsigned* __restrict__ dcol, FuseVol sv, FuseVol dv,
+                                                    unsigned* __restrict__ dst, unsigned* __restrict__ dcol, SampleVol sv, SampleVol dv,
                                                     FuseArgs fa, const unsigned* __restrict__ tab, unsigned long long* __restrict__ counts) {
   extern __shared__ __attribute__((aligned(16))) unsigned s_tab[];  // (staged with 16-B stores)
   if (LDS) {
@@ -292,7 +228,7 @@ __global__ __launch_bounds__(256) void k_fuse_sweep(const unsigned* __restrict__
       }
     }
   }
-  const unsigned long long f = fuse_wave_sum(n_fused), c = fuse_wave_sum(n_colored);
+  const unsigned long long f = hsk_wave_sum(n_fused), c = hsk_wave_sum(n_colored);
   if (lane == 0) {
     if (f) atomicAdd(&counts[0], f);
     if (c) atomicAdd(&counts[1], c);
@@ -341,7 +277,7 @@ void launch_fuse_sweep(hipStream_t s, const void* src_vol, const unsigned* src_c
   const unsigned* s32 = (const unsigned*)src_vol;
   unsigned* d32 = (unsigned*)dst_vol;
   const bool color = src_col && dst_col;
-  const FuseVol fsv = fuse_vol(sv), fdv = fuse_vol(dv);
+  const SampleVol fsv = hsk_sample_vol(sv), fdv = hsk_sample_vol(dv);
 #define HSK_FUSE_LAUNCH(L, C) \
   hipLaunchKernelGGL((k_fuse_sweep<L, C>), dim3(blocks), dim3(256), (L) ? tab_bytes : 0, s, s32, src_col, d32, dst_col, fsv, fdv, fa, tab, counts)
   if (lds && color)

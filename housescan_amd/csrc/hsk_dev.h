@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hsk_sample.h"  // the TSDF sample at a point, hsk_tsdf_unpack, hsk_div_by_const, hsk_dot3: host and device
 
 #define HSK_DIVISOR 32767
 #define HSK_MAX_WEIGHT 128
@@ -44,6 +45,19 @@ struct VolParams {
   int zchunk;      // planes a pass-A workgroup takes: 8, or 16 for volumes whose launch stays large with half the workgroups
                    // (hsk_pass_a_zchunk); also the unit of the lane-block summaries' layout (integrate.hip)
 };
+
+// what a sampler takes of it (hsk_sample.h)
+static inline SampleVol hsk_sample_vol(const VolParams& vp) {
+  SampleVol v;
+  v.X = vp.X;
+  v.Y = vp.Y;
+  v.Z = vp.Z;
+  for (int i = 0; i < 3; ++i) {
+    v.cell[i] = vp.cell[i];
+    v.icell[i] = vp.icell[i];
+  }
+  return v;
+}
 
 // ---- where a voxel lives (round 4) ------------------------------------------------------------------------------------
 // The volume is stored in 64-B BLOCKS of one lane-block each -- 4 x-adjacent voxels by 4 consecutive stored planes, the
@@ -142,24 +156,20 @@ struct PushDests {
 
 static __device__ __forceinline__ bool hsk_isnan(float x) { return x != x; }
 
+// the sum of an integer over the wave's 64 lanes, in every lane (an xor butterfly: every lane of the wave must arrive)
+template <class T>
+static __device__ __forceinline__ T hsk_wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // round-to-nearest-even with the +-1e6 range guard of the spec
 static __device__ __forceinline__ bool hsk_rint_guard(float f, int& out) {
   if (!(f > -1.0e6f && f < 1.0e6f)) return false;
   out = __float2int_rn(f);
   return true;
 }
-
-// (float)raw / 32767.0f of the specification, for an integer raw in [-32768, 32767], without the ~10-instruction
-// correctly-rounded f32 division: the product with the binary64 reciprocal, rounded to binary32, equals the binary32
-// quotient for EVERY such raw (checked exhaustively in tests/test_host_logic.py).
-static __device__ __forceinline__ float hsk_tsdf_unpack(int raw) {
-  return (float)((double)raw * (1.0 / 32767.0));
-}
-
-// x / c of the specification for a fixed binary32 divisor c, as a binary64 product with the correctly rounded binary64
-// reciprocal rc: a binary32 quotient of two binary32 numbers is either exact or at least 2^-48 (relative) away from a
-// rounding boundary (ties need c to be a power of two, where rc is exact), and the product is within 2^-52 of it.
-static __device__ __forceinline__ float hsk_div_by_const(float x, double rc) { return (float)((double)x * rc); }
 
 // ---- correctly rounded 1/x, sqrt(x) and a/n in a handful of instructions -------------------------------------------
 // The specification asks for the IEEE-754 correctly rounded results; the compiler's sequences for them cost 10-14
@@ -199,10 +209,6 @@ static __device__ __forceinline__ __amdgpu_buffer_rsrc_t hsk_buf(const void* bas
 }
 static __device__ __forceinline__ float hsk_buf_load_f32(__amdgpu_buffer_rsrc_t r, unsigned byte_off, unsigned scalar_off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)byte_off, (int)scalar_off, 0));
-}
-
-static __device__ __forceinline__ float hsk_dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return (ax * bx + ay * by) + az * bz;
 }
 
 // ---- the tile tables of a frame (one allocation per image-buffer set: launch_tile_max / launch_bilateral_scale fill the raw

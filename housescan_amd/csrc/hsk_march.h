@@ -1,9 +1,11 @@
 // hsk_march.h -- what the TSDF march's kernels share (raycast.hip: k_raycast, the tracker's model frame; view.hip:
-// k_render_view, a scene image from any camera): the voxel look-ups, the trilinear sample, the march's constants and its
-// wave-wide minimum.  The march itself is three pieces of function-body text -- hsk_march_stage.h, hsk_march_rays.h (the pinhole
-// ray) and hsk_march_loop.h -- that each kernel includes at its place: k_raycast compiles from exactly the tokens it had when
-// the text stood in raycast.hip, so its machine code cannot move when another kernel changes (tools/isa_compare.py checks
-// it).  section.hip's k_render_section puts its own ray piece between the stage and the loop.
+// k_render_view, a scene image from any camera; section.hip: k_render_section): the voxel look-up, the trilinear sample (also
+// the normals of extract.hip), the march's constants and its wave-wide minimum.  The march itself is three pieces of
+// function-body text -- hsk_march_stage.h, hsk_march_rays.h (the pinhole ray) and hsk_march_loop.h -- that each kernel includes at
+// its place; section.hip puts its own ray piece between the stage and the loop.  The sample's arithmetic -- where the point
+// lies among the voxel centres, the eight-term sum -- is hsk_sample.h's, shared with fusion and alignment; what is the
+// march's own here is the slab handling round it.  k_raycast's machine code is the bar for any change to either file: it must
+// not move (tools/isa_compare.py against a build of the parent).
 #pragma once
 #include "hsk_dev.h"
 // ------------------------------------------------------------------------------------------------------
@@ -11,14 +13,6 @@
 // neighbouring voxels (L1/L2 locality of the 4-B gathers).  Steps are owned by the slab that contains the
 // far sample's z plane; a single-device context owns all of them.
 // ------------------------------------------------------------------------------------------------------
-// voxel index from the quotient q = p / cell (floor, with the spec's range guards)
-static __device__ __forceinline__ int vox_of_q(float quot) {
-  const float q = floorf(quot);
-  if (!(q >= 0.0f)) return -1;
-  if (q > 1.0e6f) return 1000000;
-  return (int)q;
-}
-
 static __device__ __forceinline__ int raw_at(const short2* __restrict__ vol, const VolParams& vp, int x, int y, int z) {
   const int zz = z - vp.zs0;
   if (zz < 0 || zz >= vp.nzs) return 0;
@@ -34,20 +28,8 @@ static __device__ __forceinline__ int raw_at(const short2* __restrict__ vol, con
 // in flight together.
 static __device__ __forceinline__ float trilinear(const short2* __restrict__ vol, const VolParams& vp, float px, float py,
                                                   float pz) {
-  // floor(p / cell) and the fractional offsets below are the spec's f32 quotients, obtained as binary64 products
-  // (hsk_div_by_const): 3 instructions each instead of a ~10-instruction correctly rounded division
-  int gx = vox_of_q(hsk_div_by_const(px, vp.icell[0])), gy = vox_of_q(hsk_div_by_const(py, vp.icell[1])),
-      gz = vox_of_q(hsk_div_by_const(pz, vp.icell[2]));
-  const bool ok = gx > 0 && gx < vp.X - 1 && gy > 0 && gy < vp.Y - 1 && gz > 0 && gz < vp.Z - 1;
-  gx = min(max(gx, 1), vp.X - 2);
-  gy = min(max(gy, 1), vp.Y - 2);
-  gz = min(max(gz, 1), vp.Z - 2);
-  if (px < ((float)gx + 0.5f) * vp.cell[0]) gx -= 1;
-  if (py < ((float)gy + 0.5f) * vp.cell[1]) gy -= 1;
-  if (pz < ((float)gz + 0.5f) * vp.cell[2]) gz -= 1;
-  const float a = hsk_div_by_const(px - ((float)gx + 0.5f) * vp.cell[0], vp.icell[0]);
-  const float b = hsk_div_by_const(py - ((float)gy + 0.5f) * vp.cell[1], vp.icell[1]);
-  const float c = hsk_div_by_const(pz - ((float)gz + 0.5f) * vp.cell[2], vp.icell[2]);
+  const SampleCell sc = hsk_sample_cell(vp, px, py, pz);
+  const int gx = sc.x, gy = sc.y, gz = sc.z;
   // stored planes: a tap outside the slab reads plane 0 of the slab and is discarded (cannot happen when the
   // halo is sized as DESIGN.md prescribes)
   const int z0 = gz - vp.zs0, z1 = z0 + 1;
@@ -68,15 +50,9 @@ static __device__ __forceinline__ float trilinear(const short2* __restrict__ vol
   const float f010 = hsk_tsdf_unpack(in0 ? r010 : 0), f110 = hsk_tsdf_unpack(in0 ? r110 : 0);
   const float f001 = hsk_tsdf_unpack(in1 ? r001 : 0), f101 = hsk_tsdf_unpack(in1 ? r101 : 0);
   const float f011 = hsk_tsdf_unpack(in1 ? r011 : 0), f111 = hsk_tsdf_unpack(in1 ? r111 : 0);
-  float res = f000 * (1.0f - a) * (1.0f - b) * (1.0f - c);
-  res = res + f001 * (1.0f - a) * (1.0f - b) * c;
-  res = res + f010 * (1.0f - a) * b * (1.0f - c);
-  res = res + f011 * (1.0f - a) * b * c;
-  res = res + f100 * a * (1.0f - b) * (1.0f - c);
-  res = res + f101 * a * (1.0f - b) * c;
-  res = res + f110 * a * b * (1.0f - c);
-  res = res + f111 * a * b * c;
-  return ok ? res : HSK_NANF;
+  const float f[8] = {f000, f100, f010, f110, f001, f101, f011, f111};
+  const float res = hsk_sample_blend(f, sc.a, sc.b, sc.c);  // (unconditionally: a select, not a branch)
+  return sc.in ? res : HSK_NANF;
 }
 
 // floor(p / cell) of the spec without the IEEE division in the common case: q = p * (1/cell) differs from the

@@ -316,6 +316,33 @@ def test_extract_cloud_attrs_bitexact(hsk, tmp_path):
     plain.close()
 
 
+def test_extract_cloud_attrs_normals_with_three_different_cells(hsk):
+    """the alignment tests' scene, 80 x 64 x 48 over 3 m -- a cell per axis, a row pitch that is not the plane pitch: the normals
+    against mesh_twin.normal_at bit for bit, with samples whose lower tap is the last voxel of a 64-B block in x and in z"""
+    import align_twin as AT
+    import fuse_twin as FT
+    import mesh_twin as MT
+    X, Y, Z = AT.DST_DIMS
+    vol = AT.scene_volume(AT.DST_DIMS, AT.DST_SIZE, tau_of(AT.DST_SIZE, AT.DST_DIMS, 0.03))
+    trk = hsk.KinfuTracker(hsk.default_config(Z, vol_x=X, vol_y=Y, vol_z=Z, vol_size_m=AT.DST_SIZE, own_z1=Z))
+    trk.upload_tsdf(vol)
+    xyz, nrm, _, total, _ = trk.extract_cloud_attrs(rgb=False)
+    trk.close()
+    G = _Grid(vol, AT.DST_SIZE, Z, 0)
+    with np.errstate(all="ignore"):
+        want = MT.normal_at(G, xyz, AT.DST_DIMS)
+    deep = ~np.isnan(want[:, 0])
+    assert total == len(xyz) > 5000 and deep.sum() > 0.8 * total
+    assert MT.same_normals(nrm, want)
+    # the lower taps of the samples one cell either side in x and in z, by the fusion twin's arithmetic
+    for axis in (0, 2):
+        p = [xyz[deep, i].copy() for i in range(3)]
+        p[axis] = (p[axis] + G.cell[axis]).astype(f32)
+        vox = FT.sample(vol, AT.DST_SIZE, p)[3][axis]
+        low = vox - (p[axis] < ((vox.astype(f32) + f32(0.5)) * G.cell[axis]).astype(f32))
+        assert ((low & 3) == 3).sum() > 200, axis
+
+
 def test_room_scan_physical(hsk):
     """room 0 as a sensor sees it (holes, noise), synthetic colour, 256^3: the colours of the cloud against the colour of the
     scene at the point, the normals against the walls'.  Wall points near another wall (within 3 cells: corners and edges,
