@@ -111,6 +111,49 @@ class HskAlignStats(C.Structure):
     ]
 
 
+HSK_LOSS_RESET, HSK_LOSS_HOLD = 0, 1
+HSK_RELOC_FOUND, HSK_RELOC_NONE, HSK_RELOC_EMPTY = 0, 1, 2
+HSK_RELOC_STATUS = ("found", "none", "empty")
+HSK_RELOC_FINEST = -1
+HSK_RELOC_MAX_REFINE = 16
+
+
+class HskPoseScore(C.Structure):
+    """Mirror of `hsk_pose_score` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [
+        ("n_near", C.c_uint32), ("n_free", C.c_uint32), ("n_behind", C.c_uint32), ("n_unseen", C.c_uint32),
+        ("n_outside", C.c_uint32), ("n_skipped", C.c_uint32),
+        ("sum_abs", C.c_uint64),
+    ]
+
+
+class HskRelocParams(C.Structure):
+    """Mirror of `hsk_reloc_params` (include/hskinfu.h); a 0 in a field means its default."""
+
+    _fields_ = [
+        ("level", C.c_int), ("n_refine", C.c_int),
+        ("accept_fraction", C.c_float), ("accept_rms_m", C.c_float),
+        ("align", HskAlignParams),
+    ]
+
+
+class HskRelocStats(C.Structure):
+    """Mirror of `hsk_reloc_stats` (include/hskinfu.h)."""
+
+    _fields_ = [
+        ("status", C.c_int),
+        ("n_valid", C.c_uint32), ("n_candidates", C.c_uint32),
+        ("best", C.c_int32), ("n_refined", C.c_int32),
+        ("candidate", C.c_int32 * HSK_RELOC_MAX_REFINE),
+        ("score", HskPoseScore * HSK_RELOC_MAX_REFINE),
+        ("align_status", C.c_int32 * HSK_RELOC_MAX_REFINE),
+        ("iterations", C.c_int32 * HSK_RELOC_MAX_REFINE),
+        ("n_used", C.c_uint32 * HSK_RELOC_MAX_REFINE),
+        ("rms_m", C.c_float * HSK_RELOC_MAX_REFINE),
+    ]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -199,6 +242,13 @@ SYMBOLS = {
     "hsk_align_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _F, C.POINTER(HskAlignParams), _F, C.POINTER(HskAlignStats)]),
     "hsk_align_volume": (C.c_int, [_P, _P, _F, C.POINTER(HskAlignParams), _F, C.POINTER(HskAlignStats)]),
     "hsk_align_step": (C.c_int, [_D, _F, _F, _F, _F, _I]),
+    "hsk_set_loss_policy": (C.c_int, [_P, C.c_int]),
+    "hsk_get_loss_policy": (C.c_int, [_P]),
+    "hsk_score_cloud": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskPoseScore)]),
+    "hsk_rank_scores": (C.c_int, [C.POINTER(HskPoseScore), C.c_size_t, C.POINTER(C.c_uint32)]),
+    "hsk_default_reloc_params": (None, [_P, C.POINTER(HskRelocParams)]),
+    "hsk_relocalize": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(HskRelocParams), _F, C.POINTER(HskRelocStats)]),
+    "hsk_pose_lattice": (C.c_int, [_F, C.c_float, C.c_int, C.c_float, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

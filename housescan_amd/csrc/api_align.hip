@@ -77,8 +77,8 @@ extern "C" int hsk_align_step(const double sums27[27], const float m[16], const 
 
 static double max_abs3(const float* v) { return std::fmax(std::fmax(std::fabs((double)v[0]), std::fabs((double)v[1])), std::fabs((double)v[2])); }
 
-// the state and the arguments both calls ask of their destination
-static int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params* params, hsk_align_params* p, const char* who) {
+// the state and the arguments every call ask of its destination
+int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params* params, hsk_align_params* p, const char* who) {
   const std::string w(who);
   float inv[16];
   if (hsk_invert_rigid(src_to_dst, inv) != HSK_OK)
@@ -93,25 +93,13 @@ static int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align
   return require_idle(dst);
 }
 
-extern "C" int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* normals, size_t n, const float src_to_dst[16],
-                               const hsk_align_params* params, float out[16], hsk_align_stats* stats) {
-  if (!dst) return HSK_ERR_ARG;
-  if (!src_to_dst || !out || (n > 0 && (!xyz || !normals))) return fail(dst, HSK_ERR_ARG, "hsk_align_cloud: null argument");
-  hsk_align_params p;
-  if (int rc = align_check(dst, src_to_dst, params, &p, "hsk_align_cloud")) return rc;
-  hsk_ctx* k = dst;
-  HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  hsk_align_stats st;
-  memset(&st, 0, sizeof(st));
-  const size_t stride = n == 0 ? 1 : (n + p.max_points - 1) / p.max_points;
-  const size_t np = n == 0 ? 0 : (n + stride - 1) / stride;  // the points 0, stride, 2 stride, ..
-  if (stride > 0xffffffffull) return fail(k, HSK_ERR_ARG, "hsk_align_cloud: more points than a 32-bit stride over max_points covers");
-  st.stride = (uint32_t)stride;
-  st.n_points = (uint32_t)np;
-  // the scratch: the accumulators, then the cloud's six planes
+// The scratch of a cloud of np points (hsk_ctx.h: d_align, made on first use and only grown): the accumulators, the cloud's six
+// planes `*pitch` floats apart, then `extra` bytes for the caller (256-byte aligned).
+int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra) {
   const size_t acc_bytes = (size_t)HSK_ALIGN_ACC_WORDS * 8;
-  const unsigned pitch = (unsigned)((np + 63) & ~(size_t)63);
-  const size_t want = acc_bytes + (size_t)pitch * 6 * 4;
+  *pitch = (unsigned)((np + 63) & ~(size_t)63);
+  const size_t planes = (((size_t)*pitch * 6 * 4) + 255) & ~(size_t)255;
+  const size_t want = acc_bytes + planes + extra;
   if (!k->h_align) HIPCHK(k, hipHostMalloc((void**)&k->h_align, acc_bytes, hipHostMallocDefault));
   if (k->align_bytes < want) {
     if (k->d_align) HIPCHK(k, hipFree(k->d_align));
@@ -120,31 +108,23 @@ extern "C" int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* norm
     HIPCHK(k, hipMalloc(&k->d_align, want));
     k->align_bytes = want;
   }
-  unsigned long long* d_acc = (unsigned long long*)k->d_align;
-  float* d_soa = (float*)((char*)k->d_align + acc_bytes);
-  if (np > 0) {
-    std::vector<float> soa;
-    try {
-      soa.resize((size_t)pitch * 6);
-    } catch (const std::bad_alloc&) {
-      return fail(k, HSK_ERR_STATE, "hsk_align_cloud: out of host memory for the cloud");
-    }
-    for (size_t i = 0; i < np; ++i) {
-      const float* q = xyz + 3 * i * stride;
-      const float* m = normals + 3 * i * stride;
-      for (int c = 0; c < 3; ++c) {
-        soa[(size_t)c * pitch + i] = q[c];
-        soa[(size_t)(3 + c) * pitch + i] = m[c];
-      }
-    }
-    HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
-  }
+  *d_soa = (float*)((char*)k->d_align + acc_bytes);
+  if (d_extra) *d_extra = (char*)k->d_align + acc_bytes + planes;
+  return HSK_OK;
+}
+
+// The iterations over a cloud that lies in the scratch: from src_to_dst to m, st's iteration fields filled (n_points and stride
+// are the caller's).  p: resolved parameters.
+int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t np, unsigned pitch, const float src_to_dst[16], float m_out[16],
+              hsk_align_stats* stp) {
+  const size_t acc_bytes = (size_t)HSK_ALIGN_ACC_WORDS * 8;
   flush_weights(k);  // the rule reads weights
   HIPCHK(k, hipGetLastError());
   const float centre[3] = {k->vp.size[0] * 0.5f, k->vp.size[1] * 0.5f, k->vp.size[2] * 0.5f};
   float m[16];
   memcpy(m, src_to_dst, sizeof(m));
+  hsk_align_stats& st = *stp;
+  unsigned long long* d_acc = (unsigned long long*)k->d_align;
   double rot_sum = 0.0, shift_sum = 0.0;
   st.status = HSK_ALIGN_MAX_ITERS;
   for (int it = 0; it < p.max_iters; ++it) {
@@ -191,6 +171,48 @@ extern "C" int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* norm
       break;
     }
   }
+  memcpy(m_out, m, sizeof(m));
+  return HSK_OK;
+}
+
+extern "C" int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* normals, size_t n, const float src_to_dst[16],
+                               const hsk_align_params* params, float out[16], hsk_align_stats* stats) {
+  if (!dst) return HSK_ERR_ARG;
+  if (!src_to_dst || !out || (n > 0 && (!xyz || !normals))) return fail(dst, HSK_ERR_ARG, "hsk_align_cloud: null argument");
+  hsk_align_params p;
+  if (int rc = align_check(dst, src_to_dst, params, &p, "hsk_align_cloud")) return rc;
+  hsk_ctx* k = dst;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  hsk_align_stats st;
+  memset(&st, 0, sizeof(st));
+  const size_t stride = n == 0 ? 1 : (n + p.max_points - 1) / p.max_points;
+  const size_t np = n == 0 ? 0 : (n + stride - 1) / stride;  // the points 0, stride, 2 stride, ..
+  if (stride > 0xffffffffull) return fail(k, HSK_ERR_ARG, "hsk_align_cloud: more points than a 32-bit stride over max_points covers");
+  st.stride = (uint32_t)stride;
+  st.n_points = (uint32_t)np;
+  unsigned pitch = 0;
+  float* d_soa = nullptr;
+  if (int rc = align_scratch(k, np, 0, &pitch, &d_soa, nullptr)) return rc;
+  if (np > 0) {
+    std::vector<float> soa;
+    try {
+      soa.resize((size_t)pitch * 6);
+    } catch (const std::bad_alloc&) {
+      return fail(k, HSK_ERR_STATE, "hsk_align_cloud: out of host memory for the cloud");
+    }
+    for (size_t i = 0; i < np; ++i) {
+      const float* q = xyz + 3 * i * stride;
+      const float* m = normals + 3 * i * stride;
+      for (int c = 0; c < 3; ++c) {
+        soa[(size_t)c * pitch + i] = q[c];
+        soa[(size_t)(3 + c) * pitch + i] = m[c];
+      }
+    }
+    HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
+  }
+  float m[16];
+  if (int rc = align_run(k, p, d_soa, np, pitch, src_to_dst, m, &st)) return rc;
   memcpy(out, m, sizeof(m));
   if (stats) *stats = st;
   return HSK_OK;

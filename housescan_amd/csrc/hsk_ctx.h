@@ -91,6 +91,7 @@ struct hsk_ctx {
   int ring_kind[HSK_MAX_IN_FLIGHT + 1] = {};  // 0 tracked-frame candidate, 1 first frame (already complete)
   int ring_head = 0, ring_count = 0;
   bool pending_reset = false;
+  int loss_policy = HSK_LOSS_RESET;  // what a lost frame does to the scan (hsk_set_loss_policy; hskinfu_api.hip: after_loss)
   // overlapped preprocessing: stream, per-set events (preprocess done / set free again), per-set graphs of the rest
   hipStream_t pstream = nullptr;
   hipEvent_t ev_pre[2] = {}, ev_free[2] = {};
@@ -151,7 +152,8 @@ struct hsk_ctx {
   // size / offset tables and the scan's block sums (pack.hip); what the tables hold is the class and offset pass of the
   // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
   // volume alignment (hsk_align_cloud), made on first use as a destination and only grown: the accumulators (align.hip:
-  // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes; h_align: the accumulators' pinned host side
+  // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what pose scoring adds (api_reloc.hip: the poses, the slabs'
+  // partial values, the scores); h_align: the accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;
   unsigned long long* h_align = nullptr;
@@ -183,6 +185,7 @@ int download_state(hsk_ctx* k);
 void leave_slab_bookkeeping(hsk_ctx* k);
 int set_pose_internal(hsk_ctx* k, const float pose[16]);
 void enqueue_raycast_and_resize(hsk_ctx* k, int* keys, bool report = false);
+int preprocess_frame(hsk_ctx* k, const uint16_t* depth, int w, int h);  // hsk_preprocess behind its argument checks
 void hsk_mark_group_slab(hsk_ctx* k);  // hsk_group_create* marks the contexts it makes as slabs, whatever planes they own
 // the state a call needs, or its refusal (HSK_ERR_STATE): no frame in flight; colour enabled; a context that stores its whole
 // volume ("<who>: not for a slab (<sentence>)").  `errs` takes the message: hsk_fuse_volume asks of its source, too, and reports
@@ -191,6 +194,11 @@ int require_idle(const hsk_ctx* k, hsk_ctx* errs);
 inline int require_idle(hsk_ctx* k) { return require_idle(k, k); }
 int require_color(hsk_ctx* k);
 int require_whole_volume(const hsk_ctx* k, hsk_ctx* errs, const char* who, const char* sentence = "a context that stores part of its volume");
+// ---- api_align.hip ----
+int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params* params, hsk_align_params* p, const char* who);
+int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra);
+int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t np, unsigned pitch, const float src_to_dst[16], float m_out[16],
+              hsk_align_stats* st);
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

@@ -104,6 +104,19 @@ struct AlignPose {
 void launch_align_iter(hipStream_t s, const void* dst_vol, const VolParams& dv, const float* soa, unsigned n, unsigned pitch,
                        const AlignPose& m, int probes, float cos_gate, unsigned long long* acc);
 
+// pose scoring (reloc.hip): the n points of the planes x, y, z at `soa` (`pitch` floats apart) under each of
+// n_poses poses (12 floats each: R row-major, then t).  partial: n_poses x reloc_slabs(n, n_poses) x 8 64-bit words of scratch;
+// scores: n_poses records, written whole (nothing needs zeroing).  Nothing is launched with n == 0 or n_poses == 0.
+#define HSK_RELOC_MAX_SLABS 32
+struct hsk_pose_score;
+unsigned reloc_slabs(unsigned n, unsigned n_poses);
+void launch_reloc_score(hipStream_t s, const void* dst_vol, const VolParams& dv, const float* soa, unsigned n, unsigned pitch,
+                        const float* poses12, unsigned n_poses, unsigned long long* partial, hsk_pose_score* scores);
+// every stride-th of the P pixels of a vertex map and its normal map (three planes each), np = ceil(P / stride) of them, as
+// the alignment's six planes; a normal that faces away from the camera is negated
+void launch_reloc_gather(hipStream_t s, const float* vmap, const float* nmap, unsigned P, unsigned stride, unsigned np, unsigned pitch,
+                         float* soa);
+
 // sparse volume image (pack.hip): bricks of 8^3 voxels, pack_bricks of them, a class byte and a record size
 // (in 4-byte words) each.  launch_pack_scan turns the sizes into offsets in place (an exclusive scan; bsum: pack_scan_blocks
 // words of scratch) and leaves in counts[0..3] the bricks per class, in counts[4] the payload's length in words (8 words).

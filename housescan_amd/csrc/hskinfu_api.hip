@@ -215,6 +215,34 @@ static int do_reset(hsk_ctx* k) {
   return upload_state(k);
 }
 
+// A frame lost tracking: the one place that says what becomes of the scan.  HSK_LOSS_RESET restarts it (do_reset).
+// HSK_LOSS_HOLD keeps everything and puts the tracker back where the last tracked frame left it: every frame path starts a
+// frame with previous pose <- pose (k_icp_iter's first iteration, k_begin_frame) and a dropped frame leaves the state alone, so
+// (Rp, tp) is the last tracked pose whatever the path left in (R, t); the sticky flags are cleared as hsk_resume_scan clears
+// them.  The volume, the colour, the summaries, the brick flags, the model maps and the frame count are not touched.
+static int after_loss(hsk_ctx* k) {
+  if (k->loss_policy != HSK_LOSS_HOLD) return do_reset(k);
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  int r = download_state(k);
+  if (r != HSK_OK) return r;
+  memcpy(k->h_st->R, k->h_st->Rp, sizeof(k->h_st->R));
+  memcpy(k->h_st->t, k->h_st->tp, sizeof(k->h_st->t));
+  k->h_st->lost = 0;
+  k->h_st->need_reset = 0;
+  k->pending_reset = false;
+  return upload_state(k);
+}
+
+extern "C" int hsk_set_loss_policy(hsk_ctx* k, int policy) {
+  if (!k) return HSK_ERR_ARG;
+  if (policy != HSK_LOSS_RESET && policy != HSK_LOSS_HOLD) return fail(k, HSK_ERR_ARG, "hsk_set_loss_policy: unknown policy");
+  if (k->group_slab) return fail(k, HSK_ERR_STATE, "hsk_set_loss_policy: not for a slab (a group handles a loss itself)");
+  if (int ri = require_idle(k)) return ri;
+  k->loss_policy = policy;
+  return HSK_OK;
+}
+extern "C" int hsk_get_loss_policy(const hsk_ctx* k) { return k ? k->loss_policy : -1; }
+
 extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
   if (!c || !out) {
     create_error() = "hsk_create: null argument";
@@ -389,7 +417,7 @@ extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
 }
 
 static int wait_slot(hsk_ctx* k, int slot, bool pose_only = false);
-static int reset_behind_lost_frame(hsk_ctx* k);
+static int reset_behind_lost_frame(hsk_ctx* k, bool lost = false);
 extern "C" int hsk_wait_frame(hsk_ctx* k, float pose_out[16], int* tracked);
 
 extern "C" void hsk_destroy(hsk_ctx* k) {
@@ -533,10 +561,11 @@ static int hand_back(const hsk_ctx* k, float pose_out[16], int* tracked, int ver
   if (tracked) *tracked = verdict;
   return HSK_OK;
 }
-// ... at the end of a tracked one: lost, and the scan restarts (the reset's pose goes back); else the frame counts
+// ... at the end of a tracked one: lost, and the scan restarts (the reset's pose goes back) or is held (the last tracked pose
+// goes back); else the frame counts
 static int end_tracked_frame(hsk_ctx* k, float pose_out[16], int* tracked) {
   if (k->h_st->lost) {
-    const int r = do_reset(k);
+    const int r = after_loss(k);
     return r != HSK_OK ? r : hand_back(k, pose_out, tracked, 0);
   }
   k->frame += 1;
@@ -724,15 +753,15 @@ static int wait_slot(hsk_ctx* k, int slot, bool pose_only) {
 }
 
 // Tracking was lost with frames still in flight: their results stay in the ring (they report tracked = 0), the reset
-// itself happens here, before new work is enqueued.
-static int reset_behind_lost_frame(hsk_ctx* k) {
+// itself happens here, before new work is enqueued.  lost: because of a loss (the policy decides); else hsk_reset's.
+static int reset_behind_lost_frame(hsk_ctx* k, bool lost) {
   for (int i = 0; i < k->ring_count; ++i) {
     const int sl = (k->ring_head + i) % (HSK_MAX_IN_FLIGHT + 1);
     const int r = wait_slot(k, sl);
     if (r != HSK_OK) return r;
     if (k->ring_kind[sl] == 0) k->ring_kind[sl] = 2;  // dropped on the device (need_reset was set)
   }
-  return do_reset(k);
+  return lost ? after_loss(k) : do_reset(k);
 }
 
 extern "C" int hsk_submit_frame_dev(hsk_ctx* k, const void* depth_dev, int w, int h) {
@@ -762,13 +791,13 @@ static int submit_frame(hsk_ctx* k, const void* depth_dev, hipMemcpyKind kind, i
   if (k->ring_count >= HSK_MAX_IN_FLIGHT) return fail(k, HSK_ERR_STATE, "too many frames in flight: call hsk_wait_frame first");
   if (k->ring_count == 0) leave_slab_bookkeeping(k);
   hipStream_t s = k->stream;
-  const bool sync_path = k->frame == 0 || k->pending_reset || k->cfg.integrate_move_thresh > 0.0f || k->prof;
+  if (k->pending_reset) {  // (a restarted scan then takes the synchronous path with its first frame; a held one goes on pipelined)
+    r = reset_behind_lost_frame(k, true);
+    if (r != HSK_OK) return r;
+  }
+  const bool sync_path = k->frame == 0 || k->cfg.integrate_move_thresh > 0.0f || k->prof;
   if (sync_path) {
     // first frame of a (re)started scan, gated or profiled mode: run it synchronously and park the result
-    if (k->pending_reset) {
-      r = reset_behind_lost_frame(k);
-      if (r != HSK_OK) return r;
-    }
     HIPCHK(k, hipMemcpyAsync(k->B().d_raw, depth_dev, (size_t)w * h * 2, kind, s));
     HIPCHK(k, stage_color(k, k->cur, s));
     float pose[16];
@@ -882,18 +911,21 @@ extern "C" int hsk_wait_frame(hsk_ctx* k, float pose_out[16], int* tracked) {
     if (tracked) *tracked = st.lost ? 0 : 1;
     return HSK_OK;
   }
-  if (k->ring_kind[slot] == 2) {  // was in flight behind a lost frame; the reset has already happened
+  // a lost or dropped frame reports the restarted scan's pose, or under HSK_LOSS_HOLD the last tracked pose: the previous pose
+  // of its slot (a lost frame started with previous pose <- pose, a dropped one left the state alone)
+  const bool hold = k->loss_policy == HSK_LOSS_HOLD;
+  if (k->ring_kind[slot] == 2) {  // was in flight behind a lost frame; the reset (or the hold) has already happened
     if (tracked) *tracked = 0;
-    if (pose_out) rt_to_pose16(k->init_R, k->init_t, pose_out);
+    if (pose_out) rt_to_pose16(hold ? st.Rp : k->init_R, hold ? st.tp : k->init_t, pose_out);
     return HSK_OK;
   }
   if (st.lost) {
     // the volume is reset lazily: at the next submission, or now if nothing else is in flight
     k->pending_reset = true;
     if (tracked) *tracked = 0;
-    if (pose_out) rt_to_pose16(k->init_R, k->init_t, pose_out);
+    if (pose_out) rt_to_pose16(hold ? st.Rp : k->init_R, hold ? st.tp : k->init_t, pose_out);
     if (k->ring_count == 0) {
-      int r = do_reset(k);
+      int r = after_loss(k);
       if (r != HSK_OK) return r;
     }
     return HSK_OK;
@@ -936,7 +968,7 @@ extern "C" int hsk_track_stream(hsk_ctx* k, hsk_depth_stream* s, int first, int 
   auto after_collect = [&](bool lost) -> int {
     if (!lost) return HSK_OK;
     if (k->ring_count > 0) {  // the frames behind the lost one: dropped on the device; the reset, then their results discarded
-      const int rr = reset_behind_lost_frame(k);
+      const int rr = reset_behind_lost_frame(k, true);
       if (rr != HSK_OK) return rr;
     }
     while (k->ring_count > 0) {
@@ -1054,8 +1086,13 @@ extern "C" int hsk_raycast(hsk_ctx* k, const float pose[16], float* vmap, float*
 extern "C" int hsk_preprocess(hsk_ctx* k, const uint16_t* depth, int w, int h) {
   int r = check_dims(k, depth, w, h);
   if (r != HSK_OK) return r;
+  return preprocess_frame(k, depth, w, h);
+}
+int preprocess_frame(hsk_ctx* k, const uint16_t* depth, int w, int h) {
+  (void)w;
+  (void)h;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  r = stage_depth_host(k, depth);
+  int r = stage_depth_host(k, depth);
   if (r != HSK_OK) return r;
   enqueue_preprocess(k, k->stream);
   HIPCHK(k, hipStreamSynchronize(k->stream));

@@ -60,6 +60,35 @@ def _image_arrays(w, h, rgb, depth, vmap, nmap):
     return out, lambda k: out[k].ctypes.data if k in out else None
 
 
+SCORE_DTYPE = np.dtype([("n_near", "<u4"), ("n_free", "<u4"), ("n_behind", "<u4"), ("n_unseen", "<u4"), ("n_outside", "<u4"),
+                        ("n_skipped", "<u4"), ("sum_abs", "<u8")])     # hsk_pose_score
+
+
+def pose_lattice(centre, step_m, n_trans, step_rad, n_rot):
+    """candidate poses around `centre` [4, 4]: centre . T(i, j, k) step_m . Ry(a step_rad) . Rx(b step_rad) for i, j, k in
+    [-n_trans, n_trans] and a, b in [-n_rot, n_rot], offsets in the camera's own frame (hsk_pose_lattice; host only)
+    -> [n, 4, 4] float32, i slowest, b fastest"""
+    lib = _lib.load()
+    c = np.ascontiguousarray(centre, np.float32).reshape(16)
+    n = C.c_size_t()
+    if lib.hsk_pose_lattice(_fp(c), step_m, int(n_trans), step_rad, int(n_rot), None, 0, C.byref(n)) != 0:
+        raise KinfuError("pose_lattice: invalid arguments (negative counts, non-finite steps or more than 65536 poses)")
+    out = np.empty((n.value, 16), np.float32)
+    if lib.hsk_pose_lattice(_fp(c), step_m, int(n_trans), step_rad, int(n_rot), out.ctypes.data, n.value, C.byref(n)) != 0:
+        raise KinfuError("pose_lattice failed")
+    return out.reshape(-1, 4, 4)
+
+
+def rank_scores(scores):
+    """the order of a score_cloud result: key = n_near - n_free - n_behind, larger first; ties to the smaller sum_abs, then to
+    the lower index (hsk_rank_scores; host only) -> indices [n] uint32"""
+    s = np.ascontiguousarray(scores, SCORE_DTYPE)
+    order = np.empty(len(s), np.uint32)
+    if len(s) and _lib.load().hsk_rank_scores(s.ctypes.data_as(C.POINTER(_lib.HskPoseScore)), len(s), order.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise KinfuError("rank_scores failed")
+    return order
+
+
 class KinfuTracker:
     """One TSDF volume + tracker on one MI355X (one `hsk_ctx`)."""
 
@@ -485,6 +514,64 @@ class KinfuTracker:
         p = self._align_params(probes, params)
         self._ck(self.lib.hsk_align_volume(self.h, None if src is None else src.h, _fp(m), C.byref(p), _fp(out), C.byref(st)))
         return self._align_result(out, st)
+
+    # ---- loss hold and relocalisation -----------------------------------------------------------------
+    def set_loss_policy(self, policy):
+        """what a frame that loses tracking does to the scan: "reset" (the default: the volume is wiped) or "hold" (the frame
+        is dropped, the volume and the last tracked pose stay); also the C values (hsk_set_loss_policy)"""
+        self._ck(self.lib.hsk_set_loss_policy(self.h, {"reset": _lib.HSK_LOSS_RESET, "hold": _lib.HSK_LOSS_HOLD}.get(policy, policy)))
+
+    def get_loss_policy(self):
+        return ("reset", "hold")[self.lib.hsk_get_loss_policy(self.h)]
+
+    @staticmethod
+    def _poses(poses):
+        p = np.ascontiguousarray(poses, np.float32)
+        if p.size % 16:
+            raise ValueError("poses must be [n, 4, 4] (or [n, 16]) matrices")
+        return p.reshape(-1, 16)
+
+    @staticmethod
+    def _score_dict(s):
+        return {"n_near": int(s.n_near), "n_free": int(s.n_free), "n_behind": int(s.n_behind), "n_unseen": int(s.n_unseen),
+                "n_outside": int(s.n_outside), "n_skipped": int(s.n_skipped), "sum_abs": int(s.sum_abs)}
+
+    def score_cloud(self, xyz, poses):
+        """how the points xyz [n, 3] (camera coordinates) lie in this volume under each of the poses [m, 4, 4]
+        (hsk_score_cloud) -> a structured array [m] with the fields n_near, n_free, n_behind, n_unseen, n_outside,
+        n_skipped (uint32) and sum_abs (uint64); rank it with rank_scores"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        ps = self._poses(poses)
+        out = np.zeros(len(ps), SCORE_DTYPE)
+        self._ck(self.lib.hsk_score_cloud(self.h, pts.ctypes.data if len(pts) else None, len(pts), ps.ctypes.data if len(ps) else None, len(ps),
+                                          out.ctypes.data_as(C.POINTER(_lib.HskPoseScore)) if len(ps) else None))
+        return out
+
+    def default_reloc_params(self):
+        p = _lib.HskRelocParams()
+        self.lib.hsk_default_reloc_params(self.h, C.byref(p))
+        return p
+
+    def relocalize(self, depth, poses, level=None, n_refine=0, accept_fraction=0.0, accept_rms_m=0.0, probes=None, **align):
+        """find the camera pose of one depth frame in this volume among the candidate poses [m, 4, 4] (hsk_relocalize): they are
+        scored, the best n_refine refined by the volume alignment, the best accepted refinement wins.  level: 1, 2 (the
+        default) or 0 for the finest; probes and the other keywords are align_cloud's.  Overwrites the image buffers, nothing
+        else; hand the pose to resume_scan.  -> (pose [4, 4] float32, dict(status: "found" | "none" | "empty", n_valid,
+        n_candidates, best, candidates: one dict per refined candidate, by rank))"""
+        d = self._depth(depth)
+        ps = self._poses(poses)
+        p = _lib.HskRelocParams()
+        p.level = 0 if level is None else (_lib.HSK_RELOC_FINEST if int(level) == 0 else int(level))
+        p.n_refine, p.accept_fraction, p.accept_rms_m = int(n_refine), accept_fraction, accept_rms_m
+        p.align = self._align_params(probes, align)
+        out, st = np.zeros(16, np.float32), _lib.HskRelocStats()
+        self._ck(self.lib.hsk_relocalize(self.h, d.ctypes.data, d.shape[1], d.shape[0], ps.ctypes.data if len(ps) else None, len(ps),
+                                         C.byref(p), _fp(out), C.byref(st)))
+        cands = [dict(index=int(st.candidate[r]), score=self._score_dict(st.score[r]), align_status=_lib.HSK_ALIGN_STATUS[st.align_status[r]],
+                      iterations=int(st.iterations[r]), n_used=int(st.n_used[r]), rms_m=np.float32(st.rms_m[r]))
+                 for r in range(max(0, min(int(st.n_refined), _lib.HSK_RELOC_MAX_REFINE)))]
+        return out.reshape(4, 4), {"status": _lib.HSK_RELOC_STATUS[st.status], "n_valid": int(st.n_valid), "n_candidates": int(st.n_candidates),
+                                   "best": int(st.best), "candidates": cands}
 
     # ---- volume files -----------------------------------------------------------------------------------
     def pack_volume(self, with_info=False):

@@ -455,6 +455,94 @@ int hsk_align_volume(hsk_ctx* dst, hsk_ctx* src, const float src_to_dst[16], con
  * pose update is applied to (R, t - centre) and centre added back.  A singular system: *ok = 0, x6 zeros, m_next = m. */
 int hsk_align_step(const double sums27[27], const float m[16], const float centre[3], float m_next[16], float x6[6], int* ok);
 
+/* ---- Loss hold and relocalisation: keep the volume when tracking is lost, and find a frame's pose in it (DESIGN.md 3.13 the
+ * kernel, 8g the rule).  The host loop: hsk_set_loss_policy(k, HSK_LOSS_HOLD) once; a frame reports
+ * tracked = 0 and the volume stays; hsk_pose_lattice around the last pose -> hsk_relocalize with the next frame ->
+ * hsk_resume_scan(k, pose_out) -> frames are tracked again.  The search is LOCAL: the host supplies the candidate poses; a
+ * whole-room search is a host loop over lattices, not a promise (views of a bare wall are ambiguous in a box). */
+#define HSK_LOSS_RESET 0 /* a lost frame restarts the scan: the volume is wiped, the pose is the initial pose (the default) */
+#define HSK_LOSS_HOLD 1  /* a lost frame is dropped: nothing but its verdict changes                                       */
+/* Under HSK_LOSS_HOLD a frame that loses tracking reports tracked = 0 and the pose of the last tracked frame; the volume, the
+ * colour volume, the model maps and the frame count stay as they were; frames in flight behind it are dropped on the device (as
+ * under RESET) and report tracked = 0 and that same pose; the next frame submitted is tracked by ICP from the last tracked pose
+ * against the unchanged model maps.  hsk_reset still resets; hsk_track_stream stays frame for frame what hsk_process_frame
+ * gives under the same policy.  HSK_ERR_ARG: a NULL context, an unknown policy; HSK_ERR_STATE: a frame in flight, a slab of a
+ * group (a group handles a loss itself). */
+int hsk_set_loss_policy(hsk_ctx* k, int policy);
+int hsk_get_loss_policy(const hsk_ctx* k); /* -1 for NULL */
+
+/* How a cloud lies in the volume under one pose.  Every point falls in exactly one of the six counts. */
+typedef struct hsk_pose_score {
+  uint32_t n_near;    /* |F| < 1 at the moved point: on a surface the volume holds                                  */
+  uint32_t n_free;    /* F >= 1: a measured point in space the volume saw empty                                     */
+  uint32_t n_behind;  /* F <= -1                                                                                    */
+  uint32_t n_unseen;  /* one of the sample's eight voxels was never observed                                        */
+  uint32_t n_outside; /* outside the volume, or in its outer shell of voxels                                        */
+  uint32_t n_skipped; /* a NaN coordinate (an invalid pixel of a vertex map)                                        */
+  uint64_t sum_abs;   /* over the near points: rint(|F| * 65536), added as integers                                 */
+} hsk_pose_score;     /* 32 bytes */
+/* n points xyz (3 floats each, camera coordinates) under each of n_poses poses (16 floats each, row-major, p_dst = M p):
+ * out[j] is pose j's score.  The moved point is sampled once with the raycast's trilinear sample; no normals, no gradient.
+ * Synchronous.  The cloud goes up once, into the scratch buffer of hsk_align_cloud (only grown: a later call of the same size
+ * allocates nothing); dst's deferred free-space weights are written back first, nothing else of dst is written.
+ * n <= 2^20, n_poses <= 65536; n = 0 or n_poses = 0: HSK_OK (the scores are zeros).  HSK_ERR_ARG (out untouched): a NULL
+ * context, xyz (n > 0), poses or out (n_poses > 0); a count above its limit; a pose hsk_invert_rigid refuses (the message names
+ * its index).  HSK_ERR_STATE: hsk_align_cloud's cases. */
+int hsk_score_cloud(hsk_ctx* dst, const float* xyz, size_t n, const float* poses, size_t n_poses, hsk_pose_score* out);
+/* host only: order[] = the indices 0..n-1 by key = n_near - n_free - n_behind (signed), larger first; ties to the smaller
+ * sum_abs, then to the lower index.  HSK_ERR_ARG: a NULL pointer with n > 0. */
+int hsk_rank_scores(const hsk_pose_score* s, size_t n, uint32_t* order);
+
+#define HSK_RELOC_FOUND 0
+#define HSK_RELOC_NONE 1      /* no refined candidate was accepted: pose_out is the best-scored candidate, unrefined; DO NOT TRUST it */
+#define HSK_RELOC_EMPTY 2     /* the frame's level has no valid pixel, or n_poses == 0: pose_out is the identity            */
+#define HSK_RELOC_FINEST (-1) /* `level`: level 0 (0 means the default)                                                   */
+#define HSK_RELOC_MAX_REFINE 16
+typedef struct {
+  int level;              /* pyramid level whose maps are scored and refined: 1, 2 or HSK_RELOC_FINEST   default 2       */
+  int n_refine;           /* best-ranked candidates refined, 1..16                                       default 4       */
+  float accept_fraction;  /* least n_used(last iteration) / n_valid, (0, 1]                              default 0.5     */
+  float accept_rms_m;     /* largest rms of the last iteration                                           default tau / 4 */
+  hsk_align_params align; /* zeros: hsk_align_cloud's defaults                                                           */
+} hsk_reloc_params;       /* a 0 in a field means its default                                                            */
+typedef struct {
+  int status;             /* HSK_RELOC_*                                                                                 */
+  uint32_t n_valid;       /* pixels of the level with a vertex                                                           */
+  uint32_t n_candidates;  /* n_poses                                                                                     */
+  int32_t best;           /* index (into poses) of the candidate the result was refined from; NONE: the best-scored; EMPTY: -1 */
+  int32_t n_refined;      /* entries of the arrays below: min(n_refine, n_poses)                                         */
+  int32_t candidate[HSK_RELOC_MAX_REFINE];     /* by rank: index into poses (-1 beyond n_refined)                        */
+  hsk_pose_score score[HSK_RELOC_MAX_REFINE];  /* ... its score                                                          */
+  int32_t align_status[HSK_RELOC_MAX_REFINE];  /* ... its refinement's HSK_ALIGN_* status                                */
+  int32_t iterations[HSK_RELOC_MAX_REFINE];
+  uint32_t n_used[HSK_RELOC_MAX_REFINE];       /* ... of its last iteration                                              */
+  float rms_m[HSK_RELOC_MAX_REFINE];
+} hsk_reloc_stats;
+/* the defaults as values (accept_rms_m and align.max_shift_m from k's truncation distance; 0 with k NULL) */
+void hsk_default_reloc_params(const hsk_ctx* k, hsk_reloc_params* p);
+/* Finds the camera pose of one depth frame among the candidates.  Defined by composition, bit for bit: the frame is
+ * preprocessed as by hsk_preprocess; the cloud is ALL pixels of the level's vertex map in row-major order (invalid pixels are
+ * NaN: skipped by the score, never a term of the alignment), the normals are the normal map's, each negated when n . v > 0;
+ * the candidates are scored (hsk_score_cloud) and ranked (hsk_rank_scores); each of the first n_refine is refined by
+ * hsk_align_cloud(k, cloud, normals, n, candidate, &params->align, ..); a refinement is ACCEPTED when its status is
+ * HSK_ALIGN_CONVERGED, n_used[last] >= accept_fraction * n_valid and rms_m[last] <= accept_rms_m; the winner is the accepted
+ * one with the largest n_used[last], then the smallest rms, then the earlier rank.  On the device the cloud never leaves it:
+ * the read-backs are the scores and 4 KiB per alignment iteration.
+ * It overwrites the image buffers of set 0 (as hsk_preprocess does) and nothing else: not the volume (the deferred weights
+ * are written back), the tracker pose, the model maps, the flags, the frame count or the cached count passes.  The host then
+ * calls hsk_resume_scan(k, pose_out) and, if it wants the frame in the volume, hsk_integrate(depth, pose_out).
+ * params NULL: the defaults; stats may be NULL.  Every HSK_RELOC_* status returns HSK_OK.  Errors: hsk_score_cloud's and
+ * hsk_align_cloud's; a frame size that is not the context's, a level or n_refine outside its range, accept_fraction outside
+ * (0, 1] or a negative or non-finite accept_rms_m: HSK_ERR_ARG. */
+int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, const float* poses, size_t n_poses,
+                   const hsk_reloc_params* params, float pose_out[16], hsk_reloc_stats* stats);
+/* host only: the candidate lattice pose = centre . T(i step_m, j step_m, k step_m) . Ry(a step_rad) . Rx(b step_rad) for
+ * i, j, k in [-n_trans, n_trans] and a, b in [-n_rot, n_rot] -- offsets in the camera's own frame -- computed in binary64 and
+ * rounded once; i slowest, then j, k, a, and b fastest; (2 n_trans + 1)^3 (2 n_rot + 1)^2 poses, of which the one with all
+ * offsets 0 is `centre` bit for bit.  Two calls: poses == NULL sets *n only.  HSK_ERR_ARG: a NULL centre or n, a negative
+ * count, a non-finite step, more than 65536 poses, cap below the count (with *n set). */
+int hsk_pose_lattice(const float centre[16], float step_m, int n_trans, float step_rad, int n_rot, float* poses, size_t cap, size_t* n);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
