@@ -99,6 +99,24 @@ __host__ __device__ static inline int hsk_flag_words(const VolParams& vp) {
   const long bits = (long)(vp.X >> vp.bshift) * (vp.Y >> vp.bshift) * ((vp.nzs + (1 << vp.bshift) - 1) >> vp.bshift);
   return (int)(((bits + 31) / 32 + 3) / 4 * 4);  // multiple of 4 words: staged into LDS with 16-B loads
 }
+// The brick edge of a volume (X, Y, nzs of vp): 8 voxels, doubled while the bitfield is longer than HSK_FLAG_WORDS_MAX and X
+// and Y stay multiples of the doubled edge.  Bitfield <= 4 KiB (bricks of ~94 mm at every cubic size): its LDS copy then
+// never limits how many raycast blocks a CU holds, and the march was measured insensitive to the brick size between 47
+// and 94 mm.  A volume whose X or Y is 8 mod 16 stays at 8 however large it is: hsk_create refuses it once its field no
+// longer fits the LDS of a block.
+__host__ static inline int hsk_choose_bshift(VolParams vp) {
+  vp.bshift = 3;
+  while (hsk_flag_words(vp) > HSK_FLAG_WORDS_MAX && vp.bshift < 6 && ((vp.X >> (vp.bshift + 1)) << (vp.bshift + 1)) == vp.X &&
+         ((vp.Y >> (vp.bshift + 1)) << (vp.bshift + 1)) == vp.Y)
+    ++vp.bshift;
+  return vp.bshift;
+}
+// The most dynamic LDS a march kernel is launched with (the staged field, hsk_flag_words_total words): no launch above it has
+// ever been run or measured, and no kernel is opted in to more.  hsk_create takes the smaller of this and what the runtime
+// reports for a block of the device.
+#ifndef HSK_MARCH_LDS_MAX
+#define HSK_MARCH_LDS_MAX (64 * 1024)
+#endif
 // Behind the brick bitfield: one bit per SUPER-brick of (2^HSK_SUPER_SHIFT)^3 bricks ("one of my bricks has held a negative TSDF"),
 // the raycast's licence to cross such a block without looking at its steps.  Always HSK_SUPER_WORDS words (a multiple
 // of 4: staged with the same 16-B loads); a volume with more super-bricks than bits does not use it (hsk_super_ok).

@@ -264,6 +264,33 @@ extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
     create_error() = "hsk_create: device_id out of range";
     return HSK_ERR_ARG;
   }
+  {
+    // The march kernels (raycast, views, sections) stage the whole brick bitfield in dynamic LDS.  What a block of this device may
+    // ask for is the runtime's figure, read here; none of the kernels is opted in to more than HSK_MARCH_LDS_MAX (hsk_dev.h), so
+    // the smaller of the two is the limit.  A volume whose X or Y stops the brick edge from growing (hsk_choose_bshift: 648^3
+    // stays at 8^3 bricks, 66560 B) would be created fine and its first raycast could not be relied on: refuse it here,
+    // before anything is allocated, with the remedy.
+    VolParams g{};
+    g.X = c->vol_x;
+    g.Y = c->vol_y;
+    const int zs0 = c->own_z0 - c->halo < 0 ? 0 : c->own_z0 - c->halo;
+    g.nzs = (c->own_z1 + c->halo > c->vol_z ? c->vol_z : c->own_z1 + c->halo) - zs0;
+    g.bshift = hsk_choose_bshift(g);
+    int lds_block = 0;
+    if (hipDeviceGetAttribute(&lds_block, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device_id) != hipSuccess || lds_block <= 0) {
+      (void)hipGetLastError();
+      create_error() = "hsk_create: the device does not report the shared memory of a block";
+      return HSK_ERR_HIP;
+    }
+    const size_t lds_max = (size_t)lds_block < (size_t)HSK_MARCH_LDS_MAX ? (size_t)lds_block : (size_t)HSK_MARCH_LDS_MAX;
+    const size_t staged = (size_t)hsk_flag_words_total(g) * 4;
+    if (staged > lds_max) {
+      create_error() = "hsk_create: the brick bitfield of this volume (" + std::to_string(staged) + " B) does not fit the " + std::to_string(lds_max) +
+                       " B of LDS the raycast may stage it in (the device gives a block " + std::to_string(lds_block) +
+                       " B): make vol_x and vol_y multiples of 16, or the next power of two";
+      return HSK_ERR_ARG;
+    }
+  }
   hsk_ctx* k = new hsk_ctx();
   k->cfg = *c;
   auto bail = [&](int code) {
@@ -375,25 +402,13 @@ extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
   CK(hipMalloc((void**)&k->d_sums, 27 * sizeof(double)));
   CK(hipMalloc((void**)&k->d_wc, 512 * 4));
   CK(hipMalloc((void**)&k->d_keys, P0 * 4));
-  vp.bshift = 3;
-  // bitfield <= 4 KiB (bricks of ~94 mm at every volume size): its LDS copy then never limits how many raycast blocks a
-  // CU holds, and the march was measured insensitive to the brick size between 47 and 94 mm
-  while (hsk_flag_words(vp) > HSK_FLAG_WORDS_MAX && vp.bshift < 6 && ((vp.X >> (vp.bshift + 1)) << (vp.bshift + 1)) == vp.X &&
-         ((vp.Y >> (vp.bshift + 1)) << (vp.bshift + 1)) == vp.Y)
-    ++vp.bshift;
+  vp.bshift = hsk_choose_bshift(vp);
   // integrate's queue entries are 28-bit lane-block ids (4 x-voxels x 4 planes) with 4 plane bits on top
   if ((size_t)((vp.nzs + 3) / 4) * vp.Y * (vp.X / 4) >= ((size_t)1 << 28)) {
     k->err = "hsk_create: volume too large for the 28-bit lane-block ids of integrate (more than 2^32 stored voxels)";
     return bail(HSK_ERR_ARG);
   }
-  k->flags_bytes = (size_t)hsk_flag_words_total(vp) * 4;  // brick bits + super-brick bits
-  // k_raycast stages the whole bitfield in dynamic LDS; a launch may ask for at most 64 KiB of it.  Volumes whose
-  // dimensions stop the brick edge from growing (e.g. 1000^3: 125 = 5^3 bricks of 8) would be created fine and then
-  // fail at the first raycast: refuse them here, with the reason.
-  if (k->flags_bytes > 64u * 1024u) {
-    k->err = "hsk_create: the brick bitfield of this volume does not fit the raycast's LDS (64 KiB): choose vol_x, vol_y divisible by a larger power of two";
-    return bail(HSK_ERR_ARG);
-  }
+  k->flags_bytes = (size_t)hsk_flag_words_total(vp) * 4;  // brick bits + super-brick bits (it fits a block's LDS: checked above)
   CK(hipMalloc((void**)&k->d_flags, k->flags_bytes));
   k->uni_bytes = uniform_bytes(vp);
   CK(hipMalloc((void**)&k->d_uni, k->uni_bytes));

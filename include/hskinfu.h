@@ -43,7 +43,13 @@ extern "C" {
 typedef struct hsk_ctx hsk_ctx; /* opaque; one per volume / room */
 
 typedef struct {
-  int vol_x, vol_y, vol_z;      /* voxels, e.g. 256 / 512 / 1024; vol_x and vol_y multiples of 8        */
+  int vol_x, vol_y, vol_z;      /* voxels, e.g. 256 / 512 / 1024; vol_x and vol_y multiples of 8.  Large volumes want
+                                   multiples of 16 or more (best: powers of two): the brick bitfield of the stored planes
+                                   -- one bit per 8^3 voxels, per 16^3 .. 64^3 only while vol_x and vol_y are multiples of
+                                   that edge and the field is longer than 4 KiB -- is staged in LDS by the raycast, and
+                                   hsk_create refuses (HSK_ERR_ARG) a volume whose field exceeds 64 KiB or, if that is
+                                   less, what the runtime reports as the shared memory of a block of the device:
+                                   648^3 is refused (66560 B), 656^3 and 1024^3 are not                   */
   float vol_size_m[3];          /* metric extent, default 3 x 3 x 3                                    */
   float trunc_dist_m;           /* default 0.03; clamped to >= 2.1 * max cell                           */
   int width, height;            /* depth image, default 640 x 480 (the shape HoniHelper.hs:34-36 returns) */

@@ -43,7 +43,7 @@ def mesh_indexed(vol, ntri, codes, size=3.0, col=None, normals=True):
     ids = np.full(E.shape, -1, np.int64)
     ids[ez, ey, ex, ek] = np.arange(nv)
     bz, by, bx = ez + (ek == 2), ey + (ek == 1), ex + (ek == 0)
-    G = _Grid(vol, (size,) * 3, Z, 0)
+    G = _Grid(vol, (size,) * 3 if np.isscalar(size) else tuple(size), Z, 0)   # (one extent for a cube, or one per axis)
     Fa = t[ez, ey, ex].astype(f32) / f32(32767)
     Fb = t[bz, by, bx].astype(f32) / f32(32767)
     wt = (Fa / (Fa - Fb)).astype(f32)
