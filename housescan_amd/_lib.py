@@ -154,6 +154,29 @@ class HskRelocStats(C.Structure):
     ]
 
 
+HSK_PLANE_MAX_POINTS, HSK_PLANE_MAX_PLANES, HSK_PLANE_MAX_HYPOTHESES, HSK_PLANE_MAX_REFITS = 1 << 24, 64, 4096, 8
+
+
+class HskPlaneParams(C.Structure):
+    """Mirror of `hsk_plane_params` (include/hskinfu.h): 32 bytes; every field is taken as it stands."""
+
+    _fields_ = [
+        ("dist_m", C.c_float), ("cos_min", C.c_float), ("min_fraction", C.c_float),
+        ("max_planes", C.c_int32), ("n_hypotheses", C.c_int32), ("refits", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class HskPlaneRecord(C.Structure):
+    """Mirror of `hsk_plane_record` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [
+        ("abcd", C.c_float * 4),
+        ("n_inliers", C.c_uint32), ("pad", C.c_uint32),
+        ("sum_abs", C.c_uint64),
+    ]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -249,6 +272,13 @@ SYMBOLS = {
     "hsk_default_reloc_params": (None, [_P, C.POINTER(HskRelocParams)]),
     "hsk_relocalize": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(HskRelocParams), _F, C.POINTER(HskRelocStats)]),
     "hsk_pose_lattice": (C.c_int, [_F, C.c_float, C.c_int, C.c_float, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_default_plane_params": (None, [C.POINTER(HskPlaneParams)]),
+    "hsk_detect_planes_oriented": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(HskPlaneParams), C.POINTER(HskPlaneRecord), C.c_size_t,
+                                             C.POINTER(C.c_size_t), _P, C.POINTER(C.c_size_t)]),
+    "hsk_detect_planes_volume": (C.c_int, [_P, C.POINTER(HskPlaneParams), C.POINTER(HskPlaneRecord), C.c_size_t, C.POINTER(C.c_size_t), _P,
+                                           C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_score_planes": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_float, C.c_float, _P]),
+    "hsk_plane_refit": (C.c_int, [C.POINTER(C.c_int64), _F, _F, _I]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

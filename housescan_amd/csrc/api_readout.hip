@@ -251,18 +251,19 @@ int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom) {
   k->out_bytes = want;
   return HSK_OK;
 }
-// The arrays of one product in the product buffer.  add(host pointer or null, bytes) in order -> the array's number; an absent
-// array takes no space.  place() sizes the buffer once; dev<T>(i) is array i's device pointer (null when absent); copy_out()
-// brings the arrays that are there to the caller through the pinned pair, in that order, and stops at the first error.
+// The arrays of one product in the product buffer.  add(host pointer or null, bytes, keep) in order -> the array's number; an
+// array that is neither handed out (a host pointer) nor kept for a device consumer (keep) takes no space.  place() sizes the
+// buffer once; dev<T>(i) is array i's device pointer (null when absent); copy_out() brings the arrays that have a host pointer to
+// the caller through the pinned pair, in that order, and stops at the first error.
 struct ProductArrays {
   ProductLayout lay;
   int n = 0;
   void* host[4];
   size_t at[4], len[4];
   char* base = nullptr;
-  int add(void* h, size_t bytes) {
+  int add(void* h, size_t bytes, bool keep = false) {
     host[n] = h;
-    len[n] = h ? bytes : 0;
+    len[n] = (h || keep) ? bytes : 0;
     at[n] = lay.take(len[n]);
     return n++;
   }
@@ -272,11 +273,11 @@ struct ProductArrays {
     return r;
   }
   template <class T>
-  T* dev(int i) const { return host[i] ? (T*)(base + at[i]) : nullptr; }
+  T* dev(int i) const { return len[i] ? (T*)(base + at[i]) : nullptr; }
   int copy_out(hsk_ctx* k) const {
     int r = HSK_OK;
     for (int i = 0; i < n && r == HSK_OK; ++i)
-      if (len[i]) r = ::copy_out(k, host[i], base + at[i], len[i]);
+      if (host[i] && len[i]) r = ::copy_out(k, host[i], base + at[i], len[i]);
     return r;
   }
 };
@@ -401,38 +402,63 @@ extern "C" int hsk_download_color(hsk_ctx* k, uint8_t* rgbw) {
   return copy_out(k, rgbw, k->d_color, k->color_bytes);
 }
 
-// the cloud of hsk_extract_cloud (the same count pass, shared with it: kind 1) with normals and colour from k_extract_attrs
+// The cloud with attributes, in two steps shared by hsk_extract_cloud_attrs and hsk_detect_planes_volume.  cloud_count: the count
+// pass of hsk_extract_cloud (kind 1: whichever product asks first pays for it).  cloud_attrs_write: behind it, the first nw points
+// into the product buffer as the arrays 0 xyz, 1 normals, 2 rgb of `pa` -- each present when it has a host pointer, xyz and
+// normals also when `keep` asks for them on the device; the uncoloured points are counted in d_counter's second word (the totals
+// are its first, and nothing else on the stream touches it between the memset here and the caller's read).
+int cloud_count(hsk_ctx* k, size_t* total) {
+  const int r = product_counts(k, 1, k->d_counter, [&]() {
+    launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, k->d_flags);
+  });
+  if (r == HSK_OK) *total = (size_t)k->ro_totals[0];
+  return r;
+}
+static int cloud_attrs_write(hsk_ctx* k, ProductArrays& pa, size_t nw, float* xyz, float* normals, uint8_t* rgb, bool keep) {
+  const int a_xyz = pa.add(xyz, nw * 12, keep), a_nrm = pa.add(normals, nw * 12, keep), a_rgb = pa.add(rgb, nw * 3);
+  const int r = pa.place(k);
+  if (r != HSK_OK) return r;
+  unsigned long long* d_uncol = k->d_counter + 1;
+  HIPCHK(k, hipMemsetAsync(d_uncol, 0, 8, k->stream));
+  launch_extract_attrs(k->stream, k->d_vol, k->d_color, k->vp, k->d_rowcnt, k->d_rowoff, pa.dev<float>(a_xyz), pa.dev<float>(a_nrm),
+                       pa.dev<unsigned char>(a_rgb), nw, d_uncol, k->d_flags);
+  HIPCHK(k, hipGetLastError());
+  return HSK_OK;
+}
+
 extern "C" int hsk_extract_cloud_attrs(hsk_ctx* k, float* xyz, float* normals, uint8_t* rgb, size_t cap_points, size_t* n_points,
                                        size_t* n_uncolored) {
   if (!k || !n_points) return HSK_ERR_ARG;
   if (rgb && require_color(k)) return HSK_ERR_STATE;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   if (n_uncolored) *n_uncolored = 0;
-  int r = product_counts(k, 1, k->d_counter, [&]() {
-    launch_extract(k->stream, k->d_vol, k->vp, k->d_rowcnt, k->d_rowoff, k->d_counter, nullptr, 0, k->d_flags);
-  });
+  size_t total = 0;
+  int r = cloud_count(k, &total);
   if (r != HSK_OK) return r;
-  const size_t total = (size_t)k->ro_totals[0];
   *n_points = total;
   if (!xyz || cap_points == 0 || total == 0) return HSK_OK;
   const size_t nw = total < cap_points ? total : cap_points;
   ProductArrays pa;
-  const int a_xyz = pa.add(xyz, nw * 12), a_nrm = pa.add(normals, nw * 12), a_rgb = pa.add(rgb, nw * 3);
-  r = pa.place(k);
+  r = cloud_attrs_write(k, pa, nw, xyz, normals, rgb, false);
   if (r != HSK_OK) return r;
-  // (the uncoloured points are counted in d_counter's second word: the totals are its first, and nothing else on the stream
-  // touches it between this memset and the read below)
-  unsigned long long* d_uncol = k->d_counter + 1;
-  HIPCHK(k, hipMemsetAsync(d_uncol, 0, 8, k->stream));
-  launch_extract_attrs(k->stream, k->d_vol, k->d_color, k->vp, k->d_rowcnt, k->d_rowoff, pa.dev<float>(a_xyz), pa.dev<float>(a_nrm),
-                       pa.dev<unsigned char>(a_rgb), nw, d_uncol, k->d_flags);
   r = pa.copy_out(k);
   if (r == HSK_OK && rgb && n_uncolored) {
     unsigned long long u = 0;
-    r = read_u64(k, &u, d_uncol);
+    r = read_u64(k, &u, k->d_counter + 1);
     *n_uncolored = (size_t)u;
   }
   return r;
+}
+
+// all n > 0 points of the cloud cloud_count has counted, with their normals (packed triples), left in the product buffer for a
+// device consumer: no copy out
+int cloud_attrs_on_device(hsk_ctx* k, size_t n, const float** d_xyz, const float** d_normals) {
+  ProductArrays pa;
+  const int r = cloud_attrs_write(k, pa, n, nullptr, nullptr, nullptr, true);
+  if (r != HSK_OK) return r;
+  *d_xyz = pa.dev<float>(0);
+  *d_normals = pa.dev<float>(1);
+  return HSK_OK;
 }
 
 // hsk_extract_mesh_cubes' surface as an indexed mesh, welded on the device by edge identity (extract.hip: k_mesh_index_*).

@@ -153,7 +153,7 @@ struct hsk_ctx {
   // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
   // volume alignment (hsk_align_cloud), made on first use as a destination and only grown: the accumulators (align.hip:
   // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what pose scoring adds (api_reloc.hip: the poses, the slabs'
-  // partial values, the scores); h_align: the accumulators' pinned host side
+  // partial values, the scores; api_planes.hip: the labels, the hypotheses, the blocks' sums); h_align: the accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;
   unsigned long long* h_align = nullptr;
@@ -194,6 +194,8 @@ int require_idle(const hsk_ctx* k, hsk_ctx* errs);
 inline int require_idle(hsk_ctx* k) { return require_idle(k, k); }
 int require_color(hsk_ctx* k);
 int require_whole_volume(const hsk_ctx* k, hsk_ctx* errs, const char* who, const char* sentence = "a context that stores part of its volume");
+// ---- products.cpp ----
+uint32_t plane_lcg_next(uint64_t* state);  // hsk_detect_planes' generator: one step, the state in place
 // ---- api_align.hip ----
 int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params* params, hsk_align_params* p, const char* who);
 int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra);
@@ -205,6 +207,10 @@ void parallel_memcpy(void* dst, const void* src, size_t bytes);
 int copy_out(hsk_ctx* k, void* dst, const void* src_dev, size_t bytes);
 int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom = true);
 int read_u64(hsk_ctx* k, unsigned long long* dst, const unsigned long long* src_dev, int n = 1);
+// the cloud's count pass (shared with hsk_extract_cloud / hsk_extract_cloud_attrs) and, behind it, all n > 0 points with their
+// normals (packed triples) written into the product buffer and left there
+int cloud_count(hsk_ctx* k, size_t* total);
+int cloud_attrs_on_device(hsk_ctx* k, size_t n, const float** d_xyz, const float** d_normals);
 // the product buffer carved into the arrays of one product, each 256-byte aligned: take() -> the next array's offset
 struct ProductLayout {
   size_t bytes = 0;

@@ -117,6 +117,27 @@ void launch_reloc_score(hipStream_t s, const void* dst_vol, const VolParams& dv,
 void launch_reloc_gather(hipStream_t s, const float* vmap, const float* nmap, unsigned P, unsigned stride, unsigned np, unsigned pitch,
                          float* soa);
 
+// oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
+// labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
+// seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the
+// inliers of hyp[j], j < n_hyp <= HSK_PLANE_MAX_HYP; partial: plane_score_blocks(n) x n_hyp words.  moments: sums10 = the
+// inliers' count, sum of q (3), sum of q_a q_b (xx xy xz yy yz zz), q = rint(x 4096); label: the inliers get `index`, out2 = their
+// count and the sum of rint(|s| 65536); both with partial: plane_sweep_blocks(n) x 16 words.  Nothing is launched with n == 0.
+#define HSK_PLANE_MAX_HYP 4096
+#define HSK_PLANE_MAX_BLOCKS 1024
+unsigned plane_score_blocks(unsigned n);
+unsigned plane_sweep_blocks(unsigned n);
+void launch_plane_seed(hipStream_t s, const float* soa, const int* labels, const unsigned* seeds, unsigned n_hyp, unsigned pitch, float* hyp);
+void launch_plane_score(hipStream_t s, const float* soa, const int* labels, const float* hyp, unsigned n, unsigned pitch, unsigned n_hyp,
+                        float dist_m, float cos_min, unsigned* partial, unsigned* counts);
+void launch_plane_moments(hipStream_t s, const float* soa, const int* labels, const float abcd[4], unsigned n, unsigned pitch, float dist_m,
+                          float cos_min, unsigned long long* partial, unsigned long long* sums10);
+void launch_plane_label(hipStream_t s, const float* soa, int* labels, const float abcd[4], int index, unsigned n, unsigned pitch, float dist_m,
+                        float cos_min, unsigned long long* partial, unsigned long long* out2);
+void launch_plane_unlabel(hipStream_t s, int* labels, int index, unsigned n);
+// a cloud with normals as two arrays of packed triples (the product buffer's) -> the six planes
+void launch_plane_gather(hipStream_t s, const float* xyz, const float* normals, unsigned n, unsigned pitch, float* soa);
+
 // sparse volume image (pack.hip): bricks of 8^3 voxels, pack_bricks of them, a class byte and a record size
 // (in 4-byte words) each.  launch_pack_scan turns the sizes into offsets in place (an exclusive scan; bsum: pack_scan_blocks
 // words of scratch) and leaves in counts[0..3] the bricks per class, in counts[4] the payload's length in words (8 words).

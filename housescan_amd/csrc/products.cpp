@@ -329,6 +329,56 @@ extern "C" int hsk_detect_planes(const float* xyz, size_t n, float dist_thresh, 
   return HSK_OK;
 }
 
+// Oriented plane detection (include/hskinfu.h), the host's share of a round: the generator above for api_planes.hip
+// (hsk_ctx.h declares it), and one refit from the inliers' integer moments -- the same Jacobi as the detector above.
+uint32_t plane_lcg_next(uint64_t* state) {
+  Lcg g{*state};
+  const uint32_t v = g.next();
+  *state = g.s;
+  return v;
+}
+
+extern "C" int hsk_plane_refit(const int64_t sums10[10], const float prev_abcd[4], float out_abcd[4], int* ok) {
+  if (!sums10 || !prev_abcd || !out_abcd || !ok) return HSK_ERR_ARG;
+  const int64_t lim = (int64_t)1 << 62;
+  if (sums10[0] < 0 || sums10[0] > ((int64_t)1 << 24)) return HSK_ERR_ARG;
+  for (int i = 1; i < 10; ++i)
+    if (sums10[i] < -lim || sums10[i] > lim) return HSK_ERR_ARG;
+  *ok = 0;
+  float prev[4];
+  memcpy(prev, prev_abcd, sizeof(prev));  // (out_abcd may be prev_abcd)
+  memcpy(out_abcd, prev, sizeof(prev));
+  const int64_t m = sums10[0];
+  if (m < 3) return HSK_OK;
+  const int64_t* S = sums10 + 1;   // the sums of q
+  const int64_t* SS = sums10 + 4;  // xx xy xz yy yz zz
+  static const int at[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+  const double mm = (double)m * (double)m;
+  double Cm[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const __int128 num = (__int128)m * (__int128)SS[at[a][b]] - (__int128)S[a] * (__int128)S[b];  // exact: below 2^87
+      Cm[a][b] = (double)num / mm;
+    }
+  double nn[3];
+  smallest_eigvec(Cm, nn);
+  const double len = std::sqrt((nn[0] * nn[0] + nn[1] * nn[1]) + nn[2] * nn[2]);
+  if (len < 1e-12) return HSK_OK;
+  for (double& c : nn) c /= len;
+  const double dot = (nn[0] * (double)prev[0] + nn[1] * (double)prev[1]) + nn[2] * (double)prev[2];
+  if (dot < 0.0)
+    for (double& c : nn) c = -c;
+  double mean[3];
+  for (int a = 0; a < 3; ++a) mean[a] = ((double)S[a] / (double)m) / 4096.0;
+  const double d = -((nn[0] * mean[0] + nn[1] * mean[1]) + nn[2] * mean[2]);
+  out_abcd[0] = (float)nn[0];
+  out_abcd[1] = (float)nn[1];
+  out_abcd[2] = (float)nn[2];
+  out_abcd[3] = (float)d;
+  *ok = 1;
+  return HSK_OK;
+}
+
 // Convex hull (in the plane, counter-clockwise about the normal) of the points labelled `plane`; hull_xyz gets up
 // to cap vertices lying exactly on the plane.
 extern "C" int hsk_plane_hull(const float* xyz, size_t n, const int* labels, int plane, const float abcd[4], float* hull_xyz,

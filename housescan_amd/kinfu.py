@@ -64,6 +64,20 @@ SCORE_DTYPE = np.dtype([("n_near", "<u4"), ("n_free", "<u4"), ("n_behind", "<u4"
                         ("n_skipped", "<u4"), ("sum_abs", "<u8")])     # hsk_pose_score
 
 
+PLANE_DTYPE = np.dtype([("abcd", "<f4", (4,)), ("n_inliers", "<u4"), ("pad", "<u4"), ("sum_abs", "<u8")])     # hsk_plane_record
+
+
+def plane_refit(sums10, prev_abcd):
+    """one refit of a plane from its inliers' integer moments (hsk_plane_refit; host only): sums10 = count, sums of q (3), sums
+    of q_a q_b (xx xy xz yy yz zz) with q = rint(coordinate * 4096) -> (abcd [4] float32, ok)"""
+    s = np.ascontiguousarray(sums10, np.int64).reshape(10)
+    prev = np.ascontiguousarray(prev_abcd, np.float32).reshape(4)
+    out, ok = np.zeros(4, np.float32), C.c_int()
+    if _lib.load().hsk_plane_refit(s.ctypes.data_as(C.POINTER(C.c_int64)), _fp(prev), _fp(out), C.byref(ok)) != 0:
+        raise KinfuError("plane_refit: invalid arguments (a count outside 0..2^24 or a sum outside +-2^62)")
+    return out, bool(ok.value)
+
+
 def pose_lattice(centre, step_m, n_trans, step_rad, n_rot):
     """candidate poses around `centre` [4, 4]: centre . T(i, j, k) step_m . Ry(a step_rad) . Rx(b step_rad) for i, j, k in
     [-n_trans, n_trans] and a, b in [-n_rot, n_rot], offsets in the camera's own frame (hsk_pose_lattice; host only)
@@ -572,6 +586,69 @@ class KinfuTracker:
                  for r in range(max(0, min(int(st.n_refined), _lib.HSK_RELOC_MAX_REFINE)))]
         return out.reshape(4, 4), {"status": _lib.HSK_RELOC_STATUS[st.status], "n_valid": int(st.n_valid), "n_candidates": int(st.n_candidates),
                                    "best": int(st.best), "candidates": cands}
+
+    # ---- oriented plane detection -------------------------------------------------------------------------
+    @staticmethod
+    def _plane_params(over):
+        """the defaults with the keywords dist_m, cos_min, min_fraction, max_planes, n_hypotheses, refits, seed over them"""
+        p = _lib.HskPlaneParams()
+        _lib.load().hsk_default_plane_params(C.byref(p))
+        for name, val in over.items():
+            if name not in dict(p._fields_):
+                raise TypeError(f"unknown plane parameter {name!r}")
+            setattr(p, name, val)
+        return p
+
+    @staticmethod
+    def _plane_records(rec, n):
+        return np.frombuffer(rec, PLANE_DTYPE, count=n).copy()
+
+    def detect_planes_cloud(self, xyz, normals, **params):
+        """the planes of the points xyz [n, 3] with normals [n, 3], detected on the device (hsk_detect_planes_oriented); the
+        tracker's volume is not read.  Keywords: dist_m, cos_min, min_fraction, max_planes, n_hypotheses, refits, seed.
+        -> (records [k]: abcd [4] float32 with the normal into the room, n_inliers, pad, sum_abs; labels [n] int32, -1 = no
+        plane; the number of invalid points)"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(pts) != len(nrm):
+            raise ValueError(f"detect_planes_cloud: {len(pts)} points but {len(nrm)} normals")
+        p = self._plane_params(params)
+        rec = (_lib.HskPlaneRecord * _lib.HSK_PLANE_MAX_PLANES)()
+        labels = np.full(len(pts), -1, np.int32)
+        k, bad = C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_detect_planes_oriented(self.h, pts.ctypes.data if len(pts) else None, nrm.ctypes.data if len(pts) else None, len(pts),
+                                                     C.byref(p), rec, len(rec), C.byref(k), labels.ctypes.data if len(pts) else None, C.byref(bad)))
+        return self._plane_records(rec, k.value), labels, bad.value
+
+    def detect_planes(self, **params):
+        """the planes of this volume's own cloud -- extract_cloud_attrs' points and normals, which stay on the device
+        (hsk_detect_planes_volume) -> (records [k], labels [n] int32 in that cloud's order)"""
+        p = self._plane_params(params)
+        n = C.c_size_t()
+        self._ck(self.lib.hsk_detect_planes_volume(self.h, C.byref(p), None, 0, None, None, 0, C.byref(n)))
+        rec = (_lib.HskPlaneRecord * _lib.HSK_PLANE_MAX_PLANES)()
+        labels = np.full(n.value, -1, np.int32)
+        k, again = C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.hsk_detect_planes_volume(self.h, C.byref(p), rec, len(rec), C.byref(k), labels.ctypes.data if n.value else None, n.value,
+                                                   C.byref(again)))
+        if again.value != n.value:
+            raise KinfuError("detect_planes: the cloud changed between the two calls")
+        return self._plane_records(rec, k.value), labels
+
+    def score_planes(self, xyz, normals, planes_abcd, dist_m=0.02, cos_min=0.8660254037844387, labels=None):
+        """the inliers of each plane [m, 4] among the points (hsk_score_planes); labels [n] (optional): a point with a label >= 0
+        counts for no plane -> counts [m] uint32"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        pl = np.ascontiguousarray(planes_abcd, np.float32).reshape(-1, 4)
+        lab = None if labels is None else np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if len(pts) != len(nrm) or (lab is not None and len(lab) != len(pts)):
+            raise ValueError("score_planes: points, normals and labels must have one row per point")
+        out = np.zeros(len(pl), np.uint32)
+        self._ck(self.lib.hsk_score_planes(self.h, pts.ctypes.data if len(pts) else None, nrm.ctypes.data if len(pts) else None,
+                                           lab.ctypes.data if lab is not None and len(lab) else None, len(pts), pl.ctypes.data if len(pl) else None,
+                                           len(pl), dist_m, cos_min, out.ctypes.data if len(pl) else None))
+        return out
 
     # ---- volume files -----------------------------------------------------------------------------------
     def pack_volume(self, with_info=False):

@@ -118,12 +118,15 @@ def plane_hull(xyz, labels, plane, abcd):
     return hull[:n.value].copy()
 
 
-def write_room_dir(room_dir, cloud_xyz, leaf=0.03, *, cloud_rgb=None, cloud_normals=None, colored_downsampled=False, **plane_args):
+def write_room_dir(room_dir, cloud_xyz, leaf=0.03, *, cloud_rgb=None, cloud_normals=None, colored_downsampled=False, planes=None, **plane_args):
     """cloud (full resolution, KinFu frame) -> the files HouseScan's loadRoom expects. Returns (planes, n_downsampled).
     With cloud_rgb (and cloud_normals; KinfuTracker.extract_cloud_attrs) cloud_bin.pcd is written as XYZRGBNormal, the coloured
     form of HouseScan's cloud loader (Main.hs:1325-1345) -- NaN normals when cloud_normals is None; cloud_downsampled.pcd stays
     XYZ -- the form loadRoom tries first -- unless colored_downsampled.  Plane detection always runs on the same downsampled xyz.
-    Normals without colour, or colored_downsampled without colour, are refused (ValueError): there is no XYZ + normal form."""
+    Normals without colour, or colored_downsampled without colour, are refused (ValueError): there is no XYZ + normal form.
+    planes = (planes_abcd [k, 4], labels [m], xyz [m, 3]): planes found elsewhere (KinfuTracker.detect_planes on the device) with
+    the points they were found on -- the RANSAC is skipped, planes.txt holds them and the hulls are hsk_plane_hull's of the
+    labelled points; plane_args are then refused (ValueError)."""
     if cloud_rgb is None and (cloud_normals is not None or colored_downsampled):
         raise ValueError("write_room_dir: cloud_normals and colored_downsampled need cloud_rgb (the coloured file carries both)")
     lib = _lib.load()
@@ -139,11 +142,22 @@ def write_room_dir(room_dir, cloud_xyz, leaf=0.03, *, cloud_rgb=None, cloud_norm
         write_pcd_xyzrgbnormal(os.path.join(room_dir, "cloud_downsampled.pcd"), d_xyz, d_rgb, d_nrm)
     else:
         write_pcd(os.path.join(room_dir, "cloud_downsampled.pcd"), down)
-    planes, labels = detect_planes(down, **plane_args)
+    hull_pts = down
+    if planes is None:
+        planes, labels = detect_planes(down, **plane_args)
+    else:
+        if plane_args:
+            raise ValueError("write_room_dir: planes were given, so the detector's arguments have nothing to act on")
+        planes, labels, hull_pts = planes
+        planes = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+        labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        hull_pts = np.ascontiguousarray(hull_pts, np.float32).reshape(-1, 3)
+        if len(labels) != len(hull_pts):
+            raise ValueError(f"write_room_dir: {len(labels)} labels for {len(hull_pts)} points")
     _ck(lib.hsk_write_planes_txt(os.fsencode(os.path.join(room_dir, "planes.txt")), planes.ctypes.data, len(planes)),
         "hsk_write_planes_txt")
     for k, eq in enumerate(planes):
-        write_pcd(os.path.join(room_dir, f"cloud_plane_hull{k}.pcd"), plane_hull(down, labels, k, eq))
+        write_pcd(os.path.join(room_dir, f"cloud_plane_hull{k}.pcd"), plane_hull(hull_pts, labels, k, eq))
     return planes, len(down)
 
 

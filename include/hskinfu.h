@@ -549,6 +549,67 @@ int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, const float*
  * count, a non-finite step, more than 65536 poses, cap below the count (with *n set). */
 int hsk_pose_lattice(const float centre[16], float step_m, int n_trans, float step_rad, int n_rot, float* poses, size_t cap, size_t* n);
 
+/* ---- Oriented plane detection on the device: a room's planes from points with normals, a caller's cloud or the context's own
+ * volume (DESIGN.md 3.14 the kernels, 8h the rule; tests/planes_twin.py restates the rule in numpy).  With a normal at every
+ * point one point is a plane hypothesis, and the two faces of one wall -- 3 cm apart, normals opposed -- are two planes, which
+ * the unoriented host detector (hsk_detect_planes) cannot tell apart.  Every device sum is an integer: the result is the same
+ * bits whatever the launch shape.  A plane's normal points as its points' normals do: into the room.
+ * A point is VALID iff its six numbers are finite and |x|, |y|, |z| <= 64; it is an INLIER of (a, b, c, d) iff it is valid,
+ * unlabelled, |((a x + b y) + c z) + d| <= dist_m and (a nx + b ny) + c nz >= cos_min (binary32, no contraction). */
+typedef struct hsk_plane_params {
+  float dist_m;           /* largest |distance| of an inlier, (0, 1]                                     default 0.02       */
+  float cos_min;          /* least n_plane . n_point of an inlier, [-1, 1]                               default cos 30 deg */
+  float min_fraction;     /* a plane needs max(3, floor(min_fraction n)) inliers; finite, >= 0           default 0.03       */
+  int32_t max_planes;     /* 1..64                                                                       default 12         */
+  int32_t n_hypotheses;   /* seed points tried per round, 1..4096                                        default 512        */
+  int32_t refits;         /* refits of a round's best hypothesis on its inliers, 0..8                    default 2          */
+  uint64_t seed;          /* of the 64-bit LCG that draws the seed points               default 0x9E3779B97F4A7C15          */
+} hsk_plane_params;       /* 32 bytes; every field is taken as it stands (no "0 = default")                                 */
+void hsk_default_plane_params(hsk_plane_params* p);
+typedef struct hsk_plane_record {
+  float abcd[4];          /* a x + b y + c z + d = 0, (a, b, c) a unit normal (the seed point's as stored when refits = 0)  */
+  uint32_t n_inliers;     /* the points labelled with this plane                                                            */
+  uint32_t pad;           /* 0                                                                                              */
+  uint64_t sum_abs;       /* over them: rint(|distance| * 65536), added as integers (mean residual = sum_abs / 65536 / n)   */
+} hsk_plane_record;       /* 32 bytes */
+#define HSK_PLANE_MAX_POINTS ((size_t)1 << 24)
+#define HSK_PLANE_MAX_PLANES 64
+#define HSK_PLANE_MAX_HYPOTHESES 4096
+#define HSK_PLANE_MAX_REFITS 8
+/* The planes of n points xyz with normals (3 floats each), in detection order.  Round by round while fewer than max_planes are
+ * found: n_hypotheses seed points i = next() % n (hsk_detect_planes' generator, running on across rounds) each make the
+ * plane (its normal, d = -((a x + b y) + c z)) -- none when the point is invalid or labelled; every hypothesis is scored
+ * against every point, the largest count wins (ties: the first) and the detection ends when it is below the least count; the
+ * winner is refitted `refits` times on its inliers (hsk_plane_refit on their integer moments); its inliers are labelled -- or,
+ * when the refits left fewer than the least count, nothing is and the detection ends.
+ * params NULL: the defaults.  planes: cap records (at most max_planes are written); labels (may be NULL): n ints, the plane of
+ * each point or -1; *n_invalid (may be NULL): the invalid points.  Synchronous.  The context supplies the device, the stream
+ * and the scratch (hsk_align_cloud's, only grown): its volume is not read and nothing of it is written, so any idle context
+ * will do.  n = 0: HSK_OK, no planes.  HSK_ERR_ARG: a NULL context, xyz or normals (n > 0), planes or n_planes; n > 2^24; a
+ * parameter outside its range; cap < max_planes.  HSK_ERR_STATE: a frame in flight. */
+int hsk_detect_planes_oriented(hsk_ctx* k, const float* xyz, const float* normals, size_t n, const hsk_plane_params* params,
+                               hsk_plane_record* planes, size_t cap, size_t* n_planes, int32_t* labels, size_t* n_invalid);
+/* The same on the context's own cloud -- hsk_extract_cloud_attrs' points and normals, in that order, which never leave the
+ * device -- so the labels are in that cloud's order: extract it (before or after; the count pass is shared) to use them.
+ * Two calls as for the products: planes == NULL and labels == NULL set *n_points only; otherwise cap as above and, with labels,
+ * cap_labels >= *n_points (HSK_ERR_ARG with *n_points set when it is not).  Nothing the tracker reads is written, and the
+ * cached count pass stays valid.  HSK_ERR_STATE: a frame in flight; a slab of a group or a context that stores part of its
+ * volume (as hsk_render_view); HSK_ERR_ARG also: a cloud of more than 2^24 points. */
+int hsk_detect_planes_volume(hsk_ctx* k, const hsk_plane_params* params, hsk_plane_record* planes, size_t cap, size_t* n_planes,
+                             int32_t* labels, size_t cap_labels, size_t* n_points);
+/* The scoring stage alone: counts[j] = the inliers of planes_abcd[4 j ..] among the n points; labels (may be NULL: every valid
+ * point is unlabelled): n ints, a point with a label >= 0 counts for no plane.  n_planes <= 4096, n <= 2^24, dist_m in (0, 1],
+ * cos_min in [-1, 1]; n = 0: zeros.  Errors as hsk_detect_planes_oriented's. */
+int hsk_score_planes(hsk_ctx* k, const float* xyz, const float* normals, const int32_t* labels, size_t n, const float* planes_abcd,
+                     size_t n_planes, float dist_m, float cos_min, uint32_t* counts);
+/* host only: one refit.  sums10 = the inliers' count m, the sums of q_x, q_y, q_z and of q_x q_x, q_x q_y, q_x q_z, q_y q_y,
+ * q_y q_z, q_z q_z with q = rint(coordinate * 4096) (|q| <= 2^18, m <= 2^24).  C_ab = (double)(m S_ab - S_a S_b) / ((double)m
+ * (double)m), the numerator exact; the normal is C's eigenvector of the smallest eigenvalue (hsk_detect_planes' Jacobi) divided
+ * by its length, negated when its binary64 dot product with prev_abcd's normal is negative; d = -(n . mean), mean =
+ * ((double)S_a / (double)m) / 4096; the four numbers rounded to binary32 once.  *ok = 0 and out_abcd = prev_abcd: m < 3, or a
+ * length below 1e-12.  HSK_ERR_ARG: a NULL pointer, m < 0 or > 2^24, a sum outside +-2^62. */
+int hsk_plane_refit(const int64_t sums10[10], const float prev_abcd[4], float out_abcd[4], int* ok);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */

@@ -28,6 +28,10 @@ from its stitched .xf (hsk_align_volume: the room's cloud and normals against th
 which is written as <room>.refined.xf; both matrices and every iteration's n_used / rms are printed.  A registration that does
 not end CONVERGED keeps the stitched matrix.
 
+--device-planes: each room's planes are detected on the GPU from its volume's own cloud and normals (hsk_detect_planes_volume:
+oriented, on every point, the cloud never leaves the device for it) instead of by the host RANSAC on the downsampled cloud;
+write_room_dir takes them with their labels, planes.txt and the hulls come from the labelled full-resolution points.
+
 --save-volumes: behind each scan the room's volume is written to <room dir>/volume.hskv (hsk_save_volume: a sparse image packed
 on the GPU) and the room's context is closed.  --floorplan and --fuse-house then load one room at a time from its file into a
 single scratch context (hsk_load_volume), so at most two contexts are alive at once however many rooms the house has.
@@ -45,7 +49,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=False, keep=False):
+def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=False, keep=False, planes_out=None):
     """the three-turn scan inside room `variant`; returns (cloud, worst translation error [m], lost frames, fps).
     (Round 6: the frames go through the pipelined pair and the clock covers the tracker only -- the poses and the errors are
     computed outside it; the synchronous call with a pose and a norm per frame inside the loop made "2050 frames/s" of a
@@ -66,6 +70,10 @@ def scan_room(hsk, variant, n, frames, device_id=0, with_mesh=False, indexed=Fal
     lost = sum(1 for k, (_, ok) in enumerate(got) if k > 0 and not ok)   # frame 0 only seeds the model
     worst = max(float(np.linalg.norm(pose[:3, 3] - gt[:3, 3])) for (pose, _), gt in zip(got, gts))
     cloud, total = trk.extract_cloud()
+    if planes_out is not None:   # (--device-planes: the labels are in this cloud's order)
+        t1 = time.perf_counter()
+        rec, labels = trk.detect_planes(dist_m=0.025, min_fraction=0.03)
+        planes_out.append((rec, labels, 1e3 * (time.perf_counter() - t1)))
     if with_mesh and indexed:
         mesh = trk.extract_mesh_indexed(normals=True, rgb=False)[:3]   # (vertices, faces, normals)
     else:
@@ -271,6 +279,7 @@ def main():
     ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
     ap.add_argument("--fuse-house", action="store_true", help="house_fused_mesh.ply + house_fused_floorplan.ppm: the rooms' volumes fused into one house volume on the GPU")
     ap.add_argument("--refine", action="store_true", help="with --fuse-house: register every room after the first against the house fused so far (<room>.refined.xf)")
+    ap.add_argument("--device-planes", action="store_true", help="the rooms' planes from hsk_detect_planes_volume (oriented, on the GPU) instead of the host RANSAC")
     ap.add_argument("--save-volumes", action="store_true", help="<room dir>/volume.hskv behind each scan, the room's context closed; --floorplan / --fuse-house load them one at a time")
     args = ap.parse_args()
 
@@ -282,8 +291,9 @@ def main():
     report = {"rooms": []}
     dirs, variants, meshes, trackers = [], list(range(args.rooms)), [], RoomVolumes(hsk)
     for v in variants:
+        found = [] if args.device_planes else None
         res = scan_room(hsk, v, args.volume, args.frames, with_mesh=True, indexed=args.indexed_mesh,
-                        keep=args.floorplan or args.fuse_house or args.save_volumes)
+                        keep=args.floorplan or args.fuse_house or args.save_volumes, planes_out=found)
         cloud, worst, lost, fps, mesh = res[:5]
         if args.save_volumes:
             os.makedirs(os.path.join(args.out, f"room{v}"), exist_ok=True)
@@ -300,7 +310,14 @@ def main():
             trackers.add(res[5])
         meshes.append(mesh)
         d = os.path.join(args.out, f"room{v}", "walls")
-        planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, dist_thresh=0.025, min_fraction=0.03)
+        if args.device_planes:
+            rec, labels, ms = found[0]
+            planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, planes=(rec["abcd"], labels, cloud))
+            resid = [float(r["sum_abs"]) / 65536.0 / max(1, int(r["n_inliers"])) * 1e3 for r in rec]
+            print(f"room{v}: {len(rec)} planes on the device in {ms:.1f} ms, {int((labels >= 0).sum())} of {len(labels)} points on them, "
+                  f"mean residuals {[round(x, 2) for x in resid]} mm")
+        else:
+            planes, n_down = P.write_room_dir(d, cloud, leaf=0.04, dist_thresh=0.025, min_fraction=0.03)
         if args.indexed_mesh:
             P.write_ply_indexed(os.path.join(d, "mesh.ply"), mesh[0], mesh[1], normals=mesh[2])
         print(f"room{v}: {len(cloud)} points, {n_down} downsampled, {len(planes)} planes, worst pose error {worst * 1000:.1f} mm, "
