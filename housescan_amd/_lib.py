@@ -177,6 +177,47 @@ class HskPlaneRecord(C.Structure):
     ]
 
 
+HSK_RAY_HIT, HSK_RAY_FRONTIER, HSK_RAY_OPEN, HSK_RAY_BLIND, HSK_RAY_OUTSIDE = 0, 1, 2, 3, 4
+HSK_RAY_CLASS = ("hit", "frontier", "open", "blind", "outside")
+HSK_EYE_FREE, HSK_EYE_UNSEEN, HSK_EYE_SOLID, HSK_EYE_OUTSIDE = 0, 1, 2, 3
+HSK_COVER_MAX_POSES = 65536
+
+
+class HskVoxelBox(C.Structure):
+    """Mirror of `hsk_voxel_box` (include/hskinfu.h): the voxels lo <= (x, y, z) < hi."""
+
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3)]
+
+
+class HskCoverage(C.Structure):
+    """Mirror of `hsk_coverage` (include/hskinfu.h): 80 bytes."""
+
+    _fields_ = [
+        ("n_unseen", C.c_uint64), ("n_free", C.c_uint64), ("n_solid", C.c_uint64), ("n_frontier", C.c_uint64),
+        ("faces", C.c_uint64 * 6),
+    ]
+
+
+class HskProbe(C.Structure):
+    """Mirror of `hsk_probe` (include/hskinfu.h): a virtual depth camera and the samples along its rays."""
+
+    _fields_ = [
+        ("width", C.c_int), ("height", C.c_int),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("near_m", C.c_float), ("far_m", C.c_float), ("step_m", C.c_float),
+    ]
+
+
+class HskViewScore(C.Structure):
+    """Mirror of `hsk_view_score` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [
+        ("n_hit", C.c_uint32), ("n_frontier", C.c_uint32), ("n_open", C.c_uint32), ("n_blind", C.c_uint32), ("n_outside", C.c_uint32),
+        ("eye_state", C.c_uint32),
+        ("gain", C.c_uint64),
+    ]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -279,6 +320,11 @@ SYMBOLS = {
                                            C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_score_planes": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "hsk_plane_refit": (C.c_int, [C.POINTER(C.c_int64), _F, _F, _I]),
+    "hsk_default_probe": (None, [_P, C.POINTER(HskProbe)]),
+    "hsk_coverage_census": (C.c_int, [_P, C.POINTER(HskVoxelBox), C.POINTER(HskCoverage)]),
+    "hsk_score_views": (C.c_int, [_P, C.POINTER(HskProbe), _P, C.c_size_t, C.POINTER(HskViewScore)]),
+    "hsk_render_coverage": (C.c_int, [_P, C.POINTER(HskProbe), _F, _P, _P, _P, C.POINTER(HskViewScore)]),
+    "hsk_rank_views": (C.c_int, [C.POINTER(HskViewScore), C.c_size_t, C.POINTER(C.c_uint32)]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

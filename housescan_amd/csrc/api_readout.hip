@@ -358,6 +358,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) r = ensure_view(k);
   if (r == HSK_OK) HIPCHK(k, (hipError_t)view_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)section_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)cover_warm());
   return r;
 }
 

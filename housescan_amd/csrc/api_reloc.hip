@@ -26,7 +26,7 @@ struct RelocScratch {
   }
 };
 
-static int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who) {
+int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who) {
   for (size_t j = 0; j < n_poses; ++j) {
     float inv[16];
     if (hsk_invert_rigid(poses + 16 * j, inv) != HSK_OK)

@@ -174,6 +174,16 @@ struct hsk_ctx {
     }                                                                                          \
   } while (0)
 
+// the truncation distance of a configuration (hsk_create's tau): trunc_dist_m, but at least 2.1 times the largest cell
+inline float config_tau(const hsk_config* c) {
+  float m = c->vol_size_m[0] / (float)c->vol_x;
+  const float cy = c->vol_size_m[1] / (float)c->vol_y, cz = c->vol_size_m[2] / (float)c->vol_z;
+  m = m > cy ? m : cy;
+  m = m > cz ? m : cz;
+  const float lo = 2.1f * m;
+  return c->trunc_dist_m > lo ? c->trunc_dist_m : lo;
+}
+
 // ---- hskinfu_api.hip ----
 std::string& create_error();  // the thread's message of the calls that have no context (hsk_last_error(NULL))
 int fail(hsk_ctx* k, int code, const char* msg);
@@ -201,6 +211,9 @@ int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params
 int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra);
 int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t np, unsigned pitch, const float src_to_dst[16], float m_out[16],
               hsk_align_stats* st);
+// ---- api_reloc.hip ----
+// every one of the n_poses matrices (16 floats each) is rigid (hsk_invert_rigid), or HSK_ERR_ARG: "<who>: pose <index> is not rigid ..."
+int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who);
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

@@ -117,6 +117,25 @@ void launch_reloc_score(hipStream_t s, const void* dst_vol, const VolParams& dv,
 void launch_reloc_gather(hipStream_t s, const float* vmap, const float* nmap, unsigned P, unsigned stride, unsigned np, unsigned pitch,
                          float* soa);
 
+// scan coverage (cover.hip).  rays: the probe's rays (hsk_cover_point.h: CoverProbe) under each of n_poses
+// poses (12 floats each: R row-major, then t) add their classes and gain to scores[pose] -- ZEROED by the caller -- and store the
+// pose's eye_state; with any of cls / depth / gain (W x H each, n_poses == 1) the rays' own values too.  census: the counts of
+// the box a CoverSweep describes (cover_sweep: inside the grid, not empty) -> out10 = hsk_coverage's ten words; partial:
+// cover_census_blocks x 10 words of scratch.
+struct hsk_view_score;
+struct CoverProbe;
+struct CoverSweep {
+  int X, Y, Z;                       // the grid (a whole volume: every plane stored)
+  int c0, ncols, by0, nby, bz0, nbz;  // the sweep: vector columns [c0, c0 + ncols), brick rows and brick layers likewise
+  int lo[3], hi[3];                  // the box
+};
+void launch_cover_rays(hipStream_t s, const void* vol, const VolParams& vp, const CoverProbe& pr, const float* poses12, unsigned n_poses,
+                       hsk_view_score* scores, unsigned char* cls, unsigned short* depth, unsigned short* gain);
+CoverSweep cover_sweep(const VolParams& vp, const int lo[3], const int hi[3]);
+unsigned cover_census_blocks(const CoverSweep& g);
+void launch_cover_census(hipStream_t s, const void* vol, const CoverSweep& g, unsigned long long* partial, unsigned long long* out10);
+int cover_warm();     // loads cover.hip's code object (hsk_prepare_readout); a hipError_t
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the

@@ -327,10 +327,7 @@ extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
   for (int a = 0; a < 3; ++a) vp.icell[a] = 1.0 / (double)vp.cell[a];
   vp.stream_nt = 0;  // decided below, once the stored plane count is known
   vp.zchunk = 8;  // (decided below as well)
-  float m = vp.cell[0] > vp.cell[1] ? vp.cell[0] : vp.cell[1];
-  m = m > vp.cell[2] ? m : vp.cell[2];
-  const float lo = 2.1f * m;
-  vp.tau = c->trunc_dist_m > lo ? c->trunc_dist_m : lo;
+  vp.tau = config_tau(c);
   vp.tau_inv = 1.0f / vp.tau;
   for (int l = 0; l < HSK_NLEVELS; ++l) {
     const float s = (float)(1 << l);

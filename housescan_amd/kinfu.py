@@ -67,6 +67,34 @@ SCORE_DTYPE = np.dtype([("n_near", "<u4"), ("n_free", "<u4"), ("n_behind", "<u4"
 PLANE_DTYPE = np.dtype([("abcd", "<f4", (4,)), ("n_inliers", "<u4"), ("pad", "<u4"), ("sum_abs", "<u8")])     # hsk_plane_record
 
 
+VIEW_SCORE_DTYPE = np.dtype([("n_hit", "<u4"), ("n_frontier", "<u4"), ("n_open", "<u4"), ("n_blind", "<u4"), ("n_outside", "<u4"),
+                             ("eye_state", "<u4"), ("gain", "<u8")])     # hsk_view_score
+PROBE_FIELDS = ("width", "height", "fx", "fy", "cx", "cy", "near_m", "far_m", "step_m")
+
+
+def default_probe(tracker=None, **fields):
+    """the probe of the coverage calls (hsk_default_probe): the tracker's camera at a quarter of its resolution, near_m 0.4,
+    far_m 3.5, step_m half its truncation distance (without a tracker: the default configuration's); the keywords -- width,
+    height, fx, fy, cx, cy, near_m, far_m, step_m -- override its fields -> an `_lib.HskProbe`"""
+    p = _lib.HskProbe()
+    _lib.load().hsk_default_probe(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in PROBE_FIELDS:
+            raise TypeError(f"a probe has no field {name!r}")
+        setattr(p, name, val)
+    return p
+
+
+def rank_views(scores):
+    """the order of a score_views result: larger gain first; ties to the larger n_frontier, then to the lower index; the poses
+    whose eye_state is not 0 (free) behind all others (hsk_rank_views; host only) -> indices [n] uint32"""
+    s = np.ascontiguousarray(scores, VIEW_SCORE_DTYPE)
+    order = np.empty(len(s), np.uint32)
+    if len(s) and _lib.load().hsk_rank_views(s.ctypes.data_as(C.POINTER(_lib.HskViewScore)), len(s), order.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise KinfuError("rank_views failed")
+    return order
+
+
 def plane_refit(sums10, prev_abcd):
     """one refit of a plane from its inliers' integer moments (hsk_plane_refit; host only): sums10 = count, sums of q (3), sums
     of q_a q_b (xx xy xz yy yz zz) with q = rint(coordinate * 4096) -> (abcd [4] float32, ok)"""
@@ -559,6 +587,57 @@ class KinfuTracker:
         out = np.zeros(len(ps), SCORE_DTYPE)
         self._ck(self.lib.hsk_score_cloud(self.h, pts.ctypes.data if len(pts) else None, len(pts), ps.ctypes.data if len(ps) else None, len(ps),
                                           out.ctypes.data_as(C.POINTER(_lib.HskPoseScore)) if len(ps) else None))
+        return out
+
+    # ---- scan coverage ----------------------------------------------------------------------------------
+    def _probe(self, probe, fields):
+        if probe is None:
+            return default_probe(self, **fields)
+        p = _lib.HskProbe.from_buffer_copy(probe)
+        for name, val in fields.items():
+            if name not in PROBE_FIELDS:
+                raise TypeError(f"a probe has no field {name!r}")
+            setattr(p, name, val)
+        return p
+
+    def coverage(self, box=None):
+        """the census of the volume's observation state (hsk_coverage_census) over the voxels lo <= (x, y, z) < hi of
+        box = (lo, hi), None: the whole volume -> dict: n_unseen, n_free, n_solid, n_frontier (ints) and faces [6] uint64, the
+        (free voxel, unseen neighbour) pairs by direction -x, +x, -y, +y, -z, +z; legal with frames in flight"""
+        b = None
+        if box is not None:
+            b = _lib.HskVoxelBox()
+            b.lo[:] = [int(v) for v in box[0]]
+            b.hi[:] = [int(v) for v in box[1]]
+        c = _lib.HskCoverage()
+        self._ck(self.lib.hsk_coverage_census(self.h, C.byref(b) if b is not None else None, C.byref(c)))
+        return {"n_unseen": int(c.n_unseen), "n_free": int(c.n_free), "n_solid": int(c.n_solid), "n_frontier": int(c.n_frontier),
+                "faces": np.array(list(c.faces), np.uint64)}
+
+    def score_views(self, poses, probe=None, **probe_fields):
+        """how much never-seen space a camera at each of the poses [m, 4, 4] would reveal (hsk_score_views).  probe: an HskProbe
+        (default: default_probe(self)); the keywords override its fields -> a structured array [m] with VIEW_SCORE_DTYPE: n_hit,
+        n_frontier, n_open, n_blind, n_outside, eye_state (uint32) and gain (uint64); rank it with rank_views"""
+        p = self._probe(probe, probe_fields)
+        ps = self._poses(poses)
+        out = np.zeros(len(ps), VIEW_SCORE_DTYPE)
+        self._ck(self.lib.hsk_score_views(self.h, C.byref(p), ps.ctypes.data if len(ps) else None, len(ps),
+                                          out.ctypes.data_as(C.POINTER(_lib.HskViewScore)) if len(ps) else None))
+        return out
+
+    def render_coverage(self, pose, probe=None, cls=True, depth=True, gain=True, **probe_fields):
+        """the probe's rays from one pose [4, 4], pixel by pixel (hsk_render_coverage) -> dict with the arrays asked for -- cls
+        (h, w) uint8 (0 hit, 1 frontier, 2 open, 3 blind, 4 outside), depth (h, w) uint16: the deciding sample's millimetres, gain
+        (h, w) uint16 -- and score: a VIEW_SCORE_DTYPE record, score_views' for this pose"""
+        p = self._probe(probe, probe_fields)
+        m = np.ascontiguousarray(pose, np.float32).reshape(16)
+        ok = 1 <= p.width <= 4096 and 1 <= p.height <= 4096   # (otherwise the call itself refuses; nothing is allocated for it here)
+        shapes = (("cls", cls, np.uint8), ("depth", depth, np.uint16), ("gain", gain, np.uint16))
+        out = {key: np.empty((p.height, p.width), dt) for key, want, dt in shapes if want and ok}
+        sc = np.zeros(1, VIEW_SCORE_DTYPE)
+        self._ck(self.lib.hsk_render_coverage(self.h, C.byref(p), _fp(m), *(out[key].ctypes.data if key in out else None for key, _, _ in shapes),
+                                              sc.ctypes.data_as(C.POINTER(_lib.HskViewScore))))
+        out["score"] = sc[0]
         return out
 
     def default_reloc_params(self):

@@ -610,6 +610,79 @@ int hsk_score_planes(hsk_ctx* k, const float* xyz, const float* normals, const i
  * length below 1e-12.  HSK_ERR_ARG: a NULL pointer, m < 0 or > 2^24, a sum outside +-2^62. */
 int hsk_plane_refit(const int64_t sums10[10], const float prev_abcd[4], float out_abcd[4], int* ok);
 
+/* ---- Scan coverage: what the volume has never observed, and where the camera should go to see it (DESIGN.md 3.15 the kernels,
+ * 8i the rule; tests/cover_twin.py restates the rule in numpy).  A voxel is UNSEEN when its weight is 0, FREE when it was
+ * observed with a positive TSDF, SOLID when it was observed with a TSDF <= 0.  The host loop: hsk_coverage_census (is anything
+ * open, and on which side) -> hsk_pose_lattice around the current pose -> hsk_score_views -> hsk_rank_views -> show
+ * hsk_render_coverage of the best view to the operator.  Every device sum is an integer: the same bits whatever the launch shape.
+ * The three device calls behave like hsk_render_view: enqueued on hsk_stream() behind every frame submitted so far, waiting
+ * only for their own result, writing nothing the tracker reads -- legal between submit and wait of pipelined frames.  Results
+ * come through the product buffer and the pinned staging pair; nothing is allocated on a later call of the same size
+ * (hsk_prepare_readout covers the first).  HSK_ERR_STATE: a slab of a group, or any context that stores part of its volume
+ * (hsk_render_view's cases). */
+typedef struct hsk_voxel_box {
+  int lo[3], hi[3];       /* the voxels lo <= (x, y, z) < hi                                                                  */
+} hsk_voxel_box;
+typedef struct hsk_coverage {
+  uint64_t n_unseen, n_free, n_solid;   /* the box's voxels by state                                                          */
+  uint64_t n_frontier;    /* FREE voxels of the box with at least one of their six face neighbours UNSEEN; the neighbour lies
+                             inside the grid, it may lie outside the box                                                       */
+  uint64_t faces[6];      /* the pairs (FREE voxel of the box, UNSEEN neighbour) by direction: -x, +x, -y, +y, -z, +z           */
+} hsk_coverage;           /* 80 bytes */
+/* A probe is a virtual depth camera.  Pixel (u, v) looks along (dx, dy, 1), dx = ((float)u - cx) / fx, dy = ((float)v - cy) / fy;
+ * sample i = 0 .. n - 1 of its ray lies at optical-axis depth z = near_m + (float)i * step_m -- a depth sensor's own notion of
+ * range -- at the camera point (dx z, dy z, z); n = min(4096, floor((far_m - near_m) / step_m) + 1) in binary64.  A sample is
+ * INSIDE iff its voxel (floor(p / cell), unclamped) lies in the grid.  The ray walks its samples in order and ends in one class:
+ *   OUTSIDE   no sample was inside
+ *   BLIND     the first inside sample is not FREE: the camera would sit in unknown or solid space
+ *   HIT       after >= 1 FREE sample, the first non-FREE inside sample is SOLID
+ *   FRONTIER  ... is UNSEEN; the ray goes on, and its gain is the number of UNSEEN inside samples from that one onward, up to
+ *             the first SOLID sample, the first outside sample or the last sample
+ *   OPEN      every inside sample is FREE, up to the last sample or to the first outside sample behind an inside one
+ * The deciding sample of a HIT or FRONTIER ray is that first non-FREE one; its depth is rint(z * 1000) millimetres when within
+ * 1..65535, else 0 (and 0 for the other classes).
+ * step_m: keep it at or below half the truncation distance (the default).  The band of SOLID voxels behind a surface is one
+ * truncation distance thick; a longer step can carry a ray from FREE straight into the UNSEEN space behind a wall and report a
+ * frontier that is not there. */
+typedef struct hsk_probe {
+  int width, height;      /* 1..4096 each                                                                                      */
+  float fx, fy, cx, cy;   /* fx, fy finite and positive                                                                        */
+  float near_m, far_m;    /* 0 <= near_m <= far_m, finite                                                                      */
+  float step_m;           /* finite and positive                                                                               */
+} hsk_probe;
+#define HSK_RAY_HIT 0
+#define HSK_RAY_FRONTIER 1
+#define HSK_RAY_OPEN 2
+#define HSK_RAY_BLIND 3
+#define HSK_RAY_OUTSIDE 4
+#define HSK_EYE_FREE 0
+#define HSK_EYE_UNSEEN 1
+#define HSK_EYE_SOLID 2
+#define HSK_EYE_OUTSIDE 3
+typedef struct hsk_view_score {
+  uint32_t n_hit, n_frontier, n_open, n_blind, n_outside;   /* the rays by class: they sum to width * height                  */
+  uint32_t eye_state;     /* HSK_EYE_*: the voxel that holds the camera centre (OUTSIDE: none does)                            */
+  uint64_t gain;          /* the sum of the rays' gains                                                                        */
+} hsk_view_score;         /* 32 bytes */
+#define HSK_COVER_MAX_POSES ((size_t)65536)
+/* the context's camera at a quarter of its resolution (pyramid level 2), near_m = 0.4, far_m = 3.5, step_m = half the context's
+ * truncation distance; k NULL: hsk_default_config(256)'s camera and truncation distance */
+void hsk_default_probe(const hsk_ctx* k, hsk_probe* p);
+/* The census of the box (NULL: the whole volume).  HSK_ERR_ARG (out untouched): a NULL context or out; lo < 0, hi > the volume's
+ * dims or hi < lo on an axis.  An empty box (hi == lo on an axis) is legal and counts nothing. */
+int hsk_coverage_census(hsk_ctx* k, const hsk_voxel_box* box, hsk_coverage* out);
+/* One hsk_view_score per pose (n_poses matrices of 16 floats, row-major, camera -> world; at most 65536) for the probe (NULL:
+ * hsk_default_probe's).  n_poses = 0: HSK_OK.  HSK_ERR_ARG (out untouched): a NULL context, poses or out; a probe field outside
+ * its range; more than 65536 poses; a pose hsk_invert_rigid refuses (the message names its index). */
+int hsk_score_views(hsk_ctx* k, const hsk_probe* probe, const float* poses, size_t n_poses, hsk_view_score* out);
+/* One pose, per pixel (row-major, any of the three may be NULL): cls = HSK_RAY_*, depth_mm of the deciding sample, gain (saturated
+ * at 65535); score (may be NULL): what hsk_score_views gives for this pose.  Errors as hsk_score_views'. */
+int hsk_render_coverage(hsk_ctx* k, const hsk_probe* probe, const float pose[16], uint8_t* cls /* w*h */, uint16_t* depth_mm /* w*h */,
+                        uint16_t* gain /* w*h */, hsk_view_score* score);
+/* host only: order[0..n) = the indices by larger gain first; ties to the larger n_frontier, then to the lower index; the poses
+ * whose eye_state is not HSK_EYE_FREE -- viewpoints nobody can stand in -- behind all others, in the same order among themselves */
+int hsk_rank_views(const hsk_view_score* s, size_t n, uint32_t* order);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
