@@ -218,6 +218,39 @@ class HskViewScore(C.Structure):
     ]
 
 
+HSK_COMPONENT_NONE = 0xFFFFFFFF
+HSK_COMPONENT_MAX = 1 << 24
+HSK_PRUNE_UNSEEN, HSK_PRUNE_FREE = 0, 1
+
+
+class HskComponent(C.Structure):
+    """Mirror of `hsk_component` (include/hskinfu.h): 48 bytes."""
+
+    _fields_ = [
+        ("root", C.c_int32 * 3), ("pad", C.c_int32),
+        ("n_voxels", C.c_uint64),
+        ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+    ]
+
+
+class HskComponentStats(C.Structure):
+    """Mirror of `hsk_component_stats` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [("n_components", C.c_uint64), ("n_inside", C.c_uint64), ("largest", C.c_uint64), ("labels_reused", C.c_int32), ("pad", C.c_int32)]
+
+
+class HskPruneParams(C.Structure):
+    """Mirror of `hsk_prune_params` (include/hskinfu.h): 16 bytes."""
+
+    _fields_ = [("min_voxels", C.c_uint64), ("keep_largest", C.c_int32), ("fill", C.c_int32)]
+
+
+class HskPruneStats(C.Structure):
+    """Mirror of `hsk_prune_stats` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [("n_components", C.c_uint64), ("n_pruned", C.c_uint64), ("n_pruned_voxels", C.c_uint64), ("n_kept_voxels", C.c_uint64)]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -325,6 +358,10 @@ SYMBOLS = {
     "hsk_score_views": (C.c_int, [_P, C.POINTER(HskProbe), _P, C.c_size_t, C.POINTER(HskViewScore)]),
     "hsk_render_coverage": (C.c_int, [_P, C.POINTER(HskProbe), _F, _P, _P, _P, C.POINTER(HskViewScore)]),
     "hsk_rank_views": (C.c_int, [C.POINTER(HskViewScore), C.c_size_t, C.POINTER(C.c_uint32)]),
+    "hsk_default_prune_params": (None, [_P, C.POINTER(HskPruneParams)]),
+    "hsk_label_components": (C.c_int, [_P, C.POINTER(HskComponent), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskComponentStats)]),
+    "hsk_download_components": (C.c_int, [_P, _P]),
+    "hsk_prune_components": (C.c_int, [_P, C.POINTER(HskPruneParams), C.POINTER(HskPruneStats)]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

@@ -22,9 +22,8 @@ static int stage_in(hsk_ctx* k, int* turn, const void* from, size_t bytes, size_
   }
   return HSK_OK;
 }
-// The volume's content was replaced: the brick bitfield and both summary levels are made again from the volume as it now is,
-// behind whatever wrote it on the stream.  Enqueues only; the caller synchronises.
-static int volume_replaced(hsk_ctx* k) {
+// (hsk_ctx.h: the brick bitfield and both summary levels made again behind whatever wrote the volume)
+int volume_replaced(hsk_ctx* k) {
   k->vol_epoch += 1;
   HIPCHK(k, hipMemsetAsync(k->d_flags, 0, k->flags_bytes, k->stream));
   launch_rebuild_flags(k->stream, k->d_vol, k->vp, k->d_flags);

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
@@ -161,6 +162,18 @@ struct hsk_ctx {
   uint64_t pk_epoch = 0;
   bool pk_color = false;
   unsigned pk_counts[16] = {};
+  // surface components (hsk_label_components; components.hip), made on first use and only grown:
+  // d_comp = 64 B of counters, the rows' root counts / offsets and their scan's block sums, then one parent per volume word
+  // (comp_layout); d_comp_tab = the roots in ascending order, then eight words per component (count, lo, hi), then the
+  // survivors of a keep_largest prune.  What they hold is the labelling of the volume at comp_epoch (0: nothing), and
+  // comp_recs its records in their order
+  void* d_comp = nullptr;
+  size_t comp_bytes = 0;
+  void* d_comp_tab = nullptr;
+  size_t comp_tab_bytes = 0;
+  uint64_t comp_epoch = 0;
+  uint64_t comp_inside = 0;  // the voxels of all components
+  std::vector<hsk_component> comp_recs;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -204,6 +217,10 @@ int require_idle(const hsk_ctx* k, hsk_ctx* errs);
 inline int require_idle(hsk_ctx* k) { return require_idle(k, k); }
 int require_color(hsk_ctx* k);
 int require_whole_volume(const hsk_ctx* k, hsk_ctx* errs, const char* who, const char* sentence = "a context that stores part of its volume");
+// ---- api_volume.hip ----
+// The volume's content was replaced: the brick bitfield and both summary levels are made again from the volume as it now is,
+// behind whatever wrote it on the stream.  Enqueues only; the caller synchronises.
+int volume_replaced(hsk_ctx* k);
 // ---- products.cpp ----
 uint32_t plane_lcg_next(uint64_t* state);  // hsk_detect_planes' generator: one step, the state in place
 // ---- api_align.hip ----

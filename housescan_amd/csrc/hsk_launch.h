@@ -136,6 +136,27 @@ unsigned cover_census_blocks(const CoverSweep& g);
 void launch_cover_census(hipStream_t s, const void* vol, const CoverSweep& g, unsigned long long* partial, unsigned long long* out10);
 int cover_warm();     // loads cover.hip's code object (hsk_prepare_readout); a hipError_t
 
+// surface components (components.hip) of a WHOLE volume.  The scratch, carved out of one device buffer by
+// comp_layout: `rows` = one word per grid row (y, z) and one more, the rows' root counts, then -- launch_pack_scan in place -- their
+// first root's index; `parent` = one word per volume word, a voxel's at the voxel's own place (hsk_vox_index).
+struct CompBufs {
+  unsigned* counts;   // 16 words: [0..7] launch_pack_scan's ([4]: the roots)
+  unsigned* rows;     // Y * Z + 1 words
+  unsigned* bsum;     // the scan's block sums
+  unsigned* parent;   // hsk_vol_words
+};
+size_t comp_layout(const VolParams& vp, void* base /* null: the size only */, CompBufs* b);
+// label: parent[v] = the root of v's component for every INSIDE voxel, 0xFFFFFFFF elsewhere; rows' counts -> offsets; the number
+// of roots in counts[4]
+void launch_comp_label(hipStream_t s, const void* vol, const VolParams& vp, const CompBufs& b);
+// behind it, with n > 0 roots: roots[0, n) ascending; table: 8 words per root -- voxels, lo (3), hi (3, exclusive), 0
+void launch_comp_records(hipStream_t s, const VolParams& vp, const CompBufs& b, unsigned n, unsigned* roots, unsigned* table);
+// the voxels of the components with fewer than min_voxels voxels or -- n_keep > 0 -- whose root is not among keep[0, n_keep)
+// (ascending) get the fill word (fill_free: the weight kept, the TSDF +1; else 0) and the colour word 0 (col may be null)
+void launch_comp_prune(hipStream_t s, void* vol, unsigned* col, const VolParams& vp, const unsigned* parent, const unsigned* roots,
+                       const unsigned* table, unsigned n, unsigned min_voxels, const unsigned* keep, unsigned n_keep, bool fill_free);
+int comp_warm();      // loads components.hip's code object (hsk_prepare_readout); a hipError_t
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the

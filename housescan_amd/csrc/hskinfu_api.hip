@@ -155,6 +155,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_fuse);
   F(k->d_pack);
   F(k->d_align);
+  F(k->d_comp);
+  F(k->d_comp_tab);
   if (k->h_align) (void)hipHostFree(k->h_align);
   if (k->h_view) (void)hipHostFree(k->h_view);
   for (auto& b : k->ib) F(b.d_rgb);

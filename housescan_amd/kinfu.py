@@ -85,6 +85,25 @@ def default_probe(tracker=None, **fields):
     return p
 
 
+COMPONENT_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])     # hsk_component
+COMPONENT_NONE = 0xFFFFFFFF
+PRUNE_UNSEEN, PRUNE_FREE = 0, 1
+PRUNE_FIELDS = ("min_voxels", "keep_largest", "fill")
+
+
+def default_prune_params(tracker=None, **fields):
+    """the parameters of prune_components (hsk_default_prune_params): min_voxels = the voxels of a cube of edge four truncation
+    distances of the tracker (without one: the default configuration's), keep_largest 0 (no limit), fill PRUNE_UNSEEN; the
+    keywords -- min_voxels, keep_largest, fill -- override its fields -> an `_lib.HskPruneParams`"""
+    p = _lib.HskPruneParams()
+    _lib.load().hsk_default_prune_params(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in PRUNE_FIELDS:
+            raise TypeError(f"prune parameters have no field {name!r}")
+        setattr(p, name, val)
+    return p
+
+
 def rank_views(scores):
     """the order of a score_views result: larger gain first; ties to the larger n_frontier, then to the lower index; the poses
     whose eye_state is not 0 (free) behind all others (hsk_rank_views; host only) -> indices [n] uint32"""
@@ -639,6 +658,47 @@ class KinfuTracker:
                                               sc.ctypes.data_as(C.POINTER(_lib.HskViewScore))))
         out["score"] = sc[0]
         return out
+
+    # ---- surface components ----------------------------------------------------------------------------
+    def label_components(self):
+        """the connected components of the volume's inside voxels (observed, TSDF < 0; 6-neighbourhood), labelled on the device
+        (hsk_label_components) -> (records, stats): a structured array with COMPONENT_DTYPE -- root (x, y, z), n_voxels, the box
+        lo, hi (exclusive) -- ordered by n_voxels descending, ties to the smaller root; stats: n_components, n_inside, largest,
+        labels_reused (the labelling of an earlier call was still valid).  Not with frames in flight"""
+        n = C.c_size_t(0)
+        st = _lib.HskComponentStats()
+        self._ck(self.lib.hsk_label_components(self.h, None, 0, C.byref(n), C.byref(st)))
+        recs = np.zeros(n.value, COMPONENT_DTYPE)
+        if n.value:   # (the fill finds the labelling of the size query: labels_reused is the size query's)
+            self._ck(self.lib.hsk_label_components(self.h, recs.ctypes.data_as(C.POINTER(_lib.HskComponent)), n.value, C.byref(n), None))
+        return recs, {"n_components": int(st.n_components), "n_inside": int(st.n_inside), "largest": int(st.largest),
+                      "labels_reused": int(st.labels_reused)}
+
+    def download_components(self):
+        """the dense label volume [vol_z, vol_y, vol_x] uint32 (hsk_download_components): an inside voxel's label is the smallest
+        (z vol_y + y) vol_x + x of its component, every other voxel's COMPONENT_NONE"""
+        out = np.empty((self.cfg.vol_z, self.cfg.vol_y, self.cfg.vol_x), np.uint32)
+        self._ck(self.lib.hsk_download_components(self.h, out.ctypes.data))
+        return out
+
+    def default_prune_params(self):
+        return default_prune_params(self)
+
+    def prune_components(self, params=None, **fields):
+        """erases the components that are too small (hsk_prune_components): those with fewer than min_voxels voxels and, with
+        keep_largest > 0, those of rank >= keep_largest; their voxels become never observed (fill = PRUNE_UNSEEN, the default)
+        or observed free space (PRUNE_FREE), their colour 0; every other word stays bit for bit.  params: an HskPruneParams
+        (default: default_prune_params(self)); the keywords override its fields -> dict: n_components, n_pruned,
+        n_pruned_voxels, n_kept_voxels"""
+        p = default_prune_params(self) if params is None else _lib.HskPruneParams.from_buffer_copy(params)
+        for name, val in fields.items():
+            if name not in PRUNE_FIELDS:
+                raise TypeError(f"prune parameters have no field {name!r}")
+            setattr(p, name, val)
+        st = _lib.HskPruneStats()
+        self._ck(self.lib.hsk_prune_components(self.h, C.byref(p), C.byref(st)))
+        return {"n_components": int(st.n_components), "n_pruned": int(st.n_pruned), "n_pruned_voxels": int(st.n_pruned_voxels),
+                "n_kept_voxels": int(st.n_kept_voxels)}
 
     def default_reloc_params(self):
         p = _lib.HskRelocParams()

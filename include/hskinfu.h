@@ -683,6 +683,63 @@ int hsk_render_coverage(hsk_ctx* k, const hsk_probe* probe, const float pose[16]
  * whose eye_state is not HSK_EYE_FREE -- viewpoints nobody can stand in -- behind all others, in the same order among themselves */
 int hsk_rank_views(const hsk_view_score* s, size_t n, uint32_t* order);
 
+/* ---- Surface components: the volume's pieces, labelled on the device, and the call that erases the small ones (DESIGN.md 3.16
+ * the kernels, 8j the rule; tests/components_twin.py restates the rule in numpy).  All integers.  A voxel is INSIDE when it was
+ * observed (weight != 0) with a NEGATIVE TSDF -- the voxels that can be the negative end of a zero crossing, so everything the
+ * read-outs show hangs on one of them (not the coverage rule's SOLID, which also takes a TSDF of 0).  Two INSIDE voxels are
+ * adjacent when they differ by 1 on exactly one axis (6-neighbourhood; diagonal contact does not connect: the band behind a
+ * surface is at least 2.1 cells thick, so a surface is 6-connected).  With lin(x, y, z) = (z vol_y + y) vol_x + x, the label of an
+ * INSIDE voxel is the smallest lin of its component (its root), that of every other voxel HSK_COMPONENT_NONE: integers that no
+ * schedule can change.  Records are ordered by n_voxels descending, ties to the smaller root; a component's rank is its place
+ * in that order.  No flush of the deferred weights is needed to label (no deferred weight is 0 in the volume's own copy, and
+ * TSDF values are always current); the labelling stays on the device and is reused until the volume changes.  Its scratch --
+ * one 32-bit parent per stored voxel, as large as the volume itself -- is made by the first call that labels, NOT by
+ * hsk_prepare_readout (which only loads the kernels): a context that never labels does not pay for it.
+ * HSK_ERR_STATE: frames in flight, a slab of a group, or any context that stores part of its volume.  HSK_ERR_ARG: a NULL
+ * context or output, a volume of more than 2^31 voxels, and what each call lists.  A refused call writes nothing. */
+#define HSK_COMPONENT_NONE 0xffffffffu
+#define HSK_COMPONENT_MAX ((size_t)1 << 24)
+typedef struct hsk_component {
+  int32_t root[3];        /* x, y, z of the root                                                                                */
+  int32_t pad;
+  uint64_t n_voxels;
+  int32_t lo[3], hi[3];   /* the voxel bounding box, hi exclusive                                                               */
+} hsk_component;          /* 48 bytes */
+typedef struct hsk_component_stats {
+  uint64_t n_components, n_inside, largest;   /* the components, their voxels, the voxels of the first record                  */
+  int32_t labels_reused;  /* 1: the labelling of an earlier call was still valid                                                */
+  int32_t pad;
+} hsk_component_stats;    /* 32 bytes */
+#define HSK_PRUNE_UNSEEN 0   /* a pruned voxel becomes word 0: never observed                                                   */
+#define HSK_PRUNE_FREE 1     /* ... becomes (weight << 16) | 0x7fff: observed free space, its weight kept                       */
+typedef struct hsk_prune_params {
+  uint64_t min_voxels;    /* a component with fewer voxels is pruned                                                            */
+  int32_t keep_largest;   /* > 0: so is every component of rank >= keep_largest; 0: no limit; at most 4096                     */
+  int32_t fill;           /* HSK_PRUNE_UNSEEN (the default: a pruned blob may have been a real small object, and "never
+                             observed" is the honest state -- the coverage census then shows a frontier round it) or HSK_PRUNE_FREE */
+} hsk_prune_params;       /* 16 bytes */
+typedef struct hsk_prune_stats {
+  uint64_t n_components, n_pruned, n_pruned_voxels, n_kept_voxels;
+} hsk_prune_stats;        /* 32 bytes */
+/* min_voxels = the voxels of a cube of edge 4 tau, ceil((4 tau)^3 / (cell_x cell_y cell_z)) computed in binary64 from the
+ * context's binary32 truncation distance and cells (k NULL: hsk_default_config(256)'s): anything whose inside is smaller than a
+ * 12 cm cube at the default tau of 3 cm.  A stated choice, not a measurement -- set another value where it does not fit.
+ * keep_largest = 0, fill = HSK_PRUNE_UNSEEN. */
+void hsk_default_prune_params(const hsk_ctx* k, hsk_prune_params* p);
+/* Labels the volume (or finds the labelling of an earlier call still valid) and gives the records in their order.  recs NULL:
+ * the counts only (*n_components, stats).  HSK_ERR_ARG with *n_components and stats set and no record written: cap below the
+ * count; more than 2^24 components (a volume of noise; hsk_prune_components shares the limit; such a labelling is not kept:
+ * every call labels again).  stats may be NULL. */
+int hsk_label_components(hsk_ctx* k, hsk_component* recs, size_t cap, size_t* n_components, hsk_component_stats* stats);
+/* the dense label volume: vol_x * vol_y * vol_z labels, row-major, x fastest; labels first when no valid labelling is held */
+int hsk_download_components(hsk_ctx* k, uint32_t* labels);
+/* Prunes the components with n_voxels < min_voxels or, with keep_largest > 0, of rank >= keep_largest (params NULL: the
+ * defaults): every voxel of theirs gets the fill word and, where the context has colour, the colour word 0.  Every other word of
+ * the volume and of the colour volume stays as it is bit for bit (the deferred weights written back).  When nothing is pruned
+ * nothing is written and cached passes stay valid.  The pose and the model maps are not touched (as by hsk_unpack_volume): a
+ * scan may go on.  stats may be NULL.  HSK_ERR_ARG: keep_largest outside 0..4096, an unknown fill. */
+int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, hsk_prune_stats* stats);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
