@@ -251,6 +251,23 @@ class HskPruneStats(C.Structure):
     _fields_ = [("n_components", C.c_uint64), ("n_pruned", C.c_uint64), ("n_pruned_voxels", C.c_uint64), ("n_kept_voxels", C.c_uint64)]
 
 
+HSK_SIMPLIFY_QUADRIC, HSK_SIMPLIFY_MEAN = 0, 1
+
+
+class HskSimplifyParams(C.Structure):
+    """Mirror of `hsk_simplify_params` (include/hskinfu.h): 12 bytes."""
+
+    _fields_ = [("cluster_voxels", C.c_int32), ("mode", C.c_int32), ("sv_floor", C.c_float)]
+
+
+class HskSimplifyStats(C.Structure):
+    """Mirror of `hsk_simplify_stats` (include/hskinfu.h): 96 bytes."""
+
+    _fields_ = [("n_in_vertices", C.c_uint64), ("n_in_faces", C.c_uint64), ("n_clusters", C.c_uint64), ("n_out_vertices", C.c_uint64),
+                ("n_out_faces", C.c_uint64), ("n_faces_collapsed", C.c_uint64), ("n_rank", C.c_uint64 * 4), ("n_clamped", C.c_uint64),
+                ("n_uncolored", C.c_uint64)]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -319,6 +336,10 @@ SYMBOLS = {
     "hsk_extract_cloud_attrs": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_extract_mesh_indexed": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t),
                                             C.POINTER(C.c_size_t)]),
+    "hsk_default_simplify_params": (None, [_P, C.POINTER(HskSimplifyParams)]),
+    "hsk_extract_mesh_simplified": (C.c_int, [_P, C.POINTER(HskSimplifyParams), _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t,
+                                               C.POINTER(C.c_size_t), C.POINTER(HskSimplifyStats)]),
+    "hsk_cluster_vertex": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_float, _D, _I, _I]),
     "hsk_default_view": (None, [_P, C.POINTER(HskView)]),
     "hsk_render_view": (C.c_int, [_P, C.POINTER(HskView), _P, _P, _P, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_default_section": (None, [_P, C.POINTER(HskSection)]),

@@ -43,7 +43,7 @@ static int comp_state_check(hsk_ctx* k, const char* who) {
   return HSK_OK;
 }
 
-static int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want) {
+int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want) {
   if (*have >= want) return HSK_OK;
   if (*buf) HIPCHK(k, hipFree(*buf));
   *buf = nullptr;

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(1024) void k_scan_rows_fill(const unsigned* __restr
 }
 // (row_offset has room for its n entries and, behind them, the per-block sums: hsk_scan_scratch_entries)
 size_t hsk_scan_scratch_entries(int nrows) { return (size_t)nrows + (size_t)(nrows + 1023) / 1024; }
-static void launch_scan_rows(hipStream_t s, const unsigned* cnt, unsigned long long* off, int n, unsigned long long* total) {
+void launch_scan_rows(hipStream_t s, const unsigned* cnt, unsigned long long* off, int n, unsigned long long* total) {
   const int nb = (n + 1023) / 1024;
   unsigned long long* bsum = off + n;
   hipLaunchKernelGGL(k_scan_rows_sum, dim3(nb), dim3(1024), 0, s, cnt, n, bsum);

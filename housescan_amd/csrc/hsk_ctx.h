@@ -174,6 +174,19 @@ struct hsk_ctx {
   uint64_t comp_epoch = 0;
   uint64_t comp_inside = 0;  // the voxels of all components
   std::vector<hsk_component> comp_recs;
+  // the simplified mesh (hsk_extract_mesh_simplified; simplify.hip), made on first use and only grown: d_simp = the fixed scratch
+  // of the cluster size asked for (simp_layout: a byte per cluster of the grid, the cluster rows' and the cube rows' tables);
+  // d_simp_out = what is proportional to the output -- per output vertex its cluster's number and its 20 sums (164 B)
+  // ... and what d_simp holds: the count pass (the cube rows' surviving faces, the cluster bytes and rows, their scans) of the
+  // volume at simp_epoch (0: nothing) for clusters of 2^simp_shift voxels, and simp_totals its faces, vertices and clusters --
+  // a size query followed by the fill counts once, as the other products do
+  void* d_simp = nullptr;
+  size_t simp_bytes = 0;
+  uint64_t simp_epoch = 0;
+  int simp_shift = 0;
+  unsigned long long simp_totals[3] = {0, 0, 0};
+  void* d_simp_out = nullptr;
+  size_t simp_out_bytes = 0;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -231,6 +244,8 @@ int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t 
 // ---- api_reloc.hip ----
 // every one of the n_poses matrices (16 floats each) is rigid (hsk_invert_rigid), or HSK_ERR_ARG: "<who>: pose <index> is not rigid ..."
 int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who);
+// ---- api_components.hip ----
+int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want);  // a device buffer of at least `want` bytes, its content not kept
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

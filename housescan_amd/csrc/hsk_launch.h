@@ -246,3 +246,29 @@ void launch_mesh_index_count(hipStream_t s, const void* vol, const VolParams& vp
 void launch_mesh_index_write(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const CubeTable* ct_dev,
                              const unsigned* row_count, const unsigned long long* row_offset, const MeshIndexBufs& mb, float* xyz,
                              float* normals, unsigned char* rgb, unsigned long long* n_uncolored, int* faces, const unsigned* flags);
+// the exclusive scan of n row counts (extract.hip): off[i] = the items before row i, *total their sum; off has room for
+// hsk_scan_scratch_entries(n) entries
+void launch_scan_rows(hipStream_t s, const unsigned* cnt, unsigned long long* off, int n, unsigned long long* total);
+// the simplified mesh (simplify.hip): its fixed scratch for clusters of 2^s voxels, carved out of one device buffer by simp_layout
+struct SimpBufs {
+  int s;                        // log2 of the cluster's edge in voxels
+  int CX, CY, CZ;               // clusters per axis (the last one partial where a dim is no multiple of the edge)
+  int crows, cseg;              // cluster rows CY x CZ; 64-cluster segments per row
+  int frows;                    // cube rows (Y - 1) x (Z - 1): the indexed mesh's face rows
+  unsigned long long* totals;   // [0] faces out, [1] vertices out, [2] clusters that hold a vertex, [4 .. 7] vertices by rank, [8] clamped, [9] uncoloured
+  unsigned char* ref;           // a byte per cluster: referenced by a surviving face; after the rows pass 0x80 | rank in its segment
+  unsigned* cl_cnt;             // cluster rows: referenced clusters
+  unsigned long long* cl_off;   // ... and the row's first output vertex (+ the scan's block sums)
+  unsigned* tc_cnt;             // cluster rows: clusters that hold a vertex
+  unsigned long long* tc_off;
+  unsigned short* segbase;      // cluster rows x cseg: referenced clusters of the row before each segment
+  unsigned* sf_cnt;             // cube rows: surviving faces
+  unsigned long long* sf_off;   // ... and the row's first face (+ the scan's block sums)
+};
+size_t simp_layout(const VolParams& vp, int s, void* base /* null: the size only */, SimpBufs* b);
+void launch_simp_count(hipStream_t s, const void* vol, const VolParams& vp, const CubeTable* ct_dev, const unsigned* tri_count,
+                       const MeshIndexBufs& mb, const SimpBufs& sb);
+void launch_simp_write(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const CubeTable* ct_dev,
+                       const unsigned* tri_count, const MeshIndexBufs& mb, const SimpBufs& sb, unsigned n_out, unsigned* list, long long* sums,
+                       int mode, double floor_rel, float* xyz, float* normals, unsigned char* rgb, int* faces);
+int simplify_warm();

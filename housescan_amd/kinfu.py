@@ -104,6 +104,28 @@ def default_prune_params(tracker=None, **fields):
     return p
 
 
+SIMPLIFY_QUADRIC, SIMPLIFY_MEAN = 0, 1
+SIMPLIFY_STATS_FIELDS = ("n_in_vertices", "n_in_faces", "n_clusters", "n_out_vertices", "n_out_faces", "n_faces_collapsed", "n_rank",
+                         "n_clamped", "n_uncolored")
+
+
+def simplify_stats_dict(st):
+    """an `_lib.HskSimplifyStats` as a dict of ints (n_rank: a list of four)"""
+    return {name: ([int(v) for v in getattr(st, name)] if name == "n_rank" else int(getattr(st, name))) for name in SIMPLIFY_STATS_FIELDS}
+
+
+def cluster_vertex(sums16, cluster_voxels=4, mode=SIMPLIFY_QUADRIC, sv_floor=0.0):
+    """a cluster's representative vertex from its 16 integer sums (hsk_cluster_vertex; host only, the device solve's mirror):
+    n, sum p (3), sum N (3), sum N N^T (xx xy xz yy yz zz), sum N dN (3), positions in 1/256 voxel relative to the centre of the
+    cluster's cell -> (xyz [3] float64 in voxels relative to that centre, rank, clamped)"""
+    s = np.ascontiguousarray(sums16, np.int64).reshape(16)
+    xyz, rank, clamped = np.zeros(3, np.float64), C.c_int(), C.c_int()
+    if _lib.load().hsk_cluster_vertex(s.ctypes.data_as(C.POINTER(C.c_int64)), cluster_voxels, mode, sv_floor,
+                                      xyz.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rank), C.byref(clamped)) != 0:
+        raise KinfuError("cluster_vertex: invalid arguments (n <= 0, a cluster size outside 2, 4, 8, 16, an unknown mode or an sv_floor outside [0, 1))")
+    return xyz, rank.value, bool(clamped.value)
+
+
 def rank_views(scores):
     """the order of a score_views result: larger gain first; ties to the larger n_frontier, then to the lower index; the poses
     whose eye_state is not 0 (free) behind all others (hsk_rank_views; host only) -> indices [n] uint32"""
@@ -445,6 +467,26 @@ class KinfuTracker:
         if (nv.value, nf.value) != (len(verts), len(faces)):
             raise KinfuError("extract_mesh_indexed: the counts changed between the two calls")
         return verts, faces, nrm, col, nu.value
+
+    def extract_mesh_simplified(self, cluster_voxels=4, mode=SIMPLIFY_QUADRIC, normals=True, rgb=False, sv_floor=0.0):
+        """extract_mesh_indexed's surface reduced on the device by quadric vertex clustering on cells of `cluster_voxels` (2, 4, 8
+        or 16) voxels (hsk_extract_mesh_simplified): one vertex per cell, placed by the quadric of the triangles that touch it
+        (mode SIMPLIFY_QUADRIC) or at the mean of its vertices (SIMPLIFY_MEAN); the faces whose corners lie in three different
+        cells -> (vertices [n, 3] float32, faces [m, 3] int32, normals [n, 3] float32 or None, rgb [n, 3] uint8 or None, stats:
+        a dict of hsk_simplify_stats' fields).  rgb=True needs enable_color()."""
+        p = _lib.HskSimplifyParams(cluster_voxels, mode, sv_floor)
+        nv, nf, st = C.c_size_t(), C.c_size_t(), _lib.HskSimplifyStats()
+        self._ck(self.lib.hsk_extract_mesh_simplified(self.h, C.byref(p), None, None, None, 0, C.byref(nv), None, 0, C.byref(nf), C.byref(st)))
+        verts = np.empty((nv.value, 3), np.float32)
+        faces = np.empty((nf.value, 3), np.int32)
+        nrm = np.empty((nv.value, 3), np.float32) if normals else None
+        col = np.empty((nv.value, 3), np.uint8) if rgb else None
+        self._ck(self.lib.hsk_extract_mesh_simplified(self.h, C.byref(p), verts.ctypes.data, None if nrm is None else nrm.ctypes.data,
+                                                      None if col is None else col.ctypes.data, len(verts), C.byref(nv),
+                                                      faces.ctypes.data, len(faces), C.byref(nf), C.byref(st)))
+        if (nv.value, nf.value) != (len(verts), len(faces)):
+            raise KinfuError("extract_mesh_simplified: the counts changed between the two calls")
+        return verts, faces, nrm, col, simplify_stats_dict(st)
 
     # ---- scene views ----------------------------------------------------------------------------------
     def default_view(self):

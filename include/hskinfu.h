@@ -207,6 +207,75 @@ int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices /* 3 per vertex */, flo
                              uint8_t* rgb /* 3 per vertex, may be NULL */, size_t cap_vertices, size_t* n_vertices,
                              int32_t* faces /* 3 per face */, size_t cap_faces, size_t* n_faces, size_t* n_uncolored);
 
+/* ---- Simplified mesh: hsk_extract_mesh_indexed's surface reduced on the device by quadric vertex clustering (Lindstrom's
+ * out-of-core simplification, SIGGRAPH 2000; DESIGN.md 3.17 the kernels, 8k the rule).  The volume is cut into cells of
+ * c = cluster_voxels voxels; all vertices of the indexed mesh whose cube edge STARTS in a cell (the edge's lower corner g, in voxel
+ * indices: cluster (gx / c, gy / c, gz / c) -- an integer identity, not floor of the float position) become one vertex, placed
+ * by the quadric of the triangles that touch the cell; a face survives when its three vertices lie in three different clusters.
+ *   vertices: the clusters that a surviving face references, in ascending cluster order (plane, row, x).  A blob that lies wholly
+ *     inside one cluster yields nothing.  Positions are first quantised to 1/256 voxel -- 256 g off the edge's axis, 256 g +
+ *     (512 |Fa| + D) / (2 D) on it, D = |Fb - Fa| of the two stored int16 values, in integers -- and every sum of a cluster is a
+ *     64-bit integer relative to the centre of its cell: the count n and sum p of its vertices; over the input triangles with a
+ *     vertex in the cluster, each once per cluster, N = (p1 - p0) x (p2 - p0) (twice the area times the normal, towards free
+ *     space), dN = N . p0: sum N, sum N N^T, sum N dN.  |sum N dN| < 2^61.4 at c = 16 (hsk_simplify_point.h states and asserts
+ *     the arithmetic): no cluster size is refused.  The vertex, in binary64 in a fixed order (hsk_cluster_vertex is the same
+ *     text on the host): xbar = sum p / n; HSK_SIMPLIFY_MEAN: x = xbar.  HSK_SIMPLIFY_QUADRIC: A = sum N N^T is diagonalised by
+ *     8 cyclic Jacobi sweeps and x = xbar + sum over the eigenvalues lambda_i > sv_floor * lambda_max of v_i (v_i . (sum N dN -
+ *     A xbar)) / lambda_i; the vertex's rank is the number of eigenvalues kept (1 on a flat wall, 2 on an edge, 3 at a corner).
+ *     x is clamped to the cell grown by one voxel on every side, taken to metres as the soup's vertices are ((voxel + 0.5) *
+ *     cell) and rounded once to float.  With anisotropic cells the error that is minimised is the GRID's (distances measured in
+ *     voxels), not the metric one.
+ *   normals (may be NULL): sum N taken to metric space (each component over its axis's cell), scaled to length 1 in binary64;
+ *     NaN x 3 where sum N = 0.
+ *   rgb (may be NULL; needs hsk_enable_color, HSK_ERR_STATE): per channel (sum + n_c / 2) / n_c over the n_c vertices of the
+ *     cluster that hsk_extract_mesh_indexed's selection rule gives a colour; (0, 0, 0) and one count in n_uncolored where n_c = 0.
+ *   faces: the surviving faces in the indexed mesh's order, corners in its order (the winding stays), as indices into vertices.
+ *     Faces that name the same three clusters are NOT merged: identifying vertices and dropping the faces with a repeated vertex
+ *     commutes with the boundary operator, so a closed input stays closed -- every directed edge (a, b) occurs as often as
+ *     (b, a) -- exactly; merging duplicates would break that count.
+ *   protocol: hsk_extract_mesh_indexed's.  With every array NULL only the counts and stats; any subset of the arrays may be asked
+ *     for; each is written whole or not at all: a cap below its total returns HSK_ERR_ARG with the counts (and the count fields
+ *     of stats) set and nothing written.  No flush of the deferred weights; nothing the tracker reads is written, the volume
+ *     stays bit for bit; enqueued on hsk_stream() behind the frames submitted so far.  The indexed mesh's count pass is shared
+ *     (whichever product asks first pays for it; it is voided by whatever changes the volume), and the clustering's own count
+ *     pass is kept likewise for the cluster size last asked for.  params NULL: the defaults.
+ *   HSK_ERR_ARG: cluster_voxels outside {0, 2, 4, 8, 16}, an unknown mode, an sv_floor that is negative, non-finite or >= 1.
+ *   HSK_ERR_STATE: a slab of a group or any context that stores part of its volume (clusters would straddle the slabs); rgb
+ *     without colour; more than INT32_MAX input vertices.
+ *   memory, made on first use and kept, beside the indexed mesh's: one byte per cluster of the grid, 24 B + 2 B per 64 clusters
+ *     for every cluster row, 12 B per cube row (of the largest cluster grid asked for so far); and 164 B per OUTPUT vertex (its
+ *     cluster's number and 20 sums), grown by a quarter more when it has to grow.  At 512^3: 21.0 MiB at c = 2 (16 MiB of it the
+ *     cluster bytes), 5.4 MiB at c = 4, 3.3 MiB at c = 8, 3.0 MiB at c = 16, and 15.6 MiB per 100 000 output vertices. */
+#define HSK_SIMPLIFY_QUADRIC 0
+#define HSK_SIMPLIFY_MEAN 1
+typedef struct hsk_simplify_params {
+  int32_t cluster_voxels;  /* c: 2, 4, 8 or 16; 0: the default, 4                                                              */
+  int32_t mode;            /* HSK_SIMPLIFY_QUADRIC (the default) or HSK_SIMPLIFY_MEAN                                          */
+  float sv_floor;          /* eigenvalues up to sv_floor * the largest are dropped; 0: the default, 1e-3 (Lindstrom's value)   */
+} hsk_simplify_params;     /* 12 bytes */
+typedef struct hsk_simplify_stats {
+  uint64_t n_in_vertices, n_in_faces;    /* the indexed mesh                                                                   */
+  uint64_t n_clusters;                   /* clusters that hold an input vertex                                                  */
+  uint64_t n_out_vertices, n_out_faces;
+  uint64_t n_faces_collapsed;            /* input faces with two corners in one cluster: n_in_faces - n_out_faces               */
+  uint64_t n_rank[4];                    /* output vertices by the rank of their solve, 0 .. 3 (HSK_SIMPLIFY_MEAN: all rank 0)  */
+  uint64_t n_clamped;                    /* output vertices the clamp moved                                                     */
+  uint64_t n_uncolored;                  /* output vertices without a coloured input vertex (0 without rgb)                     */
+} hsk_simplify_stats;      /* 96 bytes; n_rank, n_clamped and n_uncolored are set by a call that succeeds with n_out_vertices > 0 */
+/* cluster_voxels = 4, mode = HSK_SIMPLIFY_QUADRIC, sv_floor = 1e-3; k may be NULL (the defaults do not depend on the volume) */
+void hsk_default_simplify_params(const hsk_ctx* k, hsk_simplify_params* p);
+int hsk_extract_mesh_simplified(hsk_ctx* k, const hsk_simplify_params* params, float* vertices /* 3 per vertex */,
+                                float* normals /* 3 per vertex, may be NULL */, uint8_t* rgb /* 3 per vertex, may be NULL */,
+                                size_t cap_vertices, size_t* n_vertices, int32_t* faces /* 3 per face */, size_t cap_faces,
+                                size_t* n_faces, hsk_simplify_stats* stats /* may be NULL */);
+/* The host mirror of the device solve, as hsk_plane_refit is for the planes: a cluster's representative vertex from its 16 sums
+ * -- n, sum p (3), sum N (3), sum N N^T (xx, xy, xz, yy, yz, zz), sum N dN (3), positions in 1/256 voxel relative to the centre
+ * of the cluster's cell -- as xyz_voxels relative to that centre, in voxels, with the rank of the solve and whether the clamp
+ * moved it.  Host only, needs no device.  HSK_ERR_ARG: a NULL pointer, n <= 0, or what hsk_extract_mesh_simplified refuses of
+ * cluster_voxels, mode and sv_floor (0: the defaults). */
+int hsk_cluster_vertex(const int64_t sums[16], int cluster_voxels, int mode, float sv_floor, double xyz_voxels[3], int* rank,
+                       int* clamped);
+
 /* ---- Scene views: what has been fused so far, as an image from any camera (upstream's generateImage / generateDepth and its
  * colour view; DESIGN.md 3.8 the kernel, 8b the rule).  One call marches the TSDF from a virtual pinhole camera, shades the
  * hits on the device and hands back small images.  It is enqueued on hsk_stream() behind every frame submitted so far and

@@ -23,6 +23,10 @@ context's positive octant).  house_fused_mesh.ply is one hsk_extract_mesh_indexe
 rooms overlap there is one surface, not two), house_fused_floorplan.ppm one hsk_render_section of it (--floorplan's camera);
 report.json gets a "fused_house" block with the statistics of every fuse and the milliseconds.
 
+--simplify C (with --fuse-house): the fused house's mesh once more, reduced on the GPU by quadric vertex clustering on cells of C
+voxels (2, 4, 8 or 16; hsk_extract_mesh_simplified), as house_fused_mesh_simplified.ply; the "fused_house" block gets its counts,
+statistics and milliseconds beside the full-resolution mesh's.
+
 --refine (with --fuse-house): every room after the first is first registered against the house volume fused so far, starting
 from its stitched .xf (hsk_align_volume: the room's cloud and normals against the house's TSDF), and fused by the refined matrix,
 which is written as <room>.refined.xf; both matrices and every iteration's n_used / rms are printed.  A registration that does
@@ -211,7 +215,7 @@ def floorplan(hsk, trackers, variants, Ms, out, px_per_m=100.0):
             "end_to_end_ms": round(ms, 2)}
 
 
-def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=0.25, refine=False):
+def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=0.25, refine=False, simplify=0):
     """one house volume on the GPU: every room fused into it by its .xf (with `refine`: by the .xf registered against the house
     so far); one mesh and one floor plan of the whole"""
     from housescan_amd import products as P
@@ -258,6 +262,13 @@ def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=
     mesh_ms = 1e3 * (time.perf_counter() - t0)
     P.write_ply_indexed(os.path.join(out, "house_fused_mesh.ply"), P.transform_cloud(verts, np.linalg.inv(T).astype(np.float32)), faces,
                         normals=normals)
+    simplified = None
+    if simplify:
+        t0 = time.perf_counter()
+        sv, sf, sn, _, st = house.extract_mesh_simplified(cluster_voxels=simplify, normals=True, rgb=False)
+        simplified = {"cluster_voxels": simplify, "vertices": int(len(sv)), "faces": int(len(sf)), "ms": round(1e3 * (time.perf_counter() - t0), 2), "stats": st}
+        P.write_ply_indexed(os.path.join(out, "house_fused_mesh_simplified.ply"), P.transform_cloud(sv, np.linalg.inv(T).astype(np.float32)), sf, normals=sn)
+        print(f"fused house: {len(verts)} vertices, {len(faces)} faces; simplified at c = {simplify}: {len(sv)} vertices, {len(sf)} faces")
     t0 = time.perf_counter()
     sec, W, H = house_section(hsk, variants, Ms, px_per_m)
     r = house.render_section(P.section_in_room(sec, np.linalg.inv(T).astype(np.float32)), depth=False)   # (the context sits at T^-1 in the house)
@@ -265,7 +276,7 @@ def fuse_house(hsk, trackers, variants, Ms, out, volume, px_per_m=100.0, margin=
     P.write_ppm(os.path.join(out, "house_fused_floorplan.ppm"), r["rgb"])
     house.close()
     return {"dims": dims, "size_m": [round(x, 6) for x in size], "rooms": rooms, "create_ms": round(make_ms, 2),
-            "mesh": {"vertices": int(len(verts)), "faces": int(len(faces)), "ms": round(mesh_ms, 2)},
+            "mesh": {"vertices": int(len(verts)), "faces": int(len(faces)), "ms": round(mesh_ms, 2)}, "mesh_simplified": simplified,
             "floorplan": {"width": W, "height": H, "hit": r["n_hit"], "cut": r["n_cut"], "ms": round(plan_ms, 2)}}
 
 
@@ -279,6 +290,8 @@ def main():
     ap.add_argument("--floorplan", action="store_true", help="house_floorplan.ppm + house_heights.pgm: a top-down section of the stitched house")
     ap.add_argument("--fuse-house", action="store_true", help="house_fused_mesh.ply + house_fused_floorplan.ppm: the rooms' volumes fused into one house volume on the GPU")
     ap.add_argument("--refine", action="store_true", help="with --fuse-house: register every room after the first against the house fused so far (<room>.refined.xf)")
+    ap.add_argument("--simplify", type=int, default=0, choices=(0, 2, 4, 8, 16), metavar="C",
+                    help="with --fuse-house: house_fused_mesh_simplified.ply, the fused house's mesh clustered on cells of C voxels on the GPU")
     ap.add_argument("--device-planes", action="store_true", help="the rooms' planes from hsk_detect_planes_volume (oriented, on the GPU) instead of the host RANSAC")
     ap.add_argument("--save-volumes", action="store_true", help="<room dir>/volume.hskv behind each scan, the room's context closed; --floorplan / --fuse-house load them one at a time")
     args = ap.parse_args()
@@ -356,7 +369,7 @@ def main():
         report["floorplan"] = floorplan(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out)
     if args.fuse_house:
         report["fused_house"] = fuse_house(hsk, trackers, variants, [hs.room_projection(rid) for rid in rooms], args.out, args.volume,
-                                            refine=args.refine)
+                                            refine=args.refine, simplify=args.simplify)
     trackers.close()
     report["placement_rmse"] = [None if np.isnan(x) else float(x) for x in rm]
     report["house_points"] = int(len(merged))
