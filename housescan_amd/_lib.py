@@ -251,6 +251,24 @@ class HskPruneStats(C.Structure):
     _fields_ = [("n_components", C.c_uint64), ("n_pruned", C.c_uint64), ("n_pruned_voxels", C.c_uint64), ("n_kept_voxels", C.c_uint64)]
 
 
+HSK_CLEAR_UNKNOWN = 1
+HSK_CLEAR_MAX_REACH = 255
+HSK_CLEARANCE_FAR, HSK_CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
+HSK_CLEAR_MAX_POINTS = 1 << 20
+
+
+class HskClearanceParams(C.Structure):
+    """Mirror of `hsk_clearance_params` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [("weight", C.c_uint32 * 3), ("max_d2", C.c_uint32), ("flags", C.c_uint32), ("unit_m", C.c_float)]
+
+
+class HskClearanceStats(C.Structure):
+    """Mirror of `hsk_clearance_stats` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [("n_obstacle", C.c_uint64), ("n_far", C.c_uint64), ("scratch_bytes", C.c_uint64), ("max_d2_seen", C.c_uint32), ("reused", C.c_int32)]
+
+
 HSK_SIMPLIFY_QUADRIC, HSK_SIMPLIFY_MEAN = 0, 1
 
 
@@ -383,6 +401,14 @@ SYMBOLS = {
     "hsk_label_components": (C.c_int, [_P, C.POINTER(HskComponent), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskComponentStats)]),
     "hsk_download_components": (C.c_int, [_P, _P]),
     "hsk_prune_components": (C.c_int, [_P, C.POINTER(HskPruneParams), C.POINTER(HskPruneStats)]),
+    "hsk_default_clearance_params": (None, [_P, C.POINTER(HskClearanceParams)]),
+    "hsk_clearance_d2": (C.c_uint32, [C.POINTER(HskClearanceParams), C.c_float]),
+    "hsk_build_clearance": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskClearanceStats)]),
+    "hsk_download_clearance": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskVoxelBox), _P]),
+    "hsk_clearance_at": (C.c_int, [_P, C.POINTER(HskClearanceParams), _P, C.c_size_t, _P]),
+    "hsk_clearance_floor": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.c_int, C.c_int, C.c_int, _P, C.POINTER(HskClearanceStats)]),
+    "hsk_release_clearance": (C.c_int, [_P]),
+    "hsk_rank_views_clear": (C.c_int, [C.POINTER(HskViewScore), C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

@@ -174,6 +174,14 @@ struct hsk_ctx {
   uint64_t comp_epoch = 0;
   uint64_t comp_inside = 0;  // the voxels of all components
   std::vector<hsk_component> comp_recs;
+  // the clearance field (hsk_build_clearance; clearance.hip), made by the first call that builds and freed by
+  // hsk_release_clearance: d_clear = clear_layout's counters, field and intermediates.  What it holds is the field of the volume
+  // at clear_epoch (0: nothing) for the 20 device-relevant parameter bytes in clear_key, and clear_counts its counters
+  void* d_clear = nullptr;
+  size_t clear_bytes = 0;
+  uint64_t clear_epoch = 0;
+  uint32_t clear_key[5] = {};
+  unsigned long long clear_counts[3] = {0, 0, 0};
   // the simplified mesh (hsk_extract_mesh_simplified; simplify.hip), made on first use and only grown: d_simp = the fixed scratch
   // of the cluster size asked for (simp_layout: a byte per cluster of the grid, the cluster rows' and the cube rows' tables);
   // d_simp_out = what is proportional to the output -- per output vertex its cluster's number and its 20 sums (164 B)

@@ -157,6 +157,27 @@ void launch_comp_prune(hipStream_t s, void* vol, unsigned* col, const VolParams&
                        const unsigned* table, unsigned n, unsigned min_voxels, const unsigned* keep, unsigned n_keep, bool fill_free);
 int comp_warm();      // loads components.hip's code object (hsk_prepare_readout); a hipError_t
 
+// the clearance field (clearance.hip) of a WHOLE volume: what the kernels take of the grid and the parameters
+// (the reaches computed once on the host), and the scratch, carved out of one device buffer by clear_layout -- 2.5 times the
+// volume's bytes: the field and the y pass's sums (uint32 a voxel each), the x pass's distances (uint16), all row-major, x fastest
+struct ClearGeom {
+  unsigned X, Y, Z, Zg, nw;   // the grid; its plane groups; the 64-bit mask words of a row
+  unsigned w[3], R[3];        // the axis weights and reaches
+  unsigned max_d2, flags;
+};
+struct ClearBufs {
+  unsigned long long* stats;  // 8 words: [0] obstacles, [1] FAR voxels, [2] the largest value that is not FAR
+  unsigned* field;
+  unsigned* tmp;
+  unsigned short* dx;
+};
+size_t clear_layout(const VolParams& vp, void* base /* null: the size only */, ClearBufs* b);
+void launch_clear_build(hipStream_t s, const void* vol, const ClearGeom& q, const ClearBufs& b);
+// the floor map of the band lo <= p < hi along `axis`: a, b = two arrays of one word per column; the map ends in a
+void launch_clear_floor(hipStream_t s, const void* vol, const VolParams& vp, const ClearGeom& q, int axis, int lo, int hi, unsigned* a, unsigned* b);
+void launch_clear_gather(hipStream_t s, const unsigned* field, const VolParams& vp, const float* xyz, unsigned n, unsigned* out);
+void launch_clear_box(hipStream_t s, const unsigned* field, const VolParams& vp, const int lo[3], const int hi[3], unsigned* out);  // (not empty)
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the

@@ -104,6 +104,61 @@ def default_prune_params(tracker=None, **fields):
     return p
 
 
+CLEAR_UNKNOWN = 1
+CLEARANCE_FAR, CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
+CLEARANCE_FIELDS = ("weight", "max_d2", "flags", "unit_m")
+
+
+def _clearance_fields(p, fields):
+    for name, val in fields.items():
+        if name not in CLEARANCE_FIELDS:
+            raise TypeError(f"clearance parameters have no field {name!r}")
+        if name == "weight":
+            p.weight[:] = [int(v) for v in val]
+        else:
+            setattr(p, name, val)
+    return p
+
+
+def default_clearance_params(tracker=None, **fields):
+    """the parameters of the clearance calls (hsk_default_clearance_params): flags CLEAR_UNKNOWN; the weights that make the
+    metric the cells' -- (1, 1, 1) with unit_m = the cell for cubic cells, else rint(16 (cell / cell_min)^2) with unit_m =
+    cell_min / 4 -- and max_d2 = one metre (without a tracker: the default configuration's); the keywords -- weight, max_d2,
+    flags, unit_m -- override its fields -> an `_lib.HskClearanceParams`"""
+    p = _lib.HskClearanceParams()
+    _lib.load().hsk_default_clearance_params(tracker.h if tracker is not None else None, C.byref(p))
+    return _clearance_fields(p, fields)
+
+
+def clearance_d2(params, metres):
+    """the squared distance, in the field's units, of a distance in metres: ceil((metres / unit_m)^2), saturating at 0xFFFFFFFF
+    (hsk_clearance_d2; host only)"""
+    return int(_lib.load().hsk_clearance_d2(C.byref(params), float(metres)))
+
+
+def clearance_metres(params, d2):
+    """the field's values as metres: sqrt(d2) * unit_m, inf where the value is CLEARANCE_FAR, nan where CLEARANCE_OUTSIDE"""
+    d = np.asarray(d2, np.uint32)
+    out = np.sqrt(d.astype(np.float64)) * float(params.unit_m)
+    out = np.where(d == CLEARANCE_FAR, np.inf, out)
+    return np.where(d == CLEARANCE_OUTSIDE, np.nan, out)
+
+
+def rank_views_clear(scores, eye_d2, min_d2):
+    """rank_views' order with the poses nobody can stand in behind all others: those whose eye_state is not 0 (free), whose eye_d2
+    -- clearance_at of the camera centres -- is below min_d2 or is CLEARANCE_OUTSIDE (hsk_rank_views_clear; host only) ->
+    indices [n] uint32"""
+    s = np.ascontiguousarray(scores, VIEW_SCORE_DTYPE)
+    d = np.ascontiguousarray(eye_d2, np.uint32).reshape(-1)
+    if len(d) != len(s):
+        raise ValueError("rank_views_clear: one eye_d2 per score")
+    order = np.empty(len(s), np.uint32)
+    if len(s) and _lib.load().hsk_rank_views_clear(s.ctypes.data_as(C.POINTER(_lib.HskViewScore)), d.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   int(min_d2), len(s), order.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise KinfuError("rank_views_clear failed")
+    return order
+
+
 SIMPLIFY_QUADRIC, SIMPLIFY_MEAN = 0, 1
 SIMPLIFY_STATS_FIELDS = ("n_in_vertices", "n_in_faces", "n_clusters", "n_out_vertices", "n_out_faces", "n_faces_collapsed", "n_rank",
                          "n_clamped", "n_uncolored")
@@ -741,6 +796,67 @@ class KinfuTracker:
         self._ck(self.lib.hsk_prune_components(self.h, C.byref(p), C.byref(st)))
         return {"n_components": int(st.n_components), "n_pruned": int(st.n_pruned), "n_pruned_voxels": int(st.n_pruned_voxels),
                 "n_kept_voxels": int(st.n_kept_voxels)}
+
+    # ---- clearance field ---------------------------------------------------------------------------------
+    def default_clearance_params(self, **fields):
+        return default_clearance_params(self, **fields)
+
+    def _clearance(self, params, fields):
+        p = default_clearance_params(self) if params is None else _lib.HskClearanceParams.from_buffer_copy(params)
+        return _clearance_fields(p, fields)
+
+    @staticmethod
+    def _clearance_stats(st):
+        return {"n_obstacle": int(st.n_obstacle), "n_far": int(st.n_far), "scratch_bytes": int(st.scratch_bytes),
+                "max_d2_seen": int(st.max_d2_seen), "reused": int(st.reused)}
+
+    def build_clearance(self, params=None, **fields):
+        """builds the clearance field on the device (hsk_build_clearance): per voxel the exact weighted squared distance, in
+        voxel index differences, to the nearest obstacle -- a solid voxel; with CLEAR_UNKNOWN (the default) also a never-observed
+        one and everything outside the grid -- CLEARANCE_FAR above max_d2.  params: an HskClearanceParams (default:
+        default_clearance_params(self)); the keywords override its fields -> dict: n_obstacle, n_far, scratch_bytes,
+        max_d2_seen, reused (the field of an earlier call was still valid).  Not with frames in flight"""
+        st = _lib.HskClearanceStats()
+        self._ck(self.lib.hsk_build_clearance(self.h, C.byref(self._clearance(params, fields)), C.byref(st)))
+        return self._clearance_stats(st)
+
+    def download_clearance(self, params=None, box=None, **fields):
+        """the field over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_clearance; builds
+        first when no valid field is held) -> [z, y, x] uint32"""
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        b = _lib.HskVoxelBox()
+        b.lo[:] = [int(v) for v in lo]
+        b.hi[:] = [int(v) for v in hi]
+        shape = tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0))
+        out = np.empty(shape, np.uint32)
+        self._ck(self.lib.hsk_download_clearance(self.h, C.byref(self._clearance(params, fields)), C.byref(b) if box is not None else None,
+                                                 out.ctypes.data))
+        return out
+
+    def clearance_at(self, xyz, params=None, **fields):
+        """the field at the voxels of the world points xyz [n, 3] (hsk_clearance_at; at most 2^20) -> [n] uint32, CLEARANCE_OUTSIDE
+        for a point outside the grid or with a NaN"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out = np.empty(len(pts), np.uint32)
+        self._ck(self.lib.hsk_clearance_at(self.h, C.byref(self._clearance(params, fields)), pts.ctypes.data if len(pts) else None, len(pts),
+                                           out.ctypes.data if len(pts) else None))
+        return out
+
+    def clearance_floor(self, axis, lo, hi, params=None, **fields):
+        """the floor map (hsk_clearance_floor): for the up axis (0 x, 1 y, 2 z) and its planes lo <= p < hi a column is an obstacle
+        when any voxel of its band is; the 2-D clearance over the two remaining axes -> (map [v, u] uint32 with u the
+        lower-numbered remaining axis, stats dict)"""
+        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
+        ok = axis in (0, 1, 2)
+        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
+        out = np.empty((nv, nu), np.uint32)
+        st = _lib.HskClearanceStats()
+        self._ck(self.lib.hsk_clearance_floor(self.h, C.byref(self._clearance(params, fields)), int(axis), int(lo), int(hi), out.ctypes.data, C.byref(st)))
+        return out, self._clearance_stats(st)
+
+    def release_clearance(self):
+        """frees the field and its scratch (hsk_release_clearance); the next call that needs it builds again"""
+        self._ck(self.lib.hsk_release_clearance(self.h))
 
     def default_reloc_params(self):
         p = _lib.HskRelocParams()

@@ -809,6 +809,69 @@ int hsk_download_components(hsk_ctx* k, uint32_t* labels);
  * scan may go on.  stats may be NULL.  HSK_ERR_ARG: keep_largest outside 0..4096, an unknown fill. */
 int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, hsk_prune_stats* stats);
 
+/* ---- Clearance field: how much room there is -- the exact distance from every voxel to the nearest obstacle, on the device
+ * (DESIGN.md 3.18 the kernels, 8l the rule; tests/clearance_twin.py restates the rule in numpy).  All integers.  A voxel is an
+ * OBSTACLE when it is the coverage rule's SOLID (observed with a TSDF <= 0); with the flag HSK_CLEAR_UNKNOWN so is every UNSEEN
+ * voxel (weight 0) and everything outside the grid.  The field's value at voxel v is
+ *     D(v) = min over obstacles o of  weight[0] dx^2 + weight[1] dy^2 + weight[2] dz^2      (dx, dy, dz: voxel index differences)
+ * and with HSK_CLEAR_UNKNOWN also over the three border terms weight[k] min(v_k + 1, dim_k - v_k)^2; an obstacle has D = 0; a
+ * D above max_d2, or no obstacle at all, is reported as HSK_CLEARANCE_FAR.  Metres are sqrt(D) * unit_m; the device never reads
+ * unit_m.  The per-axis reach floor(sqrt(max_d2 / weight[k])) (binary64) must not exceed HSK_CLEAR_MAX_REACH = 255 voxels: a
+ * stated choice that bounds every loop of the kernels and keeps every sum below 2^27.
+ * The default weights make the metric that of the cells: (1, 1, 1) with unit_m = the cell when the three cells are bit-equal,
+ * else weight[k] = rint(16 (cell_k / cell_min)^2) (binary64; at most 1024) with unit_m = cell_min / 4.  The rounding of a weight
+ * bends the metric along its axis by at most 1/32 of the weight (a relative error of at most 1/64 in a distance along that axis,
+ * and less than that in any other direction).  max_d2 = min(ceil((1 / unit_m)^2), 255^2 min weight): one metre.
+ * No flush of the deferred weights is needed (the rule asks of a weight only whether it is zero, of the TSDF its sign).  The
+ * field stays on the device and is reused while the volume and the 20 device-relevant parameter bytes (all but unit_m) stand;
+ * its scratch -- 2.5 times the volume's bytes: the uint32 field, one uint32 and one uint16 intermediate per voxel -- is made by
+ * the first call that builds, NOT by hsk_prepare_readout, and freed by hsk_release_clearance or hsk_destroy.  Nothing the tracker
+ * reads is written.  HSK_ERR_STATE: frames in flight, a slab of a group, or any context that stores part of its volume.
+ * HSK_ERR_ARG: a NULL context or output, a weight outside 1..1024, a reach above 255, unknown flag bits, a volume of more than
+ * 2^31 voxels, and what each call lists.  A refused call writes nothing. */
+#define HSK_CLEAR_UNKNOWN 1u
+#define HSK_CLEAR_MAX_REACH 255
+#define HSK_CLEARANCE_FAR 0xffffffffu
+#define HSK_CLEARANCE_OUTSIDE 0xfffffffeu
+#define HSK_CLEAR_MAX_POINTS ((size_t)1 << 20)
+typedef struct hsk_clearance_params {
+  uint32_t weight[3];     /* 1..1024 each                                                                                       */
+  uint32_t max_d2;        /* the largest value reported                                                                         */
+  uint32_t flags;         /* 0 or HSK_CLEAR_UNKNOWN                                                                             */
+  float unit_m;           /* metres = sqrt(d2) * unit_m; host side only                                                         */
+} hsk_clearance_params;   /* 24 bytes */
+typedef struct hsk_clearance_stats {
+  uint64_t n_obstacle;    /* obstacle voxels (of the floor map: obstacle columns)                                               */
+  uint64_t n_far;         /* voxels (columns) reported as HSK_CLEARANCE_FAR                                                     */
+  uint64_t scratch_bytes; /* the device memory the field holds                                                                  */
+  uint32_t max_d2_seen;   /* the largest value that is not HSK_CLEARANCE_FAR (0: none)                                          */
+  int32_t reused;         /* 1: the field of an earlier call was still valid                                                    */
+} hsk_clearance_stats;    /* 32 bytes */
+/* the defaults described above for the context's cells; k NULL: hsk_default_config(256)'s */
+void hsk_default_clearance_params(const hsk_ctx* k, hsk_clearance_params* p);
+/* host only: the d2 of a distance in metres, ceil((metres / unit_m)^2) in binary64, saturating at 0xffffffff; 0 for metres <= 0;
+ * 0xffffffff for a NULL p, a NaN, or a unit_m that is not finite and positive */
+uint32_t hsk_clearance_d2(const hsk_clearance_params* p, float metres);
+/* builds the field (or finds the one of an earlier call still valid; params NULL: the defaults); stats may be NULL */
+int hsk_build_clearance(hsk_ctx* k, const hsk_clearance_params* params, hsk_clearance_stats* stats);
+/* the voxels of the box (NULL: the whole volume), row-major, x fastest; builds first when no valid field is held.  HSK_ERR_ARG:
+ * lo < 0, hi > the volume's dims or hi < lo on an axis.  An empty box writes nothing. */
+int hsk_download_clearance(hsk_ctx* k, const hsk_clearance_params* params, const hsk_voxel_box* box, uint32_t* d2);
+/* the field at the voxels of n <= 2^20 world points (x, y, z triples): the voxel is floor(p / cell), unclamped; a point outside
+ * the grid, or with a NaN, gives HSK_CLEARANCE_OUTSIDE; builds first when no valid field is held */
+int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, const float* xyz, size_t n, uint32_t* d2);
+/* The floor map: for the up axis `axis` (0 x, 1 y, 2 z) and its planes lo <= p < hi, a column is an obstacle when any voxel of
+ * its band is; the map is the same transform in 2-D over the two remaining axes with their weights (border terms on those two
+ * only), one uint32 per column, row-major, the lower-numbered remaining axis fastest.  An empty band (hi == lo) has no obstacle
+ * columns.  Not cached (stats->reused = 0); stats may be NULL.  HSK_ERR_ARG: axis outside 0..2, lo < 0, hi > the axis, hi < lo. */
+int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* params, int axis, int lo, int hi, uint32_t* map, hsk_clearance_stats* stats);
+/* frees the field and its scratch (the next call that needs it builds again); HSK_ERR_ARG: a NULL context */
+int hsk_release_clearance(hsk_ctx* k);
+/* host only: hsk_rank_views' order, with the poses whose eye_state is not HSK_EYE_FREE, whose eye_d2 (hsk_clearance_at of the
+ * camera centres) is below min_d2 or is HSK_CLEARANCE_OUTSIDE behind all others, in the same order among themselves;
+ * HSK_CLEARANCE_FAR counts as clear */
+int hsk_rank_views_clear(const hsk_view_score* s, const uint32_t* eye_d2, uint32_t min_d2, size_t n, uint32_t* order);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
