@@ -269,6 +269,25 @@ class HskClearanceStats(C.Structure):
     _fields_ = [("n_obstacle", C.c_uint64), ("n_far", C.c_uint64), ("scratch_bytes", C.c_uint64), ("max_d2_seen", C.c_uint32), ("reused", C.c_int32)]
 
 
+HSK_REACH_UNREACHED, HSK_REACH_OUTSIDE, HSK_REACH_BLOCKED = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
+HSK_REACH_MAX_COST = 0xF0000000
+HSK_REACH_MAX_SEEDS = 4096
+HSK_REACH_MAX_ROUNDS = 65536
+
+
+class HskReachParams(C.Structure):
+    """Mirror of `hsk_reach_params` (include/hskinfu.h): 16 bytes."""
+
+    _fields_ = [("min_d2", C.c_uint32), ("max_cost", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class HskReachStats(C.Structure):
+    """Mirror of `hsk_reach_stats` (include/hskinfu.h): 40 bytes."""
+
+    _fields_ = [("n_passable", C.c_uint64), ("n_reached", C.c_uint64), ("scratch_bytes", C.c_uint64), ("max_cost_seen", C.c_uint32),
+                ("n_rounds", C.c_uint32), ("n_seeds_used", C.c_uint32), ("reused", C.c_int32)]
+
+
 HSK_SIMPLIFY_QUADRIC, HSK_SIMPLIFY_MEAN = 0, 1
 
 
@@ -409,6 +428,17 @@ SYMBOLS = {
     "hsk_clearance_floor": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.c_int, C.c_int, C.c_int, _P, C.POINTER(HskClearanceStats)]),
     "hsk_release_clearance": (C.c_int, [_P]),
     "hsk_rank_views_clear": (C.c_int, [C.POINTER(HskViewScore), C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "hsk_default_reach_params": (None, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskReachParams)]),
+    "hsk_build_reach": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskReachParams), _P, C.c_size_t, C.POINTER(HskReachStats)]),
+    "hsk_download_reach": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P]),
+    "hsk_reach_at": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "hsk_reach_path": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_reach_floor": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.c_int, C.c_int, C.c_int, C.POINTER(HskReachParams), _P, C.c_size_t, _P,
+                                  C.POINTER(HskReachStats)]),
+    "hsk_release_reach": (C.c_int, [_P]),
+    "hsk_reach_tiles_relaxed": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hsk_rank_views_reach": (C.c_int, [C.POINTER(HskViewScore), C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "hsk_reach_metres": (C.c_float, [C.POINTER(HskClearanceParams), C.c_uint32]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

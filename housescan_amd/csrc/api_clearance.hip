@@ -52,7 +52,7 @@ extern "C" uint32_t hsk_clearance_d2(const hsk_clearance_params* p, float metres
 }
 
 // the parameters a call works with (NULL: the defaults), checked -> the kernels' block
-static int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who, hsk_clearance_params* p, ClearGeom* q) {
+int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who, hsk_clearance_params* p, ClearGeom* q) {
   if (params)
     *p = *params;
   else
@@ -76,7 +76,7 @@ static int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const cha
   return HSK_OK;
 }
 
-static int clear_state_check(hsk_ctx* k, const char* who) {
+int clear_state_check(hsk_ctx* k, const char* who) {
   if (int rs = require_whole_volume(k, k, who)) return rs;
   if (int ri = require_idle(k)) return ri;
   if ((uint64_t)k->vp.X * (uint64_t)k->vp.Y * (uint64_t)k->vp.Z > ((uint64_t)1 << 31))
@@ -84,7 +84,7 @@ static int clear_state_check(hsk_ctx* k, const char* who) {
   return HSK_OK;
 }
 
-static void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
+void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
   key[0] = p.weight[0];
   key[1] = p.weight[1];
   key[2] = p.weight[2];
@@ -93,7 +93,7 @@ static void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
 }
 
 // the field of the volume as it stands for the checked parameters, in d_clear; *reused: nothing had to be launched
-static int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused) {
+int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused) {
   uint32_t key[5];
   clear_key_of(p, key);
   if (k->d_clear && k->clear_epoch != 0 && k->clear_epoch == k->vol_epoch && memcmp(key, k->clear_key, sizeof(key)) == 0) {

@@ -182,6 +182,19 @@ struct hsk_ctx {
   uint64_t clear_epoch = 0;
   uint32_t clear_key[5] = {};
   unsigned long long clear_counts[3] = {0, 0, 0};
+  // the reach field (hsk_build_reach; reach.hip), made by the first build and freed by hsk_release_reach: d_reach = reach_layout's
+  // counters, field, tile flags and worklists.  What it holds is the field of the volume at reach_epoch (0: nothing) for the
+  // clearance key, min_d2 and max_cost in reach_key and the seed voxels in reach_seeds (the seeds inside the grid, in the caller's
+  // order); reach_q its geometry and costs (the path trace's), reach_counts its counters, reach_rounds its rounds
+  void* d_reach = nullptr;
+  size_t reach_bytes = 0;
+  uint64_t reach_epoch = 0;
+  uint32_t reach_key[7] = {};
+  std::vector<uint32_t> reach_seeds;
+  ReachGeom reach_q = {};
+  unsigned long long reach_counts[4] = {0, 0, 0, 0};
+  uint32_t reach_rounds = 0;
+  unsigned long long reach_tiles = 0;  // the tiles relaxed over all rounds of the last hsk_build_reach that built (hsk_reach_tiles_relaxed)
   // the simplified mesh (hsk_extract_mesh_simplified; simplify.hip), made on first use and only grown: d_simp = the fixed scratch
   // of the cluster size asked for (simp_layout: a byte per cluster of the grid, the cluster rows' and the cube rows' tables);
   // d_simp_out = what is proportional to the output -- per output vertex its cluster's number and its 20 sums (164 B)
@@ -254,6 +267,13 @@ int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t 
 int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who);
 // ---- api_components.hip ----
 int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want);  // a device buffer of at least `want` bytes, its content not kept
+// ---- api_clearance.hip ----
+// the parameters a clearance call works with (NULL: the defaults), checked -> the kernels' block; the state such a call needs; the
+// field of the volume as it stands, in d_clear (*reused: nothing had to be launched)
+int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who, hsk_clearance_params* p, ClearGeom* q);
+int clear_state_check(hsk_ctx* k, const char* who);
+int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused);
+void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]);
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

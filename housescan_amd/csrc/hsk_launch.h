@@ -178,6 +178,36 @@ void launch_clear_floor(hipStream_t s, const void* vol, const VolParams& vp, con
 void launch_clear_gather(hipStream_t s, const unsigned* field, const VolParams& vp, const float* xyz, unsigned n, unsigned* out);
 void launch_clear_box(hipStream_t s, const unsigned* field, const VolParams& vp, const int lo[3], const int hi[3], unsigned* out);  // (not empty)
 
+// the reach field (reach.hip) of any X Y Z grid of clearance values -- the volume's field, or a floor map with
+// Z = 1: the grid, its tiles (hsk_reach_point.h: REACH_TILE_*), the two bounds and the 27 move costs; and the scratch, carved out
+// of one device buffer by reach_layout -- the uint32 field, row-major as the clearance field, and per tile two flag words and
+// two worklist words
+struct ReachGeom {
+  unsigned X, Y, Z, ntx, nty, ntz;
+  unsigned min_d2, max_cost;
+  unsigned cost[27];
+};
+struct ReachBufs {
+  unsigned long long* counters;  // 8 words: [0] passable, [1] reached, [2] ~ the largest value, [3] seeds used, [4], [5] the worklists' lengths
+  unsigned* field;
+  unsigned* flags[2];            // a word per tile: on the worklist of the same number
+  unsigned* list[2];
+};
+void reach_geom(unsigned X, unsigned Y, unsigned Z, const unsigned w[3], unsigned min_d2, unsigned max_cost, ReachGeom* q);
+size_t reach_layout(const ReachGeom& q, void* base /* null: the size only */, ReachBufs* b);
+// init: counters and flags cleared, BLOCKED / UNREACHED from the clearance values d2; seed: n_seeds > 0 voxels (linear indices inside
+// the grid) -> worklist 0; round: relaxes the n_active > 0 tiles of worklist `cur` and fills the other, whose length is zeroed first;
+// stats: counters [1] and [2] of the finished field ([2] as the complement of the largest value, all ones when none).  init and
+// round clear device words first and return the first error of their calls
+hipError_t launch_reach_init(hipStream_t s, const unsigned* d2, const ReachGeom& q, const ReachBufs& b);
+void launch_reach_seed(hipStream_t s, const ReachGeom& q, const ReachBufs& b, const unsigned* seeds, unsigned n_seeds);
+hipError_t launch_reach_round(hipStream_t s, const ReachGeom& q, const ReachBufs& b, int cur, unsigned n_active);
+void launch_reach_stats(hipStream_t s, const ReachGeom& q, const ReachBufs& b);
+// the path from the voxel `goal` back to a seed: out = its first `cap` voxels (x, y, z each) from the goal on; result[0] = its
+// length (0: the goal holds no value), result[1] = 1 when the walk met a voxel without a move of the path rule
+void launch_reach_path(hipStream_t s, const unsigned* field, const ReachGeom& q, unsigned goal, unsigned long long cap, int* out,
+                       unsigned long long* result);
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the

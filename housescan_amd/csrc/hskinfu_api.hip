@@ -158,6 +158,7 @@ static void free_all(hsk_ctx* k) {
   F(k->d_comp);
   F(k->d_comp_tab);
   F(k->d_clear);
+  F(k->d_reach);
   F(k->d_simp);
   F(k->d_simp_out);
   if (k->h_align) (void)hipHostFree(k->h_align);

@@ -144,6 +144,47 @@ def clearance_metres(params, d2):
     return np.where(d == CLEARANCE_OUTSIDE, np.nan, out)
 
 
+REACH_UNREACHED, REACH_OUTSIDE, REACH_BLOCKED = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
+REACH_MAX_COST = 0xF0000000
+REACH_FIELDS = ("min_d2", "max_cost")
+
+
+def default_reach_params(tracker=None, clearance=None, **fields):
+    """the parameters of the reach calls (hsk_default_reach_params) for the clearance parameters `clearance` (None: the tracker's
+    defaults): min_d2 = clearance_d2(clearance, 0.3) -- a person's half width -- clamped to its max_d2, max_cost = REACH_MAX_COST;
+    the keywords -- min_d2, max_cost -- override its fields -> an `_lib.HskReachParams`"""
+    p = _lib.HskReachParams()
+    _lib.load().hsk_default_reach_params(tracker.h if tracker is not None else None, C.byref(clearance) if clearance is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in REACH_FIELDS:
+            raise TypeError(f"reach parameters have no field {name!r}")
+        setattr(p, name, int(val))
+    return p
+
+
+def reach_metres(params, g):
+    """the reach field's values as metres: g * unit_m / 16 of the clearance parameters `params`, nan for the three markers
+    (hsk_reach_metres, element by element)"""
+    v = np.asarray(g, np.uint32)
+    with np.errstate(invalid="ignore"):
+        out = (v.astype(np.float64) * np.float64(np.float32(params.unit_m)) / 16.0).astype(np.float32)
+    return np.where(v > REACH_MAX_COST, np.float32(np.nan), out)
+
+
+def rank_views_reach(scores, eye_g, max_g=REACH_MAX_COST):
+    """rank_views' order with the poses nobody can walk to behind all others: those whose eye_g -- reach_at of the camera centres --
+    is REACH_UNREACHED, REACH_BLOCKED, REACH_OUTSIDE or above max_g (hsk_rank_views_reach; host only) -> indices [n] uint32"""
+    s = np.ascontiguousarray(scores, VIEW_SCORE_DTYPE)
+    d = np.ascontiguousarray(eye_g, np.uint32).reshape(-1)
+    if len(d) != len(s):
+        raise ValueError("rank_views_reach: one eye_g per score")
+    order = np.empty(len(s), np.uint32)
+    if len(s) and _lib.load().hsk_rank_views_reach(s.ctypes.data_as(C.POINTER(_lib.HskViewScore)), d.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   int(max_g), len(s), order.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise KinfuError("rank_views_reach failed")
+    return order
+
+
 def rank_views_clear(scores, eye_d2, min_d2):
     """rank_views' order with the poses nobody can stand in behind all others: those whose eye_state is not 0 (free), whose eye_d2
     -- clearance_at of the camera centres -- is below min_d2 or is CLEARANCE_OUTSIDE (hsk_rank_views_clear; host only) ->
@@ -857,6 +898,97 @@ class KinfuTracker:
     def release_clearance(self):
         """frees the field and its scratch (hsk_release_clearance); the next call that needs it builds again"""
         self._ck(self.lib.hsk_release_clearance(self.h))
+
+    # ---- reach field -------------------------------------------------------------------------------------
+    def default_reach_params(self, clearance=None, **fields):
+        return default_reach_params(self, clearance, **fields)
+
+    def _reach(self, params, reach, fields):
+        """-> (HskClearanceParams, HskReachParams) of a reach call: the keywords min_d2, max_cost go to the reach parameters
+        (default: default_reach_params for the clearance parameters as overridden), all others to the clearance parameters"""
+        own = {k: fields.pop(k) for k in REACH_FIELDS if k in fields}
+        cp = self._clearance(params, fields)
+        rp = default_reach_params(self, cp) if reach is None else _lib.HskReachParams.from_buffer_copy(reach)
+        for name, val in own.items():
+            setattr(rp, name, int(val))
+        return cp, rp
+
+    @staticmethod
+    def _reach_stats(st):
+        return {"n_passable": int(st.n_passable), "n_reached": int(st.n_reached), "scratch_bytes": int(st.scratch_bytes),
+                "max_cost_seen": int(st.max_cost_seen), "n_rounds": int(st.n_rounds), "n_seeds_used": int(st.n_seeds_used), "reused": int(st.reused)}
+
+    @staticmethod
+    def _seeds(seeds):
+        return np.ascontiguousarray(seeds, np.float32).reshape(-1, 3)
+
+    def build_reach(self, seeds, params=None, reach=None, **fields):
+        """builds the reach field on the device (hsk_build_reach): per voxel the length, in sixteenths of the clearance unit, of the
+        shortest chain of 26-neighbour moves from the voxels of the world points `seeds` [n, 3] (at most 4096) that keeps a
+        clearance of min_d2; REACH_UNREACHED / REACH_BLOCKED elsewhere.  params: an HskClearanceParams, reach: an HskReachParams
+        (defaults: the tracker's); the keywords min_d2, max_cost override the reach parameters, all others the clearance
+        parameters -> dict: n_passable, n_reached, scratch_bytes, max_cost_seen, n_rounds, n_seeds_used, reused"""
+        cp, rp = self._reach(params, reach, fields)
+        pts = self._seeds(seeds)
+        st = _lib.HskReachStats()
+        self._ck(self.lib.hsk_build_reach(self.h, C.byref(cp), C.byref(rp), pts.ctypes.data if len(pts) else None, len(pts), C.byref(st)))
+        return self._reach_stats(st)
+
+    def download_reach(self, box=None):
+        """the reach field held over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume
+        (hsk_download_reach) -> [z, y, x] uint32"""
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        b = _lib.HskVoxelBox()
+        b.lo[:] = [int(v) for v in lo]
+        b.hi[:] = [int(v) for v in hi]
+        out = np.empty(tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0)), np.uint32)
+        self._ck(self.lib.hsk_download_reach(self.h, C.byref(b) if box is not None else None, out.ctypes.data))
+        return out
+
+    def reach_at(self, xyz):
+        """the reach field held at the voxels of the world points xyz [n, 3] (hsk_reach_at; at most 2^20) -> [n] uint32,
+        REACH_OUTSIDE for a point outside the grid or with a NaN"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out = np.empty(len(pts), np.uint32)
+        self._ck(self.lib.hsk_reach_at(self.h, pts.ctypes.data if len(pts) else None, len(pts), out.ctypes.data if len(pts) else None))
+        return out
+
+    def reach_path(self, goal, cap=4096):
+        """the path of the field held from a seed to the voxel of the world point `goal` (hsk_reach_path) -> [n, 3] int32 voxels
+        (x, y, z), n = 0 when the goal holds no value; a path longer than `cap` voxels is asked for again with the room it needs"""
+        g = np.ascontiguousarray(goal, np.float32).reshape(3)
+        n = C.c_size_t(0)
+        out = np.empty((max(int(cap), 1), 3), np.int32)
+        rc = self.lib.hsk_reach_path(self.h, g.ctypes.data, out.ctypes.data, int(cap), C.byref(n))
+        if rc == -1 and n.value > int(cap):
+            out = np.empty((n.value, 3), np.int32)
+            rc = self.lib.hsk_reach_path(self.h, g.ctypes.data, out.ctypes.data, n.value, C.byref(n))
+        self._ck(rc)
+        return out[:n.value].copy()
+
+    def reach_floor(self, axis, lo, hi, seeds, params=None, reach=None, **fields):
+        """the floor form (hsk_reach_floor) -- where a person can walk: the same rule on clearance_floor's map of the band, the
+        seeds projected by dropping the up axis -> (map [v, u] uint32 with u the lower-numbered remaining axis, stats dict)"""
+        cp, rp = self._reach(params, reach, fields)
+        pts = self._seeds(seeds)
+        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
+        ok = axis in (0, 1, 2)
+        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
+        out = np.empty((nv, nu), np.uint32)
+        st = _lib.HskReachStats()
+        self._ck(self.lib.hsk_reach_floor(self.h, C.byref(cp), int(axis), int(lo), int(hi), C.byref(rp), pts.ctypes.data if len(pts) else None, len(pts),
+                                          out.ctypes.data, C.byref(st)))
+        return out, self._reach_stats(st)
+
+    def release_reach(self):
+        """frees the reach field and its scratch (hsk_release_reach)"""
+        self._ck(self.lib.hsk_release_reach(self.h))
+
+    def reach_tiles_relaxed(self):
+        """of the last build_reach that built -> (the tiles relaxed over all its rounds, the tiles of the grid)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.hsk_reach_tiles_relaxed(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def default_reloc_params(self):
         p = _lib.HskRelocParams()

@@ -872,6 +872,79 @@ int hsk_release_clearance(hsk_ctx* k);
  * HSK_CLEARANCE_FAR counts as clear */
 int hsk_rank_views_clear(const hsk_view_score* s, const uint32_t* eye_d2, uint32_t min_d2, size_t n, uint32_t* order);
 
+/* ---- Reach field: whether a place can be walked to, and how far the walk is -- a geodesic distance field over the scanned free
+ * space, on the device (DESIGN.md 3.19 the kernels, 8m the rule; tests/reach_twin.py restates the rule in numpy).  All integers.
+ * Let D be the clearance field above for the clearance parameters given.  A voxel is PASSABLE when D >= min_d2 (HSK_CLEARANCE_FAR
+ * passes; 1 <= min_d2 <= max_d2, so an obstacle never is).  The MOVES are the 26 neighbours d in {-1, 0, 1}^3; a move between v
+ * and v + d is allowed only when every voxel of the box the two span (2, 4 or 8) lies in the grid and is passable: no path slips
+ * diagonally between two obstacles that touch by an edge or a corner.  A move COSTS c(d) = rint(16 sqrt(weight[0] dx^2 + weight[1]
+ * dy^2 + weight[2] dz^2)) (binary64), so metres are G unit_m / 16.  The field's value G(v) is the least sum of costs over the
+ * chains of allowed moves from any seed voxel to v: 0 at a passable seed; HSK_REACH_UNREACHED where no chain of at most max_cost
+ * arrives; HSK_REACH_BLOCKED where v is not passable.  It is the least fixpoint of G(v) = min(G(v), G(u) + c) and does not depend on
+ * the order of the work.
+ * This is a 26-neighbour CHAMFER metric, not the Euclidean geodesic: across open space it overestimates a straight walk by up to
+ * sqrt(1 + (sqrt2 - 1)^2 + (sqrt3 - sqrt2)^2) - 1 = 12.8 % (8.2 % in a plane), reached in the direction (1, sqrt2 - 1, sqrt3 -
+ * sqrt2), and is exact along the 26 directions themselves up to the rounding of the costs.
+ * SEEDS are up to 4096 world points, mapped to voxels as hsk_clearance_at maps its points; a seed outside the grid, with a NaN, or
+ * on a voxel that is not passable is ignored (n_seeds_used counts the others, duplicates each).
+ * The field stays on the device and is reused while the volume, the 20 device-relevant clearance bytes, min_d2, max_cost and the
+ * seeds' voxels (those inside the grid, in the caller's order) stand.  Its scratch -- the uint32 field and four words per tile of
+ * 32 x 8 x 8 voxels -- is made by the first build, NOT by hsk_prepare_readout, and freed by hsk_release_reach or hsk_destroy.
+ * Nothing the tracker reads is written.  Errors as the clearance calls have them; HSK_ERR_ARG as well for more than 4096 seeds,
+ * flags != 0, min_d2 outside 1..max_d2, max_cost above HSK_REACH_MAX_COST.  A refused call writes nothing.  The rounds of a build
+ * are driven by the host and end when a round lowers nothing, or with HSK_ERR_STATE and no field kept after HSK_REACH_MAX_ROUNDS. */
+#define HSK_REACH_UNREACHED 0xffffffffu
+#define HSK_REACH_OUTSIDE 0xfffffffeu
+#define HSK_REACH_BLOCKED 0xfffffffdu
+#define HSK_REACH_MAX_COST 0xf0000000u
+#define HSK_REACH_MAX_SEEDS 4096
+#define HSK_REACH_MAX_ROUNDS 65536
+typedef struct hsk_reach_params {
+  uint32_t min_d2;        /* a voxel is passable when its clearance is at least this; 1..max_d2                                */
+  uint32_t max_cost;      /* values above it are not propagated; at most HSK_REACH_MAX_COST                                    */
+  uint32_t flags;         /* 0                                                                                                  */
+  uint32_t pad;
+} hsk_reach_params;       /* 16 bytes */
+typedef struct hsk_reach_stats {
+  uint64_t n_passable;    /* passable voxels (of the floor map: columns)                                                       */
+  uint64_t n_reached;     /* voxels that hold a value                                                                          */
+  uint64_t scratch_bytes; /* the device memory the field holds                                                                 */
+  uint32_t max_cost_seen; /* the largest value (0: none)                                                                       */
+  uint32_t n_rounds;      /* rounds of tile relaxations launched (0: reused, or no usable seed)                                */
+  uint32_t n_seeds_used;  /* seeds on a passable voxel of the grid                                                             */
+  int32_t reused;         /* 1: the field of an earlier call was still valid                                                   */
+} hsk_reach_stats;        /* 40 bytes */
+/* min_d2 = hsk_clearance_d2(cp, 0.3f) -- a person's half width, a stated choice -- clamped to cp's max_d2; max_cost =
+ * HSK_REACH_MAX_COST.  cp NULL: the context's default clearance parameters */
+void hsk_default_reach_params(const hsk_ctx* k, const hsk_clearance_params* cp, hsk_reach_params* p);
+/* builds the clearance field (or reuses it), then the reach field (or finds the one of an earlier call still valid: reused = 1,
+ * nothing launched); cp, params NULL: the defaults; stats may be NULL */
+int hsk_build_reach(hsk_ctx* k, const hsk_clearance_params* cp, const hsk_reach_params* params, const float* seeds_xyz, size_t n_seeds,
+                    hsk_reach_stats* stats);
+/* The three reads of the field held.  HSK_ERR_STATE when none is valid for the volume as it stands: there are no seeds to build
+ * from.  download: the voxels of the box (NULL: the whole volume), row-major, x fastest.  at: the field at the voxels of n <= 2^20
+ * world points, HSK_REACH_OUTSIDE outside the grid or with a NaN. */
+int hsk_download_reach(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* g);
+int hsk_reach_at(hsk_ctx* k, const float* xyz, size_t n, uint32_t* g);
+/* The path to the voxel of goal_xyz, from the seed to the goal, x y z each: from the goal, step to v + d for the smallest move
+ * index m = (dz + 1) 9 + (dy + 1) 3 + (dx + 1) whose move is allowed and has G(v + d) + c(d) == G(v), until G == 0.  A goal that
+ * holds no value gives *n = 0 and HSK_OK.  cap (in voxels) too small: HSK_ERR_ARG with *n = the length needed, nothing written. */
+int hsk_reach_path(hsk_ctx* k, const float goal_xyz[3], int32_t* voxels_xyz, size_t cap, size_t* n);
+/* The floor form -- where a person can walk: the same rule, by the same kernels, on hsk_clearance_floor's map of the band
+ * lo <= p < hi along `axis`: one plane deep, so only the 8 in-plane moves occur, with the weights of the two remaining axes; the
+ * seeds are projected by dropping the up axis (that coordinate does not count).  map: one uint32 per column, the lower-numbered
+ * remaining axis fastest.  Not cached. */
+int hsk_reach_floor(hsk_ctx* k, const hsk_clearance_params* cp, int axis, int lo, int hi, const hsk_reach_params* params, const float* seeds_xyz,
+                    size_t n_seeds, uint32_t* map, hsk_reach_stats* stats);
+int hsk_release_reach(hsk_ctx* k);
+/* of the last hsk_build_reach that built: the tiles relaxed over all its rounds, and the tiles of the grid (either may be NULL) */
+int hsk_reach_tiles_relaxed(const hsk_ctx* k, uint64_t* tiles_relaxed, uint64_t* tiles);
+/* host only: hsk_rank_views' order, with the poses whose eye_g (hsk_reach_at of the camera centres) is HSK_REACH_UNREACHED,
+ * HSK_REACH_BLOCKED, HSK_REACH_OUTSIDE or above max_g behind all others, in the same order among themselves */
+int hsk_rank_views_reach(const hsk_view_score* s, const uint32_t* eye_g, uint32_t max_g, size_t n, uint32_t* order);
+/* host only: g unit_m / 16; NaN for the three markers */
+float hsk_reach_metres(const hsk_clearance_params* p, uint32_t g);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
