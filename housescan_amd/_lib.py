@@ -288,6 +288,39 @@ class HskReachStats(C.Structure):
                 ("n_rounds", C.c_uint32), ("n_seeds_used", C.c_uint32), ("reused", C.c_int32)]
 
 
+HSK_PARTITION_MAX_ROOMS = 1024
+HSK_PARTITION_MAX_RADIUS = 4
+HSK_ROOM_UNASSIGNED, HSK_ROOM_OUTSIDE, HSK_ROOM_BLOCKED, HSK_ROOM_NONE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+
+
+class HskPartitionParams(C.Structure):
+    """Mirror of `hsk_partition_params` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [("core_d2", C.c_uint32), ("min_d2", C.c_uint32), ("min_core_voxels", C.c_uint32), ("max_cost", C.c_uint32), ("flags", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class HskRoom(C.Structure):
+    """Mirror of `hsk_room` (include/hskinfu.h): 88 bytes."""
+
+    _fields_ = [("n_voxels", C.c_uint64), ("n_core_voxels", C.c_uint64), ("sum", C.c_uint64 * 3), ("root", C.c_uint32 * 3), ("lo", C.c_uint32 * 3),
+                ("hi", C.c_uint32 * 3), ("max_d2", C.c_uint32), ("max_g", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class HskDoor(C.Structure):
+    """Mirror of `hsk_door` (include/hskinfu.h): 72 bytes."""
+
+    _fields_ = [("sum2", C.c_uint64 * 3), ("a", C.c_uint32), ("b", C.c_uint32), ("n_faces", C.c_uint32 * 3), ("lo", C.c_uint32 * 3),
+                ("hi", C.c_uint32 * 3), ("max_d2", C.c_uint32)]
+
+
+class HskPartitionStats(C.Structure):
+    """Mirror of `hsk_partition_stats` (include/hskinfu.h): 56 bytes."""
+
+    _fields_ = [("n_cores", C.c_uint64), ("n_passable", C.c_uint64), ("n_assigned", C.c_uint64), ("scratch_bytes", C.c_uint64), ("n_dropped", C.c_uint64),
+                ("n_rooms", C.c_uint32), ("n_doors", C.c_uint32), ("n_rounds", C.c_uint32), ("reused", C.c_int32)]
+
+
 HSK_SIMPLIFY_QUADRIC, HSK_SIMPLIFY_MEAN = 0, 1
 
 
@@ -439,6 +472,18 @@ SYMBOLS = {
     "hsk_reach_tiles_relaxed": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hsk_rank_views_reach": (C.c_int, [C.POINTER(HskViewScore), C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]),
     "hsk_reach_metres": (C.c_float, [C.POINTER(HskClearanceParams), C.c_uint32]),
+    "hsk_default_partition_params": (None, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskPartitionParams)]),
+    "hsk_build_partition": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskPartitionParams), _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(HskPartitionStats)]),
+    "hsk_partition_doors": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "hsk_download_partition": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P]),
+    "hsk_download_partition_cost": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P]),
+    "hsk_partition_at": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "hsk_partition_floor": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.c_int, C.c_int, C.c_int, C.POINTER(HskPartitionParams), _P, _P, C.c_size_t,
+                                      C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskPartitionStats)]),
+    "hsk_release_partition": (C.c_int, [_P]),
+    "hsk_partition_tiles_relaxed": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hsk_merge_rooms": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_uint32, _P]),
     "hsk_invert_rigid": (C.c_int, [_F, _F]),
     "hsk_fuse_footprint": (C.c_int, [_I, _F, _I, _F, _F, C.POINTER(C.c_int32)]),
     "hsk_write_ppm": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),

@@ -195,6 +195,23 @@ struct hsk_ctx {
   unsigned long long reach_counts[4] = {0, 0, 0, 0};
   uint32_t reach_rounds = 0;
   unsigned long long reach_tiles = 0;  // the tiles relaxed over all rounds of the last hsk_build_reach that built (hsk_reach_tiles_relaxed)
+  // the room partition (hsk_build_partition; partition.hip), made by the first build and freed by hsk_release_partition: d_part =
+  // part_layout's counters, keys, parents, tile flags, worklists and tables; d_part_tab = the dense door table of the last build
+  // or floor call (grown only).  What d_part holds is the partition of the volume at part_epoch (0: nothing) for the clearance key
+  // and the four partition parameters in part_key; part_q its geometry, part_recs and part_doors its records in their order,
+  // part_counts = passable, cores, kept cores, assigned
+  void* d_part = nullptr;
+  size_t part_bytes = 0;
+  void* d_part_tab = nullptr;
+  size_t part_tab_bytes = 0;
+  uint64_t part_epoch = 0;
+  uint32_t part_key[9] = {};
+  PartGeom part_q = {};
+  std::vector<hsk_room> part_recs;
+  std::vector<hsk_door> part_doors;
+  unsigned long long part_counts[4] = {0, 0, 0, 0};
+  uint32_t part_rounds = 0;
+  unsigned long long part_tiles = 0, part_first = 0;  // of the last build that built: tiles relaxed over all rounds, tiles of the first worklist
   // the simplified mesh (hsk_extract_mesh_simplified; simplify.hip), made on first use and only grown: d_simp = the fixed scratch
   // of the cluster size asked for (simp_layout: a byte per cluster of the grid, the cluster rows' and the cube rows' tables);
   // d_simp_out = what is proportional to the output -- per output vertex its cluster's number and its 20 sums (164 B)

@@ -208,6 +208,51 @@ void launch_reach_stats(hipStream_t s, const ReachGeom& q, const ReachBufs& b);
 void launch_reach_path(hipStream_t s, const unsigned* field, const ReachGeom& q, unsigned goal, unsigned long long cap, int* out,
                        unsigned long long* result);
 
+// the room partition (partition.hip) of any X Y Z grid of clearance values -- the volume's field, or a floor
+// map with Z = 1: the grid, the reach field's tiles, the thresholds, the axis weights (the point lookup's) and the 27 move costs;
+// and the scratch, carved out of one device buffer by part_layout -- 12 bytes a voxel: the 64-bit keys (G << 32 | label) and the
+// uint32 parents of the core labelling, both row-major as the clearance field; per tile two flag words and two worklist words;
+// the kept roots as the device found them and in ascending order, the rank (room id) of each, 16 words of sums per room
+#define PART_REC_WORDS 16   // per room: n_voxels, n_core_voxels, sum x y z, ~lo x y z, hi x y z (inclusive), max_d2, max_g (hsk_part_recs)
+#define PART_DOOR_WORDS 8   // per pair of rooms, 64 bytes: sum2 x y z, then as uint32 n_faces x y z, ~lo x y z, hi x y z (inclusive), max_d2
+struct PartGeom {
+  unsigned X, Y, Z, ntx, nty, ntz;
+  unsigned core_d2, min_d2, min_core, max_cost;
+  unsigned w[3];
+  unsigned cost[27];
+};
+struct PartBufs {
+  unsigned long long* counters;  // 16 words: [0] passable, [1] cores, [2] kept cores, [4], [5] the worklists' lengths
+  unsigned long long* keys;
+  unsigned* parent;
+  unsigned* flags[2];
+  unsigned* list[2];
+  unsigned* roots_found;         // 1024: the kept roots in the order the device met them
+  unsigned* roots;               // 1024: ascending
+  unsigned* rank;                // 1024: the room id of roots[i]
+  unsigned long long* recs;      // 1024 x PART_REC_WORDS
+};
+void part_geom(unsigned X, unsigned Y, unsigned Z, const unsigned w[3], unsigned core_d2, unsigned min_d2, unsigned min_core, unsigned max_cost,
+               PartGeom* q);
+size_t part_layout(const PartGeom& q, void* base /* null: the size only */, PartBufs* b);
+// label: counters cleared; the 6-connected components of the core voxels of d2, parent[v] = the smallest lin of v's core (COMP_NONE:
+// no core voxel); the voxels of every core counted and the cores with at least min_core voxels put into roots_found (the first
+// 1024 of them; counters [1] and [2] count them all).  init: with n_kept <= 1024 ascending roots in b.roots, every voxel's key --
+// (0, label) in a kept core, UNASSIGNED or BLOCKED -- and worklist 0: the tiles that hold an UNASSIGNED voxel.  round: relaxes the
+// n_active > 0 tiles of worklist `cur` and fills the other, whose length is zeroed first.  records / doors: with b.rank filled, the
+// sums per room (b.recs, zeroed first) and per pair of rooms (table: n_kept^2 x PART_DOOR_WORDS words, zeroed first).  Those that
+// clear device words first return the first error of their calls.
+hipError_t launch_part_label(hipStream_t s, const unsigned* d2, const PartGeom& q, const PartBufs& b);
+hipError_t launch_part_init(hipStream_t s, const unsigned* d2, const PartGeom& q, const PartBufs& b, unsigned n_kept);
+hipError_t launch_part_round(hipStream_t s, const PartGeom& q, const PartBufs& b, int cur, unsigned n_active);
+hipError_t launch_part_records(hipStream_t s, const unsigned* d2, const PartGeom& q, const PartBufs& b, unsigned n_kept);
+hipError_t launch_part_doors(hipStream_t s, const unsigned* d2, const PartGeom& q, const PartBufs& b, unsigned n_kept, unsigned long long* table);
+// a box of the field (not empty), row-major: the room ids (UNASSIGNED / BLOCKED where a voxel holds none), or the costs G
+void launch_part_box(hipStream_t s, const PartGeom& q, const PartBufs& b, unsigned n_kept, const int lo[3], const int hi[3], bool cost, unsigned* out);
+// the room ids of n points: the voxel as hsk_clearance_at finds it, then hsk_part_point.h's search with `radius`
+void launch_part_gather(hipStream_t s, const PartGeom& q, const PartBufs& b, unsigned n_kept, const VolParams& vp, const float* xyz, unsigned n, int radius,
+                        unsigned* out);
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the

@@ -159,6 +159,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_comp_tab);
   F(k->d_clear);
   F(k->d_reach);
+  F(k->d_part);
+  F(k->d_part_tab);
   F(k->d_simp);
   F(k->d_simp_out);
   if (k->h_align) (void)hipHostFree(k->h_align);

@@ -185,6 +185,39 @@ def rank_views_reach(scores, eye_g, max_g=REACH_MAX_COST):
     return order
 
 
+ROOM_UNASSIGNED, ROOM_OUTSIDE, ROOM_BLOCKED, ROOM_NONE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+PARTITION_MAX_ROOMS = 1024
+PARTITION_FIELDS = ("core_d2", "min_d2", "min_core_voxels", "max_cost")
+# the records as numpy sees them (the layout of hsk_room and hsk_door)
+ROOM_DTYPE = np.dtype([("n_voxels", "<u8"), ("n_core_voxels", "<u8"), ("sum", "<u8", 3), ("root", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3),
+                       ("max_d2", "<u4"), ("max_g", "<u4"), ("pad", "<u4")])
+DOOR_DTYPE = np.dtype([("sum2", "<u8", 3), ("a", "<u4"), ("b", "<u4"), ("n_faces", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3), ("max_d2", "<u4")])
+
+
+def default_partition_params(tracker=None, clearance=None, **fields):
+    """the parameters of the partition calls (hsk_default_partition_params) for the clearance parameters `clearance` (None: the
+    tracker's defaults): core_d2 = clearance_d2(clearance, 0.5) clamped to its max_d2, min_d2 = 1, min_core_voxels = the voxels of a
+    cube of edge 0.25 m, max_cost = REACH_MAX_COST; the keywords -- core_d2, min_d2, min_core_voxels, max_cost -- override its
+    fields -> an `_lib.HskPartitionParams`"""
+    p = _lib.HskPartitionParams()
+    _lib.load().hsk_default_partition_params(tracker.h if tracker is not None else None, C.byref(clearance) if clearance is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in PARTITION_FIELDS:
+            raise TypeError(f"partition parameters have no field {name!r}")
+        setattr(p, name, int(val))
+    return p
+
+
+def merge_rooms(doors, n_rooms, merge_d2):
+    """the caller's remedy for a room that got two cores: per room the smallest id of its class under the union of all pairs whose
+    door has max_d2 >= merge_d2 (hsk_merge_rooms; host only; doors: a DOOR_DTYPE array) -> [n_rooms] uint32"""
+    d = np.ascontiguousarray(doors, DOOR_DTYPE).reshape(-1)
+    out = np.empty(int(n_rooms), np.uint32)
+    if _lib.load().hsk_merge_rooms(d.ctypes.data if len(d) else None, len(d), int(n_rooms), int(merge_d2), out.ctypes.data if n_rooms else None) != 0:
+        raise KinfuError("merge_rooms: a door names a room that is not below n_rooms")
+    return out
+
+
 def rank_views_clear(scores, eye_d2, min_d2):
     """rank_views' order with the poses nobody can stand in behind all others: those whose eye_state is not 0 (free), whose eye_d2
     -- clearance_at of the camera centres -- is below min_d2 or is CLEARANCE_OUTSIDE (hsk_rank_views_clear; host only) ->
@@ -989,6 +1022,109 @@ class KinfuTracker:
         a, b = C.c_uint64(0), C.c_uint64(0)
         self._ck(self.lib.hsk_reach_tiles_relaxed(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    # ---- room partition ----------------------------------------------------------------------------------
+    def default_partition_params(self, clearance=None, **fields):
+        return default_partition_params(self, clearance, **fields)
+
+    def _partition(self, params, partition, fields):
+        """-> (HskClearanceParams, HskPartitionParams) of a partition call: the keywords core_d2, min_d2, min_core_voxels, max_cost go
+        to the partition parameters (default: default_partition_params for the clearance parameters as overridden), all others to
+        the clearance parameters"""
+        own = {k: fields.pop(k) for k in PARTITION_FIELDS if k in fields}
+        cp = self._clearance(params, fields)
+        pp = default_partition_params(self, cp) if partition is None else _lib.HskPartitionParams.from_buffer_copy(partition)
+        for name, val in own.items():
+            setattr(pp, name, int(val))
+        return cp, pp
+
+    @staticmethod
+    def _partition_stats(st):
+        return {name: int(getattr(st, name)) for name, _ in _lib.HskPartitionStats._fields_}
+
+    def build_partition(self, params=None, partition=None, **fields):
+        """splits the scanned free space into rooms on the device (hsk_build_partition): the cores -- the 6-connected pieces of the
+        voxels with a clearance of core_d2 -- spread through everything with a clearance of min_d2 along the reach field's moves, a
+        voxel going to the nearest core.  params: an HskClearanceParams, partition: an HskPartitionParams (defaults: the tracker's);
+        the keywords core_d2, min_d2, min_core_voxels, max_cost override the partition parameters, all others the clearance
+        parameters -> (rooms: a ROOM_DTYPE array in id order, stats dict: n_cores, n_passable, n_assigned, scratch_bytes, n_dropped,
+        n_rooms, n_doors, n_rounds, reused)"""
+        cp, pp = self._partition(params, partition, fields)
+        st = _lib.HskPartitionStats()
+        n = C.c_size_t(0)
+        self._ck(self.lib.hsk_build_partition(self.h, C.byref(cp), C.byref(pp), None, 0, C.byref(n), C.byref(st)))
+        rooms = np.zeros(n.value, ROOM_DTYPE)
+        if n.value:
+            self._ck(self.lib.hsk_build_partition(self.h, C.byref(cp), C.byref(pp), rooms.ctypes.data, n.value, C.byref(n), None))
+        return rooms, self._partition_stats(st)
+
+    def partition_doors(self):
+        """the doors of the partition held (hsk_partition_doors): one record per pair of rooms that meet -> a DOOR_DTYPE array
+        ordered by (a, b)"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.hsk_partition_doors(self.h, None, 0, C.byref(n)))
+        doors = np.zeros(n.value, DOOR_DTYPE)
+        if n.value:
+            self._ck(self.lib.hsk_partition_doors(self.h, doors.ctypes.data, n.value, C.byref(n)))
+        return doors
+
+    def _partition_box(self, call, box):
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        b = _lib.HskVoxelBox()
+        b.lo[:] = [int(v) for v in lo]
+        b.hi[:] = [int(v) for v in hi]
+        out = np.empty(tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0)), np.uint32)
+        self._ck(call(self.h, C.byref(b) if box is not None else None, out.ctypes.data))
+        return out
+
+    def download_partition(self, box=None):
+        """the room ids of the partition held over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume
+        (hsk_download_partition) -> [z, y, x] uint32; ROOM_UNASSIGNED / ROOM_BLOCKED where a voxel holds no room"""
+        return self._partition_box(self.lib.hsk_download_partition, box)
+
+    def download_partition_cost(self, box=None):
+        """the cost G of every voxel's chain to its core (hsk_download_partition_cost): the reach field seeded at every kept core
+        voxel -> [z, y, x] uint32"""
+        return self._partition_box(self.lib.hsk_download_partition_cost, box)
+
+    def partition_at(self, xyz, radius=0):
+        """the room of the world points xyz [n, 3] (hsk_partition_at; at most 2^20): that of the nearest voxel holding a room
+        within `radius` (0..4) voxels on every axis of the point's own -> [n] uint32; ROOM_OUTSIDE for a point outside the grid or
+        with a NaN, ROOM_NONE where there is no such voxel.  With a radius above 0 a surface point gets the room whose air it borders"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        out = np.empty(len(pts), np.uint32)
+        self._ck(self.lib.hsk_partition_at(self.h, pts.ctypes.data if len(pts) else None, len(pts), int(radius), out.ctypes.data if len(pts) else None))
+        return out
+
+    def partition_floor(self, axis, lo, hi, params=None, partition=None, **fields):
+        """the floor form (hsk_partition_floor): the same rule on clearance_floor's map of the band -> (map [v, u] uint32 room ids
+        with u the lower-numbered remaining axis, rooms, doors, stats dict)"""
+        cp, pp = self._partition(params, partition, fields)
+        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
+        ok = axis in (0, 1, 2)
+        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
+        out = np.empty((nv, nu), np.uint32)
+        st = _lib.HskPartitionStats()
+        rooms, doors = np.zeros(PARTITION_MAX_ROOMS, ROOM_DTYPE), np.zeros(64, DOOR_DTYPE)
+        nr, nd = C.c_size_t(0), C.c_size_t(0)
+        args = (self.h, C.byref(cp), int(axis), int(lo), int(hi), C.byref(pp), out.ctypes.data)
+        rc = self.lib.hsk_partition_floor(*args, rooms.ctypes.data, len(rooms), C.byref(nr), doors.ctypes.data, len(doors), C.byref(nd), C.byref(st))
+        if rc == -1 and nd.value > len(doors):
+            doors = np.zeros(nd.value, DOOR_DTYPE)
+            rc = self.lib.hsk_partition_floor(*args, rooms.ctypes.data, len(rooms), C.byref(nr), doors.ctypes.data, len(doors), C.byref(nd), C.byref(st))
+        self._ck(rc)
+        return out, rooms[:nr.value].copy(), doors[:nd.value].copy(), self._partition_stats(st)
+
+    def release_partition(self):
+        """frees the partition and its scratch (hsk_release_partition)"""
+        self._ck(self.lib.hsk_release_partition(self.h))
+
+    def partition_tiles_relaxed(self):
+        """of the last build_partition that built -> (the tiles relaxed over all its rounds, the tiles of its first worklist, the
+        tiles of the grid)"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.hsk_partition_tiles_relaxed(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def default_reloc_params(self):
         p = _lib.HskRelocParams()

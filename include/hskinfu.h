@@ -945,6 +945,111 @@ int hsk_rank_views_reach(const hsk_view_score* s, const uint32_t* eye_g, uint32_
 /* host only: g unit_m / 16; NaN for the three markers */
 float hsk_reach_metres(const hsk_clearance_params* p, uint32_t g);
 
+/* ---- Room partition: where one room ends and the next begins -- the scanned free space split into rooms and doors, on the device
+ * (DESIGN.md 3.20 the kernels, 8n the rule; tests/partition_twin.py restates the rule in numpy).  All integers.  Let D be the
+ * clearance field for the clearance parameters given and lin(x, y, z) = (z Y + y) X + x.
+ * CORES.  A voxel is a core voxel when D >= core_d2 (HSK_CLEARANCE_FAR passes).  The cores are the 6-connected components of the
+ * core voxels; a core's label is the smallest lin among its voxels.  A core of fewer than min_core_voxels voxels is dropped: its
+ * voxels are ordinary passable voxels.  At most HSK_PARTITION_MAX_ROOMS cores may be kept.
+ * SPREADING.  A voxel is passable when D >= min_d2, 1 <= min_d2 <= core_d2 <= max_d2.  The moves, the box rule and the costs are
+ * the reach field's.  A voxel's key is K(v) = (G, L): the lexicographically least (sum of costs, label of the core the chain
+ * starts in) over the chains of allowed moves from any voxel of a kept core to v, chains above max_cost not propagated; a kept
+ * core voxel holds (0, its label).  K is the least fixpoint of K(v) = min(K(v), K(u) + (c, 0)) and does not depend on the order
+ * of the work; G alone is the reach field seeded at every kept core voxel.
+ * ROOMS.  A room is the set of voxels that share an L.  The records are ordered by n_voxels descending, ties to the smaller root;
+ * a room's id is its rank.  A passable voxel that no chain reaches reports HSK_ROOM_UNASSIGNED, a voxel that is not passable
+ * HSK_ROOM_BLOCKED.
+ * DOORS.  A face is a pair of 6-adjacent voxels that hold two different rooms a < b; there is one record per pair of rooms with a
+ * face, ordered by (a, b).  A door's max_d2 -- the largest min(D(u), D(u')) over its faces -- is an UPPER estimate of the squared
+ * half width of the passage.  The interface between two rooms is the geodesic bisector of their two cores: it lies in the
+ * doorway only as far as the two cores are equally far from it.
+ * The partition stays on the device and is reused while the volume, the 20 device-relevant clearance bytes and the partition
+ * parameters stand.  Its scratch -- 12 bytes a voxel, four words per tile of 32 x 8 x 8 voxels, 64 bytes per pair of rooms -- is
+ * made by the first build and freed by hsk_release_partition or hsk_destroy.  Nothing the tracker reads is written.  Errors as
+ * the reach calls have them; HSK_ERR_ARG as well for flags != 0, thresholds out of order, more than 1024 kept cores, radius
+ * outside 0..4, a cap too small.  A refused call writes nothing but what it lists. */
+#define HSK_PARTITION_MAX_ROOMS 1024
+#define HSK_PARTITION_MAX_RADIUS 4
+#define HSK_ROOM_UNASSIGNED 0xffffffffu
+#define HSK_ROOM_OUTSIDE 0xfffffffeu
+#define HSK_ROOM_BLOCKED 0xfffffffdu
+#define HSK_ROOM_NONE 0xfffffffcu
+typedef struct hsk_partition_params {
+  uint32_t core_d2;         /* a voxel is a core voxel when its clearance is at least this; min_d2..max_d2                       */
+  uint32_t min_d2;          /* a voxel is passable when its clearance is at least this; 1..core_d2                               */
+  uint32_t min_core_voxels; /* a core of fewer voxels is dropped                                                                  */
+  uint32_t max_cost;        /* chains above it are not propagated; at most HSK_REACH_MAX_COST                                    */
+  uint32_t flags;           /* 0                                                                                                  */
+  uint32_t pad;
+} hsk_partition_params;     /* 24 bytes */
+typedef struct hsk_room {
+  uint64_t n_voxels;        /* voxels (of the floor form: columns) that hold this room                                           */
+  uint64_t n_core_voxels;   /* of them, voxels of its core (G == 0)                                                              */
+  uint64_t sum[3];          /* sums of x, y, z over its voxels: the centroid is sum / n_voxels (+ 0.5, in voxels)                */
+  uint32_t root[3];         /* the voxel whose lin is the room's label                                                           */
+  uint32_t lo[3], hi[3];    /* its voxels' box, hi exclusive                                                                     */
+  uint32_t max_d2;          /* the largest clearance in the room (HSK_CLEARANCE_FAR counts as the largest)                       */
+  uint32_t max_g;           /* the largest G in the room                                                                         */
+  uint32_t pad;
+} hsk_room;                 /* 88 bytes */
+typedef struct hsk_door {
+  uint64_t sum2[3];         /* sums over the faces of twice the face centre, a voxel's centre being at its index: 2 u + e_axis   */
+  uint32_t a, b;            /* the two rooms' ids, a < b                                                                         */
+  uint32_t n_faces[3];      /* faces by the axis they cross                                                                      */
+  uint32_t lo[3], hi[3];    /* the box of the faces' lower voxels, hi exclusive                                                  */
+  uint32_t max_d2;          /* the largest min(D(u), D(u')) over the faces: an upper estimate of the squared half width          */
+} hsk_door;                 /* 72 bytes */
+typedef struct hsk_partition_stats {
+  uint64_t n_cores;         /* cores before dropping                                                                             */
+  uint64_t n_passable;      /* passable voxels (of the floor form: columns)                                                      */
+  uint64_t n_assigned;      /* voxels that hold a room                                                                           */
+  uint64_t scratch_bytes;   /* the device memory the partition holds                                                             */
+  uint64_t n_dropped;       /* cores dropped for their size                                                                      */
+  uint32_t n_rooms;         /* cores kept                                                                                        */
+  uint32_t n_doors;
+  uint32_t n_rounds;        /* rounds of tile relaxations launched (0: reused)                                                   */
+  int32_t reused;           /* 1: the partition of an earlier call was still valid                                               */
+} hsk_partition_stats;      /* 56 bytes */
+/* core_d2 = hsk_clearance_d2(cp, 0.5f), clamped to cp's max_d2: wider than an interior door's half width, so anything narrower
+ * than 1 m has no core of its own and joins a neighbour -- a stated choice, not a measurement; min_d2 = 1: every voxel that is no
+ * obstacle gets a room; min_core_voxels = the voxels of a cube of edge 0.25 m (binary64, as hsk_default_prune_params computes its
+ * cube); max_cost = HSK_REACH_MAX_COST.  cp NULL: the context's default clearance parameters */
+void hsk_default_partition_params(const hsk_ctx* k, const hsk_clearance_params* cp, hsk_partition_params* p);
+/* builds the clearance field (or reuses it), then the partition (or finds the one of an earlier call still valid: reused = 1,
+ * nothing launched); cp, params NULL: the defaults; stats may be NULL.  recs NULL: counts only; else the records of all rooms in
+ * their order, cap of them at least: a cap too small gives HSK_ERR_ARG with *n_rooms = the count needed and nothing else written
+ * (the partition is held all the same).  More than HSK_PARTITION_MAX_ROOMS kept cores: HSK_ERR_ARG with the stats set (n_cores,
+ * n_rooms = the kept cores, n_dropped; all else zero) and nothing held. */
+int hsk_build_partition(hsk_ctx* k, const hsk_clearance_params* cp, const hsk_partition_params* params, hsk_room* recs, size_t cap, size_t* n_rooms,
+                        hsk_partition_stats* stats);
+/* The reads of the partition held.  HSK_ERR_STATE when none is valid for the volume as it stands.  doors: the records in their
+ * order (doors NULL: the count only; a cap too small: HSK_ERR_ARG with *n_doors = the count needed).  download: the room ids of
+ * the voxels of the box (NULL: the whole volume), row-major, x fastest; download_cost: their G, which is the reach field's value
+ * with HSK_REACH_UNREACHED and HSK_REACH_BLOCKED.  at: the room of n <= 2^20 world points -- the voxel of a point as
+ * hsk_clearance_at finds it; among the voxels within |dx|, |dy|, |dz| <= radius (0..4) of it that hold a room, the one that
+ * minimises (weight[0] dx^2 + weight[1] dy^2 + weight[2] dz^2, lin); HSK_ROOM_OUTSIDE for a point outside the grid or with a NaN,
+ * HSK_ROOM_NONE when there is no such voxel.  With a radius above 0 a surface point, which sits in an obstacle voxel, gets the room
+ * whose air it borders. */
+int hsk_partition_doors(hsk_ctx* k, hsk_door* doors, size_t cap, size_t* n_doors);
+int hsk_download_partition(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* ids);
+int hsk_download_partition_cost(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* g);
+int hsk_partition_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint32_t* ids);
+/* The floor form: the same rule, by the same kernels, on hsk_clearance_floor's map of the band lo <= p < hi along `axis`: one
+ * plane deep, so the cores are 4-connected and only the 8 in-plane moves occur, with the weights of the two remaining axes.  map:
+ * one room id per column, the lower-numbered remaining axis fastest (a record's x, y are the map's u, v; z is 0).  recs, doors:
+ * as above, either may be NULL with its cap 0 (n_rooms, n_doors may then be NULL too); a cap too small: HSK_ERR_ARG with both
+ * counts set and nothing else written.  Not cached. */
+int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cp, int axis, int lo, int hi, const hsk_partition_params* params, uint32_t* map,
+                        hsk_room* recs, size_t rec_cap, size_t* n_rooms, hsk_door* doors, size_t door_cap, size_t* n_doors, hsk_partition_stats* stats);
+int hsk_release_partition(hsk_ctx* k);
+/* of the last hsk_build_partition that built: the tiles relaxed over all its rounds, the tiles of the first worklist and the tiles
+ * of the grid (any may be NULL) */
+int hsk_partition_tiles_relaxed(const hsk_ctx* k, uint64_t* tiles_relaxed, uint64_t* first_tiles, uint64_t* tiles);
+/* host only: the caller's remedy for a room that got two cores (an L-shaped one).  map[i], i < n_rooms: the smallest id of room
+ * i's class under the union of all pairs (a, b) whose door has max_d2 >= merge_d2.  Touches nothing on the device.  HSK_ERR_ARG:
+ * a NULL argument where one is needed, a door whose rooms are not below n_rooms */
+int hsk_merge_rooms(const hsk_door* doors, size_t n_doors, size_t n_rooms, uint32_t merge_d2, uint32_t* map);
+
 /* Multi-GPU (z-slab) building blocks; device pointers so that the host's collective (RCCL through
  * torch.distributed) can run on them without a host round trip.  All work is enqueued on hsk_stream(). */
 int hsk_mgpu_frame_begin(hsk_ctx* k, const void* depth_dev, int w, int h); /* preprocess + (frame 0) transform */
