@@ -3,7 +3,8 @@
 // hsk_clearance_floor, hsk_release_clearance and the host-only hsk_rank_views_clear.  The field reads the volume as it stands, with
 // NO flush of the deferred weights (as the coverage calls and the components): the rule asks of a weight only whether it is zero
 // and of the TSDF its sign.  It stays on the device (d_clear) while vol_epoch and the 20 device-relevant parameter bytes stand.
-// Nothing the tracker reads is written; vol_epoch does not move.
+// Nothing the tracker reads is written; vol_epoch does not move.  The reads of the fields over it (api_reach.hip, api_partition.hip)
+// and the census (api_cover.hip) take from here the box check, the floor map's grid and the point gather (hsk_ctx.h).
 #pragma clang fp contract(off)
 #include <algorithm>
 #include <cmath>
@@ -84,6 +85,44 @@ int clear_state_check(hsk_ctx* k, const char* who) {
   return HSK_OK;
 }
 
+int clear_box_check(hsk_ctx* k, const hsk_voxel_box* box, const char* who, hsk_voxel_box* b, size_t* n) {
+  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
+  *n = 1;
+  for (int i = 0; i < 3; ++i) {
+    b->lo[i] = box ? box->lo[i] : 0;
+    b->hi[i] = box ? box->hi[i] : dims[i];
+    if (b->lo[i] < 0 || b->hi[i] > dims[i] || b->hi[i] < b->lo[i])
+      return fail(k, HSK_ERR_ARG, (std::string(who) + ": the box must satisfy 0 <= lo <= hi <= the volume's dims on every axis").c_str());
+    *n *= (size_t)(b->hi[i] - b->lo[i]);
+  }
+  return HSK_OK;
+}
+
+int clear_floor_grid(hsk_ctx* k, const ClearGeom& q, int axis, int lo, int hi, const char* who, FloorGrid* f) {
+  if (axis < 0 || axis > 2) return fail(k, HSK_ERR_ARG, (std::string(who) + ": axis must be 0, 1 or 2").c_str());
+  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
+  if (lo < 0 || hi > dims[axis] || hi < lo) return fail(k, HSK_ERR_ARG, (std::string(who) + ": the band must satisfy 0 <= lo <= hi <= the axis").c_str());
+  f->au = axis == 0 ? 1 : 0;
+  f->av = axis == 2 ? 1 : 2;
+  f->nu = (unsigned)dims[f->au];
+  f->nv = (unsigned)dims[f->av];
+  const unsigned w[3] = {q.w[f->au], q.w[f->av], q.w[axis]};
+  memcpy(f->w, w, sizeof(w));
+  return HSK_OK;
+}
+
+int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*)>& launch) {
+  ProductLayout lay;
+  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4);
+  int r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  char* base = (char*)k->d_out;
+  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
+  launch((const float*)(base + pts_at), (unsigned*)(base + out_at));
+  HIPCHK(k, hipGetLastError());
+  return copy_out(k, out, base + out_at, n * 4);
+}
+
 void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
   key[0] = p.weight[0];
   key[1] = p.weight[1];
@@ -149,14 +188,9 @@ extern "C" int hsk_download_clearance(hsk_ctx* k, const hsk_clearance_params* pa
   hsk_clearance_params p;
   ClearGeom q;
   if (int rc = clear_check(k, params, "hsk_download_clearance", &p, &q)) return rc;
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
   hsk_voxel_box b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = box ? box->lo[i] : 0;
-    b.hi[i] = box ? box->hi[i] : dims[i];
-    if (b.lo[i] < 0 || b.hi[i] > dims[i] || b.hi[i] < b.lo[i])
-      return fail(k, HSK_ERR_ARG, "hsk_download_clearance: the box must satisfy 0 <= lo <= hi <= the volume's dims on every axis");
-  }
+  size_t n;
+  if (int rc = clear_box_check(k, box, "hsk_download_clearance", &b, &n)) return rc;
   if (int rc = clear_state_check(k, "hsk_download_clearance")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   bool reused = false;
@@ -164,9 +198,8 @@ extern "C" int hsk_download_clearance(hsk_ctx* k, const hsk_clearance_params* pa
   if (r != HSK_OK) return r;
   ClearBufs cb;
   clear_layout(k->vp, k->d_clear, &cb);
-  const size_t n = (size_t)(b.hi[0] - b.lo[0]) * (size_t)(b.hi[1] - b.lo[1]) * (size_t)(b.hi[2] - b.lo[2]);
   if (n == 0) return HSK_OK;
-  if (n == (size_t)dims[0] * dims[1] * dims[2]) return copy_out(k, d2, cb.field, n * 4);
+  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, d2, cb.field, n * 4);
   r = ensure_product_bytes(k, n * 4);
   if (r != HSK_OK) return r;
   launch_clear_box(k->stream, cb.field, k->vp, b.lo, b.hi, (unsigned*)k->d_out);
@@ -189,15 +222,7 @@ extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, 
   if (r != HSK_OK) return r;
   ClearBufs cb;
   clear_layout(k->vp, k->d_clear, &cb);
-  ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4);
-  r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
-  char* base = (char*)k->d_out;
-  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch_clear_gather(k->stream, cb.field, k->vp, (const float*)(base + pts_at), (unsigned)n, (unsigned*)(base + out_at));
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, d2, base + out_at, n * 4);
+  return gather_points(k, xyz, n, d2, [&](const float* pts, unsigned* out) { launch_clear_gather(k->stream, cb.field, k->vp, pts, (unsigned)n, out); });
 }
 
 extern "C" int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* params, int axis, int lo, int hi, uint32_t* map, hsk_clearance_stats* stats) {
@@ -206,12 +231,11 @@ extern "C" int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* param
   hsk_clearance_params p;
   ClearGeom q;
   if (int rc = clear_check(k, params, "hsk_clearance_floor", &p, &q)) return rc;
-  if (axis < 0 || axis > 2) return fail(k, HSK_ERR_ARG, "hsk_clearance_floor: axis must be 0, 1 or 2");
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
-  if (lo < 0 || hi > dims[axis] || hi < lo) return fail(k, HSK_ERR_ARG, "hsk_clearance_floor: the band must satisfy 0 <= lo <= hi <= the axis");
+  FloorGrid f;
+  if (int rc = clear_floor_grid(k, q, axis, lo, hi, "hsk_clearance_floor", &f)) return rc;
   if (int rc = clear_state_check(k, "hsk_clearance_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  const size_t n = (size_t)dims[axis == 0 ? 1 : 0] * (size_t)dims[axis == 2 ? 1 : 2];
+  const size_t n = (size_t)f.nu * f.nv;
   ProductLayout lay;
   const size_t a_at = lay.take(n * 4), b_at = lay.take(n * 4);
   int r = ensure_product_bytes(k, lay.bytes);

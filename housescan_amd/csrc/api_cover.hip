@@ -117,16 +117,11 @@ extern "C" int hsk_coverage_census(hsk_ctx* k, const hsk_voxel_box* box, hsk_cov
   static_assert(sizeof(hsk_coverage) == 80, "hsk_coverage is ten 64-bit words");
   if (!k) return HSK_ERR_ARG;
   if (!out) return fail(k, HSK_ERR_ARG, "hsk_coverage_census: out is null");
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
   hsk_voxel_box b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = box ? box->lo[i] : 0;
-    b.hi[i] = box ? box->hi[i] : dims[i];
-    if (b.lo[i] < 0 || b.hi[i] > dims[i] || b.hi[i] < b.lo[i])
-      return fail(k, HSK_ERR_ARG, "hsk_coverage_census: the box must satisfy 0 <= lo <= hi <= the volume's dims on every axis");
-  }
+  size_t n;
+  if (int rc = clear_box_check(k, box, "hsk_coverage_census", &b, &n)) return rc;
   if (int rs = require_whole_volume(k, k, "hsk_coverage_census", "the census of a group is not summed")) return rs;
-  if (b.hi[0] == b.lo[0] || b.hi[1] == b.lo[1] || b.hi[2] == b.lo[2]) {
+  if (n == 0) {
     memset(out, 0, sizeof(*out));
     return HSK_OK;
   }

@@ -4,7 +4,7 @@
 // The partition is built from the clearance field (api_clearance.hip builds or reuses it first) and stays on the device (d_part)
 // while vol_epoch, the 20 device-relevant clearance bytes and the four partition parameters stand.  The host drives it: it reads
 // the number of kept cores and sorts their roots between the labelling and the init, reads the next worklist's length after every
-// round and stops at zero or at HSK_REACH_MAX_ROUNDS, orders the room records and sends the id table back before the door sweep.
+// round and stops at zero or at HSK_REACH_MAX_ROUNDS (api_reach.hip: relax_rounds), orders the room records and sends the id table back before the door sweep.
 // Nothing the tracker reads is written; vol_epoch does not move.
 #pragma clang fp contract(off)
 #include <algorithm>
@@ -115,15 +115,8 @@ static int part_run(hsk_ctx* k, const unsigned* d2, const PartGeom& q, const Par
   if (int r = read_u64(k, &n_active, b.counters + 4)) return r;
   out->first = n_active;
   if (!n_kept) n_active = 0;  // (no core: nothing can fall)
-  int cur = 0;
-  while (n_active) {  // (ends: at HSK_REACH_MAX_ROUNDS at the latest)
-    if (out->rounds >= HSK_REACH_MAX_ROUNDS) return fail(k, HSK_ERR_STATE, "the partition did not settle within HSK_REACH_MAX_ROUNDS rounds");
-    HIPCHK(k, launch_part_round(k->stream, q, b, cur, (unsigned)n_active));
-    out->tiles += n_active;
-    out->rounds += 1;
-    cur ^= 1;
-    if (int r = read_u64(k, &n_active, b.counters + 4 + cur)) return r;
-  }
+  auto round = [&](int cur, unsigned n) { return launch_part_round(k->stream, q, b, cur, n); };
+  if (int r = relax_rounds(k, round, b.counters + 4, n_active, "the partition", &out->rounds, &out->tiles)) return r;
   if (int r = read_u64(k, &out->counts[0], b.counters)) return r;
   if (!n_kept) return HSK_OK;
   // the records: the device's sums per ascending root -> the order n_voxels descending, ties to the smaller root -> the id table
@@ -293,19 +286,13 @@ extern "C" int hsk_partition_doors(hsk_ctx* k, hsk_door* doors, size_t cap, size
 static int part_download(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* out, bool cost, const char* who) {
   if (!k) return HSK_ERR_ARG;
   if (!out) return fail(k, HSK_ERR_ARG, (std::string(who) + ": the output is null").c_str());
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
   hsk_voxel_box b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = box ? box->lo[i] : 0;
-    b.hi[i] = box ? box->hi[i] : dims[i];
-    if (b.lo[i] < 0 || b.hi[i] > dims[i] || b.hi[i] < b.lo[i])
-      return fail(k, HSK_ERR_ARG, (std::string(who) + ": the box must satisfy 0 <= lo <= hi <= the volume's dims on every axis").c_str());
-  }
+  size_t n;
+  if (int rc = clear_box_check(k, box, who, &b, &n)) return rc;
   if (int rc = part_held(k, who)) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   PartBufs pb;
   part_layout(k->part_q, k->d_part, &pb);
-  const size_t n = (size_t)(b.hi[0] - b.lo[0]) * (size_t)(b.hi[1] - b.lo[1]) * (size_t)(b.hi[2] - b.lo[2]);
   if (n == 0) return HSK_OK;
   int r = ensure_product_bytes(k, n * 4);
   if (r != HSK_OK) return r;
@@ -332,16 +319,9 @@ extern "C" int hsk_partition_at(hsk_ctx* k, const float* xyz, size_t n, int radi
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   PartBufs pb;
   part_layout(k->part_q, k->d_part, &pb);
-  ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
-  char* base = (char*)k->d_out;
-  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch_part_gather(k->stream, k->part_q, pb, (unsigned)k->part_recs.size(), k->vp, (const float*)(base + pts_at), (unsigned)n, radius,
-                     (unsigned*)(base + out_at));
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, ids, base + out_at, n * 4);
+  return gather_points(k, xyz, n, ids, [&](const float* pts, unsigned* out) {
+    launch_part_gather(k->stream, k->part_q, pb, (unsigned)k->part_recs.size(), k->vp, pts, (unsigned)n, radius, out);
+  });
 }
 
 extern "C" int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cparams, int axis, int lo, int hi, const hsk_partition_params* params,
@@ -355,19 +335,15 @@ extern "C" int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cpara
   hsk_partition_params p;
   if (int rc = clear_check(k, cparams, "hsk_partition_floor", &cp, &cq)) return rc;
   if (int rc = part_check(k, cp, params, "hsk_partition_floor", &p)) return rc;
-  if (axis < 0 || axis > 2) return fail(k, HSK_ERR_ARG, "hsk_partition_floor: axis must be 0, 1 or 2");
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
-  if (lo < 0 || hi > dims[axis] || hi < lo) return fail(k, HSK_ERR_ARG, "hsk_partition_floor: the band must satisfy 0 <= lo <= hi <= the axis");
+  FloorGrid f;
+  if (int rc = clear_floor_grid(k, cq, axis, lo, hi, "hsk_partition_floor", &f)) return rc;
   if (int rc = clear_state_check(k, "hsk_partition_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // the map's grid: (u, v, 1), u the lower-numbered remaining axis; the same kernels, on which nothing ever crosses the third axis
   // (its neighbours lie outside the grid): the cores are 4-connected, the moves the 8 in-plane ones
-  const int au = axis == 0 ? 1 : 0, av = axis == 2 ? 1 : 2;
-  const unsigned nu = (unsigned)dims[au], nv = (unsigned)dims[av];
-  const unsigned w[3] = {cq.w[au], cq.w[av], cq.w[axis]};
   PartGeom q;
-  part_geom(nu, nv, 1u, w, p.core_d2, p.min_d2, p.min_core_voxels, p.max_cost, &q);
-  const size_t n = (size_t)nu * nv;
+  part_geom(f.nu, f.nv, 1u, f.w, p.core_d2, p.min_d2, p.min_core_voxels, p.max_cost, &q);
+  const size_t n = (size_t)f.nu * f.nv;
   ProductLayout lay;
   const size_t a_at = lay.take(n * 4), b_at = lay.take(n * 4), ids_at = lay.take(n * 4);
   const size_t part_at = lay.take(part_layout(q, nullptr, nullptr));
@@ -390,7 +366,7 @@ extern "C" int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cpara
     if (n_doors) *n_doors = res.doors.size();
     return fail(k, HSK_ERR_ARG, "hsk_partition_floor: a cap is smaller than the number of records (*n_rooms, *n_doors: the counts)");
   }
-  const int blo[3] = {0, 0, 0}, bhi[3] = {(int)nu, (int)nv, 1};
+  const int blo[3] = {0, 0, 0}, bhi[3] = {(int)f.nu, (int)f.nv, 1};
   launch_part_box(k->stream, q, pb, (unsigned)res.recs.size(), blo, bhi, false, (unsigned*)(base + ids_at));
   HIPCHK(k, hipGetLastError());
   r = copy_out(k, map, base + ids_at, n * 4);

@@ -3,7 +3,8 @@
 // hsk_reach_tiles_relaxed and the host-only hsk_rank_views_reach and hsk_reach_metres.  The field is built from the clearance field
 // (api_clearance.hip builds or reuses it first) and stays on the device (d_reach) while vol_epoch, the 20 device-relevant
 // clearance bytes, min_d2, max_cost and the seeds' voxels stand.  The host drives the rounds: it reads the next worklist's length
-// after every round and stops at zero, or at HSK_REACH_MAX_ROUNDS.  Nothing the tracker reads is written; vol_epoch does not move.
+// after every round and stops at zero, or at HSK_REACH_MAX_ROUNDS (relax_rounds, which api_partition.hip drives its rounds with
+// too).  Nothing the tracker reads is written; vol_epoch does not move.
 #pragma clang fp contract(off)
 #include <algorithm>
 #include <cmath>
@@ -67,6 +68,23 @@ static int reach_check(hsk_ctx* k, const hsk_clearance_params& cp, const hsk_rea
   return HSK_OK;
 }
 
+int relax_rounds(hsk_ctx* k, const std::function<hipError_t(int, unsigned)>& launch_round, const unsigned long long* lengths, unsigned long long n_active,
+                 const char* what, uint32_t* rounds, unsigned long long* tiles) {
+  *rounds = 0;
+  *tiles = 0;
+  int cur = 0;
+  while (n_active) {  // (ends: at HSK_REACH_MAX_ROUNDS at the latest)
+    if (*rounds >= HSK_REACH_MAX_ROUNDS)
+      return fail(k, HSK_ERR_STATE, (std::string(what) + " did not settle within HSK_REACH_MAX_ROUNDS rounds").c_str());
+    HIPCHK(k, launch_round(cur, (unsigned)n_active));
+    *tiles += n_active;
+    *rounds += 1;
+    cur ^= 1;
+    if (int r = read_u64(k, &n_active, lengths + cur)) return r;
+  }
+  return HSK_OK;
+}
+
 // The relaxation of one grid: init from the clearance values d2, the seeds (n_seeds voxels at d_seeds), rounds until a round marks
 // no tile.  counts: passable, reached, the largest value, the seeds used.
 static int reach_run(hsk_ctx* k, const unsigned* d2, const ReachGeom& q, const ReachBufs& b, const unsigned* d_seeds, unsigned n_seeds,
@@ -78,17 +96,8 @@ static int reach_run(hsk_ctx* k, const unsigned* d2, const ReachGeom& q, const R
     HIPCHK(k, hipGetLastError());
     if (int r = read_u64(k, &n_active, b.counters + 4)) return r;
   }
-  *rounds = 0;
-  *tiles = 0;
-  int cur = 0;
-  while (n_active) {  // (ends: at HSK_REACH_MAX_ROUNDS at the latest)
-    if (*rounds >= HSK_REACH_MAX_ROUNDS) return fail(k, HSK_ERR_STATE, "the reach field did not settle within HSK_REACH_MAX_ROUNDS rounds");
-    HIPCHK(k, launch_reach_round(k->stream, q, b, cur, (unsigned)n_active));
-    *tiles += n_active;
-    *rounds += 1;
-    cur ^= 1;
-    if (int r = read_u64(k, &n_active, b.counters + 4 + cur)) return r;
-  }
+  auto round = [&](int cur, unsigned n) { return launch_reach_round(k->stream, q, b, cur, n); };
+  if (int r = relax_rounds(k, round, b.counters + 4, n_active, "the reach field", rounds, tiles)) return r;
   launch_reach_stats(k->stream, q, b);
   HIPCHK(k, hipGetLastError());
   if (int r = read_u64(k, counts, b.counters, 4)) return r;
@@ -179,21 +188,15 @@ static int reach_held(hsk_ctx* k, const char* who) {
 extern "C" int hsk_download_reach(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* g) {
   if (!k) return HSK_ERR_ARG;
   if (!g) return fail(k, HSK_ERR_ARG, "hsk_download_reach: g is null");
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
   hsk_voxel_box b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = box ? box->lo[i] : 0;
-    b.hi[i] = box ? box->hi[i] : dims[i];
-    if (b.lo[i] < 0 || b.hi[i] > dims[i] || b.hi[i] < b.lo[i])
-      return fail(k, HSK_ERR_ARG, "hsk_download_reach: the box must satisfy 0 <= lo <= hi <= the volume's dims on every axis");
-  }
+  size_t n;
+  if (int rc = clear_box_check(k, box, "hsk_download_reach", &b, &n)) return rc;
   if (int rc = reach_held(k, "hsk_download_reach")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ReachBufs rb;
   reach_layout(k->reach_q, k->d_reach, &rb);
-  const size_t n = (size_t)(b.hi[0] - b.lo[0]) * (size_t)(b.hi[1] - b.lo[1]) * (size_t)(b.hi[2] - b.lo[2]);
   if (n == 0) return HSK_OK;
-  if (n == (size_t)dims[0] * dims[1] * dims[2]) return copy_out(k, g, rb.field, n * 4);
+  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, g, rb.field, n * 4);
   int r = ensure_product_bytes(k, n * 4);
   if (r != HSK_OK) return r;
   launch_clear_box(k->stream, rb.field, k->vp, b.lo, b.hi, (unsigned*)k->d_out);
@@ -210,15 +213,8 @@ extern "C" int hsk_reach_at(hsk_ctx* k, const float* xyz, size_t n, uint32_t* g)
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ReachBufs rb;
   reach_layout(k->reach_q, k->d_reach, &rb);
-  ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
-  char* base = (char*)k->d_out;
-  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch_clear_gather(k->stream, rb.field, k->vp, (const float*)(base + pts_at), (unsigned)n, (unsigned*)(base + out_at));  // (OUTSIDE is the same word)
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, g, base + out_at, n * 4);
+  // (the clearance field's gather: OUTSIDE is the same word)
+  return gather_points(k, xyz, n, g, [&](const float* pts, unsigned* out) { launch_clear_gather(k->stream, rb.field, k->vp, pts, (unsigned)n, out); });
 }
 
 extern "C" int hsk_reach_path(hsk_ctx* k, const float goal_xyz[3], int32_t* voxels_xyz, size_t cap, size_t* n) {
@@ -282,18 +278,14 @@ extern "C" int hsk_reach_floor(hsk_ctx* k, const hsk_clearance_params* cparams, 
   hsk_reach_params p;
   if (int rc = clear_check(k, cparams, "hsk_reach_floor", &cp, &cq)) return rc;
   if (int rc = reach_check(k, cp, params, seeds_xyz, n_seeds, "hsk_reach_floor", &p)) return rc;
-  if (axis < 0 || axis > 2) return fail(k, HSK_ERR_ARG, "hsk_reach_floor: axis must be 0, 1 or 2");
-  const int dims[3] = {k->vp.X, k->vp.Y, k->vp.Z};
-  if (lo < 0 || hi > dims[axis] || hi < lo) return fail(k, HSK_ERR_ARG, "hsk_reach_floor: the band must satisfy 0 <= lo <= hi <= the axis");
+  FloorGrid f;
+  if (int rc = clear_floor_grid(k, cq, axis, lo, hi, "hsk_reach_floor", &f)) return rc;
   if (int rc = clear_state_check(k, "hsk_reach_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // the map's grid: (u, v, 1), u the lower-numbered remaining axis; the same kernels, on which no move along the third axis is
   // ever allowed (its neighbours lie outside the grid)
-  const int au = axis == 0 ? 1 : 0, av = axis == 2 ? 1 : 2;
-  const unsigned nu = (unsigned)dims[au], nv = (unsigned)dims[av];
-  const unsigned w[3] = {cq.w[au], cq.w[av], cq.w[axis]};
   ReachGeom q;
-  reach_geom(nu, nv, 1u, w, p.min_d2, p.max_cost, &q);
+  reach_geom(f.nu, f.nv, 1u, f.w, p.min_d2, p.max_cost, &q);
   // the seeds, projected by dropping the up axis: that coordinate does not count, whatever it holds
   const SampleVol sv = hsk_sample_vol(k->vp);
   std::vector<uint32_t> vox;
@@ -304,9 +296,9 @@ extern "C" int hsk_reach_floor(hsk_ctx* k, const hsk_clearance_params* cparams, 
     unsigned g[3];
     bool inside;
     clear_point_voxel(sv, c[0], c[1], c[2], g[0], g[1], g[2], inside);
-    if (inside) vox.push_back((uint32_t)((size_t)g[av] * nu + g[au]));
+    if (inside) vox.push_back((uint32_t)((size_t)g[f.av] * f.nu + g[f.au]));
   }
-  const size_t n = (size_t)nu * nv;
+  const size_t n = (size_t)f.nu * f.nv;
   ProductLayout lay;
   const size_t a_at = lay.take(n * 4), b_at = lay.take(n * 4), seeds_at = lay.take((size_t)HSK_REACH_MAX_SEEDS * 4);
   const size_t reach_at = lay.take(reach_layout(q, nullptr, nullptr));

@@ -81,15 +81,6 @@ struct ClearLoadU32 {
   __device__ __forceinline__ unsigned operator()(unsigned i) const { return p[(size_t)i * stride]; }
 };
 
-static __device__ __forceinline__ unsigned clear_wave_max(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
 // AXIS 1: the y pass, uint16 distances in, capped sums out (CLEAR_INF above max_d2).  AXIS 2: the z pass, those in, the field out
 // (CLEAR_FAR above max_d2) and the counts.  Grid: x segments of 64 x segments of the axis x the third axis; a wave a segment.
 template <int AXIS>
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(256) void k_clear_axis(const void* __restrict__ in,
   }
   if (AXIS == 2) {  // (every lane of the wave arrives here: nothing above returns)
     n_far = hsk_wave_sum(n_far);
-    seen = clear_wave_max(seen);
+    seen = hsk_wave_max(seen);
     if (lane == 0u) {
       if (n_far) atomicAdd(&stats[1], (unsigned long long)n_far);
       if (seen) atomicMax(&stats[2], (unsigned long long)seen);

@@ -27,41 +27,6 @@
 #include "hsk_launch.h"
 #include "hsk_comp_point.h"
 
-// the kernels' loads and minimum: a relaxed load that other workgroups' atomics are seen by (it passes the CU's L1), and the
-// hardware's integer minimum; in LDS the same at workgroup scope
-struct CompGlobalOps {
-  static __host__ __device__ __forceinline__ unsigned load(const unsigned* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return *p;
-#endif
-  }
-  static __host__ __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicMin(p, v);
-#else
-    return CompPlainOps::fetch_min(p, v);
-#endif
-  }
-};
-struct CompLdsOps {
-  static __host__ __device__ __forceinline__ unsigned load(const unsigned* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    return *p;
-#endif
-  }
-  static __host__ __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicMin(p, v);
-#else
-    return CompPlainOps::fetch_min(p, v);
-#endif
-  }
-};
-
 // the grid, its 16-B vectors (X4 a row, Zg plane groups) and its tiles
 struct CompGeom {
   CompGrid g;
@@ -83,15 +48,6 @@ static __device__ __forceinline__ unsigned comp_wave_min(unsigned v) {
   }
   return v;
 }
-static __device__ __forceinline__ unsigned comp_wave_max(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_comp_local(const uint4* __restrict__ vol, uint4* __restrict__ parent, CompGeom q) {
   __shared__ unsigned s_lab[CT_VOX];
   const unsigned tid = threadIdx.x;
@@ -282,9 +238,9 @@ __global__ __launch_bounds__(256) void k_comp_records(const uint4* __restrict__ 
   if (__all(one && (!has || key == k_min))) {
     if (k_min == COMP_NONE) return;  // (the whole wave)
     const unsigned c = hsk_wave_sum(cnt);
-    const unsigned x_lo = comp_wave_min(has ? x0 + j_lo : COMP_NONE), x_hi = comp_wave_max(has ? x0 + j_hi : 0u);
-    const unsigned y_lo = comp_wave_min(has ? y : COMP_NONE), y_hi = comp_wave_max(has ? y + 1u : 0u);
-    const unsigned z_lo = comp_wave_min(has ? z : COMP_NONE), z_hi = comp_wave_max(has ? z + 1u : 0u);
+    const unsigned x_lo = comp_wave_min(has ? x0 + j_lo : COMP_NONE), x_hi = hsk_wave_max(has ? x0 + j_hi : 0u);
+    const unsigned y_lo = comp_wave_min(has ? y : COMP_NONE), y_hi = hsk_wave_max(has ? y + 1u : 0u);
+    const unsigned z_lo = comp_wave_min(has ? z : COMP_NONE), z_hi = hsk_wave_max(has ? z + 1u : 0u);
     if (lane == 0u) {
       const unsigned at = comp_search(roots, n, k_min);  // (ends: the interval halves)
       if (at < n) comp_record_add(table + (size_t)at * 8u, c, x_lo, x_hi, y_lo, y_hi, z_lo, z_hi);

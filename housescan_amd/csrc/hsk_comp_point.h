@@ -2,7 +2,8 @@
 // lin(x, y, z) = (z Y + y) X + x and where its parent lives, and the union-find every kernel of components.hip runs -- `find`
 // and `unite` over an array of parents.  Plain C++ with no HIP type in it: the atomic minimum and the load are a template
 // argument, so tests/comp_point_harness.cpp compiles the same text for the host with a plain minimum and labels a volume
-// sequentially, and tests/test_components_host.py compares it with the numpy twin (tests/components_twin.py).
+// sequentially, and tests/test_components_host.py compares it with the numpy twin (tests/components_twin.py).  The kernels' two
+// sets of atomic operations stand beside the sequential ones, for the device compiler alone.
 //
 // THE INVARIANT every loop below rests on: parent[v] <= v, always, for every v that is a member.  An entry starts as v, and is
 // only ever lowered (an atomic minimum with a smaller member of the same component).  So a walk v -> parent[v] -> ... is
@@ -59,6 +60,18 @@ struct CompPlainOps {
     return old;
   }
 };
+#if defined(__HIPCC__)
+// the kernels' operations (components.hip, partition.hip): a relaxed load that other workgroups' atomics are seen by (it passes the
+// CU's L1), and the hardware's integer minimum; in LDS the same at workgroup scope
+struct CompGlobalOps {
+  static __device__ __forceinline__ unsigned load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return atomicMin(p, v); }
+};
+struct CompLdsOps {
+  static __device__ __forceinline__ unsigned load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return atomicMin(p, v); }
+};
+#endif
 
 // the root of member v.  Terminates: parent[u] <= u (the invariant above), so u strictly decreases until parent[u] == u.
 template <class Ops, class Map>

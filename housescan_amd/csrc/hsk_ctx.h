@@ -7,6 +7,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -291,6 +292,24 @@ int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who,
 int clear_state_check(hsk_ctx* k, const char* who);
 int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused);
 void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]);
+// the box a read works on (NULL: the whole volume) in *b and its voxels in *n, or HSK_ERR_ARG: "<who>: the box must satisfy ..."
+int clear_box_check(hsk_ctx* k, const hsk_voxel_box* box, const char* who, hsk_voxel_box* b, size_t* n);
+// a floor map's grid, (u, v, 1) with u the lower-numbered of the two axes that remain: their numbers and lengths, and the weights
+// permuted to (u, v, axis); the axis and the band lo <= p < hi are checked first ("<who>: axis must be ...", "<who>: the band ...")
+struct FloorGrid {
+  int au, av;
+  unsigned nu, nv, w[3];
+};
+int clear_floor_grid(hsk_ctx* k, const ClearGeom& q, int axis, int lo, int hi, const char* who, FloorGrid* f);
+// n > 0 points (packed triples) go to the product buffer, launch(device points, device words) gathers a word a point, the n words
+// come back into out
+int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*)>& launch);
+// ---- api_reach.hip ----
+// The rounds of a tile relaxation: while the current worklist holds tiles -- n_active at first, in list 0 --, launch_round(cur, its
+// length) relaxes them and fills the other list, whose length the host then reads from lengths[cur ^ 1] on the device.  *rounds and
+// *tiles: the rounds run and the tiles relaxed.  HSK_ERR_STATE after HSK_REACH_MAX_ROUNDS: "<what> did not settle within ..."
+int relax_rounds(hsk_ctx* k, const std::function<hipError_t(int, unsigned)>& launch_round, const unsigned long long* lengths, unsigned long long n_active,
+                 const char* what, uint32_t* rounds, unsigned long long* tiles);
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

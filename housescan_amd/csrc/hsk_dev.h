@@ -181,6 +181,15 @@ static __device__ __forceinline__ T hsk_wave_sum(T v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// the largest of an unsigned word over the wave's 64 lanes, in every lane (likewise)
+static __device__ __forceinline__ unsigned hsk_wave_max(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
+    v = u > v ? u : v;
+  }
+  return v;
+}
 
 // round-to-nearest-even with the +-1e6 range guard of the spec
 static __device__ __forceinline__ bool hsk_rint_guard(float f, int& out) {

@@ -1,6 +1,6 @@
 // hsk_part_point.h -- the room partition (DESIGN.md 8n the rule, 3.20 the kernels): the 64-bit key (cost, label of the core the
-// chain starts in) a voxel holds, one tile's relaxation on such keys -- templated on its load and store, as the reach field's is
-// --, the order of the room records and the point lookup's search.  The moves, the box rule, the costs, the halo's index and the
+// chain starts in) a voxel holds, the value policy that makes the reach field's tile relaxation one on such keys, the order of the
+// room records and the point lookup's search.  The moves, the box rule, the costs, the tile relaxation, the halo's index and the
 // tiles a voxel is seen by are hsk_reach_point.h's, the union-find of the core labelling hsk_comp_point.h's: this file restates
 // none of them.  Plain C++ with no HIP type in it, so that tests/part_point_harness.cpp compiles the same text for the host and
 // tests/test_partition_host.py compares what it makes with the numpy twin (tests/partition_twin.py).  All integers.
@@ -13,7 +13,8 @@
 //
 // A KEY MUST NEVER BE READ OR WRITTEN IN HALVES where another worker may touch it: a torn key (new G, old L) can lie BELOW the
 // fixpoint -- the smaller cost of one core with the smaller label of another -- and a relaxation only ever lowers, so the result
-// would be wrong, not merely late.  The load and the store are therefore template arguments; the kernels pass 64-bit atomics.
+// would be wrong, not merely late.  The relaxation's tile, load and store are therefore template arguments; the kernels pass 64-bit
+// atomics.
 #pragma once
 #include "hsk_comp_point.h"
 #include "hsk_reach_point.h"
@@ -37,84 +38,15 @@ HSK_HD bool part_is_value(part_key k) { return reach_is_value(part_g(k)); }  // 
 HSK_HD bool part_core(unsigned d2, unsigned core_d2) { return d2 >= core_d2; }  // (CLEAR_FAR = 0xffffffff passes)
 
 // ---- one tile in a local store --------------------------------------------------------------------------------------------------
-// `Cells` is the reach field's tile with 64-bit cells: k(x, y, z) / set(x, y, z, v) with -1 <= x <= REACH_TILE_X (and so on; only
-// interior cells are ever set), moves(i) / set_moves(i, m).  A cell outside the grid holds PART_KEY_BLOCKED.
-
-template <class Cells, class Load>
-HSK_HD void part_tile_load(Cells& s, const Load& ld, unsigned ox, unsigned oy, unsigned oz, unsigned X, unsigned Y, unsigned Z, unsigned lane,
-                           unsigned nlanes) {
-  for (unsigned i = lane; i < (unsigned)REACH_HALO_CELLS; i += nlanes) {  // (ends: i grows by nlanes)
-    const int hx = (int)(i % REACH_HALO_X) - 1, hy = (int)((i / REACH_HALO_X) % REACH_HALO_Y) - 1, hz = (int)(i / (REACH_HALO_X * REACH_HALO_Y)) - 1;
-    const long long gx = (long long)ox + hx, gy = (long long)oy + hy, gz = (long long)oz + hz;
-    const bool in = gx >= 0 && gx < (long long)X && gy >= 0 && gy < (long long)Y && gz >= 0 && gz < (long long)Z;
-    s.set(hx, hy, hz, in ? ld(((size_t)gz * Y + (size_t)gy) * X + (size_t)gx) : PART_KEY_BLOCKED);
-  }
-}
-
-// the allowed moves of every interior voxel (hsk_reach_point.h: reach_moves_of), from the cells as loaded
-template <class Cells>
-HSK_HD void part_tile_moves(Cells& s, unsigned lane, unsigned nlanes) {
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
-    const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
-    unsigned pass = 0u;
-REACH_UNROLL
-    for (int c = 0; c < REACH_MOVES; ++c) pass |= s.k(x + reach_dx(c), y + reach_dy(c), z + reach_dz(c)) != PART_KEY_BLOCKED ? 1u << c : 0u;
-    s.set_moves(i, reach_moves_of(pass));
-  }
-}
-
-// one voxel: the least of its key and, over its allowed moves, the neighbour's key plus the move's cost, where that cost sum is at
-// most max_cost.  A neighbour that holds no room offers nothing.
-template <class Cells>
-HSK_HD part_key part_relax_voxel(const Cells& s, int x, int y, int z, unsigned moves, const unsigned* cost, unsigned max_cost) {
-  part_key best = s.k(x, y, z);
-REACH_UNROLL
-  for (int m = 0; m < REACH_MOVES; ++m) {
-    if (m == REACH_CENTRE || !((moves >> m) & 1u)) continue;
-    const part_key n = s.k(x + reach_dx(m), y + reach_dy(m), z + reach_dz(m));
-    if (!part_is_value(n)) continue;
-    const part_key cand = n + ((part_key)cost[m] << 32);  // (G + c < 2^32: the bound above)
-    best = (part_g(cand) <= max_cost && cand < best) ? cand : best;
-  }
-  return best;
-}
-
-// one sweep of this worker's voxels, in place (a key read while another worker lowers it is the old or the new one, whole: both
-// are upper bounds of the fixpoint) -> whether any of them fell
-template <class Cells>
-HSK_HD bool part_tile_sweep(Cells& s, unsigned lane, unsigned nlanes, const unsigned* cost, unsigned max_cost) {
-  bool fell = false;
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
-    const unsigned moves = s.moves(i);
-    if (!moves) continue;
-    const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
-    const part_key v = part_relax_voxel(s, x, y, z, moves, cost, max_cost);
-    if (v < s.k(x, y, z)) {
-      s.set(x, y, z, v);
-      fell = true;
-    }
-  }
-  return fell;
-}
-
-// store: every interior voxel whose key fell below the field's goes back -> the tiles that can see a voxel that fell
-// (hsk_reach_point.h: reach_seen_by), a bit per tile offset.  Only the worker of a tile ever stores its interior voxels.
-template <class Cells, class Load, class Store>
-HSK_HD unsigned part_tile_store(const Cells& s, const Load& ld, const Store& st, unsigned ox, unsigned oy, unsigned oz, unsigned X, unsigned Y, unsigned Z,
-                                unsigned lane, unsigned nlanes) {
-  unsigned seen_by = 0u;
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
-    const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
-    const unsigned gx = ox + (unsigned)x, gy = oy + (unsigned)y, gz = oz + (unsigned)z;
-    if (gx >= X || gy >= Y || gz >= Z) continue;
-    const size_t at = ((size_t)gz * Y + gy) * X + gx;
-    const part_key v = s.k(x, y, z);
-    if (v >= ld(at)) continue;
-    st(at, v);
-    seen_by |= reach_seen_by(x, y, z);
-  }
-  return seen_by;
-}
+// The tile relaxation is hsk_reach_point.h's (reach_tile_load / _moves / _sweep / _store) with this value policy: a cell is a key,
+// a move adds (c << 32) -- G + c < 2^32 by THE BOUND, so nothing is carried out of the word -- and max_cost bounds G.
+struct PartValue {
+  typedef part_key T;
+  HSK_HD T blocked() { return PART_KEY_BLOCKED; }
+  HSK_HD bool is_value(T k) { return part_is_value(k); }
+  HSK_HD T plus(T k, unsigned cost) { return k + ((part_key)cost << 32); }
+  HSK_HD unsigned cost(T k) { return part_g(k); }
+};
 
 // ---- the point lookup -----------------------------------------------------------------------------------------------------------
 // Among the voxels within |dx|, |dy|, |dz| <= radius of (x, y, z) that lie in the grid and hold a room, the one that minimises

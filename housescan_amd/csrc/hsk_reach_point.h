@@ -1,6 +1,7 @@
 // hsk_reach_point.h -- the reach field (DESIGN.md 8m the rule, 3.19 the kernels): which voxels a person can stand in, which of the
-// 26 moves between them are allowed (the box rule), what a move costs, one tile's relaxation -- templated on its load and store --
-// and the step of the path trace.  Plain C++ with no HIP type in it, so that tests/reach_point_harness.cpp compiles the same text
+// 26 moves between them are allowed (the box rule), what a move costs, one tile's relaxation -- templated on the value a cell holds
+// (the room partition relaxes its 64-bit keys with the same text: hsk_part_point.h) and on its load and store -- and the step of
+// the path trace.  Plain C++ with no HIP type in it, so that tests/reach_point_harness.cpp compiles the same text
 // for the host and tests/test_reach_host.py compares the field it makes with the numpy twin (tests/reach_twin.py).  All integers.
 //
 // THE METRIC is a 26-neighbour chamfer metric, NOT the Euclidean geodesic: a path is a chain of the 26 moves, each at its Euclidean
@@ -82,10 +83,23 @@ REACH_UNROLL
 }
 
 // ---- one tile in a local store --------------------------------------------------------------------------------------------------
-// `Cells` is a tile with its one-voxel halo and a word per interior voxel for its allowed moves: g(x, y, z) / set(x, y, z, v) with
+// ONE relaxation text for every field over the free space, templated on a value policy `V`: V::T the cell's type, V::blocked() the
+// marker of a cell that is not passable, V::is_value(v) whether a cell holds a value that can be propagated, V::plus(v, cost) the
+// value one move of that cost further and V::cost(v) the cost sum it carries, which max_cost bounds.  plus must preserve the
+// order of values and must not wrap (THE BOUND above); then the least fixpoint does not depend on the order of the work.
+// ReachValue below is the reach field's policy, PartValue (hsk_part_point.h) the room partition's.
+//
+// `Cells` is a tile with its one-voxel halo and a word per interior voxel for its allowed moves: at(x, y, z) / set(x, y, z, v) with
 // -1 <= x <= REACH_TILE_X (and so on; only interior cells are ever set), moves(i) / set_moves(i, m) with i the interior voxel's
-// index (z REACH_TILE_Y + y) REACH_TILE_X + x.  A cell outside the grid holds REACH_BLOCKED.  `lane` of `nlanes` workers takes the
+// index (z REACH_TILE_Y + y) REACH_TILE_X + x.  A cell outside the grid holds V::blocked().  `lane` of `nlanes` workers takes the
 // voxels i = lane, lane + nlanes, ...: the device runs 256 of them with a barrier between the steps, the host harness one.
+struct ReachValue {
+  typedef unsigned T;
+  HSK_HD T blocked() { return REACH_BLOCKED; }
+  HSK_HD bool is_value(T v) { return reach_is_value(v); }
+  HSK_HD T plus(T v, unsigned cost) { return v + cost; }  // (below 2^32: THE BOUND)
+  HSK_HD unsigned cost(T v) { return v; }
+};
 
 // the index into a halo array of REACH_HALO_CELLS words
 HSK_HD unsigned reach_halo_index(int x, int y, int z) {
@@ -93,56 +107,56 @@ HSK_HD unsigned reach_halo_index(int x, int y, int z) {
 }
 
 // load: the tile at voxel (ox, oy, oz) with its halo from the field `ld(linear index)` of an X Y Z grid
-template <class Cells, class Load>
+template <class V, class Cells, class Load>
 HSK_HD void reach_tile_load(Cells& s, const Load& ld, unsigned ox, unsigned oy, unsigned oz, unsigned X, unsigned Y, unsigned Z, unsigned lane,
                             unsigned nlanes) {
   for (unsigned i = lane; i < (unsigned)REACH_HALO_CELLS; i += nlanes) {  // (ends: i grows by nlanes)
     const int hx = (int)(i % REACH_HALO_X) - 1, hy = (int)((i / REACH_HALO_X) % REACH_HALO_Y) - 1, hz = (int)(i / (REACH_HALO_X * REACH_HALO_Y)) - 1;
     const long long gx = (long long)ox + hx, gy = (long long)oy + hy, gz = (long long)oz + hz;
     const bool in = gx >= 0 && gx < (long long)X && gy >= 0 && gy < (long long)Y && gz >= 0 && gz < (long long)Z;
-    s.set(hx, hy, hz, in ? ld(((size_t)gz * Y + (size_t)gy) * X + (size_t)gx) : REACH_BLOCKED);
+    s.set(hx, hy, hz, in ? ld(((size_t)gz * Y + (size_t)gy) * X + (size_t)gx) : V::blocked());
   }
 }
 
-// the allowed moves of every interior voxel, from the cells as loaded (whether a cell is BLOCKED never changes afterwards)
-template <class Cells>
+// the allowed moves of every interior voxel, from the cells as loaded (whether a cell is blocked never changes afterwards)
+template <class V, class Cells>
 HSK_HD void reach_tile_moves(Cells& s, unsigned lane, unsigned nlanes) {
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {
+  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
     const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
     unsigned pass = 0u;
 REACH_UNROLL
-    for (int c = 0; c < REACH_MOVES; ++c) pass |= s.g(x + reach_dx(c), y + reach_dy(c), z + reach_dz(c)) != REACH_BLOCKED ? 1u << c : 0u;
+    for (int c = 0; c < REACH_MOVES; ++c) pass |= s.at(x + reach_dx(c), y + reach_dy(c), z + reach_dz(c)) != V::blocked() ? 1u << c : 0u;
     s.set_moves(i, reach_moves_of(pass));
   }
 }
 
-// one voxel: the least of its value and, over its allowed moves, the neighbour's value plus the move's cost, where that is at most
-// max_cost.  A neighbour that holds no value (UNREACHED) offers nothing.
-template <class Cells>
-HSK_HD unsigned reach_relax_voxel(const Cells& s, int x, int y, int z, unsigned moves, const unsigned* cost, unsigned max_cost) {
-  unsigned best = s.g(x, y, z);
+// one voxel: the least of its value and, over its allowed moves, the neighbour's value plus the move's cost, where that cost sum
+// is at most max_cost.  A neighbour that holds no value (UNREACHED, UNASSIGNED) offers nothing.
+template <class V, class Cells>
+HSK_HD typename V::T reach_relax_voxel(const Cells& s, int x, int y, int z, unsigned moves, const unsigned* cost, unsigned max_cost) {
+  typename V::T best = s.at(x, y, z);
 REACH_UNROLL
   for (int m = 0; m < REACH_MOVES; ++m) {
     if (m == REACH_CENTRE || !((moves >> m) & 1u)) continue;
-    const unsigned n = s.g(x + reach_dx(m), y + reach_dy(m), z + reach_dz(m));
-    if (!reach_is_value(n)) continue;
-    const unsigned cand = n + cost[m];
-    best = (cand <= max_cost && cand < best) ? cand : best;
+    const typename V::T n = s.at(x + reach_dx(m), y + reach_dy(m), z + reach_dz(m));
+    if (!V::is_value(n)) continue;
+    const typename V::T cand = V::plus(n, cost[m]);
+    best = (V::cost(cand) <= max_cost && cand < best) ? cand : best;
   }
   return best;
 }
 
-// one sweep of this worker's voxels, in place (a value read while another worker lowers it is the old or the new one: both are
-// upper bounds of the fixpoint) -> whether any of them fell
-template <class Cells>
+// one sweep of this worker's voxels, in place (a value read while another worker lowers it is the old or the new one, whole: both
+// are upper bounds of the fixpoint) -> whether any of them fell
+template <class V, class Cells>
 HSK_HD bool reach_tile_sweep(Cells& s, unsigned lane, unsigned nlanes, const unsigned* cost, unsigned max_cost) {
   bool fell = false;
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {
+  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
     const unsigned moves = s.moves(i);
     if (!moves) continue;
     const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
-    const unsigned v = reach_relax_voxel(s, x, y, z, moves, cost, max_cost);
-    if (v < s.g(x, y, z)) {
+    const typename V::T v = reach_relax_voxel<V>(s, x, y, z, moves, cost, max_cost);
+    if (v < s.at(x, y, z)) {
       s.set(x, y, z, v);
       fell = true;
     }
@@ -165,19 +179,18 @@ HSK_HD unsigned reach_seen_by(int x, int y, int z) {
 }
 
 // store: every interior voxel whose value fell below the field's goes back -> the neighbouring tiles that can see a voxel that
-// fell, a bit per tile offset (indexed as the moves; the centre bit says that anything fell at all).  A voxel on a face of the
-// tile is seen across that face, one on an edge or a corner across the two or three faces and the edge or corner itself: a
-// diagonal move crosses them.
-template <class Cells, class Load, class Store>
+// fell (reach_seen_by), a bit per tile offset (indexed as the moves; the centre bit says that anything fell at all).  Only the
+// worker of a tile ever stores its interior voxels.
+template <class V, class Cells, class Load, class Store>
 HSK_HD unsigned reach_tile_store(const Cells& s, const Load& ld, const Store& st, unsigned ox, unsigned oy, unsigned oz, unsigned X, unsigned Y,
                                  unsigned Z, unsigned lane, unsigned nlanes) {
   unsigned seen_by = 0u;
-  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {
+  for (unsigned i = lane; i < (unsigned)REACH_TILE_VOXELS; i += nlanes) {  // (ends: i grows by nlanes)
     const int x = (int)(i % REACH_TILE_X), y = (int)((i / REACH_TILE_X) % REACH_TILE_Y), z = (int)(i / (REACH_TILE_X * REACH_TILE_Y));
     const unsigned gx = ox + (unsigned)x, gy = oy + (unsigned)y, gz = oz + (unsigned)z;
     if (gx >= X || gy >= Y || gz >= Z) continue;
     const size_t at = ((size_t)gz * Y + gy) * X + gx;
-    const unsigned v = s.g(x, y, z);
+    const typename V::T v = s.at(x, y, z);
     if (v >= ld(at)) continue;
     st(at, v);
     seen_by |= reach_seen_by(x, y, z);

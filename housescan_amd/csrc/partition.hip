@@ -10,7 +10,7 @@
 // neighbours across them by atomic minima in global memory.  k_part_flatten_count: parent = root, and the root's slot of the key
 // array -- idle until the init -- counts the core's voxels.  k_part_roots: the cores are counted and those of min_core voxels kept.
 // k_part_init: (0, label), UNASSIGNED or BLOCKED per voxel; the tiles that hold an UNASSIGNED voxel make the first worklist.
-// k_part_round: the reach field's tile relaxation (reach.hip: k_reach_round) on 64-bit keys.
+// k_part_round: the reach field's tile relaxation (hsk_relax_dev.h: hsk_relax_round, k_reach_round's body too) on 64-bit keys.
 // k_part_records, k_part_doors: one sweep each, integer atomics only.  k_part_box, k_part_gather: the reads.
 #pragma clang fp contract(off)
 #include <algorithm>
@@ -20,22 +20,12 @@
 #include "hsk_launch.h"
 #include "hsk_clear_point.h"
 #include "hsk_part_point.h"
+#include "hsk_relax_dev.h"
 
 static_assert(REACH_TILE_X * REACH_TILE_Y == 256, "the tile kernels: a thread per (x, y) of the tile");
 static_assert(REACH_TILE_X == 32 && REACH_TILE_Y == 8 && REACH_TILE_Z == 8, "k_part_label_faces tests a voxel's place in its tile with these");
 static_assert(PART_MAX_ROOMS == 1024 && PART_REC_WORDS == 16 && PART_DOOR_WORDS == 8, "the tables in LDS and the sums' layout");
 static_assert(32 * PART_DOOR_WORDS == 256, "k_part_doors clears its slots a thread a word");
-
-// the union-find's loads and minimum (as components.hip's): a relaxed load that other workgroups' atomics are seen by, and the
-// hardware's integer minimum; in LDS the same at workgroup scope
-struct PartGlobalOps {
-  static __device__ __forceinline__ unsigned load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return atomicMin(p, v); }
-};
-struct PartLdsOps {
-  static __device__ __forceinline__ unsigned load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-  static __device__ __forceinline__ unsigned fetch_min(unsigned* p, unsigned v) { return atomicMin(p, v); }
-};
 
 // ---- the core labelling -------------------------------------------------------------------------------------------------------
 // grid: the tiles.  Thread (x, y) of the tile takes its 8 voxels along z.  The local label of a voxel is its index in the tile,
@@ -61,10 +51,10 @@ __global__ __launch_bounds__(256) void k_part_label_tile(const unsigned* __restr
 #pragma unroll 1
   for (unsigned z = 0u; z < (unsigned)REACH_TILE_Z; ++z) {  // (8 trips)
     const unsigned i = z * 256u + tid;
-    if (PartLdsOps::load(s_par + i) == COMP_NONE) continue;
-    if (lx > 0u && PartLdsOps::load(s_par + i - 1u) != COMP_NONE) comp_unite<PartLdsOps>(s_par, map, i, i - 1u);
-    if (ly > 0u && PartLdsOps::load(s_par + i - REACH_TILE_X) != COMP_NONE) comp_unite<PartLdsOps>(s_par, map, i, i - REACH_TILE_X);
-    if (z > 0u && PartLdsOps::load(s_par + i - 256u) != COMP_NONE) comp_unite<PartLdsOps>(s_par, map, i, i - 256u);
+    if (CompLdsOps::load(s_par + i) == COMP_NONE) continue;
+    if (lx > 0u && CompLdsOps::load(s_par + i - 1u) != COMP_NONE) comp_unite<CompLdsOps>(s_par, map, i, i - 1u);
+    if (ly > 0u && CompLdsOps::load(s_par + i - REACH_TILE_X) != COMP_NONE) comp_unite<CompLdsOps>(s_par, map, i, i - REACH_TILE_X);
+    if (z > 0u && CompLdsOps::load(s_par + i - 256u) != COMP_NONE) comp_unite<CompLdsOps>(s_par, map, i, i - 256u);
   }
   __syncthreads();
 #pragma unroll 1
@@ -76,7 +66,7 @@ __global__ __launch_bounds__(256) void k_part_label_tile(const unsigned* __restr
       parent[at] = COMP_NONE;
       continue;
     }
-    const unsigned r = comp_find<PartLdsOps>(s_par, map, i);
+    const unsigned r = comp_find<CompLdsOps>(s_par, map, i);
     const unsigned rx = r % REACH_TILE_X, ry = (r / REACH_TILE_X) % REACH_TILE_Y, rz = r / 256u;
     parent[at] = ((oz + rz) * q.Y + (ty * REACH_TILE_Y + ry)) * q.X + (tx * REACH_TILE_X + rx);
     if (r == i) keys[at] = 0ull;  // (the slot that counts the core's voxels, should this voxel stay a root)
@@ -91,21 +81,21 @@ __global__ __launch_bounds__(256) void k_part_label_faces(unsigned* parent, Part
   const unsigned row = e / q.X, x = e - row * q.X, z = row / q.Y, y = row - z * q.Y;
   const bool fx = x > 0u && (x % REACH_TILE_X) == 0u, fy = y > 0u && (y % REACH_TILE_Y) == 0u, fz = z > 0u && (z % REACH_TILE_Z) == 0u;
   if (!(fx || fy || fz)) return;
-  if (PartGlobalOps::load(parent + e) == COMP_NONE) return;
+  if (CompGlobalOps::load(parent + e) == COMP_NONE) return;
   const CompDirect map;
-  if (fx && PartGlobalOps::load(parent + e - 1u) != COMP_NONE) comp_unite<PartGlobalOps>(parent, map, e, e - 1u);
-  if (fy && PartGlobalOps::load(parent + e - q.X) != COMP_NONE) comp_unite<PartGlobalOps>(parent, map, e, e - q.X);
-  if (fz && PartGlobalOps::load(parent + e - q.X * q.Y) != COMP_NONE) comp_unite<PartGlobalOps>(parent, map, e, e - q.X * q.Y);
+  if (fx && CompGlobalOps::load(parent + e - 1u) != COMP_NONE) comp_unite<CompGlobalOps>(parent, map, e, e - 1u);
+  if (fy && CompGlobalOps::load(parent + e - q.X) != COMP_NONE) comp_unite<CompGlobalOps>(parent, map, e, e - q.X);
+  if (fz && CompGlobalOps::load(parent + e - q.X * q.Y) != COMP_NONE) comp_unite<CompGlobalOps>(parent, map, e, e - q.X * q.Y);
 }
 
 // a thread a voxel: parent = root (an entry only falls, so a walk through it meanwhile stays a walk to the same root), and the
 // root's slot counts.  A wave whose core voxels all have one root adds once.
 __global__ __launch_bounds__(256) void k_part_flatten_count(unsigned* parent, unsigned long long* __restrict__ keys, unsigned n) {
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
-  const bool member = e < n && PartGlobalOps::load(parent + e) != COMP_NONE;
+  const bool member = e < n && CompGlobalOps::load(parent + e) != COMP_NONE;
   unsigned r = COMP_NONE;
   if (member) {
-    r = comp_find<PartGlobalOps>(parent, CompDirect(), e);
+    r = comp_find<CompGlobalOps>(parent, CompDirect(), e);
     __hip_atomic_store(parent + e, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   const unsigned long long mask = __ballot(member);  // (every lane of the wave arrives here)
@@ -167,34 +157,13 @@ __global__ __launch_bounds__(256) void k_part_init(const unsigned* __restrict__ 
   if ((tid & 63u) == 0u && pass) atomicAdd(&counters[0], (unsigned long long)pass);
   // only the tile that holds a voxel can lower it, and only an UNASSIGNED voxel can fall (a cost is positive, so nothing falls
   // below (0, label)): the tiles that hold one are all the first round can need
-  if (__syncthreads_or(open ? 1 : 0) && tid == 0u) {
-    flags[tile] = 1u;
-    list[atomicAdd(&counters[4], 1ull)] = tile;  // (a tile once: the list's length never exceeds the number of tiles)
-  }
+  if (__syncthreads_or(open ? 1 : 0) && tid == 0u) hsk_relax_mark(tile, flags, list, &counters[4]);  // (the flags start as zeros: a tile once)
 }
 
 // ---- the relaxation -----------------------------------------------------------------------------------------------------------
-// marks a tile for the list `list` (reach.hip: reach_mark): whoever finds the flag 0 appends the tile
-static __device__ __forceinline__ void part_mark(unsigned tile, unsigned* __restrict__ flags, unsigned* __restrict__ list, unsigned long long* __restrict__ count) {
-  if (atomicAdd(&flags[tile], 1u) == 0u) list[atomicAdd(count, 1ull)] = tile;
-}
-
-// A tile in LDS, as the shared text takes it.  A cell is read and written WHOLE, by one 64-bit access: a torn key (new G, old L)
-// can lie below the fixpoint, and then the result is wrong, not merely late (hsk_part_point.h).
-struct PartTile {
-  unsigned long long* cells;
-  unsigned* mv;
-  __device__ __forceinline__ part_key k(int x, int y, int z) const {
-    return __hip_atomic_load(cells + reach_halo_index(x, y, z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  __device__ __forceinline__ void set(int x, int y, int z, part_key v) const {
-    __hip_atomic_store(cells + reach_halo_index(x, y, z), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  __device__ __forceinline__ unsigned moves(unsigned i) const { return mv[i]; }
-  __device__ __forceinline__ void set_moves(unsigned i, unsigned v) const { mv[i] = v; }
-};
 // EVERY global read and write of a key that another workgroup may touch is ONE 64-bit relaxed atomic at agent scope: a halo cell
-// another tile's workgroup stores meanwhile is read as the old or the new key, never as half of each
+// another tile's workgroup stores meanwhile is read as the old or the new key, never as half of each (in LDS likewise, at workgroup
+// scope: hsk_relax_dev.h's RelaxTile)
 struct PartLoad {
   const unsigned long long* p;
   __device__ __forceinline__ part_key operator()(size_t i) const { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -204,56 +173,17 @@ struct PartStore {
   __device__ __forceinline__ void operator()(size_t i, part_key v) const { __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 
-// grid: the tiles of list_cur, a workgroup each.  LDS: 34 x 10 x 10 keys = 27.2 KB and 8 KB of moves.
+// grid: the tiles of list_cur, a workgroup each (hsk_relax_dev.h: hsk_relax_round).  LDS: 34 x 10 x 10 keys = 27.2 KB and 8 KB of moves.
 __global__ __launch_bounds__(256) void k_part_round(unsigned long long* keys, PartGeom q, const unsigned* __restrict__ list_cur, unsigned* __restrict__ flags_cur,
                                                     unsigned* __restrict__ flags_next, unsigned* __restrict__ list_next,
                                                     unsigned long long* __restrict__ count_next) {
   __shared__ unsigned long long s_cells[REACH_HALO_CELLS];
   __shared__ unsigned s_moves[REACH_TILE_VOXELS];
-  __shared__ unsigned s_seen[REACH_MOVES];  // per tile offset: a voxel that tile can see fell (plain stores of 1)
-  const unsigned tid = threadIdx.x;
-  const unsigned tile = list_cur[blockIdx.x];
-  const unsigned tx = tile % q.ntx, ty = (tile / q.ntx) % q.nty, tz = tile / (q.ntx * q.nty);
-  const unsigned ox = tx * REACH_TILE_X, oy = ty * REACH_TILE_Y, oz = tz * REACH_TILE_Z;
-  if (tid == 0u) flags_cur[tile] = 0u;  // (this round reads this set and clears it; marks go to the other)
-  if (tid < (unsigned)REACH_MOVES) s_seen[tid] = 0u;
-  PartTile s{s_cells, s_moves};
-  const PartLoad ld{keys};
-  part_tile_load(s, ld, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
-  __syncthreads();
-  part_tile_moves(s, tid, 256u);
-  __syncthreads();
-  // The local fixpoint, Bellman-Ford in place (reach.hip: k_reach_round): a best chain inside the tile visits no voxel twice -- the
-  // costs are positive --, so at most REACH_TILE_VOXELS sweeps change anything.  The loop ends at the first sweep in which no
-  // thread lowered a key, and after REACH_TILE_VOXELS sweeps in any case.
-#pragma unroll 1
-  for (unsigned sweep = 0u; sweep < (unsigned)REACH_TILE_VOXELS; ++sweep) {
-    const bool fell = part_tile_sweep(s, tid, 256u, q.cost, q.max_cost);
-    if (!__syncthreads_or(fell ? 1 : 0)) break;  // (block-uniform)
-  }
-  const unsigned seen_by = part_tile_store(s, ld, PartStore{keys}, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
-  if (seen_by) {  // (rare: a thread whose voxels fell; several threads may store the same 1)
-    for (int m = 0; m < REACH_MOVES; ++m)  // (27 trips)
-      if ((seen_by >> m) & 1u) s_seen[m] = 1u;
-  }
-  __syncthreads();
-  if (tid < (unsigned)REACH_MOVES && tid != (unsigned)REACH_CENTRE && s_seen[tid]) {
-    const int nx = (int)tx + reach_dx((int)tid), ny = (int)ty + reach_dy((int)tid), nz = (int)tz + reach_dz((int)tid);
-    if (nx >= 0 && nx < (int)q.ntx && ny >= 0 && ny < (int)q.nty && nz >= 0 && nz < (int)q.ntz)
-      part_mark(((unsigned)nz * q.nty + (unsigned)ny) * q.ntx + (unsigned)nx, flags_next, list_next, count_next);
-  }
+  __shared__ unsigned s_seen[REACH_MOVES];
+  hsk_relax_round<PartValue>(s_cells, s_moves, s_seen, PartLoad{keys}, PartStore{keys}, q, list_cur, flags_cur, flags_next, list_next, count_next);
 }
 
 // ---- records and doors ----------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ unsigned part_wave_max(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
-
 // the index of a key's label among the ascending roots, n_kept when the key holds no room (bisection: comp_search)
 static __device__ __forceinline__ unsigned part_index_of(part_key k, const unsigned* s_roots, unsigned n_kept) {
   return part_is_value(k) ? comp_search(s_roots, n_kept, part_label(k)) : n_kept;
@@ -321,8 +251,8 @@ __global__ __launch_bounds__(256) void k_part_records(const unsigned long long* 
       const unsigned long long cores = __ballot(has && g == 0u);
       const unsigned long long sx = hsk_wave_sum<unsigned long long>(has ? x : 0u), sy = hsk_wave_sum<unsigned long long>(has ? y : 0u),
                                sz = hsk_wave_sum<unsigned long long>(has ? z : 0u);
-      const unsigned top[8] = {part_wave_max(has ? ~x : 0u), part_wave_max(has ? ~y : 0u), part_wave_max(has ? ~z : 0u), part_wave_max(has ? x : 0u),
-                               part_wave_max(has ? y : 0u),  part_wave_max(has ? z : 0u),  part_wave_max(d),             part_wave_max(has ? g : 0u)};
+      const unsigned top[8] = {hsk_wave_max(has ? ~x : 0u), hsk_wave_max(has ? ~y : 0u), hsk_wave_max(has ? ~z : 0u), hsk_wave_max(has ? x : 0u),
+                               hsk_wave_max(has ? y : 0u),  hsk_wave_max(has ? z : 0u),  hsk_wave_max(d),             hsk_wave_max(has ? g : 0u)};
       if ((int)lane == first) {
         const unsigned slot = part_slot(s_tag, idx0);
         const unsigned long long n_vox = (unsigned long long)__popcll(mask), n_core = (unsigned long long)__popcll(cores);
@@ -477,42 +407,29 @@ __global__ __launch_bounds__(256) void k_part_gather(const unsigned long long* _
 // ---- the launchers ------------------------------------------------------------------------------------------------------------
 void part_geom(unsigned X, unsigned Y, unsigned Z, const unsigned w[3], unsigned core_d2, unsigned min_d2, unsigned min_core, unsigned max_cost,
                PartGeom* q) {
-  q->X = X, q->Y = Y, q->Z = Z;
-  q->ntx = (X + REACH_TILE_X - 1u) / REACH_TILE_X;
-  q->nty = (Y + REACH_TILE_Y - 1u) / REACH_TILE_Y;
-  q->ntz = (Z + REACH_TILE_Z - 1u) / REACH_TILE_Z;
+  hsk_relax_geom(X, Y, Z, w, q);
   q->core_d2 = core_d2;
   q->min_d2 = min_d2;
   q->min_core = min_core;
   q->max_cost = max_cost;
   for (int i = 0; i < 3; ++i) q->w[i] = w[i];
-  reach_cost_table(w, q->cost);
 }
 
 size_t part_layout(const PartGeom& q, void* base, PartBufs* b) {
-  const size_t n = (size_t)q.X * q.Y * q.Z, tiles = (size_t)q.ntx * q.nty * q.ntz;
-  size_t bytes = 0;
-  auto take = [&](size_t k) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (k + 255) & ~(size_t)255;
-    return p;
-  };
+  const size_t n = (size_t)q.X * q.Y * q.Z;
+  RelaxCarve c{base};
   PartBufs out;
-  out.counters = (unsigned long long*)take(128);
-  out.keys = (unsigned long long*)take(n * 8);
-  out.parent = (unsigned*)take(n * 4);
-  for (int i = 0; i < 2; ++i) out.flags[i] = (unsigned*)take(tiles * 4);
-  for (int i = 0; i < 2; ++i) out.list[i] = (unsigned*)take(tiles * 4);
-  out.roots_found = (unsigned*)take((size_t)PART_MAX_ROOMS * 4);
-  out.roots = (unsigned*)take((size_t)PART_MAX_ROOMS * 4);
-  out.rank = (unsigned*)take((size_t)PART_MAX_ROOMS * 4);
-  out.recs = (unsigned long long*)take((size_t)PART_MAX_ROOMS * PART_REC_WORDS * 8);
+  out.counters = (unsigned long long*)c.take(128);
+  out.keys = (unsigned long long*)c.take(n * 8);
+  out.parent = (unsigned*)c.take(n * 4);
+  c.worklists((size_t)q.ntx * q.nty * q.ntz, out.flags, out.list);
+  out.roots_found = (unsigned*)c.take((size_t)PART_MAX_ROOMS * 4);
+  out.roots = (unsigned*)c.take((size_t)PART_MAX_ROOMS * 4);
+  out.rank = (unsigned*)c.take((size_t)PART_MAX_ROOMS * 4);
+  out.recs = (unsigned long long*)c.take((size_t)PART_MAX_ROOMS * PART_REC_WORDS * 8);
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
-
-// the grid of the two sweeps with a grid-stride loop: a block a 256 voxels, at most 4096 blocks (16 a CU)
-static unsigned part_sweep_blocks(unsigned long long n) { return (unsigned)std::min<unsigned long long>((n + 255u) / 256u, 4096ull); }
 
 hipError_t launch_part_label(hipStream_t s, const unsigned* d2, const PartGeom& q, const PartBufs& b) {
   const unsigned n = (unsigned)((size_t)q.X * q.Y * q.Z), tiles = q.ntx * q.nty * q.ntz;  // (at most 2^31 voxels: the callers check)
@@ -550,7 +467,7 @@ hipError_t launch_part_records(hipStream_t s, const unsigned* d2, const PartGeom
   const unsigned long long n = (unsigned long long)q.X * q.Y * q.Z;
   const hipError_t e = hipMemsetAsync(b.recs, 0, (size_t)PART_MAX_ROOMS * PART_REC_WORDS * 8, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_part_records, dim3(part_sweep_blocks(n)), dim3(256), 0, s, (const unsigned long long*)b.keys, d2, q, n, (const unsigned*)b.roots, n_kept,
+  hipLaunchKernelGGL(k_part_records, dim3(hsk_sweep_blocks(n)), dim3(256), 0, s, (const unsigned long long*)b.keys, d2, q, n, (const unsigned*)b.roots, n_kept,
                      b.recs);
   return hipGetLastError();
 }
@@ -559,7 +476,7 @@ hipError_t launch_part_doors(hipStream_t s, const unsigned* d2, const PartGeom& 
   const unsigned long long n = (unsigned long long)q.X * q.Y * q.Z;
   const hipError_t e = hipMemsetAsync(table, 0, (size_t)n_kept * n_kept * PART_DOOR_WORDS * 8, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_part_doors, dim3(part_sweep_blocks(n)), dim3(256), 0, s, (const unsigned long long*)b.keys, d2, q, n, (const unsigned*)b.roots,
+  hipLaunchKernelGGL(k_part_doors, dim3(hsk_sweep_blocks(n)), dim3(256), 0, s, (const unsigned long long*)b.keys, d2, q, n, (const unsigned*)b.roots,
                      (const unsigned*)b.rank, n_kept, table);
   return hipGetLastError();
 }

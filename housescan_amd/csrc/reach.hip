@@ -6,7 +6,8 @@
 //
 // k_reach_init: one sweep over the clearance field writes BLOCKED / UNREACHED and counts the passable voxels.
 // k_reach_seed: a thread a seed voxel: 0 into a passable one, its tile onto the first worklist.
-// k_reach_round: a workgroup takes one tile of the current worklist, loads it with a one-voxel halo into LDS, relaxes the interior
+// k_reach_round (its body is hsk_relax_dev.h's hsk_relax_round, which k_part_round runs on 64-bit keys): a workgroup takes one
+// tile of the current worklist, loads it with a one-voxel halo into LDS, relaxes the interior
 // to a local fixpoint (the halo is read only), stores what fell, and puts the neighbouring tiles that can see a fallen voxel -- up
 // to 26 -- onto the next worklist.  A tile is appended by whoever sets its flag first, so a list holds a tile once and a round's
 // work is the active tiles' alone.  A halo value another workgroup lowers meanwhile is read as the old or the new one: both are
@@ -18,7 +19,7 @@
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
 #include "hsk_launch.h"
-#include "hsk_reach_point.h"
+#include "hsk_relax_dev.h"
 
 static_assert(REACH_TILE_X * REACH_TILE_Y == 256, "k_reach_round: a thread per (x, y) of the tile");
 
@@ -36,14 +37,6 @@ __global__ __launch_bounds__(256) void k_reach_init(const unsigned* __restrict__
   if ((threadIdx.x & 63u) == 0u && pass) atomicAdd(&counters[0], (unsigned long long)pass);
 }
 
-// marks a tile for the list `list` (its length in *count): the flag counts the marks of a round, and whoever finds it 0 appends the
-// tile, so the list holds it once and its length never exceeds the number of tiles (a round adds at most 26 marks a tile and the
-// seeds at most 4096: the count cannot wrap before the tile's relaxation clears it)
-static __device__ __forceinline__ void reach_mark(unsigned tile, unsigned* __restrict__ flags, unsigned* __restrict__ list,
-                                                  unsigned long long* __restrict__ count) {
-  if (atomicAdd(&flags[tile], 1u) == 0u) list[atomicAdd(count, 1ull)] = tile;
-}
-
 __global__ __launch_bounds__(256) void k_reach_seed(unsigned* __restrict__ g, ReachGeom q, const unsigned* __restrict__ seeds, unsigned n_seeds,
                                                     unsigned* __restrict__ flags, unsigned* __restrict__ list, unsigned long long* __restrict__ counters,
                                                     unsigned long long* __restrict__ count) {
@@ -59,23 +52,11 @@ __global__ __launch_bounds__(256) void k_reach_seed(unsigned* __restrict__ g, Re
   const unsigned x = v % q.X, y = (v / q.X) % q.Y, z = v / (q.X * q.Y);
   const unsigned tx = x / REACH_TILE_X, ty = y / REACH_TILE_Y, tz = z / REACH_TILE_Z;
   const unsigned seen_by = reach_seen_by((int)(x % REACH_TILE_X), (int)(y % REACH_TILE_Y), (int)(z % REACH_TILE_Z));
-  for (int m = 0; m < REACH_MOVES; ++m) {  // (27 trips; the centre bit is the seed's own tile)
-    if (!((seen_by >> m) & 1u)) continue;
-    const int nx = (int)tx + reach_dx(m), ny = (int)ty + reach_dy(m), nz = (int)tz + reach_dz(m);
-    if (nx >= 0 && nx < (int)q.ntx && ny >= 0 && ny < (int)q.nty && nz >= 0 && nz < (int)q.ntz)
-      reach_mark(((unsigned)nz * q.nty + (unsigned)ny) * q.ntx + (unsigned)nx, flags, list, count);
-  }
+  for (int m = 0; m < REACH_MOVES; ++m)  // (27 trips; the centre bit is the seed's own tile)
+    if ((seen_by >> m) & 1u) hsk_relax_mark_around(q, tx, ty, tz, m, flags, list, count);
 }
 
-// a tile in LDS, as the shared text takes it
-struct ReachTile {
-  unsigned* cells;
-  unsigned* mv;
-  __device__ __forceinline__ unsigned g(int x, int y, int z) const { return cells[reach_halo_index(x, y, z)]; }
-  __device__ __forceinline__ void set(int x, int y, int z, unsigned v) const { cells[reach_halo_index(x, y, z)] = v; }
-  __device__ __forceinline__ unsigned moves(unsigned i) const { return mv[i]; }
-  __device__ __forceinline__ void set_moves(unsigned i, unsigned v) const { mv[i] = v; }
-};
+// the field's global accesses are plain: a 32-bit word is never torn
 struct ReachLoad {
   const unsigned* p;
   __device__ __forceinline__ unsigned operator()(size_t i) const { return p[i]; }
@@ -85,54 +66,14 @@ struct ReachStore {
   __device__ __forceinline__ void operator()(size_t i, unsigned v) const { p[i] = v; }
 };
 
-// grid: the tiles of list_cur, a workgroup each
+// grid: the tiles of list_cur, a workgroup each (hsk_relax_dev.h: hsk_relax_round)
 __global__ __launch_bounds__(256) void k_reach_round(unsigned* g, ReachGeom q, const unsigned* __restrict__ list_cur, unsigned* __restrict__ flags_cur,
                                                      unsigned* __restrict__ flags_next, unsigned* __restrict__ list_next,
                                                      unsigned long long* __restrict__ count_next) {
   __shared__ unsigned s_cells[REACH_HALO_CELLS];
   __shared__ unsigned s_moves[REACH_TILE_VOXELS];
-  __shared__ unsigned s_seen[REACH_MOVES];  // per tile offset: a voxel that tile can see fell (plain stores of 1)
-  const unsigned tid = threadIdx.x;
-  const unsigned tile = list_cur[blockIdx.x];
-  const unsigned tx = tile % q.ntx, ty = (tile / q.ntx) % q.nty, tz = tile / (q.ntx * q.nty);
-  const unsigned ox = tx * REACH_TILE_X, oy = ty * REACH_TILE_Y, oz = tz * REACH_TILE_Z;
-  if (tid == 0u) flags_cur[tile] = 0u;  // (this round reads this set and clears it; marks go to the other)
-  if (tid < (unsigned)REACH_MOVES) s_seen[tid] = 0u;
-  ReachTile s{s_cells, s_moves};
-  const ReachLoad ld{g};
-  reach_tile_load(s, ld, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
-  __syncthreads();
-  reach_tile_moves(s, tid, 256u);
-  __syncthreads();
-  // The local fixpoint, Bellman-Ford in place: after sweep k every voxel holds at most the length of its best chain of at most k
-  // moves inside the tile from the halo or the values loaded, and such a chain visits no voxel twice (the costs are positive), so
-  // at most REACH_TILE_VOXELS sweeps change anything.  The loop ends at the first sweep in which no thread lowered a value -- every
-  // read of that sweep then saw the cells as they stay -- and after REACH_TILE_VOXELS sweeps in any case.
-#pragma unroll 1
-  for (unsigned sweep = 0u; sweep < (unsigned)REACH_TILE_VOXELS; ++sweep) {
-    const bool fell = reach_tile_sweep(s, tid, 256u, q.cost, q.max_cost);
-    if (!__syncthreads_or(fell ? 1 : 0)) break;  // (block-uniform)
-  }
-  const unsigned seen_by = reach_tile_store(s, ld, ReachStore{g}, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
-  if (seen_by) {  // (rare: a thread whose voxels fell; several threads may store the same 1)
-    for (int m = 0; m < REACH_MOVES; ++m)
-      if ((seen_by >> m) & 1u) s_seen[m] = 1u;
-  }
-  __syncthreads();
-  if (tid < (unsigned)REACH_MOVES && tid != (unsigned)REACH_CENTRE && s_seen[tid]) {
-    const int nx = (int)tx + reach_dx((int)tid), ny = (int)ty + reach_dy((int)tid), nz = (int)tz + reach_dz((int)tid);
-    if (nx >= 0 && nx < (int)q.ntx && ny >= 0 && ny < (int)q.nty && nz >= 0 && nz < (int)q.ntz)
-      reach_mark(((unsigned)nz * q.nty + (unsigned)ny) * q.ntx + (unsigned)nx, flags_next, list_next, count_next);
-  }
-}
-
-static __device__ __forceinline__ unsigned reach_wave_max(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
+  __shared__ unsigned s_seen[REACH_MOVES];
+  hsk_relax_round<ReachValue>(s_cells, s_moves, s_seen, ReachLoad{g}, ReachStore{g}, q, list_cur, flags_cur, flags_next, list_next, count_next);
 }
 
 __global__ __launch_bounds__(256) void k_reach_stats(const unsigned* __restrict__ g, unsigned long long n, unsigned long long* __restrict__ counters) {
@@ -146,7 +87,7 @@ __global__ __launch_bounds__(256) void k_reach_stats(const unsigned* __restrict_
     }
   }
   reached = hsk_wave_sum(reached);
-  top = reach_wave_max(top);
+  top = hsk_wave_max(top);
   if ((threadIdx.x & 63u) == 0u && reached) {
     atomicAdd(&counters[1], (unsigned long long)reached);
     atomicMin(&counters[2], (unsigned long long)(~top));  // (the largest value as the least complement; the word starts as all ones)
@@ -198,34 +139,20 @@ __global__ __launch_bounds__(64) void k_reach_path(const unsigned* __restrict__ 
 
 // ---- the launchers ------------------------------------------------------------------------------------------------------------
 void reach_geom(unsigned X, unsigned Y, unsigned Z, const unsigned w[3], unsigned min_d2, unsigned max_cost, ReachGeom* q) {
-  q->X = X, q->Y = Y, q->Z = Z;
-  q->ntx = (X + REACH_TILE_X - 1u) / REACH_TILE_X;
-  q->nty = (Y + REACH_TILE_Y - 1u) / REACH_TILE_Y;
-  q->ntz = (Z + REACH_TILE_Z - 1u) / REACH_TILE_Z;
+  hsk_relax_geom(X, Y, Z, w, q);
   q->min_d2 = min_d2;
   q->max_cost = max_cost;
-  reach_cost_table(w, q->cost);
 }
 
 size_t reach_layout(const ReachGeom& q, void* base, ReachBufs* b) {
-  const size_t n = (size_t)q.X * q.Y * q.Z, tiles = (size_t)q.ntx * q.nty * q.ntz;
-  size_t bytes = 0;
-  auto take = [&](size_t k) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (k + 255) & ~(size_t)255;
-    return p;
-  };
+  RelaxCarve c{base};
   ReachBufs out;
-  out.counters = (unsigned long long*)take(64);
-  out.field = (unsigned*)take(n * 4);
-  for (int i = 0; i < 2; ++i) out.flags[i] = (unsigned*)take(tiles * 4);
-  for (int i = 0; i < 2; ++i) out.list[i] = (unsigned*)take(tiles * 4);
+  out.counters = (unsigned long long*)c.take(64);
+  out.field = (unsigned*)c.take((size_t)q.X * q.Y * q.Z * 4);
+  c.worklists((size_t)q.ntx * q.nty * q.ntz, out.flags, out.list);
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
-
-// the grid of the two sweeps over the field: a block a 256 voxels, at most 4096 blocks (16 a CU), the rest by the grid-stride loop
-static unsigned reach_sweep_blocks(unsigned long long n) { return (unsigned)std::min<unsigned long long>((n + 255u) / 256u, 4096ull); }
 
 hipError_t launch_reach_init(hipStream_t s, const unsigned* d2, const ReachGeom& q, const ReachBufs& b) {
   const unsigned long long n = (unsigned long long)q.X * q.Y * q.Z, tiles = (unsigned long long)q.ntx * q.nty * q.ntz;
@@ -234,7 +161,7 @@ hipError_t launch_reach_init(hipStream_t s, const unsigned* d2, const ReachGeom&
   if (e == hipSuccess) e = hipMemsetAsync(b.flags[0], 0, tiles * 4, s);
   if (e == hipSuccess) e = hipMemsetAsync(b.flags[1], 0, tiles * 4, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_reach_init, dim3(reach_sweep_blocks(n)), dim3(256), 0, s, d2, b.field, n, q.min_d2, b.counters);
+  hipLaunchKernelGGL(k_reach_init, dim3(hsk_sweep_blocks(n)), dim3(256), 0, s, d2, b.field, n, q.min_d2, b.counters);
   return hipGetLastError();
 }
 
@@ -254,7 +181,7 @@ hipError_t launch_reach_round(hipStream_t s, const ReachGeom& q, const ReachBufs
 
 void launch_reach_stats(hipStream_t s, const ReachGeom& q, const ReachBufs& b) {
   const unsigned long long n = (unsigned long long)q.X * q.Y * q.Z;
-  hipLaunchKernelGGL(k_reach_stats, dim3(reach_sweep_blocks(n)), dim3(256), 0, s, (const unsigned*)b.field, n, b.counters);
+  hipLaunchKernelGGL(k_reach_stats, dim3(hsk_sweep_blocks(n)), dim3(256), 0, s, (const unsigned*)b.field, n, b.counters);
 }
 
 void launch_reach_path(hipStream_t s, const unsigned* field, const ReachGeom& q, unsigned goal, unsigned long long cap, int* out,

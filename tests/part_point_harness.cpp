@@ -18,7 +18,7 @@
 struct Tile {  // (exactly the cells of a tile and its halo: an access past them is the sanitizer's to find)
   std::vector<part_key> cells = std::vector<part_key>(REACH_HALO_CELLS);
   std::vector<unsigned> mv = std::vector<unsigned>(REACH_TILE_VOXELS);
-  part_key k(int x, int y, int z) const { return cells[reach_halo_index(x, y, z)]; }
+  part_key at(int x, int y, int z) const { return cells[reach_halo_index(x, y, z)]; }
   void set(int x, int y, int z, part_key v) { cells[reach_halo_index(x, y, z)] = v; }
   unsigned moves(unsigned i) const { return mv[i]; }
   void set_moves(unsigned i, unsigned v) { mv[i] = v; }
@@ -121,14 +121,14 @@ int main(int argc, char** argv) {
       const unsigned tx = tile % ntx, ty = (tile / ntx) % nty, tz = tile / (ntx * nty);
       const unsigned ox = tx * REACH_TILE_X, oy = ty * REACH_TILE_Y, oz = tz * REACH_TILE_Z;
       const Load ld{&key};
-      part_tile_load(s, ld, ox, oy, oz, X, Y, Z, 0u, 1u);
-      part_tile_moves(s, 0u, 1u);
+      reach_tile_load<PartValue>(s, ld, ox, oy, oz, X, Y, Z, 0u, 1u);
+      reach_tile_moves<PartValue>(s, 0u, 1u);
       // (bounded as on the device: at most REACH_TILE_VOXELS sweeps change anything)
       unsigned sweep = 0;
       for (; sweep < (unsigned)REACH_TILE_VOXELS; ++sweep)
-        if (!part_tile_sweep(s, 0u, 1u, cost, max_cost)) break;
+        if (!reach_tile_sweep<PartValue>(s, 0u, 1u, cost, max_cost)) break;
       if (sweep == (unsigned)REACH_TILE_VOXELS) return 6;
-      const unsigned seen_by = part_tile_store(s, ld, Store{&key}, ox, oy, oz, X, Y, Z, 0u, 1u);
+      const unsigned seen_by = reach_tile_store<PartValue>(s, ld, Store{&key}, ox, oy, oz, X, Y, Z, 0u, 1u);
       for (int m = 0; m < REACH_MOVES; ++m) {
         if (m == REACH_CENTRE || !((seen_by >> m) & 1u)) continue;
         const int nx = (int)tx + reach_dx(m), ny = (int)ty + reach_dy(m), nz = (int)tz + reach_dz(m);

@@ -2,7 +2,8 @@
 rooms at the threshold where one core becomes two, the ties at the corner eight tiles share and on a mirror plane of voxels, the
 dropping of small cores and the cap of 1024 --, its G against reach_twin's field seeded at every kept core voxel, its frontier
 form against whole-grid Jacobi sweeps; the kernels' shared text (housescan_amd/csrc/hsk_part_point.h) compiled for the host with
-the sanitizers, relaxing tile after tile in three visiting orders, against the twin -- zero differences; hsk_merge_rooms; the
+the sanitizers, relaxing tile after tile in three visiting orders, against the twin -- zero differences --, and G of its keys against the reach
+harness's field on one ragged grid (the two are one relaxation text); hsk_merge_rooms; the
 defaults; the C layout of the new structs and their Python mirror; the argument errors that need no device.  The scenes and
 constants here are the GPU tests' too."""
 import ctypes as C
@@ -19,6 +20,7 @@ import reach_twin as RE
 from test_components_host import speckled
 from test_cover_host import carved_volume
 from test_reach_host import (CORNER_DIMS, FREE_WORD, SERPENTINE_DIMS, SOLID_WORD, TILE, WEIGHTS, corridors, serpentine, tile_corner, two_rooms)
+from test_reach_host import run_harness as reach_harness
 
 f32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -292,6 +294,28 @@ def test_the_kernels_text_makes_the_twins_partition_on_the_host_in_any_tile_orde
     vol, d2, par = ragged_case(RAGGED[1], (16, 25, 44), 1)
     key, _, counts, _ = run_harness(exe, tmp_path, d2, (16, 25, 44), 9 * 16, 16, 1, RE.MAX_COST, 0)
     assert key is None and (counts["n_cores"], counts["n_kept"], counts["n_rounds"]) == (1121, 1121, 0)
+
+
+def test_the_two_harnesses_run_one_relaxation(tmp_path):
+    """the tile relaxation is one text (hsk_reach_point.h) with two value policies: on a grid of 2 x 2 x 2 tiles, every one ragged,
+    G of the partition harness's keys is the field the reach harness makes when every kept core voxel is a seed, bit for bit --
+    the markers included (a key's G is the reach field's marker)"""
+    exes = {}
+    for name in ("part_point", "reach_point"):
+        exes[name] = tmp_path / name
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
+                               "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", name + "_harness.cpp"), "-o", str(exes[name])])
+    dims, weight = (40, 12, 11), (16, 25, 44)
+    assert all(t < d < 2 * t for d, t in zip(dims, TILE))
+    d2 = np.random.default_rng(23).choice(np.array([0, 1, 3, 50, CL.FAR], np.uint32), dims[::-1], p=[0.25, 0.25, 0.2, 0.15, 0.15])
+    key, roots, counts, _ = run_harness(exes["part_point"], tmp_path, d2, weight, 50, 1, 2, RE.MAX_COST, 2)         # (singleton cores are dropped)
+    g_of_key = (key >> np.uint64(32)).astype(np.uint32)
+    seeds = [(int(x), int(y), int(z)) for z, y, x in np.argwhere(g_of_key == 0)]
+    assert 2 <= counts["n_kept"] < counts["n_cores"] and 2 * counts["n_kept"] <= len(seeds) <= RE.MAX_SEEDS
+    g, st, used, rounds, tiles, _ = reach_harness(exes["reach_point"], tmp_path, d2, weight, 1, RE.MAX_COST, 1, seeds)
+    assert used == len(seeds) and int((g != g_of_key).sum()) == 0
+    assert st["n_passable"] == counts["n_passable"] and ((g > 0) & (g <= RE.MAX_COST)).sum() >= 1000 and (g == RE.UNREACHED).sum() >= 1
+    assert (g == RE.BLOCKED).sum() == (d2 < 1).sum() and min(tiles, counts["n_tiles"]) >= 8
 
 
 # ---- 6. merge, defaults, layout, errors without a device ----------------------------------------------------------------------------------

@@ -51,18 +51,18 @@ __global__ __launch_bounds__(256) void k_reach_round_grid(unsigned* g, ReachGeom
     atomicAdd(relaxed, 1ull);
   }
   if (tid < (unsigned)REACH_MOVES) s_seen[tid] = 0u;
-  ReachTile s{s_cells, s_moves};
+  RelaxTile<unsigned> s{s_cells, s_moves};
   const ReachLoad ld{g};
-  reach_tile_load(s, ld, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
+  reach_tile_load<ReachValue>(s, ld, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
   __syncthreads();
-  reach_tile_moves(s, tid, 256u);
+  reach_tile_moves<ReachValue>(s, tid, 256u);
   __syncthreads();
 #pragma unroll 1
   for (unsigned sweep = 0u; sweep < (unsigned)REACH_TILE_VOXELS; ++sweep) {  // (bounded as in k_reach_round)
-    const bool fell = reach_tile_sweep(s, tid, 256u, q.cost, q.max_cost);
+    const bool fell = reach_tile_sweep<ReachValue>(s, tid, 256u, q.cost, q.max_cost);
     if (!__syncthreads_or(fell ? 1 : 0)) break;
   }
-  const unsigned seen_by = reach_tile_store(s, ld, ReachStore{g}, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
+  const unsigned seen_by = reach_tile_store<ReachValue>(s, ld, ReachStore{g}, ox, oy, oz, q.X, q.Y, q.Z, tid, 256u);
   if (seen_by) {
     for (int m = 0; m < REACH_MOVES; ++m)
       if ((seen_by >> m) & 1u) s_seen[m] = 1u;
