@@ -45,8 +45,7 @@ struct hsk_ctx {
   float* d_nmod[HSK_NLEVELS] = {};
   TrackState* d_st = nullptr;
   TrackState* h_st = nullptr;  // pinned
-  double* d_partials = nullptr;
-  double* d_partials2 = nullptr;  // ping-pong partner of d_partials (fused ICP iterations)
+  double* d_partials = nullptr;  // per-block ICP sums of the stage-level accumulate (launch_icp_accumulate)
   void* d_icp_pose = nullptr;     // two IcpPose slots
   double* d_sums = nullptr;
   float h_ws[169] = {};  // bilateral spatial weights (host copy: passed to the kernel by value)

@@ -174,6 +174,38 @@ struct PushDests {
 
 static __device__ __forceinline__ bool hsk_isnan(float x) { return x != x; }
 
+// The 2 x 2 mean of the map pyramid (resizeVMap / resizeNMap; the oracle's ora_resize_vmap / ora_resize_nmap):
+// NaN when the first component of any of the four taps is NaN, else (((t0 + t1) + t2) + t3) / 4 per component, and a normal
+// renormalised by 1 / sqrtf(dot).  The one text of the rule for kernels_image.hip: both levels of k_resize_maps2 and of
+// k_adopt_pyramid call it (raycast.hip's pyramid_step keeps a copy of its own: see there).
+static __device__ __forceinline__ void hsk_mean2x2(const float (&t)[4][3], bool normalize, float (&r)[3]) {
+  r[0] = r[1] = r[2] = HSK_NANF;
+  if (!(hsk_isnan(t[0][0]) || hsk_isnan(t[1][0]) || hsk_isnan(t[2][0]) || hsk_isnan(t[3][0]))) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = (((t[0][c] + t[1][c]) + t[2][c]) + t[3][c]) / 4.0f;
+    if (normalize) {
+      const float inv = 1.0f / sqrtf(hsk_dot3(r[0], r[1], r[2], r[0], r[1], r[2]));
+#pragma unroll
+      for (int c = 0; c < 3; ++c) r[c] = r[c] * inv;
+    }
+  }
+}
+
+// The last kernel of a pipelined frame reports the tracker state into the host ring (RingOut), by ONE thread of the launch:
+// the state words first, then the two marks that announce them.
+static __device__ __forceinline__ void hsk_ring_report(const TrackState* st, const RingOut& ring) {
+  const unsigned n = *ring.seq;
+  *ring.seq = n + 1u;
+  TrackState* dst = ring.slots + ring.slot_fifo[n % HSK_RING_FIFO];
+  const int* src_w = (const int*)st;
+  int* dst_w = (int*)dst;
+  for (unsigned i = 0; i < (unsigned)(offsetof(TrackState, ring_mark) / 4); ++i) dst_w[i] = src_w[i];
+  __threadfence_system();  // the state words reach the host before the marks that announce them
+  // (pose_mark: already there when the integrate's first kernel reported early; set here for the frames it did not)
+  __hip_atomic_store(&dst->pose_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(&dst->ring_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // the sum of an integer over the wave's 64 lanes, in every lane (an xor butterfly: every lane of the wave must arrive)
 template <class T>
 static __device__ __forceinline__ T hsk_wave_sum(T v) {

@@ -249,20 +249,6 @@ static __device__ __forceinline__ void shard_sum27_wave(double* a, double* tot) 
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 }
-static __device__ __forceinline__ void shard_reduce27_wave(const double* __restrict__ slot, double* tot) {
-  const int lane = threadIdx.x & 63, k = lane & 31, half = lane >> 5;
-  double a[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) a[j] = slot[(half * 16 + j) * 32 + k];
-#pragma unroll
-  for (int w = 8; w > 0; w >>= 1)
-#pragma unroll
-    for (int j = 0; j < w; ++j) a[j] = a[j] + a[j + w];
-  const double v = swap32_add_f64(a[0], a[0]);  // every lane: its half + the other half
-  if (lane < 27) tot[lane] = v;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // What the first kernel of integrate needs to finish a frame's ICP itself (launch_icp_fused hands it out instead of
 // launching k_icp_final): where the last pose estimate is, the accumulator slots, and the iteration count.

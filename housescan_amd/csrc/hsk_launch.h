@@ -294,9 +294,6 @@ void launch_pack_scatter(hipStream_t s, void* vol, bool color, const VolParams& 
 void launch_bilateral_scale(hipStream_t s, const uint16_t* src, int W, int H, Intr in, const float* ws, const float* wc,
                             uint16_t* dst, float* scaled, float* tiles);
 void launch_scale_depth(hipStream_t s, const uint16_t* src, int W, int H, Intr in, float* scaled);
-void launch_pyrdown(hipStream_t s, const uint16_t* src, int W, int H, uint16_t* dst);
-void launch_vmap_nmap_pyramid(hipStream_t s, uint16_t* const* depth, const ImgLevel* lv, float* const* vmap,
-                              float* const* nmap);
 // pyrDown x 2 and the vertex / normal maps of all three levels in one launch (depth[0] is read, depth[1], depth[2] written)
 void launch_pyramid_maps(hipStream_t s, uint16_t* const* depth, const ImgLevel* lv, float* const* vmap, float* const* nmap);
 void launch_transform_maps(hipStream_t s, const float* vs, const float* ns, int P, const TrackState* st, float* vd,
@@ -314,8 +311,7 @@ void launch_begin_frame(hipStream_t s, TrackState* st, void* icp_pose_buf);
 size_t icp_pose_bytes();
 void launch_icp_fused(hipStream_t s, float* const* vcur, float* const* ncur, float* const* vmod, float* const* nmod,
                       const ImgLevel* lv, const int* iters, TrackState* st, float dist_thresh, float angle_thresh,
-                      void* pose_buf, double* part_a, double* part_b, IcpFinal* defer_final = nullptr,
-                      hipEvent_t* level_events = nullptr);
+                      void* pose_buf, IcpFinal* defer_final = nullptr, hipEvent_t* level_events = nullptr);
 bool host_solve6(const double* in27, float* x6);
 void host_pose_update(float* R, float* t, const float* x6);
 void hsk_build_tet_table(TetTable* tt);

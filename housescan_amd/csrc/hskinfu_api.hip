@@ -134,7 +134,6 @@ static void free_all(hsk_ctx* k) {
   }
   F(k->d_st);
   F(k->d_partials);
-  F(k->d_partials2);
   F(k->d_icp_pose);
   F(k->d_sums);
   F(k->d_wc);
@@ -401,7 +400,6 @@ extern "C" int hsk_create(const hsk_config* c, hsk_ctx** out) {
   for (auto& e : k->ring_ev) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   const int nb0 = icp_num_blocks(c->width, c->height);
   CK(hipMalloc((void**)&k->d_partials, (size_t)nb0 * 27 * sizeof(double)));
-  CK(hipMalloc((void**)&k->d_partials2, (size_t)nb0 * 27 * sizeof(double)));
   CK(hipMalloc(&k->d_icp_pose, icp_pose_bytes()));
   CK(hipMemset(k->d_icp_pose, 0, icp_pose_bytes()));  // accumulator slot 0 must be empty before the first tracked frame
   CK(hipMalloc((void**)&k->d_sums, 27 * sizeof(double)));
@@ -487,8 +485,24 @@ static void enqueue_preprocess(hsk_ctx* k, hipStream_t s) {
 static void enqueue_icp(hsk_ctx* k, IcpFinal* fin = nullptr) {
   if (fin) *fin = IcpFinal{nullptr, nullptr, 0};
   launch_icp_fused(k->stream, k->B().d_vcur, k->B().d_ncur, k->d_vmod, k->d_nmod, k->lv, k->cfg.icp_iters, k->d_st,
-                   k->cfg.icp_dist_thresh_m, k->cfg.icp_angle_thresh_sin, k->d_icp_pose, k->d_partials, k->d_partials2, fin,
+                   k->cfg.icp_dist_thresh_m, k->cfg.icp_angle_thresh_sin, k->d_icp_pose, fin,
                    (k->prof && k->prof_levels && !fin) ? k->ev_icp : nullptr);
+}
+
+// the stage-level entry points' part of the preprocess: the scaled depth of the staged frame with its raw tile tables
+static void enqueue_scaled_depth(hsk_ctx* k) {
+  const int w = k->lv[0].W, h = k->lv[0].H;
+  launch_scale_depth(k->stream, k->B().d_raw, w, h, k->lv[0].in, k->B().d_scaled);
+  launch_tile_max(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  launch_tile_fine(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+}
+
+// the ICP sums of rows [row0, row1) of a level, at the pose of the device state, into 27 doubles on the device
+static void enqueue_icp_row_sums(hsk_ctx* k, int level, int row0, int row1, double* sums27_dev) {
+  const ImgLevel& lv = k->lv[level];
+  launch_icp_accumulate(k->stream, k->B().d_vcur[level], k->B().d_ncur[level], k->d_vmod[level], k->d_nmod[level], lv.W, lv.H,
+                        lv.in, k->d_st, k->cfg.icp_dist_thresh_m, k->cfg.icp_angle_thresh_sin, row0, row1, k->d_partials);
+  launch_icp_reduce(k->stream, k->d_partials, icp_num_blocks(lv.W, row1 - row0), sums27_dev);
 }
 
 // report_early: a pipelined frame -- the integrate's first kernel, which ends the frame's ICP, tells the host the pose at
@@ -1054,9 +1068,7 @@ extern "C" int hsk_integrate(hsk_ctx* k, const uint16_t* depth, int w, int h, co
   if (r != HSK_OK) return r;
   r = stage_depth_host(k, depth);
   if (r != HSK_OK) return r;
-  launch_scale_depth(k->stream, k->B().d_raw, w, h, k->lv[0].in, k->B().d_scaled);
-  launch_tile_max(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
-  launch_tile_fine(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  enqueue_scaled_depth(k);
   enqueue_integrate(k);
   HIPCHK(k, hipStreamSynchronize(k->stream));
   HIPCHK(k, hipGetLastError());
@@ -1072,9 +1084,7 @@ extern "C" int hsk_count_updates(hsk_ctx* k, const uint16_t* depth, int w, int h
   if (r != HSK_OK) return r;
   r = stage_depth_host(k, depth);
   if (r != HSK_OK) return r;
-  launch_scale_depth(k->stream, k->B().d_raw, w, h, k->lv[0].in, k->B().d_scaled);
-  launch_tile_max(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
-  launch_tile_fine(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  enqueue_scaled_depth(k);
   HIPCHK(k, hipMemsetAsync(k->d_counter, 0, 8, k->stream));
   launch_integrate(k->stream, k->d_vol, k->B().d_scaled, k->d_st, k->vp, w, h, k->lv[0].in, true, k->d_counter, k->d_flags,
                    k->B().d_tmax, k->d_zint, k->d_queue);
@@ -1136,11 +1146,7 @@ extern "C" int hsk_icp_accumulate(hsk_ctx* k, int level, const float pose_est[16
   k->h_st->lost = 0;
   r = upload_state(k);
   if (r != HSK_OK) return r;
-  const int nb = icp_num_blocks(k->lv[level].W, row1 - row0);
-  launch_icp_accumulate(k->stream, k->B().d_vcur[level], k->B().d_ncur[level], k->d_vmod[level], k->d_nmod[level],
-                        k->lv[level].W, k->lv[level].H, k->lv[level].in, k->d_st, k->cfg.icp_dist_thresh_m,
-                        k->cfg.icp_angle_thresh_sin, row0, row1, k->d_partials);
-  launch_icp_reduce(k->stream, k->d_partials, nb, k->d_sums);
+  enqueue_icp_row_sums(k, level, row0, row1, k->d_sums);
   HIPCHK(k, hipMemcpyAsync(out27, k->d_sums, 27 * sizeof(double), hipMemcpyDeviceToHost, k->stream));
   HIPCHK(k, hipStreamSynchronize(k->stream));
   *k->h_st = saved;
@@ -1271,9 +1277,7 @@ extern "C" int hsk_integrate_color(hsk_ctx* k, const uint16_t* depth, const uint
     k->rgb_src = nullptr;
     return r;
   }
-  launch_scale_depth(k->stream, k->B().d_raw, w, h, k->lv[0].in, k->B().d_scaled);
-  launch_tile_max(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
-  launch_tile_fine(k->stream, k->B().d_scaled, w, h, k->B().d_tmax);
+  enqueue_scaled_depth(k);
   const hipError_t e = stage_color(k, k->cur, k->stream);
   k->rgb_src = nullptr;
   HIPCHK(k, e);
@@ -1436,11 +1440,7 @@ extern "C" int hsk_mgpu_icp_accumulate(hsk_ctx* k, int level, int row0, int row1
     HIPCHK(k, hipMemsetAsync(sums27_dev, 0, 27 * sizeof(double), k->stream));
     return HSK_OK;
   }
-  const int nb = icp_num_blocks(k->lv[level].W, row1 - row0);
-  launch_icp_accumulate(k->stream, k->B().d_vcur[level], k->B().d_ncur[level], k->d_vmod[level], k->d_nmod[level],
-                        k->lv[level].W, k->lv[level].H, k->lv[level].in, k->d_st, k->cfg.icp_dist_thresh_m,
-                        k->cfg.icp_angle_thresh_sin, row0, row1, k->d_partials);
-  launch_icp_reduce(k->stream, k->d_partials, nb, (double*)sums27_dev);
+  enqueue_icp_row_sums(k, level, row0, row1, (double*)sums27_dev);
   return HSK_OK;
 }
 

@@ -2,6 +2,7 @@
 // (SURVEY.md A.3/A.4), map resize / transform (A.2/A.3), and the projective-association point-to-plane ICP
 // with its wavefront reduction and on-device 6x6 solve (A.5).
 #pragma clang fp contract(off)
+#include <type_traits>
 #include "hsk_dev.h"
 #ifdef HSK_ICP_TIMING
 // timing build (tools/icp_timing.sh): s_memrealtime (100 MHz) stamps of every block of every iteration; defined before
@@ -190,121 +191,25 @@ void launch_scale_depth(hipStream_t s, const uint16_t* src, int W, int H, Intr i
 }
 
 // ------------------------------------------------------------------------------------------------------
-// pyrDown (A.3): integer 5x5 gated mean
+// pyrDown (integer 5x5 gated mean) and the vertex / normal maps of the three levels (A.3)
 // ------------------------------------------------------------------------------------------------------
-__global__ void k_pyrdown(const unsigned short* __restrict__ src, int W, int H, unsigned short* __restrict__ dst) {
-  const int w2 = W >> 1, h2 = H >> 1;
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= w2 || y >= h2) return;
-  const int center = src[(2 * y) * W + 2 * x];
-  const int y0 = max(2 * y - 2, 0), y1 = min(2 * y + 2, H - 2);  // (upper clip exclusive of the last row / column, as the bilateral's)
-  const int x0 = max(2 * x - 2, 0), x1 = min(2 * x + 2, W - 2);
-  int sum = 0, count = 0;
-  for (int cy = y0; cy <= y1; ++cy)
-    for (int cx = x0; cx <= x1; ++cx) {
-      const int val = src[cy * W + cx];
-      const int d = abs(val - center);
-      if (d < 90) {
-        sum += val;
-        ++count;
-      }
-    }
-  dst[y * w2 + x] = (unsigned short)(sum / count);
-}
-void launch_pyrdown(hipStream_t s, const uint16_t* src, int W, int H, uint16_t* dst) {
-  dim3 block(64, 4), grid((W / 2 + 63) / 64, (H / 2 + 3) / 4);
-  hipLaunchKernelGGL(k_pyrdown, grid, block, 0, s, src, W, H, dst);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// vertex + normal maps (A.3), fused: the two forward neighbours are re-projected instead of re-read
-// ------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ bool vertex_of(const unsigned short* __restrict__ d, int W, int u, int v, float cx,
-                                                 float cy, float fx_inv, float fy_inv, float& X, float& Y, float& Z) {
-  const float z = (float)d[v * W + u] / 1000.0f;
-  if (z != 0.0f) {
-    X = (z * ((float)u - cx)) * fx_inv;
-    Y = (z * ((float)v - cy)) * fy_inv;
-    Z = z;
-    return true;
-  }
-  X = Y = Z = HSK_NANF;
-  return false;
-}
-
 struct PyramidArgs {
   const unsigned short* depth[HSK_NLEVELS];
   float* vmap[HSK_NLEVELS];
   float* nmap[HSK_NLEVELS];
-  int W[HSK_NLEVELS], H[HSK_NLEVELS], first_block[HSK_NLEVELS + 1];
+  int W[HSK_NLEVELS], H[HSK_NLEVELS];
+  int unused[HSK_NLEVELS + 1];  // (never read or filled: it keeps the offsets of k_pyramid_maps' argument block, and so its code, as they were)
   Intr in[HSK_NLEVELS];
 };
-// one launch for the three levels: a block belongs to the level whose block range contains it
-__global__ void k_vmap_nmap(PyramidArgs a) {
-  int l = 0;
-  if ((int)blockIdx.x >= a.first_block[1]) l = 1;
-  if ((int)blockIdx.x >= a.first_block[2]) l = 2;
-  const unsigned short* __restrict__ depth = a.depth[l];
-  float* __restrict__ vmap = a.vmap[l];
-  float* __restrict__ nmap = a.nmap[l];
-  const int W = a.W[l], H = a.H[l];
-  const Intr in = a.in[l];
-  const int bw = (W + 63) / 64, b = blockIdx.x - a.first_block[l];
-  const int u = (b % bw) * 64 + threadIdx.x, v = (b / bw) * 4 + threadIdx.y;
-  if (u >= W || v >= H) return;
-  const size_t P = (size_t)W * H, i = (size_t)v * W + u;
-  const float fx_inv = 1.0f / in.fx, fy_inv = 1.0f / in.fy;
-  float x0, y0, z0;
-  const bool ok0 = vertex_of(depth, W, u, v, in.cx, in.cy, fx_inv, fy_inv, x0, y0, z0);
-  vmap[i] = x0;
-  vmap[P + i] = y0;
-  vmap[2 * P + i] = z0;
-  float n0 = HSK_NANF, n1 = HSK_NANF, n2 = HSK_NANF;
-  if (ok0 && u < W - 1 && v < H - 1) {
-    float x1, y1, z1, x2, y2, z2;
-    const bool ok1 = vertex_of(depth, W, u + 1, v, in.cx, in.cy, fx_inv, fy_inv, x1, y1, z1);
-    const bool ok2 = vertex_of(depth, W, u, v + 1, in.cx, in.cy, fx_inv, fy_inv, x2, y2, z2);
-    if (ok1 && ok2) {
-      const float ax = x1 - x0, ay = y1 - y0, az = z1 - z0;
-      const float bx = x2 - x0, by = y2 - y0, bz = z2 - z0;
-      const float r0 = ay * bz - az * by;
-      const float r1 = az * bx - ax * bz;
-      const float r2 = ax * by - ay * bx;
-      const float inv = 1.0f / sqrtf(hsk_dot3(r0, r1, r2, r0, r1, r2));
-      n0 = r0 * inv;
-      n1 = r1 * inv;
-      n2 = r2 * inv;
-    }
-  }
-  nmap[i] = n0;
-  nmap[P + i] = n1;
-  nmap[2 * P + i] = n2;
-}
-void launch_vmap_nmap_pyramid(hipStream_t s, uint16_t* const* depth, const ImgLevel* lv, float* const* vmap,
-                              float* const* nmap) {
-  PyramidArgs a;
-  int nb = 0;
-  for (int l = 0; l < HSK_NLEVELS; ++l) {
-    a.depth[l] = depth[l];
-    a.vmap[l] = vmap[l];
-    a.nmap[l] = nmap[l];
-    a.W[l] = lv[l].W;
-    a.H[l] = lv[l].H;
-    a.in[l] = lv[l].in;
-    a.first_block[l] = nb;
-    nb += ((lv[l].W + 63) / 64) * ((lv[l].H + 3) / 4);
-  }
-  a.first_block[HSK_NLEVELS] = nb;
-  hipLaunchKernelGGL(k_vmap_nmap, dim3(nb), dim3(64, 4), 0, s, a);
-}
 
 // pyrDown x 2 and the vertex / normal maps of all three levels in ONE launch (round 5; they were three: two pyrDown
 // launches of 7 us each and the maps).  A block owns a T x T tile of level 0 = T/2 squared of level 1 = T/4 squared of level 2
 // and keeps what they need in LDS: level 2 with its +1 neighbours for the normals is T/4 + 1 squared, whose 5 x 5 windows
 // reach T/2 + 5 squared of level 1, whose windows reach T + 13 squared of level 0 (the overlap between blocks is re-read
 // from L2, the overlapping pyrDown pixels are computed again: integer arithmetic on the same inputs).  The arithmetic is
-// k_pyrdown's and k_vmap_nmap's, on the same values: bit for bit the same images and maps.  T = 16: 1200 blocks for a
-// 640 x 480 frame (with T = 32, 300 blocks of four dependent phases each, the launch took 15.8 us).
+// SURVEY.md A.3's, as the oracle's ora_pyrdown (pm_pyrdown), ora_vmap (pm_vertex) and ora_nmap (pm_maps: the two forward
+// neighbours are re-projected instead of re-read) spell it out: bit for bit their images and maps.  T = 16: 1200 blocks
+// for a 640 x 480 frame (with T = 32, 300 blocks of four dependent phases each, the launch took 15.8 us).
 #ifndef PM_T0
 #define PM_T0 16
 #endif
@@ -434,9 +339,7 @@ void launch_pyramid_maps(hipStream_t s, uint16_t* const* depth, const ImgLevel* 
     a.W[l] = lv[l].W;
     a.H[l] = lv[l].H;
     a.in[l] = lv[l].in;
-    a.first_block[l] = 0;
   }
-  a.first_block[HSK_NLEVELS] = 0;
   hipLaunchKernelGGL(k_pyramid_maps, dim3((lv[0].W + PM_T0 - 1) / PM_T0, (lv[0].H + PM_T0 - 1) / PM_T0), dim3(64, 4), 0, s, a, depth[1], depth[2]);
 }
 
@@ -472,202 +375,129 @@ void launch_transform_maps(hipStream_t s, const float* vs, const float* ns, int 
   hipLaunchKernelGGL(k_transform_maps, dim3((P + 255) / 256), dim3(256), 0, s, vs, ns, P, st, vd, nd);
 }
 
-// resizeVMap + resizeNMap (A.3): 2x2 mean, NaN if any tap is NaN; normals renormalised
-static __device__ __forceinline__ void resize_tap(const float* __restrict__ src, size_t P, int W, int x, int y, bool normalize,
-                                                  float& a, float& b, float& c) {
-  const size_t i00 = (size_t)(2 * y) * W + 2 * x, i01 = i00 + 1, i10 = i00 + W, i11 = i10 + 1;
-  a = b = c = HSK_NANF;
-  if (!(hsk_isnan(src[i00]) || hsk_isnan(src[i01]) || hsk_isnan(src[i10]) || hsk_isnan(src[i11]))) {
-    a = (((src[i00] + src[i01]) + src[i10]) + src[i11]) / 4.0f;
-    b = (((src[P + i00] + src[P + i01]) + src[P + i10]) + src[P + i11]) / 4.0f;
-    c = (((src[2 * P + i00] + src[2 * P + i01]) + src[2 * P + i10]) + src[2 * P + i11]) / 4.0f;
-    if (normalize) {
-      const float inv = 1.0f / sqrtf(hsk_dot3(a, b, c, a, b, c));
-      a = a * inv;
-      b = b * inv;
-      c = c * inv;
+// ------------------------------------------------------------------------------------------------------
+// resizeVMap + resizeNMap (A.3): levels 1 and 2 of the model maps, by the 2 x 2 mean (hsk_mean2x2) of level 0.  Level 0 comes
+// from a TAP SOURCE: tap(m, i, t) gives the three floats of pixel i of map m (0 the vertex map, 1 the normal map).
+// ------------------------------------------------------------------------------------------------------
+struct Level0Maps {  // the level-0 maps themselves
+  const float* v0;
+  const float* n0;
+  size_t P;
+  __device__ __forceinline__ void tap(int m, size_t i, float (&t)[3]) const {
+    const float* src = m == 0 ? v0 : n0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) t[ch] = src[(size_t)ch * P + i];
+  }
+};
+// The composite of the exchange: the MIN key of every pixel and, where that key is a hit, the winner's vertex / normal bits
+// (k_adopt's selection).
+struct CompositeIn {
+  const int* keys_min;
+  const int* bits;
+  size_t P;
+  __device__ __forceinline__ bool hit(size_t i) const {
+    const int km = keys_min[i];
+    return (km != HSK_KEY_NONE_I) && ((km & 1) == 0);
+  }
+  __device__ __forceinline__ void tap(int m, size_t i, float (&t)[3]) const {
+    t[0] = t[1] = t[2] = HSK_NANF;
+    if (hit(i)) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) t[ch] = __int_as_float(bits[(size_t)(3 * m + ch) * P + i]);
     }
   }
+};
+// pixel (x, y) of level 1, map m
+template <class Src>
+static __device__ __forceinline__ void resize_tap(const Src& S, int m, int W, int x, int y, float (&r)[3]) {
+  const size_t i00 = (size_t)(2 * y) * W + 2 * x, i10 = i00 + W;
+  const size_t idx[4] = {i00, i00 + 1, i10, i10 + 1};
+  float t[4][3];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) S.tap(m, idx[q], t[q]);
+  hsk_mean2x2(t, m == 1, r);
 }
-// level 0 -> level 1 and level 2 in one launch: blocks [0, nb1) write level 1; the rest write level 2 and
-// recompute the four level-1 values they average (same arithmetic, so the same bits as reading them back)
+// block b (64 x 4 threads) of level LEVEL = 1 or 2; a level-2 pixel recomputes the four level-1 values it averages (same
+// arithmetic, so the same bits as reading them back)
+template <int LEVEL, class Src>
+static __device__ __forceinline__ void resize_level(const Src& S, int W, int H, int b, float* __restrict__ vd, float* __restrict__ nd) {
+  const int w = W >> LEVEL, h = H >> LEVEL, bw = (w + 63) / 64;
+  const int x = (b % bw) * 64 + threadIdx.x, y = (b / bw) * 4 + threadIdx.y;
+  if (x >= w || y >= h) return;
+  const size_t P = (size_t)w * h, o = (size_t)y * w + x;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    float r[3];
+    if (LEVEL == 1) {
+      resize_tap(S, m, W, x, y, r);
+    } else {
+      float t[4][3];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) resize_tap(S, m, W, 2 * x + (q & 1), 2 * y + (q >> 1), t[q]);
+      hsk_mean2x2(t, m == 1, r);
+    }
+    float* __restrict__ dst = m == 0 ? vd : nd;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dst[ch * P + o] = r[ch];
+  }
+}
+// levels 1 and 2 in one launch: of the launch's blocks for them, bi in [0, nb1) writes level 1 and the rest write level 2
+template <class Src>
+static __device__ __forceinline__ void resize_levels(const Src& S, int W, int H, int bi, int nb1, float* __restrict__ v1,
+                                                     float* __restrict__ n1, float* __restrict__ v2, float* __restrict__ n2) {
+  if (bi < nb1)
+    resize_level<1>(S, W, H, bi, v1, n1);
+  else
+    resize_level<2>(S, W, H, bi - nb1, v2, n2);
+}
+static inline int resize_blocks(int w, int h) { return ((w + 63) / 64) * ((h + 3) / 4); }
+
 __global__ void k_resize_maps2(const float* __restrict__ v0, const float* __restrict__ n0, int W, int H,
                                float* __restrict__ v1, float* __restrict__ n1, float* __restrict__ v2,
                                float* __restrict__ n2, const TrackState* __restrict__ st, int nb1, RingOut ring) {
-  if (ring.slots && blockIdx.x == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
-    // last kernel of a pipelined slab frame: report the tracker state into the host ring (see k_raycast)
-    const unsigned n = *ring.seq;
-    *ring.seq = n + 1u;
-    TrackState* dst = ring.slots + ring.slot_fifo[n % HSK_RING_FIFO];
-    const int* src_w = (const int*)st;
-    int* dst_w = (int*)dst;
-    for (unsigned i = 0; i < (unsigned)(offsetof(TrackState, ring_mark) / 4); ++i) dst_w[i] = src_w[i];
-    __threadfence_system();
-    __hip_atomic_store(&dst->pose_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&dst->ring_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  // last kernel of a pipelined slab frame: report the tracker state into the host ring (see k_raycast)
+  if (ring.slots && blockIdx.x == 0 && threadIdx.x == 0 && threadIdx.y == 0) hsk_ring_report(st, ring);
   if (st->lost) return;
-  const int w1 = W >> 1, h1 = H >> 1, w2 = W >> 2, h2 = H >> 2;
-  const size_t P0 = (size_t)W * H, P1 = (size_t)w1 * h1, P2 = (size_t)w2 * h2;
-  if ((int)blockIdx.x < nb1) {
-    const int bw = (w1 + 63) / 64;
-    const int x = (blockIdx.x % bw) * 64 + threadIdx.x, y = (blockIdx.x / bw) * 4 + threadIdx.y;
-    if (x >= w1 || y >= h1) return;
-    const size_t o = (size_t)y * w1 + x;
-    float a, b, c;
-    resize_tap(v0, P0, W, x, y, false, a, b, c);
-    v1[o] = a; v1[P1 + o] = b; v1[2 * P1 + o] = c;
-    resize_tap(n0, P0, W, x, y, true, a, b, c);
-    n1[o] = a; n1[P1 + o] = b; n1[2 * P1 + o] = c;
-    return;
-  }
-  const int bw = (w2 + 63) / 64, bi = blockIdx.x - nb1;
-  const int x = (bi % bw) * 64 + threadIdx.x, y = (bi / bw) * 4 + threadIdx.y;
-  if (x >= w2 || y >= h2) return;
-  const size_t o = (size_t)y * w2 + x;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const float* src = m == 0 ? v0 : n0;
-    float* dst = m == 0 ? v2 : n2;
-    float t[4][3];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) resize_tap(src, P0, W, 2 * x + (q & 1), 2 * y + (q >> 1), m == 1, t[q][0], t[q][1], t[q][2]);
-    float a = HSK_NANF, b = HSK_NANF, c = HSK_NANF;
-    if (!(hsk_isnan(t[0][0]) || hsk_isnan(t[1][0]) || hsk_isnan(t[2][0]) || hsk_isnan(t[3][0]))) {
-      a = (((t[0][0] + t[1][0]) + t[2][0]) + t[3][0]) / 4.0f;
-      b = (((t[0][1] + t[1][1]) + t[2][1]) + t[3][1]) / 4.0f;
-      c = (((t[0][2] + t[1][2]) + t[2][2]) + t[3][2]) / 4.0f;
-      if (m == 1) {
-        const float inv = 1.0f / sqrtf(hsk_dot3(a, b, c, a, b, c));
-        a = a * inv;
-        b = b * inv;
-        c = c * inv;
-      }
-    }
-    dst[o] = a;
-    dst[P2 + o] = b;
-    dst[2 * P2 + o] = c;
-  }
+  const Level0Maps S = {v0, n0, (size_t)W * H};
+  resize_levels(S, W, H, (int)blockIdx.x, nb1, v1, n1, v2, n2);
 }
 void launch_resize_maps2(hipStream_t s, const float* v0, const float* n0, int W, int H, float* v1, float* n1, float* v2,
                          float* n2, const TrackState* st, const RingOut* ring) {
-  const int nb1 = ((W / 2 + 63) / 64) * ((H / 2 + 3) / 4), nb2 = ((W / 4 + 63) / 64) * ((H / 4 + 3) / 4);
+  const int nb1 = resize_blocks(W / 2, H / 2), nb2 = resize_blocks(W / 4, H / 4);
   const RingOut quiet = {nullptr, nullptr, nullptr};
   hipLaunchKernelGGL(k_resize_maps2, dim3(nb1 + nb2), dim3(64, 4), 0, s, v0, n0, W, H, v1, n1, v2, n2, st, nb1,
                      ring ? *ring : quiet);
 }
 
 // The END of a z-slab frame in one launch (round 6; it was k_adopt, then k_resize_maps2: 15 us of a multi-GPU frame's critical
-// path): the composite of the exchange -- the MIN key of every pixel and, where that key is a hit, the
-// winner's vertex / normal bits -- becomes the model maps of all three levels, and the tracker state is reported into the
-// host ring.  Blocks [0, nb0) write level 0 (k_adopt's selection), [nb0, nb0 + nb1) level 1, the rest level 2 -- the upper
-// levels straight from the composite, with the same selection and k_resize_maps2's arithmetic, operand for operand: the bits
-// of adopting first and resizing afterwards, without the launch boundary between them and without re-reading level 0.
-struct CompositeIn {
-  const int* keys_min;
-  const int* bits;
-  size_t P;
-};
-static __device__ __forceinline__ bool comp_hit(const CompositeIn& C, size_t i) {
-  const int km = C.keys_min[i];
-  return (km != HSK_KEY_NONE_I) && ((km & 1) == 0);
-}
-// resize_tap with level 0 read through the composite: m = 0 the vertex map, 1 the normal map
-static __device__ __forceinline__ void comp_tap(const CompositeIn& C, int m, int W, int x, int y, float& a, float& b, float& c) {
-  const size_t i00 = (size_t)(2 * y) * W + 2 * x, i01 = i00 + 1, i10 = i00 + W, i11 = i10 + 1;
-  const size_t idx[4] = {i00, i01, i10, i11};
-  float t[4][3];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bool hit = comp_hit(C, idx[q]);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) t[q][ch] = hit ? __int_as_float(C.bits[(size_t)(3 * m + ch) * C.P + idx[q]]) : HSK_NANF;
-  }
-  a = b = c = HSK_NANF;
-  if (!(hsk_isnan(t[0][0]) || hsk_isnan(t[1][0]) || hsk_isnan(t[2][0]) || hsk_isnan(t[3][0]))) {
-    a = (((t[0][0] + t[1][0]) + t[2][0]) + t[3][0]) / 4.0f;
-    b = (((t[0][1] + t[1][1]) + t[2][1]) + t[3][1]) / 4.0f;
-    c = (((t[0][2] + t[1][2]) + t[2][2]) + t[3][2]) / 4.0f;
-    if (m == 1) {
-      const float inv = 1.0f / sqrtf(hsk_dot3(a, b, c, a, b, c));
-      a = a * inv;
-      b = b * inv;
-      c = c * inv;
-    }
-  }
-}
+// path): the composite of the exchange becomes the model maps of all three levels, and the tracker state
+// is reported into the host ring.  Blocks [0, nb0) write level 0 (k_adopt's selection), the rest levels 1 and 2 straight from
+// the composite (resize_levels): the bits of adopting first and resizing afterwards, without the launch boundary between
+// them and without re-reading level 0.
 __global__ void k_adopt_pyramid(CompositeIn C, int W, int H, float* __restrict__ v0, float* __restrict__ n0, float* __restrict__ v1,
                                 float* __restrict__ n1, float* __restrict__ v2, float* __restrict__ n2,
                                 const TrackState* __restrict__ st, int nb0, int nb1, RingOut ring) {
-  if (ring.slots && blockIdx.x == 0 && threadIdx.x == 0 && threadIdx.y == 0) {
-    // last kernel of a pipelined slab frame: report the tracker state into the host ring (see k_raycast)
-    const unsigned n = *ring.seq;
-    *ring.seq = n + 1u;
-    TrackState* dst = ring.slots + ring.slot_fifo[n % HSK_RING_FIFO];
-    const int* src_w = (const int*)st;
-    int* dst_w = (int*)dst;
-    for (unsigned i = 0; i < (unsigned)(offsetof(TrackState, ring_mark) / 4); ++i) dst_w[i] = src_w[i];
-    __threadfence_system();
-    __hip_atomic_store(&dst->pose_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(&dst->ring_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  const int w1 = W >> 1, h1 = H >> 1, w2 = W >> 2, h2 = H >> 2;
-  const size_t P0 = (size_t)W * H, P1 = (size_t)w1 * h1, P2 = (size_t)w2 * h2;
+  if (ring.slots && blockIdx.x == 0 && threadIdx.x == 0 && threadIdx.y == 0) hsk_ring_report(st, ring);
   if ((int)blockIdx.x < nb0) {  // level 0: k_adopt (whatever the frame's verdict, as before)
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.y * 64 + threadIdx.x;
+    const size_t P0 = (size_t)W * H, i = (size_t)blockIdx.x * 256 + threadIdx.y * 64 + threadIdx.x;
     if (i >= P0) return;
-    const bool hit = comp_hit(C, i);
+    float v[3], n[3];
+    C.tap(0, i, v);
+    C.tap(1, i, n);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      v0[ch * P0 + i] = hit ? __int_as_float(C.bits[(size_t)ch * P0 + i]) : HSK_NANF;
-      n0[ch * P0 + i] = hit ? __int_as_float(C.bits[(size_t)(3 + ch) * P0 + i]) : HSK_NANF;
+      v0[ch * P0 + i] = v[ch];
+      n0[ch * P0 + i] = n[ch];
     }
     return;
   }
   if (st->lost) return;
-  if ((int)blockIdx.x < nb0 + nb1) {
-    const int bw = (w1 + 63) / 64, bi = blockIdx.x - nb0;
-    const int x = (bi % bw) * 64 + threadIdx.x, y = (bi / bw) * 4 + threadIdx.y;
-    if (x >= w1 || y >= h1) return;
-    const size_t o = (size_t)y * w1 + x;
-    float a, b, c;
-    comp_tap(C, 0, W, x, y, a, b, c);
-    v1[o] = a; v1[P1 + o] = b; v1[2 * P1 + o] = c;
-    comp_tap(C, 1, W, x, y, a, b, c);
-    n1[o] = a; n1[P1 + o] = b; n1[2 * P1 + o] = c;
-    return;
-  }
-  const int bw = (w2 + 63) / 64, bi = blockIdx.x - nb0 - nb1;
-  const int x = (bi % bw) * 64 + threadIdx.x, y = (bi / bw) * 4 + threadIdx.y;
-  if (x >= w2 || y >= h2) return;
-  const size_t o = (size_t)y * w2 + x;
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    float* dst = m == 0 ? v2 : n2;
-    float t[4][3];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) comp_tap(C, m, W, 2 * x + (q & 1), 2 * y + (q >> 1), t[q][0], t[q][1], t[q][2]);
-    float a = HSK_NANF, b = HSK_NANF, c = HSK_NANF;
-    if (!(hsk_isnan(t[0][0]) || hsk_isnan(t[1][0]) || hsk_isnan(t[2][0]) || hsk_isnan(t[3][0]))) {
-      a = (((t[0][0] + t[1][0]) + t[2][0]) + t[3][0]) / 4.0f;
-      b = (((t[0][1] + t[1][1]) + t[2][1]) + t[3][1]) / 4.0f;
-      c = (((t[0][2] + t[1][2]) + t[2][2]) + t[3][2]) / 4.0f;
-      if (m == 1) {
-        const float inv = 1.0f / sqrtf(hsk_dot3(a, b, c, a, b, c));
-        a = a * inv;
-        b = b * inv;
-        c = c * inv;
-      }
-    }
-    dst[o] = a;
-    dst[P2 + o] = b;
-    dst[2 * P2 + o] = c;
-  }
+  resize_levels(C, W, H, (int)blockIdx.x - nb0, nb1, v1, n1, v2, n2);
 }
 void launch_adopt_pyramid(hipStream_t s, const int* keys_min, const int* bits, int W, int H, float* v0, float* n0, float* v1, float* n1,
                           float* v2, float* n2, const TrackState* st, const RingOut* ring) {
   const size_t P0 = (size_t)W * H;
-  const int nb0 = (int)((P0 + 255) / 256), nb1 = ((W / 2 + 63) / 64) * ((H / 2 + 3) / 4), nb2 = ((W / 4 + 63) / 64) * ((H / 4 + 3) / 4);
+  const int nb0 = (int)((P0 + 255) / 256), nb1 = resize_blocks(W / 2, H / 2), nb2 = resize_blocks(W / 4, H / 4);
   const RingOut quiet = {nullptr, nullptr, nullptr};
   const CompositeIn C = {keys_min, bits, P0};
   hipLaunchKernelGGL(k_adopt_pyramid, dim3(nb0 + nb1 + nb2), dim3(64, 4), 0, s, C, W, H, v0, n0, v1, n1, v2, n2, st, nb0, nb1, ring ? *ring : quiet);
@@ -872,8 +702,13 @@ static __device__ __forceinline__ void icp_accumulate_pixels(IcpLaneIn<ICP_PX>& 
   }
 }
 
-// block reduction of the per-lane accumulators -> 27 (unscaled) sums in out[0..26], valid after the barrier
-static __device__ __forceinline__ void icp_block_sums(const double* acc, double (*sh)[32], double* out) {
+// Block reduction of the per-lane accumulators: the wave sums, the cross-wave step through LDS, and in thread k < 27 the
+// block's sum k, which goes one of two ways.  Holds a barrier: all threads of the block call it, or none.
+//   ATOMIC = false: the 27 (unscaled) sums into dst[0..26] (a row of per-block partials)
+//   ATOMIC = true : one f64 atomic add per sum into this block's shard of dst, an accumulator slot of the fused iterations
+//                   (hsk_icp_dev.h)
+template <bool ATOMIC>
+static __device__ __forceinline__ void icp_block_sums(const double* acc, double (*sh)[32], double* __restrict__ dst) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double v = wave_sum27(acc, lane);
   if ((lane & 1) == 0) sh[wave][wave_sum27_index(lane)] = v;
@@ -882,7 +717,11 @@ static __device__ __forceinline__ void icp_block_sums(const double* acc, double 
     double r = 0.0;
 #pragma unroll
     for (int w = 0; w < ICP_BLOCK / 64; ++w) r += sh[w][threadIdx.x];
-    out[threadIdx.x] = r * ICP_UNSCALE;
+    if (!ATOMIC)
+      dst[threadIdx.x] = r * ICP_UNSCALE;
+    else if (r != 0.0)
+      __hip_atomic_fetch_add(dst + (blockIdx.x % ICP_SHARDS) * 32 + threadIdx.x, r * ICP_UNSCALE, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -904,12 +743,22 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_accumulate(const float* __res
 #pragma unroll
     for (int k = 0; k < 27; ++k) acc[k] = 0.0;
   }
-  icp_block_sums(acc, sh, partials + (size_t)blockIdx.x * 27);
+  icp_block_sums<false>(acc, sh, partials + (size_t)blockIdx.x * 27);
 }
 
 // pixels per lane by level width, chosen so that a level's blocks fit the 256 CUs in one round (4:3 images)
 static inline int icp_px(int W) { return W >= 512 ? ICP_PX_FINE : (W >= 256 ? ICP_PX_MID : 1); }
 int icp_num_blocks(int W, int rows) { return (W * rows + ICP_BLOCK * icp_px(W) - 1) / (ICP_BLOCK * icp_px(W)); }
+// f(px) with px an std::integral_constant of icp_px(W): the template argument of the kernel that f launches
+template <class F>
+static inline void icp_px_dispatch(int W, F f) {
+  if (icp_px(W) == ICP_PX_FINE)
+    f(std::integral_constant<int, ICP_PX_FINE>());
+  else if (icp_px(W) == ICP_PX_MID)
+    f(std::integral_constant<int, ICP_PX_MID>());
+  else
+    f(std::integral_constant<int, 1>());
+}
 
 // The kernels gate on squared quantities.  dist2_max: the largest binary32 y with sqrtf(y) <= dist_thresh;
 // sine2_lim: the smallest y with sqrtf(y) >= angle_thresh.  With a correctly rounded, monotone sqrtf:
@@ -946,15 +795,10 @@ void launch_icp_accumulate(hipStream_t s, const float* vcur, const float* ncur, 
                            int row1, double* partials) {
   const int nb = icp_num_blocks(W, row1 - row0);
   icp_gate_limits(dist_thresh, angle_thresh, &dist_thresh, &angle_thresh);  // the kernels take the squared limits
-  if (icp_px(W) == ICP_PX_FINE)
-    hipLaunchKernelGGL(k_icp_accumulate<ICP_PX_FINE>, dim3(nb), dim3(ICP_BLOCK), 0, s, vcur, ncur, vprev, nprev, W, H, in, st,
+  icp_px_dispatch(W, [&](auto px) {
+    hipLaunchKernelGGL(k_icp_accumulate<decltype(px)::value>, dim3(nb), dim3(ICP_BLOCK), 0, s, vcur, ncur, vprev, nprev, W, H, in, st,
                        dist_thresh, angle_thresh, row0, row1, partials);
-  else if (icp_px(W) == ICP_PX_MID)
-    hipLaunchKernelGGL(k_icp_accumulate<ICP_PX_MID>, dim3(nb), dim3(ICP_BLOCK), 0, s, vcur, ncur, vprev, nprev, W, H, in, st,
-                       dist_thresh, angle_thresh, row0, row1, partials);
-  else
-    hipLaunchKernelGGL(k_icp_accumulate<1>, dim3(nb), dim3(ICP_BLOCK), 0, s, vcur, ncur, vprev, nprev, W, H, in, st,
-                       dist_thresh, angle_thresh, row0, row1, partials);
+  });
 }
 
 // reduce per-block partials -> 27 sums (one block of 256 threads)
@@ -1051,23 +895,6 @@ static __device__ __forceinline__ void shard_reduce27(const double* __restrict__
   __syncthreads();
 }
 
-// block sums -> one f64 atomic add per sum into this block's shard
-static __device__ __forceinline__ void icp_block_sums_atomic(const double* acc, double (*sh)[32], double* __restrict__ slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double v = wave_sum27(acc, lane);
-  if ((lane & 1) == 0) sh[wave][wave_sum27_index(lane)] = v;
-  __syncthreads();
-  if (threadIdx.x < 27) {
-    double r = 0.0;
-#pragma unroll
-    for (int w = 0; w < ICP_BLOCK / 64; ++w) r += sh[w][threadIdx.x];
-    if (r != 0.0)
-      __hip_atomic_fetch_add(slot + (blockIdx.x % ICP_SHARDS) * 32 + threadIdx.x, r * ICP_UNSCALE, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-
 template <int ICP_PX>
 __global__ __launch_bounds__(ICP_BLOCK) void k_icp_iter(double* __restrict__ slots, int iter, const IcpPose* __restrict__ pose_in,
                                                         TrackState* st, const float* __restrict__ vcur,
@@ -1143,7 +970,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_icp_iter(double* __restrict__ slo
     icp_accumulate_pixels<ICP_PX>(L, vprev, nprev, W, H, in, sp.R, sp.t, Rp, tp, dist_thresh, angle_thresh, acc);
     ICP_STAMP(3);
     // (no barrier here: `sh` has no other user in this kernel since the sums of the previous iteration are gathered by one wave)
-    icp_block_sums_atomic(acc, (double (*)[32])sh, slot_add);
+    icp_block_sums<true>(acc, (double (*)[32])sh, slot_add);
   }
   ICP_STAMP(4);
 }
@@ -1180,9 +1007,7 @@ static inline double* icp_slots(void* pose_buf) { return (double*)((char*)pose_b
 // enqueue the whole ICP of one frame: levels coarse -> fine, iters[l] iterations each
 void launch_icp_fused(hipStream_t s, float* const* vcur, float* const* ncur, float* const* vmod, float* const* nmod,
                       const ImgLevel* lv, const int* iters, TrackState* st, float dist_thresh, float angle_thresh,
-                      void* pose_buf, double* part_a, double* part_b, IcpFinal* defer_final, hipEvent_t* level_events) {
-  (void)part_a;
-  (void)part_b;
+                      void* pose_buf, IcpFinal* defer_final, hipEvent_t* level_events) {
   static_assert(2 * sizeof(IcpPose) <= ICP_POSE_AREA, "pose ping-pong must fit its area");
   IcpPose* pb = (IcpPose*)pose_buf;
   double* slots = icp_slots(pose_buf);
@@ -1192,17 +1017,11 @@ void launch_icp_fused(hipStream_t s, float* const* vcur, float* const* ncur, flo
     const int W = lv[l].W, H = lv[l].H;
     const int nb = icp_num_blocks(W, H);
     if (level_events) (void)hipEventRecord(level_events[HSK_NLEVELS - 1 - l], s);  // profiling: the level's iterations start
-    for (int it = 0; it < iters[l]; ++it, ++i) {
-      if (icp_px(W) == ICP_PX_FINE)
-        hipLaunchKernelGGL(k_icp_iter<ICP_PX_FINE>, dim3(nb), dim3(ICP_BLOCK), 0, s, slots, i, pb + (i & 1), st, vcur[l], ncur[l],
+    for (int it = 0; it < iters[l]; ++it, ++i)
+      icp_px_dispatch(W, [&](auto px) {
+        hipLaunchKernelGGL(k_icp_iter<decltype(px)::value>, dim3(nb), dim3(ICP_BLOCK), 0, s, slots, i, pb + (i & 1), st, vcur[l], ncur[l],
                            vmod[l], nmod[l], W, H, lv[l].in, dist_thresh, angle_thresh, pb + ((i + 1) & 1));
-      else if (icp_px(W) == ICP_PX_MID)
-        hipLaunchKernelGGL(k_icp_iter<ICP_PX_MID>, dim3(nb), dim3(ICP_BLOCK), 0, s, slots, i, pb + (i & 1), st, vcur[l], ncur[l],
-                           vmod[l], nmod[l], W, H, lv[l].in, dist_thresh, angle_thresh, pb + ((i + 1) & 1));
-      else
-        hipLaunchKernelGGL(k_icp_iter<1>, dim3(nb), dim3(ICP_BLOCK), 0, s, slots, i, pb + (i & 1), st, vcur[l], ncur[l], vmod[l], nmod[l],
-                           W, H, lv[l].in, dist_thresh, angle_thresh, pb + ((i + 1) & 1));
-    }
+      });
   }
   if (level_events) (void)hipEventRecord(level_events[HSK_NLEVELS], s);
   if (i > 0 && defer_final) {

@@ -7,7 +7,8 @@
 
 // one level of the map pyramid inside a wave that holds an 8x8 pixel tile (lane = y * 8 + x): the lane at the top
 // left of each 2x2 group (dx, dy = lane distance to its right / lower neighbour at this level) forms the mean of the
-// vertex taps and the renormalised mean of the normal taps, NaN when any tap is NaN; other lanes' results are unused
+// vertex taps and the renormalised mean of the normal taps, NaN when any tap is NaN; other lanes' results are unused.
+// (The rule is hsk_mean2x2's, hsk_dev.h, written out once more: calling it here changes k_raycast's listing.)
 static __device__ __forceinline__ void pyramid_step(const float* m, int dx, int dy, float* out) {
   float t1[6], t2[6], t3[6];
 #pragma unroll
@@ -130,8 +131,8 @@ __global__ __launch_bounds__(RC_BLOCK, RC_WPE) void k_raycast(RcArgs a) {
   RC_STAMP(3);
   if (!SLAB && pyr.v1) {
     // Model pyramid (resizeVMap / resizeNMap, A.3) from the wave's own 8x8 tile: level 1 is the 2x2 mean held by
-    // the even-even lanes, level 2 the 2x2 mean of those -- the arithmetic and its order are k_resize_maps2's, the
-    // taps arrive by lane shuffles instead of a second launch reading the maps back.
+    // the even-even lanes, level 2 the 2x2 mean of those -- the arithmetic and its order are hsk_mean2x2's (what
+    // k_resize_maps2 computes), the taps arrive by lane shuffles instead of a second launch reading the maps back.
     float m[6] = {vx, vy, vz, nx, ny, nz};
     float l1[6], l2[6];
     pyramid_step(m, 1, RC_TW, l1);
