@@ -177,6 +177,31 @@ class HskPlaneRecord(C.Structure):
     ]
 
 
+HSK_UPRIGHT_NO_YAW = 1
+HSK_UPRIGHT_UP, HSK_UPRIGHT_YAW, HSK_UPRIGHT_FLOOR, HSK_UPRIGHT_CEILING = 1, 2, 4, 8
+HSK_UPRIGHT_MAX_POINTS, HSK_UPRIGHT_MAX_REFITS, HSK_UPRIGHT_HIST_BINS, HSK_UPRIGHT_HEIGHT_BINS, HSK_UPRIGHT_AXIS_MAX2 = 1 << 24, 8, 1536, 16384, 16810000
+
+
+class HskUprightParams(C.Structure):
+    """Mirror of `hsk_upright_params` (include/hskinfu.h): 36 bytes; every field is taken as it stands."""
+
+    _fields_ = [
+        ("up_hint", C.c_float * 3), ("max_tilt_cos", C.c_float), ("cone_cos", C.c_float), ("wall_sin", C.c_float),
+        ("min_fraction", C.c_float), ("refits", C.c_int32), ("flags", C.c_uint32),
+    ]
+
+
+class HskUpright(C.Structure):
+    """Mirror of `hsk_upright` (include/hskinfu.h): 128 bytes."""
+
+    _fields_ = [
+        ("level", C.c_float * 16), ("floor_m", C.c_float), ("ceiling_m", C.c_float),
+        ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
+        ("n_points", C.c_uint32), ("n_invalid", C.c_uint32), ("n_axis", C.c_uint32 * 3), ("n_walls", C.c_uint32),
+        ("found", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
 HSK_RAY_HIT, HSK_RAY_FRONTIER, HSK_RAY_OPEN, HSK_RAY_BLIND, HSK_RAY_OUTSIDE = 0, 1, 2, 3, 4
 HSK_RAY_CLASS = ("hit", "frontier", "open", "blind", "outside")
 HSK_EYE_FREE, HSK_EYE_UNSEEN, HSK_EYE_SOLID, HSK_EYE_OUTSIDE = 0, 1, 2, 3
@@ -444,6 +469,18 @@ SYMBOLS = {
                                            C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_score_planes": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_float, C.c_float, _P]),
     "hsk_plane_refit": (C.c_int, [C.POINTER(C.c_int64), _F, _F, _I]),
+    "hsk_default_upright_params": (None, [C.POINTER(HskUprightParams)]),
+    "hsk_estimate_upright": (C.c_int, [_P, C.POINTER(HskUprightParams), C.POINTER(HskUpright)]),
+    "hsk_estimate_upright_oriented": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.POINTER(HskUprightParams), C.POINTER(HskUpright)]),
+    "hsk_upright_sums": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_float, C.c_float, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "hsk_upright_solve_seed": (C.c_int, [_P, _P, C.c_float, C.c_uint64, _P, _P, _I]),
+    "hsk_upright_solve_axis": (C.c_int, [_P, _P, _P, _I]),
+    "hsk_upright_solve_basis": (C.c_int, [_P, _P, _P]),
+    "hsk_upright_solve_yaw": (C.c_int, [_P, C.c_uint64, _P, _P, _I]),
+    "hsk_upright_solve_frame": (C.c_int, [_P, C.c_uint64, _P, C.c_int, _P, _P]),
+    "hsk_upright_solve_rows": (C.c_int, [_P, _P, _P, _P]),
+    "hsk_upright_solve_heights": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P]),
+    "hsk_level_config": (C.c_int, [_P, C.POINTER(HskUpright), C.c_float, _P, _F]),
     "hsk_default_probe": (None, [_P, C.POINTER(HskProbe)]),
     "hsk_coverage_census": (C.c_int, [_P, C.POINTER(HskVoxelBox), C.POINTER(HskCoverage)]),
     "hsk_score_views": (C.c_int, [_P, C.POINTER(HskProbe), _P, C.c_size_t, C.POINTER(HskViewScore)]),

@@ -154,7 +154,8 @@ struct hsk_ctx {
   // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
   // volume alignment (hsk_align_cloud), made on first use as a destination and only grown: the accumulators (align.hip:
   // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what pose scoring adds (api_reloc.hip: the poses, the slabs'
-  // partial values, the scores; api_planes.hip: the labels, the hypotheses, the blocks' sums); h_align: the accumulators' pinned host side
+  // partial values, the scores; api_planes.hip: the labels, the hypotheses, the blocks' sums; api_level.hip: the cube-map histogram, the blocks'
+  // partial values, the height histograms); h_align: the accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;
   unsigned long long* h_align = nullptr;

@@ -274,6 +274,37 @@ void launch_plane_unlabel(hipStream_t s, int* labels, int index, unsigned n);
 // a cloud with normals as two arrays of packed triples (the product buffer's) -> the six planes
 void launch_plane_gather(hipStream_t s, const float* xyz, const float* normals, unsigned n, unsigned pitch, float* soa);
 
+// the upright-frame estimate (level.hip) over the n points of the six planes at `soa` (`pitch` floats apart), their
+// normals weighted by w.  Every sum is an integer.  hist: HSK_LEVEL_HIST_BINS counts and one more word, the valid points -- ZEROED by
+// the caller.  sums: sums15 = per axis a < n_axes the supporters' count and the three sums of sign(N . A) N (words 4 a ..), then --
+// wall set -- the wall points of W[0], their count and the two fourth-power sums against W[1], W[2] (words 12 ..); partial:
+// level_blocks(n) x 16 words.  extents: box6 = the min (3) then max (3) of P . R_k over the valid points as signed 64-bit words
+// (INT32_MAX / INT32_MIN when there is none); classes set: the two height histograms, HSK_LEVEL_H_BINS bins a class, the floor class
+// first -- h_count, h_sum ZEROED by the caller.  Nothing is launched with n == 0.
+#define HSK_LEVEL_MAX_BLOCKS 1024
+struct LevelWeights {
+  float w[3];
+};
+struct LevelAxes {
+  int A[3][3], W[3][3];      // integer axes: |A|^2 <= HSK_UPRIGHT_AXIS_MAX2
+  long long aa[3], waa;      // |A_a|^2, |W_0|^2
+  double cone2, wall2;       // the squared cosine of the cone, the squared sine of the wall test
+  int n_axes, wall;
+};
+struct LevelFrame {
+  int R[3][3];
+  long long raa;             // |R_1|^2
+  double cone2;
+  int classes;
+};
+unsigned level_blocks(unsigned n);
+void launch_level_hist(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, unsigned* hist);
+void launch_level_sums(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, const LevelAxes& ax,
+                       unsigned long long* partial, unsigned long long* sums15);
+void launch_level_extents(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, const LevelFrame& fr,
+                          unsigned long long* partial, unsigned long long* box6, unsigned* h_count, unsigned long long* h_sum);
+int level_warm();     // loads level.hip's code object (hsk_prepare_readout); a hipError_t
+
 // sparse volume image (pack.hip): bricks of 8^3 voxels, pack_bricks of them, a class byte and a record size
 // (in 4-byte words) each.  launch_pack_scan turns the sizes into offsets in place (an exclusive scan; bsum: pack_scan_blocks
 // words of scratch) and leaves in counts[0..3] the bricks per class, in counts[4] the payload's length in words (8 words).

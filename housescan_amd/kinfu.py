@@ -1215,6 +1215,116 @@ class KinfuTracker:
                                            len(pl), dist_m, cos_min, out.ctypes.data if len(pl) else None))
         return out
 
+    # ---- upright frame ------------------------------------------------------------------------------------
+    @staticmethod
+    def _upright_params(over):
+        """the defaults with the keywords up_hint, max_tilt_cos, cone_cos, wall_sin, min_fraction, refits, flags over them"""
+        p = _lib.HskUprightParams()
+        _lib.load().hsk_default_upright_params(C.byref(p))
+        for name, val in over.items():
+            if name not in dict(p._fields_):
+                raise TypeError(f"unknown upright parameter {name!r}")
+            if name == "up_hint":
+                val = (C.c_float * 3)(*[float(v) for v in val])
+            setattr(p, name, val)
+        return p
+
+    @staticmethod
+    def _upright_dict(u):
+        return {"level": np.array(u.level, np.float32).reshape(4, 4), "floor_m": np.float32(u.floor_m), "ceiling_m": np.float32(u.ceiling_m),
+                "box_lo": np.array(u.box_lo, np.float32), "box_hi": np.array(u.box_hi, np.float32), "n_points": int(u.n_points),
+                "n_invalid": int(u.n_invalid), "n_axis": [int(v) for v in u.n_axis], "n_walls": int(u.n_walls), "found": int(u.found)}
+
+    @staticmethod
+    def _upright_struct(up):
+        u = _lib.HskUpright()
+        u.level = (C.c_float * 16)(*np.asarray(up["level"], np.float32).reshape(16))
+        u.floor_m, u.ceiling_m = float(up["floor_m"]), float(up["ceiling_m"])
+        u.box_lo = (C.c_float * 3)(*np.asarray(up["box_lo"], np.float32))
+        u.box_hi = (C.c_float * 3)(*np.asarray(up["box_hi"], np.float32))
+        u.n_points, u.n_invalid, u.n_walls, u.found = up["n_points"], up["n_invalid"], up["n_walls"], up["found"]
+        u.n_axis = (C.c_uint32 * 3)(*up["n_axis"])
+        return u
+
+    def estimate_upright(self, **params):
+        """the upright frame of this volume's own cloud, which stays on the device (hsk_estimate_upright).  Keywords: up_hint,
+        max_tilt_cos, cone_cos, wall_sin, min_fraction, refits, flags -> dict of hsk_upright's fields: level [4, 4] (row 1 is down),
+        floor_m, ceiling_m, box_lo, box_hi, n_points, n_invalid, n_axis, n_walls, found (HSK_UPRIGHT_* bits)"""
+        p, u = self._upright_params(params), _lib.HskUpright()
+        self._ck(self.lib.hsk_estimate_upright(self.h, C.byref(p), C.byref(u)))
+        return self._upright_dict(u)
+
+    def estimate_upright_oriented(self, xyz, normals, cell_weights=None, **params):
+        """the same on the points xyz [n, 3] with normals [n, 3] (hsk_estimate_upright_oriented); cell_weights: the three c_min / c_k
+        of normals that are differences over one cell per axis, None for true normals"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(pts) != len(nrm):
+            raise ValueError(f"estimate_upright_oriented: {len(pts)} points but {len(nrm)} normals")
+        w = None if cell_weights is None else np.ascontiguousarray(cell_weights, np.float32).reshape(3)
+        p, u = self._upright_params(params), _lib.HskUpright()
+        self._ck(self.lib.hsk_estimate_upright_oriented(self.h, pts.ctypes.data if len(pts) else None, nrm.ctypes.data if len(pts) else None, len(pts),
+                                                        None if w is None else w.ctypes.data, C.byref(p), C.byref(u)))
+        return self._upright_dict(u)
+
+    def upright_sums(self, xyz, normals, cell_weights=None, cone_cos=0.984807753012208, wall_sin=0.25881904510252074, hist=False, axes=None,
+                     wall_axes=None, frame=None, heights=False):
+        """the device stages of the estimate alone, for integer axes (hsk_upright_sums) -> dict with, as asked: hist [1536] uint32 and
+        n_valid; axis_sums [len(axes), 4] int64; wall_sums [3] int64; box [6] int32 and -- heights -- height_counts [2, 16384] uint32,
+        height_sums [2, 16384] int64"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        w = None if cell_weights is None else np.ascontiguousarray(cell_weights, np.float32).reshape(3)
+        out = {}
+        if hist:
+            out["hist"], out["n_valid"] = np.zeros(_lib.HSK_UPRIGHT_HIST_BINS, np.uint32), np.zeros(1, np.uint32)
+        ax = None if axes is None else np.ascontiguousarray(axes, np.int32).reshape(-1, 3)
+        if ax is not None:
+            out["axis_sums"] = np.zeros((len(ax), 4), np.int64)
+        wa = None if wall_axes is None else np.ascontiguousarray(wall_axes, np.int32).reshape(3, 3)
+        if wa is not None:
+            out["wall_sums"] = np.zeros(3, np.int64)
+        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(3, 3)
+        if fr is not None:
+            out["box"] = np.zeros(6, np.int32)
+            if heights:
+                out["height_counts"] = np.zeros((2, _lib.HSK_UPRIGHT_HEIGHT_BINS), np.uint32)
+                out["height_sums"] = np.zeros((2, _lib.HSK_UPRIGHT_HEIGHT_BINS), np.int64)
+
+        def ptr(name):
+            return out[name].ctypes.data if name in out else None
+
+        self._ck(self.lib.hsk_upright_sums(self.h, pts.ctypes.data if len(pts) else None, nrm.ctypes.data if len(pts) else None, len(pts),
+                                           None if w is None else w.ctypes.data, cone_cos, wall_sin, ptr("hist"), ptr("n_valid"),
+                                           None if ax is None else ax.ctypes.data, 0 if ax is None else len(ax), ptr("axis_sums"),
+                                           None if wa is None else wa.ctypes.data, ptr("wall_sums"), None if fr is None else fr.ctypes.data,
+                                           ptr("box"), ptr("height_counts"), ptr("height_sums")))
+        if hist:
+            out["n_valid"] = int(out["n_valid"][0])
+        return out
+
+    def level_config(self, upright, margin_m=None):
+        """the configuration of the levelled destination of this volume and the matrix fuse_from(self, M) takes (hsk_level_config);
+        margin_m None: the effective truncation distance plus two cells -> (HskConfig, M [4, 4] float32)"""
+        cfg, m = _lib.HskConfig(), np.zeros(16, np.float32)
+        u = self._upright_struct(upright)
+        self._ck(self.lib.hsk_level_config(self.h, C.byref(u), -1.0 if margin_m is None else margin_m, C.byref(cfg), _fp(m)))
+        return cfg, m.reshape(4, 4)
+
+    def levelled(self, margin_m=None, **params):
+        """a new tracker that holds this volume levelled: estimate_upright, level_config, then the fuse of this volume into the new
+        one; it stands at this tracker's pose taken into the levelled frame (call resume_scan(its pose) to scan on)
+        -> (tracker, M [4, 4] float32, the upright dict)"""
+        up = self.estimate_upright(**params)
+        cfg, m = self.level_config(up, margin_m)
+        dst = KinfuTracker(cfg)
+        try:
+            dst.fuse_from(self, m)
+        except Exception:
+            dst.close()
+            raise
+        return dst, m, up
+
     # ---- volume files -----------------------------------------------------------------------------------
     def pack_volume(self, with_info=False):
         """the volume (TSDF, and colour once enabled) as a lossless sparse image, packed on the device (hsk_pack_volume)

@@ -679,6 +679,95 @@ int hsk_score_planes(hsk_ctx* k, const float* xyz, const float* normals, const i
  * length below 1e-12.  HSK_ERR_ARG: a NULL pointer, m < 0 or > 2^24, a sum outside +-2^62. */
 int hsk_plane_refit(const int64_t sums10[10], const float prev_abcd[4], float out_abcd[4], int* ok);
 
+/* ---- Upright frame: level a scan.  The volume's frame is the first camera's; a hand-held scan that starts looking down puts the
+ * room into the volume tilted, and every floor form (hsk_clearance_floor, hsk_reach_floor, hsk_partition_floor) and floor plan
+ * wants the up axis to be one of the volume's axes.  This estimates the scan's upright (Manhattan) frame from its oriented points
+ * -- the up direction from floor and ceiling together, the two wall directions from all walls at once, the floor and ceiling
+ * heights and the content's box -- on the device, in a handful of streaming passes with integer sums: the result is the same bits
+ * whatever the launch shape (DESIGN.md 3.21 the kernels, 8o the rule; tests/level_twin.py restates the rule in numpy).
+ * hsk_level_config turns it into the configuration of a levelled, wall-aligned volume of minimal size and the matrix that
+ * hsk_fuse_volume, hsk_transform_cloud and hsk_write_xf take. */
+#define HSK_UPRIGHT_NO_YAW 1u          /* params.flags: level only, row 0 is the volume's +X projected                          */
+#define HSK_UPRIGHT_UP 1u              /* found: the up direction ...                                                           */
+#define HSK_UPRIGHT_YAW 2u             /* ... the walls' direction ...                                                          */
+#define HSK_UPRIGHT_FLOOR 4u           /* ... floor_m ...                                                                       */
+#define HSK_UPRIGHT_CEILING 8u         /* ... ceiling_m                                                                         */
+#define HSK_UPRIGHT_MAX_POINTS ((size_t)1 << 24)
+#define HSK_UPRIGHT_MAX_REFITS 8
+#define HSK_UPRIGHT_HIST_BINS 1536     /* the cube map of normals: 6 faces x 16 x 16                                            */
+#define HSK_UPRIGHT_HEIGHT_BINS 16384  /* the height histograms: 1/64 m a bin, bin 8192 begins at 0                             */
+#define HSK_UPRIGHT_AXIS_MAX2 16810000 /* the largest |A|^2 of an integer axis A = rint(a 4096): 4100^2                         */
+typedef struct hsk_upright_params {
+  float up_hint[3];       /* roughly up, in the volume's frame; finite, not zero        default (0, -1, 0): image y points down */
+  float max_tilt_cos;     /* up lies within this cone about the hint, [-1, 1]                            default cos 45 deg */
+  float cone_cos;         /* a point supports an axis when its normal lies within this cone, (0, 1]      default cos 10 deg */
+  float wall_sin;         /* a wall point's normal lies within this angle of the horizon, [0, 1]         default sin 15 deg */
+  float min_fraction;     /* an axis needs max(3, floor(min_fraction n)) supporters; finite, >= 0        default 0.02       */
+  int32_t refits;         /* 0..8                                                                        default 3          */
+  uint32_t flags;         /* HSK_UPRIGHT_NO_YAW                                                          default 0          */
+} hsk_upright_params;     /* 36 bytes; every field is taken as it stands (no "0 = default")                                 */
+void hsk_default_upright_params(hsk_upright_params* p);
+typedef struct hsk_upright {
+  float level[16];        /* row-major, a pure rotation, p_level = L p_volume: row 1 (the levelled +Y) is DOWN, row 0 the wall
+                             direction nearest the volume's +X, row 2 = row 0 x row 1.  The identity unless UP was found       */
+  float floor_m, ceiling_m; /* the levelled y of the floor and of the ceiling (floor_m > ceiling_m: y points down)            */
+  float box_lo[3], box_hi[3]; /* the valid points' box in the levelled frame                                                 */
+  uint32_t n_points, n_invalid; /* the cloud; of it, the points with a number not finite, |x| > 64, |n_k| > 2 or N = 0        */
+  uint32_t n_axis[3];     /* the supporters of the three rows in the last refit (refits = 0: [1] is the seed's support)       */
+  uint32_t n_walls;       /* the wall points the yaw was taken from                                                          */
+  uint32_t found;         /* HSK_UPRIGHT_UP | _YAW | _FLOOR | _CEILING                                                        */
+  uint32_t pad;           /* 0                                                                                                */
+} hsk_upright;            /* 128 bytes */
+/* The upright frame of the context's own cloud and normals (hsk_extract_cloud_attrs' points), which never leave the device; the
+ * normals are weighted by the cells (w_k = c_min / c_k: the raycast's normals are differences over one cell per axis).  params
+ * NULL: the defaults.  An empty cloud: HSK_OK, nothing found.  Nothing the tracker reads is written, and the cached count pass
+ * stays valid.  HSK_ERR_ARG: a NULL context or out; a parameter outside its range; a cloud of more than 2^24 points.
+ * HSK_ERR_STATE: as hsk_detect_planes_volume (a frame in flight, a slab of a group, a context that stores part of its volume). */
+int hsk_estimate_upright(hsk_ctx* k, const hsk_upright_params* params, hsk_upright* out);
+/* The same on a caller's n points with normals (3 floats each), through the alignment scratch.  cell_weights: the three w_k, each
+ * in (0, 1]; NULL: 1, 1, 1 (true normals).  n = 0: HSK_OK, nothing found.  HSK_ERR_ARG also: NULL xyz or normals with n > 0,
+ * n > 2^24, a weight outside (0, 1].  HSK_ERR_STATE: a frame in flight. */
+int hsk_estimate_upright_oriented(hsk_ctx* k, const float* xyz, const float* normals, size_t n, const float cell_weights[3],
+                                  const hsk_upright_params* params, hsk_upright* out);
+/* The device stages alone, for integer axes A = rint(a 4096) the caller gives (|A|^2 <= HSK_UPRIGHT_AXIS_MAX2, not zero); every
+ * output may be NULL and its stage is then not run:
+ *   hist: the cube-map histogram, HSK_UPRIGHT_HIST_BINS counts; n_valid: the valid points (either or both);
+ *   axis_sums: for each of the n_axes <= 3 axes (3 ints each) the count of its supporters and the three sums of sign(N . A) N;
+ *   wall_sums: for wall_axes = (up, e1, e2) the count of up's wall points and the two fourth-power sums;
+ *   box: for frame = three rows R, the min (3) and max (3) of t_k = P . R_k over the valid points (zeros when there is none), in
+ *   units of 2^-22 m; height_counts and height_sums (both or neither): 2 x HSK_UPRIGHT_HEIGHT_BINS, the floor class then the ceiling
+ *   class -- the supporters of R_1 whose normal points against it, then along it: per bin the count and the sum of t_1.
+ * cone_cos and wall_sin as in hsk_upright_params.  Errors as hsk_estimate_upright_oriented's; n = 0: zeros. */
+int hsk_upright_sums(hsk_ctx* k, const float* xyz, const float* normals, size_t n, const float cell_weights[3], float cone_cos,
+                     float wall_sin, uint32_t* hist, uint32_t* n_valid, const int32_t* axes, int n_axes, int64_t* axis_sums,
+                     const int32_t* wall_axes, int64_t* wall_sums, const int32_t* frame, int32_t* box, uint32_t* height_counts,
+                     int64_t* height_sums);
+/* host only: the steps between the device stages, in binary64 with + - x / and sqrt only.  `least`:
+ * the least count max(3, floor(min_fraction n)).  HSK_ERR_ARG: a NULL pointer, a hint that is zero or not finite.
+ *   seed: the 2 x 2 block of histogram bins of the largest support (its four counts plus their antipodes') among those whose shared
+ *   corner lies within max_tilt_cos of the hint -> the corner's direction, the support, *found = the support reaches `least`;
+ *   axis: sums4 = (count, S) -> S / |S| in the hint's hemisphere, *ok = 0 when S = 0;
+ *   basis: (e1, e2) of the plane across `up`;  yaw: wall3 = (count, re, im) -> x, *found = 0 and the plain x without it;
+ *   frame: one refit of (up, x), in place, from the three rows' sums12;  rows: the three rows (x, -up, x x -up);
+ *   heights: floor_m, ceiling_m and the bits HSK_UPRIGHT_FLOOR | HSK_UPRIGHT_CEILING from the two height histograms. */
+int hsk_upright_solve_seed(const uint32_t* hist, const float up_hint[3], float max_tilt_cos, uint64_t least, double axis[3],
+                           uint64_t* support, int* found);
+int hsk_upright_solve_axis(const int64_t sums4[4], const float up_hint[3], double axis[3], int* ok);
+int hsk_upright_solve_basis(const double up[3], double e1[3], double e2[3]);
+int hsk_upright_solve_yaw(const int64_t wall3[3], uint64_t least, const double up[3], double x[3], int* found);
+int hsk_upright_solve_frame(const int64_t sums12[12], uint64_t least, const float up_hint[3], int yaw, double up[3], double x[3]);
+int hsk_upright_solve_rows(const double up[3], const double x[3], double rows9[9], int32_t axes9[9]);
+int hsk_upright_solve_heights(const uint32_t* height_counts, const int64_t* height_sums, uint64_t least, double* floor_m,
+                              double* ceiling_m, uint32_t* found);
+/* host only: the configuration of the levelled destination of `src` and the matrix hsk_fuse_volume(dst, src, M) takes.  One
+ * isotropic cell, the source's largest; the extent is up's box plus margin_m on every side (negative: the effective truncation
+ * distance plus two cells), every dim rounded up to a multiple of 8; M = T L with the translation that puts box_lo - margin at
+ * the origin.  Camera, ICP and device fields are the source's; init_pose = M x the source's current pose (what
+ * hsk_resume_scan(dst, .) wants); trunc_dist_m = the source's effective truncation distance, and each vol_size_m[k] is the
+ * largest binary32 not above dims_k c whose quotient by dims_k does not exceed c, so the two effective distances are bit-equal.
+ * HSK_ERR_ARG: a NULL pointer, UP not found, a margin that is not finite, a box that is not finite or gives a dim above 4096. */
+int hsk_level_config(hsk_ctx* src, const hsk_upright* up, float margin_m, hsk_config* cfg, float src_to_dst[16]);
+
 /* ---- Scan coverage: what the volume has never observed, and where the camera should go to see it (DESIGN.md 3.15 the kernels,
  * 8i the rule; tests/cover_twin.py restates the rule in numpy).  A voxel is UNSEEN when its weight is 0, FREE when it was
  * observed with a positive TSDF, SOLID when it was observed with a TSDF <= 0.  The host loop: hsk_coverage_census (is anything

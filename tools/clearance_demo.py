@@ -7,7 +7,7 @@ more (floor_map.pgm: solid or never observed; floor_map_solid.pgm: solids only);
 hsk_rank_views_clear with min_d2 = hsk_clearance_d2(0.3 m) on the clearance at the camera centres (hsk_clearance_at); printed:
 how many of hsk_rank_views' top 10 the clearance moved back.
 
-usage: python tools/clearance_demo.py [--n 256] [--frames 720] [--stride 4] [--min-clear 0.3] [--out clearance_demo]"""
+usage: python tools/clearance_demo.py [--n 256] [--frames 720] [--stride 4] [--min-clear 0.3] [--out clearance_demo] [--estimate-floor]"""
 import argparse
 import os
 import sys
@@ -31,8 +31,10 @@ def main():
     ap.add_argument("--stride", type=int, default=4)
     ap.add_argument("--min-clear", type=float, default=0.3, help="metres a viewpoint must keep from anything solid or unknown")
     ap.add_argument("--out", default="clearance_demo")
+    ap.add_argument("--estimate-floor", action="store_true", help="take the floor's height from hsk_estimate_upright instead of the synthetic room's extents")
     args = ap.parse_args()
     import housescan_amd as hsk
+    from level_demo import estimated_floor        # (beside this file)
 
     os.makedirs(args.out, exist_ok=True)
     poses = [hsk.synth_room_pose(0, k, 720) for k in range(0, args.frames, args.stride)]
@@ -45,7 +47,7 @@ def main():
           f"{st['n_far']} farther than a metre, scratch {st['scratch_bytes'] / 2 ** 20:.0f} MiB")
     e = hsk.synth_room_extents(0).astype(np.float64)
     cell = 3.0 / args.n
-    floor_y = e[3]
+    floor_y = estimated_floor(trk, e[3]) if args.estimate_floor else e[3]
     lo, hi = max(0, int(np.floor((floor_y - 1.8) / cell))), min(args.n, int(np.ceil((floor_y - 0.1) / cell)))
     fmap, fst = trk.clearance_floor(1, lo, hi, par)
     metres = hsk.clearance_metres(par, fmap)

@@ -14,7 +14,7 @@ can stand in, grey one that belongs to no room, a colour per room.  The house cl
 room whose air it borders (hsk_partition_at, radius 2); the points of every room are written as a room directory
 (products.write_room_dir) and the directories loaded back (hsh_load_room).
 
-usage: python tools/partition_demo.py [--n 128] [--frames 720] [--stride 8] [--core 0.5] [--out partition_demo]"""
+usage: python tools/partition_demo.py [--n 128] [--frames 720] [--stride 8] [--core 0.5] [--out partition_demo] [--estimate-floor]"""
 import argparse
 import os
 import sys
@@ -39,8 +39,10 @@ def main():
     ap.add_argument("--stride", type=int, default=8)
     ap.add_argument("--core", type=float, default=0.5, help="metres of clearance that make a voxel part of a room's core")
     ap.add_argument("--out", default="partition_demo")
+    ap.add_argument("--estimate-floor", action="store_true", help="take the floor's height from hsk_estimate_upright instead of the synthetic room's extents")
     args = ap.parse_args()
     import housescan_amd as hsk
+    from level_demo import estimated_floor        # (beside this file)
     from housescan_amd import house as H
     from housescan_amd import products as P
 
@@ -94,7 +96,8 @@ def main():
     merged = hsk.merge_rooms(doors, len(rooms), pp.core_d2)
     print(f"    merge at core_d2: {len(set(merged.tolist()))} classes {merged.tolist()}")
     # the floor form
-    lo, hi = max(0, int(np.floor((e[3] - 1.8) / cell))), min(n, int(np.ceil((e[3] - 0.1) / cell)))
+    floor_y = estimated_floor(house, e[3]) if args.estimate_floor else e[3]
+    lo, hi = max(0, int(np.floor((floor_y - 1.8) / cell))), min(n, int(np.ceil((floor_y - 0.1) / cell)))
     fp = house.default_partition_params(walk, core_d2=pp.core_d2, min_core_voxels=int(np.ceil((0.25 / cell) ** 2)))          # (a square of edge 0.25 m, in columns)
     fmap, frooms, fdoors, fst = house.partition_floor(1, lo, hi, walk, fp)
     rgb = np.zeros(fmap.shape + (3,), np.uint8)

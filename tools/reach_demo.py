@@ -11,7 +11,7 @@ of candidate poses around the last pose of either room is scored (hsk_score_view
 hsk_rank_views_clear (0.3 m of room at the camera centre) and by hsk_rank_views_reach (the camera centre can be walked to from the
 seed).  Printed: the three heads, the walk to each of them in metres, and the path to hsk_rank_views_reach's best pose.
 
-usage: python tools/reach_demo.py [--n 128] [--frames 720] [--stride 8] [--min-clear 0.3] [--out reach_demo]"""
+usage: python tools/reach_demo.py [--n 128] [--frames 720] [--stride 8] [--min-clear 0.3] [--out reach_demo] [--estimate-floor]"""
 import argparse
 import os
 import sys
@@ -35,8 +35,10 @@ def main():
     ap.add_argument("--stride", type=int, default=8)
     ap.add_argument("--min-clear", type=float, default=0.3, help="metres a person keeps from anything solid or unknown")
     ap.add_argument("--out", default="reach_demo")
+    ap.add_argument("--estimate-floor", action="store_true", help="take the floor's height from hsk_estimate_upright instead of the synthetic room's extents")
     args = ap.parse_args()
     import housescan_amd as hsk
+    from level_demo import estimated_floor        # (beside this file)
 
     os.makedirs(args.out, exist_ok=True)
     n = args.n
@@ -64,7 +66,8 @@ def main():
           f"({100.0 * relaxed / (tiles * max(st['n_rounds'], 1)):.1f} % of tiles x rounds), scratch {st['scratch_bytes'] / 2 ** 20:.0f} MiB")
     e = hsk.synth_room_extents(0).astype(np.float64)
     cell = 3.0 / n
-    lo, hi = max(0, int(np.floor((e[3] - 1.8) / cell))), min(n, int(np.ceil((e[3] - 0.1) / cell)))
+    floor_y = estimated_floor(house, e[3]) if args.estimate_floor else e[3]
+    lo, hi = max(0, int(np.floor((floor_y - 1.8) / cell))), min(n, int(np.ceil((floor_y - 0.1) / cell)))
     fmap, fst = house.reach_floor(1, lo, hi, seed, walk, rp)
     m = hsk.reach_metres(par, fmap)
     top = max(float(np.nanmax(m)) if np.isfinite(m).any() else 1.0, 1e-6)
