@@ -20,6 +20,7 @@
 // accumulators.
 #pragma clang fp contract(off)
 #include "hsk_dev.h"
+#include "hsk_cloud_dev.h"
 #include "hsk_launch.h"
 #include "hsk_align_point.h"
 
@@ -31,14 +32,9 @@ __global__ __launch_bounds__(256) void k_align_iter(const unsigned* __restrict__
 #pragma unroll
   for (int k = 0; k < 28; ++k) acc[k] = 0.0;
   unsigned n_used = 0;
-  const float* __restrict__ sx = soa;
-  const float* __restrict__ sy = soa + aa.pitch;
-  const float* __restrict__ sz = soa + 2u * (size_t)aa.pitch;
-  const float* __restrict__ snx = soa + 3u * (size_t)aa.pitch;
-  const float* __restrict__ sny = soa + 4u * (size_t)aa.pitch;
-  const float* __restrict__ snz = soa + 5u * (size_t)aa.pitch;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < aa.n; i += n_threads) {
-    if (align_point(vol, dv, aa, sx[i], sy[i], sz[i], snx[i], sny[i], snz[i], acc)) n_used += 1;
+    const CloudPoint q = hsk_cloud_point(soa, i, aa.pitch);
+    if (align_point(vol, dv, aa, q.x, q.y, q.z, q.nx, q.ny, q.nz, acc)) n_used += 1;
   }
   // a lane's sums are integers below 2^53; over the wave and over the launch they are added as 64-bit integers
   long long mine = 0;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "hsk_ctx.h"
+#include "hsk_plane_point.h"
 
 #define HSK_ALIGN_MAX_POINTS (1u << 20)
 #define HSK_ALIGN_REACH_M 8.0  // half the box's diagonal, and (probes + 1) tau: what keeps the sums exact
@@ -93,12 +94,11 @@ int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params
   return require_idle(dst);
 }
 
-// The scratch of a cloud of np points (hsk_ctx.h: d_align, made on first use and only grown): the accumulators, the cloud's six
-// planes `*pitch` floats apart, then `extra` bytes for the caller (256-byte aligned).
-int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra) {
+// hsk_ctx.h: CloudScratch
+int align_scratch(hsk_ctx* k, size_t np, size_t extra, CloudScratch* s) {
   const size_t acc_bytes = (size_t)HSK_ALIGN_ACC_WORDS * 8;
-  *pitch = (unsigned)((np + 63) & ~(size_t)63);
-  const size_t planes = (((size_t)*pitch * 6 * 4) + 255) & ~(size_t)255;
+  s->pitch = (unsigned)((np + 63) & ~(size_t)63);
+  const size_t planes = (((size_t)s->pitch * 6 * 4) + 255) & ~(size_t)255;
   const size_t want = acc_bytes + planes + extra;
   if (!k->h_align) HIPCHK(k, hipHostMalloc((void**)&k->h_align, acc_bytes, hipHostMallocDefault));
   if (k->align_bytes < want) {
@@ -108,8 +108,42 @@ int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** 
     HIPCHK(k, hipMalloc(&k->d_align, want));
     k->align_bytes = want;
   }
-  *d_soa = (float*)((char*)k->d_align + acc_bytes);
-  if (d_extra) *d_extra = (char*)k->d_align + acc_bytes + planes;
+  s->soa = (float*)((char*)k->d_align + acc_bytes);
+  s->extra = (char*)k->d_align + acc_bytes + planes;
+  return HSK_OK;
+}
+
+int cloud_upload(hsk_ctx* k, const float* xyz, const float* normals, size_t n, size_t stride, const CloudScratch& s, size_t* n_invalid,
+                 const char* who) {
+  std::vector<float> soa;
+  try {
+    soa.resize((size_t)s.pitch * (normals ? 6 : 3));
+  } catch (const std::bad_alloc&) {
+    return fail(k, HSK_ERR_STATE, (std::string(who) + ": out of host memory for the cloud").c_str());
+  }
+  size_t bad = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const float* q = xyz + 3 * i * stride;
+    for (int c = 0; c < 3; ++c) soa[(size_t)c * s.pitch + i] = q[c];
+    if (!normals) continue;
+    const float* m = normals + 3 * i * stride;
+    for (int c = 0; c < 3; ++c) soa[(size_t)(3 + c) * s.pitch + i] = m[c];
+    if (n_invalid) bad += plane_point_valid(q[0], q[1], q[2], m[0], m[1], m[2]) ? 0 : 1;
+  }
+  if (n_invalid) *n_invalid = bad;
+  HIPCHK(k, hipMemcpyAsync(s.soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
+  return HSK_OK;
+}
+
+int cloud_from_volume(hsk_ctx* k, size_t n, size_t extra, CloudScratch* s) {
+  const float* d_xyz = nullptr;
+  const float* d_nrm = nullptr;
+  if (int rc = cloud_attrs_on_device(k, n, &d_xyz, &d_nrm)) return rc;
+  if (int rc = align_scratch(k, n, extra, s)) return rc;
+  // the cloud stays on the device: from the product buffer into the scratch's planes
+  launch_plane_gather(k->stream, d_xyz, d_nrm, (unsigned)n, s->pitch, s->soa);
+  HIPCHK(k, hipGetLastError());
   return HSK_OK;
 }
 
@@ -190,29 +224,12 @@ extern "C" int hsk_align_cloud(hsk_ctx* dst, const float* xyz, const float* norm
   if (stride > 0xffffffffull) return fail(k, HSK_ERR_ARG, "hsk_align_cloud: more points than a 32-bit stride over max_points covers");
   st.stride = (uint32_t)stride;
   st.n_points = (uint32_t)np;
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  if (int rc = align_scratch(k, np, 0, &pitch, &d_soa, nullptr)) return rc;
-  if (np > 0) {
-    std::vector<float> soa;
-    try {
-      soa.resize((size_t)pitch * 6);
-    } catch (const std::bad_alloc&) {
-      return fail(k, HSK_ERR_STATE, "hsk_align_cloud: out of host memory for the cloud");
-    }
-    for (size_t i = 0; i < np; ++i) {
-      const float* q = xyz + 3 * i * stride;
-      const float* m = normals + 3 * i * stride;
-      for (int c = 0; c < 3; ++c) {
-        soa[(size_t)c * pitch + i] = q[c];
-        soa[(size_t)(3 + c) * pitch + i] = m[c];
-      }
-    }
-    HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
-  }
+  CloudScratch cs;
+  if (int rc = align_scratch(k, np, 0, &cs)) return rc;
+  if (np > 0)
+    if (int rc = cloud_upload(k, xyz, normals, np, stride, cs, nullptr, "hsk_align_cloud")) return rc;
   float m[16];
-  if (int rc = align_run(k, p, d_soa, np, pitch, src_to_dst, m, &st)) return rc;
+  if (int rc = align_run(k, p, cs.soa, np, cs.pitch, src_to_dst, m, &st)) return rc;
   memcpy(out, m, sizeof(m));
   if (stats) *stats = st;
   return HSK_OK;

@@ -13,19 +13,18 @@
 static_assert(HSK_UPRIGHT_HIST_BINS == HSK_LEVEL_HIST_BINS && HSK_UPRIGHT_HEIGHT_BINS == HSK_LEVEL_H_BINS, "the public sizes are the kernels'");
 static_assert(sizeof(hsk_upright_params) == 36 && sizeof(hsk_upright) == 128, "the upright structs are 36 and 128 bytes");
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // what the estimate adds to the alignment's scratch behind the cloud's planes: the histogram (and the valid count), the blocks'
 // partial values, the 16 words they fold to, the height histograms' counts and sums
 struct LevelScratch {
   size_t hist_at, partial_at, sums_at, hcount_at, hsum_at, bytes;
   explicit LevelScratch(size_t n) {
-    hist_at = 0;
-    partial_at = hist_at + up256((HSK_LEVEL_HIST_BINS + 1) * 4);
-    sums_at = partial_at + up256((size_t)level_blocks((unsigned)n) * 16 * 8);
-    hcount_at = sums_at + 256;
-    hsum_at = hcount_at + up256((size_t)2 * HSK_LEVEL_H_BINS * 4);
-    bytes = hsum_at + up256((size_t)2 * HSK_LEVEL_H_BINS * 8);
+    ProductLayout L;
+    hist_at = L.take((HSK_LEVEL_HIST_BINS + 1) * 4);
+    partial_at = L.take((size_t)cloud_sweep_blocks((unsigned)n) * 16 * 8);
+    sums_at = L.take(16 * 8);
+    hcount_at = L.take((size_t)2 * HSK_LEVEL_H_BINS * 4);
+    hsum_at = L.take((size_t)2 * HSK_LEVEL_H_BINS * 8);
+    bytes = L.bytes;
   }
 };
 
@@ -65,24 +64,6 @@ static int weights_resolve(hsk_ctx* k, const float* cell_weights, LevelWeights* 
 static long long axis_len2(const int32_t a[3]) { return level_dot(a, a); }
 static bool axis_ok(const int32_t a[3]) { return axis_len2(a) > 0 && axis_len2(a) <= (long long)HSK_UPRIGHT_AXIS_MAX2; }
 
-// the caller's packed triples -> the scratch's six planes
-static int level_upload(hsk_ctx* k, const float* xyz, const float* normals, size_t n, unsigned pitch, float* d_soa, const char* who) {
-  std::vector<float> soa;
-  try {
-    soa.resize((size_t)pitch * 6);
-  } catch (const std::bad_alloc&) {
-    return fail(k, HSK_ERR_STATE, (std::string(who) + ": out of host memory for the cloud").c_str());
-  }
-  for (size_t i = 0; i < n; ++i)
-    for (int c = 0; c < 3; ++c) {
-      soa[(size_t)c * pitch + i] = xyz[3 * i + c];
-      soa[(size_t)(3 + c) * pitch + i] = normals[3 * i + c];
-    }
-  HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
-  return HSK_OK;
-}
-
 // level_estimate's three questions, answered by the kernels over the n > 0 points in the scratch's planes
 struct DeviceStages {
   hsk_ctx* k;
@@ -94,10 +75,10 @@ struct DeviceStages {
   unsigned long long *d_partial, *d_sums, *d_hsum;
   unsigned* d_hcount;
 
-  DeviceStages(hsk_ctx* k_, const float* soa, size_t n_, unsigned pitch_, void* d_extra, const LevelWeights& w_, float cone_cos, float wall_sin)
-      : k(k_), d_soa(soa), n((unsigned)n_), pitch(pitch_), w(w_) {
+  DeviceStages(hsk_ctx* k_, const CloudScratch& cs, size_t n_, const LevelWeights& w_, float cone_cos, float wall_sin)
+      : k(k_), d_soa(cs.soa), n((unsigned)n_), pitch(cs.pitch), w(w_) {
     const LevelScratch L(n_);
-    char* base = (char*)d_extra;
+    char* base = (char*)cs.extra;
     d_hist = (unsigned*)(base + L.hist_at);
     d_partial = (unsigned long long*)(base + L.partial_at);
     d_sums = (unsigned long long*)(base + L.sums_at);
@@ -165,8 +146,7 @@ struct DeviceStages {
 };
 
 // the estimate over the n > 0 points in the scratch's planes
-static int level_run(hsk_ctx* k, const float* d_soa, size_t n, unsigned pitch, void* d_extra, const LevelWeights& w, const hsk_upright_params& p,
-                     hsk_upright* out) {
+static int level_run(hsk_ctx* k, const CloudScratch& cs, size_t n, const LevelWeights& w, const hsk_upright_params& p, hsk_upright* out) {
   std::vector<uint32_t> hist, cnt;
   std::vector<int64_t> sum;
   try {
@@ -176,7 +156,7 @@ static int level_run(hsk_ctx* k, const float* d_soa, size_t n, unsigned pitch, v
   } catch (const std::bad_alloc&) {
     return fail(k, HSK_ERR_STATE, "upright estimate: out of host memory for the histograms");
   }
-  DeviceStages st(k, d_soa, n, pitch, d_extra, w, p.cone_cos, p.wall_sin);
+  DeviceStages st(k, cs, n, w, p.cone_cos, p.wall_sin);
   return level_estimate(st, (uint64_t)n, p, out, hist.data(), cnt.data(), sum.data());
 }
 
@@ -193,12 +173,10 @@ extern "C" int hsk_estimate_upright_oriented(hsk_ctx* k, const float* xyz, const
   level_clear(out, n);
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, LevelScratch(n).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  if (int rc = level_upload(k, xyz, normals, n, pitch, d_soa, "hsk_estimate_upright_oriented")) return rc;
-  return level_run(k, d_soa, n, pitch, d_extra, w, p, out);
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, LevelScratch(n).bytes, &cs)) return rc;
+  if (int rc = cloud_upload(k, xyz, normals, n, 1, cs, nullptr, "hsk_estimate_upright_oriented")) return rc;
+  return level_run(k, cs, n, w, p, out);
 }
 
 extern "C" int hsk_estimate_upright(hsk_ctx* k, const hsk_upright_params* params, hsk_upright* out) {
@@ -215,22 +193,14 @@ extern "C" int hsk_estimate_upright(hsk_ctx* k, const hsk_upright_params* params
   if (n > HSK_UPRIGHT_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_estimate_upright: the cloud has more than 2^24 points");
   level_clear(out, n);
   if (n == 0) return HSK_OK;
-  const float* d_xyz = nullptr;
-  const float* d_nrm = nullptr;
-  if (int rc = cloud_attrs_on_device(k, n, &d_xyz, &d_nrm)) return rc;
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, LevelScratch(n).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  // the cloud stays on the device: from the product buffer into the scratch's planes
-  launch_plane_gather(k->stream, d_xyz, d_nrm, (unsigned)n, pitch, d_soa);
-  HIPCHK(k, hipGetLastError());
+  CloudScratch cs;
+  if (int rc = cloud_from_volume(k, n, LevelScratch(n).bytes, &cs)) return rc;
   // the raycast's normals are differences over one cell per axis: w_k = c_min / c_k takes the cells' skew out
   float cmin = k->vp.cell[0];
   for (int c = 1; c < 3; ++c) cmin = k->vp.cell[c] < cmin ? k->vp.cell[c] : cmin;
   LevelWeights w;
   for (int c = 0; c < 3; ++c) w.w[c] = cmin / k->vp.cell[c];
-  return level_run(k, d_soa, n, pitch, d_extra, w, p, out);
+  return level_run(k, cs, n, w, p, out);
 }
 
 extern "C" int hsk_upright_sums(hsk_ctx* k, const float* xyz, const float* normals, size_t n, const float cell_weights[3], float cone_cos,
@@ -262,12 +232,10 @@ extern "C" int hsk_upright_sums(hsk_ctx* k, const float* xyz, const float* norma
   if (height_counts) memset(height_counts, 0, (size_t)2 * HSK_LEVEL_H_BINS * 4), memset(height_sums, 0, (size_t)2 * HSK_LEVEL_H_BINS * 8);
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, LevelScratch(n).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  if (int rc = level_upload(k, xyz, normals, n, pitch, d_soa, who)) return rc;
-  DeviceStages st(k, d_soa, n, pitch, d_extra, w, cone_cos, wall_sin);
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, LevelScratch(n).bytes, &cs)) return rc;
+  if (int rc = cloud_upload(k, xyz, normals, n, 1, cs, nullptr, who)) return rc;
+  DeviceStages st(k, cs, n, w, cone_cos, wall_sin);
   if (hist || n_valid) {
     std::vector<uint32_t> h(HSK_LEVEL_HIST_BINS);
     uint64_t nv = 0;

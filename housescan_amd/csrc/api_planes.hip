@@ -12,21 +12,20 @@
 
 static_assert(HSK_PLANE_MAX_HYPOTHESES == HSK_PLANE_MAX_HYP, "the public limit of hypotheses is the size of k_plane_score's table in LDS");
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // what plane detection adds to the alignment's scratch behind the cloud's planes: the labels, the seed points, the hypotheses
 // (4 floats each), their counts, the score blocks' tables, the sweep blocks' sums (16 words each) and the 16 words they add up to
 struct PlaneScratch {
   size_t labels_at, seeds_at, hyp_at, counts_at, tables_at, partial_at, sums_at, bytes;
   PlaneScratch(size_t n, size_t n_hyp) {
-    labels_at = 0;
-    seeds_at = labels_at + up256(n * 4);
-    hyp_at = seeds_at + up256(n_hyp * 4);
-    counts_at = hyp_at + up256(n_hyp * 16);
-    tables_at = counts_at + up256(n_hyp * 4);
-    partial_at = tables_at + up256((size_t)plane_score_blocks((unsigned)n) * n_hyp * 4);
-    sums_at = partial_at + up256((size_t)plane_sweep_blocks((unsigned)n) * 16 * 8);
-    bytes = sums_at + 256;
+    ProductLayout L;
+    labels_at = L.take(n * 4);
+    seeds_at = L.take(n_hyp * 4);
+    hyp_at = L.take(n_hyp * 16);
+    counts_at = L.take(n_hyp * 4);
+    tables_at = L.take((size_t)plane_score_blocks((unsigned)n) * n_hyp * 4);
+    partial_at = L.take((size_t)cloud_sweep_blocks((unsigned)n) * 16 * 8);
+    sums_at = L.take(16 * 8);
+    bytes = L.bytes;
   }
 };
 
@@ -55,37 +54,14 @@ static int plane_resolve(hsk_ctx* k, const hsk_plane_params* params, hsk_plane_p
   return ok ? HSK_OK : fail(k, HSK_ERR_ARG, (std::string(who) + ": a parameter is outside its range").c_str());
 }
 
-// the caller's packed triples -> the scratch's six planes; *n_invalid (may be null): the invalid points
-static int upload_cloud(hsk_ctx* k, const float* xyz, const float* normals, size_t n, unsigned pitch, float* d_soa, size_t* n_invalid,
-                        const char* who) {
-  std::vector<float> soa;
-  try {
-    soa.resize((size_t)pitch * 6);
-  } catch (const std::bad_alloc&) {
-    return fail(k, HSK_ERR_STATE, (std::string(who) + ": out of host memory for the cloud").c_str());
-  }
-  size_t bad = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const float* q = xyz + 3 * i;
-    const float* m = normals + 3 * i;
-    for (int c = 0; c < 3; ++c) {
-      soa[(size_t)c * pitch + i] = q[c];
-      soa[(size_t)(3 + c) * pitch + i] = m[c];
-    }
-    bad += plane_point_valid(q[0], q[1], q[2], m[0], m[1], m[2]) ? 0 : 1;
-  }
-  if (n_invalid) *n_invalid = bad;
-  HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
-  return HSK_OK;
-}
-
 // The rounds over the n > 0 points in the scratch's planes: planes[0 .. *n_planes), and the labels (host, may be null).
-static int plane_rounds(hsk_ctx* k, const float* d_soa, size_t n, unsigned pitch, void* d_extra, const hsk_plane_params& p,
-                        hsk_plane_record* planes, size_t* n_planes, int32_t* labels) {
+static int plane_rounds(hsk_ctx* k, const CloudScratch& cs, size_t n, const hsk_plane_params& p, hsk_plane_record* planes, size_t* n_planes,
+                        int32_t* labels) {
   const size_t H = (size_t)p.n_hypotheses;
   const PlaneScratch L(n, H);
-  char* base = (char*)d_extra;
+  const float* d_soa = cs.soa;
+  const unsigned pitch = cs.pitch;
+  char* base = (char*)cs.extra;
   int* d_labels = (int*)(base + L.labels_at);
   unsigned* d_seeds = (unsigned*)(base + L.seeds_at);
   float* d_hyp = (float*)(base + L.hyp_at);
@@ -175,12 +151,10 @@ extern "C" int hsk_detect_planes_oriented(hsk_ctx* k, const float* xyz, const fl
   if (n_invalid) *n_invalid = 0;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, PlaneScratch(n, (size_t)p.n_hypotheses).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  if (int rc = upload_cloud(k, xyz, normals, n, pitch, d_soa, n_invalid, "hsk_detect_planes_oriented")) return rc;
-  return plane_rounds(k, d_soa, n, pitch, d_extra, p, planes, n_planes, labels);
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, PlaneScratch(n, (size_t)p.n_hypotheses).bytes, &cs)) return rc;
+  if (int rc = cloud_upload(k, xyz, normals, n, 1, cs, n_invalid, "hsk_detect_planes_oriented")) return rc;
+  return plane_rounds(k, cs, n, p, planes, n_planes, labels);
 }
 
 extern "C" int hsk_detect_planes_volume(hsk_ctx* k, const hsk_plane_params* params, hsk_plane_record* planes, size_t cap, size_t* n_planes,
@@ -196,8 +170,6 @@ extern "C" int hsk_detect_planes_volume(hsk_ctx* k, const hsk_plane_params* para
   if (int ri = require_idle(k)) return ri;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   size_t n = 0;
-  const float* d_xyz = nullptr;
-  const float* d_nrm = nullptr;
   // the count pass alone says how many points there are: every refusal comes before the cloud is written
   if (int rc = cloud_count(k, &n)) return rc;
   *n_points = n;
@@ -206,15 +178,9 @@ extern "C" int hsk_detect_planes_volume(hsk_ctx* k, const hsk_plane_params* para
   if (n > HSK_PLANE_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_detect_planes_volume: the cloud has more than 2^24 points");
   if (labels && cap_labels < n) return fail(k, HSK_ERR_ARG, "hsk_detect_planes_volume: cap_labels is below the cloud's points");
   if (n == 0) return HSK_OK;
-  if (int rc = cloud_attrs_on_device(k, n, &d_xyz, &d_nrm)) return rc;
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, PlaneScratch(n, (size_t)p.n_hypotheses).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  // the cloud stays on the device: from the product buffer into the scratch's planes
-  launch_plane_gather(k->stream, d_xyz, d_nrm, (unsigned)n, pitch, d_soa);
-  HIPCHK(k, hipGetLastError());
-  return plane_rounds(k, d_soa, n, pitch, d_extra, p, planes, n_planes, labels);
+  CloudScratch cs;
+  if (int rc = cloud_from_volume(k, n, PlaneScratch(n, (size_t)p.n_hypotheses).bytes, &cs)) return rc;
+  return plane_rounds(k, cs, n, p, planes, n_planes, labels);
 }
 
 extern "C" int hsk_score_planes(hsk_ctx* k, const float* xyz, const float* normals, const int32_t* labels, size_t n, const float* planes_abcd,
@@ -232,18 +198,16 @@ extern "C" int hsk_score_planes(hsk_ctx* k, const float* xyz, const float* norma
   }
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   const PlaneScratch L(n, n_planes);
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, L.bytes, &pitch, &d_soa, &d_extra)) return rc;
-  if (int rc = upload_cloud(k, xyz, normals, n, pitch, d_soa, nullptr, "hsk_score_planes")) return rc;
-  char* base = (char*)d_extra;
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, L.bytes, &cs)) return rc;
+  if (int rc = cloud_upload(k, xyz, normals, n, 1, cs, nullptr, "hsk_score_planes")) return rc;
+  char* base = (char*)cs.extra;
   int* d_labels = (int*)(base + L.labels_at);
   float* d_hyp = (float*)(base + L.hyp_at);
   unsigned* d_counts = (unsigned*)(base + L.counts_at);
   if (labels) HIPCHK(k, hipMemcpyAsync(d_labels, labels, n * 4, hipMemcpyHostToDevice, k->stream));
   HIPCHK(k, hipMemcpyAsync(d_hyp, planes_abcd, n_planes * 16, hipMemcpyHostToDevice, k->stream));
-  launch_plane_score(k->stream, d_soa, labels ? d_labels : nullptr, d_hyp, (unsigned)n, pitch, (unsigned)n_planes, dist_m, cos_min,
+  launch_plane_score(k->stream, cs.soa, labels ? d_labels : nullptr, d_hyp, (unsigned)n, cs.pitch, (unsigned)n_planes, dist_m, cos_min,
                      (unsigned*)(base + L.tables_at), d_counts);
   HIPCHK(k, hipGetLastError());
   HIPCHK(k, hipMemcpyAsync(counts, d_counts, n_planes * 4, hipMemcpyDeviceToHost, k->stream));

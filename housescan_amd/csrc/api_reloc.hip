@@ -12,17 +12,16 @@
 #define HSK_RELOC_MAX_POINTS ((size_t)1 << 20)
 #define HSK_RELOC_MAX_POSES ((size_t)65536)
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // what scoring adds to the alignment's scratch behind the cloud's planes: the poses (12 floats each), the slabs' partial
 // values, the scores
 struct RelocScratch {
   size_t poses_at, partial_at, scores_at, bytes;
   RelocScratch(size_t n, size_t n_poses) {
-    poses_at = 0;
-    partial_at = poses_at + up256(n_poses * 12 * 4);
-    scores_at = partial_at + up256(n_poses * reloc_slabs((unsigned)n, (unsigned)n_poses) * 8 * 8);
-    bytes = scores_at + up256(n_poses * sizeof(hsk_pose_score));
+    ProductLayout L;
+    poses_at = L.take(n_poses * 12 * 4);
+    partial_at = L.take(n_poses * reloc_slabs((unsigned)n, (unsigned)n_poses) * 8 * 8);
+    scores_at = L.take(n_poses * sizeof(hsk_pose_score));
+    bytes = L.bytes;
   }
 };
 
@@ -36,12 +35,11 @@ int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who)
 }
 
 // the n points in the scratch's planes under the poses -> out (host).  n > 0, n_poses > 0.
-static int score_planes(hsk_ctx* k, const float* d_soa, size_t n, unsigned pitch, void* d_extra, const float* poses, size_t n_poses,
-                        hsk_pose_score* out) {
+static int score_planes(hsk_ctx* k, const CloudScratch& cs, size_t n, const float* poses, size_t n_poses, hsk_pose_score* out) {
   const RelocScratch L(n, n_poses);
-  float* d_poses = (float*)((char*)d_extra + L.poses_at);
-  unsigned long long* d_partial = (unsigned long long*)((char*)d_extra + L.partial_at);
-  hsk_pose_score* d_scores = (hsk_pose_score*)((char*)d_extra + L.scores_at);
+  float* d_poses = (float*)((char*)cs.extra + L.poses_at);
+  unsigned long long* d_partial = (unsigned long long*)((char*)cs.extra + L.partial_at);
+  hsk_pose_score* d_scores = (hsk_pose_score*)((char*)cs.extra + L.scores_at);
   std::vector<float> p12;
   try {
     p12.resize(n_poses * 12);
@@ -51,7 +49,7 @@ static int score_planes(hsk_ctx* k, const float* d_soa, size_t n, unsigned pitch
   for (size_t j = 0; j < n_poses; ++j) pose16_to_rt(poses + 16 * j, &p12[12 * j], &p12[12 * j + 9]);
   HIPCHK(k, hipMemcpyAsync(d_poses, p12.data(), p12.size() * 4, hipMemcpyHostToDevice, k->stream));
   flush_weights(k);  // the rule reads weights
-  launch_reloc_score(k->stream, k->d_vol, k->vp, d_soa, (unsigned)n, pitch, d_poses, (unsigned)n_poses, d_partial, d_scores);
+  launch_reloc_score(k->stream, k->d_vol, k->vp, cs.soa, (unsigned)n, cs.pitch, d_poses, (unsigned)n_poses, d_partial, d_scores);
   HIPCHK(k, hipGetLastError());
   HIPCHK(k, hipMemcpyAsync(out, d_scores, n_poses * sizeof(hsk_pose_score), hipMemcpyDeviceToHost, k->stream));
   HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
@@ -74,23 +72,10 @@ extern "C" int hsk_score_cloud(hsk_ctx* dst, const float* xyz, size_t n, const f
     return HSK_OK;
   }
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, RelocScratch(n, n_poses).bytes, &pitch, &d_soa, &d_extra)) return rc;
-  {
-    std::vector<float> soa;
-    try {
-      soa.resize((size_t)pitch * 3);
-    } catch (const std::bad_alloc&) {
-      return fail(k, HSK_ERR_STATE, "hsk_score_cloud: out of host memory for the cloud");
-    }
-    for (size_t i = 0; i < n; ++i)
-      for (int c = 0; c < 3; ++c) soa[(size_t)c * pitch + i] = xyz[3 * i + c];
-    HIPCHK(k, hipMemcpyAsync(d_soa, soa.data(), soa.size() * 4, hipMemcpyHostToDevice, k->stream));
-    HIPCHK(k, hipStreamSynchronize(k->stream));  // (the vector leaves with this scope)
-  }
-  return score_planes(k, d_soa, n, pitch, d_extra, poses, n_poses, out);
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, RelocScratch(n, n_poses).bytes, &cs)) return rc;
+  if (int rc = cloud_upload(k, xyz, nullptr, n, 1, cs, nullptr, "hsk_score_cloud")) return rc;
+  return score_planes(k, cs, n, poses, n_poses, out);
 }
 
 extern "C" int hsk_rank_scores(const hsk_pose_score* s, size_t n, uint32_t* order) {
@@ -190,12 +175,10 @@ extern "C" int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, c
     if (stats) *stats = st;
     return HSK_OK;
   }
-  unsigned pitch = 0;
-  float* d_soa = nullptr;
-  void* d_extra = nullptr;
-  if (int rc = align_scratch(k, n, RelocScratch(n, n_poses).bytes, &pitch, &d_soa, &d_extra)) return rc;
+  CloudScratch cs;
+  if (int rc = align_scratch(k, n, RelocScratch(n, n_poses).bytes, &cs)) return rc;
   // the cloud stays on the device: every pixel for the scores ...
-  launch_reloc_gather(k->stream, k->B().d_vcur[l], k->B().d_ncur[l], (unsigned)n, 1u, (unsigned)n, pitch, d_soa);
+  launch_reloc_gather(k->stream, k->B().d_vcur[l], k->B().d_ncur[l], (unsigned)n, 1u, (unsigned)n, cs.pitch, cs.soa);
   std::vector<hsk_pose_score> sc;
   std::vector<uint32_t> order;
   try {
@@ -204,7 +187,7 @@ extern "C" int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, c
   } catch (const std::bad_alloc&) {
     return fail(k, HSK_ERR_STATE, "hsk_relocalize: out of host memory for the scores");
   }
-  if (int rc = score_planes(k, d_soa, n, pitch, d_extra, poses, n_poses, sc.data())) return rc;
+  if (int rc = score_planes(k, cs, n, poses, n_poses, sc.data())) return rc;
   st.n_valid = (uint32_t)n - sc[0].n_skipped;
   if (st.n_valid == 0) {
     if (stats) *stats = st;
@@ -213,7 +196,7 @@ extern "C" int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, c
   (void)hsk_rank_scores(sc.data(), n_poses, order.data());
   // ... and, as hsk_align_cloud takes a cloud, every stride-th of them for the refinements
   const size_t stride = (n + ap.max_points - 1) / ap.max_points, np = (n + stride - 1) / stride;
-  if (stride > 1) launch_reloc_gather(k->stream, k->B().d_vcur[l], k->B().d_ncur[l], (unsigned)n, (unsigned)stride, (unsigned)np, pitch, d_soa);
+  if (stride > 1) launch_reloc_gather(k->stream, k->B().d_vcur[l], k->B().d_ncur[l], (unsigned)n, (unsigned)stride, (unsigned)np, cs.pitch, cs.soa);
   st.n_refined = (int32_t)std::min<size_t>((size_t)rp.n_refine, n_poses);
   st.status = HSK_RELOC_NONE;
   st.best = (int32_t)order[0];
@@ -225,7 +208,7 @@ extern "C" int hsk_relocalize(hsk_ctx* k, const uint16_t* depth, int w, int h, c
     hsk_align_stats as;
     memset(&as, 0, sizeof(as));
     float m[16];
-    if (int rc = align_run(k, ap, d_soa, np, pitch, cand, m, &as)) return rc;
+    if (int rc = align_run(k, ap, cs.soa, np, cs.pitch, cand, m, &as)) return rc;
     const int last = as.iterations - 1;
     st.candidate[r] = (int32_t)order[r];
     st.score[r] = sc[order[r]];

@@ -127,7 +127,6 @@ static __device__ __forceinline__ unsigned long long cz_unseen_column(const uint
 __global__ __launch_bounds__(256) void k_cover_census(const uint4* __restrict__ vol, CoverSweep g, unsigned n_threads, unsigned n_blocks,
                                                       unsigned long long* __restrict__ partial) {
   __shared__ unsigned long long s_u[256];
-  __shared__ unsigned s_sum[4][10];
   const unsigned tid = threadIdx.x;
   const long long ts = (long long)blockIdx.x * CZ_OWN + tid - 4;  // (a workgroup overlaps its neighbours by four threads at either end)
   const bool act = ts >= 0 && ts < (long long)n_threads;
@@ -243,12 +242,8 @@ __global__ __launch_bounds__(256) void k_cover_census(const uint4* __restrict__ 
   val[9] = (unsigned)__popcll(FB & n_zp);
 #pragma unroll
   for (int i = 0; i < 10; ++i) val[i] = hsk_wave_sum(val[i]);
-  if ((tid & 63u) == 0u) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) s_sum[tid >> 6][i] = val[i];
-  }
-  __syncthreads();
-  if (tid < 10u) partial[(size_t)tid * n_blocks + blockIdx.x] = (unsigned long long)((s_sum[0][tid] + s_sum[1][tid]) + (s_sum[2][tid] + s_sum[3][tid]));
+  const unsigned sum = hsk_block_meet<HskSum>(val);
+  if (tid < 10u) partial[(size_t)tid * n_blocks + blockIdx.x] = (unsigned long long)sum;
 }
 
 // workgroup v adds the workgroups' sums of value v (partial[v][n_blocks]) -> out[v]: hsk_coverage's words

@@ -152,14 +152,14 @@ struct hsk_ctx {
   // volume images (hsk_pack_volume / hsk_unpack_volume), made on first use: 64 B of counters, the two class tables, the two
   // size / offset tables and the scan's block sums (pack.hip); what the tables hold is the class and offset pass of the
   // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
-  // volume alignment (hsk_align_cloud), made on first use as a destination and only grown: the accumulators (align.hip:
-  // HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what pose scoring adds (api_reloc.hip: the poses, the slabs'
-  // partial values, the scores; api_planes.hip: the labels, the hypotheses, the blocks' sums; api_level.hip: the cube-map histogram, the blocks'
-  // partial values, the height histograms); h_align: the accumulators' pinned host side
+  void* d_pack = nullptr;
+  // the scratch of every call that works on a cloud (align_scratch -> CloudScratch), made on first use and only grown: the
+  // alignment's accumulators (align.hip: HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what the call carves for
+  // itself -- RelocScratch (api_reloc.hip), PlaneScratch (api_planes.hip) or LevelScratch (api_level.hip); h_align: the
+  // accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;
   unsigned long long* h_align = nullptr;
-  void* d_pack = nullptr;
   uint64_t pk_epoch = 0;
   bool pk_color = false;
   unsigned pk_counts[16] = {};
@@ -277,7 +277,22 @@ int volume_replaced(hsk_ctx* k);
 uint32_t plane_lcg_next(uint64_t* state);  // hsk_detect_planes' generator: one step, the state in place
 // ---- api_align.hip ----
 int align_check(hsk_ctx* dst, const float src_to_dst[16], const hsk_align_params* params, hsk_align_params* p, const char* who);
-int align_scratch(hsk_ctx* k, size_t np, size_t extra, unsigned* pitch, float** d_soa, void** d_extra);
+// The scratch of a cloud of np points (d_align): the accumulators, the cloud's six planes `pitch` floats apart at `soa`, then
+// `extra` bytes of the caller's at `extra` (256-byte aligned; a caller carves them with ProductLayout)
+struct CloudScratch {
+  unsigned pitch = 0;
+  float* soa = nullptr;
+  void* extra = nullptr;
+};
+int align_scratch(hsk_ctx* k, size_t np, size_t extra, CloudScratch* s);
+// The caller's packed triples, every stride-th of them -- n points in all --, into the scratch's planes: six, or, normals null, the
+// three of the positions.  *n_invalid (may be null; asks for normals): the points hsk_plane_point.h calls invalid.  HSK_ERR_STATE:
+// "<who>: out of host memory for the cloud".  Returns with the copy done.
+int cloud_upload(hsk_ctx* k, const float* xyz, const float* normals, size_t n, size_t stride, const CloudScratch& s, size_t* n_invalid,
+                 const char* who);
+// The volume's own cloud -- the n > 0 points cloud_count found -- in the planes of a scratch with `extra` bytes behind them: written
+// by the cloud's second pass and gathered on the device.  Enqueues only.
+int cloud_from_volume(hsk_ctx* k, size_t n, size_t extra, CloudScratch* s);
 int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t np, unsigned pitch, const float src_to_dst[16], float m_out[16],
               hsk_align_stats* st);
 // ---- api_reloc.hip ----

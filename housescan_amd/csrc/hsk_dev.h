@@ -206,21 +206,55 @@ static __device__ __forceinline__ void hsk_ring_report(const TrackState* st, con
   __hip_atomic_store(&dst->ring_mark, (n + 1u) | 0x80000000u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// the sum of an integer over the wave's 64 lanes, in every lane (an xor butterfly: every lane of the wave must arrive)
-template <class T>
-static __device__ __forceinline__ T hsk_wave_sum(T v) {
+// ---- integer folds: a word over the wave, a block's words over its waves ------------------------------------------------------
+// An operation is of(word, a, b): what word number `word` of a record makes of two values (integers: any order gives the same bits).
+struct HskSum {
+  template <class T>
+  static __device__ __forceinline__ T of(int, T a, T b) { return a + b; }
+};
+struct HskMin {
+  template <class T>
+  static __device__ __forceinline__ T of(int, T a, T b) { return b < a ? b : a; }
+};
+struct HskMax {
+  template <class T>
+  static __device__ __forceinline__ T of(int, T a, T b) { return b > a ? b : a; }
+};
+// a box: words 0..2 the smallest, the others the largest
+struct HskBox {
+  template <class T>
+  static __device__ __forceinline__ T of(int word, T a, T b) { return word < 3 ? HskMin::of(word, a, b) : HskMax::of(word, a, b); }
+};
+// word number `word` folded over the wave's 64 lanes, in every lane (an xor butterfly: every lane of the wave must arrive)
+template <class Op, class T>
+static __device__ __forceinline__ T hsk_wave_fold(T v, int word = 0) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  for (int o = 32; o > 0; o >>= 1) v = Op::of(word, v, __shfl_xor(v, o, 64));
   return v;
 }
-// the largest of an unsigned word over the wave's 64 lanes, in every lane (likewise)
-static __device__ __forceinline__ unsigned hsk_wave_max(unsigned v) {
+// the sum of an integer, the largest of an unsigned word
+template <class T>
+static __device__ __forceinline__ T hsk_wave_sum(T v) { return hsk_wave_fold<HskSum>(v); }
+static __device__ __forceinline__ unsigned hsk_wave_max(unsigned v) { return hsk_wave_fold<HskMax>(v); }
+// The block meet, for a block of 256 threads: each of its four waves holds its W words in its lane 0 (s); thread v < W returns the
+// block's word v, every other thread 0.  Every thread of the block arrives (a barrier); the caller stores the word where its
+// layout wants it.
+template <class Op, class T, int W>
+static __device__ __forceinline__ T hsk_block_meet(const T (&s)[W]) {
+  __shared__ T sh[4][W];
+  if ((threadIdx.x & 63u) == 0u) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u > v ? u : v;
+    for (int v = 0; v < W; ++v) sh[threadIdx.x >> 6][v] = s[v];
   }
-  return v;
+  __syncthreads();
+  T r = 0;
+  if (threadIdx.x < (unsigned)W) {
+    const int v = (int)threadIdx.x;
+    r = sh[0][v];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) r = Op::of(v, r, sh[k][v]);
+  }
+  return r;
 }
 
 // round-to-nearest-even with the +-1e6 range guard of the spec

@@ -253,16 +253,22 @@ void launch_part_box(hipStream_t s, const PartGeom& q, const PartBufs& b, unsign
 void launch_part_gather(hipStream_t s, const PartGeom& q, const PartBufs& b, unsigned n_kept, const VolParams& vp, const float* xyz, unsigned n, int radius,
                         unsigned* out);
 
+// A 256-point sweep over the n points of a cloud in the alignment's scratch (planes.hip's, level.hip's) runs cloud_sweep_blocks(n)
+// blocks, each of which leaves up to 16 integer words in partial[block][16]; launch_cloud_fold (planes.hip: k_cloud_fold) folds the
+// first n_words of the n_blocks rows into out -- their sums, or, box, signed words of which 0..2 are minima and the others maxima.
+#define HSK_CLOUD_MAX_BLOCKS 1024
+unsigned cloud_sweep_blocks(unsigned n);
+void launch_cloud_fold(hipStream_t s, const unsigned long long* partial, unsigned n_blocks, unsigned n_words, bool box, unsigned long long* out);
+
 // oriented plane detection (planes.hip) over the n points of the six planes at `soa` (`pitch` floats apart);
 // labels: n ints, < 0 = unlabelled (launch_plane_score alone takes null: every valid point is open).  Every sum is an integer.
 // seed: hyp[j] = the plane of point seeds[j] (< n), four NaNs when that point is invalid or labelled.  score: counts[j] = the
 // inliers of hyp[j], j < n_hyp <= HSK_PLANE_MAX_HYP; partial: plane_score_blocks(n) x n_hyp words.  moments: sums10 = the
 // inliers' count, sum of q (3), sum of q_a q_b (xx xy xz yy yz zz), q = rint(x 4096); label: the inliers get `index`, out2 = their
-// count and the sum of rint(|s| 65536); both with partial: plane_sweep_blocks(n) x 16 words.  Nothing is launched with n == 0.
+// count and the sum of rint(|s| 65536); both with partial: cloud_sweep_blocks(n) x 16 words.  Nothing is launched with n == 0.
 #define HSK_PLANE_MAX_HYP 4096
 #define HSK_PLANE_MAX_BLOCKS 1024
 unsigned plane_score_blocks(unsigned n);
-unsigned plane_sweep_blocks(unsigned n);
 void launch_plane_seed(hipStream_t s, const float* soa, const int* labels, const unsigned* seeds, unsigned n_hyp, unsigned pitch, float* hyp);
 void launch_plane_score(hipStream_t s, const float* soa, const int* labels, const float* hyp, unsigned n, unsigned pitch, unsigned n_hyp,
                         float dist_m, float cos_min, unsigned* partial, unsigned* counts);
@@ -278,10 +284,9 @@ void launch_plane_gather(hipStream_t s, const float* xyz, const float* normals, 
 // normals weighted by w.  Every sum is an integer.  hist: HSK_LEVEL_HIST_BINS counts and one more word, the valid points -- ZEROED by
 // the caller.  sums: sums15 = per axis a < n_axes the supporters' count and the three sums of sign(N . A) N (words 4 a ..), then --
 // wall set -- the wall points of W[0], their count and the two fourth-power sums against W[1], W[2] (words 12 ..); partial:
-// level_blocks(n) x 16 words.  extents: box6 = the min (3) then max (3) of P . R_k over the valid points as signed 64-bit words
+// cloud_sweep_blocks(n) x 16 words.  extents: box6 = the min (3) then max (3) of P . R_k over the valid points as signed 64-bit words
 // (INT32_MAX / INT32_MIN when there is none); classes set: the two height histograms, HSK_LEVEL_H_BINS bins a class, the floor class
 // first -- h_count, h_sum ZEROED by the caller.  Nothing is launched with n == 0.
-#define HSK_LEVEL_MAX_BLOCKS 1024
 struct LevelWeights {
   float w[3];
 };
@@ -297,7 +302,6 @@ struct LevelFrame {
   double cone2;
   int classes;
 };
-unsigned level_blocks(unsigned n);
 void launch_level_hist(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, unsigned* hist);
 void launch_level_sums(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, const LevelAxes& ax,
                        unsigned long long* partial, unsigned long long* sums15);

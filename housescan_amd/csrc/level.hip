@@ -10,20 +10,21 @@
 // atomics.
 // k_level_sums: for up to three integer axes the count of supporters and the three signed sums, and for one up axis the wall
 // points' count and their two fourth-power sums: 15 64-bit sums a lane, added over the wave by shuffles, over the block in LDS,
-// stored per block and added by k_level_fold.
-// k_level_extents: the min and max of the three levelled coordinates (per block, folded by k_level_fold) and the two height
+// stored per block and added by k_cloud_fold (planes.hip).
+// k_level_extents: the min and max of the three levelled coordinates (per block, folded by k_cloud_fold as a box) and the two height
 // histograms.  2 x 16384 bins of a count and a 64-bit sum do not fit LDS; they are global integer atomics, which only the
 // up-facing and down-facing points reach, and a wave's lanes of one bin -- a floor is a few bins thick -- send one add of their
 // count and one of their sum.
 #pragma clang fp contract(off)
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
+#include "hsk_cloud_dev.h"
 #include "hsk_launch.h"
 #include "hsk_level_point.h"
 
 static __device__ __forceinline__ LevelPoint level_load(const float* __restrict__ soa, unsigned i, unsigned pitch, const LevelWeights& w) {
-  return level_point(soa[i], soa[pitch + i], soa[2 * (size_t)pitch + i], soa[3 * (size_t)pitch + i], soa[4 * (size_t)pitch + i],
-                     soa[5 * (size_t)pitch + i], w.w[0], w.w[1], w.w[2]);
+  const CloudPoint q = hsk_cloud_point(soa, i, pitch);
+  return level_point(q.x, q.y, q.z, q.nx, q.ny, q.nz, w.w[0], w.w[1], w.w[2]);
 }
 
 // Every lane of the wave arrives.  The live lanes are grouped by `key`; each group's first lane gets *count = the group's size and
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void k_level_hist(const float* __restrict__ so
   for (unsigned r = 0; r < rounds; ++r) {
     const unsigned i = (r * gridDim.x + blockIdx.x) * 256u + threadIdx.x;  // (n <= 2^24: no wrap)
     const bool act = i < n;
-    const LevelPoint q = level_load(soa, act ? i : n - 1u, pitch, w);  // (a lane past the end reads the last point and counts nothing)
+    const LevelPoint q = level_load(soa, hsk_cloud_at(act, i, n), pitch, w);
     const bool live = act & q.valid;
     unsigned cnt;
     long long unused;
@@ -68,40 +69,11 @@ __global__ __launch_bounds__(256) void k_level_hist(const float* __restrict__ so
     if (acc[j] != 0u) atomicAdd(&hist[j], acc[j]);
 }
 
-// the block's n_words 64-bit values, a lane's each, into partial[block][16]: sums, or -- MINMAX -- words 0..2 minima and 3..5 maxima
-template <bool MINMAX, int n_words>
-static __device__ __forceinline__ void level_block_store(long long (&s)[16], unsigned long long* __restrict__ partial) {
-  __shared__ long long sh[4][16];
-#pragma unroll
-  for (int v = 0; v < n_words; ++v) {
-    if (MINMAX) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const long long u = __shfl_xor(s[v], o, 64);
-        s[v] = v < 3 ? (u < s[v] ? u : s[v]) : (u > s[v] ? u : s[v]);
-      }
-    } else {
-      s[v] = hsk_wave_sum(s[v]);
-    }
-  }
-  if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-    for (int v = 0; v < n_words; ++v) sh[threadIdx.x >> 6][v] = s[v];
-  }
-  __syncthreads();
-  if (threadIdx.x < (unsigned)n_words) {
-    const int v = (int)threadIdx.x;
-    long long r = sh[0][v];
-    for (int k = 1; k < 4; ++k) r = !MINMAX ? r + sh[k][v] : v < 3 ? (sh[k][v] < r ? sh[k][v] : r) : (sh[k][v] > r ? sh[k][v] : r);
-    partial[(size_t)blockIdx.x * 16u + threadIdx.x] = (unsigned long long)r;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_level_sums(const float* __restrict__ soa, unsigned n, unsigned pitch, LevelWeights w, LevelAxes ax,
                                                     unsigned long long* __restrict__ partial) {
-  long long s[16];
+  long long s[15];
 #pragma unroll
-  for (int v = 0; v < 16; ++v) s[v] = 0;
+  for (int v = 0; v < 15; ++v) s[v] = 0;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
     const LevelPoint q = level_load(soa, i, pitch, w);
 #pragma unroll
@@ -121,20 +93,20 @@ __global__ __launch_bounds__(256) void k_level_sums(const float* __restrict__ so
       s[13] += wall ? re : 0, s[14] += wall ? im : 0;
     }
   }
-  level_block_store<false, 15>(s, partial);
+  hsk_cloud_block_store<HskSum>(s, partial);
 }
 
 __global__ __launch_bounds__(256) void k_level_extents(const float* __restrict__ soa, unsigned n, unsigned pitch, LevelWeights w, LevelFrame fr,
                                                        unsigned long long* __restrict__ partial, unsigned* __restrict__ h_count,
                                                        unsigned long long* __restrict__ h_sum) {
-  long long s[16];
+  long long s[6];
 #pragma unroll
-  for (int v = 0; v < 16; ++v) s[v] = v < 3 ? 0x7fffffffll : -0x80000000ll;
+  for (int v = 0; v < 6; ++v) s[v] = v < 3 ? 0x7fffffffll : -0x80000000ll;
   const unsigned rounds = (n + gridDim.x * 256u - 1u) / (gridDim.x * 256u);  // (uniform: every lane of a wave takes every round)
   for (unsigned r = 0; r < rounds; ++r) {
     const unsigned i = (r * gridDim.x + blockIdx.x) * 256u + threadIdx.x;
     const bool act = i < n;
-    const LevelPoint q = level_load(soa, act ? i : n - 1u, pitch, w);
+    const LevelPoint q = level_load(soa, hsk_cloud_at(act, i, n), pitch, w);
     const bool live = act & q.valid;
     int t[3];
 #pragma unroll
@@ -155,56 +127,28 @@ __global__ __launch_bounds__(256) void k_level_extents(const float* __restrict__
       }
     }
   }
-  level_block_store<true, 6>(s, partial);
-}
-
-// out[v] = the blocks' partial[block][v] folded: a workgroup per value v, a lane every 256th block; minmax: v < 3 the smallest, else
-// the largest, of signed values; else their sum
-__global__ __launch_bounds__(256) void k_level_fold(const unsigned long long* __restrict__ partial, unsigned n_blocks, int minmax,
-                                                    unsigned long long* __restrict__ out) {
-  __shared__ long long sh[256];
-  const bool lo = minmax && blockIdx.x < 3u, hi = minmax && !lo;
-  long long v = lo ? 0x7fffffffll : hi ? -0x80000000ll : 0ll;
-  for (unsigned b = threadIdx.x; b < n_blocks; b += 256u) {
-    const long long u = (long long)partial[(size_t)b * 16u + blockIdx.x];
-    v = lo ? (u < v ? u : v) : hi ? (u > v ? u : v) : v + u;
-  }
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (unsigned o = 128u; o > 0u; o >>= 1) {
-    if (threadIdx.x < o) {
-      const long long u = sh[threadIdx.x + o], m = sh[threadIdx.x];
-      sh[threadIdx.x] = lo ? (u < m ? u : m) : hi ? (u > m ? u : m) : m + u;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0u) out[blockIdx.x] = (unsigned long long)sh[0];
-}
-
-unsigned level_blocks(unsigned n) {
-  const unsigned b = (n + 255u) / 256u;
-  return b < (unsigned)HSK_LEVEL_MAX_BLOCKS ? (b ? b : 1u) : (unsigned)HSK_LEVEL_MAX_BLOCKS;
+  hsk_cloud_block_store<HskBox>(s, partial);
 }
 
 void launch_level_hist(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, unsigned* hist) {
   if (n == 0) return;
-  hipLaunchKernelGGL(k_level_hist, dim3(level_blocks(n)), dim3(256), 0, s, soa, n, pitch, w, hist);
+  hipLaunchKernelGGL(k_level_hist, dim3(cloud_sweep_blocks(n)), dim3(256), 0, s, soa, n, pitch, w, hist);
 }
 
 void launch_level_sums(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, const LevelAxes& ax,
                        unsigned long long* partial, unsigned long long* sums15) {
   if (n == 0) return;
-  const unsigned nb = level_blocks(n);
+  const unsigned nb = cloud_sweep_blocks(n);
   hipLaunchKernelGGL(k_level_sums, dim3(nb), dim3(256), 0, s, soa, n, pitch, w, ax, partial);
-  hipLaunchKernelGGL(k_level_fold, dim3(15), dim3(256), 0, s, partial, nb, 0, sums15);
+  launch_cloud_fold(s, partial, nb, 15u, false, sums15);
 }
 
 void launch_level_extents(hipStream_t s, const float* soa, unsigned n, unsigned pitch, const LevelWeights& w, const LevelFrame& fr,
                           unsigned long long* partial, unsigned long long* box6, unsigned* h_count, unsigned long long* h_sum) {
   if (n == 0) return;
-  const unsigned nb = level_blocks(n);
+  const unsigned nb = cloud_sweep_blocks(n);
   hipLaunchKernelGGL(k_level_extents, dim3(nb), dim3(256), 0, s, soa, n, pitch, w, fr, partial, h_count, h_sum);
-  hipLaunchKernelGGL(k_level_fold, dim3(6), dim3(256), 0, s, partial, nb, 1, box6);
+  launch_cloud_fold(s, partial, nb, 6u, true, box6);
 }
 
 int level_warm() {

@@ -4,7 +4,7 @@
 //
 // The rule (tests/planes_twin.py restates it in numpy) is per point in hsk_plane_point.h.  Everything summed here
 // is an integer, so any order of addition gives the same bits and no result depends on the launch shape; the only atomics are
-// integer adds in a block's own LDS.  Every sum is stored per block and added by k_plane_sum / k_plane_count_sum.
+// integer adds in a block's own LDS.  Every sum is stored per block and added by k_cloud_fold / k_plane_count_sum.
 //
 // k_plane_seed: a lane per hypothesis -- its seed point's normal and d, or four NaNs (no inlier) when the point is invalid or
 // labelled.
@@ -17,9 +17,11 @@
 // k_plane_label: labels the inliers of one plane, counts them and adds rint(|s| 65536).
 // k_plane_unlabel: takes one plane's labels back (a refit that lost its support).
 // k_plane_gather: a cloud with normals as two arrays of packed triples -> the alignment's six planes.
+// k_cloud_fold: the blocks' partial[block][16] folded to 16 words, for every 256-point sweep over a cloud (level.hip's too).
 #pragma clang fp contract(off)
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
+#include "hsk_cloud_dev.h"
 #include "hsk_launch.h"
 #include "hsk_plane_point.h"
 
@@ -31,11 +33,10 @@ __global__ __launch_bounds__(256) void k_plane_seed(const float* __restrict__ so
   const unsigned j = blockIdx.x * 256u + threadIdx.x;
   if (j >= n_hyp) return;
   const unsigned i = seeds[j];  // (< n: the host's next() % n)
-  const float x = soa[i], y = soa[pitch + i], z = soa[2 * (size_t)pitch + i];
-  const float nx = soa[3 * (size_t)pitch + i], ny = soa[4 * (size_t)pitch + i], nz = soa[5 * (size_t)pitch + i];
+  const CloudPoint q = hsk_cloud_point(soa, i, pitch);
   float abcd[4];
-  plane_of_point(x, y, z, nx, ny, nz, abcd);
-  const bool open = plane_point_valid(x, y, z, nx, ny, nz) & (labels[i] < 0);
+  plane_of_point(q.x, q.y, q.z, q.nx, q.ny, q.nz, abcd);
+  const bool open = plane_point_valid(q.x, q.y, q.z, q.nx, q.ny, q.nz) & (labels[i] < 0);
   const float nan = __int_as_float(0x7fc00000);
 #pragma unroll
   for (int c = 0; c < 4; ++c) hyp[4 * (size_t)j + c] = open ? abcd[c] : nan;
@@ -49,18 +50,17 @@ __global__ __launch_bounds__(256) void k_plane_score(const float* __restrict__ s
   __syncthreads();
   const unsigned lane = threadIdx.x & 63u;
   for (unsigned base = blockIdx.x * PLANE_TILE; base < n; base += gridDim.x * PLANE_TILE) {  // (n <= 2^24, the grid <= 1024: no wrap)
-    float x[4], y[4], z[4], nx[4], ny[4], nz[4];
+    CloudPoint q[4];
     bool open[4];
     bool any = false;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const unsigned i = base + (unsigned)p * 256u + threadIdx.x;
       const bool act = i < n;
-      const unsigned at = act ? i : n - 1u;  // (n > 0 in this loop; a lane past the end reads the last point and counts nothing)
-      x[p] = soa[at], y[p] = soa[pitch + at], z[p] = soa[2 * (size_t)pitch + at];
-      nx[p] = soa[3 * (size_t)pitch + at], ny[p] = soa[4 * (size_t)pitch + at], nz[p] = soa[5 * (size_t)pitch + at];
+      const unsigned at = hsk_cloud_at(act, i, n);
+      q[p] = hsk_cloud_point(soa, at, pitch);
       const bool free_ = labels ? labels[at] < 0 : true;
-      open[p] = act & free_ & plane_point_valid(x[p], y[p], z[p], nx[p], ny[p], nz[p]);
+      open[p] = act & free_ & plane_point_valid(q[p].x, q[p].y, q[p].z, q[p].nx, q[p].ny, q[p].nz);
       any |= open[p];
     }
     if (__ballot(any) == 0ull) continue;  // (uniform over the wave; the barriers stand outside this loop)
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_plane_score(const float* __restrict__ s
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           float as;
-          cnt += (unsigned)__popcll(__ballot(plane_point_inlier(open[p], a, b, c, d, dist_m, cos_min, x[p], y[p], z[p], nx[p], ny[p], nz[p], as)));
+          cnt += (unsigned)__popcll(__ballot(plane_point_inlier(open[p], a, b, c, d, dist_m, cos_min, q[p].x, q[p].y, q[p].z, q[p].nx, q[p].ny, q[p].nz, as)));
         }
         mine = lane == jj ? cnt : mine;
       }
@@ -101,22 +101,6 @@ __global__ __launch_bounds__(256) void k_plane_count_sum(const unsigned* __restr
   if (w == 0u && j < n_hyp) counts[j] = (sh[0][lane] + sh[1][lane]) + (sh[2][lane] + sh[3][lane]);
 }
 
-// the block's `W` 64-bit sums (W <= 16), a lane's each, into partial[block][16]
-template <int W>
-static __device__ __forceinline__ void plane_block_store(long long (&s)[W], unsigned long long* __restrict__ partial) {
-  __shared__ long long sh[4][16];
-#pragma unroll
-  for (int v = 0; v < W; ++v) s[v] = hsk_wave_sum(s[v]);
-  if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-    for (int v = 0; v < W; ++v) sh[threadIdx.x >> 6][v] = s[v];
-  }
-  __syncthreads();
-  if (threadIdx.x < (unsigned)W)
-    partial[(size_t)blockIdx.x * 16u + threadIdx.x] =
-        (unsigned long long)((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]));
-}
-
 struct PlaneEq {
   float a, b, c, d;
 };
@@ -125,46 +109,50 @@ __global__ __launch_bounds__(256) void k_plane_moments(const float* __restrict__
                                                        unsigned pitch, float dist_m, float cos_min, unsigned long long* __restrict__ partial) {
   long long s[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-    const float x = soa[i], y = soa[pitch + i], z = soa[2 * (size_t)pitch + i];
-    const float nx = soa[3 * (size_t)pitch + i], ny = soa[4 * (size_t)pitch + i], nz = soa[5 * (size_t)pitch + i];
-    const bool open = plane_point_valid(x, y, z, nx, ny, nz) & (labels[i] < 0);
+    const CloudPoint q = hsk_cloud_point(soa, i, pitch);
+    const bool open = plane_point_valid(q.x, q.y, q.z, q.nx, q.ny, q.nz) & (labels[i] < 0);
     float as;
-    const bool inl = plane_point_inlier(open, e.a, e.b, e.c, e.d, dist_m, cos_min, x, y, z, nx, ny, nz, as);
-    const long long qx = plane_q(inl ? x : 0.0f), qy = plane_q(inl ? y : 0.0f), qz = plane_q(inl ? z : 0.0f);
+    const bool inl = plane_point_inlier(open, e.a, e.b, e.c, e.d, dist_m, cos_min, q.x, q.y, q.z, q.nx, q.ny, q.nz, as);
+    const long long qx = plane_q(inl ? q.x : 0.0f), qy = plane_q(inl ? q.y : 0.0f), qz = plane_q(inl ? q.z : 0.0f);
     s[0] += inl ? 1 : 0;
     s[1] += qx, s[2] += qy, s[3] += qz;
     s[4] += qx * qx, s[5] += qx * qy, s[6] += qx * qz;
     s[7] += qy * qy, s[8] += qy * qz, s[9] += qz * qz;
   }
-  plane_block_store<10>(s, partial);
+  hsk_cloud_block_store<HskSum>(s, partial);
 }
 
 __global__ __launch_bounds__(256) void k_plane_label(const float* __restrict__ soa, int* __restrict__ labels, PlaneEq e, int index, unsigned n,
                                                      unsigned pitch, float dist_m, float cos_min, unsigned long long* __restrict__ partial) {
   long long s[2] = {0, 0};
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-    const float x = soa[i], y = soa[pitch + i], z = soa[2 * (size_t)pitch + i];
-    const float nx = soa[3 * (size_t)pitch + i], ny = soa[4 * (size_t)pitch + i], nz = soa[5 * (size_t)pitch + i];
-    const bool open = plane_point_valid(x, y, z, nx, ny, nz) & (labels[i] < 0);
+    const CloudPoint q = hsk_cloud_point(soa, i, pitch);
+    const bool open = plane_point_valid(q.x, q.y, q.z, q.nx, q.ny, q.nz) & (labels[i] < 0);
     float as;
-    const bool inl = plane_point_inlier(open, e.a, e.b, e.c, e.d, dist_m, cos_min, x, y, z, nx, ny, nz, as);
+    const bool inl = plane_point_inlier(open, e.a, e.b, e.c, e.d, dist_m, cos_min, q.x, q.y, q.z, q.nx, q.ny, q.nz, as);
     if (inl) labels[i] = index;
     s[0] += inl ? 1 : 0;
     s[1] += (long long)plane_abs_q(inl ? as : 0.0f);
   }
-  plane_block_store<2>(s, partial);
+  hsk_cloud_block_store<HskSum>(s, partial);
 }
 
-// out[v] = the sum over the blocks of partial[block][v]: a workgroup per value v, a lane every 256th block
-__global__ __launch_bounds__(256) void k_plane_sum(const unsigned long long* __restrict__ partial, unsigned n_blocks,
-                                                   unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long sh[4];
-  unsigned long long v = 0ull;
-  for (unsigned b = threadIdx.x; b < n_blocks; b += 256u) v += partial[(size_t)b * 16u + blockIdx.x];
-  v = hsk_wave_sum(v);
-  if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0u) out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+// out[v] = the blocks' partial[block][v] folded: a workgroup per word v, a lane every 256th block.  box: the words are signed, v < 3
+// the smallest and the others the largest; else their sum.
+template <class Op>
+static __device__ __forceinline__ void cloud_fold(const unsigned long long* __restrict__ partial, unsigned n_blocks, long long from,
+                                                  unsigned long long* __restrict__ out) {
+  long long v[1] = {from};
+  for (unsigned b = threadIdx.x; b < n_blocks; b += 256u) v[0] = Op::of(0, v[0], (long long)partial[(size_t)b * 16u + blockIdx.x]);
+  v[0] = hsk_wave_fold<Op>(v[0]);
+  const long long r = hsk_block_meet<Op>(v);
+  if (threadIdx.x == 0u) out[blockIdx.x] = (unsigned long long)r;
+}
+__global__ __launch_bounds__(256) void k_cloud_fold(const unsigned long long* __restrict__ partial, unsigned n_blocks, int box,
+                                                    unsigned long long* __restrict__ out) {
+  if (!box) cloud_fold<HskSum>(partial, n_blocks, 0ll, out);  // (uniform over the block)
+  else if (blockIdx.x < 3u) cloud_fold<HskMin>(partial, n_blocks, 0x7fffffffll, out);
+  else cloud_fold<HskMax>(partial, n_blocks, -0x80000000ll, out);
 }
 
 __global__ __launch_bounds__(256) void k_plane_unlabel(int* __restrict__ labels, int index, unsigned n) {
@@ -187,9 +175,12 @@ unsigned plane_score_blocks(unsigned n) {
   const unsigned b = (n + PLANE_TILE - 1u) / PLANE_TILE;
   return b < (unsigned)HSK_PLANE_MAX_BLOCKS ? (b ? b : 1u) : (unsigned)HSK_PLANE_MAX_BLOCKS;
 }
-unsigned plane_sweep_blocks(unsigned n) {
+unsigned cloud_sweep_blocks(unsigned n) {
   const unsigned b = (n + 255u) / 256u;
-  return b < (unsigned)HSK_PLANE_MAX_BLOCKS ? (b ? b : 1u) : (unsigned)HSK_PLANE_MAX_BLOCKS;
+  return b < (unsigned)HSK_CLOUD_MAX_BLOCKS ? (b ? b : 1u) : (unsigned)HSK_CLOUD_MAX_BLOCKS;
+}
+void launch_cloud_fold(hipStream_t s, const unsigned long long* partial, unsigned n_blocks, unsigned n_words, bool box, unsigned long long* out) {
+  hipLaunchKernelGGL(k_cloud_fold, dim3(n_words), dim3(256), 0, s, partial, n_blocks, box ? 1 : 0, out);
 }
 
 void launch_plane_seed(hipStream_t s, const float* soa, const int* labels, const unsigned* seeds, unsigned n_hyp, unsigned pitch, float* hyp) {
@@ -208,19 +199,19 @@ void launch_plane_score(hipStream_t s, const float* soa, const int* labels, cons
 void launch_plane_moments(hipStream_t s, const float* soa, const int* labels, const float abcd[4], unsigned n, unsigned pitch, float dist_m,
                           float cos_min, unsigned long long* partial, unsigned long long* sums10) {
   if (n == 0) return;
-  const unsigned nb = plane_sweep_blocks(n);
+  const unsigned nb = cloud_sweep_blocks(n);
   const PlaneEq e = {abcd[0], abcd[1], abcd[2], abcd[3]};
   hipLaunchKernelGGL(k_plane_moments, dim3(nb), dim3(256), 0, s, soa, labels, e, n, pitch, dist_m, cos_min, partial);
-  hipLaunchKernelGGL(k_plane_sum, dim3(10), dim3(256), 0, s, partial, nb, sums10);
+  launch_cloud_fold(s, partial, nb, 10u, false, sums10);
 }
 
 void launch_plane_label(hipStream_t s, const float* soa, int* labels, const float abcd[4], int index, unsigned n, unsigned pitch, float dist_m,
                         float cos_min, unsigned long long* partial, unsigned long long* out2) {
   if (n == 0) return;
-  const unsigned nb = plane_sweep_blocks(n);
+  const unsigned nb = cloud_sweep_blocks(n);
   const PlaneEq e = {abcd[0], abcd[1], abcd[2], abcd[3]};
   hipLaunchKernelGGL(k_plane_label, dim3(nb), dim3(256), 0, s, soa, labels, e, index, n, pitch, dist_m, cos_min, partial);
-  hipLaunchKernelGGL(k_plane_sum, dim3(2), dim3(256), 0, s, partial, nb, out2);
+  launch_cloud_fold(s, partial, nb, 2u, false, out2);
 }
 
 void launch_plane_unlabel(hipStream_t s, int* labels, int index, unsigned n) {

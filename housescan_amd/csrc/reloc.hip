@@ -19,6 +19,7 @@
 #pragma clang fp contract(off)
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
+#include "hsk_cloud_dev.h"
 #include "hsk_launch.h"
 #include "hsk_reloc_point.h"
 
@@ -32,18 +33,15 @@ __global__ __launch_bounds__(256) void k_reloc_score(const unsigned* __restrict_
   for (int i = 0; i < 9; ++i) R[i] = P[i];
 #pragma unroll
   for (int i = 0; i < 3; ++i) t[i] = P[9 + i];
-  const float* __restrict__ sx = soa;
-  const float* __restrict__ sy = soa + pitch;
-  const float* __restrict__ sz = soa + 2u * (size_t)pitch;
   unsigned cnt[RELOC_SKIPPED] = {0u, 0u, 0u, 0u, 0u}, taken = 0u;  // the wave's (uniform)
   long long sum = 0;                                                 // the lane's
   const unsigned wave_off = threadIdx.x & ~63u;
   for (unsigned base = slab * 256u; base < n; base += n_slabs * 256u) {
     const unsigned i = base + threadIdx.x;
     const bool act = i < n;
-    const unsigned at = act ? i : n - 1u;  // (n > 0 in this loop; a lane past the end reads the last point and counts nothing)
+    const CloudPos p = hsk_cloud_pos(soa, hsk_cloud_at(act, i, n), pitch);
     unsigned q;
-    int cls = reloc_point(vol, dv, R, t, sx[at], sy[at], sz[at], q);
+    int cls = reloc_point(vol, dv, R, t, p.x, p.y, p.z, q);
     cls = act ? cls : -1;
     sum += act ? (long long)q : 0ll;
 #pragma unroll
@@ -52,23 +50,18 @@ __global__ __launch_bounds__(256) void k_reloc_score(const unsigned* __restrict_
     taken += wb < n ? (n - wb < 64u ? n - wb : 64u) : 0u;
   }
   sum = hsk_wave_sum(sum);
-  __shared__ unsigned long long sh[4][8];
-  if ((threadIdx.x & 63u) == 0u) {
-    unsigned long long* mine = sh[threadIdx.x >> 6];
-    unsigned rest = taken;
+  unsigned long long mine[8];  // the wave's eight words
+  unsigned rest = taken;
 #pragma unroll
-    for (int c = 0; c < RELOC_SKIPPED; ++c) {
-      mine[c] = cnt[c];
-      rest -= cnt[c];
-    }
-    mine[RELOC_SKIPPED] = rest;
-    mine[6] = (unsigned long long)sum;
-    mine[7] = 0ull;
+  for (int c = 0; c < RELOC_SKIPPED; ++c) {
+    mine[c] = cnt[c];
+    rest -= cnt[c];
   }
-  __syncthreads();
-  if (threadIdx.x < 8u)
-    partial[((size_t)pose * n_slabs + slab) * 8u + threadIdx.x] =
-        (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  mine[RELOC_SKIPPED] = rest;
+  mine[6] = (unsigned long long)sum;
+  mine[7] = 0ull;
+  const unsigned long long r = hsk_block_meet<HskSum>(mine);
+  if (threadIdx.x < 8u) partial[((size_t)pose * n_slabs + slab) * 8u + threadIdx.x] = r;
 }
 
 __global__ __launch_bounds__(256) void k_reloc_sum(const unsigned long long* __restrict__ partial, unsigned n_poses, unsigned n_slabs,

@@ -44,10 +44,11 @@ def state_of(t):
 
 
 # ---- 1. the device stages against the twin ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 70001])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 70001, 262209])
 def test_upright_sums_match_the_twin(hsk, trk, n):
-    """a partial wave, a whole one, one lane more, more than a block, and 274 blocks with a partial last one; the clouds are the
-    tilted scene's repeated with jitter behind the edge cases; the axes are integers, so no float decides an inlier: zero differences"""
+    """a partial wave, a whole one, one lane more, more than a block, 274 blocks with a partial last one, and the grid's cap of 1024
+    blocks with a second trip of one block's partial wave (1024 x 256 + 65); the clouds are the tilted scene's repeated with
+    jitter behind the edge cases; the axes are integers, so no float decides an inlier: zero differences"""
     ps, ns = jittered(n)
     assert len(ps) == n
     w = LT.cell_weights(*LT.SCENES["80x64x48"])

@@ -9,6 +9,7 @@ import pytest
 
 import planes_twin as PT
 from test_align_host import same_bits
+from test_level_host import jittered
 from test_planes_host import COS_MIN, DIST_M, assert_scene_bar, odd_cloud, scene_cloud, score_planes_for_tests, twin_scene, twin_wall
 
 pytestmark = pytest.mark.gpu
@@ -132,6 +133,18 @@ def test_detect_planes_cloud_splits_the_thin_wall(hsk, trk):
     assert_same_result((rec, labels), (ref_rec, ref_labels), "the thin wall")
     for k in range(3):
         assert len(np.unique(face[labels == k])) == 1 and (labels == k).sum() == 22500
+
+
+def test_detect_planes_cloud_on_a_sweeps_second_trip(hsk, trk):
+    """1024 x 256 + 65 points: the moments' and the labels' sweeps run the grid's cap of 1024 blocks, and block 0 takes a second
+    trip of one partial wave; the score kernel's 257th tile is partial in its first row; every field and every label"""
+    ps, ns = jittered(262209)
+    over = dict(n_hypotheses=8, max_planes=2, refits=1)
+    ref = PT.detect(ps, ns, **over)
+    assert len(ref[0]) == 2 and ref[2] > 0, (ref[0], ref[2])          # (the case cannot go empty silently)
+    got = trk.detect_planes_cloud(ps, ns, **over)
+    assert got[2] == ref[2]
+    assert_same_result(got[:2], ref[:2], "262209 points")
 
 
 # ---- 8. hsk_detect_planes_volume ----------------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-LEVEL_KERNELS = ("k_level_hist", "k_level_sums", "k_level_extents", "k_level_fold", "k_plane_gather")
+LEVEL_KERNELS = ("k_level_hist", "k_level_sums", "k_level_extents", "k_cloud_fold", "k_plane_gather")
 CLOUD_KERNELS = ("k_extract_attrs",)
 
 

@@ -29,7 +29,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KERNELS = ("k_plane_seed", "k_plane_score", "k_plane_count_sum", "k_plane_moments", "k_plane_label", "k_plane_sum", "k_plane_unlabel",
+KERNELS = ("k_plane_seed", "k_plane_score", "k_plane_count_sum", "k_plane_moments", "k_plane_label", "k_cloud_fold", "k_plane_unlabel",
            "k_plane_gather", "k_extract_attrs")
 
 
