@@ -246,6 +246,7 @@ class HskViewScore(C.Structure):
 HSK_COMPONENT_NONE = 0xFFFFFFFF
 HSK_COMPONENT_MAX = 1 << 24
 HSK_PRUNE_UNSEEN, HSK_PRUNE_FREE = 0, 1
+HSK_FILL_SURFACE, HSK_FILL_ALL = 0, 1
 
 
 class HskComponent(C.Structure):
@@ -274,6 +275,19 @@ class HskPruneStats(C.Structure):
     """Mirror of `hsk_prune_stats` (include/hskinfu.h): 32 bytes."""
 
     _fields_ = [("n_components", C.c_uint64), ("n_pruned", C.c_uint64), ("n_pruned_voxels", C.c_uint64), ("n_kept_voxels", C.c_uint64)]
+
+
+class HskFillParams(C.Structure):
+    """Mirror of `hsk_fill_params` (include/hskinfu.h): 16 bytes."""
+
+    _fields_ = [("iterations", C.c_int32), ("keep", C.c_int32), ("band", C.c_int32), ("fill_weight", C.c_int32)]
+
+
+class HskFillStats(C.Structure):
+    """Mirror of `hsk_fill_stats` (include/hskinfu.h): 48 bytes."""
+
+    _fields_ = [("n_unseen", C.c_uint64), ("n_reached", C.c_uint64), ("n_written", C.c_uint64), ("n_written_negative", C.c_uint64),
+                ("tile_visits", C.c_uint64), ("iterations_run", C.c_int32), ("pad", C.c_int32)]
 
 
 HSK_CLEAR_UNKNOWN = 1
@@ -490,6 +504,9 @@ SYMBOLS = {
     "hsk_label_components": (C.c_int, [_P, C.POINTER(HskComponent), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskComponentStats)]),
     "hsk_download_components": (C.c_int, [_P, _P]),
     "hsk_prune_components": (C.c_int, [_P, C.POINTER(HskPruneParams), C.POINTER(HskPruneStats)]),
+    "hsk_default_fill_params": (None, [_P, C.POINTER(HskFillParams)]),
+    "hsk_fill_holes": (C.c_int, [_P, C.POINTER(HskFillParams), C.POINTER(HskVoxelBox), C.POINTER(HskFillStats)]),
+    "hsk_download_fill_mask": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P]),
     "hsk_default_clearance_params": (None, [_P, C.POINTER(HskClearanceParams)]),
     "hsk_clearance_d2": (C.c_uint32, [C.POINTER(HskClearanceParams), C.c_float]),
     "hsk_build_clearance": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskClearanceStats)]),

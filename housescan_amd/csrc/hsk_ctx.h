@@ -175,6 +175,13 @@ struct hsk_ctx {
   uint64_t comp_epoch = 0;
   uint64_t comp_inside = 0;  // the voxels of all components
   std::vector<hsk_component> comp_recs;
+  // hole filling (hsk_fill_holes; fill.hip), made by the first call that fills and only grown: d_fill = fill_layout's counters,
+  // tile bytes and two state buffers.  What it holds is the mask of the last fill, at fill_mask, valid while vol_epoch is
+  // fill_epoch (0: nothing)
+  void* d_fill = nullptr;
+  size_t fill_bytes = 0;
+  uint64_t fill_epoch = 0;
+  const unsigned char* fill_mask = nullptr;
   // the clearance field (hsk_build_clearance; clearance.hip), made by the first call that builds and freed by
   // hsk_release_clearance: d_clear = clear_layout's counters, field and intermediates.  What it holds is the field of the volume
   // at clear_epoch (0: nothing) for the 20 device-relevant parameter bytes in clear_key, and clear_counts its counters

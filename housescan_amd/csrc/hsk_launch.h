@@ -399,3 +399,34 @@ void launch_simp_write(hipStream_t s, const void* vol, const unsigned* colv, con
                        const unsigned* tri_count, const MeshIndexBufs& mb, const SimpBufs& sb, unsigned n_out, unsigned* list, long long* sums,
                        int mode, double floor_rel, float* xyz, float* normals, unsigned char* rgb, int* faces);
 int simplify_warm();
+
+// hole filling (fill.hip) of a WHOLE volume.  The scratch, carved out of one device buffer by fill_layout:
+// two state buffers of one int16 per volume word, a voxel's at the voxel's own place (hsk_vox_index) -- together as large as the
+// volume --, and per 16 x 16 x 8 tile 256 bytes of FREE bits and three bytes.  Iteration `it` (1-based) reads state[(it - 1) & 1]
+// and writes state[it & 1]; with `fin` the buffer of the final states, the other one holds row-major bytes: the mask in its first
+// half, the keep rule's bytes in its second.
+#define FILL_COUNTS 16   // counts[0] n_unseen, [1] n_reached, [2] n_written, [3] n_written_negative, [4] tile visits; behind
+                         // them 256 words: [it] the states iteration `it` changed
+struct FillBufs {
+  unsigned* counts;
+  unsigned char* tile_free;  // a byte per thread of a tile's workgroup: its eight voxels' FREE bits
+  unsigned char* cand;       // a byte per tile: it holds a FREE voxel
+  unsigned char* flag[2];    // a byte per tile: its states changed in the iteration that wrote this buffer
+  short* state[2];
+  unsigned n_tiles;
+};
+size_t fill_layout(const VolParams& vp, void* base /* null: the size only */, FillBufs* b);
+inline unsigned char* fill_mask_bytes(const VolParams& vp, const FillBufs& b, int fin) { return (unsigned char*)b.state[fin ^ 1]; }
+inline unsigned char* fill_keep_bytes(const VolParams& vp, const FillBufs& b, int fin) { return (unsigned char*)b.state[fin ^ 1] + hsk_vol_words(vp); }
+// the states, bits and bytes of the volume as it stands for the box lo <= (x, y, z) < hi; the counters zeroed, counts[0] set
+void launch_fill_init(hipStream_t s, const void* vol, const VolParams& vp, const int lo[3], const int hi[3], const FillBufs& b);
+void launch_fill_round(hipStream_t s, const VolParams& vp, const FillBufs& b, int it);
+// HSK_FILL_SURFACE's bytes from the final states: within Chebyshev distance `band` of a crossing voxel
+void launch_fill_keep(hipStream_t s, const VolParams& vp, const FillBufs& b, int fin, int band);
+// the mask and counts[1 .. 3]; keep_all: HSK_FILL_ALL (launch_fill_keep's bytes are not read)
+void launch_fill_count(hipStream_t s, const void* vol, const VolParams& vp, const int lo[3], const int hi[3], const FillBufs& b, int fin, bool keep_all);
+// the masked voxels' words: (fill_weight << 16) | (value & 0xffff)
+void launch_fill_commit(hipStream_t s, void* vol, const VolParams& vp, const FillBufs& b, int fin, int fill_weight);
+// out[n] = the mask's bytes over the box, row-major
+void launch_fill_mask_box(hipStream_t s, const unsigned char* mask, const VolParams& vp, const int lo[3], const int hi[3], size_t n, unsigned char* out);
+int fill_warm();      // loads fill.hip's code object (hsk_prepare_readout); a hipError_t

@@ -104,6 +104,24 @@ def default_prune_params(tracker=None, **fields):
     return p
 
 
+FILL_SURFACE, FILL_ALL = 0, 1
+FILL_FIELDS = ("iterations", "keep", "band", "fill_weight")
+
+
+def default_fill_params(tracker=None, **fields):
+    """the parameters of fill_holes (hsk_default_fill_params): iterations = the voxels of 15 cm along the tracker's finest axis
+    (without a tracker: the default configuration's), clamped to 1..255 -- gaps up to about 30 cm across close --, keep
+    FILL_SURFACE, band 2, fill_weight 1; the keywords -- iterations, keep, band, fill_weight -- override its fields -> an
+    `_lib.HskFillParams`"""
+    p = _lib.HskFillParams()
+    _lib.load().hsk_default_fill_params(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in FILL_FIELDS:
+            raise TypeError(f"fill parameters have no field {name!r}")
+        setattr(p, name, val)
+    return p
+
+
 CLEAR_UNKNOWN = 1
 CLEARANCE_FAR, CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
 CLEARANCE_FIELDS = ("weight", "max_d2", "flags", "unit_m")
@@ -870,6 +888,47 @@ class KinfuTracker:
         self._ck(self.lib.hsk_prune_components(self.h, C.byref(p), C.byref(st)))
         return {"n_components": int(st.n_components), "n_pruned": int(st.n_pruned), "n_pruned_voxels": int(st.n_pruned_voxels),
                 "n_kept_voxels": int(st.n_kept_voxels)}
+
+    # ---- hole filling ------------------------------------------------------------------------------------
+    def default_fill_params(self, **fields):
+        return default_fill_params(self, **fields)
+
+    def _voxel_box(self, box):
+        if box is None:
+            return None
+        b = _lib.HskVoxelBox()
+        b.lo[:] = [int(v) for v in box[0]]
+        b.hi[:] = [int(v) for v in box[1]]
+        return b
+
+    def fill_holes(self, params=None, box=None, **fields):
+        """closes the volume's gaps by volumetric diffusion (hsk_fill_holes): the signed distance of the observed voxels diffuses
+        for `iterations` Jacobi steps into the never-observed voxels of box = (lo, hi) (None: the whole volume); of the voxels
+        reached, those within Chebyshev distance `band` of a zero crossing (keep = FILL_SURFACE, the default) or all of them
+        (FILL_ALL) are written with weight fill_weight; every other word, and the colour volume, stays bit for bit.  params: an
+        HskFillParams (default: default_fill_params(self)); the keywords override its fields -> dict: n_unseen, n_reached,
+        n_written, n_written_negative, tile_visits, iterations_run.  download_fill_mask tells which voxels were written.  Not with
+        frames in flight"""
+        p = default_fill_params(self) if params is None else _lib.HskFillParams.from_buffer_copy(params)
+        for name, val in fields.items():
+            if name not in FILL_FIELDS:
+                raise TypeError(f"fill parameters have no field {name!r}")
+            setattr(p, name, val)
+        b = self._voxel_box(box)
+        st = _lib.HskFillStats()
+        self._ck(self.lib.hsk_fill_holes(self.h, C.byref(p), C.byref(b) if b is not None else None, C.byref(st)))
+        return {"n_unseen": int(st.n_unseen), "n_reached": int(st.n_reached), "n_written": int(st.n_written),
+                "n_written_negative": int(st.n_written_negative), "tile_visits": int(st.tile_visits), "iterations_run": int(st.iterations_run)}
+
+    def download_fill_mask(self, box=None):
+        """which voxels the last fill_holes wrote (hsk_download_fill_mask) over the voxels lo <= (x, y, z) < hi of box = (lo, hi),
+        None: the whole volume -> [z, y, x] uint8, 1 written, 0 not; refused once the volume has changed since that fill"""
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        out = np.empty(shape, np.uint8)
+        b = self._voxel_box(box)
+        self._ck(self.lib.hsk_download_fill_mask(self.h, C.byref(b) if b is not None else None, out.ctypes.data if out.size else None))
+        return out
 
     # ---- clearance field ---------------------------------------------------------------------------------
     def default_clearance_params(self, **fields):

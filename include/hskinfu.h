@@ -898,6 +898,63 @@ int hsk_download_components(hsk_ctx* k, uint32_t* labels);
  * scan may go on.  stats may be NULL.  HSK_ERR_ARG: keep_largest outside 0..4096, an unknown fill. */
 int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, hsk_prune_stats* stats);
 
+/* ---- Hole filling: close a scan's gaps by volumetric diffusion, on the device (DESIGN.md 3.22 the kernels, 8p the rule;
+ * tests/fill_twin.py restates the rule in numpy; after Davis, Marschner, Garr and Levoy, "Filling holes in complex surfaces using
+ * volumetric diffusion", 3DPVT 2002).  The counterpart of hsk_prune_components: prune turns small observed blobs into "never
+ * observed", fill turns small never-observed gaps into surface.  All integers.
+ * STATES.  A voxel (z < vol_z) is a SOURCE iff its weight is non-zero; its value is its raw TSDF, a raw of -32768 counting as
+ * -32767 in every sum and test (the word itself is never rewritten).  Every other voxel starts UNKNOWN.  No flush of the deferred
+ * weights is needed to read (no deferred weight is 0 in the volume's own copy).
+ * ONE ITERATION is a Jacobi step: every new state comes from the previous iteration's states.  A source never changes; a
+ * non-source voxel outside the box never changes (it stays UNKNOWN).  For a non-source voxel v inside the box, K = the KNOWN
+ * voxels (sources and filled ones) among v itself and its six face neighbours inside the grid, n = |K|: n = 0, v stays UNKNOWN;
+ * otherwise v is FILLED with the value (2 U + n) div (2 n) - 32768, U the sum of value + 32768 over K -- the mean, half rounded
+ * up.  A filled voxel is computed again in every iteration: the field relaxes.  `iterations` of them run; iterations_run is the
+ * number of the first one that changed no state, or `iterations`.
+ * A CROSSING, on the final states, in hsk_extract_cloud's words: two face-adjacent KNOWN voxels, neither at 32767, one value > 0
+ * and the other < 0; both are crossing voxels (sources or filled ones, inside the box or outside it).
+ * KEEP.  HSK_FILL_SURFACE: a FILLED voxel is written iff a crossing voxel lies within Chebyshev distance `band` of it (2: the cells
+ * of the crossing and the neighbours a normal's central difference reads).  HSK_FILL_ALL: every FILLED voxel is written.  The
+ * diffusion front also runs `iterations` voxels into every wall's never-observed interior; those voxels make no crossing, carry
+ * no information, would bridge the two faces of a thin wall for hsk_label_components and bloat hsk_pack_volume: hence the default.
+ * A written voxel's word is (fill_weight << 16) | (value & 0xffff) -- with the default weight 1 the first real observation counts
+ * half.  Every other word of the volume and every word of the colour volume stays bit for bit (the deferred weights written
+ * back, as by hsk_prune_components).  When nothing is to be written nothing is written and cached passes stay valid.  The pose
+ * and the model maps are not touched: a scan may go on.
+ * KNOWN PROPERTY: where a scan simply ends (a frustum's edge) the surface is continued outward by up to `iterations` voxels, as
+ * Davis et al. describe; the box is the remedy.
+ * The scratch -- two int16 states per stored voxel, together as large as the volume -- is made by the first call that fills, NOT
+ * by hsk_prepare_readout (which only loads the kernels).
+ * HSK_ERR_STATE: frames in flight, a slab of a group, or any context that stores part of its volume.  HSK_ERR_ARG: a NULL
+ * context, a volume of more than 2^31 voxels, iterations outside 1..255, an unknown keep, band outside 0..8, fill_weight
+ * outside 1..128, a box with lo < 0, hi > the volume's dims or hi < lo on an axis (an empty box is legal and fills nothing).  A
+ * refused call writes nothing. */
+#define HSK_FILL_SURFACE 0
+#define HSK_FILL_ALL 1
+typedef struct hsk_fill_params {
+  int32_t iterations, keep, band, fill_weight;
+} hsk_fill_params;        /* 16 bytes */
+typedef struct hsk_fill_stats {
+  uint64_t n_unseen;            /* non-source voxels of the box before the call                                                */
+  uint64_t n_reached;           /* FILLED after the last iteration                                                             */
+  uint64_t n_written;           /* written to the volume                                                                       */
+  uint64_t n_written_negative;  /* ... with a value < 0                                                                        */
+  uint64_t tile_visits;         /* 16 x 16 x 8 tiles worked on, summed over the iterations: implementation-defined, reported,
+                                   never compared                                                                              */
+  int32_t iterations_run, pad;
+} hsk_fill_stats;         /* 48 bytes */
+/* iterations = clamp(ceil(0.15 / the smallest cell), 1, 255) in binary64 from the context's binary32 cells (k NULL:
+ * hsk_default_config(256)'s) -- gaps up to about 30 cm across close; a stated choice, not a measurement --, keep =
+ * HSK_FILL_SURFACE, band = 2, fill_weight = 1 */
+void hsk_default_fill_params(const hsk_ctx* k, hsk_fill_params* p);
+/* Fills the box (NULL: the whole volume) by the rule above (params NULL: the defaults).  stats may be NULL. */
+int hsk_fill_holes(hsk_ctx* k, const hsk_fill_params* params, const hsk_voxel_box* box, hsk_fill_stats* stats);
+/* One byte per voxel of the box (NULL: the whole volume), row-major, x fastest: 1, the last hsk_fill_holes wrote this voxel; 0, it
+ * did not -- what lets a caller paint filled surface differently or put the words back.  Valid while the volume is as that fill
+ * left it (a fill that wrote nothing holds an all-zero mask); otherwise HSK_ERR_STATE "hsk_download_fill_mask: no fill is held for
+ * the volume as it stands". */
+int hsk_download_fill_mask(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* mask);
+
 /* ---- Clearance field: how much room there is -- the exact distance from every voxel to the nearest obstacle, on the device
  * (DESIGN.md 3.18 the kernels, 8l the rule; tests/clearance_twin.py restates the rule in numpy).  All integers.  A voxel is an
  * OBSTACLE when it is the coverage rule's SOLID (observed with a TSDF <= 0); with the flag HSK_CLEAR_UNKNOWN so is every UNSEEN

@@ -1,0 +1,192 @@
+"""Hole filling without a GPU: the kernels' shared text (housescan_amd/csrc/hsk_fill_point.h, compiled for the host) against the
+numpy twin (tests/fill_twin.py) on the volumes the GPU tests use; the twin's own pins -- hand-computed steps, the planar wall with
+a hole; the default parameters; the C layout of the new structs and their Python mirror; the refusals that need no
+device."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import fill_cases as FC
+import fill_twin as FT
+from test_align_host import blocked
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- 1. the twin's own pins ---------------------------------------------------------------------------------------------------------
+def line(values):
+    """a 1 x 1 x n volume: (raw, weight) per voxel along x"""
+    return np.array(values, np.int16).reshape(1, 1, -1, 2)
+
+
+def test_the_twin_on_hand_computed_steps():
+    # one unknown voxel between 10 and 13: n = 2, u = 32778 + 32781, (2 U + n) div (2 n) = (131118 + 2) // 4 = 32780 -> 12: the
+    # mean 11.5, half rounded up
+    out, mask, st = FT.fill(line([(10, 1), (0, 0), (13, 5)]), 1, keep=FT.ALL, fill_weight=7)
+    assert out[0, 0].tolist() == [[10, 1], [12, 7], [13, 5]] and mask[0, 0].tolist() == [0, 1, 0]
+    assert st == {"n_unseen": 1, "n_reached": 1, "n_written": 1, "n_written_negative": 0, "iterations_run": 1}
+    # negative halves round up too: the mean of -10 and -13 is -11.5 -> -11
+    assert FT.fill(line([(-10, 1), (0, 0), (-13, 1)]), 1, keep=FT.ALL)[0][0, 0, 1].tolist() == [-11, 1]
+    # a raw of -32768 counts as -32767, and its word is not rewritten
+    out, _, _ = FT.fill(line([(-32768, 1), (0, 0)]), 1, keep=FT.ALL)
+    assert out[0, 0].tolist() == [[-32768, 1], [-32767, 1]]
+    # Jacobi: the front advances one voxel an iteration, and a filled voxel is computed again from itself and its neighbours
+    v = line([(100, 1), (0, 0), (0, 0), (0, 0)])
+    s1, _, r1 = FT.iterate(v, 1)
+    s2, _, r2 = FT.iterate(v, 2)
+    assert s1[0, 0].tolist() == [100, 100, FT.UNKNOWN, FT.UNKNOWN] and s2[0, 0].tolist() == [100, 100, 100, FT.UNKNOWN] and (r1, r2) == (1, 2)
+    assert FT.iterate(v, 9)[2] == 4 and FT.iterate(v, 4)[2] == 4 and FT.iterate(v, 3)[2] == 3        # iteration 4 is the first that changes nothing
+    v = line([(100, 1), (0, 0), (0, 0), (-101, 1)])
+    assert FT.iterate(v, 1)[0][0, 0].tolist() == [100, 100, -101, -101]
+    # iteration 2: (100 + 100 - 101) / 3 = 33 and (100 - 101 - 101) / 3 = -34
+    assert FT.iterate(v, 2)[0][0, 0].tolist() == [100, 33, -34, -101]
+    # no source: nothing is reached; a voxel outside the box stays unknown and is not counted
+    assert FT.fill(np.zeros((2, 3, 4, 2), np.int16), 5)[2] == {"n_unseen": 24, "n_reached": 0, "n_written": 0, "n_written_negative": 0, "iterations_run": 1}
+    out, mask, st = FT.fill(line([(100, 1), (0, 0), (0, 0), (-101, 1)]), 3, keep=FT.ALL, box=((0, 0, 0), (2, 1, 1)))
+    assert out[0, 0].tolist() == [[100, 1], [100, 1], [0, 0], [-101, 1]] and st["n_unseen"] == 1 and st["n_reached"] == 1
+
+
+def test_the_keep_rule_on_a_line():
+    # values 300 200 100 | -100 -200 -300 filled between two sources: the crossing is the pair (2, 3); band 0 keeps those two,
+    # band 1 two more; a voxel at 32767 makes no crossing
+    v = np.zeros((1, 1, 12, 2), np.int16)
+    v[0, 0, 0] = (30000, 1)
+    v[0, 0, 11] = (-30000, 1)
+    state, free, _ = FT.iterate(v, 40)
+    c = FT.crossing_voxels(state)[0, 0]
+    assert c.sum() == 2 and c[5] and c[6]
+    for band in (0, 1, 3):
+        _, mask, st = FT.fill(v, 40, band=band)
+        assert mask[0, 0].tolist() == [0] + [1 if abs(x - 5.5) <= band + 0.5 else 0 for x in range(1, 11)] + [0] and st["n_written"] == 2 + 2 * band
+    assert FT.fill(v, 40, band=8)[2]["n_written"] == 10 == FT.fill(v, 40, keep=FT.ALL)[2]["n_written"]
+    sat = line([(32767, 1), (-5, 1), (0, 0)])
+    assert not FT.crossing_voxels(FT.initial_states(sat)).any() and FT.fill(sat, 1)[2]["n_written"] == 0 and FT.fill(sat, 1)[2]["n_reached"] == 1
+    # Chebyshev: the corner of the cube counts
+    m = np.zeros((5, 5, 5), bool)
+    m[2, 2, 2] = True
+    assert FT.dilate(m, 1).sum() == 27 and FT.dilate(m, 2).all() and FT.dilate(m, 0).sum() == 1
+
+
+@pytest.mark.parametrize("hole, iterations, reached, kept", [(12, 16, 24584, 864), (6, 8, 13320, 216), (20, 24, 28800, 2400)])
+def test_the_planar_wall_closes_on_the_twin(hole, iterations, reached, kept):
+    """the wall at z0 = 30.3 voxels with a hole x hole column hole, SURFACE, band 2: every hole column gets exactly one z crossing,
+    within 0.25 voxel of z0 (measured: 30.305 .. 30.341 over the three sizes); the counts are the twin's own, recorded here"""
+    vol, (x0, x1, y0, y1) = FT.planar_wall(hole=hole)
+    out, mask, st = FC.twin_of(("wall", hole, iterations), vol, dict(iterations=iterations))
+    assert (st["n_reached"], st["n_written"], st["n_written_negative"]) == (reached, kept, kept // 2)
+    zs = [FT.column_crossings(out, x, y) for y in range(y0, y1) for x in range(x0, x1)]
+    assert all(len(z) == 1 for z in zs) and len(zs) == hole * hole
+    print(f"hole {hole}: crossings at {min(z[0] for z in zs):.3f} .. {max(z[0] for z in zs):.3f}, {st}")
+    assert all(abs(z[0] - 30.3) <= 0.25 for z in zs)
+    assert all(FT.column_crossings(vol, x, y) == [] for y in range(y0, y1) for x in range(x0, x1))
+    # what is written lies in the hole's columns, two planes either side of the crossing's pair: 6 planes of hole^2
+    assert mask.sum() == 6 * hole * hole and mask[28:34, y0:y1, x0:x1].all()
+
+
+# ---- 2. the kernels' shared text on the host -------------------------------------------------------------------------------------
+def run_harness(exe, tmp_path, vol, iterations, keep=FT.SURFACE, band=2, fill_weight=1, box=None):
+    Z, Y, X = vol.shape[:3]
+    lo, hi = ((0, 0, 0), (X, Y, Z)) if box is None else box
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(src, "wb") as f:
+        f.write(np.array([X, Y, Z, iterations, keep, band, fill_weight, *lo, *hi], np.int32).tobytes())
+        f.write(blocked(vol).tobytes())
+    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    raw = open(dst, "rb").read()
+    n = X * Y * Z
+    state = np.frombuffer(raw, np.int16, n).reshape(Z, Y, X)
+    mask = np.frombuffer(raw, np.uint8, n, 2 * n).reshape(Z, Y, X)
+    words = np.frombuffer(raw, np.uint32, n, 3 * n).reshape(Z, Y, X)
+    st = np.frombuffer(raw, np.uint64, 5, 7 * n)
+    out = np.stack([(words & 0xffff).astype(np.uint16).view(np.int16), (words >> 16).astype(np.uint16).view(np.int16)], axis=-1)
+    stats = dict(zip(("n_unseen", "n_reached", "n_written", "n_written_negative", "iterations_run"), map(int, st)))
+    return state, out, mask, stats
+
+
+def test_the_kernels_step_equals_the_twin_on_the_host(tmp_path):
+    """hsk_fill_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
+    program), filling sequentially: final states, words, mask and stats against the twin, zero differences"""
+    exe = tmp_path / "fill_point"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "fill_point_harness.cpp"), "-o", str(exe)])
+    cases = [(name, vol, params, box, FC.shape_twin(name)) for name, (vol, params, box) in FC.shapes().items()]
+    for dims, (it, keep) in (((72, 56, 40), FC.RANDOM_PARAMS[0]), ((80, 64, 41), FC.RANDOM_PARAMS[3])):
+        cases.append((f"random {dims}", FC.random_volume(dims), dict(iterations=it, keep=keep), None, FC.random_twin(dims, it, keep)))
+    for name, vol, params, box, (ref, ref_mask, ref_st) in cases:
+        state, out, mask, st = run_harness(exe, tmp_path, vol, box=box, **params)
+        print(f"{name}: {st}")
+        assert int((state.astype(np.int32) != FT.iterate(vol, params["iterations"], box)[0]).sum()) == 0, name
+        assert int((out != ref).sum()) == 0 and int((mask != ref_mask).sum()) == 0 and st == ref_st, name
+
+
+def test_the_cases_reach_what_they_are_for():
+    """the conditions of the shared volumes, on the twin"""
+    S = FC.shapes()
+    for name in ("no source", "no non-source", "an empty box"):
+        assert FC.shape_twin(name)[2]["n_written"] == 0 and np.array_equal(FC.shape_twin(name)[0], S[name][0]), name
+    assert FC.shape_twin("no source")[2]["n_unseen"] == 12 * 24 * 32 and FC.shape_twin("no non-source")[2]["n_unseen"] == 0
+    assert FC.shape_twin("an empty box")[2]["n_unseen"] == 0
+    one = FC.shape_twin("one unknown voxel")
+    assert one[2]["n_written"] == 1 and one[1][5, 11, 15] == 1 and one[2]["iterations_run"] == 2
+    six = FC.shape_twin("a hole on each grid face")[1]
+    assert six[:, :, 0].any() and six[:, :, -1].any() and six[:, 0].any() and six[:, -1].any() and six[0].any() and six[-1].any()
+    low = FC.shape_twin("hole across x = 16, y = 16, z = 8")[1]
+    assert low[7, 15:17, 15:17].all() and low[8, 15:17, 15:17].all()                                  # written on both sides of all three tile faces
+    raw = S["a source with raw -32768"][0]
+    assert (raw[..., 0] == -32768).sum() == 80 and np.array_equal(FC.shape_twin("a source with raw -32768")[0][raw[..., 1] != 0], raw[raw[..., 1] != 0])
+    assert FC.shape_twin("a source with raw -32768")[0][..., 0].min() == -32768 and (FC.shape_twin("a source with raw -32768")[0][raw[..., 1] == 0][:, 0] >= -32767).all()
+    half, whole = FC.shape_twin("a box through the hole"), FC.shape_twin("planar wall")
+    assert 0 < half[2]["n_written"] < whole[2]["n_written"] and not half[1][:, :, 20:].any() and half[1][:, :, 14:20].any()
+    b0, b2, b8 = (FC.shape_twin(n)[2]["n_written"] for n in ("band 0", "fill_weight 128", "band 8"))
+    assert 0 < b0 < b2 < b8 and (FC.shape_twin("fill_weight 128")[0][FC.shape_twin("fill_weight 128")[1] == 1][:, 1] == 128).all()
+    long = FC.shape_twin("255 iterations")[2]
+    assert long["n_reached"] == long["n_unseen"] and 30 < long["iterations_run"] <= 255
+    for dims in FC.RANDOM_DIMS:
+        st = FC.random_twin(dims, *FC.RANDOM_PARAMS[0])[2]
+        assert st["n_written"] > 1000 and st["n_reached"] > st["n_written"], dims
+
+
+# ---- 3. the default parameters, header, C layout, Python mirror, errors without a device ------------------------------------------
+def test_default_fill_params_without_a_context(hsk):
+    p = hsk.default_fill_params()
+    assert (p.iterations, p.keep, p.band, p.fill_weight) == (13, hsk._lib.HSK_FILL_SURFACE, 2, 1)      # 256 voxels over 3 m: ceil(12.8)
+    assert FT.default_iterations((3.0 / 512,) * 3) == 26 and FT.default_iterations((3.0 / 256,) * 3) == 13
+    assert FT.default_iterations((np.float32(3.0) / np.float32(80), 3.0 / 64, 3.0 / 48)) == 4           # the tests' 80-voxel grids
+    assert FT.default_iterations((1.0, 1.0, 1.0)) == 1 and FT.default_iterations((1e-5, 1.0, 1.0)) == 255
+    q = hsk.default_fill_params(iterations=7, keep=1, band=0, fill_weight=128)
+    assert (q.iterations, q.keep, q.band, q.fill_weight) == (7, 1, 0, 128)
+    with pytest.raises(TypeError, match="no field"):
+        hsk.default_fill_params(size=3)
+    hsk._lib.load().hsk_default_fill_params(None, None)
+
+
+def test_fill_structs_have_the_c_layout(tmp_path, hsk):
+    from housescan_amd import _lib
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d\\n", '
+                   'sizeof(hsk_fill_params), offsetof(hsk_fill_params, keep), offsetof(hsk_fill_params, band), offsetof(hsk_fill_params, fill_weight), '
+                   'sizeof(hsk_fill_stats), offsetof(hsk_fill_stats, n_reached), offsetof(hsk_fill_stats, n_written), '
+                   'offsetof(hsk_fill_stats, n_written_negative), offsetof(hsk_fill_stats, tile_visits), offsetof(hsk_fill_stats, iterations_run), '
+                   'HSK_FILL_SURFACE, HSK_FILL_ALL);return 0;}\n')
+    exe = tmp_path / "sz"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
+    P, S = _lib.HskFillParams, _lib.HskFillStats
+    assert got == [C.sizeof(P), P.keep.offset, P.band.offset, P.fill_weight.offset, C.sizeof(S), S.n_reached.offset, S.n_written.offset,
+                   S.n_written_negative.offset, S.tile_visits.offset, S.iterations_run.offset, _lib.HSK_FILL_SURFACE, _lib.HSK_FILL_ALL]
+    assert C.sizeof(P) == 16 and C.sizeof(S) == 48
+    assert (FT.SURFACE, FT.ALL) == (_lib.HSK_FILL_SURFACE, _lib.HSK_FILL_ALL) == (hsk.FILL_SURFACE, hsk.FILL_ALL)
+    assert tuple(n for n, _ in P._fields_) == hsk.kinfu.FILL_FIELDS
+
+
+def test_null_contexts_are_refused(hsk):
+    lib, L = hsk._lib.load(), hsk._lib
+    st = L.HskFillStats(n_written=77)
+    assert lib.hsk_fill_holes(None, None, None, C.byref(st)) == -1 and st.n_written == 77
+    mask = np.full(4, 9, np.uint8)
+    assert lib.hsk_download_fill_mask(None, None, mask.ctypes.data) == -1 and (mask == 9).all()
+    for name in ("fill_holes", "download_fill_mask", "default_fill_params"):
+        assert callable(getattr(hsk.KinfuTracker, name))
