@@ -290,6 +290,44 @@ class HskFillStats(C.Structure):
                 ("tile_visits", C.c_uint64), ("iterations_run", C.c_int32), ("pad", C.c_int32)]
 
 
+HSK_DIFF_UNSEEN, HSK_DIFF_ONLY_REF, HSK_DIFF_ONLY_CUR, HSK_DIFF_SAME, HSK_DIFF_APPEARED, HSK_DIFF_VANISHED, HSK_DIFF_MINOR = range(7)
+HSK_ADOPT_APPEARED, HSK_ADOPT_VANISHED = 1, 2
+
+
+class HskDiffParams(C.Structure):
+    """Mirror of `hsk_diff_params` (include/hskinfu.h): 16 bytes."""
+
+    _fields_ = [("thresh", C.c_int32), ("min_weight", C.c_int32), ("min_voxels", C.c_uint64)]
+
+
+class HskDiffRegion(C.Structure):
+    """Mirror of `hsk_diff_region` (include/hskinfu.h): 64 bytes."""
+
+    _fields_ = [
+        ("root", C.c_int32 * 3), ("pad", C.c_int32),
+        ("n_voxels", C.c_uint64), ("n_appeared", C.c_uint64), ("n_vanished", C.c_uint64),
+        ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+    ]
+
+
+class HskDiffStats(C.Structure):
+    """Mirror of `hsk_diff_stats` (include/hskinfu.h): 80 bytes."""
+
+    _fields_ = [("n_class", C.c_uint64 * 7), ("n_regions", C.c_uint64), ("n_minor_regions", C.c_uint64), ("largest", C.c_uint64)]
+
+
+class HskAdoptParams(C.Structure):
+    """Mirror of `hsk_adopt_params` (include/hskinfu.h): 8 bytes."""
+
+    _fields_ = [("which", C.c_int32), ("halo", C.c_int32)]
+
+
+class HskAdoptStats(C.Structure):
+    """Mirror of `hsk_adopt_stats` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [("n_targets", C.c_uint64), ("n_adopted", C.c_uint64), ("n_colored", C.c_uint64)]
+
+
 HSK_CLEAR_UNKNOWN = 1
 HSK_CLEAR_MAX_REACH = 255
 HSK_CLEARANCE_FAR, HSK_CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
@@ -507,6 +545,12 @@ SYMBOLS = {
     "hsk_default_fill_params": (None, [_P, C.POINTER(HskFillParams)]),
     "hsk_fill_holes": (C.c_int, [_P, C.POINTER(HskFillParams), C.POINTER(HskVoxelBox), C.POINTER(HskFillStats)]),
     "hsk_download_fill_mask": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P]),
+    "hsk_default_diff_params": (None, [_P, C.POINTER(HskDiffParams)]),
+    "hsk_diff_volume": (C.c_int, [_P, _P, C.POINTER(HskDiffParams), C.POINTER(HskDiffRegion), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskDiffStats)]),
+    "hsk_download_diff": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P, _P]),
+    "hsk_diff_at": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
+    "hsk_adopt_diff": (C.c_int, [_P, _P, C.POINTER(HskAdoptParams), C.POINTER(HskAdoptStats)]),
+    "hsk_release_diff": (C.c_int, [_P]),
     "hsk_default_clearance_params": (None, [_P, C.POINTER(HskClearanceParams)]),
     "hsk_clearance_d2": (C.c_uint32, [C.POINTER(HskClearanceParams), C.c_float]),
     "hsk_build_clearance": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskClearanceStats)]),

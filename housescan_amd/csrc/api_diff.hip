@@ -1,0 +1,318 @@
+// api_diff.hip -- the C ABI's volume differencing (include/hskinfu.h "Volume differencing"; DESIGN.md 3.23 the kernels, 8q the
+// rule): hsk_default_diff_params, hsk_diff_volume, hsk_download_diff, hsk_diff_at, hsk_adopt_diff, hsk_release_diff.  The rule
+// compares weights with min_weight, so both contexts' deferred weights are written back first (as hsk_fuse_volume does; that
+// changes nothing either context returns).  The regions are components.hip's labelling run on the class words, in a scratch of
+// the diff's own (d_diff): hsk_label_components' cached labelling (d_comp, comp_epoch) is neither read nor written.  The diff
+// stays on the device with its records and stats on the host while the three parts of diff_key stand; a call with the same cur
+// and parameters meanwhile is answered from them.  Adopting writes the volume in
+// hsk_prune_components' order: flush the deferred weights, write, volume_replaced.
+#pragma clang fp contract(off)
+#include <algorithm>
+#include <new>
+
+#include "hsk_ctx.h"
+#include "hsk_diff_point.h"
+
+static_assert(HSK_DIFF_UNSEEN == DIFF_UNSEEN && HSK_DIFF_ONLY_REF == DIFF_ONLY_REF && HSK_DIFF_ONLY_CUR == DIFF_ONLY_CUR && HSK_DIFF_SAME == DIFF_SAME &&
+                  HSK_DIFF_APPEARED == DIFF_APPEARED && HSK_DIFF_VANISHED == DIFF_VANISHED && HSK_DIFF_MINOR == DIFF_MINOR &&
+                  HSK_ADOPT_APPEARED == DIFF_ADOPT_APPEARED && HSK_ADOPT_VANISHED == DIFF_ADOPT_VANISHED && HSK_COMPONENT_NONE == COMP_NONE,
+              "hsk_diff_point.h restates the header's numbers");
+static_assert(sizeof(hsk_diff_params) == 16 && sizeof(hsk_diff_region) == 64 && sizeof(hsk_diff_stats) == 80 && sizeof(hsk_adopt_params) == 8 &&
+                  sizeof(hsk_adopt_stats) == 24,
+              "the diff structs");
+
+extern "C" void hsk_default_diff_params(const hsk_ctx* k, hsk_diff_params* p) {
+  if (!p) return;
+  hsk_prune_params pp;
+  hsk_default_prune_params(k, &pp);
+  memset(p, 0, sizeof(*p));
+  p->thresh = 16384;
+  p->min_weight = 1;
+  p->min_voxels = pp.min_voxels;
+}
+
+// the state a diff call needs of one context, reported in `errs`
+static int diff_state_check(hsk_ctx* k, hsk_ctx* errs, const char* who) {
+  if (int rs = require_whole_volume(k, errs, who)) return rs;
+  if (int ri = require_idle(k, errs)) return ri;
+  if ((uint64_t)k->vp.X * (uint64_t)k->vp.Y * (uint64_t)k->vp.Z > ((uint64_t)1 << 31))
+    return fail(errs, HSK_ERR_ARG, (std::string(who) + ": the volume has more than 2^31 voxels").c_str());
+  return HSK_OK;
+}
+// a diff is held for ref's volume as it stands
+static int diff_held_check(hsk_ctx* ref, const char* who) {
+  if (!ref->d_diff || ref->diff_key[0] == 0 || ref->diff_key[0] != ref->vol_epoch)
+    return fail(ref, HSK_ERR_STATE, (std::string(who) + ": no diff is held for the volume as it stands").c_str());
+  return HSK_OK;
+}
+
+// d_diff_tab for n regions: the roots, the records' eight words each, the two class counts each
+struct DiffTab {
+  size_t bytes;
+  unsigned *roots, *table, *av;
+};
+static DiffTab diff_tab(const hsk_ctx* k, size_t n) {
+  ProductLayout l;
+  char* base = (char*)k->d_diff_tab;
+  DiffTab t;
+  const size_t roots_at = l.take(n * 4), table_at = l.take(n * 32), av_at = l.take(n * 8);
+  t.roots = (unsigned*)(base + roots_at);
+  t.table = (unsigned*)(base + table_at);
+  t.av = (unsigned*)(base + av_at);
+  t.bytes = l.bytes;
+  return t;
+}
+
+extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params* params, hsk_diff_region* recs, size_t cap, size_t* n_regions,
+                               hsk_diff_stats* stats) {
+  if (!ref) return HSK_ERR_ARG;
+  if (!cur || !n_regions) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: null argument");
+  if (ref == cur) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: ref and cur are the same context");
+  hsk_diff_params p;
+  hsk_default_diff_params(ref, &p);  // (zeroes the whole struct first)
+  if (params) {
+    p.thresh = params->thresh;
+    p.min_weight = params->min_weight;
+    p.min_voxels = params->min_voxels;
+  }
+  if (p.thresh < 1 || p.thresh > 65534) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: thresh must lie in 1..65534");
+  if (p.min_weight < 1 || p.min_weight > 128) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: min_weight must lie in 1..128");
+  if (p.min_voxels < 1) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: min_voxels must be at least 1");
+  for (hsk_ctx* c : {ref, cur})
+    if (int rc = diff_state_check(c, ref, "hsk_diff_volume")) return rc;
+  if (ref->vp.X != cur->vp.X || ref->vp.Y != cur->vp.Y || ref->vp.Z != cur->vp.Z || memcmp(ref->cfg.vol_size_m, cur->cfg.vol_size_m, 3 * sizeof(float)) != 0 ||
+      memcmp(&ref->vp.tau, &cur->vp.tau, sizeof(float)) != 0)
+    return fail(ref, HSK_ERR_ARG,
+                "hsk_diff_volume: the volumes do not lie on the same grid (dims, size_m and effective truncation distance must be equal); resample cur first: "
+                "hsk_fuse_volume into an empty context of ref's configuration");
+  if (ref->cfg.device_id != cur->cfg.device_id) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: the contexts are on different devices");
+  hsk_ctx* k = ref;
+  // the diff of an earlier call still fits: both volumes stand, cur is the same context, the parameters are the same.  Nothing is
+  // launched; the records and stats are the held ones (what a size query followed by the fill costs once, as the labelling's)
+  const bool held = k->d_diff && k->diff_key[0] != 0 && k->diff_key[0] == k->vol_epoch && k->diff_key[1] == cur->serial && k->diff_key[2] == cur->vol_epoch &&
+                    memcmp(&k->diff_params, &p, sizeof(p)) == 0;
+  if (held) {
+    const size_t n = k->diff_recs.size();
+    *n_regions = n;
+    if (stats) *stats = k->diff_stats;
+    if (!recs) return HSK_OK;
+    if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
+    if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
+    return HSK_OK;
+  }
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  // cur: read only.  Its deferred weights are written back; everything its stream holds must have ended before ref's stream reads it
+  flush_weights(cur);
+  HIPCHK(k, hipStreamSynchronize(cur->stream));
+  flush_weights(k);
+  k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;  // (the scratch is about to be written: an earlier diff goes)
+  k->diff_recs.clear();
+  int r = ensure_grown(k, &k->d_diff, &k->diff_bytes, diff_layout(k->vp, nullptr, nullptr));
+  if (r != HSK_OK) return r;
+  DiffBufs b;
+  diff_layout(k->vp, k->d_diff, &b);
+  launch_diff_classify(k->stream, k->d_vol, cur->d_vol, k->vp, b, p.thresh, p.min_weight);
+  launch_comp_label(k->stream, b.cls, k->vp, b.comp);
+  HIPCHK(k, hipGetLastError());
+  unsigned counts[DIFF_COUNTS], n_roots = 0;
+  r = copy_out(k, counts, b.counts, sizeof(counts));
+  if (r == HSK_OK) r = copy_out(k, &n_roots, b.comp.counts + 4, sizeof(n_roots));
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  hsk_diff_stats st;
+  memset(&st, 0, sizeof(st));
+  for (int c = 0; c < DIFF_CLASSES; ++c) st.n_class[c] = counts[c];
+  *n_regions = 0;
+  if ((size_t)n_roots > HSK_COMPONENT_MAX) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: more than 2^24 regions: nothing is held");
+  std::vector<unsigned> roots, table, av;
+  try {
+    roots.resize(n_roots);
+    table.resize((size_t)n_roots * 8);
+    av.resize((size_t)n_roots * 2);
+  } catch (const std::bad_alloc&) {
+    return fail(k, HSK_ERR_STATE, "hsk_diff_volume: out of host memory for the records");
+  }
+  if (n_roots > 0) {
+    r = ensure_grown(k, &k->d_diff_tab, &k->diff_tab_bytes, diff_tab(k, n_roots).bytes);
+    if (r != HSK_OK) return r;
+    const DiffTab t = diff_tab(k, n_roots);
+    launch_comp_records(k->stream, k->vp, b.comp, n_roots, t.roots, t.table);
+    // the MINOR step: the words of a region below min_voxels keep their class in the weight half and stop being members
+    const unsigned min_voxels = p.min_voxels > 0xffffffffull ? 0xffffffffu : (unsigned)p.min_voxels;  // (no region has 2^32 voxels)
+    launch_comp_prune(k->stream, b.cls, nullptr, k->vp, b.comp.parent, t.roots, t.table, n_roots, min_voxels, t.roots, 0u, true);
+    launch_diff_records(k->stream, k->vp, b, n_roots, t.roots, t.av);
+    HIPCHK(k, hipGetLastError());
+    r = copy_out(k, roots.data(), t.roots, (size_t)n_roots * 4);
+    if (r == HSK_OK) r = copy_out(k, table.data(), t.table, (size_t)n_roots * 32);
+    if (r == HSK_OK) r = copy_out(k, av.data(), t.av, (size_t)n_roots * 8);
+    if (r != HSK_OK) return r;
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    HIPCHK(k, hipGetLastError());
+  }
+  const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
+  uint64_t kept_a = 0, kept_v = 0;
+  try {
+    for (size_t i = 0; i < n_roots; ++i) {
+      const unsigned* t8 = &table[i * 8];
+      if ((uint64_t)t8[0] < p.min_voxels) {
+        st.n_minor_regions += 1;
+        continue;
+      }
+      hsk_diff_region c;
+      memset(&c, 0, sizeof(c));
+      unsigned x, y, z;
+      g.xyz(roots[i], x, y, z);
+      c.root[0] = (int32_t)x;
+      c.root[1] = (int32_t)y;
+      c.root[2] = (int32_t)z;
+      c.n_voxels = t8[0];
+      c.n_appeared = av[2 * i];
+      c.n_vanished = av[2 * i + 1];
+      for (int a = 0; a < 3; ++a) {
+        c.lo[a] = (int32_t)t8[1 + a];
+        c.hi[a] = (int32_t)t8[4 + a];
+      }
+      kept_a += c.n_appeared;
+      kept_v += c.n_vanished;
+      k->diff_recs.push_back(c);
+    }
+  } catch (const std::bad_alloc&) {
+    k->diff_recs.clear();
+    return fail(k, HSK_ERR_STATE, "hsk_diff_volume: out of host memory for the records");
+  }
+  std::sort(k->diff_recs.begin(), k->diff_recs.end(), [&](const hsk_diff_region& a, const hsk_diff_region& c) {
+    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
+                              g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
+  });
+  // the final classes: what the kept regions hold stays APPEARED or VANISHED, the rest of CHANGED is MINOR
+  st.n_class[DIFF_MINOR] = (st.n_class[DIFF_APPEARED] - kept_a) + (st.n_class[DIFF_VANISHED] - kept_v);
+  st.n_class[DIFF_APPEARED] = kept_a;
+  st.n_class[DIFF_VANISHED] = kept_v;
+  st.n_regions = k->diff_recs.size();
+  st.largest = k->diff_recs.empty() ? 0 : k->diff_recs[0].n_voxels;
+  k->diff_stats = st;
+  memset(&k->diff_params, 0, sizeof(k->diff_params));  // (compared as bytes: the padding, if any, is zero on both sides)
+  k->diff_params.thresh = p.thresh;
+  k->diff_params.min_weight = p.min_weight;
+  k->diff_params.min_voxels = p.min_voxels;
+  k->diff_key[0] = k->vol_epoch;
+  k->diff_key[1] = cur->serial;
+  k->diff_key[2] = cur->vol_epoch;
+  const size_t n = k->diff_recs.size();
+  *n_regions = n;
+  if (stats) *stats = st;
+  if (!recs) return HSK_OK;
+  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
+  if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
+  return HSK_OK;
+}
+
+extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* cls, uint32_t* region) {
+  if (!k) return HSK_ERR_ARG;
+  hsk_voxel_box bx;
+  size_t n;
+  if (int rc = clear_box_check(k, box, "hsk_download_diff", &bx, &n)) return rc;
+  if (n > 0 && !cls) return fail(k, HSK_ERR_ARG, "hsk_download_diff: cls is null");
+  if (int rc = diff_state_check(k, k, "hsk_download_diff")) return rc;
+  if (int rc = diff_held_check(k, "hsk_download_diff")) return rc;
+  if (n == 0) return HSK_OK;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  ProductLayout lay;
+  const size_t cls_at = lay.take(n), region_at = lay.take(region ? n * 4 : 0);
+  int r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  DiffBufs b;
+  diff_layout(k->vp, k->d_diff, &b);
+  char* base = (char*)k->d_out;
+  launch_diff_box(k->stream, k->vp, b, bx.lo, bx.hi, n, (unsigned char*)(base + cls_at), region ? (unsigned*)(base + region_at) : nullptr);
+  HIPCHK(k, hipGetLastError());
+  r = copy_out(k, cls, base + cls_at, n);
+  if (r == HSK_OK && region) r = copy_out(k, region, base + region_at, n * 4);
+  return r;
+}
+
+extern "C" int hsk_diff_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint32_t* region) {
+  if (!k) return HSK_ERR_ARG;
+  if (n > 0 && (!xyz || !cls)) return fail(k, HSK_ERR_ARG, "hsk_diff_at: null argument");
+  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_diff_at: more than 2^20 points");
+  if (radius < 0 || radius > 4) return fail(k, HSK_ERR_ARG, "hsk_diff_at: radius must lie in 0..4");
+  if (int rc = diff_state_check(k, k, "hsk_diff_at")) return rc;
+  if (int rc = diff_held_check(k, "hsk_diff_at")) return rc;
+  if (n == 0) return HSK_OK;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  ProductLayout lay;
+  const size_t pts_at = lay.take(n * 12), region_at = lay.take(n * 4), cls_at = lay.take(n);
+  int r = ensure_product_bytes(k, lay.bytes);
+  if (r != HSK_OK) return r;
+  DiffBufs b;
+  diff_layout(k->vp, k->d_diff, &b);
+  char* base = (char*)k->d_out;
+  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
+  launch_diff_gather(k->stream, k->vp, b, (const float*)(base + pts_at), (unsigned)n, radius, (unsigned*)(base + region_at), (unsigned char*)(base + cls_at));
+  HIPCHK(k, hipGetLastError());
+  r = copy_out(k, cls, base + cls_at, n);
+  if (r == HSK_OK && region) r = copy_out(k, region, base + region_at, n * 4);
+  return r;
+}
+
+extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params* params, hsk_adopt_stats* stats) {
+  if (!ref) return HSK_ERR_ARG;
+  if (!cur) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: null argument");
+  if (ref == cur) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: ref and cur are the same context");
+  hsk_adopt_params p;
+  p.which = HSK_ADOPT_APPEARED | HSK_ADOPT_VANISHED;
+  p.halo = 2;
+  if (params) p = *params;
+  if (p.which < 1 || p.which > 3) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: which must be HSK_ADOPT_APPEARED, HSK_ADOPT_VANISHED or both");
+  if (p.halo < 0 || p.halo > 8) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: halo must lie in 0..8");
+  for (hsk_ctx* c : {ref, cur})
+    if (int rc = diff_state_check(c, ref, "hsk_adopt_diff")) return rc;
+  if (int rc = diff_held_check(ref, "hsk_adopt_diff")) return rc;
+  if (ref->diff_key[1] != cur->serial || ref->diff_key[2] != cur->vol_epoch)
+    return fail(ref, HSK_ERR_STATE, "hsk_adopt_diff: no diff is held for the volumes as they stand (cur is another context, or its volume has changed)");
+  hsk_ctx* k = ref;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  HIPCHK(k, hipStreamSynchronize(cur->stream));
+  DiffBufs b;
+  diff_layout(k->vp, k->d_diff, &b);
+  launch_diff_halo(k->stream, cur->d_vol, k->vp, b, p.which, p.halo);
+  HIPCHK(k, hipGetLastError());
+  unsigned counts[2] = {0, 0};
+  int r = copy_out(k, counts, b.counts + 8, sizeof(counts));
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  hsk_adopt_stats st;
+  memset(&st, 0, sizeof(st));
+  st.n_targets = counts[0];
+  st.n_adopted = counts[1];
+  if (st.n_adopted > 0) {
+    st.n_colored = (k->d_color && cur->d_color) ? st.n_adopted : 0;
+    flush_weights(k);  // the words that stay are to hold their weights
+    launch_diff_adopt(k->stream, k->d_vol, cur->d_vol, k->d_color, cur->d_color, k->vp, b);
+    HIPCHK(k, hipGetLastError());
+    k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;  // (the held diff described the volume as it was)
+    r = volume_replaced(k);
+    if (r != HSK_OK) return r;
+    HIPCHK(k, hipStreamSynchronize(k->stream));
+    HIPCHK(k, hipGetLastError());
+  }  // (else nothing is written, vol_epoch does not move: cached passes and the diff stay valid)
+  if (stats) *stats = st;
+  return HSK_OK;
+}
+
+extern "C" int hsk_release_diff(hsk_ctx* k) {
+  if (!k) return HSK_ERR_ARG;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  for (void** buf : {&k->d_diff, &k->d_diff_tab})
+    if (*buf) {
+      HIPCHK(k, hipStreamSynchronize(k->stream));
+      HIPCHK(k, hipFree(*buf));
+      *buf = nullptr;
+    }
+  k->diff_bytes = k->diff_tab_bytes = 0;
+  k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;
+  k->diff_recs.clear();
+  return HSK_OK;
+}

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -28,8 +29,15 @@ struct ImgBufs {
   unsigned char* d_rgb = nullptr;  // the frame's colour image (RGB8), only once colour is enabled (hsk_enable_color)
 };
 
+// a number no other context of the process ever had (a diff names the context it was made with; an address can come back)
+inline uint64_t next_ctx_serial() {
+  static std::atomic<uint64_t> n{0};
+  return n.fetch_add(1) + 1;
+}
+
 struct hsk_ctx {
   hsk_config cfg;
+  uint64_t serial = next_ctx_serial();
   hipStream_t stream = nullptr;
   bool own_stream = false;
   VolParams vp;
@@ -182,6 +190,19 @@ struct hsk_ctx {
   size_t fill_bytes = 0;
   uint64_t fill_epoch = 0;
   const unsigned char* fill_mask = nullptr;
+  // volume differencing (hsk_diff_volume; diff.hip), made by the first call that diffs and freed by hsk_release_diff: d_diff =
+  // diff_layout's counters, class words, byte volumes and labelling scratch; d_diff_tab = the regions' roots, records and class
+  // counts (grown only).  What they hold is the diff of this volume at diff_key[0] against the context with the serial diff_key[1]
+  // at its epoch diff_key[2] (all 0: nothing); diff_recs the kept regions' records in their order, diff_stats
+  // the call's stats, diff_params its parameters: hsk_diff_volume answers a call with the same cur and parameters from them
+  void* d_diff = nullptr;
+  size_t diff_bytes = 0;
+  void* d_diff_tab = nullptr;
+  size_t diff_tab_bytes = 0;
+  uint64_t diff_key[3] = {0, 0, 0};
+  std::vector<hsk_diff_region> diff_recs;
+  hsk_diff_stats diff_stats = {};
+  hsk_diff_params diff_params = {};
   // the clearance field (hsk_build_clearance; clearance.hip), made by the first call that builds and freed by
   // hsk_release_clearance: d_clear = clear_layout's counters, field and intermediates.  What it holds is the field of the volume
   // at clear_epoch (0: nothing) for the 20 device-relevant parameter bytes in clear_key, and clear_counts its counters

@@ -430,3 +430,31 @@ void launch_fill_commit(hipStream_t s, void* vol, const VolParams& vp, const Fil
 // out[n] = the mask's bytes over the box, row-major
 void launch_fill_mask_box(hipStream_t s, const unsigned char* mask, const VolParams& vp, const int lo[3], const int hi[3], size_t n, unsigned char* out);
 int fill_warm();      // loads fill.hip's code object (hsk_prepare_readout); a hipError_t
+
+// volume differencing (diff.hip) of two WHOLE volumes on one grid.  The scratch, carved out of one device
+// buffer by diff_layout: the counters, the class words (one per volume word, in the volume's layout: hsk_diff_point.h), two byte
+// volumes (row-major) for the adopt set, and a labelling scratch of its own (comp_layout: never the one hsk_label_components holds)
+#define DIFF_COUNTS 16  // [0..6] the classes before the MINOR step, [8] the adopt targets, [9] the adopt set
+struct DiffBufs {
+  unsigned* counts;
+  unsigned* cls;           // hsk_vol_words
+  unsigned char* mask[2];  // X Y Z bytes each
+  CompBufs comp;
+};
+size_t diff_layout(const VolParams& vp, void* base /* null: the size only */, DiffBufs* b);
+// the class words of (ref, cur) and counts[0..6]
+void launch_diff_classify(hipStream_t s, const void* ref, const void* cur, const VolParams& vp, const DiffBufs& b, int thresh, int min_weight);
+// behind the labelling and the MINOR step: av[2 i], av[2 i + 1] = the APPEARED and VANISHED voxels of region roots[i] (0, 0 for a
+// region that was not kept)
+void launch_diff_records(hipStream_t s, const VolParams& vp, const DiffBufs& b, unsigned n, const unsigned* roots, unsigned* av);
+// the n > 0 voxels of a box, row-major: class bytes and (region may be null) labels
+void launch_diff_box(hipStream_t s, const VolParams& vp, const DiffBufs& b, const int lo[3], const int hi[3], size_t n, unsigned char* cls,
+                     unsigned* region);
+// hsk_diff_at's choice for n > 0 points
+void launch_diff_gather(hipStream_t s, const VolParams& vp, const DiffBufs& b, const float* xyz, unsigned n, int radius, unsigned* region,
+                        unsigned char* cls);
+// the adopt set's halo in mask[1] and its counts: counts[8] the targets, counts[9] the set; nothing but the scratch is written
+void launch_diff_halo(hipStream_t s, const void* cur, const VolParams& vp, const DiffBufs& b, int which, int halo);
+// the masked copy: cur's words into ref and, ref_col not null, cur's colour words (cur_col null: the colour word 0)
+void launch_diff_adopt(hipStream_t s, void* ref, const void* cur, unsigned* ref_col, const unsigned* cur_col, const VolParams& vp, const DiffBufs& b);
+int diff_warm();      // loads diff.hip's code object (hsk_prepare_readout); a hipError_t

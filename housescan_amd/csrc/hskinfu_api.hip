@@ -157,6 +157,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_comp);
   F(k->d_comp_tab);
   F(k->d_fill);
+  F(k->d_diff);
+  F(k->d_diff_tab);
   F(k->d_clear);
   F(k->d_reach);
   F(k->d_part);

@@ -106,6 +106,25 @@ def default_prune_params(tracker=None, **fields):
 
 FILL_SURFACE, FILL_ALL = 0, 1
 FILL_FIELDS = ("iterations", "keep", "band", "fill_weight")
+DIFF_UNSEEN, DIFF_ONLY_REF, DIFF_ONLY_CUR, DIFF_SAME, DIFF_APPEARED, DIFF_VANISHED, DIFF_MINOR = range(7)
+ADOPT_APPEARED, ADOPT_VANISHED = 1, 2
+DIFF_FIELDS = ("thresh", "min_weight", "min_voxels")
+ADOPT_FIELDS = ("which", "halo")
+DIFF_REGION_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("n_appeared", "<u8"), ("n_vanished", "<u8"),
+                              ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])     # hsk_diff_region
+
+
+def default_diff_params(tracker=None, **fields):
+    """the parameters of diff_volume (hsk_default_diff_params): thresh 16384 (half the truncation distance), min_weight 1,
+    min_voxels = default_prune_params' value for the tracker (without one: the default configuration's); the keywords -- thresh,
+    min_weight, min_voxels -- override its fields -> an `_lib.HskDiffParams`"""
+    p = _lib.HskDiffParams()
+    _lib.load().hsk_default_diff_params(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in DIFF_FIELDS:
+            raise TypeError(f"diff parameters have no field {name!r}")
+        setattr(p, name, int(val))
+    return p
 
 
 def default_fill_params(tracker=None, **fields):
@@ -930,6 +949,87 @@ class KinfuTracker:
         self._ck(self.lib.hsk_download_fill_mask(self.h, C.byref(b) if b is not None else None, out.ctypes.data if out.size else None))
         return out
 
+    # ---- volume differencing ----------------------------------------------------------------------------
+    def default_diff_params(self, **fields):
+        return default_diff_params(self, **fields)
+
+    def diff_volume(self, cur, params=None, **fields):
+        """what changed between this tracker's volume (the older scan, `ref`) and `cur`'s (the newer one) on the same grid
+        (hsk_diff_volume): per voxel a class -- DIFF_UNSEEN, ONLY_REF, ONLY_CUR, SAME, APPEARED, VANISHED --, the changed voxels
+        grouped into 6-connected regions, those below min_voxels turned into DIFF_MINOR.  params: an HskDiffParams (default:
+        default_diff_params(self)); the keywords override its fields -> (records, stats): a structured array with
+        DIFF_REGION_DTYPE -- root, n_voxels, n_appeared, n_vanished, the box lo, hi (exclusive) -- of the kept regions, ordered by
+        n_voxels descending, ties to the smaller root; stats: n_class [7], n_regions, n_minor_regions, largest.  The diff is held in
+        this tracker: download_diff, diff_at, adopt_diff.  A cur in another frame is resampled first (resampled_like).  The size
+        query and the fill diff once: the second call is answered from the held diff"""
+        p = default_diff_params(self) if params is None else _lib.HskDiffParams.from_buffer_copy(params)
+        for name, val in fields.items():
+            if name not in DIFF_FIELDS:
+                raise TypeError(f"diff parameters have no field {name!r}")
+            setattr(p, name, int(val))
+        n = C.c_size_t(0)
+        st = _lib.HskDiffStats()
+        self._ck(self.lib.hsk_diff_volume(self.h, cur.h, C.byref(p), None, 0, C.byref(n), C.byref(st)))
+        recs = np.zeros(n.value, DIFF_REGION_DTYPE)
+        if n.value:
+            self._ck(self.lib.hsk_diff_volume(self.h, cur.h, C.byref(p), recs.ctypes.data_as(C.POINTER(_lib.HskDiffRegion)), n.value, C.byref(n), C.byref(st)))
+        return recs, {"n_class": np.array(list(st.n_class), np.uint64), "n_regions": int(st.n_regions), "n_minor_regions": int(st.n_minor_regions),
+                      "largest": int(st.largest)}
+
+    def download_diff(self, box=None, region=True):
+        """the held diff over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_diff) ->
+        (cls [z, y, x] uint8, region [z, y, x] uint32 or None): a region is the root's (z vol_y + y) vol_x + x for APPEARED and
+        VANISHED voxels, COMPONENT_NONE elsewhere; refused once this tracker's volume has changed since the diff"""
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        cls = np.empty(shape, np.uint8)
+        reg = np.empty(shape, np.uint32) if region else None
+        b = self._voxel_box(box)
+        self._ck(self.lib.hsk_download_diff(self.h, C.byref(b) if b is not None else None, cls.ctypes.data if cls.size else None,
+                                            reg.ctypes.data if region and reg.size else None))
+        return cls, reg
+
+    def diff_at(self, xyz, radius=1):
+        """the held diff at the world points xyz [n, 3] (hsk_diff_at, 2^20 points a call): the nearest APPEARED or VANISHED voxel within
+        Chebyshev `radius` (0..4) of the point's voxel, else the voxel's own class -> (cls [n] uint8, region [n] uint32); a point
+        outside the grid gives DIFF_UNSEEN and COMPONENT_NONE"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        cls, reg = np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint32)
+        step = _lib.HSK_CLEAR_MAX_POINTS                    # (the call takes 2^20 points: a mesh's vertices go in pieces)
+        for at in range(0, max(len(pts), 1), step):
+            m = min(step, len(pts) - at)
+            self._ck(self.lib.hsk_diff_at(self.h, pts[at:].ctypes.data if m else None, m, int(radius), cls[at:].ctypes.data if m else None,
+                                          reg[at:].ctypes.data if m else None))
+        return cls, reg
+
+    def adopt_diff(self, cur, which=ADOPT_APPEARED | ADOPT_VANISHED, halo=2):
+        """takes cur's words (and colour) where a kept region of the held diff says the scene changed (hsk_adopt_diff): every voxel
+        cur has observed within Chebyshev `halo` (0..8) of a kept region's voxels of the classes `which` selects; a following
+        fuse_volume(cur) then merges without ghosts -> dict: n_targets, n_adopted, n_colored"""
+        p = _lib.HskAdoptParams(int(which), int(halo))
+        st = _lib.HskAdoptStats()
+        self._ck(self.lib.hsk_adopt_diff(self.h, cur.h, C.byref(p), C.byref(st)))
+        return {"n_targets": int(st.n_targets), "n_adopted": int(st.n_adopted), "n_colored": int(st.n_colored)}
+
+    def release_diff(self):
+        """frees the held diff and its scratch (hsk_release_diff)"""
+        self._ck(self.lib.hsk_release_diff(self.h))
+
+    def resampled_like(self, ref, cur_to_ref=None, color=False):
+        """this tracker's volume on ref's grid: a new tracker with ref's configuration, and this volume fused into it with the
+        rigid matrix cur_to_ref [4, 4] (None: the identity) -- into an empty volume fusion gives exactly the sampled words; color:
+        the new tracker gets a colour volume first, which the fusion fills when this tracker has colour -> the new tracker (the
+        caller closes it); what ref.diff_volume takes of a scan made in another frame or at another resolution"""
+        out = KinfuTracker(ref.cfg)
+        try:
+            if color:
+                out.enable_color()
+            out.fuse_from(self, np.eye(4, dtype=np.float32) if cur_to_ref is None else cur_to_ref)
+        except Exception:
+            out.close()
+            raise
+        return out
+
     # ---- clearance field ---------------------------------------------------------------------------------
     def default_clearance_params(self, **fields):
         return default_clearance_params(self, **fields)
@@ -1679,6 +1779,28 @@ def synth_sensor_frames(count, first=0, seed=1234, sigma_mm=1.2, range_cut_m=3.5
     else:
         poses = [synth_room_pose(room, k, scan) for k in range(first, first + count)]
     return poses, [synth_sensor_depth(p, -1 if room is None else room, seed + first + i, sigma_mm, range_cut_m, absorbing)[0] for i, p in enumerate(poses)]
+
+
+def synth_box_depth(depth, pose, lo, hi, fx=525.0, fy=525.0, cx=319.5, cy=239.5):
+    """a depth frame with an axis-aligned box lo .. hi (metres, in the frame of `pose`) composited in: per pixel min(depth, the
+    box's depth along the pixel's ray), a pixel without depth (0) taking the box's -> uint16 millimetres.  What a second scan of
+    a room with a new object in it looks like (tools/diff_demo.py)"""
+    d = np.asarray(depth)
+    h, w = d.shape
+    m = np.asarray(pose, np.float64).reshape(4, 4)
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    ray = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], axis=-1) @ m[:3, :3].T      # world direction per unit of depth
+    t0, t1 = np.zeros((h, w)), np.full((h, w), np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for ax in range(3):
+            a, b = (lo[ax] - m[ax, 3]) / ray[..., ax], (hi[ax] - m[ax, 3]) / ray[..., ax]
+            t0, t1 = np.maximum(t0, np.minimum(a, b)), np.minimum(t1, np.maximum(a, b))
+    mm = np.rint(t0 * 1000.0)
+    hit = (t0 <= t1) & (t0 > 1e-9) & (mm >= 1) & (mm <= 65535)
+    out = d.copy()
+    take = hit & ((d == 0) | (mm < d))
+    out[take] = mm[take].astype(np.uint16)
+    return out
 
 
 def synth_room_extents(variant):

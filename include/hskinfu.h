@@ -955,6 +955,113 @@ int hsk_fill_holes(hsk_ctx* k, const hsk_fill_params* params, const hsk_voxel_bo
  * the volume as it stands". */
 int hsk_download_fill_mask(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* mask);
 
+/* ---- Volume differencing: what changed between two scans of the same place, and the call that adopts it (DESIGN.md 3.23 the
+ * kernels, 8q the rule; tests/diff_twin.py restates the rule in numpy).  hsk_fuse_volume merges two sessions by a weighted mean:
+ * a chair that was moved becomes two half-weight ghosts.  hsk_diff_volume says where the scene changed; hsk_adopt_diff takes the
+ * newer scan's words there, so that a following hsk_fuse_volume merges without ghosts.  All integers.
+ * INPUTS.  `ref` is the older scan -- the result lives in it, on its grid --, `cur` the newer one.  Both are whole volumes on the
+ * SAME GRID: equal dims, size_m bit-equal, effective truncation distance bit-equal, same device.  A cur in another frame or at
+ * another resolution is resampled first: create an empty context with ref's configuration and hsk_fuse_volume(empty, cur,
+ * cur_to_ref) -- into an empty destination the fusion rule gives exactly the sampled word; this rule samples nothing.  Both
+ * contexts' deferred free-space weights are written back first, as hsk_fuse_volume does.
+ * PER VOXEL (z < vol_z), with the words (raw_a, W_a) of ref and (raw_b, W_b) of cur: r = max(raw, -32767) -- a raw of -32768
+ * counts as -32767; the word is never rewritten --; a voxel is observed in a volume iff W >= min_weight; d = r_b - r_a:
+ *   HSK_DIFF_UNSEEN    observed in neither            HSK_DIFF_ONLY_REF  in ref only          HSK_DIFF_ONLY_CUR  in cur only
+ *   HSK_DIFF_SAME      in both, -thresh < d < thresh
+ *   HSK_DIFF_APPEARED  in both, d <= -thresh (matter came nearer: something is there now)
+ *   HSK_DIFF_VANISHED  in both, d >= thresh
+ *   HSK_DIFF_MINOR     APPEARED or VANISHED, but in a region below min_voxels
+ * REGIONS.  CHANGED = APPEARED + VANISHED, before the MINOR step.  Two CHANGED voxels are adjacent when they differ by 1 on
+ * exactly one axis (the components' 6-neighbourhood); a region is a connected component of CHANGED whatever the mix of its two
+ * classes -- a thing pushed 10 cm is one region with both counts --, its label the smallest lin(x, y, z) = (z vol_y + y) vol_x + x
+ * among its voxels.  A region with n_voxels >= min_voxels is KEPT; every voxel of any other region gets the class MINOR.  Records
+ * exist for kept regions only, ordered by n_voxels descending, ties to the smaller root.  More than HSK_COMPONENT_MAX regions in
+ * all: HSK_ERR_ARG, nothing held.
+ * DEFAULTS: thresh = 16384, half the truncation distance; min_weight = 1; min_voxels = hsk_default_prune_params' value, the
+ * voxels of a cube of edge 4 tau.  Stated choices, not measurements -- set other values where they do not fit.  Ranges: thresh
+ * 1..65534, min_weight 1..128, min_voxels >= 1.
+ * KNOWN PROPERTY: the TSDF's slope is one tau per tau, so a residual misalignment of delta along a surface normal moves the values
+ * by delta / tau.  At the default thresh a static wall stays SAME up to delta < tau / 2 (with tau = 2.1 cells: shifts of 0.5, 1.0
+ * and 1.04 cells give no CHANGED voxel, 1.1 cells flood the wall); beyond that the whole wall becomes one large region.  The
+ * remedy is a better matrix (hsk_align_volume) or a larger thresh.
+ * ADOPT.  T = the voxels of kept regions whose class `which` selects (a mask of HSK_ADOPT_APPEARED and HSK_ADOPT_VANISHED; the
+ * default is both).  The adopt set S = every voxel with W_b != 0 within Chebyshev distance `halo` (0..8, default 2: the cells of
+ * the crossing and the neighbours a normal's central difference reads; clipped at the grid) of a voxel of T.  Every voxel of S
+ * gets cur's word as it is, raw and weight; when both contexts have colour also cur's colour word; when only ref has colour the
+ * colour word 0 (prune's convention).  Every other word of ref, every other colour word and all of cur stay bit for bit.  When S
+ * is empty nothing is written and cached passes stay valid; otherwise the write follows hsk_prune_components' order and the held
+ * diff is no longer valid.  The pose and the model maps are not touched.
+ * KNOWN PROPERTY: the inside of a vanished object, which ref never observed, stays never-observed beyond the halo.  A following
+ * hsk_fuse_volume(ref, cur) takes it from cur (where the destination's weight is 0 the fusion rule is a copy), or hsk_fill_holes
+ * closes it.  With halo >= 1 ref's zero crossings become cur's and ref equals cur on every voxel both observe; with halo = 0
+ * neither holds (the voxels next to a region keep ref's values), though differencing again finds no CHANGED voxel either way.
+ * VALIDITY.  The diff is held in ref for (ref's volume, cur's identity, cur's volume).  hsk_download_diff and hsk_diff_at need
+ * ref unchanged since, hsk_adopt_diff both unchanged and cur to be the context the diff was made with; otherwise HSK_ERR_STATE
+ * "<call>: no diff is held for the volume as it stands" (for the volumes as they stand).
+ * The scratch -- 2.5 times the volume's bytes: the class words, a labelling of its own (never hsk_label_components', whose
+ * labels_reused keeps its meaning) and two byte volumes for the adopt set -- is made by the first call that diffs, NOT by
+ * hsk_prepare_readout (which only loads the kernels), and freed by hsk_release_diff or hsk_destroy.
+ * hsk_download_diff and hsk_diff_at work through the grow-only product buffer of the read-outs: a whole-volume download with
+ * labels grows it to 5 bytes a voxel (671 MB at 512^3), which stays allocated beside the scratch until hsk_destroy.
+ * HSK_ERR_ARG: a NULL argument, ref == cur, unequal grids or truncation distances ("... resample cur first: hsk_fuse_volume into
+ * an empty context of ref's configuration"), another device, more than 2^31 voxels, a parameter out of range.  HSK_ERR_STATE:
+ * frames in flight in either context, a slab of a group or a context that stores part of its volume, no valid diff held.  A
+ * refused call writes nothing. */
+#define HSK_DIFF_UNSEEN 0
+#define HSK_DIFF_ONLY_REF 1
+#define HSK_DIFF_ONLY_CUR 2
+#define HSK_DIFF_SAME 3
+#define HSK_DIFF_APPEARED 4
+#define HSK_DIFF_VANISHED 5
+#define HSK_DIFF_MINOR 6
+#define HSK_ADOPT_APPEARED 1
+#define HSK_ADOPT_VANISHED 2
+typedef struct hsk_diff_params {
+  int32_t thresh, min_weight;
+  uint64_t min_voxels;
+} hsk_diff_params;        /* 16 bytes */
+typedef struct hsk_diff_region {
+  int32_t root[3], pad;   /* x, y, z of the root                                                                                */
+  uint64_t n_voxels, n_appeared, n_vanished;
+  int32_t lo[3], hi[3];   /* the voxel bounding box, hi exclusive                                                               */
+} hsk_diff_region;        /* 64 bytes */
+typedef struct hsk_diff_stats {
+  uint64_t n_class[7];    /* the voxels by final class: APPEARED and VANISHED of kept regions only, the others' under MINOR     */
+  uint64_t n_regions;     /* kept                                                                                               */
+  uint64_t n_minor_regions, largest;   /* the regions below min_voxels; the voxels of the first record                         */
+} hsk_diff_stats;         /* 80 bytes */
+typedef struct hsk_adopt_params {
+  int32_t which, halo;
+} hsk_adopt_params;       /* 8 bytes */
+typedef struct hsk_adopt_stats {
+  uint64_t n_targets;     /* |T|                                                                                                */
+  uint64_t n_adopted;     /* |S|                                                                                                */
+  uint64_t n_colored;     /* the voxels of S that got cur's colour word (both contexts have colour; else 0)                    */
+} hsk_adopt_stats;        /* 24 bytes */
+/* the defaults described above for the context's cells and truncation distance; k NULL: hsk_default_config(256)'s */
+void hsk_default_diff_params(const hsk_ctx* k, hsk_diff_params* p);
+/* Diffs cur against ref (params NULL: the defaults), holds the result in ref and gives the records in their order.  recs NULL: the
+ * counts only (*n_regions, stats).  HSK_ERR_ARG with *n_regions and stats set and no record written: cap below the count (the
+ * diff is held all the same).  stats may be NULL.  While both volumes stand, a further call with the same cur and the same
+ * parameters launches nothing and gives the held records and stats: the size query followed by the fill diffs once. */
+int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params* params, hsk_diff_region* recs, size_t cap, size_t* n_regions,
+                    hsk_diff_stats* stats);
+/* The voxels of the box (NULL: the whole volume), row-major, x fastest: cls = one HSK_DIFF_* byte each; region (may be NULL) =
+ * the region's root lin for APPEARED and VANISHED voxels, HSK_COMPONENT_NONE elsewhere, MINOR included.  HSK_ERR_ARG: lo < 0,
+ * hi > the volume's dims or hi < lo on an axis.  An empty box writes nothing. */
+int hsk_download_diff(hsk_ctx* ref, const hsk_voxel_box* box, uint8_t* cls, uint32_t* region);
+/* The diff at n <= 2^20 world points (x, y, z triples) -- what tints a cloud or a mesh: a surface point of a new object lies
+ * inside its APPEARED shell.  A point's voxel is found as hsk_clearance_at finds it; a point outside the grid gives
+ * HSK_DIFF_UNSEEN and HSK_COMPONENT_NONE.  Candidates are the voxels within Chebyshev `radius` (0..4) of that voxel whose class
+ * is APPEARED or VANISHED; the result is the candidate with the smallest (dx^2 + dy^2 + dz^2, lin), its class and its region;
+ * with no candidate the own voxel's class and HSK_COMPONENT_NONE.  region may be NULL. */
+int hsk_diff_at(hsk_ctx* ref, const float* xyz, size_t n, int radius, uint8_t* cls, uint32_t* region);
+/* Adopts cur's words by the rule above (params NULL: which = both, halo = 2).  stats may be NULL.  HSK_ERR_ARG: which outside
+ * 1..3, halo outside 0..8. */
+int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params* params, hsk_adopt_stats* stats);
+/* frees the held diff and its scratch (the next hsk_diff_volume makes it again); HSK_ERR_ARG: a NULL context */
+int hsk_release_diff(hsk_ctx* ref);
+
 /* ---- Clearance field: how much room there is -- the exact distance from every voxel to the nearest obstacle, on the device
  * (DESIGN.md 3.18 the kernels, 8l the rule; tests/clearance_twin.py restates the rule in numpy).  All integers.  A voxel is an
  * OBSTACLE when it is the coverage rule's SOLID (observed with a TSDF <= 0); with the flag HSK_CLEAR_UNKNOWN so is every UNSEEN
