@@ -77,11 +77,11 @@ int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who,
   return HSK_OK;
 }
 
-int clear_state_check(hsk_ctx* k, const char* who) {
-  if (int rs = require_whole_volume(k, k, who)) return rs;
-  if (int ri = require_idle(k)) return ri;
+int volume_state_check(hsk_ctx* k, hsk_ctx* errs, const char* who) {
+  if (int rs = require_whole_volume(k, errs, who)) return rs;
+  if (int ri = require_idle(k, errs)) return ri;
   if ((uint64_t)k->vp.X * (uint64_t)k->vp.Y * (uint64_t)k->vp.Z > ((uint64_t)1 << 31))
-    return fail(k, HSK_ERR_ARG, (std::string(who) + ": the volume has more than 2^31 voxels").c_str());
+    return fail(errs, HSK_ERR_ARG, (std::string(who) + ": the volume has more than 2^31 voxels").c_str());
   return HSK_OK;
 }
 
@@ -111,16 +111,29 @@ int clear_floor_grid(hsk_ctx* k, const ClearGeom& q, int axis, int lo, int hi, c
   return HSK_OK;
 }
 
-int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*)>& launch) {
+int download_rows(hsk_ctx* k, const void* field, size_t elem_bytes, const hsk_voxel_box& b, size_t n, void* out) {
+  if (n == 0) return HSK_OK;
+  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, out, field, n * elem_bytes);
+  int r = ensure_product_bytes(k, n * elem_bytes);
+  if (r != HSK_OK) return r;
+  launch_box_rows(k->stream, field, elem_bytes, k->vp, b.lo, b.hi, n, k->d_out);
+  HIPCHK(k, hipGetLastError());
+  return copy_out(k, out, k->d_out, n * elem_bytes);
+}
+
+int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*, unsigned char*)>& launch,
+                  uint8_t* bytes) {
   ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4);
+  const size_t pts_at = lay.take(n * 12), out_at = lay.take(n * 4), bytes_at = lay.take(bytes ? n : 0);
   int r = ensure_product_bytes(k, lay.bytes);
   if (r != HSK_OK) return r;
   char* base = (char*)k->d_out;
   HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch((const float*)(base + pts_at), (unsigned*)(base + out_at));
+  launch((const float*)(base + pts_at), (unsigned*)(base + out_at), bytes ? (unsigned char*)(base + bytes_at) : nullptr);
   HIPCHK(k, hipGetLastError());
-  return copy_out(k, out, base + out_at, n * 4);
+  if (bytes) r = copy_out(k, bytes, base + bytes_at, n);
+  if (r == HSK_OK && out) r = copy_out(k, out, base + out_at, n * 4);
+  return r;
 }
 
 void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
@@ -164,7 +177,7 @@ extern "C" int hsk_build_clearance(hsk_ctx* k, const hsk_clearance_params* param
   hsk_clearance_params p;
   ClearGeom q;
   if (int rc = clear_check(k, params, "hsk_build_clearance", &p, &q)) return rc;
-  if (int rc = clear_state_check(k, "hsk_build_clearance")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_build_clearance")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   bool reused = false;
   int r = clear_build(k, p, q, &reused);
@@ -191,20 +204,14 @@ extern "C" int hsk_download_clearance(hsk_ctx* k, const hsk_clearance_params* pa
   hsk_voxel_box b;
   size_t n;
   if (int rc = clear_box_check(k, box, "hsk_download_clearance", &b, &n)) return rc;
-  if (int rc = clear_state_check(k, "hsk_download_clearance")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_download_clearance")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   bool reused = false;
   int r = clear_build(k, p, q, &reused);
   if (r != HSK_OK) return r;
   ClearBufs cb;
   clear_layout(k->vp, k->d_clear, &cb);
-  if (n == 0) return HSK_OK;
-  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, d2, cb.field, n * 4);
-  r = ensure_product_bytes(k, n * 4);
-  if (r != HSK_OK) return r;
-  launch_clear_box(k->stream, cb.field, k->vp, b.lo, b.hi, (unsigned*)k->d_out);
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, d2, k->d_out, n * 4);
+  return download_rows(k, cb.field, 4, b, n, d2);
 }
 
 extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, const float* xyz, size_t n, uint32_t* d2) {
@@ -214,7 +221,7 @@ extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, 
   hsk_clearance_params p;
   ClearGeom q;
   if (int rc = clear_check(k, params, "hsk_clearance_at", &p, &q)) return rc;
-  if (int rc = clear_state_check(k, "hsk_clearance_at")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_clearance_at")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   bool reused = false;
@@ -222,7 +229,7 @@ extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, 
   if (r != HSK_OK) return r;
   ClearBufs cb;
   clear_layout(k->vp, k->d_clear, &cb);
-  return gather_points(k, xyz, n, d2, [&](const float* pts, unsigned* out) { launch_clear_gather(k->stream, cb.field, k->vp, pts, (unsigned)n, out); });
+  return gather_points(k, xyz, n, d2, [&](const float* pts, unsigned* out, unsigned char*) { launch_clear_gather(k->stream, cb.field, k->vp, pts, (unsigned)n, out); });
 }
 
 extern "C" int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* params, int axis, int lo, int hi, uint32_t* map, hsk_clearance_stats* stats) {
@@ -233,7 +240,7 @@ extern "C" int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* param
   if (int rc = clear_check(k, params, "hsk_clearance_floor", &p, &q)) return rc;
   FloorGrid f;
   if (int rc = clear_floor_grid(k, q, axis, lo, hi, "hsk_clearance_floor", &f)) return rc;
-  if (int rc = clear_state_check(k, "hsk_clearance_floor")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_clearance_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   const size_t n = (size_t)f.nu * f.nv;
   ProductLayout lay;

@@ -34,15 +34,6 @@ extern "C" void hsk_default_prune_params(const hsk_ctx* k, hsk_prune_params* p) 
   p->fill = HSK_PRUNE_UNSEEN;
 }
 
-// the state the three calls need, in require_whole_volume's and require_idle's words; and a volume lin can number
-static int comp_state_check(hsk_ctx* k, const char* who) {
-  if (int rs = require_whole_volume(k, k, who)) return rs;
-  if (int ri = require_idle(k)) return ri;
-  if ((uint64_t)k->vp.X * (uint64_t)k->vp.Y * (uint64_t)k->vp.Z > ((uint64_t)1 << 31))
-    return fail(k, HSK_ERR_ARG, (std::string(who) + ": the volume has more than 2^31 voxels").c_str());
-  return HSK_OK;
-}
-
 int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want) {
   if (*have >= want) return HSK_OK;
   if (*buf) HIPCHK(k, hipFree(*buf));
@@ -144,7 +135,7 @@ extern "C" int hsk_label_components(hsk_ctx* k, hsk_component* recs, size_t cap,
   static_assert(sizeof(hsk_component_stats) == 32 && sizeof(hsk_prune_params) == 16 && sizeof(hsk_prune_stats) == 32, "the components' structs");
   if (!k) return HSK_ERR_ARG;
   if (!n_components) return fail(k, HSK_ERR_ARG, "hsk_label_components: n_components is null");
-  if (int rc = comp_state_check(k, "hsk_label_components")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_label_components")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   size_t n = 0;
   bool reused = false;
@@ -171,7 +162,7 @@ extern "C" int hsk_label_components(hsk_ctx* k, hsk_component* recs, size_t cap,
 extern "C" int hsk_download_components(hsk_ctx* k, uint32_t* labels) {
   if (!k) return HSK_ERR_ARG;
   if (!labels) return fail(k, HSK_ERR_ARG, "hsk_download_components: labels is null");
-  if (int rc = comp_state_check(k, "hsk_download_components")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_download_components")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   size_t n = 0;
   bool reused = false;
@@ -197,7 +188,7 @@ extern "C" int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, 
     hsk_default_prune_params(k, &p);
   if (p.keep_largest < 0 || p.keep_largest > 4096) return fail(k, HSK_ERR_ARG, "hsk_prune_components: keep_largest must lie in 0..4096");
   if (p.fill != HSK_PRUNE_UNSEEN && p.fill != HSK_PRUNE_FREE) return fail(k, HSK_ERR_ARG, "hsk_prune_components: fill is neither HSK_PRUNE_UNSEEN nor HSK_PRUNE_FREE");
-  if (int rc = comp_state_check(k, "hsk_prune_components")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_prune_components")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   size_t n = 0;
   bool reused = false;

@@ -31,14 +31,6 @@ extern "C" void hsk_default_diff_params(const hsk_ctx* k, hsk_diff_params* p) {
   p->min_voxels = pp.min_voxels;
 }
 
-// the state a diff call needs of one context, reported in `errs`
-static int diff_state_check(hsk_ctx* k, hsk_ctx* errs, const char* who) {
-  if (int rs = require_whole_volume(k, errs, who)) return rs;
-  if (int ri = require_idle(k, errs)) return ri;
-  if ((uint64_t)k->vp.X * (uint64_t)k->vp.Y * (uint64_t)k->vp.Z > ((uint64_t)1 << 31))
-    return fail(errs, HSK_ERR_ARG, (std::string(who) + ": the volume has more than 2^31 voxels").c_str());
-  return HSK_OK;
-}
 // a diff is held for ref's volume as it stands
 static int diff_held_check(hsk_ctx* ref, const char* who) {
   if (!ref->d_diff || ref->diff_key[0] == 0 || ref->diff_key[0] != ref->vol_epoch)
@@ -63,6 +55,17 @@ static DiffTab diff_tab(const hsk_ctx* k, size_t n) {
   return t;
 }
 
+// hsk_diff_volume's answer from the held records and stats
+static int diff_reply(hsk_ctx* k, hsk_diff_region* recs, size_t cap, size_t* n_regions, hsk_diff_stats* stats) {
+  const size_t n = k->diff_recs.size();
+  *n_regions = n;
+  if (stats) *stats = k->diff_stats;
+  if (!recs) return HSK_OK;
+  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
+  if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
+  return HSK_OK;
+}
+
 extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params* params, hsk_diff_region* recs, size_t cap, size_t* n_regions,
                                hsk_diff_stats* stats) {
   if (!ref) return HSK_ERR_ARG;
@@ -79,7 +82,7 @@ extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params
   if (p.min_weight < 1 || p.min_weight > 128) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: min_weight must lie in 1..128");
   if (p.min_voxels < 1) return fail(ref, HSK_ERR_ARG, "hsk_diff_volume: min_voxels must be at least 1");
   for (hsk_ctx* c : {ref, cur})
-    if (int rc = diff_state_check(c, ref, "hsk_diff_volume")) return rc;
+    if (int rc = volume_state_check(c, ref, "hsk_diff_volume")) return rc;
   if (ref->vp.X != cur->vp.X || ref->vp.Y != cur->vp.Y || ref->vp.Z != cur->vp.Z || memcmp(ref->cfg.vol_size_m, cur->cfg.vol_size_m, 3 * sizeof(float)) != 0 ||
       memcmp(&ref->vp.tau, &cur->vp.tau, sizeof(float)) != 0)
     return fail(ref, HSK_ERR_ARG,
@@ -91,15 +94,7 @@ extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params
   // launched; the records and stats are the held ones (what a size query followed by the fill costs once, as the labelling's)
   const bool held = k->d_diff && k->diff_key[0] != 0 && k->diff_key[0] == k->vol_epoch && k->diff_key[1] == cur->serial && k->diff_key[2] == cur->vol_epoch &&
                     memcmp(&k->diff_params, &p, sizeof(p)) == 0;
-  if (held) {
-    const size_t n = k->diff_recs.size();
-    *n_regions = n;
-    if (stats) *stats = k->diff_stats;
-    if (!recs) return HSK_OK;
-    if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
-    if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
-    return HSK_OK;
-  }
+  if (held) return diff_reply(k, recs, cap, n_regions, stats);
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // cur: read only.  Its deferred weights are written back; everything its stream holds must have ended before ref's stream reads it
   flush_weights(cur);
@@ -199,13 +194,7 @@ extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params
   k->diff_key[0] = k->vol_epoch;
   k->diff_key[1] = cur->serial;
   k->diff_key[2] = cur->vol_epoch;
-  const size_t n = k->diff_recs.size();
-  *n_regions = n;
-  if (stats) *stats = st;
-  if (!recs) return HSK_OK;
-  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
-  if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
-  return HSK_OK;
+  return diff_reply(k, recs, cap, n_regions, stats);
 }
 
 extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* cls, uint32_t* region) {
@@ -214,7 +203,7 @@ extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* 
   size_t n;
   if (int rc = clear_box_check(k, box, "hsk_download_diff", &bx, &n)) return rc;
   if (n > 0 && !cls) return fail(k, HSK_ERR_ARG, "hsk_download_diff: cls is null");
-  if (int rc = diff_state_check(k, k, "hsk_download_diff")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_download_diff")) return rc;
   if (int rc = diff_held_check(k, "hsk_download_diff")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
@@ -237,23 +226,14 @@ extern "C" int hsk_diff_at(hsk_ctx* k, const float* xyz, size_t n, int radius, u
   if (n > 0 && (!xyz || !cls)) return fail(k, HSK_ERR_ARG, "hsk_diff_at: null argument");
   if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_diff_at: more than 2^20 points");
   if (radius < 0 || radius > 4) return fail(k, HSK_ERR_ARG, "hsk_diff_at: radius must lie in 0..4");
-  if (int rc = diff_state_check(k, k, "hsk_diff_at")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_diff_at")) return rc;
   if (int rc = diff_held_check(k, "hsk_diff_at")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), region_at = lay.take(n * 4), cls_at = lay.take(n);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
   DiffBufs b;
   diff_layout(k->vp, k->d_diff, &b);
-  char* base = (char*)k->d_out;
-  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch_diff_gather(k->stream, k->vp, b, (const float*)(base + pts_at), (unsigned)n, radius, (unsigned*)(base + region_at), (unsigned char*)(base + cls_at));
-  HIPCHK(k, hipGetLastError());
-  r = copy_out(k, cls, base + cls_at, n);
-  if (r == HSK_OK && region) r = copy_out(k, region, base + region_at, n * 4);
-  return r;
+  return gather_points(
+      k, xyz, n, region, [&](const float* pts, unsigned* reg, unsigned char* c) { launch_diff_gather(k->stream, k->vp, b, pts, (unsigned)n, radius, reg, c); }, cls);
 }
 
 extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params* params, hsk_adopt_stats* stats) {
@@ -267,7 +247,7 @@ extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params
   if (p.which < 1 || p.which > 3) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: which must be HSK_ADOPT_APPEARED, HSK_ADOPT_VANISHED or both");
   if (p.halo < 0 || p.halo > 8) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: halo must lie in 0..8");
   for (hsk_ctx* c : {ref, cur})
-    if (int rc = diff_state_check(c, ref, "hsk_adopt_diff")) return rc;
+    if (int rc = volume_state_check(c, ref, "hsk_adopt_diff")) return rc;
   if (int rc = diff_held_check(ref, "hsk_adopt_diff")) return rc;
   if (ref->diff_key[1] != cur->serial || ref->diff_key[2] != cur->vol_epoch)
     return fail(ref, HSK_ERR_STATE, "hsk_adopt_diff: no diff is held for the volumes as they stand (cur is another context, or its volume has changed)");

@@ -47,7 +47,7 @@ extern "C" int hsk_fill_holes(hsk_ctx* k, const hsk_fill_params* params, const h
   hsk_voxel_box b;
   size_t n_box;
   if (int rc = clear_box_check(k, box, "hsk_fill_holes", &b, &n_box)) return rc;
-  if (int rc = clear_state_check(k, "hsk_fill_holes")) return rc;  // (prune's refusals: in flight, a slab, more than 2^31 voxels)
+  if (int rc = volume_state_check(k, k, "hsk_fill_holes")) return rc;  // (prune's refusals: in flight, a slab, more than 2^31 voxels)
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   k->fill_epoch = 0;  // (the scratch is about to be written: the mask of an earlier fill goes)
   int r = ensure_grown(k, &k->d_fill, &k->fill_bytes, fill_layout(k->vp, nullptr, nullptr));
@@ -101,15 +101,10 @@ extern "C" int hsk_download_fill_mask(hsk_ctx* k, const hsk_voxel_box* box, uint
   size_t n;
   if (int rc = clear_box_check(k, box, "hsk_download_fill_mask", &b, &n)) return rc;
   if (n > 0 && !mask) return fail(k, HSK_ERR_ARG, "hsk_download_fill_mask: mask is null");
-  if (int rc = clear_state_check(k, "hsk_download_fill_mask")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_download_fill_mask")) return rc;
   if (!k->d_fill || k->fill_epoch == 0 || k->fill_epoch != k->vol_epoch)
     return fail(k, HSK_ERR_STATE, "hsk_download_fill_mask: no fill is held for the volume as it stands");
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, mask, k->fill_mask, n);
-  int r = ensure_product_bytes(k, n);
-  if (r != HSK_OK) return r;
-  launch_fill_mask_box(k->stream, k->fill_mask, k->vp, b.lo, b.hi, n, (unsigned char*)k->d_out);
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, mask, k->d_out, n);
+  return download_rows(k, k->fill_mask, 1, b, n, mask);
 }

@@ -205,7 +205,7 @@ extern "C" int hsk_build_partition(hsk_ctx* k, const hsk_clearance_params* cpara
   if (recs && !n_rooms) return fail(k, HSK_ERR_ARG, "hsk_build_partition: n_rooms is null");
   if (int rc = clear_check(k, cparams, "hsk_build_partition", &cp, &cq)) return rc;
   if (int rc = part_check(k, cp, params, "hsk_build_partition", &p)) return rc;
-  if (int rc = clear_state_check(k, "hsk_build_partition")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_build_partition")) return rc;
   uint32_t key[9];
   clear_key_of(cp, key);
   key[5] = p.core_d2;
@@ -263,7 +263,7 @@ extern "C" int hsk_build_partition(hsk_ctx* k, const hsk_clearance_params* cpara
 
 // the reads: a partition must be held
 static int part_held(hsk_ctx* k, const char* who) {
-  if (int rc = clear_state_check(k, who)) return rc;
+  if (int rc = volume_state_check(k, k, who)) return rc;
   if (!(k->d_part && k->part_epoch != 0 && k->part_epoch == k->vol_epoch))
     return fail(k, HSK_ERR_STATE, (std::string(who) + ": no partition of the volume as it stands is held (hsk_build_partition makes one)").c_str());
   return HSK_OK;
@@ -319,7 +319,7 @@ extern "C" int hsk_partition_at(hsk_ctx* k, const float* xyz, size_t n, int radi
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   PartBufs pb;
   part_layout(k->part_q, k->d_part, &pb);
-  return gather_points(k, xyz, n, ids, [&](const float* pts, unsigned* out) {
+  return gather_points(k, xyz, n, ids, [&](const float* pts, unsigned* out, unsigned char*) {
     launch_part_gather(k->stream, k->part_q, pb, (unsigned)k->part_recs.size(), k->vp, pts, (unsigned)n, radius, out);
   });
 }
@@ -337,7 +337,7 @@ extern "C" int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cpara
   if (int rc = part_check(k, cp, params, "hsk_partition_floor", &p)) return rc;
   FloorGrid f;
   if (int rc = clear_floor_grid(k, cq, axis, lo, hi, "hsk_partition_floor", &f)) return rc;
-  if (int rc = clear_state_check(k, "hsk_partition_floor")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_partition_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // the map's grid: (u, v, 1), u the lower-numbered remaining axis; the same kernels, on which nothing ever crosses the third axis
   // (its neighbours lie outside the grid): the cores are 4-connected, the moves the 8 in-plane ones

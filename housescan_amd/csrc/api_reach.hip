@@ -125,7 +125,7 @@ extern "C" int hsk_build_reach(hsk_ctx* k, const hsk_clearance_params* cparams, 
   hsk_reach_params p;
   if (int rc = clear_check(k, cparams, "hsk_build_reach", &cp, &cq)) return rc;
   if (int rc = reach_check(k, cp, params, seeds_xyz, n_seeds, "hsk_build_reach", &p)) return rc;
-  if (int rc = clear_state_check(k, "hsk_build_reach")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_build_reach")) return rc;
   // the seeds' voxels: a point outside the grid, or with a NaN, is dropped here; one on a voxel that is not passable on the device
   const SampleVol sv = hsk_sample_vol(k->vp);
   std::vector<uint32_t> vox;
@@ -179,7 +179,7 @@ extern "C" int hsk_build_reach(hsk_ctx* k, const hsk_clearance_params* cparams, 
 
 // the reads: a field must be held
 static int reach_held(hsk_ctx* k, const char* who) {
-  if (int rc = clear_state_check(k, who)) return rc;
+  if (int rc = volume_state_check(k, k, who)) return rc;
   if (!(k->d_reach && k->reach_epoch != 0 && k->reach_epoch == k->vol_epoch))
     return fail(k, HSK_ERR_STATE, (std::string(who) + ": no reach field of the volume as it stands is held (hsk_build_reach makes one)").c_str());
   return HSK_OK;
@@ -195,13 +195,7 @@ extern "C" int hsk_download_reach(hsk_ctx* k, const hsk_voxel_box* box, uint32_t
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ReachBufs rb;
   reach_layout(k->reach_q, k->d_reach, &rb);
-  if (n == 0) return HSK_OK;
-  if (n == (size_t)k->vp.X * k->vp.Y * k->vp.Z) return copy_out(k, g, rb.field, n * 4);
-  int r = ensure_product_bytes(k, n * 4);
-  if (r != HSK_OK) return r;
-  launch_clear_box(k->stream, rb.field, k->vp, b.lo, b.hi, (unsigned*)k->d_out);
-  HIPCHK(k, hipGetLastError());
-  return copy_out(k, g, k->d_out, n * 4);
+  return download_rows(k, rb.field, 4, b, n, g);
 }
 
 extern "C" int hsk_reach_at(hsk_ctx* k, const float* xyz, size_t n, uint32_t* g) {
@@ -214,7 +208,7 @@ extern "C" int hsk_reach_at(hsk_ctx* k, const float* xyz, size_t n, uint32_t* g)
   ReachBufs rb;
   reach_layout(k->reach_q, k->d_reach, &rb);
   // (the clearance field's gather: OUTSIDE is the same word)
-  return gather_points(k, xyz, n, g, [&](const float* pts, unsigned* out) { launch_clear_gather(k->stream, rb.field, k->vp, pts, (unsigned)n, out); });
+  return gather_points(k, xyz, n, g, [&](const float* pts, unsigned* out, unsigned char*) { launch_clear_gather(k->stream, rb.field, k->vp, pts, (unsigned)n, out); });
 }
 
 extern "C" int hsk_reach_path(hsk_ctx* k, const float goal_xyz[3], int32_t* voxels_xyz, size_t cap, size_t* n) {
@@ -280,7 +274,7 @@ extern "C" int hsk_reach_floor(hsk_ctx* k, const hsk_clearance_params* cparams, 
   if (int rc = reach_check(k, cp, params, seeds_xyz, n_seeds, "hsk_reach_floor", &p)) return rc;
   FloorGrid f;
   if (int rc = clear_floor_grid(k, cq, axis, lo, hi, "hsk_reach_floor", &f)) return rc;
-  if (int rc = clear_state_check(k, "hsk_reach_floor")) return rc;
+  if (int rc = volume_state_check(k, k, "hsk_reach_floor")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // the map's grid: (u, v, 1), u the lower-numbered remaining axis; the same kernels, on which no move along the third axis is
   // ever allowed (its neighbours lie outside the grid)

@@ -16,8 +16,8 @@
 // that serves every legal reach: a tile of 64 lanes with its halo fits 64 KiB of LDS only up to a reach of 96, short of the 170 of
 // a 512^3 volume's default metre; DESIGN.md 3.18 has both forms measured (tools/clearance_axis_forms.hip) where the tile fits.
 // The z pass writes the field and adds n_far and max_d2_seen, wave-reduced first.
-// k_clear_project, k_clear_axis_plain, k_clear_gather, k_clear_box: the floor map's column test and its two passes over a 2-D
-// array, the lookup of n points, a box of the field.  A thread an item; speed does not matter there.
+// k_clear_project, k_clear_axis_plain, k_clear_gather: the floor map's column test and its two passes over a 2-D array, the
+// lookup of n points.  A thread an item; speed does not matter there.  (A box of the field: volume_sweep.hip's k_box_rows.)
 #pragma clang fp contract(off)
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_clear_axis(const void* __restrict__ in,
   }
 }
 
-// ---- the floor map, the point lookup, a box of the field ----------------------------------------------------------------------
+// ---- the floor map, the point lookup ------------------------------------------------------------------------------------------
 // a column of the band lo <= p < hi along `axis` is an obstacle when any voxel of it is; u: the lower-numbered remaining axis
 __global__ __launch_bounds__(256) void k_clear_project(const unsigned* __restrict__ vol, VolParams vp, unsigned flags, int axis, int lo, int hi,
                                                        unsigned nu, unsigned nv, unsigned* __restrict__ map) {
@@ -159,30 +159,17 @@ __global__ __launch_bounds__(256) void k_clear_gather(const unsigned* __restrict
   out[e] = inside ? v : CLEAR_OUTSIDE;
 }
 
-__global__ __launch_bounds__(256) void k_clear_box(const unsigned* __restrict__ field, unsigned X, unsigned Y, int x0, int y0, int z0, unsigned bx,
-                                                   unsigned by, unsigned long long n, unsigned* __restrict__ out) {
-  const unsigned long long e = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-  if (e >= n) return;
-  const unsigned x = (unsigned)(e % bx), t = (unsigned)(e / bx), y = t % by, z = t / by;
-  out[e] = field[((size_t)((unsigned)z0 + z) * Y + ((unsigned)y0 + y)) * X + ((unsigned)x0 + x)];
-}
-
 // ---- the launchers ------------------------------------------------------------------------------------------------------------
 size_t clear_layout(const VolParams& vp, void* base, ClearBufs* b) {
   const size_t n = (size_t)vp.X * vp.Y * vp.Z;
-  size_t bytes = 0;
-  auto take = [&](size_t k) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (k + 255) & ~(size_t)255;
-    return p;
-  };
+  ScratchCarve c{base};
   ClearBufs out;
-  out.stats = (unsigned long long*)take(64);
-  out.field = (unsigned*)take(n * 4);
-  out.tmp = (unsigned*)take(n * 4);
-  out.dx = (unsigned short*)take(n * 2);
+  out.stats = (unsigned long long*)c.take(64);
+  out.field = (unsigned*)c.take(n * 4);
+  out.tmp = (unsigned*)c.take(n * 4);
+  out.dx = (unsigned short*)c.take(n * 2);
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
 
 void launch_clear_build(hipStream_t s, const void* vol, const ClearGeom& q, const ClearBufs& b) {
@@ -208,11 +195,4 @@ void launch_clear_floor(hipStream_t s, const void* vol, const VolParams& vp, con
 
 void launch_clear_gather(hipStream_t s, const unsigned* field, const VolParams& vp, const float* xyz, unsigned n, unsigned* out) {
   hipLaunchKernelGGL(k_clear_gather, dim3((n + 255u) / 256u), dim3(256), 0, s, field, hsk_sample_vol(vp), xyz, n, out);
-}
-
-void launch_clear_box(hipStream_t s, const unsigned* field, const VolParams& vp, const int lo[3], const int hi[3], unsigned* out) {
-  const unsigned bx = (unsigned)(hi[0] - lo[0]), by = (unsigned)(hi[1] - lo[1]), bz = (unsigned)(hi[2] - lo[2]);
-  const unsigned long long n = (unsigned long long)bx * by * bz;
-  hipLaunchKernelGGL(k_clear_box, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, s, field, (unsigned)vp.X, (unsigned)vp.Y, lo[0], lo[1], lo[2], bx, by,
-                     n, out);
 }

@@ -25,33 +25,15 @@
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
 #include "hsk_launch.h"
-#include "hsk_comp_point.h"
+#include "hsk_vol_sweep.h"
 
-// the grid, its 16-B vectors (X4 a row, Zg plane groups) and its tiles
-struct CompGeom {
-  CompGrid g;
-  unsigned X4, Zg, ntx, nty, ntz, n4;
-};
-#define CT_VOX 2048u  // voxels of a tile: 16 x 16 x 8
+#define CT_VOX 2048u  // voxels of a tile (hsk_vol_sweep.h): 16 x 16 x 8
 
-static __device__ __forceinline__ void comp_words(const uint4& v, unsigned w[4]) {
-  w[0] = v.x;
-  w[1] = v.y;
-  w[2] = v.z;
-  w[3] = v.w;
-}
-static __device__ __forceinline__ unsigned comp_wave_min(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-    v = u < v ? u : v;
-  }
-  return v;
-}
-__global__ __launch_bounds__(256) void k_comp_local(const uint4* __restrict__ vol, uint4* __restrict__ parent, CompGeom q) {
+__global__ __launch_bounds__(256) void k_comp_local(const uint4* __restrict__ vol, uint4* __restrict__ parent, VolTiles q) {
   __shared__ unsigned s_lab[CT_VOX];
   const unsigned tid = threadIdx.x;
-  const unsigned tx = blockIdx.x % q.ntx, tr = blockIdx.x / q.ntx, ty = tr % q.nty, tz = tr / q.nty;
+  unsigned tx, ty, tz;
+  vol_tile(q, blockIdx.x, tx, ty, tz);
   const unsigned c = tid & 15u, yl = tid >> 4, lb = c >> 2, pl = c & 3u;
   const unsigned x0 = 16u * tx + 4u * lb, y = 16u * ty + yl;
   const bool column = x0 < q.g.X && y < q.g.Y;  // (X is a multiple of 4: a vector lies inside the grid or outside it)
@@ -70,7 +52,7 @@ __global__ __launch_bounds__(256) void k_comp_local(const uint4* __restrict__ vo
 #pragma unroll
   for (int gg = 0; gg < 2; ++gg) {
     unsigned w[4];
-    comp_words(v[gg], w);
+    vol_words(v[gg], w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned l = (((4u * (unsigned)gg + pl) * 16u + yl) * 16u) + 4u * lb + (unsigned)j;
@@ -121,9 +103,10 @@ static __device__ __forceinline__ void comp_pair(unsigned* __restrict__ parent, 
   // comp_unite ends by the decreasing invariant and waits for nobody)
   if (a != COMP_NONE && b != COMP_NONE) comp_unite<CompGlobalOps>(parent, g, a, b);
 }
-__global__ __launch_bounds__(256) void k_comp_merge(unsigned* __restrict__ parent, CompGeom q) {
+__global__ __launch_bounds__(256) void k_comp_merge(unsigned* __restrict__ parent, VolTiles q) {
   const unsigned tid = threadIdx.x;
-  const unsigned tx = blockIdx.x % q.ntx, tr = blockIdx.x / q.ntx, ty = tr % q.nty, tz = tr / q.nty;
+  unsigned tx, ty, tz;
+  vol_tile(q, blockIdx.x, tx, ty, tz);
   {  // the face z = 8 tz against the plane before it
     const unsigned x = 16u * tx + (tid & 15u), y = 16u * ty + (tid >> 4), z = 8u * tz;
     if (tz > 0u && x < q.g.X && y < q.g.Y && z < q.g.Z) comp_pair(parent, q.g, x, y, z, x, y, z - 1u);
@@ -138,21 +121,12 @@ __global__ __launch_bounds__(256) void k_comp_merge(unsigned* __restrict__ paren
   }
 }
 
-// vector i of the parents -> its first voxel; false: no voxel (beyond the end, or a padding plane)
-static __device__ __forceinline__ bool comp_vector(const CompGeom& q, unsigned i, unsigned& x0, unsigned& y, unsigned& z) {
-  const unsigned pl = i & 3u, t = i >> 2, xb = t % q.X4, t2 = t / q.X4;
-  y = t2 % q.g.Y;
-  z = 4u * (t2 / q.g.Y) + pl;
-  x0 = 4u * xb;
-  return i < q.n4 && z < q.g.Z;
-}
-
-__global__ __launch_bounds__(256) void k_comp_flatten(uint4* __restrict__ parent, CompGeom q, unsigned* __restrict__ rows) {
+__global__ __launch_bounds__(256) void k_comp_flatten(uint4* __restrict__ parent, VolVectors q, unsigned* __restrict__ rows) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   unsigned x0, y, z;
-  if (!comp_vector(q, i, x0, y, z)) return;
+  if (!vol_vector(q, i, x0, y, z)) return;
   unsigned p[4];
-  comp_words(parent[i], p);
+  vol_words(parent[i], p);
   if ((p[0] & p[1] & p[2] & p[3]) == COMP_NONE) return;
   const unsigned own = q.g.lin(x0, y, z);
   unsigned n_roots = 0u;
@@ -172,7 +146,7 @@ __global__ __launch_bounds__(256) void k_comp_flatten(uint4* __restrict__ parent
 }
 
 // a wave per grid row: the row's roots to their places in the ascending list, their records reset
-__global__ __launch_bounds__(256) void k_comp_roots(const unsigned* __restrict__ parent, CompGeom q, const unsigned* __restrict__ rows,
+__global__ __launch_bounds__(256) void k_comp_roots(const unsigned* __restrict__ parent, VolVectors q, const unsigned* __restrict__ rows,
                                                     unsigned* __restrict__ roots, unsigned* __restrict__ table) {
   const unsigned row = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (row >= q.g.Y * q.g.Z) return;  // (the whole wave)
@@ -214,13 +188,13 @@ static __device__ __forceinline__ void comp_record_add(unsigned* __restrict__ t,
   if (y_hi > CompGlobalOps::load(&t[5])) atomicMax(&t[5], y_hi);
   if (z_hi > CompGlobalOps::load(&t[6])) atomicMax(&t[6], z_hi);
 }
-__global__ __launch_bounds__(256) void k_comp_records(const uint4* __restrict__ parent, CompGeom q, unsigned n, const unsigned* __restrict__ roots,
+__global__ __launch_bounds__(256) void k_comp_records(const uint4* __restrict__ parent, VolVectors q, unsigned n, const unsigned* __restrict__ roots,
                                                       unsigned* __restrict__ table) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
   unsigned x0, y, z;
-  const bool live = comp_vector(q, i, x0, y, z);
+  const bool live = vol_vector(q, i, x0, y, z);
   unsigned p[4] = {COMP_NONE, COMP_NONE, COMP_NONE, COMP_NONE};
-  if (live) comp_words(parent[i], p);
+  if (live) vol_words(parent[i], p);
   // this thread's members: their root when they share one, how many, their span in x
   unsigned key = COMP_NONE, cnt = 0u, j_lo = 4u, j_hi = 0u;
   bool one = true;
@@ -234,13 +208,13 @@ __global__ __launch_bounds__(256) void k_comp_records(const uint4* __restrict__ 
     j_hi = (unsigned)j + 1u;
   }
   const bool has = key != COMP_NONE;
-  const unsigned k_min = comp_wave_min(key);  // (every lane of the wave arrives here: nothing above returns)
+  const unsigned k_min = hsk_wave_fold<HskMin>(key);  // (every lane of the wave arrives here: nothing above returns)
   if (__all(one && (!has || key == k_min))) {
     if (k_min == COMP_NONE) return;  // (the whole wave)
     const unsigned c = hsk_wave_sum(cnt);
-    const unsigned x_lo = comp_wave_min(has ? x0 + j_lo : COMP_NONE), x_hi = hsk_wave_max(has ? x0 + j_hi : 0u);
-    const unsigned y_lo = comp_wave_min(has ? y : COMP_NONE), y_hi = hsk_wave_max(has ? y + 1u : 0u);
-    const unsigned z_lo = comp_wave_min(has ? z : COMP_NONE), z_hi = hsk_wave_max(has ? z + 1u : 0u);
+    const unsigned x_lo = hsk_wave_fold<HskMin>(has ? x0 + j_lo : COMP_NONE), x_hi = hsk_wave_max(has ? x0 + j_hi : 0u);
+    const unsigned y_lo = hsk_wave_fold<HskMin>(has ? y : COMP_NONE), y_hi = hsk_wave_max(has ? y + 1u : 0u);
+    const unsigned z_lo = hsk_wave_fold<HskMin>(has ? z : COMP_NONE), z_hi = hsk_wave_max(has ? z + 1u : 0u);
     if (lane == 0u) {
       const unsigned at = comp_search(roots, n, k_min);  // (ends: the interval halves)
       if (at < n) comp_record_add(table + (size_t)at * 8u, c, x_lo, x_hi, y_lo, y_hi, z_lo, z_hi);
@@ -256,17 +230,17 @@ __global__ __launch_bounds__(256) void k_comp_records(const uint4* __restrict__ 
 }
 
 template <bool COLOR>
-__global__ __launch_bounds__(256) void k_comp_prune(uint4* __restrict__ vol, unsigned* __restrict__ col, const uint4* __restrict__ parent, CompGeom q,
+__global__ __launch_bounds__(256) void k_comp_prune(uint4* __restrict__ vol, unsigned* __restrict__ col, const uint4* __restrict__ parent, VolVectors q,
                                                     const unsigned* __restrict__ roots, const unsigned* __restrict__ table, unsigned n,
                                                     unsigned min_voxels, const unsigned* __restrict__ keep, unsigned n_keep, int fill_free) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   unsigned x0, y, z;
-  if (!comp_vector(q, i, x0, y, z)) return;
+  if (!vol_vector(q, i, x0, y, z)) return;
   unsigned p[4];
-  comp_words(parent[i], p);
+  vol_words(parent[i], p);
   if ((p[0] & p[1] & p[2] & p[3]) == COMP_NONE) return;
   unsigned w[4];
-  comp_words(vol[i], w);
+  vol_words(vol[i], w);
   unsigned last = COMP_NONE;
   bool last_pruned = false, changed = false;
 #pragma unroll
@@ -285,39 +259,20 @@ __global__ __launch_bounds__(256) void k_comp_prune(uint4* __restrict__ vol, uns
   if (changed) vol[i] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-static CompGeom comp_geom(const VolParams& vp) {
-  CompGeom q;
-  q.g.X = (unsigned)vp.X;
-  q.g.Y = (unsigned)vp.Y;
-  q.g.Z = (unsigned)vp.Z;
-  q.X4 = (unsigned)vp.X >> 2;
-  q.Zg = ((unsigned)vp.Z + 3u) >> 2;
-  q.ntx = ((unsigned)vp.X + 15u) >> 4;
-  q.nty = ((unsigned)vp.Y + 15u) >> 4;
-  q.ntz = (q.Zg + 1u) >> 1;
-  q.n4 = q.X4 * q.g.Y * q.Zg * 4u;
-  return q;
-}
-
 size_t comp_layout(const VolParams& vp, void* base, CompBufs* b) {
   const size_t n_rows = (size_t)vp.Y * (size_t)vp.Z + 1;
-  size_t bytes = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (n + 255) & ~(size_t)255;
-    return p;
-  };
+  ScratchCarve c{base};
   CompBufs out;
-  out.counts = (unsigned*)take(64);
-  out.rows = (unsigned*)take(n_rows * 4);
-  out.bsum = (unsigned*)take((pack_scan_blocks(n_rows) + 1) * 4);
-  out.parent = (unsigned*)take(hsk_vol_words(vp) * 4);
+  out.counts = (unsigned*)c.take(64);
+  out.rows = (unsigned*)c.take(n_rows * 4);
+  out.bsum = (unsigned*)c.take((pack_scan_blocks(n_rows) + 1) * 4);
+  out.parent = (unsigned*)c.take(hsk_vol_words(vp) * 4);
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
 
 void launch_comp_label(hipStream_t s, const void* vol, const VolParams& vp, const CompBufs& b) {
-  const CompGeom q = comp_geom(vp);
+  const VolTiles q = vol_tiles(vp);
   const size_t n_rows = (size_t)vp.Y * (size_t)vp.Z + 1;
   const unsigned n_tiles = q.ntx * q.nty * q.ntz;
   (void)hipMemsetAsync(b.rows, 0, n_rows * 4, s);
@@ -328,7 +283,7 @@ void launch_comp_label(hipStream_t s, const void* vol, const VolParams& vp, cons
 }
 
 void launch_comp_records(hipStream_t s, const VolParams& vp, const CompBufs& b, unsigned n, unsigned* roots, unsigned* table) {
-  const CompGeom q = comp_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   const unsigned n_rows = q.g.Y * q.g.Z;
   hipLaunchKernelGGL(k_comp_roots, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, (const unsigned*)b.parent, q, (const unsigned*)b.rows, roots, table);
   hipLaunchKernelGGL(k_comp_records, dim3((q.n4 + 255u) / 256u), dim3(256), 0, s, (const uint4*)b.parent, q, n, (const unsigned*)roots, table);
@@ -336,7 +291,7 @@ void launch_comp_records(hipStream_t s, const VolParams& vp, const CompBufs& b, 
 
 void launch_comp_prune(hipStream_t s, void* vol, unsigned* col, const VolParams& vp, const unsigned* parent, const unsigned* roots,
                        const unsigned* table, unsigned n, unsigned min_voxels, const unsigned* keep, unsigned n_keep, bool fill_free) {
-  const CompGeom q = comp_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   const dim3 grid((q.n4 + 255u) / 256u);
   if (col)
     hipLaunchKernelGGL((k_comp_prune<true>), grid, dim3(256), 0, s, (uint4*)vol, col, (const uint4*)parent, q, roots, table, n, min_voxels, keep, n_keep,

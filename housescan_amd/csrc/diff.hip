@@ -11,7 +11,7 @@
 // box, launch_comp_prune with the FREE fill for the MINOR step (api_diff.hip).
 // k_diff_records: per kept region its APPEARED and VANISHED voxels; a wave whose members share one root adds once.
 // k_diff_box, k_diff_gather: a box of class bytes and labels, row-major; the point query.  A thread an item.
-// k_diff_mark, k_diff_dilate, k_diff_adopt: the adopt set.  Targets as bytes, row-major, a word of four bytes a thread; three
+// k_diff_mark, k_diff_adopt: the adopt set.  Targets as bytes, row-major, a word of four bytes a thread; volume_sweep.hip's three
 // passes of Chebyshev reach, one an axis; then the masked copy of cur's words (and colour) into ref, counted first without a
 // write (the host writes nothing, and flushes nothing, when the set is empty).
 // Every index below is formed from a vector number below n4 or a voxel inside the grid: no access leaves the buffers.
@@ -19,39 +19,11 @@
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
 #include "hsk_launch.h"
+#include "hsk_vol_sweep.h"
 #include "hsk_clear_point.h"
 #include "hsk_diff_point.h"
 
-// the grid and its 16-B vectors: X4 a row, Zg plane groups, n4 in all (padding planes included)
-struct DiffGeom {
-  CompGrid g;
-  unsigned X4, Zg, n4;
-};
-
-static __device__ __forceinline__ void diff_words(const uint4& v, unsigned w[4]) {
-  w[0] = v.x;
-  w[1] = v.y;
-  w[2] = v.z;
-  w[3] = v.w;
-}
-// vector i -> its first voxel; false: no voxel (beyond the end, or a padding plane)
-static __device__ __forceinline__ bool diff_vector(const DiffGeom& q, unsigned i, unsigned& x0, unsigned& y, unsigned& z) {
-  const unsigned pl = i & 3u, t = i >> 2, xb = t % q.X4, t2 = t / q.X4;
-  y = t2 % q.g.Y;
-  z = 4u * (t2 / q.g.Y) + pl;
-  x0 = 4u * xb;
-  return i < q.n4 && z < q.g.Z;
-}
-// quad i of a row-major byte volume (four x-adjacent voxels, one aligned word: X is a multiple of 4) -> its first voxel
-static __device__ __forceinline__ bool diff_quad(const DiffGeom& q, unsigned i, unsigned& x0, unsigned& y, unsigned& z) {
-  const unsigned xb = i % q.X4, r = i / q.X4;
-  x0 = 4u * xb;
-  y = r % q.g.Y;
-  z = r / q.g.Y;
-  return z < q.g.Z;
-}
-
-__global__ __launch_bounds__(256) void k_diff_classify(const uint4* __restrict__ ref, const uint4* __restrict__ cur, uint4* __restrict__ cls, DiffGeom q,
+__global__ __launch_bounds__(256) void k_diff_classify(const uint4* __restrict__ ref, const uint4* __restrict__ cur, uint4* __restrict__ cls, VolVectors q,
                                                        int thresh, int min_weight, unsigned* __restrict__ counts) {
   uint4 a[4], b[4];
   unsigned at[4];
@@ -60,7 +32,7 @@ __global__ __launch_bounds__(256) void k_diff_classify(const uint4* __restrict__
   for (int c = 0; c < 4; ++c) {
     at[c] = (blockIdx.x * 4u + (unsigned)c) * 256u + threadIdx.x;
     unsigned x0, y, z;
-    voxels[c] = diff_vector(q, at[c], x0, y, z);
+    voxels[c] = vol_vector(q, at[c], x0, y, z);
     stored[c] = at[c] < q.n4;
     a[c] = b[c] = make_uint4(0u, 0u, 0u, 0u);
     if (voxels[c]) {  // (a padding plane is no voxel: not read, its class words 0)
@@ -72,8 +44,8 @@ __global__ __launch_bounds__(256) void k_diff_classify(const uint4* __restrict__
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     unsigned wa[4], wb[4], o[4];
-    diff_words(a[c], wa);
-    diff_words(b[c], wb);
+    vol_words(a[c], wa);
+    vol_words(b[c], wb);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = diff_class(wa[j], wb[j], thresh, min_weight);
@@ -90,15 +62,15 @@ __global__ __launch_bounds__(256) void k_diff_classify(const uint4* __restrict__
 }
 
 // av[2 at] the APPEARED, av[2 at + 1] the VANISHED voxels of region roots[at]; only kept regions have members left
-__global__ __launch_bounds__(256) void k_diff_records(const uint4* __restrict__ cls, const uint4* __restrict__ parent, DiffGeom q, unsigned n,
+__global__ __launch_bounds__(256) void k_diff_records(const uint4* __restrict__ cls, const uint4* __restrict__ parent, VolVectors q, unsigned n,
                                                       const unsigned* __restrict__ roots, unsigned* __restrict__ av) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
   unsigned x0, y, z;
-  const bool live = diff_vector(q, i, x0, y, z);
+  const bool live = vol_vector(q, i, x0, y, z);
   unsigned w[4] = {0u, 0u, 0u, 0u}, p[4] = {COMP_NONE, COMP_NONE, COMP_NONE, COMP_NONE};
   if (live) {
-    diff_words(cls[i], w);
-    diff_words(parent[i], p);
+    vol_words(cls[i], w);
+    vol_words(parent[i], p);
   }
   unsigned key = COMP_NONE, n_a = 0u, n_v = 0u;
   bool one = true;
@@ -132,16 +104,13 @@ __global__ __launch_bounds__(256) void k_diff_records(const uint4* __restrict__ 
   }
 }
 
-struct DiffBox {
-  int lo[3], hi[3];
-};
 // the box lo <= (x, y, z) < hi, row-major: class bytes and (region not null) labels
-__global__ __launch_bounds__(256) void k_diff_box(const unsigned* __restrict__ cls, const unsigned* __restrict__ parent, DiffGeom q, DiffBox box, unsigned n,
+__global__ __launch_bounds__(256) void k_diff_box(const unsigned* __restrict__ cls, const unsigned* __restrict__ parent, VolVectors q, VoxBox box, unsigned n,
                                                   unsigned char* __restrict__ out, unsigned* __restrict__ region) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
-  const unsigned bx = (unsigned)(box.hi[0] - box.lo[0]), by = (unsigned)(box.hi[1] - box.lo[1]);
-  const unsigned r = i / bx, x = i - r * bx, z = r / by, y = r - z * by;
+  unsigned x, y, z;
+  vol_box_voxel(box, i, x, y, z);
   const size_t at = q.g.at_xyz(x + (unsigned)box.lo[0], y + (unsigned)box.lo[1], z + (unsigned)box.lo[2]);
   const int c = diff_word_class(cls[at]);
   out[i] = (unsigned char)c;
@@ -153,7 +122,7 @@ struct DiffClassAt {
   CompGrid g;
   HSK_HD_MEMBER int operator()(unsigned x, unsigned y, unsigned z) const { return diff_word_class(cls[g.at_xyz(x, y, z)]); }
 };
-__global__ __launch_bounds__(256) void k_diff_gather(const unsigned* __restrict__ cls, const unsigned* __restrict__ parent, DiffGeom q, SampleVol sv,
+__global__ __launch_bounds__(256) void k_diff_gather(const unsigned* __restrict__ cls, const unsigned* __restrict__ parent, VolVectors q, SampleVol sv,
                                                      const float* __restrict__ xyz, unsigned n, int radius, unsigned* __restrict__ region,
                                                      unsigned char* __restrict__ out) {
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
@@ -169,15 +138,15 @@ __global__ __launch_bounds__(256) void k_diff_gather(const unsigned* __restrict_
 }
 
 // the targets as bytes (0 or 1), row-major; counts[8]: how many
-__global__ __launch_bounds__(256) void k_diff_mark(const uint4* __restrict__ cls, DiffGeom q, int which, unsigned* __restrict__ mask,
+__global__ __launch_bounds__(256) void k_diff_mark(const uint4* __restrict__ cls, VolVectors q, int which, unsigned* __restrict__ mask,
                                                    unsigned* __restrict__ counts) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   unsigned x0, y, z;
-  const bool live = diff_vector(q, i, x0, y, z);
+  const bool live = vol_vector(q, i, x0, y, z);
   unsigned m = 0u, n_t = 0u;
   if (live) {
     unsigned w[4];
-    diff_words(cls[i], w);
+    vol_words(cls[i], w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool t = diff_adopt_target(diff_word_class(w[j]), which);
@@ -190,44 +159,19 @@ __global__ __launch_bounds__(256) void k_diff_mark(const uint4* __restrict__ cls
   if ((threadIdx.x & 63u) == 0u && s) atomicAdd(&counts[8], s);
 }
 
-// dst = src dilated by `halo` along one axis (0 x, 1 y, 2 z); bytes are 0 or 1
-__global__ __launch_bounds__(256) void k_diff_dilate(const unsigned char* __restrict__ src, DiffGeom q, int axis, int halo, unsigned* __restrict__ dst) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  unsigned x0, y, z;
-  if (!diff_quad(q, i, x0, y, z)) return;
-  unsigned m = 0u;
-  if (axis == 0) {
-    const unsigned char* __restrict__ r = src + (size_t)q.g.lin(0u, y, z);
-    for (int d = -halo; d <= halo + 3; ++d) {  // (at most 20 trips: halo <= 8)
-      const unsigned x = x0 + (unsigned)d;
-      if (x >= q.g.X || !r[x]) continue;
-      // voxel x reaches x0 + j for |x - (x0 + j)| <= halo, that is j in d - halo .. d + halo
-#pragma unroll
-      for (int j = 0; j < 4; ++j) m |= (j >= d - halo && j <= d + halo) ? 1u << (8 * j) : 0u;
-    }
-  } else {
-    for (int d = -halo; d <= halo; ++d) {  // (at most 17 trips)
-      const unsigned yy = axis == 1 ? y + (unsigned)d : y, zz = axis == 2 ? z + (unsigned)d : z;
-      if (yy >= q.g.Y || zz >= q.g.Z) continue;
-      m |= ((const unsigned*)src)[(size_t)q.g.lin(x0, yy, zz) >> 2];
-    }
-  }
-  dst[i] = m;
-}
-
 // MODE 0: count the adopt set (counts[9]); 1: write cur's words; 2: and cur's colour words; 3: and the colour word 0
 template <int MODE>
 __global__ __launch_bounds__(256) void k_diff_adopt(uint4* __restrict__ ref, const uint4* __restrict__ cur, unsigned* __restrict__ ref_col,
-                                                    const unsigned* __restrict__ cur_col, const unsigned* __restrict__ mask, DiffGeom q,
+                                                    const unsigned* __restrict__ cur_col, const unsigned* __restrict__ mask, VolVectors q,
                                                     unsigned* __restrict__ counts) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   unsigned x0, y, z;
-  const bool live = diff_vector(q, i, x0, y, z);
+  const bool live = vol_vector(q, i, x0, y, z);
   unsigned n_s = 0u;
   const unsigned m = live ? mask[(size_t)q.g.lin(x0, y, z) >> 2] : 0u;
   if (m != 0u) {
     unsigned wb[4];
-    diff_words(cur[i], wb);
+    vol_words(cur[i], wb);
     unsigned take = 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -237,7 +181,7 @@ __global__ __launch_bounds__(256) void k_diff_adopt(uint4* __restrict__ ref, con
     }
     if (MODE != 0 && take != 0u) {
       unsigned wa[4];
-      diff_words(ref[i], wa);
+      vol_words(ref[i], wa);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (!((take >> j) & 1u)) continue;
@@ -255,84 +199,58 @@ __global__ __launch_bounds__(256) void k_diff_adopt(uint4* __restrict__ ref, con
   }
 }
 
-static DiffGeom diff_geom(const VolParams& vp) {
-  DiffGeom q;
-  q.g.X = (unsigned)vp.X;
-  q.g.Y = (unsigned)vp.Y;
-  q.g.Z = (unsigned)vp.Z;
-  q.X4 = (unsigned)vp.X >> 2;
-  q.Zg = ((unsigned)vp.Z + 3u) >> 2;
-  q.n4 = q.X4 * q.g.Y * q.Zg * 4u;
-  return q;
-}
-static DiffBox diff_box(const int lo[3], const int hi[3]) {
-  DiffBox b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = lo[i];
-    b.hi[i] = hi[i];
-  }
-  return b;
-}
-
 size_t diff_layout(const VolParams& vp, void* base, DiffBufs* b) {
-  size_t bytes = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (n + 255) & ~(size_t)255;
-    return p;
-  };
+  ScratchCarve c{base};
   DiffBufs out;
-  out.counts = (unsigned*)take(DIFF_COUNTS * 4);
-  out.cls = (unsigned*)take(hsk_vol_words(vp) * 4);
-  out.mask[0] = (unsigned char*)take((size_t)vp.X * vp.Y * vp.Z);
-  out.mask[1] = (unsigned char*)take((size_t)vp.X * vp.Y * vp.Z);
-  char* comp = take(comp_layout(vp, nullptr, nullptr));
+  out.counts = (unsigned*)c.take(DIFF_COUNTS * 4);
+  out.cls = (unsigned*)c.take(hsk_vol_words(vp) * 4);
+  out.mask[0] = (unsigned char*)c.take((size_t)vp.X * vp.Y * vp.Z);
+  out.mask[1] = (unsigned char*)c.take((size_t)vp.X * vp.Y * vp.Z);
+  char* comp = c.take(comp_layout(vp, nullptr, nullptr));
   comp_layout(vp, comp, &out.comp);
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
 
 void launch_diff_classify(hipStream_t s, const void* ref, const void* cur, const VolParams& vp, const DiffBufs& b, int thresh, int min_weight) {
-  const DiffGeom q = diff_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   (void)hipMemsetAsync(b.counts, 0, DIFF_COUNTS * 4, s);
   hipLaunchKernelGGL(k_diff_classify, dim3((q.n4 + 1023u) / 1024u), dim3(256), 0, s, (const uint4*)ref, (const uint4*)cur, (uint4*)b.cls, q, thresh,
                      min_weight, b.counts);
 }
 
 void launch_diff_records(hipStream_t s, const VolParams& vp, const DiffBufs& b, unsigned n, const unsigned* roots, unsigned* av) {
-  const DiffGeom q = diff_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   (void)hipMemsetAsync(av, 0, (size_t)n * 8, s);
   hipLaunchKernelGGL(k_diff_records, dim3((q.n4 + 255u) / 256u), dim3(256), 0, s, (const uint4*)b.cls, (const uint4*)b.comp.parent, q, n, roots, av);
 }
 
 void launch_diff_box(hipStream_t s, const VolParams& vp, const DiffBufs& b, const int lo[3], const int hi[3], size_t n, unsigned char* cls,
                      unsigned* region) {
-  const DiffGeom q = diff_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   hipLaunchKernelGGL(k_diff_box, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const unsigned*)b.cls, (const unsigned*)b.comp.parent, q,
-                     diff_box(lo, hi), (unsigned)n, cls, region);
+                     vox_box(lo, hi), (unsigned)n, cls, region);
 }
 
 void launch_diff_gather(hipStream_t s, const VolParams& vp, const DiffBufs& b, const float* xyz, unsigned n, int radius, unsigned* region,
                         unsigned char* cls) {
-  const DiffGeom q = diff_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   hipLaunchKernelGGL(k_diff_gather, dim3((n + 255u) / 256u), dim3(256), 0, s, (const unsigned*)b.cls, (const unsigned*)b.comp.parent, q,
                      hsk_sample_vol(vp), xyz, n, radius, region, cls);
 }
 
 void launch_diff_halo(hipStream_t s, const void* cur, const VolParams& vp, const DiffBufs& b, int which, int halo) {
-  const DiffGeom q = diff_geom(vp);
-  const dim3 vectors((q.n4 + 255u) / 256u), quads((q.X4 * q.g.Y * q.g.Z + 255u) / 256u);
+  const VolVectors q = vol_vectors(vp);
+  const dim3 vectors((q.n4 + 255u) / 256u);
   (void)hipMemsetAsync(b.counts + 8, 0, 8, s);
   hipLaunchKernelGGL(k_diff_mark, vectors, dim3(256), 0, s, (const uint4*)b.cls, q, which, (unsigned*)b.mask[0], b.counts);
-  hipLaunchKernelGGL(k_diff_dilate, quads, dim3(256), 0, s, (const unsigned char*)b.mask[0], q, 0, halo, (unsigned*)b.mask[1]);
-  hipLaunchKernelGGL(k_diff_dilate, quads, dim3(256), 0, s, (const unsigned char*)b.mask[1], q, 1, halo, (unsigned*)b.mask[0]);
-  hipLaunchKernelGGL(k_diff_dilate, quads, dim3(256), 0, s, (const unsigned char*)b.mask[0], q, 2, halo, (unsigned*)b.mask[1]);
+  launch_mask_dilate3(s, vp, b.mask[0], b.mask[1], halo);  // (the result: mask[1])
   hipLaunchKernelGGL((k_diff_adopt<0>), vectors, dim3(256), 0, s, (uint4*)nullptr, (const uint4*)cur, (unsigned*)nullptr, (const unsigned*)nullptr,
                      (const unsigned*)b.mask[1], q, b.counts);
 }
 
 void launch_diff_adopt(hipStream_t s, void* ref, const void* cur, unsigned* ref_col, const unsigned* cur_col, const VolParams& vp, const DiffBufs& b) {
-  const DiffGeom q = diff_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   const dim3 vectors((q.n4 + 255u) / 256u);
   const unsigned* m = (const unsigned*)b.mask[1];
   if (!ref_col)

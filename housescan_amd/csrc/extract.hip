@@ -697,22 +697,17 @@ size_t mesh_index_layout(const VolParams& vp, void* base, MeshIndexBufs* b) {
   const int z_end = hsk_mesh_z_end(vp);
   const int rows = z_end > vp.zo0 ? vp.Y * (z_end - vp.zo0 + 1) : 0;
   const int nseg = (vp.X + 63) / 64;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? (char*)base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
+  ScratchCarve c{base};
   MeshIndexBufs m;
   m.rows = rows;
   m.nseg = nseg;
-  m.totals = (unsigned long long*)take(32);
-  m.bits = (unsigned long long*)take((size_t)rows * 3 * nseg * 8);
-  m.voff = (unsigned long long*)take(hsk_scan_scratch_entries(rows) * 8);
-  m.vcount = (unsigned*)take((size_t)rows * 4);
-  m.segbase = (unsigned short*)take((size_t)rows * nseg * 2);
+  m.totals = (unsigned long long*)c.take(32);
+  m.bits = (unsigned long long*)c.take((size_t)rows * 3 * nseg * 8);
+  m.voff = (unsigned long long*)c.take(hsk_scan_scratch_entries(rows) * 8);
+  m.vcount = (unsigned*)c.take((size_t)rows * 4);
+  m.segbase = (unsigned short*)c.take((size_t)rows * nseg * 2);
   if (b) *b = m;
-  return off;
+  return c.bytes;
 }
 
 __global__ __launch_bounds__(256) void k_mesh_index_mark(const short2* __restrict__ vol, VolParams vp, const CubeTable* __restrict__ ct,

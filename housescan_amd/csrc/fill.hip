@@ -4,7 +4,7 @@
 //
 // THE STATE is one int16 per stored voxel at the voxel's own place in the block layout (hsk_vox_index), FILL_UNKNOWN in the
 // padding planes, in two buffers: iteration i reads buffer (i - 1) & 1 and writes buffer i & 1, the final states are those of
-// buffer iterations & 1.  A tile is components.hip's: 16 x 16 x 8 voxels, 4 lane-blocks wide, 16 rows, two plane groups; a thread
+// buffer iterations & 1.  A tile is hsk_vol_sweep.h's: 16 x 16 x 8 voxels, 4 lane-blocks wide, 16 rows, two plane groups; a thread
 // owns planes 2 h, 2 h + 1 of one lane-block of one row of one plane group: two adjacent 16-B vectors of the volume and ONE 16-B
 // vector of a state buffer.
 // k_fill_init: a workgroup per tile writes both state buffers from the volume, a byte per thread with its eight voxels' FREE
@@ -12,10 +12,9 @@
 // candidate), whether it holds a source (the "changed" byte iteration 1 reads) and a zero (the byte iteration 1 writes).
 // k_fill_round: a workgroup per tile; see the argument at its test for which tiles work.  A working tile stages its states and a
 // one-voxel halo in LDS (18 x 18 x 10 int16), applies fill_step to its FREE voxels and stores every vector of the tile.
-// k_fill_cross, k_fill_dilate: the keep rule of HSK_FILL_SURFACE in row-major bytes -- the crossing voxels (a workgroup per tile,
-// staged as an iteration stages it), then their dilation by `band` along x, y and z in turn (a Chebyshev ball is the product of
-// three intervals).  The bytes live in the state buffer that does not hold the final states: its first half and its second half
-// in turn.
+// k_fill_cross: the keep rule of HSK_FILL_SURFACE in row-major bytes -- the crossing voxels (a workgroup per tile, staged as an
+// iteration stages it); volume_sweep.hip's k_mask_dilate then dilates them by `band` along x, y and z in turn.  The bytes live in
+// the state buffer that does not hold the final states: its first half and its second half in turn.
 // k_fill_count: the mask (a row-major byte per voxel: this voxel is written) and the counts, a thread per lane-block;
 // k_fill_commit: the words, through the mask -- a vector of the volume is stored only when one of its words changes.
 // No kernel waits on another workgroup; no loop's trip count depends on data.
@@ -23,14 +22,9 @@
 #include "../../include/hskinfu.h"
 #include "hsk_dev.h"
 #include "hsk_launch.h"
-#include "hsk_comp_point.h"
+#include "hsk_vol_sweep.h"
 #include "hsk_fill_point.h"
 
-// the grid, its 16-B vectors of the volume (X4 a row, Zg plane groups, n4 in all) and its tiles
-struct FillGeom {
-  CompGrid g;
-  unsigned X4, Zg, ntx, nty, ntz, n4;
-};
 #define FT_X 18u  // a staged tile's extents: the tile and a one-voxel halo
 #define FT_Y 18u
 #define FT_Z 10u
@@ -43,7 +37,7 @@ struct FillThread {
   bool stored;         // the thread's vectors exist
   size_t v16;          // its vector of a state buffer, in 16-B units; its two of the volume are 2 v16, 2 v16 + 1
 };
-static __device__ __forceinline__ FillThread fill_thread(const FillGeom& q, unsigned tx, unsigned ty, unsigned tz, unsigned tid) {
+static __device__ __forceinline__ FillThread fill_thread(const VolTiles& q, unsigned tx, unsigned ty, unsigned tz, unsigned tid) {
   FillThread t;
   t.h = tid & 1u;
   t.lb = (tid >> 1) & 3u;
@@ -56,16 +50,10 @@ static __device__ __forceinline__ FillThread fill_thread(const FillGeom& q, unsi
   t.v16 = (((size_t)t.zg * q.g.Y + t.y) * q.X4 + (t.x0 >> 2)) * 2u + t.h;
   return t;
 }
-static __device__ __forceinline__ void fill_words(const uint4& v, unsigned w[4]) {
-  w[0] = v.x;
-  w[1] = v.y;
-  w[2] = v.z;
-  w[3] = v.w;
-}
 // eight states <-> a 16-B vector (element e in the low or high half of word e / 2)
 static __device__ __forceinline__ void fill_unpack(const uint4& v, int s[8]) {
   unsigned w[4];
-  fill_words(v, w);
+  vol_words(v, w);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     s[2 * i] = (int)(short)(w[i] & 0xffffu);
@@ -80,12 +68,13 @@ static __device__ __forceinline__ uint4 fill_pack(const int s[8]) {
 }
 #define FILL_UNKNOWN_VEC make_uint4(0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u)
 
-__global__ __launch_bounds__(256) void k_fill_init(const uint4* __restrict__ vol, FillGeom q, FillBox box, uint4* __restrict__ st0, uint4* __restrict__ st1,
+__global__ __launch_bounds__(256) void k_fill_init(const uint4* __restrict__ vol, VolTiles q, VoxBox box, uint4* __restrict__ st0, uint4* __restrict__ st1,
                                                    unsigned char* __restrict__ tile_free, unsigned char* __restrict__ cand,
                                                    unsigned char* __restrict__ flag0, unsigned char* __restrict__ flag1, unsigned* __restrict__ counts) {
   __shared__ unsigned s_n[2];
   const unsigned tid = threadIdx.x, tile = blockIdx.x;
-  const unsigned tx = tile % q.ntx, tr = tile / q.ntx, ty = tr % q.nty, tz = tr / q.nty;
+  unsigned tx, ty, tz;
+  vol_tile(q, tile, tx, ty, tz);
   const FillThread t = fill_thread(q, tx, ty, tz, tid);
   if (tid < 2u) s_n[tid] = 0u;
   uint4 v[2];
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void k_fill_init(const uint4* __restrict__ vol
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     unsigned w[4];
-    fill_words(v[p], w);
+    vol_words(v[p], w);
     const unsigned z = 4u * t.zg + 2u * t.h + (unsigned)p;
     const bool voxel = t.stored && z < q.g.Z;
 #pragma unroll
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(256) void k_fill_init(const uint4* __restrict__ vol
       s[4 * p + j] = fill_initial(w[j]);  // (no voxel: the word is 0, FILL_UNKNOWN)
       const bool src = fill_is_source(w[j]);
       n_src += src ? 1u : 0u;
-      const bool fr = voxel && !src && fill_in_box(box, (int)(t.x0 + (unsigned)j), (int)t.y, (int)z);
+      const bool fr = voxel && !src && vox_in_box(box, (int)(t.x0 + (unsigned)j), (int)t.y, (int)z);
       free_bits |= (fr ? 1u : 0u) << (4 * p + j);
     }
   }
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(256) void k_fill_init(const uint4* __restrict__ vol
 
 // a halo voxel's state: FILL_UNKNOWN outside the grid (x, y, z may be -1 as unsigned or one past the end).  The padding planes
 // hold FILL_UNKNOWN, so z is tested against the stored planes only.
-static __device__ __forceinline__ int fill_halo(const short* __restrict__ st, const FillGeom& q, unsigned x, unsigned y, unsigned z) {
+static __device__ __forceinline__ int fill_halo(const short* __restrict__ st, const VolTiles& q, unsigned x, unsigned y, unsigned z) {
   if (x >= q.g.X || y >= q.g.Y || z >= 4u * q.Zg) return FILL_UNKNOWN;
   return (int)st[q.g.at_xyz(x, y, z)];
 }
@@ -144,7 +133,7 @@ static __device__ __forceinline__ int fill_halo(const short* __restrict__ st, co
 // The tile's states and a one-voxel halo of them into s_st (FT_Z x FT_Y x FT_X; the halo's edges and corners are not staged: a
 // voxel's six face neighbours never lie there), the thread's own eight into s.  Every load is issued before the first is used:
 // the thread's vector and its four halo voxels.  Every thread of the workgroup arrives (it ends in a barrier).
-static __device__ __forceinline__ void fill_stage(const short* __restrict__ rd, const FillGeom& q, const FillThread& t, unsigned tx, unsigned ty, unsigned tz,
+static __device__ __forceinline__ void fill_stage(const short* __restrict__ rd, const VolTiles& q, const FillThread& t, unsigned tx, unsigned ty, unsigned tz,
                                                   unsigned tid, short* __restrict__ s_st, int s[8]) {
   const uint4 own = t.stored ? ((const uint4*)rd)[t.v16] : FILL_UNKNOWN_VEC;
   const unsigned a = tid & 15u, b = tid >> 4, f = tid >> 7, c = (tid >> 4) & 7u;
@@ -165,13 +154,14 @@ static __device__ __forceinline__ void fill_stage(const short* __restrict__ rd, 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void k_fill_round(const short* __restrict__ rd, uint4* __restrict__ wr, FillGeom q, const unsigned char* __restrict__ tile_free,
+__global__ __launch_bounds__(256) void k_fill_round(const short* __restrict__ rd, uint4* __restrict__ wr, VolTiles q, const unsigned char* __restrict__ tile_free,
                                                     const unsigned char* __restrict__ cand, const unsigned char* __restrict__ flag_rd,
                                                     unsigned char* __restrict__ flag_wr, unsigned* __restrict__ changed, unsigned* __restrict__ visits) {
   __shared__ short s_st[FT_Z * FT_Y * FT_X];
   __shared__ unsigned s_changed;
   const unsigned tid = threadIdx.x, tile = blockIdx.x;
-  const unsigned tx = tile % q.ntx, tr = tile / q.ntx, ty = tr % q.nty, tz = tr / q.nty;
+  unsigned tx, ty, tz;
+  vol_tile(q, tile, tx, ty, tz);
   // WHICH TILES WORK.  Write S_i(T) for tile T's states after iteration i (S_0: k_fill_init's), and c_i(T) for "S_i(T) differs
   // from S_{i-1}(T)", with c_0(T) = "T holds a KNOWN voxel".  Iteration i reads buffer R = (i - 1) & 1 and writes W = i & 1.
   // Invariant before iteration i: R holds S_{i-1} everywhere, W holds S_{i-2}(T) (i = 1: S_0) in every tile, and flag_rd[T] =
@@ -223,19 +213,12 @@ __global__ __launch_bounds__(256) void k_fill_round(const short* __restrict__ rd
   }
 }
 
-// thread i of a row-major sweep -> its four voxels (x0 .. x0 + 3, y, z); false: beyond the end
-static __device__ __forceinline__ bool fill_quad(const FillGeom& q, unsigned i, unsigned& x0, unsigned& y, unsigned& z) {
-  const unsigned r = i / q.X4;
-  x0 = 4u * (i - r * q.X4);
-  z = r / q.g.Y;
-  y = r - z * q.g.Y;
-  return z < q.g.Z;
-}
 // the crossing voxels of the final states, a row-major byte each: a workgroup per tile, staged as an iteration stages it
-__global__ __launch_bounds__(256) void k_fill_cross(const short* __restrict__ st, FillGeom q, unsigned* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_fill_cross(const short* __restrict__ st, VolTiles q, unsigned* __restrict__ out) {
   __shared__ short s_st[FT_Z * FT_Y * FT_X];
   const unsigned tid = threadIdx.x, tile = blockIdx.x;
-  const unsigned tx = tile % q.ntx, tr = tile / q.ntx, ty = tr % q.nty, tz = tr / q.nty;
+  unsigned tx, ty, tz;
+  vol_tile(q, tile, tx, ty, tz);
   const FillThread t = fill_thread(q, tx, ty, tz, tid);
   int s[8];
   fill_stage(st, q, t, tx, ty, tz, tid, s_st, s);
@@ -255,45 +238,11 @@ __global__ __launch_bounds__(256) void k_fill_cross(const short* __restrict__ st
   }
 }
 
-// dst = src dilated by `band` along one axis (0 x, 1 y, 2 z); bytes are 0 or 1
-__global__ __launch_bounds__(256) void k_fill_dilate(const unsigned char* __restrict__ src, FillGeom q, int axis, int band, unsigned* __restrict__ dst) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  unsigned x0, y, z;
-  if (!fill_quad(q, i, x0, y, z)) return;
-  unsigned m = 0u;
-  if (axis == 0) {
-    const unsigned char* __restrict__ r = src + (size_t)q.g.lin(0u, y, z);
-    for (int d = -band; d <= band + 3; ++d) {  // (at most 20 trips: band <= 8)
-      const unsigned x = x0 + (unsigned)d;
-      if (x >= q.g.X || !r[x]) continue;
-      // voxel x reaches x0 + j for |x - (x0 + j)| <= band, that is j in d - band .. d + band
-#pragma unroll
-      for (int j = 0; j < 4; ++j) m |= (j >= d - band && j <= d + band) ? 1u << (8 * j) : 0u;
-    }
-  } else {
-    for (int d = -band; d <= band; ++d) {  // (at most 17 trips)
-      const unsigned yy = axis == 1 ? y + (unsigned)d : y, zz = axis == 2 ? z + (unsigned)d : z;
-      if (yy >= q.g.Y || zz >= q.g.Z) continue;
-      m |= ((const unsigned*)src)[(size_t)q.g.lin(x0, yy, zz) >> 2];
-    }
-  }
-  dst[i] = m;
-}
-
-// vector i of the volume -> its first voxel; false: no voxel (beyond the end, or a padding plane)
-static __device__ __forceinline__ bool fill_vector(const FillGeom& q, unsigned i, unsigned& x0, unsigned& y, unsigned& z) {
-  const unsigned pl = i & 3u, t = i >> 2, xb = t % q.X4, t2 = t / q.X4;
-  y = t2 % q.g.Y;
-  z = 4u * (t2 / q.g.Y) + pl;
-  x0 = 4u * xb;
-  return i < q.n4 && z < q.g.Z;
-}
-
 // the mask and the counts: counts[1] the FILLED voxels, [2] those that are written, [3] those of them with a negative value.  A
 // thread per lane-block (4 x-adjacent voxels by 4 planes): 64 contiguous bytes of the volume, 32 of the states, and one word of
 // the keep bytes and of the mask in each of its planes -- consecutive threads, consecutive words in all four arrays.
-__global__ __launch_bounds__(256) void k_fill_count(const uint4* __restrict__ vol, const uint4* __restrict__ st, const unsigned* __restrict__ keep, FillGeom q,
-                                                    FillBox box, unsigned* __restrict__ mask, unsigned* __restrict__ counts) {
+__global__ __launch_bounds__(256) void k_fill_count(const uint4* __restrict__ vol, const uint4* __restrict__ st, const unsigned* __restrict__ keep, VolVectors q,
+                                                    VoxBox box, unsigned* __restrict__ mask, unsigned* __restrict__ counts) {
   unsigned n_reached = 0u, n_written = 0u, n_neg = 0u;
   // (four lane-blocks a thread and one set of atomics a workgroup: at 512^3 the three counters take 8 192 additions each, not the
   // 131 072 a wave-wise sum would send to the same three words)
@@ -318,12 +267,12 @@ __global__ __launch_bounds__(256) void k_fill_count(const uint4* __restrict__ vo
       const unsigned z = 4u * zg + (unsigned)pl;
       if (z >= q.g.Z) continue;
       unsigned w[4];
-      fill_words(v[pl], w);
+      vol_words(v[pl], w);
       unsigned m = 0u;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int sj = s[4 * pl + j];
-        const bool filled = !fill_is_source(w[j]) && sj != FILL_UNKNOWN && fill_in_box(box, (int)(x0 + (unsigned)j), (int)y, (int)z);
+        const bool filled = !fill_is_source(w[j]) && sj != FILL_UNKNOWN && vox_in_box(box, (int)(x0 + (unsigned)j), (int)y, (int)z);
         const bool written = filled && ((kp[pl] >> (8 * j)) & 0xffu) != 0u;
         n_reached += filled ? 1u : 0u;
         n_written += written ? 1u : 0u;
@@ -338,15 +287,15 @@ __global__ __launch_bounds__(256) void k_fill_count(const uint4* __restrict__ vo
   if (threadIdx.x < 3u && total) atomicAdd(&counts[1u + threadIdx.x], total);
 }
 
-__global__ __launch_bounds__(256) void k_fill_commit(uint4* __restrict__ vol, const uint2* __restrict__ st, const unsigned* __restrict__ mask, FillGeom q,
+__global__ __launch_bounds__(256) void k_fill_commit(uint4* __restrict__ vol, const uint2* __restrict__ st, const unsigned* __restrict__ mask, VolVectors q,
                                                      int fill_weight) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   unsigned x0, y, z;
-  if (!fill_vector(q, i, x0, y, z)) return;
+  if (!vol_vector(q, i, x0, y, z)) return;
   const unsigned m = mask[(size_t)q.g.lin(x0, y, z) >> 2];
   if (m == 0u) return;
   unsigned w[4];
-  fill_words(vol[i], w);
+  vol_words(vol[i], w);
   const uint2 sv = st[i];
   const int s[4] = {(int)(short)(sv.x & 0xffffu), (int)(short)(sv.x >> 16), (int)(short)(sv.y & 0xffffu), (int)(short)(sv.y >> 16)};
 #pragma unroll
@@ -355,101 +304,55 @@ __global__ __launch_bounds__(256) void k_fill_commit(uint4* __restrict__ vol, co
   vol[i] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// the box lo <= (x, y, z) < hi of the mask, row-major
-__global__ __launch_bounds__(256) void k_fill_mask_box(const unsigned char* __restrict__ mask, FillGeom q, FillBox box, unsigned n, unsigned char* __restrict__ out) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const unsigned bx = (unsigned)(box.hi[0] - box.lo[0]), by = (unsigned)(box.hi[1] - box.lo[1]);
-  const unsigned r = i / bx, x = i - r * bx, z = r / by, y = r - z * by;
-  out[i] = mask[q.g.lin(x + (unsigned)box.lo[0], y + (unsigned)box.lo[1], z + (unsigned)box.lo[2])];
-}
-
-static FillGeom fill_geom(const VolParams& vp) {
-  FillGeom q;
-  q.g.X = (unsigned)vp.X;
-  q.g.Y = (unsigned)vp.Y;
-  q.g.Z = (unsigned)vp.Z;
-  q.X4 = (unsigned)vp.X >> 2;
-  q.Zg = ((unsigned)vp.Z + 3u) >> 2;
-  q.ntx = ((unsigned)vp.X + 15u) >> 4;
-  q.nty = ((unsigned)vp.Y + 15u) >> 4;
-  q.ntz = (q.Zg + 1u) >> 1;
-  q.n4 = q.X4 * q.g.Y * q.Zg * 4u;
-  return q;
-}
-static FillBox fill_box(const int lo[3], const int hi[3]) {
-  FillBox b;
-  for (int i = 0; i < 3; ++i) {
-    b.lo[i] = lo[i];
-    b.hi[i] = hi[i];
-  }
-  return b;
-}
-static unsigned fill_quads(const FillGeom& q) { return q.X4 * q.g.Y * q.g.Z; }
-
 size_t fill_layout(const VolParams& vp, void* base, FillBufs* b) {
-  const FillGeom q = fill_geom(vp);
+  const VolTiles q = vol_tiles(vp);
   const size_t n_tiles = (size_t)q.ntx * q.nty * q.ntz;
-  size_t bytes = 0;
-  auto take = [&](size_t n) {
-    char* p = base ? (char*)base + bytes : nullptr;
-    bytes += (n + 255) & ~(size_t)255;
-    return p;
-  };
+  ScratchCarve c{base};
   FillBufs out;
-  out.counts = (unsigned*)take((FILL_COUNTS + 256) * 4);
-  out.tile_free = (unsigned char*)take(n_tiles * 256);
-  out.cand = (unsigned char*)take(n_tiles);
-  out.flag[0] = (unsigned char*)take(n_tiles);
-  out.flag[1] = (unsigned char*)take(n_tiles);
-  out.state[0] = (short*)take(hsk_vol_words(vp) * 2);
-  out.state[1] = (short*)take(hsk_vol_words(vp) * 2);
+  out.counts = (unsigned*)c.take((FILL_COUNTS + 256) * 4);
+  out.tile_free = (unsigned char*)c.take(n_tiles * 256);
+  out.cand = (unsigned char*)c.take(n_tiles);
+  out.flag[0] = (unsigned char*)c.take(n_tiles);
+  out.flag[1] = (unsigned char*)c.take(n_tiles);
+  out.state[0] = (short*)c.take(hsk_vol_words(vp) * 2);
+  out.state[1] = (short*)c.take(hsk_vol_words(vp) * 2);
   out.n_tiles = (unsigned)n_tiles;
   if (b) *b = out;
-  return bytes;
+  return c.bytes;
 }
 
 void launch_fill_init(hipStream_t s, const void* vol, const VolParams& vp, const int lo[3], const int hi[3], const FillBufs& b) {
-  const FillGeom q = fill_geom(vp);
+  const VolTiles q = vol_tiles(vp);
   (void)hipMemsetAsync(b.counts, 0, (FILL_COUNTS + 256) * 4, s);
-  hipLaunchKernelGGL(k_fill_init, dim3(b.n_tiles), dim3(256), 0, s, (const uint4*)vol, q, fill_box(lo, hi), (uint4*)b.state[0], (uint4*)b.state[1], b.tile_free,
+  hipLaunchKernelGGL(k_fill_init, dim3(b.n_tiles), dim3(256), 0, s, (const uint4*)vol, q, vox_box(lo, hi), (uint4*)b.state[0], (uint4*)b.state[1], b.tile_free,
                      b.cand, b.flag[0], b.flag[1], b.counts);
 }
 
 void launch_fill_round(hipStream_t s, const VolParams& vp, const FillBufs& b, int it) {
-  const FillGeom q = fill_geom(vp);
+  const VolTiles q = vol_tiles(vp);
   const int rd = (it - 1) & 1, wr = it & 1;
   hipLaunchKernelGGL(k_fill_round, dim3(b.n_tiles), dim3(256), 0, s, (const short*)b.state[rd], (uint4*)b.state[wr], q, (const unsigned char*)b.tile_free,
                      (const unsigned char*)b.cand, (const unsigned char*)b.flag[rd], b.flag[wr], b.counts + FILL_COUNTS + it, b.counts + 4);
 }
 
 void launch_fill_keep(hipStream_t s, const VolParams& vp, const FillBufs& b, int fin, int band) {
-  const FillGeom q = fill_geom(vp);
-  const dim3 grid((fill_quads(q) + 255u) / 256u);
+  const VolTiles q = vol_tiles(vp);
   unsigned char* m0 = fill_mask_bytes(vp, b, fin);
-  unsigned char* m1 = fill_keep_bytes(vp, b, fin);
   hipLaunchKernelGGL(k_fill_cross, dim3(b.n_tiles), dim3(256), 0, s, (const short*)b.state[fin], q, (unsigned*)m0);
-  hipLaunchKernelGGL(k_fill_dilate, grid, dim3(256), 0, s, (const unsigned char*)m0, q, 0, band, (unsigned*)m1);
-  hipLaunchKernelGGL(k_fill_dilate, grid, dim3(256), 0, s, (const unsigned char*)m1, q, 1, band, (unsigned*)m0);
-  hipLaunchKernelGGL(k_fill_dilate, grid, dim3(256), 0, s, (const unsigned char*)m0, q, 2, band, (unsigned*)m1);
+  launch_mask_dilate3(s, vp, m0, fill_keep_bytes(vp, b, fin), band);  // (the result: the keep bytes)
 }
 
 void launch_fill_count(hipStream_t s, const void* vol, const VolParams& vp, const int lo[3], const int hi[3], const FillBufs& b, int fin, bool keep_all) {
-  const FillGeom q = fill_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   hipLaunchKernelGGL(k_fill_count, dim3(((q.n4 >> 2) + 1023u) / 1024u), dim3(256), 0, s, (const uint4*)vol, (const uint4*)b.state[fin],
-                     keep_all ? (const unsigned*)nullptr : (const unsigned*)fill_keep_bytes(vp, b, fin), q, fill_box(lo, hi), (unsigned*)fill_mask_bytes(vp, b, fin),
+                     keep_all ? (const unsigned*)nullptr : (const unsigned*)fill_keep_bytes(vp, b, fin), q, vox_box(lo, hi), (unsigned*)fill_mask_bytes(vp, b, fin),
                      b.counts);
 }
 
 void launch_fill_commit(hipStream_t s, void* vol, const VolParams& vp, const FillBufs& b, int fin, int fill_weight) {
-  const FillGeom q = fill_geom(vp);
+  const VolVectors q = vol_vectors(vp);
   hipLaunchKernelGGL(k_fill_commit, dim3((q.n4 + 255u) / 256u), dim3(256), 0, s, (uint4*)vol, (const uint2*)b.state[fin],
                      (const unsigned*)fill_mask_bytes(vp, b, fin), q, fill_weight);
-}
-
-void launch_fill_mask_box(hipStream_t s, const unsigned char* mask, const VolParams& vp, const int lo[3], const int hi[3], size_t n, unsigned char* out) {
-  const FillGeom q = fill_geom(vp);
-  hipLaunchKernelGGL(k_fill_mask_box, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mask, q, fill_box(lo, hi), (unsigned)n, out);
 }
 
 int fill_warm() {

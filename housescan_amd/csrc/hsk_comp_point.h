@@ -46,6 +46,14 @@ struct CompGrid {
     return at_xyz(x, y, z);
   }
 };
+// the voxels lo <= (x, y, z) < hi of such a grid
+struct VoxBox {
+  int lo[3], hi[3];
+};
+HSK_HD VoxBox vox_box(const int lo[3], const int hi[3]) { return VoxBox{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}}; }
+HSK_HD bool vox_in_box(const VoxBox& b, int x, int y, int z) {
+  return x >= b.lo[0] && x < b.hi[0] && y >= b.lo[1] && y < b.hi[1] && z >= b.lo[2] && z < b.hi[2];
+}
 // a table indexed by the label itself (a tile's labels in LDS)
 struct CompDirect {
   HSK_HD_MEMBER size_t at(unsigned l) const { return (size_t)l; }

@@ -329,10 +329,12 @@ int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who)
 // ---- api_components.hip ----
 int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want);  // a device buffer of at least `want` bytes, its content not kept
 // ---- api_clearance.hip ----
-// the parameters a clearance call works with (NULL: the defaults), checked -> the kernels' block; the state such a call needs; the
-// field of the volume as it stands, in d_clear (*reused: nothing had to be launched)
+// the parameters a clearance call works with (NULL: the defaults), checked -> the kernels' block; the field of the volume as it
+// stands, in d_clear (*reused: nothing had to be launched)
 int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who, hsk_clearance_params* p, ClearGeom* q);
-int clear_state_check(hsk_ctx* k, const char* who);
+// the state a pass over a whole volume needs of k, reported in `errs`: require_whole_volume's and require_idle's refusals, and a
+// volume lin can number (HSK_ERR_ARG: "<who>: the volume has more than 2^31 voxels")
+int volume_state_check(hsk_ctx* k, hsk_ctx* errs, const char* who);
 int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused);
 void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]);
 // the box a read works on (NULL: the whole volume) in *b and its voxels in *n, or HSK_ERR_ARG: "<who>: the box must satisfy ..."
@@ -344,9 +346,13 @@ struct FloorGrid {
   unsigned nu, nv, w[3];
 };
 int clear_floor_grid(hsk_ctx* k, const ClearGeom& q, int axis, int lo, int hi, const char* who, FloorGrid* f);
-// n > 0 points (packed triples) go to the product buffer, launch(device points, device words) gathers a word a point, the n words
-// come back into out
-int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*)>& launch);
+// the tail of a box download: the n voxels of the checked box b of a row-major device field (elem_bytes 1 or 4 a voxel) into out.
+// n == 0: nothing; the whole volume: one copy; else through the product buffer
+int download_rows(hsk_ctx* k, const void* field, size_t elem_bytes, const hsk_voxel_box& b, size_t n, void* out);
+// n > 0 points (packed triples) go to the product buffer, launch(device points, device words, device bytes) gathers a word a point
+// and -- bytes not null -- a byte a point, the n words come back into out (may be null) and the n bytes into bytes
+int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const std::function<void(const float*, unsigned*, unsigned char*)>& launch,
+                  uint8_t* bytes = nullptr);
 // ---- api_reach.hip ----
 // The rounds of a tile relaxation: while the current worklist holds tiles -- n_active at first, in list 0 --, launch_round(cur, its
 // length) relaxes them and fills the other list, whose length the host then reads from lengths[cur ^ 1] on the device.  *rounds and

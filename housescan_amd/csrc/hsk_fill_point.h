@@ -21,16 +21,8 @@ HSK_HD int fill_source_value(unsigned word) {
 // the state a voxel starts with
 HSK_HD int fill_initial(unsigned word) { return fill_is_source(word) ? fill_source_value(word) : FILL_UNKNOWN; }
 
-// the voxels lo <= (x, y, z) < hi
-struct FillBox {
-  int lo[3], hi[3];
-};
-HSK_HD bool fill_in_box(const FillBox& b, int x, int y, int z) {
-  return x >= b.lo[0] && x < b.hi[0] && y >= b.lo[1] && y < b.hi[1] && z >= b.lo[2] && z < b.hi[2];
-}
-
-// One Jacobi step of a non-source voxel inside the box: s[0] its own state, s[1..6] its face neighbours' (FILL_UNKNOWN for one
-// outside the grid), all of the previous iteration.  With K the KNOWN ones among the seven, n = |K| and U the sum of
+// One Jacobi step of a non-source voxel inside the box (a VoxBox, hsk_comp_point.h): s[0] its own state, s[1..6] its face neighbours'
+// (FILL_UNKNOWN for one outside the grid), all of the previous iteration.  With K the KNOWN ones among the seven, n = |K| and U the sum of
 // value + 32768 over K: FILL_UNKNOWN when n = 0, else (2 U + n) div (2 n) - 32768 -- the mean, half rounded up.  (U <= 7 * 65535:
 // no overflow.  Every term lies in 1..65535, so does the mean: the result is never FILL_UNKNOWN.)
 HSK_HD int fill_step(const int s[7]) {

@@ -3,6 +3,18 @@
 #include "hsk_dev.h"
 #include "hsk_icp_dev.h"
 
+// what the *_layout functions below carve a pass's scratch with: take(n) -> the next array of n bytes, 256-byte aligned, of the
+// device buffer at `base` (null: the sizes only); `bytes`: what has been taken
+struct ScratchCarve {
+  void* base;
+  size_t bytes = 0;
+  char* take(size_t n) {
+    char* p = base ? (char*)base + bytes : nullptr;
+    bytes += (n + 255) & ~(size_t)255;
+    return p;
+  }
+};
+
 // volume
 void launch_integrate(hipStream_t s, void* vol, const float* scaled, const TrackState* st, const VolParams& vp, int W,
                       int H, Intr in, bool count_only, unsigned long long* counter, unsigned* flags,
@@ -136,6 +148,13 @@ unsigned cover_census_blocks(const CoverSweep& g);
 void launch_cover_census(hipStream_t s, const void* vol, const CoverSweep& g, unsigned long long* partial, unsigned long long* out10);
 int cover_warm();     // loads cover.hip's code object (hsk_prepare_readout); a hipError_t
 
+// what the passes over a WHOLE volume share (volume_sweep.hip; hsk_vol_sweep.h the device text).  A row-major byte volume of zeros
+// and ones dilated by the Chebyshev radius r <= 8, an axis a launch: x a -> b, y b -> a, z a -> b -- the result is in b, a is
+// overwritten.  The n > 0 elements (elem_bytes 1 or 4 each) of the box lo <= (x, y, z) < hi of a row-major field, row-major.
+void launch_mask_dilate3(hipStream_t s, const VolParams& vp, unsigned char* a, unsigned char* b, int r);
+void launch_box_rows(hipStream_t s, const void* field, size_t elem_bytes, const VolParams& vp, const int lo[3], const int hi[3], size_t n, void* out);
+int sweep_warm();     // loads volume_sweep.hip's code object (hsk_prepare_readout); a hipError_t
+
 // surface components (components.hip) of a WHOLE volume.  The scratch, carved out of one device buffer by
 // comp_layout: `rows` = one word per grid row (y, z) and one more, the rows' root counts, then -- launch_pack_scan in place -- their
 // first root's index; `parent` = one word per volume word, a voxel's at the voxel's own place (hsk_vox_index).
@@ -176,7 +195,6 @@ void launch_clear_build(hipStream_t s, const void* vol, const ClearGeom& q, cons
 // the floor map of the band lo <= p < hi along `axis`: a, b = two arrays of one word per column; the map ends in a
 void launch_clear_floor(hipStream_t s, const void* vol, const VolParams& vp, const ClearGeom& q, int axis, int lo, int hi, unsigned* a, unsigned* b);
 void launch_clear_gather(hipStream_t s, const unsigned* field, const VolParams& vp, const float* xyz, unsigned n, unsigned* out);
-void launch_clear_box(hipStream_t s, const unsigned* field, const VolParams& vp, const int lo[3], const int hi[3], unsigned* out);  // (not empty)
 
 // the reach field (reach.hip) of any X Y Z grid of clearance values -- the volume's field, or a floor map with
 // Z = 1: the grid, its tiles (hsk_reach_point.h: REACH_TILE_*), the two bounds and the 27 move costs; and the scratch, carved out
@@ -427,8 +445,6 @@ void launch_fill_keep(hipStream_t s, const VolParams& vp, const FillBufs& b, int
 void launch_fill_count(hipStream_t s, const void* vol, const VolParams& vp, const int lo[3], const int hi[3], const FillBufs& b, int fin, bool keep_all);
 // the masked voxels' words: (fill_weight << 16) | (value & 0xffff)
 void launch_fill_commit(hipStream_t s, void* vol, const VolParams& vp, const FillBufs& b, int fin, int fill_weight);
-// out[n] = the mask's bytes over the box, row-major
-void launch_fill_mask_box(hipStream_t s, const unsigned char* mask, const VolParams& vp, const int lo[3], const int hi[3], size_t n, unsigned char* out);
 int fill_warm();      // loads fill.hip's code object (hsk_prepare_readout); a hipError_t
 
 // volume differencing (diff.hip) of two WHOLE volumes on one grid.  The scratch, carved out of one device

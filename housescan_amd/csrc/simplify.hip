@@ -56,23 +56,18 @@ size_t simp_layout(const VolParams& vp, int s, void* base, SimpBufs* b) {
   m.crows = m.CY * m.CZ;
   m.cseg = (m.CX + 63) / 64;
   m.frows = (vp.Y - 1) * (vp.Z - 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? (char*)base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  m.totals = (unsigned long long*)take(128);
-  m.ref = (unsigned char*)take((size_t)m.CX * m.crows);
-  m.cl_cnt = (unsigned*)take((size_t)m.crows * 4);
-  m.cl_off = (unsigned long long*)take(hsk_scan_scratch_entries(m.crows) * 8);
-  m.tc_cnt = (unsigned*)take((size_t)m.crows * 4);
-  m.tc_off = (unsigned long long*)take(hsk_scan_scratch_entries(m.crows) * 8);
-  m.segbase = (unsigned short*)take((size_t)m.crows * m.cseg * 2);
-  m.sf_cnt = (unsigned*)take((size_t)m.frows * 4);
-  m.sf_off = (unsigned long long*)take(hsk_scan_scratch_entries(m.frows) * 8);
+  ScratchCarve carve{base};
+  m.totals = (unsigned long long*)carve.take(128);
+  m.ref = (unsigned char*)carve.take((size_t)m.CX * m.crows);
+  m.cl_cnt = (unsigned*)carve.take((size_t)m.crows * 4);
+  m.cl_off = (unsigned long long*)carve.take(hsk_scan_scratch_entries(m.crows) * 8);
+  m.tc_cnt = (unsigned*)carve.take((size_t)m.crows * 4);
+  m.tc_off = (unsigned long long*)carve.take(hsk_scan_scratch_entries(m.crows) * 8);
+  m.segbase = (unsigned short*)carve.take((size_t)m.crows * m.cseg * 2);
+  m.sf_cnt = (unsigned*)carve.take((size_t)m.frows * 4);
+  m.sf_off = (unsigned long long*)carve.take(hsk_scan_scratch_entries(m.frows) * 8);
   if (b) *b = m;
-  return off;
+  return carve.bytes;
 }
 
 template <bool WRITE>

@@ -119,6 +119,10 @@ def shapes():
          dict(min_voxels=20), [(BOTH, 8), (BOTH, 2)], color="both")
     case("identical volumes", boxed, boxed.copy(), room_p, [(BOTH, 2)])
     case("everything changed", flat((9, 24, 24)), flat((9, 24, 24), raw=APP), adopts=[(BOTH, 0)])
+    # the widest halo from two opposite corners of a grid with X = 24 (no multiple of 16) and Z = 9 (one ragged plane group): the x
+    # window runs past both row ends, the y and z windows past both faces
+    small = flat((9, 24, 24))
+    case("halo 8 from two corners", small, painted(small, [(sl(0, 0, 0), APP), (sl(8, 23, 23), VAN)]), adopts=[(BOTH, 8)], color="both")
     # cur has never-observed voxels inside the halo: they are not adopted
     cur = painted(ref, [(sl((5, 9), (6, 10), (4, 8)), APP), (sl((3, 6), (4, 12), (8, 11)), (123, 0)), (sl(9, (5, 11), (3, 9)), (0, 0))])
     case("cur unobserved inside the halo", ref, cur, adopts=[(BOTH, 2), (BOTH, 1)], color="both")

@@ -20,7 +20,7 @@ int main(int argc, char** argv) {
   if (fread(h, 4, 13, f) != 13) return 2;
   const CompGrid g{(unsigned)h[0], (unsigned)h[1], (unsigned)h[2]};
   const int iterations = h[3], keep = h[4], band = h[5], fill_weight = h[6];
-  FillBox box;
+  VoxBox box;
   for (int a = 0; a < 3; ++a) box.lo[a] = h[7 + a], box.hi[a] = h[10 + a];
   // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
   const size_t words = (size_t)g.X * g.Y * ((g.Z + 3u) & ~3u), n = (size_t)g.X * g.Y * g.Z;
@@ -38,7 +38,7 @@ int main(int argc, char** argv) {
         const unsigned w = vol[g.at_xyz((unsigned)x, (unsigned)y, (unsigned)z)];
         const size_t l = g.lin((unsigned)x, (unsigned)y, (unsigned)z);
         cur[l] = (short)fill_initial(w);
-        fr[l] = !fill_is_source(w) && fill_in_box(box, x, y, z);
+        fr[l] = !fill_is_source(w) && vox_in_box(box, x, y, z);
         st[0] += fr[l];
       }
   // a voxel's state and its six face neighbours', FILL_UNKNOWN outside the grid

@@ -3,10 +3,11 @@
 
   scan     the first `--frames` frames of room 0's scripted scan fused at `--n`^3
   calls    host time (ms, median of `--reps`, the first call reported apart, ending in the call's own wait) of hsk_build_clearance
-           behind a volume change and again (reused), of hsk_clearance_at for 4096 points and of hsk_clearance_floor, beside
+           behind a volume change and again (reused), of hsk_clearance_at for 4096 points, of hsk_clearance_floor and of
+           hsk_download_clearance of the box 0.3 n .. 0.8 n on every axis (a partial box: through k_box_rows), beside
            hsk_label_components behind a volume change and hsk_coverage_census on the same volume; the scratch bytes
   kernels  the same work once more in ONE `rocprofv3 --kernel-trace --stats` child (no counters in that run): medians (us) of the
-           k_clear_* kernels beside k_comp_local and k_pack_classify, which stream the same words
+           k_clear_* kernels and k_box_rows beside k_comp_local and k_pack_classify, which stream the same words
   No bar is set: nothing here had been measured before.
 
 usage: python tools/clearance_bench.py [--reps 10] [--n 512] [--frames 60] [--skip kernels] [--out FILE]"""
@@ -24,7 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KERNELS = ("k_clear_rows(", "k_clear_axis<1>", "k_clear_axis<2>", "k_clear_project(", "k_clear_axis_plain(", "k_clear_gather(", "k_comp_local(", "k_pack_classify(",
+KERNELS = ("k_clear_rows(", "k_clear_axis<1>", "k_clear_axis<2>", "k_clear_project(", "k_clear_axis_plain(", "k_clear_gather(", "k_box_rows<", "k_comp_local(", "k_pack_classify(",
            "k_cover_census(")
 
 
@@ -66,6 +67,7 @@ def work(args):
     out["at_4096"] = stat([timed(lambda: trk.clearance_at(pts)) for _ in range(n)])
     lo, hi = int(args.n * 0.3), int(args.n * 0.8)
     out["floor"] = stat([timed(lambda: trk.clearance_floor(1, lo, hi)) for _ in range(n)])
+    out["download_box"] = stat([timed(lambda: trk.download_clearance(box=((lo, lo, lo), (hi, hi, hi)))) for _ in range(n)])
     out["label_components"] = stat([changed(trk.label_components) for _ in range(n)])
     out["coverage_census"] = stat([timed(trk.coverage) for _ in range(n)])
     out["pack_volume"] = stat([changed(trk.pack_volume) for _ in range(n)])

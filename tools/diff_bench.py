@@ -10,7 +10,7 @@ with a box composited into its depth frames; writes profiles/r27/diff_bench.json
            in the same run hsk_label_components behind a volume change, hsk_prune_components and hsk_fuse_volume (cur into ref
            with the identity) on the same volumes
   kernels  the same work once more in ONE `rocprofv3 --kernel-trace` child (no counters in that run): medians (us) and launch
-           counts of the k_diff_* kernels beside the labelling's and k_fuse_sweep; the classification sweep's and the fuse
+           counts of the k_diff_* kernels and k_mask_dilate beside the labelling's and k_fuse_sweep; the classification sweep's and the fuse
            sweep's GB/s over the same nominal traffic (two reads and one write of a volume)
   No bar is set: nobody has measured this before.
 
@@ -29,7 +29,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-KERNELS = ("k_diff_classify", "k_diff_records", "k_diff_box", "k_diff_gather", "k_diff_mark", "k_diff_dilate", "k_diff_adopt", "k_comp_local", "k_comp_merge",
+KERNELS = ("k_diff_classify", "k_diff_records", "k_diff_box", "k_diff_gather", "k_diff_mark", "k_mask_dilate", "k_diff_adopt", "k_comp_local", "k_comp_merge",
            "k_comp_flatten", "k_comp_roots", "k_comp_records", "k_comp_prune", "k_fuse_sweep", "k_fuse_bricks")
 BOX = ((1.3, 1.3, 2.1), (1.7, 1.7, 2.4))       # hangs in front of the wall the first frames look at
 

@@ -11,7 +11,7 @@ it as one JSON object.
            that hold a never-observed voxel) and the scratch's size (fill.hip's fill_layout: two int16 states per stored voxel, 259
            bytes per tile, the counters)
   kernels  the same work once more in ONE `rocprofv3 --kernel-trace` child (no counters in that run): medians (us) and launch
-           counts of the k_fill_* kernels beside k_comp_prune, k_pack_classify and k_cover_census
+           counts of the k_fill_* kernels and k_mask_dilate beside k_comp_prune, k_pack_classify and k_cover_census
   No bar is set: nobody has measured this before.
 
 usage: python tools/fill_bench.py [--reps 10] [--n 512] [--frames 60] [--skip kernels]"""
@@ -29,7 +29,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-FILL_KERNELS = ("k_fill_init", "k_fill_round", "k_fill_cross", "k_fill_dilate", "k_fill_count", "k_fill_commit")
+FILL_KERNELS = ("k_fill_init", "k_fill_round", "k_fill_cross", "k_mask_dilate", "k_fill_count", "k_fill_commit")
 
 
 def timed(fn):
