@@ -328,6 +328,55 @@ class HskAdoptStats(C.Structure):
     _fields_ = [("n_targets", C.c_uint64), ("n_adopted", C.c_uint64), ("n_colored", C.c_uint64)]
 
 
+HSK_SPLIT_NONE, HSK_SPLIT_FLOOR, HSK_SPLIT_CEILING, HSK_SPLIT_WALL, HSK_SPLIT_OTHER, HSK_SPLIT_OBJECT, HSK_SPLIT_MINOR = range(7)
+HSK_KIND_FLOOR, HSK_KIND_CEILING, HSK_KIND_WALL, HSK_KIND_OTHER = 1, 2, 3, 4
+HSK_REMOVE_ERASE, HSK_REMOVE_RESTORE = 0, 1
+HSK_SPLIT_MAX_PLANES, HSK_REMOVE_MAX_OBJECTS = 64, 256
+
+
+class HskSplitPlane(C.Structure):
+    """Mirror of `hsk_split_plane` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [("abcd", C.c_float * 4), ("kind", C.c_int32), ("pad", C.c_int32)]
+
+
+class HskSplitParams(C.Structure):
+    """Mirror of `hsk_split_params` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [("dist_m", C.c_float), ("back_m", C.c_float), ("cos_min", C.c_float), ("pad", C.c_int32), ("min_voxels", C.c_uint64)]
+
+
+class HskObject(C.Structure):
+    """Mirror of `hsk_object` (include/hskinfu.h): 104 bytes."""
+
+    _fields_ = [
+        ("root", C.c_int32 * 3), ("pad", C.c_int32),
+        ("n_voxels", C.c_uint64), ("sum", C.c_uint64 * 3),
+        ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+        ("contact", C.c_uint32 * 4), ("plane_mask", C.c_uint64),
+        ("height_lo", C.c_int32), ("height_hi", C.c_int32),
+    ]
+
+
+class HskSplitStats(C.Structure):
+    """Mirror of `hsk_split_stats` (include/hskinfu.h): 104 bytes."""
+
+    _fields_ = [("n_class", C.c_uint64 * 7), ("n_objects", C.c_uint64), ("n_minor_objects", C.c_uint64), ("largest", C.c_uint64),
+                ("n_edge", C.c_uint64), ("n_no_normal", C.c_uint64), ("reused", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class HskRemoveParams(C.Structure):
+    """Mirror of `hsk_remove_params` (include/hskinfu.h): 12 bytes."""
+
+    _fields_ = [("mode", C.c_int32), ("halo", C.c_int32), ("fill_weight", C.c_int32)]
+
+
+class HskRemoveStats(C.Structure):
+    """Mirror of `hsk_remove_stats` (include/hskinfu.h): 40 bytes."""
+
+    _fields_ = [("n_objects", C.c_uint64), ("n_targets", C.c_uint64), ("n_written", C.c_uint64), ("n_restored", C.c_uint64), ("n_colored", C.c_uint64)]
+
+
 HSK_CLEAR_UNKNOWN = 1
 HSK_CLEAR_MAX_REACH = 255
 HSK_CLEARANCE_FAR, HSK_CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
@@ -551,6 +600,15 @@ SYMBOLS = {
     "hsk_diff_at": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P]),
     "hsk_adopt_diff": (C.c_int, [_P, _P, C.POINTER(HskAdoptParams), C.POINTER(HskAdoptStats)]),
     "hsk_release_diff": (C.c_int, [_P]),
+    "hsk_default_split_params": (None, [_P, C.POINTER(HskSplitParams)]),
+    "hsk_default_remove_params": (None, [_P, C.POINTER(HskRemoveParams)]),
+    "hsk_split_plane_kinds": (C.c_int, [C.POINTER(HskSplitPlane), C.c_size_t, C.POINTER(C.c_float), C.c_float, C.c_float]),
+    "hsk_split_scene": (C.c_int, [_P, C.POINTER(HskSplitPlane), C.c_size_t, C.POINTER(HskSplitParams), C.POINTER(HskObject), C.c_size_t, C.POINTER(C.c_size_t),
+                                  C.POINTER(HskSplitStats)]),
+    "hsk_download_split": (C.c_int, [_P, C.POINTER(HskVoxelBox), _P, _P, _P]),
+    "hsk_split_at": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P]),
+    "hsk_remove_objects": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(HskRemoveParams), C.POINTER(HskRemoveStats)]),
+    "hsk_release_split": (C.c_int, [_P]),
     "hsk_default_clearance_params": (None, [_P, C.POINTER(HskClearanceParams)]),
     "hsk_clearance_d2": (C.c_uint32, [C.POINTER(HskClearanceParams), C.c_float]),
     "hsk_build_clearance": (C.c_int, [_P, C.POINTER(HskClearanceParams), C.POINTER(HskClearanceStats)]),

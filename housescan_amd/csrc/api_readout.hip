@@ -363,6 +363,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) HIPCHK(k, (hipError_t)comp_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)fill_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)diff_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)split_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)sweep_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)simplify_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)level_warm());

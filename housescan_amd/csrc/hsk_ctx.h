@@ -203,6 +203,20 @@ struct hsk_ctx {
   std::vector<hsk_diff_region> diff_recs;
   hsk_diff_stats diff_stats = {};
   hsk_diff_params diff_params = {};
+  // the scene split (hsk_split_scene; split.hip), made by the first call that splits and freed by hsk_release_split: d_split =
+  // split_layout's counters, tables, class words, byte volumes and labelling scratch; d_split_tab = the objects' roots and records
+  // (grown only).  What they hold is the split of this volume at split_epoch (0: nothing) for the planes split_planes and the
+  // parameters split_params, compared as bytes; split_recs the kept objects' records in their order, split_stats the call's stats:
+  // hsk_split_scene answers a call with the same planes and parameters from them
+  void* d_split = nullptr;
+  size_t split_bytes = 0;
+  void* d_split_tab = nullptr;
+  size_t split_tab_bytes = 0;
+  uint64_t split_epoch = 0;
+  std::vector<hsk_split_plane> split_planes;
+  hsk_split_params split_params = {};
+  std::vector<hsk_object> split_recs;
+  hsk_split_stats split_stats = {};
   // the clearance field (hsk_build_clearance; clearance.hip), made by the first call that builds and freed by
   // hsk_release_clearance: d_clear = clear_layout's counters, field and intermediates.  What it holds is the field of the volume
   // at clear_epoch (0: nothing) for the 20 device-relevant parameter bytes in clear_key, and clear_counts its counters

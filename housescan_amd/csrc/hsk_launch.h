@@ -474,3 +474,47 @@ void launch_diff_halo(hipStream_t s, const void* cur, const VolParams& vp, const
 // the masked copy: cur's words into ref and, ref_col not null, cur's colour words (cur_col null: the colour word 0)
 void launch_diff_adopt(hipStream_t s, void* ref, const void* cur, unsigned* ref_col, const unsigned* cur_col, const VolParams& vp, const DiffBufs& b);
 int diff_warm();      // loads diff.hip's code object (hsk_prepare_readout); a hipError_t
+
+// the scene split (split.hip) of a WHOLE volume.  The scratch, carved out of one device buffer by split_layout:
+// the counters, the planes as the host converted them, the removal's selected objects, the class words (one per volume word, in the
+// volume's layout: hsk_split_point.h), two byte volumes (row-major) for the removal, and a labelling scratch of its own
+// (comp_layout: never the one hsk_label_components holds)
+#define SPLIT_COUNTS 16  // [1..5] the classes before the MINOR step, [6] edge-rule voxels, [7] voxels with G = 0, [8] the removal's
+                         // targets, [9] its written and [10] its restored voxels
+// an object's record on the device, SPLIT_REC_WORDS words: three 64-bit sums of x, y, z; the contacts by kind; the 64-bit plane
+// mask; the heights, as ~key and key with key = height ^ 0x80000000 (both only ever raised from 0)
+#define SPLIT_REC_WORDS 16
+#define SPLIT_REC_CONTACT 6
+#define SPLIT_REC_MASK 10
+#define SPLIT_REC_HLO 12
+#define SPLIT_REC_HHI 13
+struct SplitPlaneQ;
+struct SplitRule;
+struct SplitSelected;
+struct SplitBufs {
+  unsigned* counts;
+  SplitPlaneQ* planes;     // SPLIT_MAX_PLANES
+  SplitSelected* sel;      // SPLIT_MAX_SELECTED
+  unsigned* cls;           // hsk_vol_words
+  unsigned char* mask[2];  // X Y Z bytes each
+  CompBufs comp;
+};
+size_t split_layout(const VolParams& vp, void* base /* null: the size only */, SplitBufs* b);
+// the class words of the volume for the planes in b.planes, and counts[1..7]
+void launch_split_classify(hipStream_t s, const void* vol, const VolParams& vp, const SplitBufs& b, const SplitRule& r);
+// behind the labelling and the MINOR step: the records of the kept objects among roots[0, n) (zeros for the others)
+void launch_split_records(hipStream_t s, const VolParams& vp, const SplitBufs& b, unsigned n, const unsigned* roots, unsigned* rec, int floor_plane);
+// the n > 0 voxels of a box, row-major: class bytes and (may be null) plane bytes and labels
+void launch_split_box(hipStream_t s, const VolParams& vp, const SplitBufs& b, const int lo[3], const int hi[3], size_t n, unsigned char* cls,
+                      unsigned char* plane, unsigned* object);
+// hsk_split_at's choice for n > 0 points
+void launch_split_gather(hipStream_t s, const VolParams& vp, const SplitBufs& b, const float* xyz, unsigned n, int radius, unsigned char* cls,
+                         unsigned char* plane, unsigned* object);
+// the removal of the n_sel objects in b.sel (uni: the union of their grown boxes): the halo in mask[1] and counts[8..10]; nothing
+// but the scratch is written
+void launch_split_halo(hipStream_t s, const void* vol, const VolParams& vp, const SplitBufs& b, unsigned n_sel, const int uni_lo[3], const int uni_hi[3],
+                       const SplitRule& r, int mode, int halo, int fill_weight);
+// the masked write of rules 1 and 2 (col not null: a written voxel's colour word becomes 0)
+void launch_split_restore(hipStream_t s, void* vol, unsigned* col, const VolParams& vp, const SplitBufs& b, unsigned n_sel, const int uni_lo[3],
+                          const int uni_hi[3], const SplitRule& r, int mode, int fill_weight);
+int split_warm();     // loads split.hip's code object (hsk_prepare_readout); a hipError_t

@@ -159,6 +159,8 @@ static void free_all(hsk_ctx* k) {
   F(k->d_fill);
   F(k->d_diff);
   F(k->d_diff_tab);
+  F(k->d_split);
+  F(k->d_split_tab);
   F(k->d_clear);
   F(k->d_reach);
   F(k->d_part);

@@ -127,6 +127,64 @@ def default_diff_params(tracker=None, **fields):
     return p
 
 
+SPLIT_NONE, SPLIT_FLOOR, SPLIT_CEILING, SPLIT_WALL, SPLIT_OTHER, SPLIT_OBJECT, SPLIT_MINOR = range(7)
+KIND_FLOOR, KIND_CEILING, KIND_WALL, KIND_OTHER = 1, 2, 3, 4
+REMOVE_ERASE, REMOVE_RESTORE = 0, 1
+SPLIT_FIELDS = ("dist_m", "back_m", "cos_min", "min_voxels")
+REMOVE_FIELDS = ("mode", "halo", "fill_weight")
+SPLIT_PLANE_DTYPE = np.dtype([("abcd", "<f4", (4,)), ("kind", "<i4"), ("pad", "<i4")])     # hsk_split_plane
+OBJECT_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("sum", "<u8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
+                         ("contact", "<u4", (4,)), ("plane_mask", "<u8"), ("height_lo", "<i4"), ("height_hi", "<i4")])     # hsk_object
+
+
+def default_split_params(tracker=None, **fields):
+    """the parameters of split_scene (hsk_default_split_params): dist_m 0.04, back_m = the truncation distance + 0.04, cos_min
+    cos 30 deg, min_voxels = default_prune_params' value for the tracker (without one: the default configuration's); the keywords
+    -- dist_m, back_m, cos_min, min_voxels -- override its fields -> an `_lib.HskSplitParams`"""
+    p = _lib.HskSplitParams()
+    _lib.load().hsk_default_split_params(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in SPLIT_FIELDS:
+            raise TypeError(f"split parameters have no field {name!r}")
+        setattr(p, name, int(val) if name == "min_voxels" else float(val))
+    return p
+
+
+def default_remove_params(tracker=None, **fields):
+    """the parameters of remove_objects (hsk_default_remove_params): REMOVE_RESTORE, halo = clamp(ceil(tau / the smallest cell) + 1,
+    1, 8), fill_weight 1; the keywords -- mode, halo, fill_weight -- override its fields -> an `_lib.HskRemoveParams`"""
+    p = _lib.HskRemoveParams()
+    _lib.load().hsk_default_remove_params(tracker.h if tracker is not None else None, C.byref(p))
+    for name, val in fields.items():
+        if name not in REMOVE_FIELDS:
+            raise TypeError(f"remove parameters have no field {name!r}")
+        setattr(p, name, int(val))
+    return p
+
+
+def split_planes(abcd, kinds=KIND_OTHER):
+    """n planes [n, 4] (a plane_record array's "abcd" will do) with their kinds (one, or n) -> a SPLIT_PLANE_DTYPE array"""
+    a = np.asarray(abcd, np.float32).reshape(-1, 4)
+    out = np.zeros(len(a), SPLIT_PLANE_DTYPE)
+    out["abcd"] = a
+    out["kind"] = kinds
+    return out
+
+
+def split_plane_kinds(planes, up, level_cos=None, wall_sin=None):
+    """sets the kinds of a SPLIT_PLANE_DTYPE array (or of planes [n, 4]) from the up direction (hsk_split_plane_kinds; host only):
+    KIND_FLOOR where the normal lies within level_cos (default cos 15 deg) of up, KIND_CEILING of -up, KIND_WALL within wall_sin
+    (default sin 15 deg) of the horizon, else KIND_OTHER; up is minus row 1 of an upright frame's level matrix -> the array"""
+    pl = np.ascontiguousarray(planes if getattr(planes, "dtype", None) == SPLIT_PLANE_DTYPE else split_planes(planes)).copy()
+    u = (C.c_float * 3)(*[float(v) for v in up])
+    lc = float(np.cos(np.radians(15.0))) if level_cos is None else float(level_cos)
+    ws = float(np.sin(np.radians(15.0))) if wall_sin is None else float(wall_sin)
+    rc = _lib.load().hsk_split_plane_kinds(pl.ctypes.data_as(C.POINTER(_lib.HskSplitPlane)) if len(pl) else None, len(pl), u, lc, ws)
+    if rc != 0:
+        raise KinfuError(f"hsk_split_plane_kinds failed ({rc}): {_lib.load().hsk_last_error(None).decode()}")
+    return pl
+
+
 def default_fill_params(tracker=None, **fields):
     """the parameters of fill_holes (hsk_default_fill_params): iterations = the voxels of 15 cm along the tracker's finest axis
     (without a tracker: the default configuration's), clamped to 1..255 -- gaps up to about 30 cm across close --, keep
@@ -1014,6 +1072,95 @@ class KinfuTracker:
     def release_diff(self):
         """frees the held diff and its scratch (hsk_release_diff)"""
         self._ck(self.lib.hsk_release_diff(self.h))
+
+    # ---- scene split ---------------------------------------------------------------------------------------
+    def default_split_params(self, **fields):
+        return default_split_params(self, **fields)
+
+    def default_remove_params(self, **fields):
+        return default_remove_params(self, **fields)
+
+    @staticmethod
+    def _split_planes(planes):
+        if getattr(planes, "dtype", None) == SPLIT_PLANE_DTYPE:
+            return np.ascontiguousarray(planes)
+        return split_planes(np.zeros((0, 4), np.float32) if planes is None else planes)
+
+    def split_scene(self, planes, params=None, **fields):
+        """which INSIDE voxels belong to the planes (the structure) and which to objects (hsk_split_scene).  planes: a
+        SPLIT_PLANE_DTYPE array (split_planes, split_plane_kinds), at most 64; params: an HskSplitParams (default:
+        default_split_params(self)); the keywords override its fields -> (records, stats): a structured array with OBJECT_DTYPE --
+        root, n_voxels, sum, the box lo, hi (exclusive), contact, plane_mask, height_lo, height_hi -- of the kept objects, ordered
+        by n_voxels descending, ties to the smaller root; stats: n_class [7], n_objects, n_minor_objects, largest, n_edge,
+        n_no_normal, reused.  The split is held in this tracker: download_split, split_at, remove_objects"""
+        p = default_split_params(self) if params is None else _lib.HskSplitParams.from_buffer_copy(params)
+        for name, val in fields.items():
+            if name not in SPLIT_FIELDS:
+                raise TypeError(f"split parameters have no field {name!r}")
+            setattr(p, name, int(val) if name == "min_voxels" else float(val))
+        pl = self._split_planes(planes)
+        ptr = pl.ctypes.data_as(C.POINTER(_lib.HskSplitPlane)) if len(pl) else None
+        n = C.c_size_t(0)
+        st = _lib.HskSplitStats()
+        self._ck(self.lib.hsk_split_scene(self.h, ptr, len(pl), C.byref(p), None, 0, C.byref(n), C.byref(st)))
+        recs = np.zeros(n.value, OBJECT_DTYPE)
+        if n.value:
+            first = int(st.reused)
+            self._ck(self.lib.hsk_split_scene(self.h, ptr, len(pl), C.byref(p), recs.ctypes.data_as(C.POINTER(_lib.HskObject)), n.value, C.byref(n), C.byref(st)))
+            st.reused = first                              # (the fill is always answered from the size query's split)
+        return recs, {"n_class": np.array(list(st.n_class), np.uint64), "n_objects": int(st.n_objects), "n_minor_objects": int(st.n_minor_objects),
+                      "largest": int(st.largest), "n_edge": int(st.n_edge), "n_no_normal": int(st.n_no_normal), "reused": int(st.reused)}
+
+    def download_split(self, box=None, plane=True, object=True):
+        """the held split over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_split) ->
+        (cls [z, y, x] uint8, plane [z, y, x] uint8 or None, object [z, y, x] uint32 or None): a plane is the index of the voxel's
+        plane, 0xff where it has none; an object the root's (z vol_y + y) vol_x + x for OBJECT voxels, COMPONENT_NONE elsewhere;
+        refused once this tracker's volume has changed since the split"""
+        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
+        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        cls = np.empty(shape, np.uint8)
+        pln = np.empty(shape, np.uint8) if plane else None
+        obj = np.empty(shape, np.uint32) if object else None
+        b = self._voxel_box(box)
+        self._ck(self.lib.hsk_download_split(self.h, C.byref(b) if b is not None else None, cls.ctypes.data if cls.size else None,
+                                             pln.ctypes.data if plane and pln.size else None, obj.ctypes.data if object and obj.size else None))
+        return cls, pln, obj
+
+    def split_at(self, xyz, radius=1):
+        """the held split at the world points xyz [n, 3] (hsk_split_at, 2^20 points a call): the nearest voxel with a class within
+        Chebyshev `radius` (0..4) of the point's voxel -> (cls [n] uint8, plane [n] uint8, object [n] uint32); with none, or outside
+        the grid, SPLIT_NONE, 0xff and COMPONENT_NONE"""
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        cls, pln, obj = np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint32)
+        step = _lib.HSK_CLEAR_MAX_POINTS                    # (the call takes 2^20 points: a mesh's vertices go in pieces)
+        for at in range(0, max(len(pts), 1), step):
+            m = min(step, len(pts) - at)
+            self._ck(self.lib.hsk_split_at(self.h, pts[at:].ctypes.data if m else None, m, int(radius), cls[at:].ctypes.data if m else None,
+                                           pln[at:].ctypes.data if m else None, obj[at:].ctypes.data if m else None))
+        return cls, pln, obj
+
+    def remove_objects(self, roots=None, params=None, **fields):
+        """takes kept objects of the held split out of the volume (hsk_remove_objects).  roots: their labels (None: all kept);
+        params: an HskRemoveParams (default: default_remove_params(self)); the keywords -- mode, halo, fill_weight -- override its
+        fields.  REMOVE_RESTORE rewrites what the objects hid from the planes they touched, REMOVE_ERASE only erases -> dict:
+        n_objects, n_targets, n_written, n_restored, n_colored"""
+        p = default_remove_params(self) if params is None else _lib.HskRemoveParams.from_buffer_copy(params)
+        for name, val in fields.items():
+            if name not in REMOVE_FIELDS:
+                raise TypeError(f"remove parameters have no field {name!r}")
+            setattr(p, name, int(val))
+        st = _lib.HskRemoveStats()
+        if roots is None:
+            self._ck(self.lib.hsk_remove_objects(self.h, None, 0, C.byref(p), C.byref(st)))
+        else:
+            r = np.ascontiguousarray(roots, np.uint32).reshape(-1)
+            keep = r if len(r) else np.zeros(1, np.uint32)     # (a pointer that is not NULL: an empty selection, not "all")
+            self._ck(self.lib.hsk_remove_objects(self.h, keep.ctypes.data, len(r), C.byref(p), C.byref(st)))
+        return {name: int(getattr(st, name)) for name in ("n_objects", "n_targets", "n_written", "n_restored", "n_colored")}
+
+    def release_split(self):
+        """frees the held split and its scratch (hsk_release_split)"""
+        self._ck(self.lib.hsk_release_split(self.h))
 
     def resampled_like(self, ref, cur_to_ref=None, color=False):
         """this tracker's volume on ref's grid: a new tracker with ref's configuration, and this volume fused into it with the

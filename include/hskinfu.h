@@ -1062,6 +1062,139 @@ int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params* params, h
 /* frees the held diff and its scratch (the next hsk_diff_volume makes it again); HSK_ERR_ARG: a NULL context */
 int hsk_release_diff(hsk_ctx* ref);
 
+/* ---- Scene split: structure, objects, and the room without them (DESIGN.md 3.24 the kernels, 8r the rule; tests/split_twin.py
+ * restates the rule in numpy).  Every product of the building -- planes, the cuboid, floor plans, clearance, reach, rooms -- is
+ * bent by the furniture in the scan.  hsk_split_scene says which INSIDE voxels belong to given planes (the structure) and groups
+ * the others into objects; hsk_remove_objects takes objects out and rewrites what they hid from the planes they touched.  All
+ * device arithmetic is in integers or in the fixed binary64 products named below: the same bits whatever the launch shape.
+ * PLANES.  n_planes in 0..64 of hsk_split_plane: abcd as hsk_plane_record's (the normal points into the room), kind one of
+ * HSK_KIND_*.  HSK_ERR_ARG: a number not finite, a normal's length outside [0.5, 2], |d| > 64, an unknown kind.  The host converts
+ * once, in binary64 from the binary32 inputs, with rint; c_j are the context's binary32 cells, tau its effective truncation
+ * distance, c_min the smallest cell:  Q_j = rint(a_j c_j 2^29), Q_d = rint(d 2^30), N_j = rint(a_j 4096), front = rint(dist_m 2^30),
+ * back = rint(back_m 2^30), tauq = rint(tau 2^30), w_j = rint(4096 c_min / c_j).  The signed distance of voxel (x, y, z) -- its
+ * centre lies at (index + 1/2) cell -- to plane k, in units of 2^-30 m, int64:
+ *   s_k = Q_x (2 x + 1) + Q_y (2 y + 1) + Q_z (2 z + 1) + Q_d
+ * VOXELS (the whole grid, z < vol_z).  INSIDE: weight != 0 and raw < 0 (the components' rule).  Values r = max(raw, -32767); a voxel
+ * is observed iff its weight != 0.  A voxel that is not INSIDE has the class HSK_SPLIT_NONE.
+ * GRADIENT of an INSIDE voxel, per axis j, from its two neighbours on that axis (outside the grid counts as unobserved): both
+ * observed g_j = r(+1) - r(-1); only +1 observed g_j = 2 (r(+1) - r(0)); only -1 observed g_j = 2 (r(0) - r(-1)); neither 0.
+ * G_j = g_j w_j, int64.
+ * AGAINST PLANE k.  NEAR: -back <= s_k <= front.  ALIGNED: G = 0, or dot = sum G_j N_kj > 0 and (double)dot (double)dot >=
+ * cos2 ((double)|G|^2 (double)|N_k|^2), cos2 = (double)cos_min (double)cos_min; |G|^2 and |N_k|^2 are int64 sums, converted once;
+ * every product is binary64 with no contraction.
+ * CLASS.  m = the planes NEAR, q = the planes NEAR and ALIGNED.  q >= 1: the voxel's plane is the one of least (|s_k|, k) among
+ * those q, its class that plane's kind.  q = 0 and m >= 2: the same among the m planes -- the EDGE RULE: at a floor-wall or
+ * wall-wall edge the gradient is diagonal and agrees with neither plane; without the rule every room edge is a strip of OBJECT
+ * that chains the furniture together.  Otherwise the class is HSK_SPLIT_OBJECT and the plane 0xff.
+ * OBJECTS: the 6-connected components of the OBJECT voxels, labelled by their smallest lin = (z vol_y + y) vol_x + x.  An object
+ * with n_voxels >= min_voxels is KEPT; every voxel of any other object gets the class HSK_SPLIT_MINOR.  Records exist for kept
+ * objects only, ordered by n_voxels descending, ties to the smaller root.  More than HSK_COMPONENT_MAX objects in all:
+ * HSK_ERR_ARG, nothing held.
+ * DEFAULTS (stated choices, not measurements): dist_m = 0.04, back_m = tau + 0.04, cos_min = cos 30 deg, min_voxels =
+ * hsk_default_prune_params' value.  Ranges: dist_m in (0, 1], back_m in (0, 2], cos_min in [0, 1], min_voxels >= 1.
+ * VALIDITY.  The split is held in the context for (its volume, the planes' bytes, the parameters' bytes): the same call again
+ * launches nothing (stats.reused = 1), so a size query followed by the fill splits once.  hsk_download_split, hsk_split_at and
+ * hsk_remove_objects need the volume unchanged since; otherwise HSK_ERR_STATE "<call>: no split is held for the volume as it
+ * stands".  The scratch -- 2.5 times the volume's bytes: the class words, a labelling of its own (never hsk_label_components')
+ * and two byte volumes -- is made by the first call that splits, NOT by hsk_prepare_readout (which only loads the kernels), and
+ * freed by hsk_release_split or hsk_destroy.
+ * REMOVAL.  roots: the labels of up to 256 kept objects (a label named twice counts once); NULL: all kept (more than 256 kept:
+ * HSK_ERR_ARG).  T = the voxels of the selected objects; H = the voxels within Chebyshev `halo` of T; B_o = object o's box grown
+ * by halo and clipped; A(v) = the OR of plane_mask(o) over the selected o with v in B_o.  Per voxel v, in this order:
+ *   1. mode = HSK_REMOVE_RESTORE, A(v) != 0, v in some B_o, and (v in H or weight(v) = 0): the word becomes P(v): s = the least
+ *      s_k(v) over k in A(v); s < -tauq: word 0; else sc = min(s, tauq), raw = floor((65534 sc + tauq) / (2 tauq)) in int64, the
+ *      word (fill_weight << 16) | (raw & 0xffff) -- what an ideal scan of those planes would hold.  Every voxel of H is
+ *      rewritten, structure included.
+ *   2. otherwise, v in T, or v in H and observed and not INSIDE: word 0.
+ *   3. otherwise unchanged.
+ * A written voxel (rule 1 or 2) gets the colour word 0; every other word and colour word stays bit for bit.  When no voxel would
+ * be written nothing is, and cached passes stay valid; otherwise the write follows hsk_prune_components' order (deferred weights
+ * written back, the volume's epoch counted up) and the held split is no longer valid.  The pose and the model maps are not
+ * touched.  Defaults: HSK_REMOVE_RESTORE, halo = clamp(ceil(tau / c_min) + 1, 1, 8), fill_weight = 1.
+ * KNOWN PROPERTIES: the unobserved interior and shadow inside a removed object's grown box become the empty room, including space
+ * nobody saw.  An object without contact (plane_mask = 0) is simply erased.
+ * HSK_ERR_ARG: a NULL argument, more than 2^31 voxels, a parameter out of range, a root that is no kept object's label.
+ * HSK_ERR_STATE: frames in flight, a slab of a group or a context that stores part of its volume, no valid split held.  A refused
+ * call writes nothing. */
+#define HSK_SPLIT_NONE 0
+#define HSK_SPLIT_FLOOR 1
+#define HSK_SPLIT_CEILING 2
+#define HSK_SPLIT_WALL 3
+#define HSK_SPLIT_OTHER 4
+#define HSK_SPLIT_OBJECT 5
+#define HSK_SPLIT_MINOR 6
+#define HSK_KIND_FLOOR 1
+#define HSK_KIND_CEILING 2
+#define HSK_KIND_WALL 3
+#define HSK_KIND_OTHER 4
+#define HSK_REMOVE_ERASE 0
+#define HSK_REMOVE_RESTORE 1
+#define HSK_SPLIT_MAX_PLANES 64
+#define HSK_REMOVE_MAX_OBJECTS 256
+typedef struct hsk_split_plane {
+  float abcd[4];
+  int32_t kind, pad;
+} hsk_split_plane;        /* 24 bytes */
+typedef struct hsk_split_params {
+  float dist_m, back_m, cos_min;
+  int32_t pad;
+  uint64_t min_voxels;
+} hsk_split_params;       /* 24 bytes */
+typedef struct hsk_object {
+  int32_t root[3], pad;   /* x, y, z of the root                                                                                */
+  uint64_t n_voxels;
+  uint64_t sum[3];        /* the sums of the voxels' x, y, z (centroid = sum / n_voxels + 1/2, in cells)                        */
+  int32_t lo[3], hi[3];   /* the voxel bounding box, hi exclusive                                                               */
+  uint32_t contact[4];    /* [kind - 1]: the object's voxels with at least one 6-neighbour of class FLOOR, CEILING, WALL, OTHER */
+  uint64_t plane_mask;    /* bit k: some voxel of the object has a 6-neighbour whose plane is k                                 */
+  int32_t height_lo, height_hi; /* the least and the largest s_f >> 14 (arithmetic; units of 2^-16 m) over the object's voxels,
+                             f the first plane of kind FLOOR in the list; both 0 when there is none                             */
+} hsk_object;             /* 104 bytes */
+typedef struct hsk_split_stats {
+  uint64_t n_class[7];    /* the voxels by final class                                                                          */
+  uint64_t n_objects;     /* kept                                                                                               */
+  uint64_t n_minor_objects, largest;   /* the objects below min_voxels; the voxels of the first record                         */
+  uint64_t n_edge;        /* voxels classed by the edge rule                                                                    */
+  uint64_t n_no_normal;   /* INSIDE voxels with G = 0                                                                           */
+  uint32_t reused, pad;   /* 1: answered from the held split                                                                    */
+} hsk_split_stats;        /* 104 bytes */
+typedef struct hsk_remove_params {
+  int32_t mode, halo, fill_weight;   /* HSK_REMOVE_*; 0..8; 1..128 */
+} hsk_remove_params;      /* 12 bytes */
+typedef struct hsk_remove_stats {
+  uint64_t n_objects;     /* selected                                                                                           */
+  uint64_t n_targets;     /* |T|                                                                                                */
+  uint64_t n_written;     /* the voxels rule 1 or 2 applies to                                                                  */
+  uint64_t n_restored;    /* of them, those whose new word is not 0                                                             */
+  uint64_t n_colored;     /* the colour words set to 0 (n_written with colour enabled, else 0)                                  */
+} hsk_remove_stats;       /* 40 bytes */
+/* the defaults described above for the context's cells and truncation distance; k NULL: hsk_default_config(256)'s */
+void hsk_default_split_params(const hsk_ctx* k, hsk_split_params* p);
+void hsk_default_remove_params(const hsk_ctx* k, hsk_remove_params* p);
+/* host only, binary64: planes[i].kind from the normal and the up direction: t = n . u / (|n| |u|); FLOOR iff t >= level_cos,
+ * CEILING iff t <= -level_cos, WALL iff |t| <= wall_sin, else OTHER.  up is minus row 1 of hsk_upright.level.  The defaults
+ * are cos 15 deg and sin 15 deg.  HSK_ERR_ARG: a NULL pointer (n > 0), a number not finite, a zero normal or up, a threshold
+ * outside [0, 1]. */
+int hsk_split_plane_kinds(hsk_split_plane* planes, size_t n, const float up[3], float level_cos, float wall_sin);
+/* Classifies, labels and tabulates (params NULL: the defaults), holds the result in the context and gives the kept objects'
+ * records in their order.  recs NULL: the counts only (*n_objects, stats).  HSK_ERR_ARG with *n_objects and stats set and no
+ * record written: cap below the count (the split is held all the same).  stats may be NULL. */
+int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t n_planes, const hsk_split_params* params, hsk_object* recs, size_t cap,
+                    size_t* n_objects, hsk_split_stats* stats);
+/* The voxels of the box (NULL: the whole volume), row-major, x fastest: cls = one HSK_SPLIT_* byte each; plane (may be NULL) = the
+ * plane's index for the four structure classes, 0xff elsewhere; object (may be NULL) = the object's root lin for OBJECT voxels,
+ * HSK_COMPONENT_NONE elsewhere, MINOR included.  An empty box writes nothing. */
+int hsk_download_split(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* cls, uint8_t* plane, uint32_t* object);
+/* The split at n <= 2^20 world points (x, y, z triples) -- what tints a cloud or a mesh by class.  A point's voxel is found as
+ * hsk_clearance_at finds it.  Candidates are the voxels within Chebyshev `radius` (0..4) of that voxel whose class is not NONE;
+ * the result is the candidate with the smallest (dx^2 + dy^2 + dz^2, lin): its class, plane and object; with no candidate, or
+ * outside the grid, HSK_SPLIT_NONE, 0xff and HSK_COMPONENT_NONE.  plane and object may be NULL. */
+int hsk_split_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint8_t* plane, uint32_t* object);
+/* Removes objects by the rule above (params NULL: the defaults).  stats may be NULL. */
+int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, const hsk_remove_params* params, hsk_remove_stats* stats);
+/* frees the held split and its scratch (the next hsk_split_scene makes it again); HSK_ERR_ARG: a NULL context */
+int hsk_release_split(hsk_ctx* k);
+
 /* ---- Clearance field: how much room there is -- the exact distance from every voxel to the nearest obstacle, on the device
  * (DESIGN.md 3.18 the kernels, 8l the rule; tests/clearance_twin.py restates the rule in numpy).  All integers.  A voxel is an
  * OBSTACLE when it is the coverage rule's SOLID (observed with a TSDF <= 0); with the flag HSK_CLEAR_UNKNOWN so is every UNSEEN
