@@ -464,6 +464,29 @@ class HskSimplifyStats(C.Structure):
                 ("n_uncolored", C.c_uint64)]
 
 
+HSK_TEXEL_OWNED, HSK_TEXEL_INSIDE, HSK_TEXEL_PROJECTED, HSK_TEXEL_COLORED, HSK_TEXEL_NORMAL = 1, 2, 4, 8, 16
+
+
+class HskTextureParams(C.Structure):
+    """Mirror of `hsk_texture_params` (include/hskinfu.h): 20 bytes."""
+
+    _fields_ = [("texels_per_metre", C.c_float), ("atlas_width", C.c_int32), ("n_iter", C.c_int32), ("f_tol", C.c_float), ("max_offset_m", C.c_float)]
+
+
+class HskTextureChart(C.Structure):
+    """Mirror of `hsk_texture_chart` (include/hskinfu.h): 16 bytes."""
+
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("s", C.c_int32), ("half_rot", C.c_int32)]
+
+
+class HskTextureInfo(C.Structure):
+    """Mirror of `hsk_texture_info` (include/hskinfu.h): 104 bytes."""
+
+    _fields_ = [("width", C.c_uint64), ("height", C.c_uint64), ("n_faces_charted", C.c_uint64), ("n_faces_skipped", C.c_uint64),
+                ("n_blocks", C.c_uint64 * 4), ("n_owned", C.c_uint64), ("n_inside", C.c_uint64), ("n_projected", C.c_uint64),
+                ("n_colored", C.c_uint64), ("n_normal", C.c_uint64)]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -533,6 +556,11 @@ SYMBOLS = {
     "hsk_extract_mesh_indexed": (C.c_int, [_P, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t, C.POINTER(C.c_size_t),
                                             C.POINTER(C.c_size_t)]),
     "hsk_default_simplify_params": (None, [_P, C.POINTER(HskSimplifyParams)]),
+    "hsk_product_capacity": (C.c_size_t, [_P]),
+    "hsk_default_texture_params": (None, [_P, C.POINTER(HskTextureParams)]),
+    "hsk_texture_layout": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_float, C.c_int, _P, _P, C.POINTER(HskTextureInfo)]),
+    "hsk_bake_texture": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskTextureParams), _P, _P, _P, C.c_size_t, _P, _P,
+                                   C.POINTER(HskTextureInfo)]),
     "hsk_extract_mesh_simplified": (C.c_int, [_P, C.POINTER(HskSimplifyParams), _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t,
                                                C.POINTER(C.c_size_t), C.POINTER(HskSimplifyStats)]),
     "hsk_cluster_vertex": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_float, _D, _I, _I]),
@@ -697,6 +725,8 @@ SYMBOLS = {
     "hsk_write_ply_mesh": (C.c_int, [C.c_char_p, _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "hsk_weld_triangles": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_size_t), _P]),
     "hsk_write_ply_indexed": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
+    "hsk_write_ply_textured": (C.c_int, [C.c_char_p, _P, _P, C.c_size_t, _P, C.c_size_t, _P, C.c_char_p]),
+    "hsk_write_png_rgb": (C.c_int, [C.c_char_p, _P, C.c_int, C.c_int]),
     "hsk_voxel_downsample": (C.c_int, [_P, C.c_size_t, C.c_float, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_voxel_downsample_attrs": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_float, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "hsk_write_pcd_xyzrgbnormal": (C.c_int, [C.c_char_p, _P, _P, _P, C.c_size_t]),

@@ -251,6 +251,7 @@ int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom) {
   k->out_bytes = want;
   return HSK_OK;
 }
+extern "C" size_t hsk_product_capacity(const hsk_ctx* k) { return k ? k->out_bytes : 0; }
 // The arrays of one product in the product buffer.  add(host pointer or null, bytes, keep) in order -> the array's number; an
 // array that is neither handed out (a host pointer) nor kept for a device consumer (keep) takes no space.  place() sizes the
 // buffer once; dev<T>(i) is array i's device pointer (null when absent); copy_out() brings the arrays that have a host pointer to
@@ -367,6 +368,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) HIPCHK(k, (hipError_t)sweep_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)simplify_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)level_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)texture_warm());
   return r;
 }
 

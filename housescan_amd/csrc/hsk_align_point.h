@@ -5,10 +5,12 @@
 // operator: both builds forbid contraction.
 #pragma once
 #include "hsk_sample.h"
+#ifndef HSK_UNROLL
 #if defined(__HIPCC__)
 #define HSK_UNROLL _Pragma("unroll")
 #else
 #define HSK_UNROLL
+#endif
 #endif
 
 #define ALIGN_SCALE 67108864.0  // 2^26

@@ -518,3 +518,14 @@ void launch_split_halo(hipStream_t s, const void* vol, const VolParams& vp, cons
 void launch_split_restore(hipStream_t s, void* vol, unsigned* col, const VolParams& vp, const SplitBufs& b, unsigned n_sel, const int uni_lo[3],
                           const int uni_hi[3], const SplitRule& r, int mode, int fill_weight);
 int split_warm();     // loads split.hip's code object (hsk_prepare_readout); a hipError_t
+
+// baked textures (texture.hip) from a WHOLE volume: a wave per 8 x 8 tile of the ta.W x ta.H atlas bakes its
+// texels by hsk_texture_point.h's rule into rgb, nrm (3 bytes a texel) and mask (1), each of which may be null and all of which
+// the caller has cleared; counts: HSK_VIEW_COUNT_SLOTS slots of 16 words, a wave adds its texels by mask bit to words 0 .. 4 of
+// one of them (cleared likewise)
+struct TexArgs;
+struct TexBlock;
+void launch_bake_texture(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const TexArgs& ta, const unsigned* tiles,
+                         const TexBlock* blocks, const int* faces, const float* vertices, unsigned char* rgb, unsigned char* nrm,
+                         unsigned char* mask, unsigned long long* counts);
+int texture_warm();   // loads texture.hip's code object (hsk_prepare_readout); a hipError_t

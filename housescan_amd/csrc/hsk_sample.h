@@ -27,6 +27,9 @@ HSK_HD float hsk_div_by_const(float x, double rc) { return (float)((double)x * r
 
 HSK_HD float hsk_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
+// a unit normal's component as a colour level (HSK_VIEW_NORMALS; the baked normal map of 8s)
+HSK_HD unsigned hsk_normal_level(float n) { return (unsigned)(int)rintf((n * 0.5f + 0.5f) * 255.0f); }
+
 HSK_HD int hsk_min_i(int a, int b) { return a < b ? a : b; }
 HSK_HD int hsk_max_i(int a, int b) { return a > b ? a : b; }
 

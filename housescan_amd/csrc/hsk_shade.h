@@ -135,9 +135,9 @@ static __device__ __forceinline__ bool shade_hit(const ViewCam* __restrict__ cam
     c0 = c1 = c2 = (unsigned)br;
   } else if (tl.mode == HSK_VIEW_NORMALS) {
     if (!hsk_isnan(nx)) {
-      c0 = (unsigned)(int)rintf((nx * 0.5f + 0.5f) * 255.0f);
-      c1 = (unsigned)(int)rintf((ny * 0.5f + 0.5f) * 255.0f);
-      c2 = (unsigned)(int)rintf((nz * 0.5f + 0.5f) * 255.0f);
+      c0 = hsk_normal_level(nx);
+      c1 = hsk_normal_level(ny);
+      c2 = hsk_normal_level(nz);
     }
   } else {
     int gx, gy, gz;

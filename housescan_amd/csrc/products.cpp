@@ -646,21 +646,24 @@ extern "C" int hsk_write_ply_mesh(const char* path, const float* tri_xyz, size_t
 }
 
 // binary little-endian PLY 1.0 of an indexed mesh: per vertex x y z [nx ny nz] [red green blue], interleaved and unpadded (NaN
-// normal components written as 0); per face a uchar 3 and three int indices, every face as given.  The indices are checked
-// before the file is created.
-extern "C" int hsk_write_ply_indexed(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
-                                     const int32_t* faces, size_t n_faces) {
+// normal components written as 0); per face a uchar 3 and three int indices, every face as given -- and, with uv, a uchar 6 and
+// the face's six texture coordinates behind them (the form Meshlab reads, with the atlas named in a comment line).  The indices
+// are checked before the file is created.
+static int write_ply_mesh(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
+                          const int32_t* faces, size_t n_faces, const char* texture_file, const float* uv) {
   if (!path || (n_vertices && !vertices) || (n_faces && !faces)) return HSK_ERR_ARG;
   for (size_t i = 0; i < 3 * n_faces; ++i)
     if (faces[i] < 0 || (size_t)faces[i] >= n_vertices) return HSK_ERR_ARG;
   FILE* f = fopen(path, "wb");
   if (!f) return HSK_ERR_STATE;
-  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n", n_vertices);
+  fprintf(f, "ply\nformat binary_little_endian 1.0\n");
+  if (texture_file) fprintf(f, "comment TextureFile %s\n", texture_file);
+  fprintf(f, "element vertex %zu\nproperty float x\nproperty float y\nproperty float z\n", n_vertices);
   if (normals) fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
   if (rgb) fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-  fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", n_faces);
-  const size_t rec = 12 + (normals ? 12 : 0) + (rgb ? 3 : 0), batch = 8192;
-  std::vector<unsigned char> buf(batch * (rec > 13 ? rec : 13));
+  fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\n%send_header\n", n_faces, uv ? "property list uchar float texcoord\n" : "");
+  const size_t rec = 12 + (normals ? 12 : 0) + (rgb ? 3 : 0), frec = uv ? 38 : 13, batch = 8192;
+  std::vector<unsigned char> buf(batch * (rec > frec ? rec : frec));
   bool ok = true;
   for (size_t i0 = 0; i0 < n_vertices && ok; i0 += batch) {
     const size_t m = n_vertices - i0 < batch ? n_vertices - i0 : batch;
@@ -687,11 +690,99 @@ extern "C" int hsk_write_ply_indexed(const char* path, const float* vertices, co
   for (size_t t0 = 0; t0 < n_faces && ok; t0 += batch) {
     const size_t m = n_faces - t0 < batch ? n_faces - t0 : batch;
     for (size_t j = 0; j < m; ++j) {
-      buf[13 * j] = 3;
-      memcpy(&buf[13 * j + 1], faces + 3 * (t0 + j), 12);
+      buf[frec * j] = 3;
+      memcpy(&buf[frec * j + 1], faces + 3 * (t0 + j), 12);
+      if (uv) {
+        buf[frec * j + 13] = 6;
+        memcpy(&buf[frec * j + 14], uv + 6 * (t0 + j), 24);
+      }
     }
-    ok = fwrite(buf.data(), 13, m, f) == m;
+    ok = fwrite(buf.data(), frec, m, f) == m;
   }
+  const int rc = fclose(f);
+  return (ok && rc == 0) ? HSK_OK : HSK_ERR_STATE;
+}
+extern "C" int hsk_write_ply_indexed(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
+                                     const int32_t* faces, size_t n_faces) {
+  return write_ply_mesh(path, vertices, normals, rgb, n_vertices, faces, n_faces, nullptr, nullptr);
+}
+// ... with the atlas's file name (no line break in it) and the faces' texture coordinates (hsk_bake_texture's uv)
+extern "C" int hsk_write_ply_textured(const char* path, const float* vertices, const float* normals, size_t n_vertices, const int32_t* faces,
+                                      size_t n_faces, const float* uv, const char* texture_file) {
+  if (!texture_file || !*texture_file || strpbrk(texture_file, "\r\n") || (n_faces && !uv)) return HSK_ERR_ARG;
+  return write_ply_mesh(path, vertices, normals, nullptr, n_vertices, faces, n_faces, texture_file, uv);
+}
+
+// 8-bit RGB PNG of a w x h image (rows top to bottom): the zlib stream is made of stored deflate blocks -- no compression, so no
+// library: only the chunks' crc32 and the stream's adler32 are computed
+static uint32_t png_crc(uint32_t c, const unsigned char* p, size_t n) {
+  static uint32_t tab[256];
+  if (!tab[1])
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t v = i;
+      for (int k = 0; k < 8; ++k) v = (v & 1u) ? 0xedb88320u ^ (v >> 1) : v >> 1;
+      tab[i] = v;
+    }
+  for (size_t i = 0; i < n; ++i) c = tab[(c ^ p[i]) & 255u] ^ (c >> 8);
+  return c;
+}
+static void png_be32(unsigned char* p, uint32_t v) {
+  p[0] = (unsigned char)(v >> 24), p[1] = (unsigned char)(v >> 16), p[2] = (unsigned char)(v >> 8), p[3] = (unsigned char)v;
+}
+static bool png_chunk(FILE* f, const char type[4], const unsigned char* data, size_t n) {
+  unsigned char head[8], tail[4];
+  png_be32(head, (uint32_t)n);
+  memcpy(head + 4, type, 4);
+  png_be32(tail, png_crc(png_crc(0xffffffffu, head + 4, 4), data, n) ^ 0xffffffffu);
+  return fwrite(head, 1, 8, f) == 8 && (n == 0 || fwrite(data, 1, n, f) == n) && fwrite(tail, 1, 4, f) == 4;
+}
+extern "C" int hsk_write_png_rgb(const char* path, const uint8_t* rgb, int w, int h) {
+  if (!path || !rgb || w <= 0 || h <= 0) return HSK_ERR_ARG;
+  const size_t row = 1 + 3 * (size_t)w, raw = row * (size_t)h, n_blocks = (raw + 65534) / 65535;
+  const size_t zbytes = 2 + raw + 5 * n_blocks + 4;
+  if (zbytes > 0x7fffffffu) return HSK_ERR_ARG;  // (a chunk's length is 31 bits: one IDAT holds the image)
+  std::vector<unsigned char> z;
+  z.reserve(zbytes);
+  z.push_back(0x78), z.push_back(0x01);
+  uint32_t a = 1, b = 0;
+  size_t in_block = 0, done = 0;  // bytes still to go in the open stored block; filtered bytes written so far
+  auto put = [&](const unsigned char* p, size_t n) {
+    while (n) {
+      if (!in_block) {
+        const size_t len = raw - done < 65535 ? raw - done : 65535;
+        z.push_back(done + len == raw ? 1 : 0);
+        z.push_back((unsigned char)len), z.push_back((unsigned char)(len >> 8));
+        z.push_back((unsigned char)~len), z.push_back((unsigned char)(~len >> 8));
+        in_block = len;
+      }
+      const size_t m = n < in_block ? n : in_block;
+      z.insert(z.end(), p, p + m);
+      for (size_t i = 0; i < m; ++i) {
+        a += p[i];
+        if (a >= 65521u) a -= 65521u;
+        b += a;
+        if (b >= 65521u) b -= 65521u;
+      }
+      p += m, n -= m, in_block -= m, done += m;
+    }
+  };
+  const unsigned char none = 0;  // the filter byte of every row
+  for (int y = 0; y < h; ++y) {
+    put(&none, 1);
+    put(rgb + 3 * (size_t)w * (size_t)y, 3 * (size_t)w);
+  }
+  unsigned char ad[4];
+  png_be32(ad, (b << 16) | a);
+  z.insert(z.end(), ad, ad + 4);
+  FILE* f = fopen(path, "wb");
+  if (!f) return HSK_ERR_STATE;
+  static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+  unsigned char ihdr[13];
+  png_be32(ihdr, (uint32_t)w);
+  png_be32(ihdr + 4, (uint32_t)h);
+  ihdr[8] = 8, ihdr[9] = 2, ihdr[10] = 0, ihdr[11] = 0, ihdr[12] = 0;
+  const bool ok = fwrite(sig, 1, 8, f) == 8 && png_chunk(f, "IHDR", ihdr, 13) && png_chunk(f, "IDAT", z.data(), z.size()) &&
+                  png_chunk(f, "IEND", nullptr, 0);
   const int rc = fclose(f);
   return (ok && rc == 0) ? HSK_OK : HSK_ERR_STATE;
 }

@@ -350,6 +350,34 @@ def cluster_vertex(sums16, cluster_voxels=4, mode=SIMPLIFY_QUADRIC, sv_floor=0.0
     return xyz, rank.value, bool(clamped.value)
 
 
+TEXEL_OWNED, TEXEL_INSIDE, TEXEL_PROJECTED, TEXEL_COLORED, TEXEL_NORMAL = (_lib.HSK_TEXEL_OWNED, _lib.HSK_TEXEL_INSIDE, _lib.HSK_TEXEL_PROJECTED,
+                                                                             _lib.HSK_TEXEL_COLORED, _lib.HSK_TEXEL_NORMAL)
+TEXTURE_INFO_FIELDS = ("width", "height", "n_faces_charted", "n_faces_skipped", "n_blocks", "n_owned", "n_inside", "n_projected", "n_colored", "n_normal")
+TEXTURE_CHART_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("s", np.int32), ("half_rot", np.int32)])
+
+
+def texture_info_dict(info):
+    return {name: ([int(v) for v in getattr(info, name)] if name == "n_blocks" else int(getattr(info, name))) for name in TEXTURE_INFO_FIELDS}
+
+
+def _texture_mesh(vertices, faces):
+    return np.ascontiguousarray(vertices, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+
+
+def texture_layout(vertices, faces, texels_per_metre, atlas_width=0):
+    """the atlas layout of an indexed triangle mesh (hsk_texture_layout; host only, needs no device): two faces to a block of 8,
+    16, 32 or 64 texels by their longest edge at `texels_per_metre`, blocks in Morton order inside 64 x 64 super-tiles across
+    `atlas_width` (0: 1024) -> dict: uv [m, 3, 2] float32 in the faces' corner order (v = 1 at the images' top row), charts
+    [m] TEXTURE_CHART_DTYPE (-1: a skipped face), and hsk_texture_info's fields (the texel counts are a bake's)"""
+    v, f = _texture_mesh(vertices, faces)
+    uv, charts, info = np.zeros((len(f), 3, 2), np.float32), np.zeros(len(f), TEXTURE_CHART_DTYPE), _lib.HskTextureInfo()
+    lib = _lib.load()
+    if lib.hsk_texture_layout(v.ctypes.data, len(v), f.ctypes.data, len(f), texels_per_metre, atlas_width, uv.ctypes.data, charts.ctypes.data,
+                              C.byref(info)) != 0:
+        raise KinfuError((lib.hsk_last_error(None) or b"hsk_texture_layout failed").decode())
+    return dict(texture_info_dict(info), uv=uv, charts=charts)
+
+
 def rank_views(scores):
     """the order of a score_views result: larger gain first; ties to the larger n_frontier, then to the lower index; the poses
     whose eye_state is not 0 (free) behind all others (hsk_rank_views; host only) -> indices [n] uint32"""
@@ -477,6 +505,10 @@ class KinfuTracker:
     def flush_weights(self):
         """write the deferred free-space weights back into the volume (what a read-out does first); enqueued only"""
         self._ck(self.lib.hsk_flush_weights(self.h))
+
+    def product_capacity(self):
+        """the product buffer's size in bytes as it stands (hsk_product_capacity): it only grows"""
+        return int(self.lib.hsk_product_capacity(self.h))
 
     def prepare_readout(self, product_bytes=0):
         """allocate now what a read-out would allocate on its first use (pinned staging, row tables, product buffer)"""
@@ -711,6 +743,30 @@ class KinfuTracker:
         if (nv.value, nf.value) != (len(verts), len(faces)):
             raise KinfuError("extract_mesh_simplified: the counts changed between the two calls")
         return verts, faces, nrm, col, simplify_stats_dict(st)
+
+    # ---- baked textures -------------------------------------------------------------------------------
+    def bake_texture(self, vertices, faces, texels_per_metre=0.0, atlas_width=0, n_iter=4, f_tol=0.01, max_offset_m=0.0, rgb=True,
+                     normal_rgb=False, mask=True):
+        """a colour atlas for an indexed triangle mesh in volume coordinates -- extract_mesh_simplified's, or any other -- baked
+        on the device from the volume as it stands (hsk_bake_texture), legal with frames in flight: texture_layout's charts, every
+        owned texel projected onto the surface and coloured from the colour volume there.  texels_per_metre 0: one texel per
+        voxel; atlas_width 0: 1024; max_offset_m 0: four cells.  -> texture_layout's dict with the texel counts filled and the
+        images asked for: rgb (h, w, 3) uint8 (needs enable_color()), normal_rgb (h, w, 3) uint8, mask (h, w) uint8 of TEXEL_* bits."""
+        v, f = _texture_mesh(vertices, faces)
+        p = _lib.HskTextureParams(texels_per_metre, atlas_width, n_iter, f_tol, max_offset_m)
+        info = _lib.HskTextureInfo()
+        args = (self.h, v.ctypes.data, len(v), f.ctypes.data, len(f), C.byref(p))
+        self._ck(self.lib.hsk_bake_texture(*args, None, None, None, 0, None, None, C.byref(info)))
+        w, h = int(info.width), int(info.height)
+        out = {"rgb": np.empty((h, w, 3), np.uint8) if rgb else None, "normal_rgb": np.empty((h, w, 3), np.uint8) if normal_rgb else None,
+               "mask": np.empty((h, w), np.uint8) if mask else None}
+        uv, charts = np.zeros((len(f), 3, 2), np.float32), np.zeros(len(f), TEXTURE_CHART_DTYPE)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self._ck(self.lib.hsk_bake_texture(*args, ptr(out["rgb"]), ptr(out["normal_rgb"]), ptr(out["mask"]), w * h, uv.ctypes.data, charts.ctypes.data,
+                                           C.byref(info)))
+        if (int(info.width), int(info.height)) != (w, h):
+            raise KinfuError("bake_texture: the atlas changed size between the two calls")
+        return dict(texture_info_dict(info), uv=uv, charts=charts, **{k: a for k, a in out.items() if a is not None})
 
     # ---- scene views ----------------------------------------------------------------------------------
     def default_view(self):

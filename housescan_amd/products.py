@@ -176,6 +176,27 @@ def write_ply_indexed(path, vertices, faces, normals=None, rgb=None):
                                   None if col is None else col.ctypes.data, len(v), f.ctypes.data, len(f)), "hsk_write_ply_indexed")
 
 
+def write_ply_textured(path, vertices, faces, uv, texture_file, normals=None):
+    """indexed mesh with per-face texture coordinates -> binary little-endian .ply that names its atlas in a "comment TextureFile"
+    line: x y z [nx ny nz] per vertex, per face the indices and six floats texcoord (KinfuTracker.bake_texture's uv)"""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    t = np.ascontiguousarray(uv, np.float32).reshape(-1, 6)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(t) != len(f) or (nrm is not None and len(nrm) != len(v)):
+        raise ValueError("write_ply_textured: uv needs one row per face, normals one per vertex")
+    _ck(_lib.load().hsk_write_ply_textured(os.fsencode(path), v.ctypes.data, None if nrm is None else nrm.ctypes.data, len(v), f.ctypes.data, len(f),
+                                           t.ctypes.data, os.fsencode(texture_file)), "hsk_write_ply_textured")
+
+
+def write_png_rgb(path, rgb):
+    """(h, w, 3) uint8 image -> 8-bit RGB PNG with stored (uncompressed) deflate blocks: KinfuTracker.bake_texture's rgb"""
+    a = np.ascontiguousarray(rgb, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("write_png_rgb: an (h, w, 3) uint8 array is needed")
+    _ck(_lib.load().hsk_write_png_rgb(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0]), "hsk_write_png_rgb")
+
+
 def write_ppm(path, rgb):
     """(h, w, 3) uint8 image -> binary PPM (P6): KinfuTracker.render_view's rgb"""
     a = np.ascontiguousarray(rgb, np.uint8)

@@ -140,6 +140,9 @@ int hsk_download_scaled_depth(hsk_ctx* k, float* out);
  * calls this once from the worker thread that created the context: the first hsk_extract_* then costs what every later
  * one does (it was 7 ms against 0.7).  Optional; idempotent; the buffers still grow on demand. */
 int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes);
+/* the product buffer's size in bytes as it stands (0: not made yet, or k NULL): it only grows, by a quarter more than what is asked
+ * for, so a call that leaves it unchanged has allocated none of it */
+size_t hsk_product_capacity(const hsk_ctx* k);
 /* TSDF zero-crossing cloud: packed float32 xyz (the layout of Cloud.cloudPoints, Main.hs:120) in voxel order. */
 int hsk_extract_cloud(hsk_ctx* k, float* xyz, size_t cap_points, size_t* n_points);
 /* TSDF zero level set as a triangle soup, 9 floats per triangle, marching tetrahedra (6 Kuhn tetrahedra per cube),
@@ -275,6 +278,80 @@ int hsk_extract_mesh_simplified(hsk_ctx* k, const hsk_simplify_params* params, f
  * cluster_voxels, mode and sv_floor (0: the defaults). */
 int hsk_cluster_vertex(const int64_t sums[16], int cluster_voxels, int mode, float sv_floor, double xyz_voxels[3], int* rank,
                        int* clamped);
+
+/* ---- Baked textures: a colour atlas for any indexed triangle mesh in volume coordinates -- hsk_extract_mesh_simplified's, or one
+ * that never came from this library -- at the colour volume's own density, sampled on the device (DESIGN.md 3.25 the kernel, 8s
+ * the rule in full; hsk_texture_point.h is its text, for host and device alike).
+ *   layout (hsk_texture_layout; host only, integers and binary64 in a fixed order): a face is SKIPPED -- no chart, uv 0, counted in
+ *     n_faces_skipped -- when an index is out of range or repeated, a coordinate is not finite, or L2 = 0, L2 the largest squared
+ *     edge length ((dx dx + dy dy) + dz dz of the coordinates' exact binary64 differences).  T = L2 (tpm tpm); the face's block
+ *     side s is the smallest of 8, 16, 32, 64 with (s - 5)^2 >= T, else 64.  Edge k joins corners k and k + 1 mod 3; r is the
+ *     corner opposite the longest edge (the lowest on a tie) and chart corner j holds face corner (j + r) mod 3, so r sits at the
+ *     chart's right angle.  The faces of one size, in ascending index, pair up two to a block of s x s texels (half A, then half
+ *     B; an odd last face leaves B empty); blocks are placed largest size first at a running offset counted in 8 x 8-texel tiles
+ *     that grows by (s / 8)^2 per block: offset >> 6 numbers a 64 x 64 super-tile, row-major across the width W, and the low 6
+ *     bits are a Morton code inside it (x the even bits), so every block is aligned to its size.  H = 64 ceil(super-tiles / (W /
+ *     64)); H > 16384 is refused (HSK_ERR_ARG) with the needed H in info.height, so that a caller can lower the density.
+ *     Inside a block, texel (i, j) has its centre at (i + 1/2, j + 1/2); half A owns the texels with i + j <= s - 2, half B the
+ *     rest; A's chart corners are (1, 1), (s - 4, 1), (1, s - 4), B's the point mirror (s - x, s - y): a bilinear look-up anywhere
+ *     inside a face's uv triangle touches only texels that the face owns.  uv: u = x / W, v = 1 - y / H (row 0 of the images is
+ *     the top), formed in binary64 and rounded once, in the face's corner order.
+ *   texel: an unowned texel (no block, or the empty half B) is (0, 0, 0) with mask 0.  Otherwise (x, y) is the texel's centre
+ *     in its block (mirrored in half B), u = (x - 1) / (s - 5), v = (y - 1) / (s - 5), P0 = (c0 + u (c1 - c0)) + v (c2 - c0) with
+ *     the chart's corners -- ALSO for owned texels outside the triangle, which are not dilated from neighbours but baked at the
+ *     extrapolated point.  P0 is projected onto the TSDF's zero level set by up to n_iter Newton steps P <- P - (F / g.g) g, F the
+ *     trilinear sample (hsk_sample.h) and g its gradient; it has succeeded once |F| <= f_tol, and fails when a sample leaves the
+ *     volume's shell or has a never-observed tap, g.g is not > 0, |P - P0|^2 is not <= max_offset^2, or the steps run out; a
+ *     failed texel stays at P0.  At the final point: rgb = the trilinear mean of the eight colour voxels around it over those that
+ *     have a colour, min(255, (int)(c + 0.5)) per channel ((0, 0, 0) where their weights sum to 0 or the point is outside the
+ *     shell); normal_rgb = g / |g| encoded as HSK_VIEW_NORMALS does ((0, 0, 0) without a valid sample).
+ *   mask: HSK_TEXEL_OWNED | _INSIDE (all three barycentrics >= 0) | _PROJECTED | _COLORED | _NORMAL; info counts each -- the last
+ *     five counts only in a call that bakes (asks for rgb, normal_rgb or mask).
+ *   protocol: every output may be NULL; with all NULL the info only, which is how a caller sizes rgb / normal_rgb (3 W H bytes)
+ *     and mask (W H).  Each output is written whole or not at all: cap_texels < W H with rgb, normal_rgb or mask asked for is
+ *     HSK_ERR_ARG with info set and nothing written.  The read-outs' contract: enqueued on hsk_stream() behind the frames
+ *     submitted so far, nothing the tracker reads is written, the volume stays bit for bit, no flush of the deferred weights (a
+ *     weight is only asked whether it is zero); the mesh, the block records and the tile table go up in one copy into the
+ *     product buffer, the images come back through the pinned pair; a later call of the same size allocates nothing.
+ *   HSK_ERR_ARG: a NULL mesh with n > 0; more than INT32_MAX vertices or faces; texels_per_metre negative or not finite,
+ *     atlas_width no multiple of 64 in 64 .. 16384 (0: 1024), n_iter outside 0 .. 16, f_tol or max_offset_m negative or not
+ *     finite; the cap; the H overflow.
+ *   HSK_ERR_STATE: rgb without hsk_enable_color (normal_rgb and mask need none); a slab of a group or any context that stores
+ *     part of its volume. */
+#define HSK_TEXEL_OWNED 1
+#define HSK_TEXEL_INSIDE 2
+#define HSK_TEXEL_PROJECTED 4
+#define HSK_TEXEL_COLORED 8
+#define HSK_TEXEL_NORMAL 16
+typedef struct hsk_texture_params {
+  float texels_per_metre;  /* 0: the default, 1 / the smallest cell -- one texel per voxel                                     */
+  int32_t atlas_width;     /* W: a multiple of 64 in 64 .. 16384; 0: the default, 1024                                         */
+  int32_t n_iter;          /* Newton steps at most, 0 .. 16 (hsk_default_texture_params: 4); taken as it is                   */
+  float f_tol;             /* |F| <= f_tol is on the surface, in units of tau (hsk_default_texture_params: 0.01); as it is     */
+  float max_offset_m;      /* how far the projection may move a texel's point; 0: the default, 4 x the largest cell           */
+} hsk_texture_params;      /* 20 bytes */
+typedef struct hsk_texture_chart {
+  int32_t x0, y0;          /* the block's first texel                                                                          */
+  int32_t s;               /* its side                                                                                         */
+  int32_t half_rot;        /* half (0: A, 1: B) | rotation r << 8                                                              */
+} hsk_texture_chart;       /* 16 bytes; all four -1 for a skipped face */
+typedef struct hsk_texture_info {
+  uint64_t width, height;                    /* W, H (the H the mesh needs, also where it is refused)                          */
+  uint64_t n_faces_charted, n_faces_skipped;
+  uint64_t n_blocks[4];                      /* blocks of side 8, 16, 32, 64                                                   */
+  uint64_t n_owned, n_inside, n_projected, n_colored, n_normal;  /* texels by mask bit (a call that bakes)                     */
+} hsk_texture_info;        /* 104 bytes */
+/* texels_per_metre = atlas_width = 0 and max_offset_m = 0 (the defaults above), n_iter = 4, f_tol = 0.01; k may be NULL */
+void hsk_default_texture_params(const hsk_ctx* k, hsk_texture_params* p);
+/* The layout alone: host only, needs no device and no context (errors: hsk_last_error(NULL)).  texels_per_metre must be > 0 here
+ * (there is no volume to take the default from); atlas_width 0: 1024.  uv (6 per face), charts (one per face) and info may each
+ * be NULL. */
+int hsk_texture_layout(const float* vertices, size_t n_vertices, const int32_t* faces, size_t n_faces, float texels_per_metre,
+                       int atlas_width, float* uv, hsk_texture_chart* charts, hsk_texture_info* info);
+int hsk_bake_texture(hsk_ctx* k, const float* vertices /* 3 per vertex */, size_t n_vertices, const int32_t* faces /* 3 per face */,
+                     size_t n_faces, const hsk_texture_params* params /* NULL: the defaults */, uint8_t* rgb /* 3 W H */,
+                     uint8_t* normal_rgb /* 3 W H */, uint8_t* mask /* W H */, size_t cap_texels, float* uv /* 6 per face */,
+                     hsk_texture_chart* charts /* one per face */, hsk_texture_info* info);
 
 /* ---- Scene views: what has been fused so far, as an image from any camera (upstream's generateImage / generateDepth and its
  * colour view; DESIGN.md 3.8 the kernel, 8b the rule).  One call marches the TSDF from a virtual pinhole camera, shades the
@@ -1600,6 +1677,17 @@ int hsk_weld_triangles(const float* tri_xyz, size_t n_triangles, float* vertices
  * outside [0, n_vertices): HSK_ERR_ARG and no file; an I/O failure: HSK_ERR_STATE; an empty mesh is valid. */
 int hsk_write_ply_indexed(const char* path, const float* vertices, const float* normals, const uint8_t* rgb, size_t n_vertices,
                           const int32_t* faces, size_t n_faces);
+/* hsk_write_ply_indexed's file for a textured mesh (hsk_bake_texture): a "comment TextureFile <texture_file>" line names the
+ * atlas, the vertices carry no colour, and every face record is followed by a uchar 6 and the face's six floats u0 v0 u1 v1 u2 v2
+ * (property list uchar float texcoord, 38 B per face) -- the form Meshlab reads.  normals may be NULL.  HSK_ERR_ARG also for a
+ * NULL or empty texture_file, one with a line break in it, or uv NULL with n_faces > 0. */
+int hsk_write_ply_textured(const char* path, const float* vertices, const float* normals, size_t n_vertices, const int32_t* faces,
+                           size_t n_faces, const float* uv /* 6 per face */, const char* texture_file);
+/* 8-bit RGB PNG of a w x h image, rows top to bottom (hsk_bake_texture's rgb and normal_rgb as they are): IHDR, one IDAT, IEND.
+ * The zlib stream holds stored (uncompressed) deflate blocks of up to 65535 bytes, so the file is 3 w h + h bytes and a little
+ * more, and nothing but crc32 and adler32 is computed.  HSK_ERR_ARG: a NULL pointer, w or h <= 0, an image whose stream would
+ * not fit one chunk (2^31 bytes); an I/O failure: HSK_ERR_STATE.  hsk_write_ppm writes the same pixels as a PPM. */
+int hsk_write_png_rgb(const char* path, const uint8_t* rgb, int w, int h);
 int hsk_voxel_downsample(const float* xyz, size_t n, float leaf_m, float* out, size_t cap, size_t* n_out);
 /* the same leaves, xyz bit-identical to hsk_voxel_downsample's and in the same order, with the rounded mean colour and the
  * renormalised mean of the non-NaN normals of each leaf (NaN x 3 when it has none).  rgb / normals (inputs) may be NULL,
