@@ -487,6 +487,24 @@ class HskTextureInfo(C.Structure):
                 ("n_colored", C.c_uint64), ("n_normal", C.c_uint64)]
 
 
+HSK_TEXEL_KEYFRAME = 32
+HSK_KEYTEX_BEST, HSK_KEYTEX_BLEND, HSK_KEYTEX_NONE = 0, 1, 255
+
+
+class HskKeytexParams(C.Structure):
+    """Mirror of `hsk_keytex_params` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [("mode", C.c_int32), ("z_min_m", C.c_float), ("z_max_m", C.c_float), ("cos_min", C.c_float), ("border_px", C.c_float),
+                ("occlusion_tol_m", C.c_float), ("blend_floor", C.c_float), ("fallback_volume", C.c_int32)]
+
+
+class HskKeytexInfo(C.Structure):
+    """Mirror of `hsk_keytex_info` (include/hskinfu.h): 48 bytes."""
+
+    _fields_ = [("n_keyframes", C.c_uint64), ("n_keyed", C.c_uint64), ("n_fallback", C.c_uint64), ("n_uncolored", C.c_uint64),
+                ("n_pairs_seen", C.c_uint64), ("n_pairs_occluded", C.c_uint64)]
+
+
 class HskVolumeInfo(C.Structure):
     """Mirror of `hsk_volume_info` (include/hskinfu.h): the header of a sparse volume image ("HSKV")."""
 
@@ -561,6 +579,16 @@ SYMBOLS = {
     "hsk_texture_layout": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_float, C.c_int, _P, _P, C.POINTER(HskTextureInfo)]),
     "hsk_bake_texture": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskTextureParams), _P, _P, _P, C.c_size_t, _P, _P,
                                    C.POINTER(HskTextureInfo)]),
+    "hsk_enable_keyframes": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "hsk_add_keyframe": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int)]),
+    "hsk_keyframe_count": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "hsk_get_keyframe": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "hsk_clear_keyframes": (C.c_int, [_P]),
+    "hsk_release_keyframes": (C.c_int, [_P]),
+    "hsk_keyframe_wanted": (C.c_int, [_P, C.c_size_t, _P, C.c_float, C.c_float]),
+    "hsk_default_keytex_params": (None, [_P, C.POINTER(HskKeytexParams)]),
+    "hsk_bake_texture_keyframes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskTextureParams), C.POINTER(HskKeytexParams), _P, _P, _P, _P,
+                                             C.c_size_t, _P, _P, C.POINTER(HskTextureInfo), C.POINTER(HskKeytexInfo)]),
     "hsk_extract_mesh_simplified": (C.c_int, [_P, C.POINTER(HskSimplifyParams), _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t), _P, C.c_size_t,
                                                C.POINTER(C.c_size_t), C.POINTER(HskSimplifyStats)]),
     "hsk_cluster_vertex": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_float, _D, _I, _I]),

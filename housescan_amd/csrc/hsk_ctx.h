@@ -268,6 +268,12 @@ struct hsk_ctx {
   unsigned long long simp_totals[3] = {0, 0, 0};
   void* d_simp_out = nullptr;
   size_t simp_out_bytes = 0;
+  // the keyframe store (hsk_enable_keyframes; hsk_keytex_point.h: KeyStore), one allocation made there and freed by
+  // hsk_release_keyframes: key_cap slots of key_slot_bytes(key_w, key_h), key_n of them taken; key_rec = the host's copy of the
+  // taken slots' records, 16 floats each (hsk_get_keyframe).  Nothing the tracker reads; hsk_reset leaves it alone
+  void* d_key = nullptr;
+  int key_cap = 0, key_w = 0, key_h = 0, key_n = 0;
+  std::vector<float> key_rec;
 };
 
 #define HIPCHK(k, call)                                                                        \
@@ -373,6 +379,20 @@ int gather_points(hsk_ctx* k, const float* xyz, size_t n, uint32_t* out, const s
 // *tiles: the rounds run and the tiles relaxed.  HSK_ERR_STATE after HSK_REACH_MAX_ROUNDS: "<what> did not settle within ..."
 int relax_rounds(hsk_ctx* k, const std::function<hipError_t(int, unsigned)>& launch_round, const unsigned long long* lengths, unsigned long long n_active,
                  const char* what, uint32_t* rounds, unsigned long long* tiles);
+// ---- api_texture.hip ----
+// hsk_bake_texture (kb null) and hsk_bake_texture_keyframes behind their own checks: the layout, the upload, the launch and the
+// way back.  kb: the store and the rule's parameters, the source plane (may be null) and the call's second info (may be null)
+struct KeyStore;
+struct KeyArgs;
+struct KeyBake {
+  const KeyStore* ks;
+  const KeyArgs* ka;
+  uint8_t* source;
+  hsk_keytex_info* kinfo;
+};
+int texture_bake(hsk_ctx* k, const char* who, const float* vertices, size_t n_vertices, const int32_t* faces, size_t n_faces,
+                 const hsk_texture_params* params, uint8_t* rgb, uint8_t* normal_rgb, uint8_t* mask, size_t cap_texels, float* uv,
+                 hsk_texture_chart* charts, hsk_texture_info* info, const KeyBake* kb);
 // ---- api_readout.hip ----
 int ensure_pinned(hsk_ctx* k);
 void parallel_memcpy(void* dst, const void* src, size_t bytes);

@@ -529,3 +529,13 @@ void launch_bake_texture(hipStream_t s, const void* vol, const unsigned* colv, c
                          const TexBlock* blocks, const int* faces, const float* vertices, unsigned char* rgb, unsigned char* nrm,
                          unsigned char* mask, unsigned long long* counts);
 int texture_warm();   // loads texture.hip's code object (hsk_prepare_readout); a hipError_t
+
+// keyframe textures (keytex.hip): launch_bake_texture with the colour from the keyframes of ks by
+// hsk_keytex_point.h's rule, and the source plane (1 byte a texel, may be null, cleared by the caller like the others -- to
+// HSK_KEYTEX_NONE); a wave adds its texels by mask bit to words 0 .. 5 of its slot, its pairs seen and occluded to words 6 and 7
+struct KeyStore;
+struct KeyArgs;
+void launch_bake_keytex(hipStream_t s, const void* vol, const unsigned* colv, const VolParams& vp, const TexArgs& ta, const KeyStore& ks,
+                        const KeyArgs& ka, const unsigned* tiles, const TexBlock* blocks, const int* faces, const float* vertices,
+                        unsigned char* rgb, unsigned char* nrm, unsigned char* mask, unsigned char* source, unsigned long long* counts);
+int keytex_warm();    // loads keytex.hip's code object (hsk_prepare_readout); a hipError_t

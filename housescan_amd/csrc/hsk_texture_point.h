@@ -182,14 +182,23 @@ HSK_HD void tex_sample(const unsigned* vol, const SampleVol& v, float px, float 
   hsk_sample_values(w, s.f);
 }
 
-// Texel (px, py) of the atlas: vol = the TSDF in the device's block layout, colv = the colour volume, row-major (null: no colour).
-// tiles, blocks, faces and vertices are the layout's and the mesh's.
-HSK_HD void tex_texel(const unsigned* vol, const unsigned* colv, const SampleVol& v, const TexArgs& ta, const unsigned* tiles,
-                      const TexBlock* blocks, const int* faces, const float* vertices, int px, int py, TexelOut& o) {
-  o.mask = 0u;
-  o.rgb[0] = o.rgb[1] = o.rgb[2] = 0u;
-  o.nrm[0] = o.nrm[1] = o.nrm[2] = 0u;
-  o.p[0] = o.p[1] = o.p[2] = 0.0f;
+// What a texel's colour and normal are taken at: its final point (the projection's, or P0 where that failed), the sample there and
+// the mask's OWNED, INSIDE and PROJECTED bits (0: an unowned texel, nothing else set).  tex_texel is this, then tex_colour and
+// tex_normal; the keyframe bake (hsk_keytex_point.h) takes the same point and asks its keyframes for the colour.
+struct TexPoint {
+  unsigned mask;
+  float p[3];
+  TexSample sm;
+};
+
+// Texel (px, py) of the atlas: vol = the TSDF in the device's block layout.  tiles, blocks, faces and vertices are the layout's and
+// the mesh's.
+HSK_HD void tex_point(const unsigned* vol, const SampleVol& v, const TexArgs& ta, const unsigned* tiles, const TexBlock* blocks, const int* faces,
+                      const float* vertices, int px, int py, TexPoint& tp) {
+  tp.mask = 0u;
+  tp.p[0] = tp.p[1] = tp.p[2] = 0.0f;
+  TexSample& sm = tp.sm;
+  sm.valid = false;
   const unsigned tile = tiles[(size_t)(py >> 3) * (size_t)(ta.W >> 3) + (size_t)(px >> 3)];
   if (tile == TEX_EMPTY) return;
   const TexBlock& b = blocks[tile];
@@ -218,7 +227,6 @@ HSK_HD void tex_texel(const unsigned* vol, const unsigned* colv, const SampleVol
   unsigned mask = TEX_OWNED | ((bu >= 0.0f && bv >= 0.0f && bw >= 0.0f) ? TEX_INSIDE : 0u);
   // the projection onto the zero level set: Newton steps along the gradient, from P0
   float qx = p0x, qy = p0y, qz = p0z;
-  TexSample sm;
   bool projected = false;
   for (int it = 0;; ++it) {
     tex_sample(vol, v, qx, qy, qz, sm);
@@ -246,44 +254,63 @@ HSK_HD void tex_texel(const unsigned* vol, const unsigned* colv, const SampleVol
     qx = p0x, qy = p0y, qz = p0z;
     tex_sample(vol, v, qx, qy, qz, sm);
   }
-  o.p[0] = qx, o.p[1] = qy, o.p[2] = qz;
-  const SampleCell& sc = sm.sc;
-  // the colour: the eight taps' trilinear mean over the taps that have a colour, in the blend's term order
-  if (colv && sc.in) {
-    const float a0 = 1.0f - sc.a, b0 = 1.0f - sc.b, e0 = 1.0f - sc.c;
-    const float wt[8] = {a0 * b0 * e0, a0 * b0 * sc.c, a0 * sc.b * e0, a0 * sc.b * sc.c, sc.a * b0 * e0, sc.a * b0 * sc.c, sc.a * sc.b * e0,
-                         sc.a * sc.b * sc.c};
-    const int order[8] = {0, 4, 2, 6, 1, 5, 3, 7};  // dx + 2 dy + 4 dz of each term
-    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
-    HSK_UNROLL
-    for (int k = 0; k < 8; ++k) {
-      const int t = order[k];
-      const unsigned cw = colv[((size_t)(sc.z + (t >> 2)) * (size_t)v.Y + (size_t)(sc.y + ((t >> 1) & 1))) * (size_t)v.X + (size_t)(sc.x + (t & 1))];
-      const float w = (cw >> 24) ? wt[k] : 0.0f;
-      sw = sw + w;
-      sr = sr + w * (float)(cw & 255u);
-      sg = sg + w * (float)((cw >> 8) & 255u);
-      sb = sb + w * (float)((cw >> 16) & 255u);
-    }
-    if (sw > 0.0f) {
-      mask |= TEX_COLORED;
-      o.rgb[0] = (unsigned)hsk_min_i(255, (int)(sr / sw + 0.5f));
-      o.rgb[1] = (unsigned)hsk_min_i(255, (int)(sg / sw + 0.5f));
-      o.rgb[2] = (unsigned)hsk_min_i(255, (int)(sb / sw + 0.5f));
-    }
+  tp.p[0] = qx, tp.p[1] = qy, tp.p[2] = qz;
+  tp.mask = mask;
+}
+
+// the colour at a sample's cell: the eight taps' trilinear mean over the taps that have a colour, in the blend's term order.
+// colv = the colour volume, row-major.  false: the point is outside the shell or no tap has a colour (rgb untouched)
+HSK_HD bool tex_colour(const unsigned* colv, const SampleVol& v, const SampleCell& sc, unsigned rgb[3]) {
+  if (!sc.in) return false;
+  const float a0 = 1.0f - sc.a, b0 = 1.0f - sc.b, e0 = 1.0f - sc.c;
+  const float wt[8] = {a0 * b0 * e0, a0 * b0 * sc.c, a0 * sc.b * e0, a0 * sc.b * sc.c, sc.a * b0 * e0, sc.a * b0 * sc.c, sc.a * sc.b * e0,
+                       sc.a * sc.b * sc.c};
+  const int order[8] = {0, 4, 2, 6, 1, 5, 3, 7};  // dx + 2 dy + 4 dz of each term
+  float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f;
+  HSK_UNROLL
+  for (int k = 0; k < 8; ++k) {
+    const int t = order[k];
+    const unsigned cw = colv[((size_t)(sc.z + (t >> 2)) * (size_t)v.Y + (size_t)(sc.y + ((t >> 1) & 1))) * (size_t)v.X + (size_t)(sc.x + (t & 1))];
+    const float w = (cw >> 24) ? wt[k] : 0.0f;
+    sw = sw + w;
+    sr = sr + w * (float)(cw & 255u);
+    sg = sg + w * (float)((cw >> 8) & 255u);
+    sb = sb + w * (float)((cw >> 16) & 255u);
   }
-  // the normal: the gradient at the final point, to length 1
-  if (sm.valid) {
-    float gx, gy, gz;
-    hsk_sample_gradient(sm.f, sc.a, sc.b, sc.c, v.icell, gx, gy, gz);
-    const float gg = hsk_dot3(gx, gy, gz, gx, gy, gz);
-    if (gg > 0.0f) {
-      const float len = sqrtf(gg);
-      mask |= TEX_NORMAL;
-      o.nrm[0] = hsk_normal_level(gx / len);
-      o.nrm[1] = hsk_normal_level(gy / len);
-      o.nrm[2] = hsk_normal_level(gz / len);
-    }
-  }
-  o.mask = mask;
+  if (!(sw > 0.0f)) return false;
+  rgb[0] = (unsigned)hsk_min_i(255, (int)(sr / sw + 0.5f));
+  rgb[1] = (unsigned)hsk_min_i(255, (int)(sg / sw + 0.5f));
+  rgb[2] = (unsigned)hsk_min_i(255, (int)(sb / sw + 0.5f));
+  return true;
+}
+
+// the normal at a sample: its gradient to length 1, n, and as colour levels, nrm.  false: no valid sample or no gradient (both
+// untouched)
+HSK_HD bool tex_normal(const TexSample& sm, const SampleVol& v, float n[3], unsigned nrm[3]) {
+  if (!sm.valid) return false;
+  float gx, gy, gz;
+  hsk_sample_gradient(sm.f, sm.sc.a, sm.sc.b, sm.sc.c, v.icell, gx, gy, gz);
+  const float gg = hsk_dot3(gx, gy, gz, gx, gy, gz);
+  if (!(gg > 0.0f)) return false;
+  const float len = sqrtf(gg);
+  n[0] = gx / len, n[1] = gy / len, n[2] = gz / len;
+  nrm[0] = hsk_normal_level(n[0]);
+  nrm[1] = hsk_normal_level(n[1]);
+  nrm[2] = hsk_normal_level(n[2]);
+  return true;
+}
+
+// Texel (px, py) of the atlas with its colour from the colour volume colv, row-major (null: no colour)
+HSK_HD void tex_texel(const unsigned* vol, const unsigned* colv, const SampleVol& v, const TexArgs& ta, const unsigned* tiles,
+                      const TexBlock* blocks, const int* faces, const float* vertices, int px, int py, TexelOut& o) {
+  o.rgb[0] = o.rgb[1] = o.rgb[2] = 0u;
+  o.nrm[0] = o.nrm[1] = o.nrm[2] = 0u;
+  TexPoint tp;
+  tex_point(vol, v, ta, tiles, blocks, faces, vertices, px, py, tp);
+  o.mask = tp.mask;
+  o.p[0] = tp.p[0], o.p[1] = tp.p[1], o.p[2] = tp.p[2];
+  if (!(tp.mask & TEX_OWNED)) return;
+  if (colv && tex_colour(colv, v, tp.sm.sc, o.rgb)) o.mask |= TEX_COLORED;
+  float n[3];
+  if (tex_normal(tp.sm, v, n, o.nrm)) o.mask |= TEX_NORMAL;
 }

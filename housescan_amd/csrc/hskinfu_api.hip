@@ -167,6 +167,7 @@ static void free_all(hsk_ctx* k) {
   F(k->d_part_tab);
   F(k->d_simp);
   F(k->d_simp_out);
+  F(k->d_key);
   if (k->h_align) (void)hipHostFree(k->h_align);
   if (k->h_view) (void)hipHostFree(k->h_view);
   for (auto& b : k->ib) F(b.d_rgb);

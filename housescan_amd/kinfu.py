@@ -378,6 +378,21 @@ def texture_layout(vertices, faces, texels_per_metre, atlas_width=0):
     return dict(texture_info_dict(info), uv=uv, charts=charts)
 
 
+TEXEL_KEYFRAME, KEYTEX_BEST, KEYTEX_BLEND, KEYTEX_NONE = _lib.HSK_TEXEL_KEYFRAME, _lib.HSK_KEYTEX_BEST, _lib.HSK_KEYTEX_BLEND, _lib.HSK_KEYTEX_NONE
+KEYTEX_INFO_FIELDS = ("n_keyframes", "n_keyed", "n_fallback", "n_uncolored", "n_pairs_seen", "n_pairs_occluded")
+
+
+def keyframe_wanted(poses, pose, min_translation_m=0.3, min_angle_rad=0.3490658503988659):   # (20 degrees)
+    """the host's keyframe selection rule (hsk_keyframe_wanted; no device): True when `poses` ([n, 4, 4], the keyframes kept so far) is
+    empty or every one of them differs from `pose` by more than min_translation_m in position or by more than min_angle_rad in rotation"""
+    ps = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+    p = np.ascontiguousarray(pose, np.float32).reshape(16)
+    r = _lib.load().hsk_keyframe_wanted(ps.ctypes.data if len(ps) else None, len(ps), p.ctypes.data, min_translation_m, min_angle_rad)
+    if r < 0:
+        raise KinfuError("keyframe_wanted: the thresholds must be finite and not negative")
+    return bool(r)
+
+
 def rank_views(scores):
     """the order of a score_views result: larger gain first; ties to the larger n_frontier, then to the lower index; the poses
     whose eye_state is not 0 (free) behind all others (hsk_rank_views; host only) -> indices [n] uint32"""
@@ -767,6 +782,83 @@ class KinfuTracker:
         if (int(info.width), int(info.height)) != (w, h):
             raise KinfuError("bake_texture: the atlas changed size between the two calls")
         return dict(texture_info_dict(info), uv=uv, charts=charts, **{k: a for k, a in out.items() if a is not None})
+
+    # ---- keyframe textures ---------------------------------------------------------------------------
+    def enable_keyframes(self, cap=64, w=None, h=None):
+        """a device store for up to `cap` (1 .. 255) keyframes of w x h pixels (None: the sensor's size) -- hsk_enable_keyframes"""
+        self._ck(self.lib.hsk_enable_keyframes(self.h, cap, self.cfg.width if w is None else w, self.cfg.height if h is None else h))
+
+    def add_keyframe(self, depth, rgb, pose=None, intr=None):
+        """keep a colour frame with its depth image (uint16 millimetres, 0 invalid: the frame's own, or render_view's depth at the same
+        pose), its camera-to-world pose in the volume's frame (None: get_pose()) and fx fy cx cy (None: the sensor's); legal with
+        frames in flight -> the keyframe's index"""
+        d, c = np.ascontiguousarray(depth, np.uint16), np.ascontiguousarray(rgb, np.uint8)
+        if d.ndim != 2 or c.shape != d.shape + (3,):
+            raise ValueError("add_keyframe: depth must be (h, w) and rgb (h, w, 3)")
+        p = np.ascontiguousarray(self.get_pose() if pose is None else pose, np.float32).reshape(16)
+        k = None if intr is None else np.ascontiguousarray(intr, np.float32).reshape(4)
+        index = C.c_int()
+        self._ck(self.lib.hsk_add_keyframe(self.h, d.ctypes.data, c.ctypes.data, d.shape[1], d.shape[0], p.ctypes.data, None if k is None else k.ctypes.data,
+                                           C.byref(index)))
+        return index.value
+
+    def keyframe_count(self):
+        """-> dict: n, cap, w, h and the store's bytes (all 0 without a store)"""
+        n, cap, w, h, b = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+        self._ck(self.lib.hsk_keyframe_count(self.h, C.byref(n), C.byref(cap), C.byref(w), C.byref(h), C.byref(b)))
+        return dict(n=n.value, cap=cap.value, w=w.value, h=h.value, bytes=int(b.value))
+
+    def get_keyframe(self, index, images=True):
+        """what add_keyframe took -> (pose [4, 4] float32, intr [4] float32, depth (h, w) uint16 or None, rgb (h, w, 3) uint8 or None)"""
+        kc = self.keyframe_count()
+        pose, intr = np.zeros((4, 4), np.float32), np.zeros(4, np.float32)
+        d = np.empty((kc["h"], kc["w"]), np.uint16) if images else None
+        c = np.empty((kc["h"], kc["w"], 3), np.uint8) if images else None
+        self._ck(self.lib.hsk_get_keyframe(self.h, index, pose.ctypes.data, intr.ctypes.data, None if d is None else d.ctypes.data,
+                                           None if c is None else c.ctypes.data))
+        return pose, intr, d, c
+
+    def clear_keyframes(self):
+        """forget the keyframes, keep the store: the caller's duty when the volume's frame is no longer theirs"""
+        self._ck(self.lib.hsk_clear_keyframes(self.h))
+
+    def release_keyframes(self):
+        self._ck(self.lib.hsk_release_keyframes(self.h))
+
+    def default_keytex_params(self):
+        p = _lib.HskKeytexParams()
+        self.lib.hsk_default_keytex_params(self.h, C.byref(p))
+        return p
+
+    def bake_texture_keyframes(self, vertices, faces, texels_per_metre=0.0, atlas_width=0, n_iter=4, f_tol=0.01, max_offset_m=0.0, rgb=True,
+                               normal_rgb=False, mask=True, source=True, **keytex):
+        """bake_texture with the colour from the keyframes (hsk_bake_texture_keyframes): every texel is projected into every keyframe,
+        tested against its depth image, and coloured by the keyframe that sees it best (mode=KEYTEX_BEST) or by the weighted mean of
+        those within blend_floor of the best (KEYTEX_BLEND).  Needs no enable_color(); with one, texels no keyframe passes take the
+        colour volume's colour (fallback_volume).  **keytex: fields of hsk_keytex_params that replace the defaults (mode, z_min_m,
+        z_max_m, cos_min, border_px, occlusion_tol_m, blend_floor, fallback_volume) -> bake_texture's dict plus source (h, w) uint8
+        (the winning keyframe, KEYTEX_NONE: none) and hsk_keytex_info's fields."""
+        v, f = _texture_mesh(vertices, faces)
+        p = _lib.HskTextureParams(texels_per_metre, atlas_width, n_iter, f_tol, max_offset_m)
+        kp = self.default_keytex_params()
+        for name, val in keytex.items():
+            if name not in dict(kp._fields_):
+                raise TypeError(f"bake_texture_keyframes: hsk_keytex_params has no field {name!r}")
+            setattr(kp, name, val)
+        info, kinfo = _lib.HskTextureInfo(), _lib.HskKeytexInfo()
+        args = (self.h, v.ctypes.data, len(v), f.ctypes.data, len(f), C.byref(p), C.byref(kp))
+        self._ck(self.lib.hsk_bake_texture_keyframes(*args, None, None, None, None, 0, None, None, C.byref(info), None))
+        w, h = int(info.width), int(info.height)
+        out = {"rgb": np.empty((h, w, 3), np.uint8) if rgb else None, "normal_rgb": np.empty((h, w, 3), np.uint8) if normal_rgb else None,
+               "mask": np.empty((h, w), np.uint8) if mask else None, "source": np.empty((h, w), np.uint8) if source else None}
+        uv, charts = np.zeros((len(f), 3, 2), np.float32), np.zeros(len(f), TEXTURE_CHART_DTYPE)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self._ck(self.lib.hsk_bake_texture_keyframes(*args, ptr(out["rgb"]), ptr(out["normal_rgb"]), ptr(out["mask"]), ptr(out["source"]), w * h,
+                                                     uv.ctypes.data, charts.ctypes.data, C.byref(info), C.byref(kinfo)))
+        if (int(info.width), int(info.height)) != (w, h):
+            raise KinfuError("bake_texture_keyframes: the atlas changed size between the two calls")
+        return dict(texture_info_dict(info), uv=uv, charts=charts, **{k: int(getattr(kinfo, k)) for k in KEYTEX_INFO_FIELDS},
+                    **{k: a for k, a in out.items() if a is not None})
 
     # ---- scene views ----------------------------------------------------------------------------------
     def default_view(self):

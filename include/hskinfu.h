@@ -353,6 +353,95 @@ int hsk_bake_texture(hsk_ctx* k, const float* vertices /* 3 per vertex */, size_
                      uint8_t* normal_rgb /* 3 W H */, uint8_t* mask /* W H */, size_t cap_texels, float* uv /* 6 per face */,
                      hsk_texture_chart* charts /* one per face */, hsk_texture_info* info);
 
+/* ---- Keyframe textures: the atlas of "Baked textures" with its colour from photographs instead of the colour volume (DESIGN.md
+ * 3.26 the kernel, 8t the rule in full; hsk_keytex_point.h is its text, for host and device alike).  A colour voxel is a running
+ * mean over every frame that saw it and no sharper than a voxel; a keyframe is one colour frame kept whole with its depth image
+ * and its pose.  The bake projects every texel's point into every keyframe, tests it against the keyframe's depth, and takes the
+ * colour of the keyframe that sees it best.  rgb needs NO hsk_enable_color: a depth-only scan can have a picture.
+ *   the store: one device allocation of cap slots made by hsk_enable_keyframes and by nothing later; a slot is a 64-byte record
+ *     (the 12 pose floats that matter, fx fy cx cy), the colour image packed to one 32-bit word a pixel (R | G << 8 | B << 16) and
+ *     the depth image as uint16: 64 + 6 w h bytes rounded up to 256 (hsk_keyframe_count: bytes).  All keyframes share one size.
+ *     A second hsk_enable_keyframes with the same cap, w, h keeps the store and its contents; with others it is HSK_ERR_STATE
+ *     until hsk_release_keyframes.  The store does not depend on the volume: hsk_reset and the reset after a tracking loss leave
+ *     it alone.  THE CALLER clears it (hsk_clear_keyframes) when the volume's frame is no longer the keyframes' frame -- after a
+ *     reset that starts a new scan, a hsk_set_pose into another frame, a volume replaced by an upload, a fusion or a levelled copy.
+ *   hsk_add_keyframe: both images are copied before it returns; the copy is enqueued on hsk_stream() behind the frames submitted
+ *     so far and writes nothing the tracker reads, so it is legal between hsk_submit_frame and hsk_wait_frame.  depth_mm is in the
+ *     sensor's unit, millimetres, 0 = invalid: either the frame's own depth image, or hsk_render_view's depth_mm at the same pose
+ *     -- the model's clean depth, which has no sensor noise and no holes the scan has closed.  pose: camera-to-world, row-major, in
+ *     the volume's frame (a caller who moves the volume pre-multiplies); only its upper three rows are kept.  intr: fx fy cx cy,
+ *     NULL = the context's camera.  *index (may be NULL): the slot taken.  A full store is HSK_ERR_STATE with nothing written; a
+ *     size that is not the store's, a NULL image, a pose entry that is not finite, fx or fy not finite or not positive, cx or cy
+ *     not finite: HSK_ERR_ARG.
+ *   hsk_keyframe_wanted: the host's selection rule, no context, binary64 in a fixed order.  1 when n = 0; else 1 when EVERY
+ *     stored pose i differs from `pose` by more than min_translation_m in position (the root of (dx dx + dy dy) + dz dz) OR by
+ *     more than min_angle_rad in rotation (acos of (trace(Ri^T R) - 1) / 2 clamped to [-1, 1], the trace summed row by row); else
+ *     0.  HSK_ERR_ARG: a threshold negative or not finite, pose NULL, poses NULL with n > 0.
+ *   the bake (hsk_bake_texture_keyframes): the layout, uv, charts, normal_rgb, the texel's point and the mask bits OWNED, INSIDE,
+ *     PROJECTED and NORMAL are hsk_bake_texture's bit for bit, with its protocol (all NULL: the info only; each output written
+ *     whole or not at all; enqueued on hsk_stream(); nothing the tracker reads is written; no flush; a later call of the same size
+ *     allocates nothing) and its refusals.  A texel with HSK_TEXEL_NORMAL is looked up in keyframes k = 0 .. n - 1 in ascending
+ *     order, binary32, one rounding per written operator.  q = the texel's final point, nh = its gradient over its length, R, t
+ *     the keyframe's pose:
+ *       1. d = q - t; x_c, y_c, z_c = dot3(d, column 0, 1, 2 of R), dot3(a, b) = (a0 b0 + a1 b1) + a2 b2; z_min_m <= z_c <= z_max_m.
+ *       2. r2 = dot3(d, d); c = -dot3(nh, d) / sqrtf(r2); c >= cos_min.
+ *       3. u = fx (x_c / z_c) + cx, v likewise (pixel centres at integers); border_px <= u <= (float)(w - 1) - border_px, v against
+ *          h; iu = min((int)u, w - 2), a = u - (float)iu, likewise iv, b.
+ *       4. every tap (iu + i, iv + j), i, j in 0, 1, has depth D != 0 and fabsf(z_c - (float)D * 0.001f) <= occlusion_tol_m; one
+ *          failing tap fails the keyframe for this texel (which also rejects depth edges, holes and whatever walked past the
+ *          lens).  (texel, keyframe) pairs that reach this step count in n_pairs_seen, those that fail it in n_pairs_occluded.
+ *       5. per channel top = c00 + a (c10 - c00), bot = c01 + a (c11 - c01), val = top + b (bot - top); the weight w_k = c / r2.
+ *     HSK_KEYTEX_BEST: the keyframe of the largest w_k, the lowest index on a tie; rgb = min(255, (int)(val + 0.5f)).
+ *     HSK_KEYTEX_BLEND: over the passing keyframes with w_k >= blend_floor * w_max, in ascending k, sw += w_k, s += w_k val;
+ *       rgb = min(255, (int)(s / sw + 0.5f)) (sw = 0, every weight 0: the best keyframe's val).
+ *     source (W H bytes): the index of w_max in both modes, HSK_KEYTEX_NONE where no keyframe passes.
+ *     A keyed texel has HSK_TEXEL_KEYFRAME.  A texel no keyframe passes: with fallback_volume != 0 on a context with colour it
+ *     takes hsk_bake_texture's colour and HSK_TEXEL_COLORED where the colour volume has one (n_fallback); otherwise it is
+ *     (0, 0, 0) (n_uncolored, owned texels only).  HSK_TEXEL_COLORED is therefore set only where the colour volume coloured the
+ *     texel, and n_keyed + n_fallback + n_uncolored = n_owned.  With an empty store every texel falls back: the images are
+ *     hsk_bake_texture's.
+ *   The defaults (hsk_default_keytex_params) are stated CHOICES, not measurements: BEST, z_min_m 0.3, z_max_m 4.0, cos_min 0.2,
+ *     border_px 4, occlusion_tol_m 3 x the largest cell (k NULL: 0.03), blend_floor 0.5, fallback_volume 1.
+ *   HSK_ERR_ARG (the bake): what hsk_bake_texture refuses; an unknown mode; a parameter negative or not finite; z_min_m > z_max_m;
+ *     cos_min > 1; blend_floor > 1.  HSK_ERR_STATE: no store; a slab of a group or a context that stores part of its volume
+ *     (every call here that takes a context; hsk_keyframe_count, hsk_clear_keyframes and hsk_release_keyframes never
+ *     refuse). */
+#define HSK_TEXEL_KEYFRAME 32      /* the texel's colour comes from a keyframe */
+#define HSK_KEYTEX_BEST  0
+#define HSK_KEYTEX_BLEND 1
+#define HSK_KEYTEX_NONE  255       /* source plane: no keyframe */
+typedef struct hsk_keytex_params {
+  int32_t mode;                    /* HSK_KEYTEX_*                                                                             */
+  float z_min_m, z_max_m;          /* the range of z_c in which a keyframe is trusted                                          */
+  float cos_min;                   /* the smallest cosine between the texel's normal and the direction to the camera           */
+  float border_px;                 /* the image margin a pixel must keep                                                       */
+  float occlusion_tol_m;           /* how far a tap's depth may lie from the texel's                                           */
+  float blend_floor;               /* HSK_KEYTEX_BLEND: the share of the best weight a keyframe needs, 0 .. 1                  */
+  int32_t fallback_volume;         /* != 0: texels no keyframe passes take the colour volume's colour, where there is one      */
+} hsk_keytex_params;               /* 32 bytes */
+typedef struct hsk_keytex_info {
+  uint64_t n_keyframes;            /* the store's keyframes at the call                                                        */
+  uint64_t n_keyed, n_fallback, n_uncolored;   /* owned texels by where their colour comes from (a call that bakes)            */
+  uint64_t n_pairs_seen, n_pairs_occluded;     /* (texel, keyframe) pairs at step 4, and those that failed it                  */
+} hsk_keytex_info;                 /* 48 bytes */
+int hsk_enable_keyframes(hsk_ctx* k, int cap /* 1 .. 255 */, int w, int h /* 2 .. 4096 each */);
+int hsk_add_keyframe(hsk_ctx* k, const uint16_t* depth_mm, const uint8_t* rgb, int w, int h, const float pose[16],
+                     const float intr[4] /* fx fy cx cy; NULL: the context's camera */, int* index /* may be NULL */);
+/* every output may be NULL; without a store all are 0 */
+int hsk_keyframe_count(const hsk_ctx* k, int* n, int* cap, int* w, int* h, uint64_t* bytes);
+/* what went in: the pose with the last row 0 0 0 1.  HSK_ERR_ARG: an index outside 0 .. n - 1; HSK_ERR_STATE: no store */
+int hsk_get_keyframe(hsk_ctx* k, int index, float pose[16], float intr[4], uint16_t* depth_mm /* may be NULL */,
+                     uint8_t* rgb /* may be NULL */);
+int hsk_clear_keyframes(hsk_ctx* k);     /* n = 0, the memory kept */
+int hsk_release_keyframes(hsk_ctx* k);   /* the memory freed; hsk_destroy does it too */
+int hsk_keyframe_wanted(const float* poses /* 16 per keyframe */, size_t n, const float pose[16], float min_translation_m,
+                        float min_angle_rad);   /* host only, no context */
+void hsk_default_keytex_params(const hsk_ctx* k /* may be NULL */, hsk_keytex_params* p);
+int hsk_bake_texture_keyframes(hsk_ctx* k, const float* vertices, size_t n_vertices, const int32_t* faces, size_t n_faces,
+                               const hsk_texture_params* tp /* NULL: the defaults */, const hsk_keytex_params* kp /* NULL: the defaults */,
+                               uint8_t* rgb /* 3 W H */, uint8_t* normal_rgb /* 3 W H */, uint8_t* mask /* W H */, uint8_t* source /* W H */,
+                               size_t cap_texels, float* uv, hsk_texture_chart* charts, hsk_texture_info* info, hsk_keytex_info* kinfo);
+
 /* ---- Scene views: what has been fused so far, as an image from any camera (upstream's generateImage / generateDepth and its
  * colour view; DESIGN.md 3.8 the kernel, 8b the rule).  One call marches the TSDF from a virtual pinhole camera, shades the
  * hits on the device and hands back small images.  It is enqueued on hsk_stream() behind every frame submitted so far and
