@@ -23,13 +23,14 @@ def tau_of(size, dims, trunc):
     return max(f32(trunc), lo)
 
 
-def _integrate(vol, size, trunc, scaled, fx, fy, cx, cy, pose, zs0, Z=None):
-    nz, Y, X, _ = vol.shape
-    Z = Z or nz
+def _project(dims, size, scaled, fx, fy, cx, cy, pose, zs0, nz=None):
+    """the projection of A.4 for the nz stored planes from zs0 on of a (X, Y, Z) = dims volume over `size` metres: per voxel
+    (arrays [nz, Y, X], or what broadcasts to it) ok -- in front (D6), a finite pixel inside the image --, the pixel (u, v),
+    its scaled depth Ds (0 where not ok), sdf = Ds - |g|, and g = (gx, gy, gz), the voxel centre minus the camera centre"""
+    X, Y, Z = dims
+    nz = Z if nz is None else nz
     H, W = scaled.shape
     cell = [f32(size[0]) / f32(X), f32(size[1]) / f32(Y), f32(size[2]) / f32(Z)]
-    tau = tau_of(size, (X, Y, Z), trunc)
-    tau_inv = f32(1) / tau
     R = pose[:3, :3].astype(f32)
     t = pose[:3, 3].astype(f32)
     Ri = R.T.copy()
@@ -52,6 +53,15 @@ def _integrate(vol, size, trunc, scaled, fx, fy, cx, cy, pose, zs0, Z=None):
     Ds = np.where(ok, scaled[np.clip(v, 0, H - 1), np.clip(u, 0, W - 1)], f32(0))
     dist = np.sqrt(gz * gz + (gx * gx + gy * gy))
     sdf = Ds - dist
+    return ok, u, v, Ds, sdf, gx, gy, gz
+
+
+def _integrate(vol, size, trunc, scaled, fx, fy, cx, cy, pose, zs0, Z=None):
+    nz, Y, X, _ = vol.shape
+    Z = Z or nz
+    tau = tau_of(size, (X, Y, Z), trunc)
+    tau_inv = f32(1) / tau
+    ok, _, _, Ds, sdf, _, _, _ = _project((X, Y, Z), size, scaled, fx, fy, cx, cy, pose, zs0, nz)
     upd = ok & (Ds != 0) & (sdf >= -tau)
     F = np.minimum(sdf * tau_inv, f32(1)).astype(f32)
     tp = vol[..., 0].astype(f32)

@@ -6,59 +6,22 @@ import os
 import numpy as np
 import pytest
 
-from np_twin import _Grid, _vox, scale_depth, tau_of
+from color_twin import band_of, integrate_color, np_attrs
+from np_twin import _Grid, scale_depth, tau_of
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 FX, FY, CX, CY = 525.0, 525.0, 319.5, 239.5
+SIZE3 = (3.0, 3.0, 3.0)
 
 
-def band_of(n, band_m, size=3.0, trunc=0.03):
-    cell = f32(size) / f32(n)
-    b = f32(band_m) if band_m > 0 else f32(2.0) * cell
-    return min(b, tau_of((size,) * 3, (n, n, n), trunc))
+def cube_band(n, band_m):
+    return band_of((n, n, n), SIZE3, band_m, 0.03)
 
 
-def np_color(col, scaled, rgb, pose, band, max_w, size=3.0):
-    """one frame's colour update of `col` ([nz, Y, X, 4] uint8, in place): the projection of np_twin._integrate, then
-    -band < sdf < band, c' = (c w + p + ((w + 1) >> 1)) // (w + 1), w' = min(w + 1, max_w)"""
-    nz, Y, X, _ = col.shape
-    H, W = scaled.shape
-    cell = [f32(size) / f32(X), f32(size) / f32(Y), f32(size) / f32(nz)]
-    R = pose[:3, :3].astype(f32)
-    t = pose[:3, 3].astype(f32)
-    Ri = R.T.copy()
-    x = np.arange(X, dtype=f32)[None, None, :]
-    y = np.arange(Y, dtype=f32)[None, :, None]
-    gx = (x + f32(0.5)) * cell[0] - t[0]
-    gy = (y + f32(0.5)) * cell[1] - t[1]
-    for z0 in range(0, nz, 32):
-        z = np.arange(z0, min(z0 + 32, nz)).astype(f32)[:, None, None]
-        gz = (z + f32(0.5)) * cell[2] - t[2]
-        cam = [(Ri[i, 0] * gx + Ri[i, 1] * gy) + Ri[i, 2] * gz for i in range(3)]
-        with np.errstate(all="ignore"):
-            front = cam[2] >= f32(1.17549435e-38)
-            inv_z = f32(1) / cam[2]
-            fu = (cam[0] * f32(FX)) * inv_z + f32(CX)
-            fv = (cam[1] * f32(FY)) * inv_z + f32(CY)
-            ok = front & (fu > f32(-1e6)) & (fu < f32(1e6)) & (fv > f32(-1e6)) & (fv < f32(1e6))
-            u = np.where(ok, np.rint(np.where(ok, fu, 0)), -1).astype(np.int64)
-            v = np.where(ok, np.rint(np.where(ok, fv, 0)), -1).astype(np.int64)
-        ok &= (u >= 0) & (v >= 0) & (u < W) & (v < H)
-        Ds = np.where(ok, scaled[np.clip(v, 0, H - 1), np.clip(u, 0, W - 1)], f32(0))
-        dist = np.sqrt(gz * gz + (gx * gx + gy * gy))
-        sdf = Ds - dist
-        upd = ok & (Ds != 0) & (sdf > -band) & (sdf < band)
-        iz, iy, ix = np.nonzero(upd)
-        if len(iz) == 0:
-            continue
-        p = rgb[v[iz, iy, ix], u[iz, iy, ix]].astype(np.int64)
-        blk = col[z0:z0 + 32]
-        c = blk[iz, iy, ix, :3].astype(np.int64)
-        w = blk[iz, iy, ix, 3].astype(np.int64)
-        w1 = w + 1
-        blk[iz, iy, ix, :3] = ((c * w[:, None] + p + (w1 >> 1)[:, None]) // w1[:, None]).astype(np.uint8)
-        blk[iz, iy, ix, 3] = np.minimum(w1, max_w).astype(np.uint8)
+def cube_color(col, scaled, rgb, pose, band, max_w):
+    """one frame's colour update of a cubic volume over 3 m, from the default camera (tests/color_twin.py)"""
+    return integrate_color(col, SIZE3, scaled, rgb, FX, FY, CX, CY, pose, band, max_w)
 
 
 def frame_of(hsk, src, k):
@@ -87,13 +50,13 @@ def test_integrate_color_stage_bitexact(hsk, n, src, band_m, max_w):
     trk.upload_color(col)
     assert np.array_equal(trk.download_color(), col)
     tsdf0 = trk.download_tsdf()
-    band = band_of(n, band_m)
+    band = cube_band(n, band_m)
     for k in (3, 9):
         pose, depth, rgb = frame_of(hsk, src, k)
         trk.integrate_color(depth, rgb, pose)
         scaled = trk.download_scaled_depth()
         assert np.array_equal(scaled.view(np.uint32), scale_depth(depth, FX, FY, CX, CY).view(np.uint32))
-        np_color(col, scaled, rgb, pose, band, max_w)
+        cube_color(col, scaled, rgb, pose, band, max_w)
         got = trk.download_color()
         bad = np.argwhere((got != col).any(axis=3))
         assert len(bad) == 0, f"{len(bad)} voxels differ, first {bad[:5].tolist()}"
@@ -125,7 +88,7 @@ def replay(n, frames, results, max_w=64):
     col = np.zeros((n, n, n, 4), np.uint8)
     for k, ((_, depth, rgb), (pose, ok)) in enumerate(zip(frames, results)):
         if ok or k == 0:  # frame 0 integrates at the initial pose; every tracked frame integrates (no gate)
-            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), max_w)
+            cube_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, cube_band(n, 0.0), max_w)
     return col
 
 
@@ -187,7 +150,7 @@ def test_depth_only_frames_leave_color(hsk, use_graph):
     col = np.zeros((n, n, n, 4), np.uint8)
     for k, (((_, depth, rgb)), ((pose, ok), colored)) in enumerate(zip(frames, results)):
         if colored and (ok or k == 0):
-            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), 64)
+            cube_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, cube_band(n, 0.0), 64)
     assert np.array_equal(before, col)
     trk.close()
 
@@ -227,51 +190,6 @@ def test_loss_zeroes_color(hsk):
     trk.reset()
     assert not trk.download_color().any()
     trk.close()
-
-
-def np_attrs(tsdf, col, xyz, size=3.0):
-    """per point of the cloud (voxel order: plane, row, x, axis): the normal of the raycast on the TSDF and the colour of the
-    selection rule -> (normals, rgb, n_uncolored)"""
-    nz, Y, X, _ = tsdf.shape
-    t = tsdf[..., 0].astype(np.int32)
-    valid = (tsdf[..., 1] != 0) & (t != 32767)
-    M = np.zeros((nz, Y, X, 3), bool)
-    for k, (sa, sb) in enumerate([((slice(None), slice(None), slice(0, -1)), (slice(None), slice(None), slice(1, None))),
-                                   ((slice(None), slice(0, -1), slice(None)), (slice(None), slice(1, None), slice(None))),
-                                   ((slice(0, -1), slice(None), slice(None)), (slice(1, None), slice(None), slice(None)))]):
-        a, b = t[sa], t[sb]
-        M[sa + (k,)] = valid[sa] & valid[sb] & (((a > 0) & (b < 0)) | ((a < 0) & (b > 0)))
-    z, y, x, k = np.nonzero(M)
-    assert len(z) == len(xyz)
-    bz, by, bx = z + (k == 2), y + (k == 1), x + (k == 0)
-    ta, tb = np.abs(t[z, y, x]), np.abs(t[bz, by, bx])
-    ca, cb = col[z, y, x], col[bz, by, bx]
-    take_a = ta <= tb
-    first = np.where(take_a[:, None], ca, cb)
-    other = np.where(take_a[:, None], cb, ca)
-    pick = np.where((first[:, 3] == 0)[:, None], other, first)
-    unc = pick[:, 3] == 0
-    rgb = np.where(unc[:, None], 0, pick[:, :3]).astype(np.uint8)
-    G = _Grid(tsdf, (size,) * 3, nz, 0)
-    p = [xyz[:, i].copy() for i in range(3)]
-    dims = (X, Y, nz)
-    deep = np.ones(len(xyz), bool)
-    for i in range(3):
-        q = _vox(p[i], G.cell[i])
-        deep &= (q > 1) & (q < dims[i] - 2)
-    nrm = np.full((len(xyz), 3), np.nan, np.float32)
-    n = []
-    for i in range(3):
-        hi = [c.copy() for c in p]
-        lo = [c.copy() for c in p]
-        hi[i] = (hi[i] + G.cell[i]).astype(f32)
-        lo[i] = (lo[i] - G.cell[i]).astype(f32)
-        n.append((G.trilinear(hi) - G.trilinear(lo)).astype(f32))
-    with np.errstate(all="ignore"):
-        ninv = f32(1) / np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
-    for i in range(3):
-        nrm[deep, i] = (n[i] * ninv)[deep]
-    return nrm, rgb, int(unc.sum())
 
 
 def test_extract_cloud_attrs_bitexact(hsk, tmp_path):
@@ -421,7 +339,7 @@ def test_gated_frames_color_when_they_integrate(hsk):
         integrated.append(did)
         prev = cur
         if did:
-            np_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, band_of(n, 0.0), 64)
+            cube_color(col, scale_depth(depth, FX, FY, CX, CY), rgb, pose, cube_band(n, 0.0), 64)
         assert np.array_equal(trk.download_color(), col), f"frame {k} (integrated: {did})"
     assert integrated[0] and any(integrated[1:]) and not all(integrated), integrated
     trk.close()
@@ -454,6 +372,6 @@ def test_enable_after_graph_capture(hsk, use_graph, mode):
     assert all(ok for _, ok in res)
     col = np.zeros((n, n, n, 4), np.uint8)
     for (_, d, c), (pose, _) in zip(rest, res):
-        np_color(col, scale_depth(d, FX, FY, CX, CY), c, pose, band_of(n, 0.0), 64)
+        cube_color(col, scale_depth(d, FX, FY, CX, CY), c, pose, cube_band(n, 0.0), 64)
     assert np.array_equal(trk.download_color(), col)
     trk.close()
