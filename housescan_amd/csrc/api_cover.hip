@@ -65,25 +65,20 @@ static int cover_run(hsk_ctx* k, const CoverProbe& cp, const float* poses, size_
   int r = ensure_pinned(k);
   if (r != HSK_OK) return r;
   const size_t P = (size_t)cp.W * cp.H;
-  ProductLayout lay;
-  const size_t poses_at = lay.take(n * 48), scores_at = lay.take(n * sizeof(hsk_view_score));
-  const size_t cls_at = lay.take(cls ? P : 0), dep_at = lay.take(depth_mm ? P * 2 : 0), gain_at = lay.take(gain ? P * 2 : 0);
-  r = ensure_product_bytes(k, lay.bytes);
+  ProductArrays pa;  // (the poses and the scores are the kernel's own: they lie there whether or not the scores are handed out)
+  const int a_poses = pa.add(nullptr, n * 48, true), a_scores = pa.add(scores, n * sizeof(hsk_view_score), true);
+  const int a_cls = pa.add(cls, P), a_dep = pa.add(depth_mm, P * 2), a_gain = pa.add(gain, P * 2);
+  r = pa.place(k);
   if (r != HSK_OK) return r;
-  char* base = (char*)k->d_out;
   float* h12 = (float*)k->h_pin[0];  // (free: every call that uses the pair waits for its own result before it returns; 65536 poses are 3 MiB)
   for (size_t j = 0; j < n; ++j) pose16_to_rt(poses + 16 * j, h12 + 12 * j, h12 + 12 * j + 9);
-  HIPCHK(k, hipMemcpyAsync(base + poses_at, h12, n * 48, hipMemcpyHostToDevice, k->stream));
-  HIPCHK(k, hipMemsetAsync(base + scores_at, 0, n * sizeof(hsk_view_score), k->stream));
-  launch_cover_rays(k->stream, k->d_vol, k->vp, cp, (const float*)(base + poses_at), (unsigned)n, (hsk_view_score*)(base + scores_at),
-                    cls ? (unsigned char*)(base + cls_at) : nullptr, depth_mm ? (unsigned short*)(base + dep_at) : nullptr,
-                    gain ? (unsigned short*)(base + gain_at) : nullptr);
+  HIPCHK(k, hipMemcpyAsync(pa.dev<float>(a_poses), h12, n * 48, hipMemcpyHostToDevice, k->stream));
+  HIPCHK(k, hipMemsetAsync(pa.dev<hsk_view_score>(a_scores), 0, n * sizeof(hsk_view_score), k->stream));
+  launch_cover_rays(k->stream, k->d_vol, k->vp, cp, pa.dev<float>(a_poses), (unsigned)n, pa.dev<hsk_view_score>(a_scores), pa.dev<unsigned char>(a_cls),
+                    pa.dev<unsigned short>(a_dep), pa.dev<unsigned short>(a_gain));
   HIPCHK(k, hipGetLastError());
   // (copy_out's first piece goes through the first pinned buffer: behind the poses' copy in the stream's order)
-  if (scores) r = copy_out(k, scores, base + scores_at, n * sizeof(hsk_view_score));
-  if (r == HSK_OK && cls) r = copy_out(k, cls, base + cls_at, P);
-  if (r == HSK_OK && depth_mm) r = copy_out(k, depth_mm, base + dep_at, P * 2);
-  if (r == HSK_OK && gain) r = copy_out(k, gain, base + gain_at, P * 2);
+  r = pa.copy_out(k);
   if (r != HSK_OK) return r;
   HIPCHK(k, hipStreamSynchronize(k->stream));  // (a call without an output still ends with its work done)
   return HSK_OK;

@@ -207,18 +207,14 @@ extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* 
   if (int rc = diff_held_check(k, "hsk_download_diff")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  ProductLayout lay;
-  const size_t cls_at = lay.take(n), region_at = lay.take(region ? n * 4 : 0);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
+  ProductArrays pa;
+  const int a_cls = pa.add(cls, n), a_region = pa.add(region, n * 4);
+  if (int r = pa.place(k)) return r;
   DiffBufs b;
   diff_layout(k->vp, k->d_diff, &b);
-  char* base = (char*)k->d_out;
-  launch_diff_box(k->stream, k->vp, b, bx.lo, bx.hi, n, (unsigned char*)(base + cls_at), region ? (unsigned*)(base + region_at) : nullptr);
+  launch_diff_box(k->stream, k->vp, b, bx.lo, bx.hi, n, pa.dev<unsigned char>(a_cls), pa.dev<unsigned>(a_region));
   HIPCHK(k, hipGetLastError());
-  r = copy_out(k, cls, base + cls_at, n);
-  if (r == HSK_OK && region) r = copy_out(k, region, base + region_at, n * 4);
-  return r;
+  return pa.copy_out(k);
 }
 
 extern "C" int hsk_diff_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint32_t* region) {

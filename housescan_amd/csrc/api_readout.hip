@@ -252,36 +252,6 @@ int ensure_product_bytes(hsk_ctx* k, size_t want, bool headroom) {
   return HSK_OK;
 }
 extern "C" size_t hsk_product_capacity(const hsk_ctx* k) { return k ? k->out_bytes : 0; }
-// The arrays of one product in the product buffer.  add(host pointer or null, bytes, keep) in order -> the array's number; an
-// array that is neither handed out (a host pointer) nor kept for a device consumer (keep) takes no space.  place() sizes the
-// buffer once; dev<T>(i) is array i's device pointer (null when absent); copy_out() brings the arrays that have a host pointer to
-// the caller through the pinned pair, in that order, and stops at the first error.
-struct ProductArrays {
-  ProductLayout lay;
-  int n = 0;
-  void* host[4];
-  size_t at[4], len[4];
-  char* base = nullptr;
-  int add(void* h, size_t bytes, bool keep = false) {
-    host[n] = h;
-    len[n] = (h || keep) ? bytes : 0;
-    at[n] = lay.take(len[n]);
-    return n++;
-  }
-  int place(hsk_ctx* k) {
-    const int r = ensure_product_bytes(k, lay.bytes);
-    base = (char*)k->d_out;
-    return r;
-  }
-  template <class T>
-  T* dev(int i) const { return len[i] ? (T*)(base + at[i]) : nullptr; }
-  int copy_out(hsk_ctx* k) const {
-    int r = HSK_OK;
-    for (int i = 0; i < n && r == HSK_OK; ++i)
-      if (host[i] && len[i]) r = ::copy_out(k, host[i], base + at[i], len[i]);
-    return r;
-  }
-};
 // n 64-bit words of device memory, once the stream has produced them
 int read_u64(hsk_ctx* k, unsigned long long* dst, const unsigned long long* src_dev, int n) {
   HIPCHK(k, hipMemcpyAsync(dst, src_dev, (size_t)n * 8, hipMemcpyDeviceToHost, k->stream));

@@ -105,21 +105,15 @@ extern "C" int hsk_extract_mesh_simplified(hsk_ctx* k, const hsk_simplify_params
   const size_t list_at = scratch.take(nv * 4), sums_at = scratch.take(nv * SIMP_REC * 8);
   r = ensure_grown(k, &k->d_simp_out, &k->simp_out_bytes, scratch.bytes + (scratch.bytes >> 2));
   if (r != HSK_OK) return r;
-  ProductLayout out;  // (an array that is not asked for takes no space)
-  const size_t xyz_at = out.take(vertices ? nv * 12 : 0), nrm_at = out.take(normals ? nv * 12 : 0), rgb_at = out.take(rgb ? nv * 3 : 0),
-               fc_at = out.take(faces ? nf * 12 : 0);
-  r = ensure_product_bytes(k, out.bytes);
+  ProductArrays out;  // (an array that is not asked for takes no space)
+  const int a_xyz = out.add(vertices, nv * 12), a_nrm = out.add(normals, nv * 12), a_rgb = out.add(rgb, nv * 3), a_fc = out.add(faces, nf * 12);
+  r = out.place(k);
   if (r != HSK_OK) return r;
-  char* ob = (char*)k->d_out;
   launch_simp_write(k->stream, k->d_vol, rgb ? k->d_color : nullptr, k->vp, k->d_cube_tab, k->d_rowcnt, mb, sb, (unsigned)nv,
                     (unsigned*)((char*)k->d_simp_out + list_at), (long long*)((char*)k->d_simp_out + sums_at), p.mode, (double)p.sv_floor,
-                    vertices ? (float*)(ob + xyz_at) : nullptr, normals ? (float*)(ob + nrm_at) : nullptr,
-                    rgb ? (unsigned char*)(ob + rgb_at) : nullptr, faces ? (int*)(ob + fc_at) : nullptr);
+                    out.dev<float>(a_xyz), out.dev<float>(a_nrm), out.dev<unsigned char>(a_rgb), out.dev<int>(a_fc));
   HIPCHK(k, hipGetLastError());
-  if (vertices) r = copy_out(k, vertices, ob + xyz_at, nv * 12);
-  if (r == HSK_OK && normals) r = copy_out(k, normals, ob + nrm_at, nv * 12);
-  if (r == HSK_OK && rgb) r = copy_out(k, rgb, ob + rgb_at, nv * 3);
-  if (r == HSK_OK && faces && nf) r = copy_out(k, faces, ob + fc_at, nf * 12);
+  r = out.copy_out(k);
   if (r != HSK_OK) return r;
   unsigned long long counts[6];
   r = read_u64(k, counts, sb.totals + 4, 6);

@@ -307,20 +307,14 @@ extern "C" int hsk_download_split(hsk_ctx* k, const hsk_voxel_box* box, uint8_t*
   if (int rc = split_held_check(k, "hsk_download_split")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  ProductLayout lay;
-  const size_t cls_at = lay.take(n), plane_at = lay.take(plane ? n : 0), object_at = lay.take(object ? n * 4 : 0);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
+  ProductArrays pa;
+  const int a_cls = pa.add(cls, n), a_plane = pa.add(plane, n), a_object = pa.add(object, n * 4);
+  if (int r = pa.place(k)) return r;
   SplitBufs b;
   split_layout(k->vp, k->d_split, &b);
-  char* base = (char*)k->d_out;
-  launch_split_box(k->stream, k->vp, b, bx.lo, bx.hi, n, (unsigned char*)(base + cls_at), plane ? (unsigned char*)(base + plane_at) : nullptr,
-                   object ? (unsigned*)(base + object_at) : nullptr);
+  launch_split_box(k->stream, k->vp, b, bx.lo, bx.hi, n, pa.dev<unsigned char>(a_cls), pa.dev<unsigned char>(a_plane), pa.dev<unsigned>(a_object));
   HIPCHK(k, hipGetLastError());
-  r = copy_out(k, cls, base + cls_at, n);
-  if (r == HSK_OK && plane) r = copy_out(k, plane, base + plane_at, n);
-  if (r == HSK_OK && object) r = copy_out(k, object, base + object_at, n * 4);
-  return r;
+  return pa.copy_out(k);
 }
 
 extern "C" int hsk_split_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint8_t* plane, uint32_t* object) {
@@ -332,21 +326,16 @@ extern "C" int hsk_split_at(hsk_ctx* k, const float* xyz, size_t n, int radius, 
   if (int rc = split_held_check(k, "hsk_split_at")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  ProductLayout lay;
-  const size_t pts_at = lay.take(n * 12), cls_at = lay.take(n), plane_at = lay.take(plane ? n : 0), object_at = lay.take(object ? n * 4 : 0);
-  int r = ensure_product_bytes(k, lay.bytes);
-  if (r != HSK_OK) return r;
+  ProductArrays pa;  // (the points first: kept for the gather, not handed back)
+  const int a_pts = pa.add(nullptr, n * 12, true), a_cls = pa.add(cls, n), a_plane = pa.add(plane, n), a_object = pa.add(object, n * 4);
+  if (int r = pa.place(k)) return r;
   SplitBufs b;
   split_layout(k->vp, k->d_split, &b);
-  char* base = (char*)k->d_out;
-  HIPCHK(k, hipMemcpyAsync(base + pts_at, xyz, n * 12, hipMemcpyHostToDevice, k->stream));
-  launch_split_gather(k->stream, k->vp, b, (const float*)(base + pts_at), (unsigned)n, radius, (unsigned char*)(base + cls_at),
-                      plane ? (unsigned char*)(base + plane_at) : nullptr, object ? (unsigned*)(base + object_at) : nullptr);
+  HIPCHK(k, hipMemcpyAsync(pa.dev<float>(a_pts), xyz, n * 12, hipMemcpyHostToDevice, k->stream));
+  launch_split_gather(k->stream, k->vp, b, pa.dev<float>(a_pts), (unsigned)n, radius, pa.dev<unsigned char>(a_cls), pa.dev<unsigned char>(a_plane),
+                      pa.dev<unsigned>(a_object));
   HIPCHK(k, hipGetLastError());
-  r = copy_out(k, cls, base + cls_at, n);
-  if (r == HSK_OK && plane) r = copy_out(k, plane, base + plane_at, n);
-  if (r == HSK_OK && object) r = copy_out(k, object, base + object_at, n * 4);
-  return r;
+  return pa.copy_out(k);
 }
 
 extern "C" int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, const hsk_remove_params* params, hsk_remove_stats* stats) {

@@ -412,3 +412,33 @@ struct ProductLayout {
     return at;
   }
 };
+// The arrays of one product in the product buffer.  add(host pointer or null, bytes, keep) in order -> the array's number; an
+// array that is neither handed out (a host pointer) nor kept for a device consumer (keep) takes no space.  place() sizes the
+// buffer once; dev<T>(i) is array i's device pointer (null when absent); copy_out() brings the arrays that have a host pointer to
+// the caller through the pinned pair, in that order, and stops at the first error.
+struct ProductArrays {
+  ProductLayout lay;
+  int n = 0;
+  void* host[5];
+  size_t at[5], len[5];
+  char* base = nullptr;
+  int add(void* h, size_t bytes, bool keep = false) {
+    host[n] = h;
+    len[n] = (h || keep) ? bytes : 0;
+    at[n] = lay.take(len[n]);
+    return n++;
+  }
+  int place(hsk_ctx* k) {
+    const int r = ensure_product_bytes(k, lay.bytes);
+    base = (char*)k->d_out;
+    return r;
+  }
+  template <class T>
+  T* dev(int i) const { return len[i] ? (T*)(base + at[i]) : nullptr; }
+  int copy_out(hsk_ctx* k) const {
+    int r = HSK_OK;
+    for (int i = 0; i < n && r == HSK_OK; ++i)
+      if (host[i] && len[i]) r = ::copy_out(k, host[i], base + at[i], len[i]);
+    return r;
+  }
+};

@@ -60,71 +60,125 @@ def _image_arrays(w, h, rgb, depth, vmap, nmap):
     return out, lambda k: out[k].ctypes.data if k in out else None
 
 
-SCORE_DTYPE = np.dtype([("n_near", "<u4"), ("n_free", "<u4"), ("n_behind", "<u4"), ("n_unseen", "<u4"), ("n_outside", "<u4"),
-                        ("n_skipped", "<u4"), ("sum_abs", "<u8")])     # hsk_pose_score
+def _override(p, allowed, what, over):
+    """the keywords `over` into the ctypes structure `p`: a name outside `allowed` raises TypeError(f"{what} {name!r}"); a value is
+    coerced by its field's C type -- float() for a float field, int() for an integer field, element by element for an array -> p"""
+    types = dict(p._fields_)
+
+    def cast(t, v):
+        return float(v) if t in (C.c_float, C.c_double) else int(v)
+
+    for name, val in over.items():
+        if name not in allowed:
+            raise TypeError(f"{what} {name!r}")
+        t = types[name]
+        setattr(p, name, t(*[cast(t._type_, v) for v in val]) if issubclass(t, C.Array) else cast(t, val))
+    return p
 
 
-PLANE_DTYPE = np.dtype([("abcd", "<f4", (4,)), ("n_inliers", "<u4"), ("pad", "<u4"), ("sum_abs", "<u8")])     # hsk_plane_record
+def _params(kind, tracker, params, over, clearance=()):
+    """the parameters of a call of `kind` = (structure, the C default call's name, the names a caller may set, the TypeError's
+    text): a copy of the caller's `params`, or, None, the C defaults for `tracker` (None: the default configuration's) -- for the
+    reach and partition calls behind `clearance` = (their clearance parameters or None,) --, then the keywords `over` -> the structure"""
+    struct, default, allowed, what = kind
+    if params is None:
+        p = struct()
+        getattr(_lib.load(), default)(tracker.h if tracker is not None else None, *(None if c is None else C.byref(c) for c in clearance), C.byref(p))
+    else:
+        p = struct.from_buffer_copy(params)
+    return _override(p, allowed, what, over)
 
 
-VIEW_SCORE_DTYPE = np.dtype([("n_hit", "<u4"), ("n_frontier", "<u4"), ("n_open", "<u4"), ("n_blind", "<u4"), ("n_outside", "<u4"),
-                             ("eye_state", "<u4"), ("gain", "<u8")])     # hsk_view_score
+def _box(cfg, box):
+    """box = (lo, hi), None: the whole volume -> (an `_lib.HskVoxelBox` or None, the [z, y, x] shape of its voxels)"""
+    if box is None:
+        return None, (cfg.vol_z, cfg.vol_y, cfg.vol_x)
+    b = _lib.HskVoxelBox()
+    b.lo[:] = [int(v) for v in box[0]]
+    b.hi[:] = [int(v) for v in box[1]]
+    return b, tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0))
+
+
+def _at_points(xyz, dtypes, call):
+    """the world points xyz [n, 3] through call(points, m, *outputs) in pieces of HSK_CLEAR_MAX_POINTS, what the C calls take
+    (no points: one call with every pointer None) -> one [n] array per dtype"""
+    pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    outs = [np.empty(len(pts), dt) for dt in dtypes]
+    step = _lib.HSK_CLEAR_MAX_POINTS
+    for at in range(0, max(len(pts), 1), step):
+        m = min(step, len(pts) - at)
+        call(pts[at:].ctypes.data if m else None, m, *(o[at:].ctypes.data if m else None for o in outs))
+    return outs
+
+
+def _records(struct, call, st=None):
+    """the two calls of a record read-out: call(None, 0, n, stats) asks for the count, call(records, n, n, None) fills them (the
+    fill is answered from what the size query left: its stats are the size query's) -> a structured array of `struct`"""
+    n = C.c_size_t(0)
+    call(None, 0, C.byref(n), None if st is None else C.byref(st))
+    recs = np.zeros(n.value, np.dtype(struct))
+    if n.value:
+        call(recs.ctypes.data_as(C.POINTER(struct)), n.value, C.byref(n), None)
+    return recs
+
+
+def _stats_dict(st):
+    """a ctypes stats structure as a dict in field order, `pad` left out: a scalar as an int, an array as a uint64 array"""
+    return {name: np.array(getattr(st, name)).astype(np.uint64) if issubclass(t, C.Array) else int(getattr(st, name))
+            for name, t in st._fields_ if name != "pad"}
+
+
+def _floor_shape(cfg, axis):
+    """a floor map's (nv, nu) for the up axis, u the lower-numbered remaining axis ((1, 1) for an axis the call refuses)"""
+    dims = (cfg.vol_x, cfg.vol_y, cfg.vol_z)
+    return (dims[1 if axis == 2 else 2], dims[1 if axis == 0 else 0]) if axis in (0, 1, 2) else (1, 1)
+
+
+# the records as numpy sees them: the layout of their structures
+SCORE_DTYPE = np.dtype(_lib.HskPoseScore)
+PLANE_DTYPE = np.dtype(_lib.HskPlaneRecord)
+VIEW_SCORE_DTYPE = np.dtype(_lib.HskViewScore)
 PROBE_FIELDS = ("width", "height", "fx", "fy", "cx", "cy", "near_m", "far_m", "step_m")
+_PROBE = (_lib.HskProbe, "hsk_default_probe", PROBE_FIELDS, "a probe has no field")
 
 
 def default_probe(tracker=None, **fields):
     """the probe of the coverage calls (hsk_default_probe): the tracker's camera at a quarter of its resolution, near_m 0.4,
     far_m 3.5, step_m half its truncation distance (without a tracker: the default configuration's); the keywords -- width,
     height, fx, fy, cx, cy, near_m, far_m, step_m -- override its fields -> an `_lib.HskProbe`"""
-    p = _lib.HskProbe()
-    _lib.load().hsk_default_probe(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in PROBE_FIELDS:
-            raise TypeError(f"a probe has no field {name!r}")
-        setattr(p, name, val)
-    return p
+    return _params(_PROBE, tracker, None, fields)
 
 
-COMPONENT_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])     # hsk_component
+COMPONENT_DTYPE = np.dtype(_lib.HskComponent)
 COMPONENT_NONE = 0xFFFFFFFF
 PRUNE_UNSEEN, PRUNE_FREE = 0, 1
 PRUNE_FIELDS = ("min_voxels", "keep_largest", "fill")
+_PRUNE = (_lib.HskPruneParams, "hsk_default_prune_params", PRUNE_FIELDS, "prune parameters have no field")
 
 
 def default_prune_params(tracker=None, **fields):
     """the parameters of prune_components (hsk_default_prune_params): min_voxels = the voxels of a cube of edge four truncation
     distances of the tracker (without one: the default configuration's), keep_largest 0 (no limit), fill PRUNE_UNSEEN; the
     keywords -- min_voxels, keep_largest, fill -- override its fields -> an `_lib.HskPruneParams`"""
-    p = _lib.HskPruneParams()
-    _lib.load().hsk_default_prune_params(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in PRUNE_FIELDS:
-            raise TypeError(f"prune parameters have no field {name!r}")
-        setattr(p, name, val)
-    return p
+    return _params(_PRUNE, tracker, None, fields)
 
 
 FILL_SURFACE, FILL_ALL = 0, 1
 FILL_FIELDS = ("iterations", "keep", "band", "fill_weight")
+_FILL = (_lib.HskFillParams, "hsk_default_fill_params", FILL_FIELDS, "fill parameters have no field")
 DIFF_UNSEEN, DIFF_ONLY_REF, DIFF_ONLY_CUR, DIFF_SAME, DIFF_APPEARED, DIFF_VANISHED, DIFF_MINOR = range(7)
 ADOPT_APPEARED, ADOPT_VANISHED = 1, 2
 DIFF_FIELDS = ("thresh", "min_weight", "min_voxels")
+_DIFF = (_lib.HskDiffParams, "hsk_default_diff_params", DIFF_FIELDS, "diff parameters have no field")
 ADOPT_FIELDS = ("which", "halo")
-DIFF_REGION_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("n_appeared", "<u8"), ("n_vanished", "<u8"),
-                              ("lo", "<i4", (3,)), ("hi", "<i4", (3,))])     # hsk_diff_region
+DIFF_REGION_DTYPE = np.dtype(_lib.HskDiffRegion)
 
 
 def default_diff_params(tracker=None, **fields):
     """the parameters of diff_volume (hsk_default_diff_params): thresh 16384 (half the truncation distance), min_weight 1,
     min_voxels = default_prune_params' value for the tracker (without one: the default configuration's); the keywords -- thresh,
     min_weight, min_voxels -- override its fields -> an `_lib.HskDiffParams`"""
-    p = _lib.HskDiffParams()
-    _lib.load().hsk_default_diff_params(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in DIFF_FIELDS:
-            raise TypeError(f"diff parameters have no field {name!r}")
-        setattr(p, name, int(val))
-    return p
+    return _params(_DIFF, tracker, None, fields)
 
 
 SPLIT_NONE, SPLIT_FLOOR, SPLIT_CEILING, SPLIT_WALL, SPLIT_OTHER, SPLIT_OBJECT, SPLIT_MINOR = range(7)
@@ -132,34 +186,23 @@ KIND_FLOOR, KIND_CEILING, KIND_WALL, KIND_OTHER = 1, 2, 3, 4
 REMOVE_ERASE, REMOVE_RESTORE = 0, 1
 SPLIT_FIELDS = ("dist_m", "back_m", "cos_min", "min_voxels")
 REMOVE_FIELDS = ("mode", "halo", "fill_weight")
-SPLIT_PLANE_DTYPE = np.dtype([("abcd", "<f4", (4,)), ("kind", "<i4"), ("pad", "<i4")])     # hsk_split_plane
-OBJECT_DTYPE = np.dtype([("root", "<i4", (3,)), ("pad", "<i4"), ("n_voxels", "<u8"), ("sum", "<u8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
-                         ("contact", "<u4", (4,)), ("plane_mask", "<u8"), ("height_lo", "<i4"), ("height_hi", "<i4")])     # hsk_object
+_SPLIT = (_lib.HskSplitParams, "hsk_default_split_params", SPLIT_FIELDS, "split parameters have no field")
+_REMOVE = (_lib.HskRemoveParams, "hsk_default_remove_params", REMOVE_FIELDS, "remove parameters have no field")
+SPLIT_PLANE_DTYPE = np.dtype(_lib.HskSplitPlane)
+OBJECT_DTYPE = np.dtype(_lib.HskObject)
 
 
 def default_split_params(tracker=None, **fields):
     """the parameters of split_scene (hsk_default_split_params): dist_m 0.04, back_m = the truncation distance + 0.04, cos_min
     cos 30 deg, min_voxels = default_prune_params' value for the tracker (without one: the default configuration's); the keywords
     -- dist_m, back_m, cos_min, min_voxels -- override its fields -> an `_lib.HskSplitParams`"""
-    p = _lib.HskSplitParams()
-    _lib.load().hsk_default_split_params(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in SPLIT_FIELDS:
-            raise TypeError(f"split parameters have no field {name!r}")
-        setattr(p, name, int(val) if name == "min_voxels" else float(val))
-    return p
+    return _params(_SPLIT, tracker, None, fields)
 
 
 def default_remove_params(tracker=None, **fields):
     """the parameters of remove_objects (hsk_default_remove_params): REMOVE_RESTORE, halo = clamp(ceil(tau / the smallest cell) + 1,
     1, 8), fill_weight 1; the keywords -- mode, halo, fill_weight -- override its fields -> an `_lib.HskRemoveParams`"""
-    p = _lib.HskRemoveParams()
-    _lib.load().hsk_default_remove_params(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in REMOVE_FIELDS:
-            raise TypeError(f"remove parameters have no field {name!r}")
-        setattr(p, name, int(val))
-    return p
+    return _params(_REMOVE, tracker, None, fields)
 
 
 def split_planes(abcd, kinds=KIND_OTHER):
@@ -190,29 +233,13 @@ def default_fill_params(tracker=None, **fields):
     (without a tracker: the default configuration's), clamped to 1..255 -- gaps up to about 30 cm across close --, keep
     FILL_SURFACE, band 2, fill_weight 1; the keywords -- iterations, keep, band, fill_weight -- override its fields -> an
     `_lib.HskFillParams`"""
-    p = _lib.HskFillParams()
-    _lib.load().hsk_default_fill_params(tracker.h if tracker is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in FILL_FIELDS:
-            raise TypeError(f"fill parameters have no field {name!r}")
-        setattr(p, name, val)
-    return p
+    return _params(_FILL, tracker, None, fields)
 
 
 CLEAR_UNKNOWN = 1
 CLEARANCE_FAR, CLEARANCE_OUTSIDE = 0xFFFFFFFF, 0xFFFFFFFE
 CLEARANCE_FIELDS = ("weight", "max_d2", "flags", "unit_m")
-
-
-def _clearance_fields(p, fields):
-    for name, val in fields.items():
-        if name not in CLEARANCE_FIELDS:
-            raise TypeError(f"clearance parameters have no field {name!r}")
-        if name == "weight":
-            p.weight[:] = [int(v) for v in val]
-        else:
-            setattr(p, name, val)
-    return p
+_CLEARANCE = (_lib.HskClearanceParams, "hsk_default_clearance_params", CLEARANCE_FIELDS, "clearance parameters have no field")
 
 
 def default_clearance_params(tracker=None, **fields):
@@ -220,9 +247,7 @@ def default_clearance_params(tracker=None, **fields):
     metric the cells' -- (1, 1, 1) with unit_m = the cell for cubic cells, else rint(16 (cell / cell_min)^2) with unit_m =
     cell_min / 4 -- and max_d2 = one metre (without a tracker: the default configuration's); the keywords -- weight, max_d2,
     flags, unit_m -- override its fields -> an `_lib.HskClearanceParams`"""
-    p = _lib.HskClearanceParams()
-    _lib.load().hsk_default_clearance_params(tracker.h if tracker is not None else None, C.byref(p))
-    return _clearance_fields(p, fields)
+    return _params(_CLEARANCE, tracker, None, fields)
 
 
 def clearance_d2(params, metres):
@@ -242,19 +267,14 @@ def clearance_metres(params, d2):
 REACH_UNREACHED, REACH_OUTSIDE, REACH_BLOCKED = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD
 REACH_MAX_COST = 0xF0000000
 REACH_FIELDS = ("min_d2", "max_cost")
+_REACH = (_lib.HskReachParams, "hsk_default_reach_params", REACH_FIELDS, "reach parameters have no field")
 
 
 def default_reach_params(tracker=None, clearance=None, **fields):
     """the parameters of the reach calls (hsk_default_reach_params) for the clearance parameters `clearance` (None: the tracker's
     defaults): min_d2 = clearance_d2(clearance, 0.3) -- a person's half width -- clamped to its max_d2, max_cost = REACH_MAX_COST;
     the keywords -- min_d2, max_cost -- override its fields -> an `_lib.HskReachParams`"""
-    p = _lib.HskReachParams()
-    _lib.load().hsk_default_reach_params(tracker.h if tracker is not None else None, C.byref(clearance) if clearance is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in REACH_FIELDS:
-            raise TypeError(f"reach parameters have no field {name!r}")
-        setattr(p, name, int(val))
-    return p
+    return _params(_REACH, tracker, None, fields, (clearance,))
 
 
 def reach_metres(params, g):
@@ -283,10 +303,9 @@ def rank_views_reach(scores, eye_g, max_g=REACH_MAX_COST):
 ROOM_UNASSIGNED, ROOM_OUTSIDE, ROOM_BLOCKED, ROOM_NONE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 PARTITION_MAX_ROOMS = 1024
 PARTITION_FIELDS = ("core_d2", "min_d2", "min_core_voxels", "max_cost")
-# the records as numpy sees them (the layout of hsk_room and hsk_door)
-ROOM_DTYPE = np.dtype([("n_voxels", "<u8"), ("n_core_voxels", "<u8"), ("sum", "<u8", 3), ("root", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3),
-                       ("max_d2", "<u4"), ("max_g", "<u4"), ("pad", "<u4")])
-DOOR_DTYPE = np.dtype([("sum2", "<u8", 3), ("a", "<u4"), ("b", "<u4"), ("n_faces", "<u4", 3), ("lo", "<u4", 3), ("hi", "<u4", 3), ("max_d2", "<u4")])
+_PARTITION = (_lib.HskPartitionParams, "hsk_default_partition_params", PARTITION_FIELDS, "partition parameters have no field")
+ROOM_DTYPE = np.dtype(_lib.HskRoom)
+DOOR_DTYPE = np.dtype(_lib.HskDoor)
 
 
 def default_partition_params(tracker=None, clearance=None, **fields):
@@ -294,13 +313,7 @@ def default_partition_params(tracker=None, clearance=None, **fields):
     tracker's defaults): core_d2 = clearance_d2(clearance, 0.5) clamped to its max_d2, min_d2 = 1, min_core_voxels = the voxels of a
     cube of edge 0.25 m, max_cost = REACH_MAX_COST; the keywords -- core_d2, min_d2, min_core_voxels, max_cost -- override its
     fields -> an `_lib.HskPartitionParams`"""
-    p = _lib.HskPartitionParams()
-    _lib.load().hsk_default_partition_params(tracker.h if tracker is not None else None, C.byref(clearance) if clearance is not None else None, C.byref(p))
-    for name, val in fields.items():
-        if name not in PARTITION_FIELDS:
-            raise TypeError(f"partition parameters have no field {name!r}")
-        setattr(p, name, int(val))
-    return p
+    return _params(_PARTITION, tracker, None, fields, (clearance,))
 
 
 def merge_rooms(doors, n_rooms, merge_d2):
@@ -353,7 +366,7 @@ def cluster_vertex(sums16, cluster_voxels=4, mode=SIMPLIFY_QUADRIC, sv_floor=0.0
 TEXEL_OWNED, TEXEL_INSIDE, TEXEL_PROJECTED, TEXEL_COLORED, TEXEL_NORMAL = (_lib.HSK_TEXEL_OWNED, _lib.HSK_TEXEL_INSIDE, _lib.HSK_TEXEL_PROJECTED,
                                                                              _lib.HSK_TEXEL_COLORED, _lib.HSK_TEXEL_NORMAL)
 TEXTURE_INFO_FIELDS = ("width", "height", "n_faces_charted", "n_faces_skipped", "n_blocks", "n_owned", "n_inside", "n_projected", "n_colored", "n_normal")
-TEXTURE_CHART_DTYPE = np.dtype([("x0", np.int32), ("y0", np.int32), ("s", np.int32), ("half_rot", np.int32)])
+TEXTURE_CHART_DTYPE = np.dtype(_lib.HskTextureChart)
 
 
 def texture_info_dict(info):
@@ -726,18 +739,24 @@ class KinfuTracker:
         """extract_mesh(cubes=True)'s surface as an indexed mesh welded on the device by edge identity ->
         (vertices [n, 3] float32, faces [m, 3] int32, normals [n, 3] float32 or None, rgb [n, 3] uint8 or None, n_uncolored);
         vertices[faces] is the triangle soup bit for bit.  rgb=True needs enable_color()."""
-        nv, nf, nu = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        self._ck(self.lib.hsk_extract_mesh_indexed(self.h, None, None, None, 0, C.byref(nv), None, 0, C.byref(nf), None))
+        nu = C.c_size_t()
+        return self._indexed_mesh("extract_mesh_indexed", normals, rgb, lambda first, *a: self.lib.hsk_extract_mesh_indexed(
+            self.h, *a, None if first else C.byref(nu))) + (nu.value,)
+
+    def _indexed_mesh(self, who, normals, rgb, call):
+        """the size query and the fill of an indexed mesh: call(first, vertices, normals, rgb, their capacity, nv, faces, their
+        capacity, nf) -> (vertices [n, 3] float32, faces [m, 3] int32, normals [n, 3] float32 or None, rgb [n, 3] uint8 or None)"""
+        nv, nf = C.c_size_t(), C.c_size_t()
+        self._ck(call(True, None, None, None, 0, C.byref(nv), None, 0, C.byref(nf)))
         verts = np.empty((nv.value, 3), np.float32)
         faces = np.empty((nf.value, 3), np.int32)
         nrm = np.empty((nv.value, 3), np.float32) if normals else None
         col = np.empty((nv.value, 3), np.uint8) if rgb else None
-        self._ck(self.lib.hsk_extract_mesh_indexed(self.h, verts.ctypes.data, None if nrm is None else nrm.ctypes.data,
-                                                   None if col is None else col.ctypes.data, len(verts), C.byref(nv),
-                                                   faces.ctypes.data, len(faces), C.byref(nf), C.byref(nu)))
+        self._ck(call(False, verts.ctypes.data, None if nrm is None else nrm.ctypes.data, None if col is None else col.ctypes.data, len(verts),
+                      C.byref(nv), faces.ctypes.data, len(faces), C.byref(nf)))
         if (nv.value, nf.value) != (len(verts), len(faces)):
-            raise KinfuError("extract_mesh_indexed: the counts changed between the two calls")
-        return verts, faces, nrm, col, nu.value
+            raise KinfuError(f"{who}: the counts changed between the two calls")
+        return verts, faces, nrm, col
 
     def extract_mesh_simplified(self, cluster_voxels=4, mode=SIMPLIFY_QUADRIC, normals=True, rgb=False, sv_floor=0.0):
         """extract_mesh_indexed's surface reduced on the device by quadric vertex clustering on cells of `cluster_voxels` (2, 4, 8
@@ -746,18 +765,10 @@ class KinfuTracker:
         cells -> (vertices [n, 3] float32, faces [m, 3] int32, normals [n, 3] float32 or None, rgb [n, 3] uint8 or None, stats:
         a dict of hsk_simplify_stats' fields).  rgb=True needs enable_color()."""
         p = _lib.HskSimplifyParams(cluster_voxels, mode, sv_floor)
-        nv, nf, st = C.c_size_t(), C.c_size_t(), _lib.HskSimplifyStats()
-        self._ck(self.lib.hsk_extract_mesh_simplified(self.h, C.byref(p), None, None, None, 0, C.byref(nv), None, 0, C.byref(nf), C.byref(st)))
-        verts = np.empty((nv.value, 3), np.float32)
-        faces = np.empty((nf.value, 3), np.int32)
-        nrm = np.empty((nv.value, 3), np.float32) if normals else None
-        col = np.empty((nv.value, 3), np.uint8) if rgb else None
-        self._ck(self.lib.hsk_extract_mesh_simplified(self.h, C.byref(p), verts.ctypes.data, None if nrm is None else nrm.ctypes.data,
-                                                      None if col is None else col.ctypes.data, len(verts), C.byref(nv),
-                                                      faces.ctypes.data, len(faces), C.byref(nf), C.byref(st)))
-        if (nv.value, nf.value) != (len(verts), len(faces)):
-            raise KinfuError("extract_mesh_simplified: the counts changed between the two calls")
-        return verts, faces, nrm, col, simplify_stats_dict(st)
+        st = _lib.HskSimplifyStats()
+        mesh = self._indexed_mesh("extract_mesh_simplified", normals, rgb, lambda first, *a: self.lib.hsk_extract_mesh_simplified(
+            self.h, C.byref(p), *a, C.byref(st)))
+        return mesh + (simplify_stats_dict(st),)
 
     # ---- baked textures -------------------------------------------------------------------------------
     def bake_texture(self, vertices, faces, texels_per_metre=0.0, atlas_width=0, n_iter=4, f_tol=0.01, max_offset_m=0.0, rgb=True,
@@ -769,19 +780,23 @@ class KinfuTracker:
         images asked for: rgb (h, w, 3) uint8 (needs enable_color()), normal_rgb (h, w, 3) uint8, mask (h, w) uint8 of TEXEL_* bits."""
         v, f = _texture_mesh(vertices, faces)
         p = _lib.HskTextureParams(texels_per_metre, atlas_width, n_iter, f_tol, max_offset_m)
-        info = _lib.HskTextureInfo()
         args = (self.h, v.ctypes.data, len(v), f.ctypes.data, len(f), C.byref(p))
-        self._ck(self.lib.hsk_bake_texture(*args, None, None, None, 0, None, None, C.byref(info)))
+        base, out = self._bake("bake_texture", len(f), {"rgb": (rgb, 3), "normal_rgb": (normal_rgb, 3), "mask": (mask, 1)},
+                               lambda first, images, *a: self.lib.hsk_bake_texture(*args, *images, *a))
+        return dict(base, **out)
+
+    def _bake(self, who, n_faces, wanted, call):
+        """the size query and the fill of a bake: call(first, the pointers of the images in `wanted`'s order -- name: (asked for,
+        channels) --, cap_texels, uv, charts, info) -> (texture_layout's dict, the images asked for by name)"""
+        info = _lib.HskTextureInfo()
+        self._ck(call(True, [None] * len(wanted), 0, None, None, C.byref(info)))
         w, h = int(info.width), int(info.height)
-        out = {"rgb": np.empty((h, w, 3), np.uint8) if rgb else None, "normal_rgb": np.empty((h, w, 3), np.uint8) if normal_rgb else None,
-               "mask": np.empty((h, w), np.uint8) if mask else None}
-        uv, charts = np.zeros((len(f), 3, 2), np.float32), np.zeros(len(f), TEXTURE_CHART_DTYPE)
-        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        self._ck(self.lib.hsk_bake_texture(*args, ptr(out["rgb"]), ptr(out["normal_rgb"]), ptr(out["mask"]), w * h, uv.ctypes.data, charts.ctypes.data,
-                                           C.byref(info)))
+        out = {k: np.empty((h, w, 3) if ch == 3 else (h, w), np.uint8) for k, (want, ch) in wanted.items() if want}
+        uv, charts = np.zeros((n_faces, 3, 2), np.float32), np.zeros(n_faces, TEXTURE_CHART_DTYPE)
+        self._ck(call(False, [out[k].ctypes.data if k in out else None for k in wanted], w * h, uv.ctypes.data, charts.ctypes.data, C.byref(info)))
         if (int(info.width), int(info.height)) != (w, h):
-            raise KinfuError("bake_texture: the atlas changed size between the two calls")
-        return dict(texture_info_dict(info), uv=uv, charts=charts, **{k: a for k, a in out.items() if a is not None})
+            raise KinfuError(f"{who}: the atlas changed size between the two calls")
+        return dict(texture_info_dict(info), uv=uv, charts=charts), out
 
     # ---- keyframe textures ---------------------------------------------------------------------------
     def enable_keyframes(self, cap=64, w=None, h=None):
@@ -840,25 +855,12 @@ class KinfuTracker:
         (the winning keyframe, KEYTEX_NONE: none) and hsk_keytex_info's fields."""
         v, f = _texture_mesh(vertices, faces)
         p = _lib.HskTextureParams(texels_per_metre, atlas_width, n_iter, f_tol, max_offset_m)
-        kp = self.default_keytex_params()
-        for name, val in keytex.items():
-            if name not in dict(kp._fields_):
-                raise TypeError(f"bake_texture_keyframes: hsk_keytex_params has no field {name!r}")
-            setattr(kp, name, val)
-        info, kinfo = _lib.HskTextureInfo(), _lib.HskKeytexInfo()
+        kp = _override(self.default_keytex_params(), dict(_lib.HskKeytexParams._fields_), "bake_texture_keyframes: hsk_keytex_params has no field", keytex)
+        kinfo = _lib.HskKeytexInfo()
         args = (self.h, v.ctypes.data, len(v), f.ctypes.data, len(f), C.byref(p), C.byref(kp))
-        self._ck(self.lib.hsk_bake_texture_keyframes(*args, None, None, None, None, 0, None, None, C.byref(info), None))
-        w, h = int(info.width), int(info.height)
-        out = {"rgb": np.empty((h, w, 3), np.uint8) if rgb else None, "normal_rgb": np.empty((h, w, 3), np.uint8) if normal_rgb else None,
-               "mask": np.empty((h, w), np.uint8) if mask else None, "source": np.empty((h, w), np.uint8) if source else None}
-        uv, charts = np.zeros((len(f), 3, 2), np.float32), np.zeros(len(f), TEXTURE_CHART_DTYPE)
-        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        self._ck(self.lib.hsk_bake_texture_keyframes(*args, ptr(out["rgb"]), ptr(out["normal_rgb"]), ptr(out["mask"]), ptr(out["source"]), w * h,
-                                                     uv.ctypes.data, charts.ctypes.data, C.byref(info), C.byref(kinfo)))
-        if (int(info.width), int(info.height)) != (w, h):
-            raise KinfuError("bake_texture_keyframes: the atlas changed size between the two calls")
-        return dict(texture_info_dict(info), uv=uv, charts=charts, **{k: int(getattr(kinfo, k)) for k in KEYTEX_INFO_FIELDS},
-                    **{k: a for k, a in out.items() if a is not None})
+        base, out = self._bake("bake_texture_keyframes", len(f), {"rgb": (rgb, 3), "normal_rgb": (normal_rgb, 3), "mask": (mask, 1), "source": (source, 1)},
+                               lambda first, images, *a: self.lib.hsk_bake_texture_keyframes(*args, *images, *a, None if first else C.byref(kinfo)))
+        return dict(base, **{k: int(getattr(kinfo, k)) for k in KEYTEX_INFO_FIELDS}, **out)
 
     # ---- scene views ----------------------------------------------------------------------------------
     def default_view(self):
@@ -931,8 +933,7 @@ class KinfuTracker:
         m = np.ascontiguousarray(src_to_dst, np.float32).reshape(16)
         st = _lib.HskFuseStats()
         self._ck(self.lib.hsk_fuse_volume(self.h, None if src is None else src.h, _fp(m), C.byref(st)))
-        return {"n_fused": int(st.n_fused), "n_colored": int(st.n_colored), "chunks_total": int(st.chunks_total),
-                "chunks_swept": int(st.chunks_swept), "box": tuple(int(x) for x in st.box)}
+        return dict(_stats_dict(st), box=tuple(int(x) for x in st.box))
 
     # ---- volume alignment -----------------------------------------------------------------------------
     def default_align_params(self):
@@ -948,11 +949,7 @@ class KinfuTracker:
         p = _lib.HskAlignParams()
         if probes is not None:
             p.probes = _lib.HSK_ALIGN_DIRECT if int(probes) == 0 else int(probes)
-        for name, val in over.items():
-            if not hasattr(p, name) or name == "probes":
-                raise TypeError(f"unknown alignment parameter {name!r}")
-            setattr(p, name, val)
-        return p
+        return _override(p, [name for name, _ in p._fields_ if name != "probes"], "unknown alignment parameter", over)
 
     @staticmethod
     def _align_result(out, st):
@@ -1006,11 +1003,6 @@ class KinfuTracker:
             raise ValueError("poses must be [n, 4, 4] (or [n, 16]) matrices")
         return p.reshape(-1, 16)
 
-    @staticmethod
-    def _score_dict(s):
-        return {"n_near": int(s.n_near), "n_free": int(s.n_free), "n_behind": int(s.n_behind), "n_unseen": int(s.n_unseen),
-                "n_outside": int(s.n_outside), "n_skipped": int(s.n_skipped), "sum_abs": int(s.sum_abs)}
-
     def score_cloud(self, xyz, poses):
         """how the points xyz [n, 3] (camera coordinates) lie in this volume under each of the poses [m, 4, 4]
         (hsk_score_cloud) -> a structured array [m] with the fields n_near, n_free, n_behind, n_unseen, n_outside,
@@ -1024,28 +1016,15 @@ class KinfuTracker:
 
     # ---- scan coverage ----------------------------------------------------------------------------------
     def _probe(self, probe, fields):
-        if probe is None:
-            return default_probe(self, **fields)
-        p = _lib.HskProbe.from_buffer_copy(probe)
-        for name, val in fields.items():
-            if name not in PROBE_FIELDS:
-                raise TypeError(f"a probe has no field {name!r}")
-            setattr(p, name, val)
-        return p
+        return _params(_PROBE, self, probe, fields)
 
     def coverage(self, box=None):
         """the census of the volume's observation state (hsk_coverage_census) over the voxels lo <= (x, y, z) < hi of
         box = (lo, hi), None: the whole volume -> dict: n_unseen, n_free, n_solid, n_frontier (ints) and faces [6] uint64, the
         (free voxel, unseen neighbour) pairs by direction -x, +x, -y, +y, -z, +z; legal with frames in flight"""
-        b = None
-        if box is not None:
-            b = _lib.HskVoxelBox()
-            b.lo[:] = [int(v) for v in box[0]]
-            b.hi[:] = [int(v) for v in box[1]]
         c = _lib.HskCoverage()
-        self._ck(self.lib.hsk_coverage_census(self.h, C.byref(b) if b is not None else None, C.byref(c)))
-        return {"n_unseen": int(c.n_unseen), "n_free": int(c.n_free), "n_solid": int(c.n_solid), "n_frontier": int(c.n_frontier),
-                "faces": np.array(list(c.faces), np.uint64)}
+        self._ck(self.lib.hsk_coverage_census(self.h, _box(self.cfg, box)[0], C.byref(c)))
+        return _stats_dict(c)
 
     def score_views(self, poses, probe=None, **probe_fields):
         """how much never-seen space a camera at each of the poses [m, 4, 4] would reveal (hsk_score_views).  probe: an HskProbe
@@ -1079,14 +1058,9 @@ class KinfuTracker:
         (hsk_label_components) -> (records, stats): a structured array with COMPONENT_DTYPE -- root (x, y, z), n_voxels, the box
         lo, hi (exclusive) -- ordered by n_voxels descending, ties to the smaller root; stats: n_components, n_inside, largest,
         labels_reused (the labelling of an earlier call was still valid).  Not with frames in flight"""
-        n = C.c_size_t(0)
-        st = _lib.HskComponentStats()
-        self._ck(self.lib.hsk_label_components(self.h, None, 0, C.byref(n), C.byref(st)))
-        recs = np.zeros(n.value, COMPONENT_DTYPE)
-        if n.value:   # (the fill finds the labelling of the size query: labels_reused is the size query's)
-            self._ck(self.lib.hsk_label_components(self.h, recs.ctypes.data_as(C.POINTER(_lib.HskComponent)), n.value, C.byref(n), None))
-        return recs, {"n_components": int(st.n_components), "n_inside": int(st.n_inside), "largest": int(st.largest),
-                      "labels_reused": int(st.labels_reused)}
+        st = _lib.HskComponentStats()   # (the fill finds the labelling of the size query: labels_reused is the size query's)
+        recs = _records(_lib.HskComponent, lambda *a: self._ck(self.lib.hsk_label_components(self.h, *a)), st)
+        return recs, _stats_dict(st)
 
     def download_components(self):
         """the dense label volume [vol_z, vol_y, vol_x] uint32 (hsk_download_components): an inside voxel's label is the smallest
@@ -1104,27 +1078,13 @@ class KinfuTracker:
         or observed free space (PRUNE_FREE), their colour 0; every other word stays bit for bit.  params: an HskPruneParams
         (default: default_prune_params(self)); the keywords override its fields -> dict: n_components, n_pruned,
         n_pruned_voxels, n_kept_voxels"""
-        p = default_prune_params(self) if params is None else _lib.HskPruneParams.from_buffer_copy(params)
-        for name, val in fields.items():
-            if name not in PRUNE_FIELDS:
-                raise TypeError(f"prune parameters have no field {name!r}")
-            setattr(p, name, val)
-        st = _lib.HskPruneStats()
+        p, st = _params(_PRUNE, self, params, fields), _lib.HskPruneStats()
         self._ck(self.lib.hsk_prune_components(self.h, C.byref(p), C.byref(st)))
-        return {"n_components": int(st.n_components), "n_pruned": int(st.n_pruned), "n_pruned_voxels": int(st.n_pruned_voxels),
-                "n_kept_voxels": int(st.n_kept_voxels)}
+        return _stats_dict(st)
 
     # ---- hole filling ------------------------------------------------------------------------------------
     def default_fill_params(self, **fields):
         return default_fill_params(self, **fields)
-
-    def _voxel_box(self, box):
-        if box is None:
-            return None
-        b = _lib.HskVoxelBox()
-        b.lo[:] = [int(v) for v in box[0]]
-        b.hi[:] = [int(v) for v in box[1]]
-        return b
 
     def fill_holes(self, params=None, box=None, **fields):
         """closes the volume's gaps by volumetric diffusion (hsk_fill_holes): the signed distance of the observed voxels diffuses
@@ -1134,25 +1094,16 @@ class KinfuTracker:
         HskFillParams (default: default_fill_params(self)); the keywords override its fields -> dict: n_unseen, n_reached,
         n_written, n_written_negative, tile_visits, iterations_run.  download_fill_mask tells which voxels were written.  Not with
         frames in flight"""
-        p = default_fill_params(self) if params is None else _lib.HskFillParams.from_buffer_copy(params)
-        for name, val in fields.items():
-            if name not in FILL_FIELDS:
-                raise TypeError(f"fill parameters have no field {name!r}")
-            setattr(p, name, val)
-        b = self._voxel_box(box)
-        st = _lib.HskFillStats()
-        self._ck(self.lib.hsk_fill_holes(self.h, C.byref(p), C.byref(b) if b is not None else None, C.byref(st)))
-        return {"n_unseen": int(st.n_unseen), "n_reached": int(st.n_reached), "n_written": int(st.n_written),
-                "n_written_negative": int(st.n_written_negative), "tile_visits": int(st.tile_visits), "iterations_run": int(st.iterations_run)}
+        p, st = _params(_FILL, self, params, fields), _lib.HskFillStats()
+        self._ck(self.lib.hsk_fill_holes(self.h, C.byref(p), _box(self.cfg, box)[0], C.byref(st)))
+        return _stats_dict(st)
 
     def download_fill_mask(self, box=None):
         """which voxels the last fill_holes wrote (hsk_download_fill_mask) over the voxels lo <= (x, y, z) < hi of box = (lo, hi),
         None: the whole volume -> [z, y, x] uint8, 1 written, 0 not; refused once the volume has changed since that fill"""
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        b, shape = _box(self.cfg, box)
         out = np.empty(shape, np.uint8)
-        b = self._voxel_box(box)
-        self._ck(self.lib.hsk_download_fill_mask(self.h, C.byref(b) if b is not None else None, out.ctypes.data if out.size else None))
+        self._ck(self.lib.hsk_download_fill_mask(self.h, b, out.ctypes.data if out.size else None))
         return out
 
     # ---- volume differencing ----------------------------------------------------------------------------
@@ -1168,45 +1119,25 @@ class KinfuTracker:
         n_voxels descending, ties to the smaller root; stats: n_class [7], n_regions, n_minor_regions, largest.  The diff is held in
         this tracker: download_diff, diff_at, adopt_diff.  A cur in another frame is resampled first (resampled_like).  The size
         query and the fill diff once: the second call is answered from the held diff"""
-        p = default_diff_params(self) if params is None else _lib.HskDiffParams.from_buffer_copy(params)
-        for name, val in fields.items():
-            if name not in DIFF_FIELDS:
-                raise TypeError(f"diff parameters have no field {name!r}")
-            setattr(p, name, int(val))
-        n = C.c_size_t(0)
-        st = _lib.HskDiffStats()
-        self._ck(self.lib.hsk_diff_volume(self.h, cur.h, C.byref(p), None, 0, C.byref(n), C.byref(st)))
-        recs = np.zeros(n.value, DIFF_REGION_DTYPE)
-        if n.value:
-            self._ck(self.lib.hsk_diff_volume(self.h, cur.h, C.byref(p), recs.ctypes.data_as(C.POINTER(_lib.HskDiffRegion)), n.value, C.byref(n), C.byref(st)))
-        return recs, {"n_class": np.array(list(st.n_class), np.uint64), "n_regions": int(st.n_regions), "n_minor_regions": int(st.n_minor_regions),
-                      "largest": int(st.largest)}
+        p, st = _params(_DIFF, self, params, fields), _lib.HskDiffStats()
+        recs = _records(_lib.HskDiffRegion, lambda *a: self._ck(self.lib.hsk_diff_volume(self.h, cur.h, C.byref(p), *a)), st)
+        return recs, _stats_dict(st)
 
     def download_diff(self, box=None, region=True):
         """the held diff over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_diff) ->
         (cls [z, y, x] uint8, region [z, y, x] uint32 or None): a region is the root's (z vol_y + y) vol_x + x for APPEARED and
         VANISHED voxels, COMPONENT_NONE elsewhere; refused once this tracker's volume has changed since the diff"""
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        b, shape = _box(self.cfg, box)
         cls = np.empty(shape, np.uint8)
         reg = np.empty(shape, np.uint32) if region else None
-        b = self._voxel_box(box)
-        self._ck(self.lib.hsk_download_diff(self.h, C.byref(b) if b is not None else None, cls.ctypes.data if cls.size else None,
-                                            reg.ctypes.data if region and reg.size else None))
+        self._ck(self.lib.hsk_download_diff(self.h, b, cls.ctypes.data if cls.size else None, reg.ctypes.data if region and reg.size else None))
         return cls, reg
 
     def diff_at(self, xyz, radius=1):
         """the held diff at the world points xyz [n, 3] (hsk_diff_at, 2^20 points a call): the nearest APPEARED or VANISHED voxel within
         Chebyshev `radius` (0..4) of the point's voxel, else the voxel's own class -> (cls [n] uint8, region [n] uint32); a point
         outside the grid gives DIFF_UNSEEN and COMPONENT_NONE"""
-        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        cls, reg = np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint32)
-        step = _lib.HSK_CLEAR_MAX_POINTS                    # (the call takes 2^20 points: a mesh's vertices go in pieces)
-        for at in range(0, max(len(pts), 1), step):
-            m = min(step, len(pts) - at)
-            self._ck(self.lib.hsk_diff_at(self.h, pts[at:].ctypes.data if m else None, m, int(radius), cls[at:].ctypes.data if m else None,
-                                          reg[at:].ctypes.data if m else None))
-        return cls, reg
+        return tuple(_at_points(xyz, (np.uint8, np.uint32), lambda pts, m, *out: self._ck(self.lib.hsk_diff_at(self.h, pts, m, int(radius), *out))))
 
     def adopt_diff(self, cur, which=ADOPT_APPEARED | ADOPT_VANISHED, halo=2):
         """takes cur's words (and colour) where a kept region of the held diff says the scene changed (hsk_adopt_diff): every voxel
@@ -1215,7 +1146,7 @@ class KinfuTracker:
         p = _lib.HskAdoptParams(int(which), int(halo))
         st = _lib.HskAdoptStats()
         self._ck(self.lib.hsk_adopt_diff(self.h, cur.h, C.byref(p), C.byref(st)))
-        return {"n_targets": int(st.n_targets), "n_adopted": int(st.n_adopted), "n_colored": int(st.n_colored)}
+        return _stats_dict(st)
 
     def release_diff(self):
         """frees the held diff and its scratch (hsk_release_diff)"""
@@ -1241,70 +1172,45 @@ class KinfuTracker:
         root, n_voxels, sum, the box lo, hi (exclusive), contact, plane_mask, height_lo, height_hi -- of the kept objects, ordered
         by n_voxels descending, ties to the smaller root; stats: n_class [7], n_objects, n_minor_objects, largest, n_edge,
         n_no_normal, reused.  The split is held in this tracker: download_split, split_at, remove_objects"""
-        p = default_split_params(self) if params is None else _lib.HskSplitParams.from_buffer_copy(params)
-        for name, val in fields.items():
-            if name not in SPLIT_FIELDS:
-                raise TypeError(f"split parameters have no field {name!r}")
-            setattr(p, name, int(val) if name == "min_voxels" else float(val))
+        p, st = _params(_SPLIT, self, params, fields), _lib.HskSplitStats()
         pl = self._split_planes(planes)
         ptr = pl.ctypes.data_as(C.POINTER(_lib.HskSplitPlane)) if len(pl) else None
-        n = C.c_size_t(0)
-        st = _lib.HskSplitStats()
-        self._ck(self.lib.hsk_split_scene(self.h, ptr, len(pl), C.byref(p), None, 0, C.byref(n), C.byref(st)))
-        recs = np.zeros(n.value, OBJECT_DTYPE)
-        if n.value:
-            first = int(st.reused)
-            self._ck(self.lib.hsk_split_scene(self.h, ptr, len(pl), C.byref(p), recs.ctypes.data_as(C.POINTER(_lib.HskObject)), n.value, C.byref(n), C.byref(st)))
-            st.reused = first                              # (the fill is always answered from the size query's split)
-        return recs, {"n_class": np.array(list(st.n_class), np.uint64), "n_objects": int(st.n_objects), "n_minor_objects": int(st.n_minor_objects),
-                      "largest": int(st.largest), "n_edge": int(st.n_edge), "n_no_normal": int(st.n_no_normal), "reused": int(st.reused)}
+        recs = _records(_lib.HskObject, lambda *a: self._ck(self.lib.hsk_split_scene(self.h, ptr, len(pl), C.byref(p), *a)), st)
+        return recs, _stats_dict(st)
 
     def download_split(self, box=None, plane=True, object=True):
         """the held split over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_split) ->
         (cls [z, y, x] uint8, plane [z, y, x] uint8 or None, object [z, y, x] uint32 or None): a plane is the index of the voxel's
         plane, 0xff where it has none; an object the root's (z vol_y + y) vol_x + x for OBJECT voxels, COMPONENT_NONE elsewhere;
         refused once this tracker's volume has changed since the split"""
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        shape = tuple(max(int(hi[i]) - int(lo[i]), 0) for i in (2, 1, 0))
+        b, shape = _box(self.cfg, box)
         cls = np.empty(shape, np.uint8)
         pln = np.empty(shape, np.uint8) if plane else None
         obj = np.empty(shape, np.uint32) if object else None
-        b = self._voxel_box(box)
-        self._ck(self.lib.hsk_download_split(self.h, C.byref(b) if b is not None else None, cls.ctypes.data if cls.size else None,
-                                             pln.ctypes.data if plane and pln.size else None, obj.ctypes.data if object and obj.size else None))
+        self._ck(self.lib.hsk_download_split(self.h, b, cls.ctypes.data if cls.size else None, pln.ctypes.data if plane and pln.size else None,
+                                             obj.ctypes.data if object and obj.size else None))
         return cls, pln, obj
 
     def split_at(self, xyz, radius=1):
         """the held split at the world points xyz [n, 3] (hsk_split_at, 2^20 points a call): the nearest voxel with a class within
         Chebyshev `radius` (0..4) of the point's voxel -> (cls [n] uint8, plane [n] uint8, object [n] uint32); with none, or outside
         the grid, SPLIT_NONE, 0xff and COMPONENT_NONE"""
-        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        cls, pln, obj = np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint8), np.empty(len(pts), np.uint32)
-        step = _lib.HSK_CLEAR_MAX_POINTS                    # (the call takes 2^20 points: a mesh's vertices go in pieces)
-        for at in range(0, max(len(pts), 1), step):
-            m = min(step, len(pts) - at)
-            self._ck(self.lib.hsk_split_at(self.h, pts[at:].ctypes.data if m else None, m, int(radius), cls[at:].ctypes.data if m else None,
-                                           pln[at:].ctypes.data if m else None, obj[at:].ctypes.data if m else None))
-        return cls, pln, obj
+        return tuple(_at_points(xyz, (np.uint8, np.uint8, np.uint32),
+                                lambda pts, m, *out: self._ck(self.lib.hsk_split_at(self.h, pts, m, int(radius), *out))))
 
     def remove_objects(self, roots=None, params=None, **fields):
         """takes kept objects of the held split out of the volume (hsk_remove_objects).  roots: their labels (None: all kept);
         params: an HskRemoveParams (default: default_remove_params(self)); the keywords -- mode, halo, fill_weight -- override its
         fields.  REMOVE_RESTORE rewrites what the objects hid from the planes they touched, REMOVE_ERASE only erases -> dict:
         n_objects, n_targets, n_written, n_restored, n_colored"""
-        p = default_remove_params(self) if params is None else _lib.HskRemoveParams.from_buffer_copy(params)
-        for name, val in fields.items():
-            if name not in REMOVE_FIELDS:
-                raise TypeError(f"remove parameters have no field {name!r}")
-            setattr(p, name, int(val))
-        st = _lib.HskRemoveStats()
+        p, st = _params(_REMOVE, self, params, fields), _lib.HskRemoveStats()
         if roots is None:
             self._ck(self.lib.hsk_remove_objects(self.h, None, 0, C.byref(p), C.byref(st)))
         else:
             r = np.ascontiguousarray(roots, np.uint32).reshape(-1)
             keep = r if len(r) else np.zeros(1, np.uint32)     # (a pointer that is not NULL: an empty selection, not "all")
             self._ck(self.lib.hsk_remove_objects(self.h, keep.ctypes.data, len(r), C.byref(p), C.byref(st)))
-        return {name: int(getattr(st, name)) for name in ("n_objects", "n_targets", "n_written", "n_restored", "n_colored")}
+        return _stats_dict(st)
 
     def release_split(self):
         """frees the held split and its scratch (hsk_release_split)"""
@@ -1330,13 +1236,7 @@ class KinfuTracker:
         return default_clearance_params(self, **fields)
 
     def _clearance(self, params, fields):
-        p = default_clearance_params(self) if params is None else _lib.HskClearanceParams.from_buffer_copy(params)
-        return _clearance_fields(p, fields)
-
-    @staticmethod
-    def _clearance_stats(st):
-        return {"n_obstacle": int(st.n_obstacle), "n_far": int(st.n_far), "scratch_bytes": int(st.scratch_bytes),
-                "max_d2_seen": int(st.max_d2_seen), "reused": int(st.reused)}
+        return _params(_CLEARANCE, self, params, fields)
 
     def build_clearance(self, params=None, **fields):
         """builds the clearance field on the device (hsk_build_clearance): per voxel the exact weighted squared distance, in
@@ -1346,41 +1246,29 @@ class KinfuTracker:
         max_d2_seen, reused (the field of an earlier call was still valid).  Not with frames in flight"""
         st = _lib.HskClearanceStats()
         self._ck(self.lib.hsk_build_clearance(self.h, C.byref(self._clearance(params, fields)), C.byref(st)))
-        return self._clearance_stats(st)
+        return _stats_dict(st)
 
     def download_clearance(self, params=None, box=None, **fields):
         """the field over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume (hsk_download_clearance; builds
         first when no valid field is held) -> [z, y, x] uint32"""
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        b = _lib.HskVoxelBox()
-        b.lo[:] = [int(v) for v in lo]
-        b.hi[:] = [int(v) for v in hi]
-        shape = tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0))
+        b, shape = _box(self.cfg, box)
         out = np.empty(shape, np.uint32)
-        self._ck(self.lib.hsk_download_clearance(self.h, C.byref(self._clearance(params, fields)), C.byref(b) if box is not None else None,
-                                                 out.ctypes.data))
+        self._ck(self.lib.hsk_download_clearance(self.h, C.byref(self._clearance(params, fields)), b, out.ctypes.data))
         return out
 
     def clearance_at(self, xyz, params=None, **fields):
         """the field at the voxels of the world points xyz [n, 3] (hsk_clearance_at; at most 2^20) -> [n] uint32, CLEARANCE_OUTSIDE
         for a point outside the grid or with a NaN"""
-        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        out = np.empty(len(pts), np.uint32)
-        self._ck(self.lib.hsk_clearance_at(self.h, C.byref(self._clearance(params, fields)), pts.ctypes.data if len(pts) else None, len(pts),
-                                           out.ctypes.data if len(pts) else None))
-        return out
+        p = self._clearance(params, fields)
+        return _at_points(xyz, (np.uint32,), lambda *a: self._ck(self.lib.hsk_clearance_at(self.h, C.byref(p), *a)))[0]
 
     def clearance_floor(self, axis, lo, hi, params=None, **fields):
         """the floor map (hsk_clearance_floor): for the up axis (0 x, 1 y, 2 z) and its planes lo <= p < hi a column is an obstacle
         when any voxel of its band is; the 2-D clearance over the two remaining axes -> (map [v, u] uint32 with u the
         lower-numbered remaining axis, stats dict)"""
-        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
-        ok = axis in (0, 1, 2)
-        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
-        out = np.empty((nv, nu), np.uint32)
-        st = _lib.HskClearanceStats()
+        out, st = np.empty(_floor_shape(self.cfg, axis), np.uint32), _lib.HskClearanceStats()
         self._ck(self.lib.hsk_clearance_floor(self.h, C.byref(self._clearance(params, fields)), int(axis), int(lo), int(hi), out.ctypes.data, C.byref(st)))
-        return out, self._clearance_stats(st)
+        return out, _stats_dict(st)
 
     def release_clearance(self):
         """frees the field and its scratch (hsk_release_clearance); the next call that needs it builds again"""
@@ -1395,15 +1283,7 @@ class KinfuTracker:
         (default: default_reach_params for the clearance parameters as overridden), all others to the clearance parameters"""
         own = {k: fields.pop(k) for k in REACH_FIELDS if k in fields}
         cp = self._clearance(params, fields)
-        rp = default_reach_params(self, cp) if reach is None else _lib.HskReachParams.from_buffer_copy(reach)
-        for name, val in own.items():
-            setattr(rp, name, int(val))
-        return cp, rp
-
-    @staticmethod
-    def _reach_stats(st):
-        return {"n_passable": int(st.n_passable), "n_reached": int(st.n_reached), "scratch_bytes": int(st.scratch_bytes),
-                "max_cost_seen": int(st.max_cost_seen), "n_rounds": int(st.n_rounds), "n_seeds_used": int(st.n_seeds_used), "reused": int(st.reused)}
+        return cp, _params(_REACH, self, reach, own, (cp,))
 
     @staticmethod
     def _seeds(seeds):
@@ -1419,26 +1299,20 @@ class KinfuTracker:
         pts = self._seeds(seeds)
         st = _lib.HskReachStats()
         self._ck(self.lib.hsk_build_reach(self.h, C.byref(cp), C.byref(rp), pts.ctypes.data if len(pts) else None, len(pts), C.byref(st)))
-        return self._reach_stats(st)
+        return _stats_dict(st)
 
     def download_reach(self, box=None):
         """the reach field held over the voxels lo <= (x, y, z) < hi of box = (lo, hi), None: the whole volume
         (hsk_download_reach) -> [z, y, x] uint32"""
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        b = _lib.HskVoxelBox()
-        b.lo[:] = [int(v) for v in lo]
-        b.hi[:] = [int(v) for v in hi]
-        out = np.empty(tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0)), np.uint32)
-        self._ck(self.lib.hsk_download_reach(self.h, C.byref(b) if box is not None else None, out.ctypes.data))
+        b, shape = _box(self.cfg, box)
+        out = np.empty(shape, np.uint32)
+        self._ck(self.lib.hsk_download_reach(self.h, b, out.ctypes.data))
         return out
 
     def reach_at(self, xyz):
         """the reach field held at the voxels of the world points xyz [n, 3] (hsk_reach_at; at most 2^20) -> [n] uint32,
         REACH_OUTSIDE for a point outside the grid or with a NaN"""
-        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        out = np.empty(len(pts), np.uint32)
-        self._ck(self.lib.hsk_reach_at(self.h, pts.ctypes.data if len(pts) else None, len(pts), out.ctypes.data if len(pts) else None))
-        return out
+        return _at_points(xyz, (np.uint32,), lambda *a: self._ck(self.lib.hsk_reach_at(self.h, *a)))[0]
 
     def reach_path(self, goal, cap=4096):
         """the path of the field held from a seed to the voxel of the world point `goal` (hsk_reach_path) -> [n, 3] int32 voxels
@@ -1458,14 +1332,10 @@ class KinfuTracker:
         seeds projected by dropping the up axis -> (map [v, u] uint32 with u the lower-numbered remaining axis, stats dict)"""
         cp, rp = self._reach(params, reach, fields)
         pts = self._seeds(seeds)
-        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
-        ok = axis in (0, 1, 2)
-        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
-        out = np.empty((nv, nu), np.uint32)
-        st = _lib.HskReachStats()
+        out, st = np.empty(_floor_shape(self.cfg, axis), np.uint32), _lib.HskReachStats()
         self._ck(self.lib.hsk_reach_floor(self.h, C.byref(cp), int(axis), int(lo), int(hi), C.byref(rp), pts.ctypes.data if len(pts) else None, len(pts),
                                           out.ctypes.data, C.byref(st)))
-        return out, self._reach_stats(st)
+        return out, _stats_dict(st)
 
     def release_reach(self):
         """frees the reach field and its scratch (hsk_release_reach)"""
@@ -1487,14 +1357,7 @@ class KinfuTracker:
         the clearance parameters"""
         own = {k: fields.pop(k) for k in PARTITION_FIELDS if k in fields}
         cp = self._clearance(params, fields)
-        pp = default_partition_params(self, cp) if partition is None else _lib.HskPartitionParams.from_buffer_copy(partition)
-        for name, val in own.items():
-            setattr(pp, name, int(val))
-        return cp, pp
-
-    @staticmethod
-    def _partition_stats(st):
-        return {name: int(getattr(st, name)) for name, _ in _lib.HskPartitionStats._fields_}
+        return cp, _params(_PARTITION, self, partition, own, (cp,))
 
     def build_partition(self, params=None, partition=None, **fields):
         """splits the scanned free space into rooms on the device (hsk_build_partition): the cores -- the 6-connected pieces of the
@@ -1505,30 +1368,18 @@ class KinfuTracker:
         n_rooms, n_doors, n_rounds, reused)"""
         cp, pp = self._partition(params, partition, fields)
         st = _lib.HskPartitionStats()
-        n = C.c_size_t(0)
-        self._ck(self.lib.hsk_build_partition(self.h, C.byref(cp), C.byref(pp), None, 0, C.byref(n), C.byref(st)))
-        rooms = np.zeros(n.value, ROOM_DTYPE)
-        if n.value:
-            self._ck(self.lib.hsk_build_partition(self.h, C.byref(cp), C.byref(pp), rooms.ctypes.data, n.value, C.byref(n), None))
-        return rooms, self._partition_stats(st)
+        rooms = _records(_lib.HskRoom, lambda *a: self._ck(self.lib.hsk_build_partition(self.h, C.byref(cp), C.byref(pp), *a)), st)
+        return rooms, _stats_dict(st)
 
     def partition_doors(self):
         """the doors of the partition held (hsk_partition_doors): one record per pair of rooms that meet -> a DOOR_DTYPE array
         ordered by (a, b)"""
-        n = C.c_size_t(0)
-        self._ck(self.lib.hsk_partition_doors(self.h, None, 0, C.byref(n)))
-        doors = np.zeros(n.value, DOOR_DTYPE)
-        if n.value:
-            self._ck(self.lib.hsk_partition_doors(self.h, doors.ctypes.data, n.value, C.byref(n)))
-        return doors
+        return _records(_lib.HskDoor, lambda recs, cap, n, _: self._ck(self.lib.hsk_partition_doors(self.h, recs, cap, n)))
 
     def _partition_box(self, call, box):
-        lo, hi = ((0, 0, 0), (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)) if box is None else box
-        b = _lib.HskVoxelBox()
-        b.lo[:] = [int(v) for v in lo]
-        b.hi[:] = [int(v) for v in hi]
-        out = np.empty(tuple(max(b.hi[i] - b.lo[i], 0) for i in (2, 1, 0)), np.uint32)
-        self._ck(call(self.h, C.byref(b) if box is not None else None, out.ctypes.data))
+        b, shape = _box(self.cfg, box)
+        out = np.empty(shape, np.uint32)
+        self._ck(call(self.h, b, out.ctypes.data))
         return out
 
     def download_partition(self, box=None):
@@ -1545,20 +1396,13 @@ class KinfuTracker:
         """the room of the world points xyz [n, 3] (hsk_partition_at; at most 2^20): that of the nearest voxel holding a room
         within `radius` (0..4) voxels on every axis of the point's own -> [n] uint32; ROOM_OUTSIDE for a point outside the grid or
         with a NaN, ROOM_NONE where there is no such voxel.  With a radius above 0 a surface point gets the room whose air it borders"""
-        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-        out = np.empty(len(pts), np.uint32)
-        self._ck(self.lib.hsk_partition_at(self.h, pts.ctypes.data if len(pts) else None, len(pts), int(radius), out.ctypes.data if len(pts) else None))
-        return out
+        return _at_points(xyz, (np.uint32,), lambda pts, m, out: self._ck(self.lib.hsk_partition_at(self.h, pts, m, int(radius), out)))[0]
 
     def partition_floor(self, axis, lo, hi, params=None, partition=None, **fields):
         """the floor form (hsk_partition_floor): the same rule on clearance_floor's map of the band -> (map [v, u] uint32 room ids
         with u the lower-numbered remaining axis, rooms, doors, stats dict)"""
         cp, pp = self._partition(params, partition, fields)
-        dims = (self.cfg.vol_x, self.cfg.vol_y, self.cfg.vol_z)
-        ok = axis in (0, 1, 2)
-        nu, nv = (dims[1 if axis == 0 else 0], dims[1 if axis == 2 else 2]) if ok else (1, 1)
-        out = np.empty((nv, nu), np.uint32)
-        st = _lib.HskPartitionStats()
+        out, st = np.empty(_floor_shape(self.cfg, axis), np.uint32), _lib.HskPartitionStats()
         rooms, doors = np.zeros(PARTITION_MAX_ROOMS, ROOM_DTYPE), np.zeros(64, DOOR_DTYPE)
         nr, nd = C.c_size_t(0), C.c_size_t(0)
         args = (self.h, C.byref(cp), int(axis), int(lo), int(hi), C.byref(pp), out.ctypes.data)
@@ -1567,7 +1411,7 @@ class KinfuTracker:
             doors = np.zeros(nd.value, DOOR_DTYPE)
             rc = self.lib.hsk_partition_floor(*args, rooms.ctypes.data, len(rooms), C.byref(nr), doors.ctypes.data, len(doors), C.byref(nd), C.byref(st))
         self._ck(rc)
-        return out, rooms[:nr.value].copy(), doors[:nd.value].copy(), self._partition_stats(st)
+        return out, rooms[:nr.value].copy(), doors[:nd.value].copy(), _stats_dict(st)
 
     def release_partition(self):
         """frees the partition and its scratch (hsk_release_partition)"""
@@ -1600,7 +1444,7 @@ class KinfuTracker:
         out, st = np.zeros(16, np.float32), _lib.HskRelocStats()
         self._ck(self.lib.hsk_relocalize(self.h, d.ctypes.data, d.shape[1], d.shape[0], ps.ctypes.data if len(ps) else None, len(ps),
                                          C.byref(p), _fp(out), C.byref(st)))
-        cands = [dict(index=int(st.candidate[r]), score=self._score_dict(st.score[r]), align_status=_lib.HSK_ALIGN_STATUS[st.align_status[r]],
+        cands = [dict(index=int(st.candidate[r]), score=_stats_dict(st.score[r]), align_status=_lib.HSK_ALIGN_STATUS[st.align_status[r]],
                       iterations=int(st.iterations[r]), n_used=int(st.n_used[r]), rms_m=np.float32(st.rms_m[r]))
                  for r in range(max(0, min(int(st.n_refined), _lib.HSK_RELOC_MAX_REFINE)))]
         return out.reshape(4, 4), {"status": _lib.HSK_RELOC_STATUS[st.status], "n_valid": int(st.n_valid), "n_candidates": int(st.n_candidates),
@@ -1612,11 +1456,7 @@ class KinfuTracker:
         """the defaults with the keywords dist_m, cos_min, min_fraction, max_planes, n_hypotheses, refits, seed over them"""
         p = _lib.HskPlaneParams()
         _lib.load().hsk_default_plane_params(C.byref(p))
-        for name, val in over.items():
-            if name not in dict(p._fields_):
-                raise TypeError(f"unknown plane parameter {name!r}")
-            setattr(p, name, val)
-        return p
+        return _override(p, dict(p._fields_), "unknown plane parameter", over)
 
     @staticmethod
     def _plane_records(rec, n):
@@ -1675,13 +1515,7 @@ class KinfuTracker:
         """the defaults with the keywords up_hint, max_tilt_cos, cone_cos, wall_sin, min_fraction, refits, flags over them"""
         p = _lib.HskUprightParams()
         _lib.load().hsk_default_upright_params(C.byref(p))
-        for name, val in over.items():
-            if name not in dict(p._fields_):
-                raise TypeError(f"unknown upright parameter {name!r}")
-            if name == "up_hint":
-                val = (C.c_float * 3)(*[float(v) for v in val])
-            setattr(p, name, val)
-        return p
+        return _override(p, dict(p._fields_), "unknown upright parameter", over)
 
     @staticmethod
     def _upright_dict(u):

@@ -175,6 +175,52 @@ def test_the_split_is_held_and_dropped_with_the_volume(hsk):
         trk.close()
 
 
+def test_every_subset_of_the_optional_arrays_gives_the_full_calls_bytes(hsk):
+    """hsk_split_at, hsk_download_split and hsk_download_diff called directly with their optional arrays null, both or each alone, on
+    the small room's 32 x 24 x 20 grid and a box that is neither empty nor the whole volume: cls, and whichever array is present,
+    equal the full call's (an absent array takes no room in the product buffer: the others move up)"""
+    key = ("shape", "objects in the small room")
+    c = SC.case_of(key)
+    trk, cur = loaded(hsk, key), ctx(hsk, c["dims"], c["size"])
+    try:
+        lib = trk.lib
+        recs, _ = split(hsk, trk, c)
+        assert len(recs) > 0
+        pts = SC.query_points(c["dims"], c["size"])
+        full = trk.split_at(pts, 2)
+        assert len(set(full[1].tolist())) > 1 and len(set(full[2].tolist())) > 1          # (planes and objects are both met)
+        for want_plane, want_object in ((False, False), (True, False), (False, True)):
+            cls, pln, obj = np.full(len(pts), 9, np.uint8), np.full(len(pts), 9, np.uint8), np.full(len(pts), 9, np.uint32)
+            assert lib.hsk_split_at(trk.h, pts.ctypes.data, len(pts), 2, cls.ctypes.data, pln.ctypes.data if want_plane else None,
+                                    obj.ctypes.data if want_object else None) == 0
+            assert np.array_equal(cls, full[0]) and np.array_equal(pln, full[1] if want_plane else np.full(len(pts), 9, np.uint8))
+            assert np.array_equal(obj, full[2] if want_object else np.full(len(pts), 9, np.uint32)), (want_plane, want_object)
+        lo, hi = (3, 2, 1), (29, 20, 17)
+        box = hsk._lib.HskVoxelBox((C.c_int * 3)(*lo), (C.c_int * 3)(*hi))
+        shape = (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0])
+        full = trk.download_split(box=(lo, hi))
+        assert full[0].shape == shape and len(np.unique(full[1])) > 1 and len(np.unique(full[2])) > 1
+        for want_plane, want_object in ((False, False), (True, False), (False, True)):
+            cls, pln, obj = np.full(shape, 9, np.uint8), np.full(shape, 9, np.uint8), np.full(shape, 9, np.uint32)
+            assert lib.hsk_download_split(trk.h, C.byref(box), cls.ctypes.data, pln.ctypes.data if want_plane else None,
+                                          obj.ctypes.data if want_object else None) == 0
+            assert np.array_equal(cls, full[0]) and np.array_equal(pln, full[1] if want_plane else np.full(shape, 9, np.uint8))
+            assert np.array_equal(obj, full[2] if want_object else np.full(shape, 9, np.uint32)), (want_plane, want_object)
+        # the diff against the small room without its objects
+        cur.upload_tsdf(SC.small_room())
+        regions, _ = trk.diff_volume(cur, min_voxels=1)
+        assert len(regions) > 0
+        full = trk.download_diff(box=(lo, hi))
+        assert full[0].shape == shape and len(np.unique(full[0])) > 1 and len(np.unique(full[1])) > 1
+        for want_region in (False, True):
+            cls, reg = np.full(shape, 9, np.uint8), np.full(shape, 9, np.uint32)
+            assert lib.hsk_download_diff(trk.h, C.byref(box), cls.ctypes.data, reg.ctypes.data if want_region else None) == 0
+            assert np.array_equal(cls, full[0]) and np.array_equal(reg, full[1] if want_region else np.full(shape, 9, np.uint32)), want_region
+    finally:
+        trk.close()
+        cur.close()
+
+
 def test_the_context_after_a_removal_equals_a_fresh_one_with_the_same_words(hsk):
     key = ("room", "two boxes")
     c, col = SC.case_of(key), SC.color_of(key)
