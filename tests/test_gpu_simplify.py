@@ -1,7 +1,12 @@
 """hsk_extract_mesh_simplified on the GPU: vertices, normals, colours, faces, counts and every statistic bit for bit against the
 numpy restatement of the rule (tests/simplify_twin.py) at every cluster size and in both modes, on the small volumes of
 tests/test_simplify_host.py and on a scanned room; a closed surface stays closed; a flat plane stays flat; the quadric finds a box's
-corners where the mean does not; the call protocol, the count cache, the refusals."""
+corners where the mean does not; the call protocol, the count cache, the refusals.  The simplified mesh's tests:
+  tests/test_simplify_host.py          the twin pinned by hand and to the kernels' shared text on the host; the small volumes
+  tests/test_gpu_simplify.py           this file: cluster rows of one 64-cluster segment, at most 1024 cluster rows
+  tests/simplify_cases.py              the wide and tall volumes and the census of what an input reaches
+  tests/test_simplify_shapes_host.py   that census asserted on the twin alone
+  tests/test_gpu_simplify_shapes.py    the device against the twin on those volumes: many segments, a second scan block"""
 import ctypes as C
 
 import numpy as np
