@@ -6,16 +6,14 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_align_point.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 1);
   int dims[3], J;
   float size[3], m[16], tau, gate;
   unsigned n;
-  bool ok = fread(dims, 4, 3, f) == 3 && fread(size, 4, 3, f) == 3 && fread(m, 4, 16, f) == 16 && fread(&tau, 4, 1, f) == 1 &&
-            fread(&gate, 4, 1, f) == 1 && fread(&J, 4, 1, f) == 1 && fread(&n, 4, 1, f) == 1;
-  if (!ok) return 2;
+  if (!(in.get(dims, 3) && in.get(size, 3) && in.get(m, 16) && in.get(&tau, 1) && in.get(&gate, 1) && in.get(&J, 1) && in.get(&n, 1))) return 2;
   AlignVol dv;
   AlignArgs aa;
   dv.X = dims[0];
@@ -32,11 +30,9 @@ int main(int argc, char** argv) {
   aa.cos_gate = gate;
   aa.J = J;
   aa.n = aa.pitch = n;
-  std::vector<unsigned> vol((size_t)dv.X * dv.Y * ((dv.Z + 3) & ~3));
+  std::vector<unsigned> vol(volume_words(dv.X, dv.Y, dv.Z));
   std::vector<float> soa((size_t)n * 6);
-  ok = fread(vol.data(), 4, vol.size(), f) == vol.size() && fread(soa.data(), 4, soa.size(), f) == soa.size();
-  fclose(f);
-  if (!ok) return 2;
+  if (!(in.get(vol) && in.get(soa))) return 2;
   double acc[28] = {0.0};
   unsigned n_used = 0;
   for (unsigned i = 0; i < n; ++i)

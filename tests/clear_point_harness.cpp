@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_clear_point.h"
+#include "harness_io.h"
 
 struct LoadDx {
   const unsigned short* p;
@@ -23,12 +24,11 @@ struct LoadU32 {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int dims[3];
   unsigned par[5], n_pts;
   float size[3];
-  if (fread(dims, 4, 3, f) != 3 || fread(par, 4, 5, f) != 5 || fread(size, 4, 3, f) != 3 || fread(&n_pts, 4, 1, f) != 1) return 2;
+  if (!(in.get(dims, 3) && in.get(par, 5) && in.get(size, 3) && in.get(&n_pts, 1))) return 2;
   const unsigned X = (unsigned)dims[0], Y = (unsigned)dims[1], Z = (unsigned)dims[2];
   const unsigned w[3] = {par[0], par[1], par[2]}, max_d2 = par[3], flags = par[4];
   unsigned R[3];
@@ -37,13 +37,9 @@ int main(int argc, char** argv) {
     if (R[a] > CLEAR_MAX_REACH) return 4;
   }
   std::vector<float> pts((size_t)n_pts * 3);
-  if (n_pts && fread(pts.data(), 12, n_pts, f) != n_pts) return 2;
-  // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
-  const size_t words = (size_t)X * Y * ((Z + 3u) & ~3u), n = (size_t)X * Y * Z;
-  std::vector<unsigned> vol(words);
-  const bool ok = fread(vol.data(), 4, words, f) == words;
-  fclose(f);
-  if (!ok) return 2;
+  const size_t n = (size_t)X * Y * Z;
+  std::vector<unsigned> vol(volume_words(X, Y, Z));
+  if (!(in.get(pts) && in.get(vol))) return 2;
   unsigned long long stats[3] = {0, 0, 0};
   // the x pass: a row's obstacle bits as exactly nw mask words, then every voxel's nearest bit
   const unsigned nw = (X + CLEAR_MASK_BITS - 1u) / CLEAR_MASK_BITS;
@@ -94,9 +90,7 @@ int main(int argc, char** argv) {
     const unsigned v = field[((size_t)z * Y + y) * X + x];
     at_pts[i] = inside ? v : CLEAR_OUTSIDE;
   }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
-  bool wr = fwrite(field.data(), 4, n, o) == n && fwrite(stats, 8, 3, o) == 3;
-  wr = wr && (n_pts == 0 || fwrite(at_pts.data(), 4, n_pts, o) == n_pts);
-  return fclose(o) == 0 && wr ? 0 : 2;
+  HarnessOut o(argv[2]);
+  o.put(field.data(), n), o.put(stats, 3), o.put(at_pts.data(), n_pts);
+  return o.finish();
 }

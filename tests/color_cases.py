@@ -3,7 +3,7 @@
 (tests/test_gpu_parity.py) for any image size, with a colour image of independent random bytes."""
 import numpy as np
 
-from test_gpu_parity import _lookat_pose, _random_pose
+from parity_cases import _lookat_pose, _random_pose
 
 TRUNC = 0.03
 # (X, Y, Z) voxels over metres
@@ -76,3 +76,55 @@ def fuzz_case(volume, camera, seed, frames=8):
 def inside(pose, size):
     t = pose[:3, 3]
     return bool(all(0.0 < t[i] < size[i] for i in range(3)))
+
+
+def frame_of(hsk, src, k):
+    """(pose, depth, rgb) of frame k of the scripted stream ("synth") or of room 0's scan ("room")"""
+    if src == "synth":
+        pose = hsk.synth_pose(k)
+        return pose, hsk.synth_depth(pose), hsk.synth_rgb(pose)
+    pose = hsk.synth_room_pose(0, k, 720)
+    return pose, hsk.synth_room_depth(0, pose), hsk.synth_rgb(pose, 0)
+
+
+def run_tracker(hsk, n, frames, color=True, use_graph=0, mode="sync", profile=False):
+    trk = hsk.KinfuTracker(n=n, use_graph=use_graph)
+    if color:
+        trk.enable_color()
+    if profile:
+        trk.set_profiling(1)
+    out = []
+    if mode == "sync":
+        for pose, depth, rgb in frames:
+            out.append(trk.process_frame_rgbd(depth, rgb) if color else trk.process_frame(depth))
+    else:
+        for i, (pose, depth, rgb) in enumerate(frames):
+            trk.submit_frame_rgbd(depth, rgb) if color else trk.submit_frame(depth)
+            if i >= 2:
+                out.append(trk.wait_frame())
+        while len(out) < len(frames):
+            out.append(trk.wait_frame())
+    return trk, out
+
+
+def read_pcd_xyzrgbnormal(path):
+    """numpy parse of the binary PCD: header lines, then 32-B records -> (header dict, xyz, rgb bits, normals, curvature)"""
+    raw = open(path, "rb").read()
+    head, pos = {}, 0
+    while True:
+        end = raw.index(b"\n", pos)
+        line = raw[pos:end].decode()
+        pos = end + 1
+        if line.startswith("#"):
+            continue
+        key, _, val = line.partition(" ")
+        head[key] = val
+        if key == "DATA":
+            break
+    n = int(head["POINTS"])
+    rec = np.frombuffer(raw[pos:], dtype=np.uint32)
+    assert rec.size == 8 * n, (rec.size, n)
+    rec = rec.reshape(n, 8)
+    xyz = rec[:, 0:3].copy().view(np.float32)
+    nrm = rec[:, 4:7].copy().view(np.float32)
+    return head, xyz, rec[:, 3].copy(), nrm, rec[:, 7].copy().view(np.float32)

@@ -9,19 +9,16 @@
 
 #include "../housescan_amd/csrc/hsk_comp_point.h"
 #include "../include/hskinfu.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int dims[3];
-  if (fread(dims, 4, 3, f) != 3) return 2;
+  if (!in.get(dims, 3)) return 2;
   const CompGrid g{(unsigned)dims[0], (unsigned)dims[1], (unsigned)dims[2]};
-  // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
-  const size_t words = (size_t)g.X * g.Y * ((g.Z + 3u) & ~3u);
+  const size_t words = volume_words(g.X, g.Y, g.Z);
   std::vector<unsigned> vol(words), parent(words, COMP_NONE);
-  const bool ok = fread(vol.data(), 4, words, f) == words;
-  fclose(f);
-  if (!ok) return 2;
+  if (!in.get(vol)) return 2;
   for (unsigned z = 0; z < g.Z; ++z)
     for (unsigned y = 0; y < g.Y; ++y)
       for (unsigned x = 0; x < g.X; ++x)
@@ -66,10 +63,8 @@ int main(int argc, char** argv) {
     return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), b.n_voxels,
                               g.lin((unsigned)b.root[0], (unsigned)b.root[1], (unsigned)b.root[2]));
   });
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
+  HarnessOut o(argv[2]);
   const unsigned n = (unsigned)recs.size();
-  bool w = fwrite(labels.data(), 4, labels.size(), o) == labels.size() && fwrite(&n, 4, 1, o) == 1;
-  w = w && (n == 0 || fwrite(recs.data(), sizeof(hsk_component), n, o) == n);
-  return fclose(o) == 0 && w ? 0 : 2;
+  o.put(labels), o.put(&n, 1), o.put(recs);
+  return o.finish();
 }

@@ -7,15 +7,14 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_cover_point.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 1);
   int dims[3], wh[2];
   float size[3], pf[7];
   unsigned n_poses;
-  bool ok = fread(dims, 4, 3, f) == 3 && fread(size, 4, 3, f) == 3 && fread(wh, 4, 2, f) == 2 && fread(pf, 4, 7, f) == 7 && fread(&n_poses, 4, 1, f) == 1;
-  if (!ok) return 2;
+  if (!(in.get(dims, 3) && in.get(size, 3) && in.get(wh, 2) && in.get(pf, 7) && in.get(&n_poses, 1))) return 2;
   SampleVol dv;
   dv.X = dims[0];
   dv.Y = dims[1];
@@ -35,11 +34,8 @@ int main(int argc, char** argv) {
   pr.step_m = pf[6];
   pr.n = cover_sample_count(pf[4], pf[5], pf[6]);
   std::vector<float> poses((size_t)n_poses * 16);
-  // (exactly the volume's words, as the device allocates them: a read past them is the sanitizer's to find)
-  std::vector<unsigned> vol((size_t)dv.X * dv.Y * ((dv.Z + 3) & ~3));
-  ok = fread(poses.data(), 4, poses.size(), f) == poses.size() && fread(vol.data(), 4, vol.size(), f) == vol.size();
-  fclose(f);
-  if (!ok) return 2;
+  std::vector<unsigned> vol(volume_words(dv.X, dv.Y, dv.Z));
+  if (!(in.get(poses) && in.get(vol))) return 2;
   for (unsigned j = 0; j < n_poses; ++j) {
     const float* m = &poses[(size_t)j * 16];
     float R[9], t[3];

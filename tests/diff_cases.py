@@ -5,6 +5,17 @@ import numpy as np
 import diff_twin as DT
 from fill_cases import RANDOM_DIMS, random_volume
 
+
+def words_of(raw, n, offset):
+    w = np.frombuffer(raw, np.uint32, n, offset)
+    return np.stack([(w & 0xffff).astype(np.uint16).view(np.int16), (w >> 16).astype(np.uint16).view(np.int16)], axis=-1)
+
+
+def records_as_dicts(recs):
+    return [{"root": tuple(map(int, c["root"])), "n_voxels": int(c["n_voxels"]), "n_appeared": int(c["n_appeared"]), "n_vanished": int(c["n_vanished"]),
+             "lo": tuple(map(int, c["lo"])), "hi": tuple(map(int, c["hi"]))} for c in recs]
+
+
 _CACHE = {}
 RANDOM_MIN_VOXELS = 8
 BOTH = DT.ADOPT_APPEARED | DT.ADOPT_VANISHED

@@ -16,6 +16,7 @@
 
 #include "../housescan_amd/csrc/hsk_diff_point.h"
 #include "../include/hskinfu.h"
+#include "harness_io.h"
 
 struct ClassAt {
   const std::vector<unsigned>* words;
@@ -24,24 +25,18 @@ struct ClassAt {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int h[12];
-  if (fread(h, 4, 12, f) != 12) return 2;
+  if (!in.get(h, 12)) return 2;
   const CompGrid g{(unsigned)h[0], (unsigned)h[1], (unsigned)h[2]};
   const int thresh = h[3], min_weight = h[4], which = h[6], halo = h[7], radius = h[10];
   const unsigned min_voxels = (unsigned)h[5];
   const bool ref_col = h[8] != 0, cur_col = h[9] != 0;
   const size_t n_at = (size_t)h[11];
-  // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
-  const size_t words = (size_t)g.X * g.Y * ((g.Z + 3u) & ~3u), n = (size_t)g.X * g.Y * g.Z;
+  const size_t words = volume_words(g.X, g.Y, g.Z), n = (size_t)g.X * g.Y * g.Z;
   std::vector<unsigned> ref(words), cur(words), ca(ref_col ? n : 0), cb(cur_col ? n : 0);
   std::vector<int> at(3 * n_at);
-  auto get = [&](void* p, size_t size, size_t count) { return count == 0 || fread(p, size, count, f) == count; };  // (no null pointer to fread)
-  bool ok = get(ref.data(), 4, words) && get(cur.data(), 4, words) && get(ca.data(), 4, ca.size()) && get(cb.data(), 4, cb.size());
-  ok = ok && get(at.data(), 4, at.size());
-  fclose(f);
-  if (!ok) return 2;
+  if (!(in.get(ref) && in.get(cur) && in.get(ca) && in.get(cb) && in.get(at))) return 2;
   const unsigned X = g.X, Y = g.Y, Z = g.Z;
   // the class words and the labelling's initial parents
   std::vector<unsigned> cw(words, 0u), parent(words, COMP_NONE);
@@ -149,11 +144,9 @@ int main(int argc, char** argv) {
         if (ref_col) ca[l] = cur_col ? cb[l] : 0u;
         st[2] += (ref_col && cur_col) ? 1 : 0;
       }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
+  HarnessOut o(argv[2]);
   const unsigned long long counts[2] = {n_kept, n_minor};
-  auto put = [&](const void* p, size_t size, size_t count) { return count == 0 || fwrite(p, size, count, o) == count; };
-  bool w = put(cls.data(), 1, n) && put(region.data(), 4, n) && put(counts, 8, 2) && put(recs.data(), sizeof(hsk_diff_region), recs.size());
-  w = w && put(at_cls.data(), 1, n_at) && put(at_region.data(), 4, n_at) && put(out.data(), 4, n) && put(ca.data(), 4, ca.size()) && put(st, 8, 3);
-  return fclose(o) == 0 && w ? 0 : 2;
+  o.put(cls.data(), n), o.put(region.data(), n), o.put(counts, 2), o.put(recs);
+  o.put(at_cls.data(), n_at), o.put(at_region.data(), n_at), o.put(out.data(), n), o.put(ca), o.put(st, 3);
+  return o.finish();
 }

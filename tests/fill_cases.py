@@ -3,8 +3,8 @@ parameters it is filled with, and the twin's result of each, computed once."""
 import numpy as np
 
 import fill_twin as FT
-from test_components_host import speckled
-from test_cover_host import carved_volume
+from components_cases import speckled
+from cover_cases import carved_volume
 
 _CACHE = {}
 RANDOM_DIMS = [(80, 64, 48), (80, 64, 46), (80, 64, 41), (72, 56, 40)]

@@ -12,22 +12,19 @@
 #include "../housescan_amd/csrc/hsk_comp_point.h"
 #include "../housescan_amd/csrc/hsk_fill_point.h"
 #include "../include/hskinfu.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int h[13];
-  if (fread(h, 4, 13, f) != 13) return 2;
+  if (!in.get(h, 13)) return 2;
   const CompGrid g{(unsigned)h[0], (unsigned)h[1], (unsigned)h[2]};
   const int iterations = h[3], keep = h[4], band = h[5], fill_weight = h[6];
   VoxBox box;
   for (int a = 0; a < 3; ++a) box.lo[a] = h[7 + a], box.hi[a] = h[10 + a];
-  // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
-  const size_t words = (size_t)g.X * g.Y * ((g.Z + 3u) & ~3u), n = (size_t)g.X * g.Y * g.Z;
-  std::vector<unsigned> vol(words);
-  const bool ok = fread(vol.data(), 4, words, f) == words;
-  fclose(f);
-  if (!ok) return 2;
+  const size_t n = (size_t)g.X * g.Y * g.Z;
+  std::vector<unsigned> vol(volume_words(g.X, g.Y, g.Z));
+  if (!in.get(vol)) return 2;
   const int X = (int)g.X, Y = (int)g.Y, Z = (int)g.Z;
   std::vector<short> cur(n), nxt(n);
   std::vector<unsigned char> fr(n), cross(n, 0), mask(n, 0);
@@ -99,8 +96,7 @@ int main(int argc, char** argv) {
         st[2] += 1;
         st[3] += cur[l] < 0;
       }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
-  bool w = fwrite(cur.data(), 2, n, o) == n && fwrite(mask.data(), 1, n, o) == n && fwrite(out.data(), 4, n, o) == n && fwrite(st, 8, 5, o) == 5;
-  return fclose(o) == 0 && w ? 0 : 2;
+  HarnessOut o(argv[2]);
+  o.put(cur), o.put(mask), o.put(out), o.put(st, 5);
+  return o.finish();
 }

@@ -11,9 +11,24 @@ import keytex_twin as KT
 import simplify_twin as ST
 import texture_cases as TC
 import view_twin as VT
-from test_simplify_host import BOX_DIMS, twin_of
+from simplify_cases import BOX_DIMS, twin_of
 
 f32 = np.float32
+
+
+def differing(got, tw):
+    """the differing bytes of a keyframe bake against the twin's: every output, the charts and both infos"""
+    n = 0
+    for name in ("rgb", "normal_rgb", "mask", "source"):
+        assert got[name].shape == tw[name].shape, (name, got[name].shape, tw[name].shape)
+        n += int((got[name] != tw[name]).sum())
+    n += int((np.ascontiguousarray(got["uv"]).view(np.uint32) != tw["uv"].view(np.uint32)).sum())
+    n += int((np.asarray(got["charts"]).view(np.int32).reshape(-1, 4) != tw["charts"].view(np.int32).reshape(-1, 4)).sum())
+    n += sum(a != b for a, b in zip(TC.info_list(got["info"]), TC.info_list(tw["info"])))
+    n += sum(a != b for a, b in zip(kinfo_list(got["kinfo"]), kinfo_list(tw["kinfo"])))
+    return n
+
+
 _CACHE = {}
 KW, KH, KF = 50, 38, 40.0
 INTR = np.array([KF, KF, (KW - 1) / 2.0, (KH - 1) / 2.0], f32)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_level_solve.h"
+#include "harness_io.h"
 
 struct HostStages {
   const float *X, *Y, *Z, *NX, *NY, *NZ;
@@ -87,17 +88,13 @@ struct HostStages {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 1);
   unsigned n;
   hsk_upright_params p;
   HostStages st;
-  bool ok = fread(&n, 4, 1, f) == 1 && fread(&p, sizeof(p), 1, f) == 1 && fread(st.w, 4, 3, f) == 3;
-  if (!ok) return 2;
+  if (!(in.get(&n, 1) && in.get(&p, 1) && in.get(st.w, 3))) return 2;
   std::vector<float> soa((size_t)n * 6);
-  ok = fread(soa.data(), 4, soa.size(), f) == soa.size();
-  fclose(f);
-  if (!ok) return 2;
+  if (!in.get(soa)) return 2;
   st.n = n;
   st.X = soa.data(), st.Y = st.X + n, st.Z = st.Y + n, st.NX = st.Z + n, st.NY = st.NX + n, st.NZ = st.NY + n;
   st.cone2 = (double)p.cone_cos * (double)p.cone_cos;

@@ -3,6 +3,7 @@ the normal and colour rules of hsk_extract_cloud_attrs, from a downloaded volume
 (oracle.mc_table()).  Whole volumes: every plane stored and owned."""
 import numpy as np
 
+from kit import same_bits
 from np_twin import _Grid, _vox
 
 f32 = np.float32
@@ -102,12 +103,6 @@ def normal_at(G, xyz, dims):
     for i in range(3):
         nrm[deep, i] = (n[i] * ninv)[deep]
     return nrm
-
-
-def same_bits(a, b):
-    """bit-for-bit equality of float32 arrays"""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def same_normals(a, b):

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_part_point.h"
+#include "harness_io.h"
 
 struct Tile {  // (exactly the cells of a tile and its halo: an access past them is the sanitizer's to find)
   std::vector<part_key> cells = std::vector<part_key>(REACH_HALO_CELLS);
@@ -33,22 +34,18 @@ struct Store {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int dims[3];
   unsigned par[10];
-  if (fread(dims, 4, 3, f) != 3 || fread(par, 4, 10, f) != 10) return 2;
+  if (!(in.get(dims, 3) && in.get(par, 10))) return 2;
   const unsigned n_points = par[9];
   std::vector<unsigned> points(n_points);
-  if (n_points && fread(points.data(), 4, n_points, f) != n_points) return 2;
   const unsigned X = (unsigned)dims[0], Y = (unsigned)dims[1], Z = (unsigned)dims[2];
   const unsigned w[3] = {par[0], par[1], par[2]}, core_d2 = par[3], min_d2 = par[4], min_core = par[5], max_cost = par[6], order = par[7];
   const int radius = (int)par[8];
   const size_t n = (size_t)X * Y * Z;
   std::vector<unsigned> d2(n);
-  const bool ok = fread(d2.data(), 4, n, f) == n;
-  fclose(f);
-  if (!ok || max_cost > REACH_MAX_COST || radius > PART_MAX_RADIUS || !(1u <= min_d2 && min_d2 <= core_d2)) return 2;
+  if (!(in.get(points) && in.get(d2)) || max_cost > REACH_MAX_COST || radius > PART_MAX_RADIUS || !(1u <= min_d2 && min_d2 <= core_d2)) return 2;
   unsigned cost[REACH_MOVES];
   reach_cost_table(w, cost);
   unsigned long long counts[6] = {0, 0, 0, 0, 0, 0};
@@ -76,9 +73,8 @@ int main(int argc, char** argv) {
       if (size[i] >= min_core) roots.push_back((unsigned)i);  // (ascending)
     }
   counts[1] = roots.size();
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
-  if (roots.size() > (size_t)PART_MAX_ROOMS) return fwrite(counts, 8, 6, o) == 6 && fclose(o) == 0 ? 0 : 2;
+  HarnessOut o(argv[2]);
+  if (roots.size() > (size_t)PART_MAX_ROOMS) return o.put(counts, 6), o.finish();
   // the tiles, their flags and worklists; init
   const unsigned ntx = (X + REACH_TILE_X - 1u) / REACH_TILE_X, nty = (Y + REACH_TILE_Y - 1u) / REACH_TILE_Y, ntz = (Z + REACH_TILE_Z - 1u) / REACH_TILE_Z;
   const size_t tiles = (size_t)ntx * nty * ntz;
@@ -139,12 +135,12 @@ int main(int argc, char** argv) {
     counts[3] += 1;
     cur ^= 1;
   }
-  bool wr = fwrite(counts, 8, 6, o) == 6 && fwrite(key.data(), 8, n, o) == n && (roots.empty() || fwrite(roots.data(), 4, roots.size(), o) == roots.size());
+  o.put(counts, 6), o.put(key.data(), n), o.put(roots);
   const Load ld{&key};
   for (unsigned v : points) {
     if (v >= n) return 4;
     const part_key found = part_nearest(ld, X, Y, Z, v % X, (v / X) % Y, v / (X * Y), radius, w);
-    wr = wr && fwrite(&found, 8, 1, o) == 1;
+    o.put(&found, 1);
   }
-  return fclose(o) == 0 && wr ? 0 : 2;
+  return o.finish();
 }

@@ -7,20 +7,16 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_plane_point.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 1);
   unsigned n, n_planes;
   float dist_m, cos_min;
-  bool ok = fread(&n, 4, 1, f) == 1 && fread(&n_planes, 4, 1, f) == 1 && fread(&dist_m, 4, 1, f) == 1 && fread(&cos_min, 4, 1, f) == 1;
-  if (!ok) return 2;
+  if (!(in.get(&n, 1) && in.get(&n_planes, 1) && in.get(&dist_m, 1) && in.get(&cos_min, 1))) return 2;
   std::vector<float> planes((size_t)n_planes * 4), soa((size_t)n * 6);
   std::vector<int> labels(n);
-  ok = fread(planes.data(), 4, planes.size(), f) == planes.size() && fread(soa.data(), 4, soa.size(), f) == soa.size() &&
-       fread(labels.data(), 4, labels.size(), f) == labels.size();
-  fclose(f);
-  if (!ok) return 2;
+  if (!(in.get(planes) && in.get(soa) && in.get(labels))) return 2;
   const float *X = soa.data(), *Y = X + n, *Z = Y + n, *NX = Z + n, *NY = NX + n, *NZ = NY + n;
   unsigned long long n_valid = 0;
   for (unsigned i = 0; i < n; ++i) n_valid += plane_point_valid(X[i], Y[i], Z[i], NX[i], NY[i], NZ[i]) ? 1 : 0;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_reach_point.h"
+#include "harness_io.h"
 
 struct Tile {  // (exactly the cells of a tile and its halo: an access past them is the sanitizer's to find)
   std::vector<unsigned> cells = std::vector<unsigned>(REACH_HALO_CELLS), mv = std::vector<unsigned>(REACH_TILE_VOXELS);
@@ -29,23 +30,18 @@ struct Store {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int dims[3];
   unsigned par[6], n_seeds, n_goals;
-  if (fread(dims, 4, 3, f) != 3 || fread(par, 4, 6, f) != 6 || fread(&n_seeds, 4, 1, f) != 1) return 2;
+  if (!(in.get(dims, 3) && in.get(par, 6) && in.get(&n_seeds, 1))) return 2;
   std::vector<unsigned> seeds(n_seeds);
-  if (n_seeds && fread(seeds.data(), 4, n_seeds, f) != n_seeds) return 2;
-  if (fread(&n_goals, 4, 1, f) != 1) return 2;
+  if (!(in.get(seeds) && in.get(&n_goals, 1))) return 2;
   std::vector<unsigned> goals(n_goals);
-  if (n_goals && fread(goals.data(), 4, n_goals, f) != n_goals) return 2;
   const unsigned X = (unsigned)dims[0], Y = (unsigned)dims[1], Z = (unsigned)dims[2];
   const unsigned w[3] = {par[0], par[1], par[2]}, min_d2 = par[3], max_cost = par[4], order = par[5];
   const size_t n = (size_t)X * Y * Z;
   std::vector<unsigned> d2(n);
-  const bool ok = fread(d2.data(), 4, n, f) == n;
-  fclose(f);
-  if (!ok || n_seeds > REACH_MAX_SEEDS || max_cost > REACH_MAX_COST) return 2;
+  if (!(in.get(goals) && in.get(d2)) || n_seeds > REACH_MAX_SEEDS || max_cost > REACH_MAX_COST) return 2;
   unsigned cost[REACH_MOVES];
   reach_cost_table(w, cost);
   unsigned long long counts[6] = {0, 0, 0, 0, 0, 0};
@@ -124,9 +120,8 @@ int main(int argc, char** argv) {
       counts[1] += 1;
       if (g[i] > counts[2]) counts[2] = g[i];
     }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
-  bool wr = fwrite(g.data(), 4, n, o) == n && fwrite(counts, 8, 6, o) == 6;
+  HarnessOut o(argv[2]);
+  o.put(g.data(), n), o.put(counts, 6);
   // the paths
   const Load ld{&g};
   for (unsigned goal : goals) {
@@ -144,8 +139,8 @@ int main(int argc, char** argv) {
         gv -= cost[m];
       }
     const unsigned len = (unsigned)(back.size() / 3);
-    wr = wr && fwrite(&len, 4, 1, o) == 1;
-    for (unsigned i = len; i > 0; --i) wr = wr && fwrite(&back[3 * (size_t)(i - 1)], 4, 3, o) == 3;
+    o.put(&len, 1);
+    for (unsigned i = len; i > 0; --i) o.put(&back[3 * (size_t)(i - 1)], 3);
   }
-  return fclose(o) == 0 && wr ? 0 : 2;
+  return o.finish();
 }

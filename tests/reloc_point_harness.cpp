@@ -7,15 +7,14 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_reloc_point.h"
+#include "harness_io.h"
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 1 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 1);
   int dims[3];
   float size[3];
   unsigned n_poses, n;
-  bool ok = fread(dims, 4, 3, f) == 3 && fread(size, 4, 3, f) == 3 && fread(&n_poses, 4, 1, f) == 1 && fread(&n, 4, 1, f) == 1;
-  if (!ok) return 2;
+  if (!(in.get(dims, 3) && in.get(size, 3) && in.get(&n_poses, 1) && in.get(&n, 1))) return 2;
   SampleVol dv;
   dv.X = dims[0];
   dv.Y = dims[1];
@@ -25,11 +24,8 @@ int main(int argc, char** argv) {
     dv.icell[i] = 1.0 / (double)dv.cell[i];
   }
   std::vector<float> poses((size_t)n_poses * 16), soa((size_t)n * 3);
-  std::vector<unsigned> vol((size_t)dv.X * dv.Y * ((dv.Z + 3) & ~3));
-  ok = fread(poses.data(), 4, poses.size(), f) == poses.size() && fread(vol.data(), 4, vol.size(), f) == vol.size() &&
-       fread(soa.data(), 4, soa.size(), f) == soa.size();
-  fclose(f);
-  if (!ok) return 2;
+  std::vector<unsigned> vol(volume_words(dv.X, dv.Y, dv.Z));
+  if (!(in.get(poses) && in.get(vol) && in.get(soa))) return 2;
   for (unsigned j = 0; j < n_poses; ++j) {
     const float* m = &poses[(size_t)j * 16];
     float R[9], t[3];

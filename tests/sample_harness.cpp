@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../housescan_amd/csrc/hsk_sample.h"
+#include "harness_io.h"
 
 static int bits(float f) {
   int i;
@@ -17,12 +18,11 @@ static int bits(float f) {
 }
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int dims[3];
   float size[3];
   unsigned n;
-  if (!(fread(dims, 4, 3, f) == 3 && fread(size, 4, 3, f) == 3 && fread(&n, 4, 1, f) == 1)) return 2;
+  if (!(in.get(dims, 3) && in.get(size, 3) && in.get(&n, 1))) return 2;
   SampleVol v;
   v.X = dims[0];
   v.Y = dims[1];
@@ -31,11 +31,9 @@ int main(int argc, char** argv) {
     v.cell[i] = size[i] / (float)dims[i];
     v.icell[i] = 1.0 / (double)v.cell[i];
   }
-  std::vector<unsigned> vol((size_t)v.X * v.Y * ((v.Z + 3) & ~3));
+  std::vector<unsigned> vol(volume_words(v.X, v.Y, v.Z));
   std::vector<float> p((size_t)n * 3);
-  const bool ok = fread(vol.data(), 4, vol.size(), f) == vol.size() && fread(p.data(), 4, p.size(), f) == p.size();
-  fclose(f);
-  if (!ok) return 2;
+  if (!(in.get(vol) && in.get(p))) return 2;
   std::vector<int> out((size_t)n * 15);
   for (unsigned i = 0; i < n; ++i) {
     const float px = p[i], py = p[n + i], pz = p[2 * (size_t)n + i];
@@ -54,8 +52,7 @@ int main(int argc, char** argv) {
     o[9] = bits(gx), o[10] = bits(gy), o[11] = bits(gz);
     hsk_voxel_at(v, px, py, pz, o[12], o[13], o[14]);
   }
-  f = fopen(argv[2], "wb");
-  if (!f || fwrite(out.data(), 4, out.size(), f) != out.size()) return 2;
-  fclose(f);
-  return 0;
+  HarnessOut o(argv[2]);
+  o.put(out);
+  return o.finish();
 }

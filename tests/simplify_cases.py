@@ -6,8 +6,153 @@ on an input that misses the code it is there for."""
 import numpy as np
 
 import simplify_twin as ST
-from mesh_twin import mesh_indexed
-from test_simplify_host import grid, volume_of
+from kit import same_bits
+from mesh_twin import mesh_indexed, same_normals
+
+CLUSTERS = (2, 4, 8, 16)
+MODES = (ST.QUADRIC, ST.MEAN)
+BOX_DIMS, BOX_SIZE = (72, 40, 24), (2.7, 1.6, 1.2)      # X crosses the indexed mesh's 64-voxel segment; no dim a multiple of 16
+SMALL_DIMS, SMALL_SIZE = (32, 24, 12), (3.0, 3.0, 3.0)  # (anisotropic cells)
+_CACHE = {}
+
+
+def grid(dims):
+    X, Y, Z = dims
+    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
+    return x.astype(np.float64), y.astype(np.float64), z.astype(np.float64)
+
+
+def volume_of(dist_voxels, tau=3.0, weight=3):
+    """a signed distance in voxels (positive: free space) -> [Z, Y, X, 2] int16 (tsdf, weight), every weight non-zero"""
+    t = np.clip(np.rint(dist_voxels / tau * 32767.0), -32767, 32767).astype(np.int16)
+    return np.stack([t, np.full(t.shape, weight, np.int16)], axis=-1)
+
+
+def box_distance(dims, lo, hi):
+    """the free inside of an axis-aligned box room: the distance to the nearest wall, negative in the walls"""
+    x, y, z = grid(dims)
+    return np.minimum.reduce([x - lo[0], hi[0] - x, y - lo[1], hi[1] - y, z - lo[2], hi[2] - z])
+
+
+def box_volume():
+    return volume_of(box_distance(BOX_DIMS, (5.3, 4.7, 3.4), (66.6, 35.2, 20.3)))
+
+
+def sphere_volume():
+    x, y, z = grid((32, 32, 32))
+    return volume_of(np.sqrt((x - 15.3) ** 2 + (y - 16.1) ** 2 + (z - 15.7) ** 2) - 9.4)
+
+
+def two_walls_volume():
+    """free space, one plane of solid voxels at x = 11, free space again: two parallel surfaces one voxel apart"""
+    x, y, z = grid(SMALL_DIMS)
+    t = np.where(x == 11, -6000.0 - 41.0 * y - 13.0 * z, 8000.0 + 37.0 * y + 11.0 * z)
+    return np.stack([t.astype(np.int16), np.full(t.shape, 2, np.int16)], axis=-1)
+
+
+def holes_volume():
+    v = box_volume()
+    rng = np.random.default_rng(1905)
+    v[rng.random(v.shape[:3]) < 0.1, 1] = 0
+    return v
+
+
+def exact_zeros_volume():
+    """stored TSDF exactly 0 on the grid planes x = 12 and x = 20: edges with the ratio exactly 1 (-4000 -> 0) and exactly 0 (0 -> -4000)"""
+    x, _, _ = grid(SMALL_DIMS)
+    t = np.minimum(x - 12.0, 20.0 - x) * 4000.0
+    v = np.stack([t.astype(np.int16), np.full(t.shape, 1, np.int16)], axis=-1)
+    assert (v[..., 0] == 0).sum() == 2 * 24 * 12
+    return v
+
+
+def six_faces_volume():
+    """a tilted plane that meets all six faces of the volume"""
+    x, y, z = grid(SMALL_DIMS)
+    return volume_of((x / 31.0 + y / 23.0 + z / 11.0 - 1.5) * 9.0)
+
+
+def blob_volume():
+    """one solid voxel at (5, 5, 5): the lower corners of its six cut edges are 4 or 5 on every axis -- one cluster at every size"""
+    v = volume_of(np.full(SMALL_DIMS[::-1], 2.0))
+    v[5, 5, 5, 0] = -9000
+    return v
+
+
+def empty_volume():
+    return np.zeros(SMALL_DIMS[::-1] + (2,), np.int16)
+
+
+def box_colour():
+    rng = np.random.default_rng(77)
+    X, Y, Z = BOX_DIMS
+    col = rng.integers(0, 256, (Z, Y, X, 4), dtype=np.uint8)
+    col[..., 3] = np.where(rng.random((Z, Y, X)) < 0.45, 0, 5)
+    col[:, :, :14, 3] = 0                                  # (no colour at all near the wall x = 5.3: uncoloured clusters)
+    return col
+
+
+def small_cases():
+    """{name: (volume, dims, size, colour or None)}: the GPU list's uploaded volumes"""
+    if "cases" not in _CACHE:
+        _CACHE["cases"] = {
+            "box": (box_volume(), BOX_DIMS, BOX_SIZE, None),
+            "sphere": (sphere_volume(), (32, 32, 32), (3.0, 3.0, 3.0), None),
+            "two walls": (two_walls_volume(), SMALL_DIMS, SMALL_SIZE, None),
+            "holes": (holes_volume(), BOX_DIMS, BOX_SIZE, None),
+            "exact zeros": (exact_zeros_volume(), SMALL_DIMS, SMALL_SIZE, None),
+            "six faces": (six_faces_volume(), SMALL_DIMS, SMALL_SIZE, None),
+            "blob": (blob_volume(), SMALL_DIMS, SMALL_SIZE, None),
+            "empty": (empty_volume(), SMALL_DIMS, SMALL_SIZE, None),
+            "box with colour": (box_volume(), BOX_DIMS, BOX_SIZE, box_colour()),
+        }
+    return _CACHE["cases"]
+
+
+def case_of(name):
+    """a small case or a shape case by its name (the two lists share no name)"""
+    return small_cases()[name] if name in small_cases() else shape_cases()[name]
+
+
+def mesh_of(oracle, name):
+    """the indexed mesh of a case, made once"""
+    if ("mesh", name) not in _CACHE:
+        vol, _, size, col = case_of(name)
+        _CACHE[("mesh", name)] = mesh_indexed(vol, *oracle.mc_table(), size=size, col=col, normals=False)
+    return _CACHE[("mesh", name)]
+
+
+def twin_of(oracle, name, c, mode):
+    """the twin's result for a case, made once and left unchanged"""
+    key = ("twin", name, c, mode)
+    if key not in _CACHE:
+        vol, _, size, col = case_of(name)
+        _CACHE[key] = ST.simplify(vol, *oracle.mc_table(), c=c, mode=mode, size=size, col=col, mesh=mesh_of(oracle, name))
+    return _CACHE[key]
+
+
+def directed_edge_balance(faces):
+    """the largest |count(a, b) - count(b, a)| over the directed edges of a face list (0: closed)"""
+    f = np.asarray(faces, np.int64)
+    if not len(f):
+        return 0
+    a = np.concatenate([f[:, 0], f[:, 1], f[:, 2]])
+    b = np.concatenate([f[:, 1], f[:, 2], f[:, 0]])
+    n = int(f.max()) + 1
+    fwd, nf = np.unique(a * n + b, return_counts=True)
+    bwd, nb = np.unique(b * n + a, return_counts=True)
+    return 0 if (np.array_equal(fwd, bwd) and np.array_equal(nf, nb)) else 1 + int(np.setxor1d(fwd, bwd).size)
+
+
+def signed_volume(vertices, faces):
+    v = np.asarray(vertices, np.float64)[np.asarray(faces, np.int64)]
+    return float(np.einsum("ij,ij->i", v[:, 0], np.cross(v[:, 1], v[:, 2])).sum() / 6.0)
+
+
+def stats_list(st):
+    return [st["n_in_vertices"], st["n_in_faces"], st["n_clusters"], st["n_out_vertices"], st["n_out_faces"], st["n_faces_collapsed"]] + st["n_rank"] + \
+        [st["n_clamped"], st["n_uncolored"]]
+
 
 HALL_DIMS, HALL_SIZE = (1032, 24, 21), (6.45, 0.3, 0.21)      # CX = 516, 258, 129, 65 at c = 2, 4, 8, 16: 9, 5, 3, 2 segments
 TALL_DIMS, TALL_SIZE = (24, 72, 61), (0.6, 1.2, 1.5)          # 36 x 31 = 1116 cluster rows at c = 2: a second scan block
@@ -20,7 +165,6 @@ WIDE_FRAMES = 4
 # three straddle cx = 63 | 64 (x = 127 | 128, 255 | 256, 511 | 512); in clusters of 16 the end wall (x = 1026.6) and the floor do
 HALL_WALLS = ((126.4, 130.7), (253.5, 258.2), (509.3, 515.6), (700.2, 703.9))
 HALL_FLIP = (10, 11, 126)                                     # (z, y, x): the free voxel 0.4 in front of the first wall
-_CACHE = {}
 
 
 def room_distance(dims):
@@ -71,32 +215,15 @@ def tall_volume():
 
 def shape_cases():
     """{name: (volume, dims, size, colour or None)}: the uploaded volumes, made once"""
-    if "cases" not in _CACHE:
-        _CACHE["cases"] = {
+    if "shapes" not in _CACHE:
+        _CACHE["shapes"] = {
             "hall": (hall_volume(), HALL_DIMS, HALL_SIZE, hall_colour()),
             "tall": (tall_volume(), TALL_DIMS, TALL_SIZE, None),
         }
-        _CACHE["cases"]["hall flipped"] = (hall_flipped(), HALL_DIMS, HALL_SIZE, _CACHE["cases"]["hall"][3])
-        for vol, _, _, _ in _CACHE["cases"].values():
+        _CACHE["shapes"]["hall flipped"] = (hall_flipped(), HALL_DIMS, HALL_SIZE, _CACHE["shapes"]["hall"][3])
+        for vol, _, _, _ in _CACHE["shapes"].values():
             vol.setflags(write=False)
-    return _CACHE["cases"]
-
-
-def mesh_of(oracle, name):
-    """the indexed mesh of a case, made once"""
-    if ("mesh", name) not in _CACHE:
-        vol, _, size, col = shape_cases()[name]
-        _CACHE[("mesh", name)] = mesh_indexed(vol, *oracle.mc_table(), size=size, col=col, normals=False)
-    return _CACHE[("mesh", name)]
-
-
-def twin_of(oracle, name, c, mode):
-    """the twin's result for a case, made once and left unchanged"""
-    key = ("twin", name, c, mode)
-    if key not in _CACHE:
-        vol, _, size, col = shape_cases()[name]
-        _CACHE[key] = ST.simplify(vol, *oracle.mc_table(), c=c, mode=mode, size=size, col=col, mesh=mesh_of(oracle, name))
-    return _CACHE[key]
+    return _CACHE["shapes"]
 
 
 def wide_frames(synth_frames):
@@ -186,3 +313,20 @@ def census(vol, mesh, tw, c):
     out["trip_rows"] = int((three & (~held & left & right).any(axis=1)).sum())
     out["trip_rows_skipped"] = int((three & (~held & clear & left & right).any(axis=1)).sum())
     return out
+
+
+def check(trk, tw, c, mode, rgb=False, tag=""):
+    """one call of the context against a twin result: every array and every statistic"""
+    v, f, nrm, col, st = trk.extract_mesh_simplified(cluster_voxels=c, mode=mode, normals=True, rgb=rgb)
+    tag = (tag, c, mode)
+    assert same_bits(v, tw["vertices"]), (tag, len(v), len(tw["vertices"]))
+    assert same_normals(nrm, tw["normals"]), tag
+    assert f.shape == tw["faces"].shape and np.array_equal(f, tw["faces"]), tag
+    want = dict(tw["stats"])
+    if rgb:
+        assert np.array_equal(col, tw["rgb"]), tag
+    else:
+        assert col is None
+        want["n_uncolored"] = 0
+    assert stats_list(st) == stats_list(want), (tag, st, want)
+    return v, f, st

@@ -7,6 +7,13 @@ import split_twin as ST
 from diff_cases import sl
 from fill_cases import RANDOM_DIMS, random_volume
 
+FIELDS = ("root", "n_voxels", "sum", "lo", "hi", "contact", "plane_mask", "height_lo", "height_hi")
+
+
+def records_as_dicts(recs):
+    return [{n: (int(c[n]) if np.ndim(c[n]) == 0 else tuple(int(v) for v in c[n])) for n in FIELDS} for c in recs]
+
+
 _CACHE = {}
 CELL = 0.05                       # the hand-built grids' cell; the truncation distance is then 2.1 cells
 RANDOM_CELL = 0.0375

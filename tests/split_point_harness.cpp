@@ -18,6 +18,7 @@
 
 #include "../housescan_amd/csrc/hsk_split_point.h"
 #include "../include/hskinfu.h"
+#include "harness_io.h"
 
 struct WordAt {
   const std::vector<unsigned>* words;
@@ -26,12 +27,11 @@ struct WordAt {
 };
 
 int main(int argc, char** argv) {
-  FILE* f = argc > 2 ? fopen(argv[1], "rb") : nullptr;
-  if (!f) return 2;
+  HarnessIn in(argc, argv, 2);
   int h[12];
   long long r7[7];
   double cos2;
-  if (fread(h, 4, 12, f) != 12 || fread(r7, 8, 7, f) != 7 || fread(&cos2, 8, 1, f) != 1) return 2;
+  if (!(in.get(h, 12) && in.get(r7, 7) && in.get(&cos2, 1))) return 2;
   const CompGrid g{(unsigned)h[0], (unsigned)h[1], (unsigned)h[2]};
   const int n_planes = h[3], mode = h[5], halo = h[6], fill_weight = h[7], radius = h[9];
   const unsigned min_voxels = (unsigned)h[4];
@@ -49,20 +49,16 @@ int main(int argc, char** argv) {
   std::vector<SplitPlaneQ> planes((size_t)n_planes);
   for (int k = 0; k < n_planes; ++k) {
     long long p8[8];
-    if (fread(p8, 8, 8, f) != 8) return 2;
+    if (!in.get(p8, 8)) return 2;
     SplitPlaneQ& p = planes[(size_t)k];
     for (int j = 0; j < 3; ++j) p.Q[j] = p8[j], p.N[j] = (int)p8[4 + j];
     p.Qd = p8[3];
     p.kind = (int)p8[7];
   }
-  // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
-  const size_t words = (size_t)g.X * g.Y * ((g.Z + 3u) & ~3u), n = (size_t)g.X * g.Y * g.Z;
+  const size_t words = volume_words(g.X, g.Y, g.Z), n = (size_t)g.X * g.Y * g.Z;
   std::vector<unsigned> vol(words), col(has_col ? n : 0), roots_in(n_roots_in > 0 ? (size_t)n_roots_in : 0);
   std::vector<int> at(3 * n_at);
-  auto get = [&](void* p, size_t size, size_t count) { return count == 0 || fread(p, size, count, f) == count; };  // (no null pointer to fread)
-  const bool ok = get(vol.data(), 4, words) && get(col.data(), 4, col.size()) && get(at.data(), 4, at.size()) && get(roots_in.data(), 4, roots_in.size());
-  fclose(f);
-  if (!ok) return 2;
+  if (!(in.get(vol) && in.get(col) && in.get(at) && in.get(roots_in))) return 2;
   const unsigned X = g.X, Y = g.Y, Z = g.Z;
   const WordAt vol_at{&vol, g};
   // the class words and the labelling's initial parents
@@ -235,12 +231,9 @@ int main(int argc, char** argv) {
         if (has_col) col[l] = 0u;
         st[4] += has_col ? 1 : 0;
       }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 2;
+  HarnessOut o(argv[2]);
   const unsigned long long counts[4] = {recs.size(), n_minor, n_edge, n_flat};
-  auto put = [&](const void* p, size_t size, size_t count) { return count == 0 || fwrite(p, size, count, o) == count; };
-  bool w = put(cls.data(), 1, n) && put(pln.data(), 1, n) && put(label.data(), 4, n) && put(counts, 8, 4) && put(recs.data(), sizeof(hsk_object), recs.size());
-  w = w && put(at_cls.data(), 1, n_at) && put(at_pln.data(), 1, n_at) && put(at_obj.data(), 4, n_at) && put(out.data(), 4, n) && put(col.data(), 4, col.size()) &&
-      put(st, 8, 5);
-  return fclose(o) == 0 && w ? 0 : 2;
+  o.put(cls.data(), n), o.put(pln.data(), n), o.put(label.data(), n), o.put(counts, 4), o.put(recs);
+  o.put(at_cls.data(), n_at), o.put(at_pln.data(), n_at), o.put(at_obj.data(), n_at), o.put(out.data(), n), o.put(col), o.put(st, 5);
+  return o.finish();
 }

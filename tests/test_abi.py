@@ -1,5 +1,5 @@
-"""The C-ABI library loads without a GPU and exports every symbol include/hskinfu.h declares; the ctypes
-mirror of hsk_config has the C layout; without a HIP device the product fails loudly (no CPU fallback)."""
+"""The C-ABI library loads without a GPU and exports every symbol include/hskinfu.h declares; every ctypes
+mirror and every integer constant of housescan_amd/_lib.py has the C layout and the C value; without a HIP device the product fails loudly (no CPU fallback)."""
 import ctypes as C
 import os
 import re
@@ -8,7 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT, c_values
+
 HEADER = os.path.join(ROOT, "include", "hskinfu.h")
 
 
@@ -52,19 +53,83 @@ def test_house_header_is_plain_c(tmp_path):
                            str(src), "-o", str(tmp_path / "c.o")])
 
 
-def test_config_struct_layout_matches_c(tmp_path, hsk):
+# ---- the whole ABI's layout, generated from the mirrors ------------------------------------------------------------------------
+# typedefs of the header without a body: handles, which have no layout to mirror
+OPAQUE = {"hsk_ctx", "hsk_group", "hsk_depth_stream"}
+# structs of the header that have a body and, on purpose, no mirror in _lib.py: {C name: reason}
+NO_MIRROR = {}
+MIN_STRUCTS, MIN_CONSTANTS = 50, 106            # the counts when this test was written: floors, to be raised when the tree grows
+
+
+def header_structs():
+    """(the names of the header's typedef'd structs that have a body, those that have none)"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    bodied, opaque = set(), set()
+    for m in re.finditer(r"\btypedef\s+struct\b\s*(\w*)\s*([{;\w])", src):
+        if m[2] != "{":
+            opaque.add(re.match(r"\w+", src[m.start(2):])[0])
+            continue
+        depth, k = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(src[k], 0)
+            k += 1
+        bodied.add(re.match(r"\s*(\w+)\s*;", src[k:])[1])
+    return bodied, opaque
+
+
+def c_name(cls):
+    """HskFillParams -> hsk_fill_params"""
+    return re.sub(r"(?<!^)(?=[A-Z])", "_", cls.__name__).lower()
+
+
+def mirror_members(cls, path="", base=0):
+    """[(member path as C writes it, offset from the outermost struct, size)] of every field, nested structs entered"""
+    out = []
+    for name, typ, *bits in cls._fields_:
+        assert not bits, f"{cls.__name__}.{name}: a bit field has no offsetof"
+        f = getattr(cls, name)
+        out.append((path + name, base + f.offset, f.size))
+        if isinstance(typ, type) and issubclass(typ, C.Structure):
+            out += mirror_members(typ, path + name + ".", base + f.offset)
+    return out
+
+
+def test_every_struct_mirror_has_the_c_layout(tmp_path):
+    """sizeof of every ctypes.Structure of _lib.py, and offsetof and sizeof of every field, against a C99 program generated from the
+    mirrors and compiled against the header; every struct of the header has a mirror, every mirror a struct of the header"""
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(){printf("%zu %zu %zu %zu\\n", '
-                   'sizeof(hsk_config), offsetof(hsk_config, init_pose), offsetof(hsk_config, own_z0), '
-                   'offsetof(hsk_config, use_graph));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    size, off_pose, off_own, off_graph = map(int, subprocess.check_output([str(exe)], text=True).split())
-    assert size == C.sizeof(_lib.HskConfig)
-    assert off_pose == _lib.HskConfig.init_pose.offset
-    assert off_own == _lib.HskConfig.own_z0.offset
-    assert off_graph == _lib.HskConfig.use_graph.offset
+    mirrors = {c_name(v): v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    bodied, opaque = header_structs()
+    assert opaque == OPAQUE, opaque ^ OPAQUE
+    assert not set(mirrors) - bodied, f"mirrors without a struct in include/hskinfu.h: {sorted(set(mirrors) - bodied)}"
+    assert bodied - set(mirrors) == set(NO_MIRROR), f"header structs without a mirror in _lib.py: {sorted(bodied - set(mirrors) - set(NO_MIRROR))}"
+    what, expressions, want = [], [], []
+    for name, cls in sorted(mirrors.items()):
+        what.append(f"sizeof({name})")
+        expressions.append(f"sizeof({name})")
+        want.append(C.sizeof(cls))
+        for member, offset, size in mirror_members(cls):
+            what += [f"{name}.{member}: offset", f"{name}.{member}: size"]
+            expressions += [f"offsetof({name}, {member})", f"sizeof((({name}*)0)->{member})"]
+            want += [offset, size]
+    got = c_values(tmp_path, expressions)
+    wrong = [f"{w}: C {g} != ctypes {e}" for w, g, e in zip(what, got, want) if g != e]
+    print(f"{len(mirrors)} structs, {(len(want) - len(mirrors)) // 2} fields, {len(want)} numbers")
+    assert len(got) == len(want) and not wrong, "\n".join(wrong)
+    assert len(mirrors) >= MIN_STRUCTS, len(mirrors)
+
+
+def test_every_integer_constant_has_the_c_value(tmp_path):
+    from housescan_amd import _lib
+    constants = {k: v for k, v in vars(_lib).items() if k.startswith("HSK_") and isinstance(v, int) and not isinstance(v, bool)}
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    missing = [k for k in constants if not re.search(rf"\b{k}\b", src)]
+    assert not missing, f"constants of _lib.py that include/hskinfu.h does not name: {missing}"
+    got = c_values(tmp_path, sorted(constants))
+    wrong = [f"{k}: C {g} != _lib.py {constants[k]}" for k, g in zip(sorted(constants), got) if g != constants[k]]
+    print(f"{len(constants)} constants")
+    assert len(got) == len(constants) and not wrong, "\n".join(wrong)
+    assert len(constants) >= MIN_CONSTANTS, len(constants)
 
 
 def test_header_is_plain_c(tmp_path):

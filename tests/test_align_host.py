@@ -3,31 +3,16 @@ properties DESIGN.md 8f claims for the rule, shown on the twin with the analytic
 floor, as an 80 x 64 x 48 volume over 3 m: three different cells); the header, the C layout of the new structs and their Python
 mirror."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
-import np_twin as T
+import kit
+from align_cases import HALF_CELL_M, M_TRUE, PERTURBED, TAU, _CACHE, scene
+from kit import blocked, same_bits
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TAU = T.tau_of(AT.DST_SIZE, AT.DST_DIMS, 0.03)
-HALF_CELL_M = 0.5 * 3.0 / 80          # half the smallest destination cell: 18.75 mm
-M_TRUE = AT.rigid(2.5, (40.0, -30.0, 20.0))
-PERTURBED = (AT.rigid(2.0, (150.0, -100.0, 120.0)) @ M_TRUE).astype(f32)
-
-_CACHE = {}
-
-
-def scene():
-    """(destination volume, source points, source normals), made once"""
-    if "scene" not in _CACHE:
-        ps, ns = AT.source_cloud(M_TRUE)
-        _CACHE["scene"] = (AT.scene_volume(AT.DST_DIMS, AT.DST_SIZE, TAU), ps, ns)
-    return _CACHE["scene"]
 
 
 def run(name, M0, **kw):
@@ -36,11 +21,6 @@ def run(name, M0, **kw):
         vol, ps, ns = scene()
         _CACHE[name] = AT.align(vol, AT.DST_SIZE, TAU, ps, ns, M0, **kw)
     return _CACHE[name]
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def test_the_scene_is_the_one_the_rule_was_tried_on():
@@ -161,25 +141,12 @@ def test_nan_normals_never_contribute_and_the_subsample_is_every_stride_th_point
 
 
 # ---- 2b. the kernel's work on one point, compiled for the host ------------------------------------------------------
-def blocked(vol):
-    """a host volume [Z, Y, X, 2] as the device stores it: 64-B blocks of 4 x-adjacent voxels by 4 planes, the
-    pair (tsdf, weight) in one 32-bit word"""
-    Z, Y, X, _ = vol.shape
-    out = np.zeros(X * Y * ((Z + 3) & ~3), np.uint32)
-    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
-    idx = ((((z >> 2) * Y + y) * (X // 4) + (x >> 2)) * 16) + (z & 3) * 4 + (x & 3)
-    out[idx.reshape(-1)] = ((vol[..., 0].astype(np.int64) & 0xffff) | ((vol[..., 1].astype(np.int64) & 0xffff) << 16)).reshape(-1)
-    return out
-
-
 def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
     """housescan_amd/csrc/hsk_align_point.h -- the text every lane of k_align_iter runs -- built for the host with the address and
     undefined-behaviour sanitizers (their runtime linked into the program): the 28 sums (as integers in units of 2^-26) and
     n_used against the twin, zero differences; points that are NaN, infinite or kilometres away gather inside the volume like
     any other"""
-    exe = tmp_path / "align_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "align_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("align_point", tmp_path)
     vol, ps, ns = scene()
     words = blocked(vol)
     rng = np.random.default_rng(1)
@@ -198,7 +165,7 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
             for part in (np.array(AT.DST_DIMS, np.int32), np.array(AT.DST_SIZE, f32), np.asarray(M, f32), f32(TAU), f32(gate), np.int32(J),
                          np.uint32(len(p)), words, np.ascontiguousarray(np.concatenate([p.T, n.T]), f32)):
                 f.write(part.tobytes())
-        out = subprocess.check_output([str(exe), str(path)], text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0")).split()
+        out = kit.run_harness(exe, path, text=True).split()
         got, n_used = np.array([int(v) for v in out[:28]], np.int64), int(out[28])
         ref, ref_used, _ = AT.iteration(vol, AT.DST_SIZE, TAU, p, n, M, J, gate)
         ref = np.rint(ref * 67108864.0).astype(np.int64)
@@ -208,20 +175,9 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
 
 
 # ---- 3. header, C layout, Python mirror -------------------------------------------------------------------------
-def test_align_structs_have_the_c_layout(tmp_path, hsk):
+def test_align_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d\\n", '
-                   'sizeof(hsk_align_params), offsetof(hsk_align_params, cos_gate), offsetof(hsk_align_params, min_points), '
-                   'offsetof(hsk_align_params, max_shift_m), sizeof(hsk_align_stats), offsetof(hsk_align_stats, n_used), '
-                   'offsetof(hsk_align_stats, rms_m), offsetof(hsk_align_stats, x_last), offsetof(hsk_align_stats, sums_last), '
-                   'HSK_ALIGN_MAX_ITERS_CAP, HSK_ALIGN_DIRECT);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, S = _lib.HskAlignParams, _lib.HskAlignStats
-    assert got == [C.sizeof(P), P.cos_gate.offset, P.min_points.offset, P.max_shift_m.offset, C.sizeof(S), S.n_used.offset, S.rms_m.offset,
-                   S.x_last.offset, S.sums_last.offset, _lib.HSK_ALIGN_MAX_ITERS_CAP, _lib.HSK_ALIGN_DIRECT]
     assert [n for n, _ in P._fields_] == ["max_iters", "probes", "cos_gate", "max_points", "min_points", "eps_rot", "eps_trans_m", "max_rot",
                                           "max_shift_m"]
     assert (_lib.HSK_ALIGN_CONVERGED, _lib.HSK_ALIGN_MAX_ITERS, _lib.HSK_ALIGN_FEW, _lib.HSK_ALIGN_DEGENERATE, _lib.HSK_ALIGN_DIVERGED) == (

@@ -12,7 +12,8 @@ import textwrap
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT
+
 
 FAKE_WORKER = textwrap.dedent('''
     import argparse, json, os, sys, time

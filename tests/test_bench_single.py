@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT
 
 
 @pytest.mark.parametrize("first", [0, 75])

@@ -6,36 +6,24 @@ no device.  The volumes and constants here are the GPU tests' too."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
 import clearance_twin as CL
-from test_align_host import blocked
-from test_components_host import speckled
-from test_cover_host import carved_volume
+import kit
+from clearance_cases import AXIS_SEG, MASK_BITS, SCENE_DEFAULTS, lookup_points, twin_field
+from components_cases import speckled
+from cover_cases import carved_volume
+from kit import ROOT, blocked
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENE_DEFAULTS = {"weight": (16, 25, 44), "max_d2": 11378, "flags": CL.UNKNOWN, "unit_m": f32(0.009375)}
-# the kernels' seams (hsk_clear_point.h; read back from the header below): a row mask's words, an axis pass's segments
-MASK_BITS, AXIS_SEG = 64, 16
-_CACHE = {}
 
 
 def header_constant(name):
     src = open(os.path.join(ROOT, "housescan_amd", "csrc", "hsk_clear_point.h")).read()
     return int(re.search(r"#define\s+%s\s+(\d+)u?\b" % name, src).group(1))
-
-
-def twin_field(name, vol, weight, max_d2, flags):
-    """the twin's field of a named volume, made once per (name, parameters)"""
-    key = (name, tuple(weight), int(max_d2), int(flags))
-    if key not in _CACHE:
-        _CACHE[key] = CL.field(vol, weight, max_d2, flags)
-    return _CACHE[key]
 
 
 def random_states(rng, dims, p_solid=0.03, p_unseen=0.1):
@@ -96,7 +84,7 @@ def run_harness(exe, tmp_path, vol, weight, max_d2, flags, size_m, pts):
         for part in (np.array([X, Y, Z], np.int32), np.array(list(weight) + [max_d2, flags], np.uint32), np.array(size_m, f32), np.uint32(len(pts)), pts,
                      blocked(vol)):
             f.write(np.ascontiguousarray(part).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     n = X * Y * Z
     fld = np.frombuffer(raw, np.uint32, n).reshape(Z, Y, X)
@@ -104,25 +92,11 @@ def run_harness(exe, tmp_path, vol, weight, max_d2, flags, size_m, pts):
     return fld, {"n_obstacle": int(st[0]), "n_far": int(st[1]), "max_d2_seen": int(st[2])}, np.frombuffer(raw, np.uint32, len(pts), n * 4 + 24)
 
 
-def lookup_points(size_m, dims, seed=3):
-    """points at voxel centres, on voxel faces, outside the grid and non-finite"""
-    rng = np.random.default_rng(seed)
-    cell = np.array([f32(size_m[i]) / f32(dims[i]) for i in range(3)], f32)
-    idx = rng.integers(0, dims, (40, 3))
-    centres = ((idx + 0.5) * cell).astype(f32)
-    faces = (idx * cell).astype(f32)
-    edge = np.array([[0.0, 0.0, 0.0], size_m, [size_m[0], 1.0, 1.0], [1.0, -0.0, 1.0], [2.99 * size_m[0] / 3.0, 1.0, 1.0]], f32)
-    odd = np.array([[-0.01, 1.0, 1.0], [1.0, 1.0, 40.0], [np.nan, 1.0, 1.0], [1.0, np.inf, 1.0], [1.0, 1.0, -np.inf], [1e30, 1e30, 1e30], [np.nan] * 3], f32)
-    return np.concatenate([centres, faces, edge, odd])
-
-
 def test_the_kernels_text_makes_the_twins_field_on_the_host(tmp_path):
     """hsk_clear_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program): row masks, nearest bits, windowed minima and the point lookup against the twin, zero differences"""
     assert (header_constant("CLEAR_MASK_BITS"), header_constant("CLEAR_AXIS_SEG"), header_constant("CLEAR_MAX_REACH")) == (MASK_BITS, AXIS_SEG, CL.MAX_REACH)
-    exe = tmp_path / "clear_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "clear_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("clear_point", tmp_path)
     for name, vol in host_cases().items():
         Z, Y, X = vol.shape[:3]
         size = (3.0 * X / 80, 3.0 * Y / 64, 3.0 * Z / 48)
@@ -200,20 +174,9 @@ def test_rank_views_clear(hsk):
         hsk.rank_views_clear(s, d[:3], 5)
 
 
-def test_clearance_structs_have_the_c_layout(tmp_path, hsk):
+def test_clearance_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %u %u %u %d %zu\\n", '
-                   'sizeof(hsk_clearance_params), offsetof(hsk_clearance_params, max_d2), offsetof(hsk_clearance_params, flags), '
-                   'offsetof(hsk_clearance_params, unit_m), sizeof(hsk_clearance_stats), offsetof(hsk_clearance_stats, scratch_bytes), '
-                   'offsetof(hsk_clearance_stats, max_d2_seen), offsetof(hsk_clearance_stats, reused), HSK_CLEARANCE_FAR, HSK_CLEARANCE_OUTSIDE, '
-                   'HSK_CLEAR_UNKNOWN, HSK_CLEAR_MAX_REACH, HSK_CLEAR_MAX_POINTS);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, S = _lib.HskClearanceParams, _lib.HskClearanceStats
-    assert got == [C.sizeof(P), P.max_d2.offset, P.flags.offset, P.unit_m.offset, C.sizeof(S), S.scratch_bytes.offset, S.max_d2_seen.offset, S.reused.offset,
-                   _lib.HSK_CLEARANCE_FAR, _lib.HSK_CLEARANCE_OUTSIDE, _lib.HSK_CLEAR_UNKNOWN, _lib.HSK_CLEAR_MAX_REACH, _lib.HSK_CLEAR_MAX_POINTS]
     assert (C.sizeof(P), C.sizeof(S)) == (24, 32)
     assert (CL.FAR, CL.OUTSIDE, CL.UNKNOWN, CL.MAX_REACH) == (_lib.HSK_CLEARANCE_FAR, _lib.HSK_CLEARANCE_OUTSIDE, _lib.HSK_CLEAR_UNKNOWN, _lib.HSK_CLEAR_MAX_REACH)
     assert (hsk.kinfu.CLEARANCE_FAR, hsk.kinfu.CLEARANCE_OUTSIDE, hsk.kinfu.CLEAR_UNKNOWN) == (CL.FAR, CL.OUTSIDE, CL.UNKNOWN)

@@ -9,32 +9,11 @@ import pytest
 import housescan_amd as hsk
 from housescan_amd import _lib, products
 
+from color_cases import read_pcd_xyzrgbnormal
+
 NEW_SYMBOLS = ["hsk_enable_color", "hsk_process_frame_rgbd", "hsk_submit_frame_rgbd", "hsk_integrate_color", "hsk_download_color",
                "hsk_upload_color", "hsk_extract_cloud_attrs", "hsk_voxel_downsample_attrs", "hsk_write_pcd_xyzrgbnormal",
                "hsk_synth_render_rgb", "hsk_synth_color_at"]
-
-
-def read_pcd_xyzrgbnormal(path):
-    """numpy parse of the binary PCD: header lines, then 32-B records -> (header dict, xyz, rgb bits, normals, curvature)"""
-    raw = open(path, "rb").read()
-    head, pos = {}, 0
-    while True:
-        end = raw.index(b"\n", pos)
-        line = raw[pos:end].decode()
-        pos = end + 1
-        if line.startswith("#"):
-            continue
-        key, _, val = line.partition(" ")
-        head[key] = val
-        if key == "DATA":
-            break
-    n = int(head["POINTS"])
-    rec = np.frombuffer(raw[pos:], dtype=np.uint32)
-    assert rec.size == 8 * n, (rec.size, n)
-    rec = rec.reshape(n, 8)
-    xyz = rec[:, 0:3].copy().view(np.float32)
-    nrm = rec[:, 4:7].copy().view(np.float32)
-    return head, xyz, rec[:, 3].copy(), nrm, rec[:, 7].copy().view(np.float32)
 
 
 def test_new_symbols_bound():

@@ -3,42 +3,20 @@ the numpy twin (tests/cover_twin.py), ray for ray; hsk_rank_views against the tw
 half-tau step, shown on the twin; the C layout of the new structs and their Python mirror; hsk_default_probe; the argument errors
 that need no device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
 import cover_twin as CT
+import kit
 import np_twin as T
 import reloc_twin as RT
-from test_align_host import TAU, blocked, scene
+from align_cases import scene
+from cover_cases import AWAY, TOWARDS, carved_volume, probe_40x30
+from kit import blocked
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATCH = (slice(16, 28), slice(25, 42), slice(61, 80))        # (z, y, x): a never-observed patch cut into the x = 2.7 m wall
-PATCH_CENTRE = (2.64375, 1.5703125, 1.375)
-EYE = (1.0, 1.5, 1.4)
-
-_CACHE = {}
-
-
-def carved_volume():
-    """the 80 x 64 x 48 scene with the patch set to (0, 0)"""
-    if "carved" not in _CACHE:
-        vol = scene()[0].copy()
-        vol[PATCH] = 0
-        _CACHE["carved"] = vol
-    return _CACHE["carved"]
-
-
-def probe_40x30(near_m=0.1, far_m=3.5, step_tau=0.5, w=40, h=30):
-    return CT.probe(w, h, 33.0, 33.0, (w - 1) / 2, (h - 1) / 2, near_m, far_m, f32(step_tau) * f32(TAU))
-
-
-TOWARDS = RT.look_at(EYE, PATCH_CENTRE)
-AWAY = RT.look_at(EYE, (0.3, 1.5, 1.4))
 
 
 def odd_translations():
@@ -72,7 +50,7 @@ def run_harness(exe, tmp_path, vol, pr, poses):
         for part in (np.array(AT.DST_DIMS, np.int32), np.array(AT.DST_SIZE, f32), np.array([pr["width"], pr["height"]], np.int32),
                      np.array([pr[k] for k in ("fx", "fy", "cx", "cy", "near_m", "far_m", "step_m")], f32), np.uint32(len(poses)), poses, blocked(vol)):
             f.write(np.ascontiguousarray(part).tobytes())
-    out = subprocess.check_output([str(exe), str(path)], text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    out = kit.run_harness(exe, path, text=True)
     rows = [np.array(line.split(), np.int64) for line in out.strip().splitlines()]
     assert len(rows) == len(poses)
     return [(int(r[0]), r[1:].reshape(pr["height"], pr["width"], 3)) for r in rows]
@@ -83,9 +61,7 @@ def test_the_kernels_ray_function_equals_the_twin_on_the_host(tmp_path):
     """the text every lane of k_cover_rays runs, built for the host with the address and undefined-behaviour sanitizers (their
     runtime linked into the program): class, depth and gain of every ray and every pose's eye_state against the twin, zero
     differences; a NaN or an infinity in a pose's translation makes its rays OUTSIDE and reads nothing out of bounds"""
-    exe = tmp_path / "cover_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cover_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("cover_point", tmp_path)
     vol = carved_volume()
     S = CT.states(vol)
     assert ((S == CT.UNSEEN).sum(), (S == CT.FREE).sum(), (S == CT.SOLID).sum()) == (100980, 106556, 38224)
@@ -181,22 +157,9 @@ def test_fully_scanned_walls_show_no_frontier_at_half_tau_and_the_patch_ranks_fi
 
 
 # ---- 4. header, C layout, Python mirror ---------------------------------------------------------------------------------------
-def test_cover_structs_have_the_c_layout(tmp_path, hsk):
+def test_cover_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
-                   '%d %d %d %d %d %d %d %d %d\\n", sizeof(hsk_voxel_box), offsetof(hsk_voxel_box, hi), sizeof(hsk_coverage), offsetof(hsk_coverage, n_frontier), '
-                   'offsetof(hsk_coverage, faces), sizeof(hsk_probe), offsetof(hsk_probe, fx), offsetof(hsk_probe, near_m), offsetof(hsk_probe, step_m), '
-                   'sizeof(hsk_view_score), offsetof(hsk_view_score, n_outside), offsetof(hsk_view_score, eye_state), offsetof(hsk_view_score, gain), '
-                   'HSK_RAY_HIT, HSK_RAY_FRONTIER, HSK_RAY_OPEN, HSK_RAY_BLIND, HSK_RAY_OUTSIDE, HSK_EYE_FREE, HSK_EYE_UNSEEN, HSK_EYE_SOLID, '
-                   'HSK_EYE_OUTSIDE);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     B, V, P, S = _lib.HskVoxelBox, _lib.HskCoverage, _lib.HskProbe, _lib.HskViewScore
-    assert got == [C.sizeof(B), B.hi.offset, C.sizeof(V), V.n_frontier.offset, V.faces.offset, C.sizeof(P), P.fx.offset, P.near_m.offset, P.step_m.offset,
-                   C.sizeof(S), S.n_outside.offset, S.eye_state.offset, S.gain.offset, _lib.HSK_RAY_HIT, _lib.HSK_RAY_FRONTIER, _lib.HSK_RAY_OPEN,
-                   _lib.HSK_RAY_BLIND, _lib.HSK_RAY_OUTSIDE, _lib.HSK_EYE_FREE, _lib.HSK_EYE_UNSEEN, _lib.HSK_EYE_SOLID, _lib.HSK_EYE_OUTSIDE]
     assert C.sizeof(S) == 32 and C.sizeof(V) == 80 and hsk.kinfu.VIEW_SCORE_DTYPE.itemsize == 32 and CT.VIEW_SCORE_DTYPE == hsk.kinfu.VIEW_SCORE_DTYPE
     assert [n for n, _ in S._fields_] == list(CT.CLASSES) + ["eye_state", "gain"]
     assert (_lib.HSK_RAY_HIT, _lib.HSK_RAY_FRONTIER, _lib.HSK_RAY_OPEN, _lib.HSK_RAY_BLIND, _lib.HSK_RAY_OUTSIDE) == (CT.HIT, CT.FRONTIER, CT.OPEN, CT.BLIND, CT.OUTSIDE)

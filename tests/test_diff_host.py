@@ -3,17 +3,15 @@ the numpy twin (tests/diff_twin.py) on the volume pairs the GPU tests use; the t
 analytic room and the shifted wall; the default parameters; the C layout of the new structs and their Python
 mirror; the refusals that need no device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import diff_cases as DC
 import diff_twin as DT
-from test_align_host import blocked
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit
+from diff_cases import records_as_dicts, words_of
+from kit import blocked
 
 
 def line(values):
@@ -146,9 +144,6 @@ def test_the_cases_reach_what_they_are_for():
 
 
 # ---- 2. the kernels' shared text on the host -------------------------------------------------------------------------------------
-def words_of(raw, n, offset):
-    w = np.frombuffer(raw, np.uint32, n, offset)
-    return np.stack([(w & 0xffff).astype(np.uint16).view(np.int16), (w >> 16).astype(np.uint16).view(np.int16)], axis=-1)
 
 
 def run_harness(exe, tmp_path, ref, cur, params, which, halo, ref_color, cur_color, voxels, radius):
@@ -165,7 +160,7 @@ def run_harness(exe, tmp_path, ref, cur, params, which, halo, ref_color, cur_col
             if col is not None:
                 f.write(np.ascontiguousarray(col).tobytes())
         f.write(np.asarray(voxels, np.int32).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     n, m = X * Y * Z, len(voxels)
     cls = np.frombuffer(raw, np.uint8, n).reshape(Z, Y, X)
@@ -188,18 +183,11 @@ def run_harness(exe, tmp_path, ref, cur, params, which, halo, ref_color, cur_col
     return cls, region, recs, n_minor, at_cls, at_region, out, col, st
 
 
-def records_as_dicts(recs):
-    return [{"root": tuple(map(int, c["root"])), "n_voxels": int(c["n_voxels"]), "n_appeared": int(c["n_appeared"]), "n_vanished": int(c["n_vanished"]),
-             "lo": tuple(map(int, c["lo"])), "hi": tuple(map(int, c["hi"]))} for c in recs]
-
-
 def test_the_kernels_rule_equals_the_twin_on_the_host(tmp_path):
     """hsk_diff_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program), diffing and adopting sequentially: classes, labels, records in order, the point query and the adopted volume and
     colour against the twin, zero differences"""
-    exe = tmp_path / "diff_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "diff_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("diff_point", tmp_path)
     cases = []
     for name, c in DC.shapes().items():
         ca, cb = DC.colors_of(name)
@@ -237,26 +225,9 @@ def test_default_diff_params_without_a_context(hsk):
     hsk._lib.load().hsk_default_diff_params(None, None)
 
 
-def test_diff_structs_have_the_c_layout(tmp_path, hsk):
+def test_diff_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
-                   '%d %d %d %d %d %d %d %d %d\\n", '
-                   'sizeof(hsk_diff_params), offsetof(hsk_diff_params, min_weight), offsetof(hsk_diff_params, min_voxels), '
-                   'sizeof(hsk_diff_region), offsetof(hsk_diff_region, n_voxels), offsetof(hsk_diff_region, n_appeared), offsetof(hsk_diff_region, n_vanished), '
-                   'offsetof(hsk_diff_region, lo), offsetof(hsk_diff_region, hi), '
-                   'sizeof(hsk_diff_stats), offsetof(hsk_diff_stats, n_regions), offsetof(hsk_diff_stats, n_minor_regions), offsetof(hsk_diff_stats, largest), '
-                   'sizeof(hsk_adopt_params), offsetof(hsk_adopt_params, halo), sizeof(hsk_adopt_stats), offsetof(hsk_adopt_stats, n_adopted), '
-                   'offsetof(hsk_adopt_stats, n_colored), HSK_DIFF_UNSEEN, HSK_DIFF_ONLY_REF, HSK_DIFF_ONLY_CUR, HSK_DIFF_SAME, HSK_DIFF_APPEARED, '
-                   'HSK_DIFF_VANISHED, HSK_DIFF_MINOR, HSK_ADOPT_APPEARED, HSK_ADOPT_VANISHED);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, R, S, A, T = _lib.HskDiffParams, _lib.HskDiffRegion, _lib.HskDiffStats, _lib.HskAdoptParams, _lib.HskAdoptStats
-    assert got == [C.sizeof(P), P.min_weight.offset, P.min_voxels.offset, C.sizeof(R), R.n_voxels.offset, R.n_appeared.offset, R.n_vanished.offset, R.lo.offset,
-                   R.hi.offset, C.sizeof(S), S.n_regions.offset, S.n_minor_regions.offset, S.largest.offset, C.sizeof(A), A.halo.offset, C.sizeof(T),
-                   T.n_adopted.offset, T.n_colored.offset, _lib.HSK_DIFF_UNSEEN, _lib.HSK_DIFF_ONLY_REF, _lib.HSK_DIFF_ONLY_CUR, _lib.HSK_DIFF_SAME,
-                   _lib.HSK_DIFF_APPEARED, _lib.HSK_DIFF_VANISHED, _lib.HSK_DIFF_MINOR, _lib.HSK_ADOPT_APPEARED, _lib.HSK_ADOPT_VANISHED]
     assert (C.sizeof(P), C.sizeof(R), C.sizeof(S), C.sizeof(A), C.sizeof(T)) == (16, 64, 80, 8, 24)
     assert hsk.kinfu.DIFF_REGION_DTYPE.itemsize == 64 and [hsk.kinfu.DIFF_REGION_DTYPE.fields[n][1] for n, _ in R._fields_] == [getattr(R, n).offset for n, _ in R._fields_]
     assert (DT.UNSEEN, DT.ONLY_REF, DT.ONLY_CUR, DT.SAME, DT.APPEARED, DT.VANISHED, DT.MINOR) == (

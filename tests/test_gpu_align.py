@@ -12,7 +12,8 @@ import pytest
 import align_twin as AT
 import fuse_twin as FT
 import np_twin as T
-from test_align_host import HALF_CELL_M, M_TRUE, TAU, same_bits
+from align_cases import HALF_CELL_M, M_TRUE, TAU
+from kit import same_bits, volume_ctx
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -24,7 +25,7 @@ _S = {}
 
 
 def dst_ctx(hsk, dims=AT.DST_DIMS, size=AT.DST_SIZE, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
+    return volume_ctx(hsk, dims, size, **over)
 
 
 @pytest.fixture(scope="module")

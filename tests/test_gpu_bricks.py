@@ -10,8 +10,8 @@ import pytest
 import align_twin as AT
 import brick_twin as BT
 import mesh_twin as MT
+from kit import assert_same_bits
 from np_twin import _Grid
-from test_gpu_parity import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 

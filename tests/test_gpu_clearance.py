@@ -11,10 +11,10 @@ import pytest
 import align_twin as AT
 import clearance_twin as CL
 import reloc_twin as RT
-from test_align_host import same_bits
-from test_clearance_host import AXIS_SEG, MASK_BITS, SCENE_DEFAULTS, lookup_points, twin_field
-from test_components_host import injected_volume, speckled
-from test_cover_host import PATCH_CENTRE, carved_volume
+from clearance_cases import AXIS_SEG, MASK_BITS, SCENE_DEFAULTS, lookup_points, twin_field
+from components_cases import injected_volume, speckled
+from cover_cases import PATCH_CENTRE, carved_volume
+from kit import same_bits, state_of, volume_ctx
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -23,8 +23,7 @@ SOLID_WORD = (-100, 1)
 
 
 def ctx(hsk, dims, size=None, **over):
-    size = size or (3.0 * dims[0] / 80, 3.0 * dims[1] / 64, 3.0 * dims[2] / 48)       # the scene's cells at every shape
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
+    return volume_ctx(hsk, dims, size or (3.0 * dims[0] / 80, 3.0 * dims[1] / 64, 3.0 * dims[2] / 48), **over)       # the scene's cells at every shape
 
 
 def check(trk, vol, ref, flags, **par):
@@ -288,10 +287,6 @@ def test_floor_maps(hsk):
 
 
 # ---- 9. nothing else moves ----------------------------------------------------------------------------------------------------------------
-def state_of(trk):
-    return [trk.get_pose()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
-
-
 def test_nothing_else_moves_and_a_scan_goes_on(hsk, synth_frames):
     a, b = hsk.KinfuTracker(n=64), hsk.KinfuTracker(n=64)
     try:
@@ -303,12 +298,12 @@ def test_nothing_else_moves_and_a_scan_goes_on(hsk, synth_frames):
             assert oka == okb and (oka or k == 0), f"frame {k}: tracked {oka} with the field, {okb} without"
             poses_a.append(pa), poses_b.append(pb)
             if k == 3:
-                before, vol = state_of(a), a.download_tsdf()
+                before, vol = state_of(a, False), a.download_tsdf()
                 a.build_clearance()
                 fld = a.download_clearance()
                 a.clearance_at(np.array([[1.5, 1.5, 1.0]], f32))
                 a.clearance_floor(1, 10, 40)
-                for u, v in zip(before, state_of(a)):
+                for u, v in zip(before, state_of(a, False)):
                     assert same_bits(u, v)
                 assert np.array_equal(a.download_tsdf(), vol) and np.array_equal(fld, CL.field(vol, (1, 1, 1), 456, CL.UNKNOWN))
                 b.download_tsdf()                     # (the same flush of the deferred weights on both sides)

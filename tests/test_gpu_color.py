@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from color_cases import frame_of, run_tracker
 from color_twin import band_of, integrate_color, np_attrs
 from np_twin import _Grid, scale_depth, tau_of
 
@@ -22,15 +23,6 @@ def cube_band(n, band_m):
 def cube_color(col, scaled, rgb, pose, band, max_w):
     """one frame's colour update of a cubic volume over 3 m, from the default camera (tests/color_twin.py)"""
     return integrate_color(col, SIZE3, scaled, rgb, FX, FY, CX, CY, pose, band, max_w)
-
-
-def frame_of(hsk, src, k):
-    """(pose, depth, rgb) of frame k of the scripted stream ("synth") or of room 0's scan ("room")"""
-    if src == "synth":
-        pose = hsk.synth_pose(k)
-        return pose, hsk.synth_depth(pose), hsk.synth_rgb(pose)
-    pose = hsk.synth_room_pose(0, k, 720)
-    return pose, hsk.synth_room_depth(0, pose), hsk.synth_rgb(pose, 0)
 
 
 def random_color(rng, n, max_w):
@@ -62,26 +54,6 @@ def test_integrate_color_stage_bitexact(hsk, n, src, band_m, max_w):
         assert len(bad) == 0, f"{len(bad)} voxels differ, first {bad[:5].tolist()}"
     assert np.array_equal(trk.download_tsdf(), tsdf0), "integrate_color must leave the TSDF alone"
     trk.close()
-
-
-def run_tracker(hsk, n, frames, color=True, use_graph=0, mode="sync", profile=False):
-    trk = hsk.KinfuTracker(n=n, use_graph=use_graph)
-    if color:
-        trk.enable_color()
-    if profile:
-        trk.set_profiling(1)
-    out = []
-    if mode == "sync":
-        for pose, depth, rgb in frames:
-            out.append(trk.process_frame_rgbd(depth, rgb) if color else trk.process_frame(depth))
-    else:
-        for i, (pose, depth, rgb) in enumerate(frames):
-            trk.submit_frame_rgbd(depth, rgb) if color else trk.submit_frame(depth)
-            if i >= 2:
-                out.append(trk.wait_frame())
-        while len(out) < len(frames):
-            out.append(trk.wait_frame())
-    return trk, out
 
 
 def replay(n, frames, results, max_w=64):
@@ -223,7 +195,7 @@ def test_extract_cloud_attrs_bitexact(hsk, tmp_path):
             call()
     # the room directory: cloud_bin.pcd parses back to the extracted arrays
     from housescan_amd import products
-    from test_color_host import read_pcd_xyzrgbnormal
+    from color_cases import read_pcd_xyzrgbnormal
     d = str(tmp_path / "room")
     products.write_room_dir(d, xyz, cloud_rgb=rgb, cloud_normals=nrm)
     _, xb, bits, nb, _ = read_pcd_xyzrgbnormal(os.path.join(d, "cloud_bin.pcd"))

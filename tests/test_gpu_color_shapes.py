@@ -8,6 +8,7 @@ import pytest
 
 import color_cases as CC
 import color_twin as CT
+from kit import same_bits
 from np_twin import scale_depth, tau_of
 
 pytestmark = pytest.mark.gpu
@@ -256,7 +257,7 @@ def test_readouts_pick_color_in_a_volume_with_a_cell_per_axis(hsk, oracle):
     ntri, codes = oracle.mc_table()
     with np.errstate(all="ignore"):
         tw = MT.mesh_indexed(vol, ntri, codes, size=AT.DST_SIZE, col=col)
-    assert MT.same_bits(v, tw["vertices"]) and np.array_equal(f, tw["faces"]) and len(f) > 5000
+    assert same_bits(v, tw["vertices"]) and np.array_equal(f, tw["faces"]) and len(f) > 5000
     assert MT.same_normals(mn, tw["normals"])
     bad = np.argwhere((mrgb != tw["rgb"]).any(axis=1))
     assert len(bad) == 0, f"mesh: {len(bad)} of {len(v)} colours differ, first vertices {bad[:5, 0].tolist()}"

@@ -12,20 +12,16 @@ import align_twin as AT
 import components_twin as KT
 import np_twin as T
 import reloc_twin as RT
-from test_align_host import same_bits
-from test_cover_host import EYE, carved_volume
-from test_components_host import BLOBS, grow, injected_volume, shapes, speckled, twin_of
+from components_cases import BLOBS, grow, injected_volume, shapes, speckled, twin_of
+from cover_cases import EYE, carved_volume
+from kit import dims_of, same_bits, state_of, volume_ctx
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
 def ctx(hsk, dims, size=AT.DST_SIZE, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-
-
-def dims_of(vol):
-    return vol.shape[2], vol.shape[1], vol.shape[0]
+    return volume_ctx(hsk, dims, size, **over)
 
 
 def check_against_twin(trk, name, vol):
@@ -227,10 +223,6 @@ def test_the_pruned_room_reads_out_like_the_room_that_never_had_the_blobs(hsk, m
 
 
 # ---- 6. the context otherwise does not move ----------------------------------------------------------------------------------------
-def state_of(trk):
-    return [trk.get_pose()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
-
-
 def test_pose_and_maps_stay_and_a_scan_goes_on(hsk, synth_frames):
     trk = hsk.KinfuTracker(n=64)
     try:
@@ -246,13 +238,13 @@ def test_pose_and_maps_stay_and_a_scan_goes_on(hsk, synth_frames):
         ring1 = grow(core) & ~core
         vol[core], vol[ring1], vol[grow(core | ring1) & ~core & ~ring1] = (-20000, 4), (9000, 4), (24000, 4)
         trk.upload_tsdf(vol)
-        before = state_of(trk)
+        before = state_of(trk, False)
         rec, _ = trk.label_components()
         trk.download_components()
         st = trk.prune_components()
         print(f"mid-scan: {st}")
         assert st["n_pruned"] >= 1 and (rec["n_voxels"] == 27).any()
-        for a, b in zip(before, state_of(trk)):
+        for a, b in zip(before, state_of(trk, False)):
             assert same_bits(a, b)
         assert not KT.inside(trk.download_tsdf())[core].any()
         for k in range(4, 8):

@@ -14,7 +14,7 @@ import threading
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_bits
+from kit import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 

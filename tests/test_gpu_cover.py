@@ -11,8 +11,9 @@ import pytest
 import align_twin as AT
 import cover_twin as CT
 import reloc_twin as RT
-from test_align_host import TAU, same_bits
-from test_cover_host import AWAY, EYE, TOWARDS, carved_volume, probe_40x30
+from align_cases import TAU
+from cover_cases import AWAY, EYE, TOWARDS, carved_volume, probe_40x30
+from kit import same_bits, state_of, volume_ctx
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -20,7 +21,7 @@ SIZE64 = (3.0, 3.0, 3.0)
 
 
 def ctx(hsk, dims, size=AT.DST_SIZE, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
+    return volume_ctx(hsk, dims, size, **over)
 
 
 @pytest.fixture(scope="module")
@@ -49,10 +50,6 @@ def as_kwargs(pr):
 def probe_of(p):
     """an HskProbe as the twin's dict"""
     return CT.probe(p.width, p.height, p.fx, p.fy, p.cx, p.cy, p.near_m, p.far_m, p.step_m)
-
-
-def state_of(trk):
-    return [trk.get_pose(), trk.download_tsdf()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
 
 
 # ---- 1. hsk_score_views against the twin ---------------------------------------------------------------------------------------
@@ -218,12 +215,12 @@ def test_the_three_calls_move_nothing_of_the_context(hsk):
     try:
         for k in range(3):
             trk.process_frame(hsk.synth_depth(hsk.synth_pose(k)))
-        before = state_of(trk)
+        before = state_of(trk, True)
         trk.coverage()
         trk.coverage(((1, 2, 3), (60, 61, 62)))
         trk.score_views(np.stack([trk.get_pose(), hsk.synth_pose(10)]))
         trk.render_coverage(trk.get_pose())
-        for a, b in zip(before, state_of(trk)):
+        for a, b in zip(before, state_of(trk, True)):
             assert same_bits(a, b)
         pose, ok = trk.process_frame(hsk.synth_depth(hsk.synth_pose(3)))        # ... and the scan goes on
         assert ok

@@ -9,8 +9,8 @@ import pytest
 import diff_cases as DC
 import diff_twin as DT
 import fuse_twin as FT
-from test_align_host import same_bits
-from test_diff_host import records_as_dicts
+from diff_cases import records_as_dicts
+from kit import dims_of, same_bits, volume_ctx
 
 pytestmark = pytest.mark.gpu
 CELL = 0.05      # the hand-built grids' cell; the truncation distance is then 2.1 cells
@@ -21,14 +21,7 @@ def size_of(dims):
 
 
 def ctx(hsk, dims, size=None, color=False, **over):
-    trk = hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size or size_of(dims), own_z1=dims[2], **over))
-    if color:
-        trk.enable_color()
-    return trk
-
-
-def dims_of(vol):
-    return vol.shape[2], vol.shape[1], vol.shape[0]
+    return volume_ctx(hsk, dims, size or size_of(dims), color, **over)
 
 
 def pair(hsk, ref, cur, ref_color=None, cur_color=None):

@@ -9,18 +9,14 @@ import pytest
 import align_twin as AT
 import fill_cases as FC
 import fill_twin as FT
-from test_align_host import same_bits
+from kit import dims_of, same_bits, state_of, volume_ctx
 
 pytestmark = pytest.mark.gpu
 TWIN_STATS = ("n_unseen", "n_reached", "n_written", "n_written_negative", "iterations_run")
 
 
 def ctx(hsk, dims, size=AT.DST_SIZE, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-
-
-def dims_of(vol):
-    return vol.shape[2], vol.shape[1], vol.shape[0]
+    return volume_ctx(hsk, dims, size, **over)
 
 
 def check_fill(trk, name, twin, box=None, **params):
@@ -153,20 +149,16 @@ def test_fill_on_a_volume_with_deferred_weights_and_the_scan_goes_on(hsk):
         b.close()
 
 
-def state_of(trk):
-    return [trk.get_pose()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
-
-
 def test_pose_and_maps_stay_and_tracking_goes_on(hsk, synth_frames):
     trk = hsk.KinfuTracker(n=64)
     try:
         for k in range(4):
             trk.process_frame(synth_frames(k)[1])
-        before = state_of(trk)
+        before = state_of(trk, False)
         st = trk.fill_holes()
         print(f"mid-scan: {st}")
         assert st["n_written"] > 0
-        for a, b in zip(before, state_of(trk)):
+        for a, b in zip(before, state_of(trk, False)):
             assert same_bits(a, b)
         for k in range(4, 8):
             pose, ok = trk.process_frame(synth_frames(k)[1])

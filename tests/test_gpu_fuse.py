@@ -12,66 +12,13 @@ import pytest
 import fuse_twin as FT
 import section_twin as ST
 import view_twin as VT
-from test_fuse_host import PLANE_N, PLANE_TAU, general, plane_case
-from test_gpu_section import SCAN_FRAMES, ortho_cam, room_frames
-from view_twin import same_bits
+from fuse_cases import HOUSE_DIMS, HOUSE_SIZE, N, PLANE_N, PLANE_TAU, SIZE, _close_scans, general, make_ctx, plane_case, room_scan  # noqa: F401  (the fixture closes the scans)
+from kit import same_bits_nan
+from section_cases import SCAN_FRAMES, ortho_cam, room_frames
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-N = 128
-SIZE = (3.0, 3.0, 3.0)
-HOUSE_DIMS, HOUSE_SIZE = (256, 128, 128), (6.0, 3.0, 3.0)
 CELL = 3.0 / N
-
-SCAN_STEP = 3    # every third frame of the scripted three-turn scan: 240 frames per room
-
-_SCANS = {}
-
-
-def scan_room(hsk, variant, lo=0, hi=SCAN_FRAMES, step=SCAN_STEP):
-    """a room's RGB-D scan at 128^3: depth and colour of the scripted trajectory's frames, fused at the script's own poses
-    through the stage-level calls (at 47 mm of truncation the TRACKER loses this trajectory near frame 190; what is under test
-    here is what happens to a scanned volume, not how its poses were found)"""
-    trk = hsk.KinfuTracker(n=N, init_pose=hsk.synth_room_pose(variant, 0, SCAN_FRAMES))
-    trk.enable_color()
-    for at in range(lo, hi, 48 * step):
-        ks = list(range(at, min(at + 48 * step, hi), step))
-        for k, (d, c) in zip(ks, room_frames_at(hsk, variant, ks)):
-            pose = hsk.synth_room_pose(variant, k, SCAN_FRAMES)
-            trk.integrate(d, pose)
-            trk.integrate_color(d, c, pose)
-    return trk
-
-
-def room_frames_at(hsk, variant, ks):
-    from concurrent.futures import ThreadPoolExecutor
-    poses = [hsk.synth_room_pose(variant, k, SCAN_FRAMES) for k in ks]
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(lambda p: (hsk.synth_room_depth(variant, p), hsk.synth_rgb(p, variant)), poses))
-
-
-def room_scan(hsk, variant):
-    """(tracker, tsdf, colour volume) of a room's RGB-D scan at 128^3, made once per module"""
-    if variant not in _SCANS:
-        trk = scan_room(hsk, variant)
-        _SCANS[variant] = (trk, trk.download_tsdf(), trk.download_color())
-    return _SCANS[variant]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_scans():
-    yield
-    for trk, _, _ in _SCANS.values():
-        trk.close()
-    _SCANS.clear()
-
-
-def make_ctx(hsk, dims=(N, N, N), size=SIZE, color=True, **over):
-    cfg = hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, **over)
-    trk = hsk.KinfuTracker(cfg)
-    if color:
-        trk.enable_color()
-    return trk
 
 
 def empty_like_ctx(dims, color=True):
@@ -226,26 +173,26 @@ def test_the_fused_context_equals_a_fresh_one_with_the_same_volume(hsk):
         fresh.upload_tsdf(tsdf)
         fresh.upload_color(col)
         for a, b in zip(fused.extract_cloud_attrs(), fresh.extract_cloud_attrs()):
-            assert same_bits(np.asarray(a), np.asarray(b)), "cloud"
+            assert same_bits_nan(np.asarray(a), np.asarray(b)), "cloud"
         assert fused.extract_cloud(cap=0)[1] > 1000
         for a, b in zip(fused.extract_mesh_indexed(), fresh.extract_mesh_indexed()):
-            assert same_bits(np.asarray(a), np.asarray(b)), "indexed mesh"
+            assert same_bits_nan(np.asarray(a), np.asarray(b)), "indexed mesh"
         pose = hsk.synth_room_pose(0, 40, SCAN_FRAMES)
         va = fused.render_view(pose=pose, mode=VT.COLOR_LIT, vmap=True, nmap=True)
         vb = fresh.render_view(pose=pose, mode=VT.COLOR_LIT, vmap=True, nmap=True)
         assert va["n_hit"] > 1000
         for key in va:
-            assert same_bits(np.asarray(va[key]), np.asarray(vb[key])), f"view: {key}"
+            assert same_bits_nan(np.asarray(va[key]), np.asarray(vb[key])), f"view: {key}"
         down = ST.look((1.5, -0.5, 1.5), (1.5, 0.5, 1.5), (0, 0, 1))
         sec = dict(ortho_cam(down), clip=[(0, 1, 0, -1.4)], mode=VT.LAMBERT, light=(0.3, -1.0, 0.2), light_in_camera=False,
                    light_directional=True, vmap=True, nmap=True)
         sa, sb = fused.render_section(**sec), fresh.render_section(**sec)
         assert sa["n_hit"] + sa["n_cut"] > 1000
         for key in sa:
-            assert same_bits(np.asarray(sa[key]), np.asarray(sb[key])), f"section: {key}"
+            assert same_bits_nan(np.asarray(sa[key]), np.asarray(sb[key])), f"section: {key}"
         # scanning on: the raycast sets the pose and the model maps; then the same frame integrates into both
         for a, b in zip(fused.raycast(pose, want_keys=True), fresh.raycast(pose, want_keys=True)):
-            assert same_bits(a, b), "raycast"
+            assert same_bits_nan(a, b), "raycast"
         depth = hsk.synth_room_depth(0, pose)
         fused.integrate(depth, pose)
         fresh.integrate(depth, pose)
@@ -268,7 +215,7 @@ def test_the_source_is_untouched(hsk):
         dst.close()
     assert np.array_equal(src.download_tsdf(), s_tsdf) and np.array_equal(src.download_color(), s_col)
     for a, b in zip(cloud, src.extract_cloud_attrs()):
-        assert same_bits(np.asarray(a), np.asarray(b))
+        assert same_bits_nan(np.asarray(a), np.asarray(b))
 
 
 # ---- 6. the rule's own properties, on the device -----------------------------------------------------------------

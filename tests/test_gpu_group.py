@@ -8,10 +8,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_bits
+from kit import ROOT, assert_same_bits
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _reference(hsk, synth_frames, n, frames):

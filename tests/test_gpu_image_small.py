@@ -9,7 +9,7 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_bits
+from kit import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 N_FRAMES = 5

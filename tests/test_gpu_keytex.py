@@ -13,8 +13,8 @@ import keytex_cases as KC
 import keytex_twin as KT
 import texture_cases as TC
 import texture_twin as TT
-from test_gpu_texture import loaded
-from test_keytex_host import differing
+from keytex_cases import differing
+from texture_cases import loaded
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

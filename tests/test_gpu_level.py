@@ -10,16 +10,15 @@ import pytest
 
 import align_twin as AT
 import level_twin as LT
-from test_align_host import same_bits
-from test_level_host import ANGLE_BAR_DEG, assert_same_upright, jittered, tilted, twin_of
+from kit import same_bits, state_of, volume_ctx
+from level_cases import ANGLE_BAR_DEG, assert_same_upright, jittered, tilted, twin_of
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
 def ctx(hsk, scene, **over):
-    (X, Y, Z), size = LT.SCENES[scene]
-    return hsk.KinfuTracker(hsk.default_config(Z, vol_x=X, vol_y=Y, vol_z=Z, vol_size_m=size, own_z1=Z, **over))
+    return volume_ctx(hsk, *LT.SCENES[scene], **over)
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +36,6 @@ def tilted_src(hsk):
     t.upload_tsdf(tilted("80x64x48", "a")[0])
     yield t
     t.close()
-
-
-def state_of(t):
-    return [t.get_pose(), t.download_tsdf()] + [t.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
 
 
 # ---- 1. the device stages against the twin ------------------------------------------------------------------------------------
@@ -115,9 +110,9 @@ def test_estimate_upright_on_the_uploaded_tilted_scene(hsk, scene):
         t.upload_tsdf(vol)
         xyz, nrm, _, total, _ = t.extract_cloud_attrs(rgb=False)
         assert total == len(ps) and same_bits(xyz, ps)
-        before = state_of(t)
+        before = state_of(t, True)
         got = t.estimate_upright()
-        for a, b in zip(before, state_of(t)):
+        for a, b in zip(before, state_of(t, True)):
             assert same_bits(a, b), "hsk_estimate_upright moved something"
         assert_same_upright(got, ref, scene)
         xyz2, nrm2, _, total2, _ = t.extract_cloud_attrs(rgb=False)

@@ -4,10 +4,10 @@ and a room scanned at 512^3 written as a coloured .ply."""
 import numpy as np
 import pytest
 
-from mesh_twin import mesh_indexed, same_bits, same_normals
-from test_gpu_color import frame_of, run_tracker
-from test_mesh import sphere_volume
-from test_mesh_indexed_host import planted_zeros_volume, random_sign_volume, read_ply_indexed
+from color_cases import frame_of, run_tracker
+from kit import same_bits
+from mesh_cases import planted_zeros_volume, random_sign_volume, read_ply_indexed, sphere_volume
+from mesh_twin import mesh_indexed, same_normals
 
 pytestmark = pytest.mark.gpu
 

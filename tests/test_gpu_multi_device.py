@@ -12,10 +12,9 @@ import textwrap
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_bits
+from kit import ROOT, assert_same_bits
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _n_devices():

@@ -10,26 +10,13 @@ import pytest
 
 import pack_twin as PT
 import view_twin as VT
-from test_gpu_fuse import HOUSE_DIMS, HOUSE_SIZE, N, SIZE, make_ctx, room_scan, _close_scans  # noqa: F401  (the fixture closes the scans)
-from test_gpu_section import SCAN_FRAMES, room_frames
-from view_twin import same_bits
+from fuse_cases import HOUSE_DIMS, HOUSE_SIZE, N, SIZE, _close_scans, make_ctx, room_scan  # noqa: F401  (the fixture closes the scans)
+from kit import same_bits_nan
+from pack_cases import assert_same_image, ctx_fields
+from section_cases import SCAN_FRAMES, room_frames
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def ctx_fields(hsk, trk):
-    """the header fields a context contributes, computed here from its configuration (binary32 throughout, as hsk_create)"""
-    cfg = trk.cfg
-    dims = (cfg.vol_x, cfg.vol_y, cfg.vol_z)
-    size = np.array(cfg.vol_size_m[:], f32)
-    cell = size / np.array(dims, f32)
-    tau = max(f32(cfg.trunc_dist_m), f32(2.1) * cell.max())
-    color = trk.color_params if getattr(trk, "color_params", None) else None
-    return PT.default_fields(dims, size_m=tuple(size), trunc_dist_m=f32(cfg.trunc_dist_m), trunc_eff_m=f32(tau), width=cfg.width,
-                             height=cfg.height, fx=cfg.fx, fy=cfg.fy, cx=cfg.cx, cy=cfg.cy, pose=tuple(trk.get_pose().reshape(-1)),
-                             frame=trk.lib.hsk_mgpu_frame_index(trk.h), color_max_weight=color[0] if color else 0,
-                             color_band_m=f32(min(f32(2.0) * cell.max(), tau)) if color else f32(0.0))
 
 
 def with_color(trk, max_weight=64):
@@ -40,17 +27,6 @@ def with_color(trk, max_weight=64):
 
 def twin_image(hsk, trk):
     return PT.pack(trk.download_tsdf(), trk.download_color() if getattr(trk, "color_params", None) else None, ctx_fields(hsk, trk))
-
-
-def assert_same_image(got, want, what):
-    if got == want:
-        return
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    n = min(len(a), len(b))
-    bad = np.flatnonzero(a[:n] != b[:n])
-    f = PT.info(want)
-    raise AssertionError(f"{what}: {len(got)} bytes against the twin's {len(want)}; {len(bad)} differ, first at {bad[:8].tolist()} "
-                         f"(sections at {f['at']}); device header {PT.read_header(got) if len(got) >= 256 else None}")
 
 
 def scanned_twin_is_nontrivial(img, color=True):
@@ -179,18 +155,18 @@ def test_pack_writes_the_deferred_weights_back_first(hsk):
 # ---- 3. round trip: the destination is a whole, consistent context -------------------------------------------------
 def assert_same_context(hsk, a, b, tsdf):
     for x, y in zip(a.extract_cloud_attrs(), b.extract_cloud_attrs()):
-        assert same_bits(np.asarray(x), np.asarray(y)), "cloud"
+        assert same_bits_nan(np.asarray(x), np.asarray(y)), "cloud"
     assert a.extract_cloud(cap=0)[1] > 1000
     for x, y in zip(a.extract_mesh_indexed(), b.extract_mesh_indexed()):
-        assert same_bits(np.asarray(x), np.asarray(y)), "indexed mesh"
+        assert same_bits_nan(np.asarray(x), np.asarray(y)), "indexed mesh"
     pose = hsk.synth_room_pose(0, 40, SCAN_FRAMES)
     va = a.render_view(pose=pose, mode=VT.COLOR_LIT, vmap=True, nmap=True)
     vb = b.render_view(pose=pose, mode=VT.COLOR_LIT, vmap=True, nmap=True)
     assert va["n_hit"] > 1000
     for key in va:
-        assert same_bits(np.asarray(va[key]), np.asarray(vb[key])), f"view: {key}"
+        assert same_bits_nan(np.asarray(va[key]), np.asarray(vb[key])), f"view: {key}"
     for x, y in zip(a.raycast(pose, want_keys=True), b.raycast(pose, want_keys=True)):
-        assert same_bits(x, y), "raycast"
+        assert same_bits_nan(x, y), "raycast"
     depth, rgb = hsk.synth_room_depth(0, pose), hsk.synth_rgb(pose, 0)
     for t in (a, b):
         t.integrate(depth, pose)

@@ -8,34 +8,15 @@ import os
 import numpy as np
 import pytest
 
+from kit import ROOT, assert_same_bits
+from parity_cases import _lookat_pose, _random_depth, _random_pose
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # The fuzz tests hold two assertions about what the suite's OWN seeds happen to produce (so many updates, so many lost
 # frames): they show that the seeds exercise what they are meant to, and say nothing about parity.  tools/fuzz_campaign.py,
 # which runs the same tests over hundreds of other seeds, switches them off -- so that every parity comparison behind them
 # still runs for every seed (a seed that tripped the expectation used to leave its volume and its pipelined run unchecked).
 SEED_EXPECTATIONS = True
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def assert_same_bits(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape, what
-    # NaNs: compare "is NaN" masks, then bit patterns elsewhere (the sign/payload of a NaN is not part of the contract)
-    if a.dtype.kind == "f":
-        na, nb = np.isnan(a), np.isnan(b)
-        assert np.array_equal(na, nb), f"{what}: NaN masks differ at {np.argwhere(na != nb)[:5]}"
-        ok = bits(np.where(na, 0, a).astype(a.dtype)) == bits(np.where(nb, 0, b).astype(b.dtype))
-    else:
-        ok = a == b
-    if not ok.all():
-        idx = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {len(idx)} of {ok.size} elements differ, first at {idx[:5].tolist()}: "
-                             f"{a[tuple(idx[0])]} vs {b[tuple(idx[0])]}")
 
 
 @pytest.mark.parametrize("n", [64, 128, 256, 512])   # 512: the headline size, every voxel compared
@@ -72,48 +53,6 @@ def test_integrate_ragged_and_empty(hsk, oracle, synth_frames):
         trk.integrate(depth, p)
         assert_same_bits(trk.download_tsdf(), vol, "tsdf (ragged volume)")
     trk.close()
-
-
-def _random_pose(rng, centre, spread):
-    """camera-to-world: a rotation by a random angle about a random axis (any angle: the camera may look away from the
-    volume, upside down, along an axis), the centre anywhere within `spread` of `centre`"""
-    ax = rng.normal(size=3)
-    ax /= np.linalg.norm(ax)
-    ang = rng.uniform(-np.pi, np.pi)
-    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
-    R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
-    P = np.eye(4, dtype=np.float32)
-    P[:3, :3] = R.astype(np.float32)
-    P[:3, 3] = (np.asarray(centre) + rng.uniform(-1, 1, 3) * spread).astype(np.float32)
-    return P
-
-
-def _lookat_pose(rng, centre, spread):
-    """camera somewhere within `spread` of `centre`, its z axis towards a point near the centre, any roll"""
-    P = _random_pose(rng, centre, spread)
-    z = np.asarray(centre) + rng.uniform(-0.3, 0.3, 3) * spread - P[:3, 3]
-    z /= np.linalg.norm(z) + 1e-9
-    x = np.cross(rng.normal(size=3), z)
-    x /= np.linalg.norm(x)
-    P[:3, :3] = np.stack([x, np.cross(z, x), z], axis=1).astype(np.float32)
-    return P
-
-
-def _random_depth(rng, h=480, w=640):
-    """blocky random depth in millimetres: patches of 1..48 px with independent values (discontinuities at every patch
-    edge: the tile min / max tables of pass A see their worst case), holes, a band of per-pixel noise, and a few
-    extreme values (1 mm, 65535 mm)"""
-    by, bx = int(rng.integers(1, 49)), int(rng.integers(1, 49))
-    coarse = rng.integers(300, 5000, size=(h // by + 2, w // bx + 2))
-    d = np.kron(coarse, np.ones((by, bx), np.int64))[:h, :w]
-    d = d + rng.integers(-20, 21, size=(h, w)) * (rng.random((h, w)) < 0.5)
-    d[rng.random((h, w)) < 0.1] = 0
-    hy, hx = rng.integers(0, h - 60), rng.integers(0, w - 80)
-    d[hy:hy + 60, hx:hx + 80] = 0
-    ex = rng.random((h, w))
-    d[ex < 0.001] = 1
-    d[ex > 0.999] = 65535
-    return np.clip(d, 0, 65535).astype(np.uint16)
 
 
 @pytest.mark.parametrize("seed", range(9))

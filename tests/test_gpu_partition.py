@@ -14,11 +14,12 @@ import align_twin as AT
 import clearance_twin as CL
 import partition_twin as PT
 import reach_twin as RE
-from test_clearance_host import SCENE_DEFAULTS, twin_field
-from test_components_host import injected_volume
-from test_cover_host import carved_volume
-from test_partition_host import (DOOR_THRESHOLD, MIRROR_DIMS, MIRROR_PAD, RAGGED, clear_params, d2_of, mirror_rooms, ragged_case, serpentine_core_d2, twin_partition)
-from test_reach_host import CORNER_DIMS, SERPENTINE_DIMS, SOLID_WORD, TILE, WEIGHTS, centre, corridors, scene_size, serpentine, tile_corner, two_rooms
+from clearance_cases import SCENE_DEFAULTS, twin_field
+from components_cases import injected_volume
+from cover_cases import carved_volume
+from kit import volume_ctx
+from partition_cases import (DOOR_THRESHOLD, MIRROR_DIMS, MIRROR_PAD, RAGGED, clear_params, d2_of, mirror_rooms, ragged_case, serpentine_core_d2, twin_partition)
+from reach_cases import CORNER_DIMS, SERPENTINE_DIMS, SOLID_WORD, TILE, WEIGHTS, centre, corridors, scene_size, serpentine, tile_corner, two_rooms
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -26,8 +27,7 @@ STAT_KEYS = ("n_cores", "n_rooms", "n_dropped", "n_passable", "n_assigned", "n_d
 
 
 def ctx(hsk, dims, size=None, **over):
-    size = size or scene_size(dims)
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
+    return volume_ctx(hsk, dims, size or scene_size(dims), **over)
 
 
 def scratch_bound(dims, n_rooms):

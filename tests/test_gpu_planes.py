@@ -8,17 +8,16 @@ import numpy as np
 import pytest
 
 import planes_twin as PT
-from test_align_host import same_bits
-from test_level_host import jittered
-from test_planes_host import COS_MIN, DIST_M, assert_scene_bar, odd_cloud, scene_cloud, score_planes_for_tests, twin_scene, twin_wall
+from kit import same_bits, state_of, volume_ctx
+from level_cases import jittered
+from planes_cases import COS_MIN, DIST_M, assert_scene_bar, odd_cloud, scene_cloud, score_planes_for_tests, twin_scene, twin_wall
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
 
 def ctx(hsk, **over):
-    X, Y, Z = PT.SCENE_DIMS
-    return hsk.KinfuTracker(hsk.default_config(Z, vol_x=X, vol_y=Y, vol_z=Z, vol_size_m=PT.SCENE_SIZE, own_z1=Z, **over))
+    return volume_ctx(hsk, PT.SCENE_DIMS, PT.SCENE_SIZE, **over)
 
 
 @pytest.fixture(scope="module")
@@ -28,10 +27,6 @@ def trk(hsk):
     t.upload_tsdf(scene_cloud()[0])
     yield t
     t.close()
-
-
-def state_of(t):
-    return [t.get_pose(), t.download_tsdf()] + [t.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
 
 
 def assert_same_result(got, ref, what):
@@ -58,7 +53,7 @@ def test_score_planes_matches_the_twin(hsk, trk):
     inl = np.concatenate([PT.inliers(planes[j:j + 64], ps, ns, ok, DIST_M, COS_MIN)[0] for j in range(0, len(planes), 64)])
     assert inl.shape == (513, n_all) and (inl.sum(axis=1) > 1000).sum() >= 6 and (inl.sum(axis=1) == 0).sum() >= 2
     assert np.array_equal(inl.sum(axis=1).astype(np.uint32), PT.score(ps, ns, planes, DIST_M, COS_MIN))
-    before = state_of(trk)
+    before = state_of(trk, True)
     for n in (0, 1, 63, 64, 65, 257, n_all):
         for m in (1, 3, 513):
             pl = planes[:m] if m > 1 else planes[4:5]
@@ -73,7 +68,7 @@ def test_score_planes_matches_the_twin(hsk, trk):
     # other thresholds: everything that faces the plane's way within a metre; nothing
     for dist_m, cos_min in ((1.0, -1.0), (0.001, 1.0)):
         assert np.array_equal(trk.score_planes(ps, ns, planes[:9], dist_m, cos_min), PT.score(ps, ns, planes[:9], dist_m, cos_min))
-    for a, b in zip(before, state_of(trk)):
+    for a, b in zip(before, state_of(trk, True)):
         assert same_bits(a, b), "hsk_score_planes moved something"
 
 
@@ -82,7 +77,7 @@ def test_detect_planes_cloud_matches_the_twin_on_the_scene(hsk, trk):
     """(a), every field and every label; then the parameters' corners: one hypothesis per round, one plane, no refit"""
     _, ps, ns = scene_cloud()
     ref_rec, ref_labels, ref_bad = twin_scene()
-    before = state_of(trk)
+    before = state_of(trk, True)
     rec, labels, bad = trk.detect_planes_cloud(ps, ns)
     assert bad == ref_bad == 0
     assert_same_result((rec, labels), (ref_rec, ref_labels), "the scene")
@@ -94,7 +89,7 @@ def test_detect_planes_cloud_matches_the_twin_on_the_scene(hsk, trk):
         print(f"{over}: {len(got[0])} planes, {got[0]['n_inliers']}")
         assert_same_result(got[:2], ref[:2], over)
     assert len(trk.detect_planes_cloud(ps, ns, max_planes=1)[0]) == 1
-    for a, b in zip(before, state_of(trk)):
+    for a, b in zip(before, state_of(trk, True)):
         assert same_bits(a, b), "hsk_detect_planes_oriented moved something"
 
 
@@ -157,9 +152,9 @@ def test_detect_planes_volume_is_the_cloud_form_on_the_contexts_own_cloud(hsk):
     try:
         t.upload_tsdf(vol)
         cloud_before, total_before = t.extract_cloud()
-        before = state_of(t)
+        before = state_of(t, True)
         rec, labels = t.detect_planes()
-        for a, b in zip(before, state_of(t)):
+        for a, b in zip(before, state_of(t, True)):
             assert same_bits(a, b), "hsk_detect_planes_volume moved something"
         cloud_after, total_after = t.extract_cloud()
         assert total_after == total_before == len(labels) and same_bits(cloud_after, cloud_before)

@@ -13,12 +13,11 @@ import align_twin as AT
 import clearance_twin as CL
 import reach_twin as RE
 import reloc_twin as RT
-from test_align_host import same_bits
-from test_clearance_host import SCENE_DEFAULTS, twin_field
-from test_components_host import injected_volume, speckled
-from test_cover_host import EYE, carved_volume
-from test_reach_host import (CORNER_DIMS, FREE_WORD, SERPENTINE_DIMS, SOLID_WORD, STAIR_DIMS, TILE, WEIGHTS, centre, check_path, corridors, free_volume, hand_d2,
-                             hand_params, scene_size, serpentine, staircase, tile_corner, twin_reach, two_rooms)
+from clearance_cases import SCENE_DEFAULTS, twin_field
+from components_cases import injected_volume, speckled
+from cover_cases import EYE, carved_volume
+from kit import same_bits, state_of, volume_ctx
+from reach_cases import (CORNER_DIMS, FREE_WORD, SERPENTINE_DIMS, SOLID_WORD, STAIR_DIMS, TILE, WEIGHTS, centre, check_path, corridors, free_volume, hand_d2, hand_params, scene_size, serpentine, staircase, tile_corner, twin_reach, two_rooms)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -26,8 +25,7 @@ STAT_KEYS = ("n_passable", "n_reached", "max_cost_seen")
 
 
 def ctx(hsk, dims, size=None, **over):
-    size = size or scene_size(dims)
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
+    return volume_ctx(hsk, dims, size or scene_size(dims), **over)
 
 
 def scratch_bound(dims):
@@ -304,10 +302,6 @@ def test_a_volume_with_deferred_weights(hsk):
         b.close()
 
 
-def state_of(trk):
-    return [trk.get_pose()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
-
-
 def test_nothing_else_moves_and_a_scan_goes_on(hsk, synth_frames):
     a, b = hsk.KinfuTracker(n=64), hsk.KinfuTracker(n=64)
     try:
@@ -320,13 +314,13 @@ def test_nothing_else_moves_and_a_scan_goes_on(hsk, synth_frames):
             assert oka == okb and (oka or k == 0), f"frame {k}: tracked {oka} with the field, {okb} without"
             poses_a.append(pa), poses_b.append(pb)
             if k == 3:
-                before, vol = state_of(a), a.download_tsdf()
+                before, vol = state_of(a, False), a.download_tsdf()
                 st = a.build_reach(pts, flags=0)
                 g = a.download_reach()
                 a.reach_at(np.array(pts, f32))
                 a.reach_path(pts[1])
                 a.reach_floor(1, 10, 40, pts, flags=0)
-                for u, v in zip(before, state_of(a)):
+                for u, v in zip(before, state_of(a, False)):
                     assert same_bits(u, v)
                 ref, used = RE.field(CL.field(vol, (1, 1, 1), 456, 0), (1, 1, 1), 41, RE.MAX_COST, tuple(RE.seed_voxels((3.0,) * 3, (64,) * 3, pts)))
                 assert np.array_equal(a.download_tsdf(), vol) and np.array_equal(g, ref) and st["n_seeds_used"] == used and st["n_reached"] >= 1000

@@ -11,8 +11,8 @@ import pytest
 
 import align_twin as AT
 import reloc_twin as RT
-from test_align_host import same_bits
-from test_reloc_host import HALF_CELL_M, ROOM_DIMS, ROOM_SIZE, ROOM_TAU, displaced_pair, room_volume, score_cases, thick_wall_volume
+from kit import assert_state, same_bits, state_of, volume_ctx
+from reloc_cases import HALF_CELL_M, ROOM_DIMS, ROOM_SIZE, ROOM_TAU, displaced_pair, room_volume, score_cases, thick_wall_volume
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -20,12 +20,8 @@ CAM = dict(width=320, height=240, fx=262.5, fy=262.5, cx=159.5, cy=119.5)
 LATTICE = (0.2, 3, float(np.radians(20.0)), 2)       # around the last pose: 8575 candidates
 
 
-def ctx(hsk, dims, size, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-
-
 def room_ctx(hsk):
-    trk = ctx(hsk, ROOM_DIMS, ROOM_SIZE, **CAM)
+    trk = volume_ctx(hsk, ROOM_DIMS, ROOM_SIZE, **CAM)
     trk.upload_tsdf(room_volume())
     return trk
 
@@ -54,15 +50,6 @@ def frame_cloud(trk, depth, level):
     return P, N
 
 
-def state_of(trk):
-    return [trk.get_pose(), trk.download_tsdf()] + [trk.download_map(kind, level) for kind in (2, 3) for level in (0, 1, 2)]
-
-
-def assert_state(trk, before, what):
-    for a, b in zip(before, state_of(trk)):
-        assert same_bits(a, b), what
-
-
 def score_records(cls, q, n, m):
     """the twin's scores of the first n points under the first m poses, from its classes of all points under all poses"""
     out = np.zeros(m, RT.SCORE_DTYPE)
@@ -89,10 +76,10 @@ def test_score_cloud_matches_the_twin(hsk):
     cls, q = RT.classes(vol, AT.DST_SIZE, ps, poses)
     for c in range(6):
         assert (cls == c).any(), RT.CLASSES[c]
-    trk = ctx(hsk, AT.DST_DIMS, AT.DST_SIZE)
+    trk = volume_ctx(hsk, AT.DST_DIMS, AT.DST_SIZE)
     try:
         trk.upload_tsdf(vol)
-        before = state_of(trk)
+        before = state_of(trk, True)
         for n in (0, 1, 63, 1000, n_all):
             for m in (1, 5, 257):
                 got = trk.score_cloud(ps[:n], poses[:m])
@@ -149,7 +136,7 @@ VIEWS = (RT.look_at((2.3, 1.7, 0.8), (1.1, 0.8, 2.5)), RT.look_at((2.2, 1.8, 1.0
 def windowed_room_ctx(hsk):
     vol = room_volume().copy()
     vol[80:, 38:86, 48:112] = 0          # z >= 2.5 m, y in 0.89 .. 2.02 m, x in 0.9 .. 2.1 m
-    trk = ctx(hsk, ROOM_DIMS, ROOM_SIZE, **CAM)
+    trk = volume_ctx(hsk, ROOM_DIMS, ROOM_SIZE, **CAM)
     trk.upload_tsdf(vol)
     return trk
 
@@ -197,7 +184,7 @@ def relocalize_is_its_composition(hsk, room):
     view, depth = chosen
     start = RT.displaced(view, (0.03, -0.02, 0.04), 2.0, -1.5).astype(f32)
     poses = hsk.pose_lattice(start, 0.04, 1, float(np.radians(2.0)), 1)         # 243 candidates within reach of the truth and beyond it
-    before = state_of(room)
+    before = state_of(room, True)
     for level, kw in ((2, {}), (1, dict(n_refine=6, accept_fraction=0.3, probes=2, max_iters=12))):
         got_pose, got = room.relocalize(depth, poses, level=level, **kw)
         ref_pose, ref = composed(hsk, room, depth, poses, level, **kw)

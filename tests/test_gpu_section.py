@@ -5,30 +5,23 @@ shown to hold hits, cut outlines and background; a tracker that does not notice 
 frames; the errors; two rooms placed by .xf matrices composited into one floor plan; and what the floor plan of room 0 must
 look like physically."""
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import section_twin as ST
 import view_twin as VT
-from test_gpu_view import RAGGED, SENSOR, assert_trackers_equal, frames_of, moved, scan
-from view_twin import same_bits
+from kit import same_bits_nan
+from section_cases import SCAN_FRAMES, SIDE, SPAN, ortho_cam, room_frames
+from view_cases import RAGGED, SENSOR, assert_trackers_equal, frames_of, moved, scan
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 SIZE, TRUNC = (3.0, 3.0, 3.0), 0.03
-SCAN_FRAMES = 720
-SIDE, SPAN = 200, 3.2                    # the named cameras: 200 x 200 pixels over 3.2 m (62.5 px/m), or a pinhole with f = 180
 KEYS = ("rgb", "depth", "vmap", "nmap")
 
 
 # ---- scans --------------------------------------------------------------------------------------------
-def room_frames(hsk, variant, lo, hi):
-    """frames lo..hi-1 of the scripted scan inside room `variant` (the renderers release the GIL: eight at a time)"""
-    poses = [hsk.synth_room_pose(variant, k, SCAN_FRAMES) for k in range(lo, hi)]
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(lambda p: (hsk.synth_room_depth(variant, p), hsk.synth_rgb(p, variant)), poses))
 
 
 def scan_room(hsk, variant, n):
@@ -68,10 +61,6 @@ def _close_scans():
 
 
 # ---- cameras ------------------------------------------------------------------------------------------
-def ortho_cam(pose, side=SIDE, span=SPAN, width=None, height=None):
-    w, h = width or side, height or side
-    ppm = side / span
-    return dict(width=w, height=h, fx=ppm, fy=ppm, cx=(w - 1) / 2.0, cy=(h - 1) / 2.0, pose=pose, projection=ST.ORTHO)
 
 
 def room_cameras(ext):
@@ -123,8 +112,8 @@ def assert_section(got, ref, what):
     """every pixel of every output and the three counts, zero differences"""
     for key in ("n_hit", "n_cut", "n_uncolored"):
         assert got[key] == ref[key], f"{what}: {key} {got[key]} != {ref[key]}"
-    assert same_bits(got["vmap"], ref["vmap"]), f"{what}: vmap ({(np.isnan(got['vmap'][0]) != np.isnan(ref['vmap'][0])).sum()} hit pixels differ)"
-    assert same_bits(got["nmap"], ref["nmap"]), f"{what}: nmap"
+    assert same_bits_nan(got["vmap"], ref["vmap"]), f"{what}: vmap ({(np.isnan(got['vmap'][0]) != np.isnan(ref['vmap'][0])).sum()} hit pixels differ)"
+    assert same_bits_nan(got["nmap"], ref["nmap"]), f"{what}: nmap"
     bad = np.argwhere(got["depth"] != ref["depth"])
     assert len(bad) == 0, f"{what}: {len(bad)} depth pixels differ, first {bad[:4].tolist()}"
     bad = np.argwhere((got["rgb"] != ref["rgb"]).any(axis=2))
@@ -157,7 +146,7 @@ def test_degenerate_section_is_render_view(hsk, n, color):
             assert a["n_hit"] > 0.2 * cam["width"] * cam["height"], what
             assert (b["n_hit"], b["n_uncolored"], b["n_cut"]) == (a["n_hit"], a["n_uncolored"], 0), what
             for key in KEYS:
-                assert same_bits(a[key], b[key]), f"{what}: {key}"
+                assert same_bits_nan(a[key], b[key]), f"{what}: {key}"
             checked += 1
     assert checked == 4 * len(modes)
     trk.close()
@@ -422,7 +411,7 @@ def test_house_floor_plan_of_two_rooms(hsk):
     for (trk, tsdf, color), M in zip(rooms, xfs):
         rs = products.section_in_room(hs, M)
         rt = ST.in_room(house, M)
-        assert same_bits(ST.from_struct(rs)["pose"], rt["pose"]) and same_bits(np.array(ST.from_struct(rs)["clip"], f32), np.array(rt["clip"], f32))
+        assert same_bits_nan(ST.from_struct(rs)["pose"], rt["pose"]) and same_bits_nan(np.array(ST.from_struct(rs)["clip"], f32), np.array(rt["clip"], f32))
         got = trk.render_section(rs, vmap=True, nmap=True)
         ref = ST.render(tsdf, SIZE, TRUNC, rt, color=color)
         sh = shares(ref)

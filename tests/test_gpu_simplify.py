@@ -13,40 +13,19 @@ import numpy as np
 import pytest
 
 import simplify_twin as ST
-from mesh_twin import mesh_indexed, same_bits, same_normals
-from test_simplify_host import (BOX_DIMS, BOX_SIZE, CLUSTERS, MODES, box_distance, directed_edge_balance, grid, mesh_of, signed_volume, small_cases,
-                                stats_list, twin_of, volume_of)
+from kit import same_bits, volume_ctx
+from mesh_twin import mesh_indexed, same_normals
+from simplify_cases import (BOX_DIMS, BOX_SIZE, CLUSTERS, MODES, box_distance, check, directed_edge_balance, grid, mesh_of, signed_volume, small_cases, stats_list, twin_of, volume_of)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def ctx(hsk, dims, size, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-
-
-def check(trk, tw, c, mode, rgb=False, tag=""):
-    """one call of the context against a twin result: every array and every statistic"""
-    v, f, nrm, col, st = trk.extract_mesh_simplified(cluster_voxels=c, mode=mode, normals=True, rgb=rgb)
-    tag = (tag, c, mode)
-    assert same_bits(v, tw["vertices"]), (tag, len(v), len(tw["vertices"]))
-    assert same_normals(nrm, tw["normals"]), tag
-    assert f.shape == tw["faces"].shape and np.array_equal(f, tw["faces"]), tag
-    want = dict(tw["stats"])
-    if rgb:
-        assert np.array_equal(col, tw["rgb"]), tag
-    else:
-        assert col is None
-        want["n_uncolored"] = 0
-    assert stats_list(st) == stats_list(want), (tag, st, want)
-    return v, f, st
 
 
 # ---- 1. parity with the twin ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["box", "sphere", "two walls", "holes", "exact zeros", "six faces", "blob", "empty", "box with colour"])
 def test_uploaded_volumes_match_the_twin(hsk, oracle, name):
     vol, dims, size, col = small_cases()[name]
-    trk = ctx(hsk, dims, size)
+    trk = volume_ctx(hsk, dims, size)
     try:
         if col is not None:
             trk.enable_color()
@@ -84,7 +63,7 @@ def test_a_scanned_room_matches_the_twin(hsk, oracle, synth_frames):
 # ---- 2. what the rule promises ----------------------------------------------------------------------------------------------------
 def test_a_closed_surface_stays_closed_on_the_device(hsk, oracle):
     vol, dims, size, _ = small_cases()["sphere"]
-    trk = ctx(hsk, dims, size)
+    trk = volume_ctx(hsk, dims, size)
     try:
         trk.upload_tsdf(vol)
         mesh = mesh_of(oracle, "sphere")

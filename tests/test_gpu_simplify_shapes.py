@@ -10,9 +10,9 @@ import pytest
 
 import simplify_cases as SC
 import simplify_twin as ST
-from mesh_twin import mesh_indexed, same_bits, same_normals
-from test_gpu_simplify import check, ctx
-from test_simplify_host import CLUSTERS, MODES, stats_list
+from kit import same_bits, volume_ctx
+from mesh_twin import mesh_indexed, same_normals
+from simplify_cases import CLUSTERS, MODES, check, stats_list
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -20,7 +20,7 @@ f32 = np.float32
 
 def hall_ctx(hsk):
     vol, dims, size, col = SC.shape_cases()["hall"]
-    trk = ctx(hsk, dims, size)
+    trk = volume_ctx(hsk, dims, size)
     try:
         trk.enable_color()
         trk.upload_color(col)
@@ -50,7 +50,7 @@ def test_the_hall_matches_the_twin(hsk, oracle):
 
 def test_the_tall_room_matches_the_twin(hsk, oracle):
     vol, dims, size, _ = SC.shape_cases()["tall"]
-    trk = ctx(hsk, dims, size)
+    trk = volume_ctx(hsk, dims, size)
     try:
         trk.upload_tsdf(vol)
         for c in CLUSTERS:
@@ -64,7 +64,7 @@ def test_the_tall_room_matches_the_twin(hsk, oracle):
 def test_a_scanned_wide_volume_matches_the_twin(hsk, oracle, synth_frames):
     """320 x 48 x 40 over 3 m, four frames integrated at their ground-truth poses (no tracking): the read-out runs on the volume
     with its deferred weights, before any download, the twin on the download afterwards; the volume is what it was"""
-    trk = ctx(hsk, SC.WIDE_DIMS, SC.WIDE_SIZE)
+    trk = volume_ctx(hsk, SC.WIDE_DIMS, SC.WIDE_SIZE)
     try:
         for pose, depth in SC.wide_frames(synth_frames):
             trk.integrate(depth, pose)

@@ -9,23 +9,16 @@ import pytest
 import diff_twin as DT
 import split_cases as SC
 import split_twin as ST
-from test_align_host import same_bits
-from test_split_host import records_as_dicts
+from kit import same_bits, volume_ctx
+from split_cases import records_as_dicts
 
 pytestmark = pytest.mark.gpu
-
-
-def ctx(hsk, dims, size, color=False, **over):
-    trk = hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-    if color:
-        trk.enable_color()
-    return trk
 
 
 def loaded(hsk, key):
     """a context holding the case's volume (and colour volume)"""
     c, col = SC.case_of(key), SC.color_of(key)
-    trk = ctx(hsk, c["dims"], c["size"], color=col is not None)
+    trk = volume_ctx(hsk, c["dims"], c["size"], color=col is not None)
     trk.upload_tsdf(c["vol"])
     if col is not None:
         trk.upload_color(col)
@@ -181,7 +174,7 @@ def test_every_subset_of_the_optional_arrays_gives_the_full_calls_bytes(hsk):
     equal the full call's (an absent array takes no room in the product buffer: the others move up)"""
     key = ("shape", "objects in the small room")
     c = SC.case_of(key)
-    trk, cur = loaded(hsk, key), ctx(hsk, c["dims"], c["size"])
+    trk, cur = loaded(hsk, key), volume_ctx(hsk, c["dims"], c["size"])
     try:
         lib = trk.lib
         recs, _ = split(hsk, trk, c)
@@ -224,7 +217,7 @@ def test_every_subset_of_the_optional_arrays_gives_the_full_calls_bytes(hsk):
 def test_the_context_after_a_removal_equals_a_fresh_one_with_the_same_words(hsk):
     key = ("room", "two boxes")
     c, col = SC.case_of(key), SC.color_of(key)
-    trk, fresh = loaded(hsk, key), ctx(hsk, c["dims"], c["size"], color=True)
+    trk, fresh = loaded(hsk, key), volume_ctx(hsk, c["dims"], c["size"], color=True)
     try:
         split(hsk, trk, c)
         trk.label_components()

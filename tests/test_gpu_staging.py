@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import pack_twin as PT
-from test_gpu_fuse import make_ctx
-from test_gpu_pack import assert_same_image, ctx_fields
+from fuse_cases import make_ctx
+from pack_cases import assert_same_image, ctx_fields
 
 pytestmark = pytest.mark.gpu
 

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_same_bits
+from kit import assert_same_bits
 
 pytestmark = pytest.mark.gpu
 

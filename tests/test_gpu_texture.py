@@ -12,26 +12,12 @@ import pytest
 import simplify_twin as ST
 import texture_cases as TC
 import texture_twin as TT
-from mesh_twin import same_bits
-from test_simplify_host import twin_of
-from test_texture_host import check_failed, check_wall, differing
+from kit import same_bits
+from simplify_cases import twin_of
+from texture_cases import check_failed, check_wall, differing, loaded
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def ctx(hsk, dims, size, **over):
-    return hsk.KinfuTracker(hsk.default_config(dims[2], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], vol_size_m=size, own_z1=dims[2], **over))
-
-
-def loaded(hsk, vol, col, size):
-    Z, Y, X, _ = vol.shape
-    trk = ctx(hsk, (X, Y, Z), size)
-    if col is not None:
-        trk.enable_color()
-        trk.upload_color(col)
-    trk.upload_tsdf(vol)
-    return trk
 
 
 def bake(trk, v, f, **params):

@@ -8,61 +8,16 @@ import numpy as np
 import pytest
 
 import view_twin as VT
-from view_twin import same_bits
+from kit import same_bits_nan
+from view_cases import RAGGED, SENSOR, assert_trackers_equal, frames_of, moved, rot_y, scan
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-SENSOR = dict(width=640, height=480, fx=525.0, fy=525.0, cx=319.5, cy=239.5)
 WIDE = dict(width=800, height=600, fx=400.0, fy=400.0, cx=399.5, cy=299.5)
-RAGGED = dict(width=333, height=217, fx=270.0, fy=270.0, cx=166.0, cy=108.0)
 FULLHD = dict(width=1920, height=1080, fx=1000.0, fy=1000.0, cx=959.5, cy=539.5)
 FREE = dict(width=1280, height=960, fx=1050.0, fy=1050.0, cx=639.5, cy=479.5)
 ONE = dict(width=1, height=1, fx=525.0, fy=525.0, cx=0.0, cy=0.0)
 MODES = (VT.LAMBERT, VT.NORMALS, VT.COLOR, VT.COLOR_LIT)
-
-
-def rot_y(deg):
-    a = np.radians(deg)
-    m = np.eye(4, dtype=f32)
-    m[0, 0] = m[2, 2] = np.cos(a)
-    m[0, 2] = np.sin(a)
-    m[2, 0] = -np.sin(a)
-    return m
-
-
-def moved(pose, deg=15.0, dx=0.3):
-    """`pose` turned about the camera's own y axis, then shifted sideways in the world: a place the stream never visited"""
-    p = (np.asarray(pose, np.float64) @ rot_y(deg).astype(np.float64)).astype(f32)
-    p[0, 3] = f32(p[0, 3] + f32(dx))
-    return p
-
-
-def frames_of(hsk, src, count):
-    """[(depth, rgb)] of the scripted stream ("synth") or of room 0's scan ("room"), and the first pose"""
-    if src == "synth":
-        poses = [hsk.synth_pose(k) for k in range(count)]
-        return [(hsk.synth_depth(p), hsk.synth_rgb(p)) for p in poses], poses[0]
-    poses = [hsk.synth_room_pose(0, k, 720) for k in range(count)]
-    return [(hsk.synth_room_depth(0, p), hsk.synth_rgb(p, 0)) for p in poses], poses[0]
-
-
-def scan(hsk, dims, src, count, color=True, **over):
-    """a tracker that has taken `count` RGB-D frames, pipelined; its last pose"""
-    frames, first = frames_of(hsk, src, count)
-    if src == "room":
-        over["init_pose"] = first
-    trk = hsk.KinfuTracker(n=dims[0], vol_x=dims[0], vol_y=dims[1], vol_z=dims[2], own_z1=dims[2], **over)
-    if color:
-        trk.enable_color()
-    pose = None
-    for i, (d, c) in enumerate(frames):
-        trk.submit_frame_rgbd(d, c) if color else trk.submit_frame(d)
-        if i >= 1:
-            pose, ok = trk.wait_frame()
-            assert ok or i == 1
-    pose, ok = trk.wait_frame()
-    assert ok
-    return trk, pose
 
 
 def reference(oracle, dims, tsdf, color, cam, pose, mode, light, light_in_camera, background):
@@ -76,9 +31,9 @@ def assert_view(got, vm, nm, ref, what):
     assert got["n_hit"] == ref["n_hit"], f"{what}: n_hit {got['n_hit']} != {ref['n_hit']}"
     assert got["n_uncolored"] == ref["n_uncolored"], f"{what}: n_uncolored {got['n_uncolored']} != {ref['n_uncolored']}"
     if "vmap" in got:
-        assert same_bits(got["vmap"], vm), f"{what}: vmap"
+        assert same_bits_nan(got["vmap"], vm), f"{what}: vmap"
     if "nmap" in got:
-        assert same_bits(got["nmap"], nm), f"{what}: nmap"
+        assert same_bits_nan(got["nmap"], nm), f"{what}: nmap"
     bad = np.argwhere(got["depth"] != ref["depth"])
     assert len(bad) == 0, f"{what}: {len(bad)} depth pixels differ, first {bad[:4].tolist()}"
     bad = np.argwhere((got["rgb"] != ref["rgb"]).any(axis=2))
@@ -195,7 +150,7 @@ def test_same_geometry_as_stage_raycast(hsk, n, frames):
         got = trk.render_view(pose=pose, vmap=True, nmap=True)
         assert got["n_hit"] > 0.2 * 640 * 480
         v, nm = trk.raycast(pose)   # (overwrites the tracker's pose and model maps: the stage call)
-        assert same_bits(got["vmap"], v) and same_bits(got["nmap"], nm)
+        assert same_bits_nan(got["vmap"], v) and same_bits_nan(got["nmap"], nm)
         assert got["n_hit"] == (~np.isnan(v[0])).sum()
     trk.close()
 
@@ -225,21 +180,6 @@ def run_pair(hsk, n, frames, with_views, use_graph=0, color=False, resubmit_afte
     return trk, out
 
 
-def assert_trackers_equal(a, ra, b, rb, color):
-    for k, ((pa, oka), (pb, okb)) in enumerate(zip(ra, rb)):
-        assert oka == okb, f"verdict of frame {k}"
-        assert np.array_equal(pa.view(np.uint32), pb.view(np.uint32)), f"pose of frame {k}"
-    a.synchronize()
-    b.synchronize()
-    for level in range(3):
-        for kind in (2, 3):
-            assert same_bits(a.download_map(kind, level), b.download_map(kind, level)), f"model map {kind} level {level}"
-    assert np.array_equal(a.get_pose().view(np.uint32), b.get_pose().view(np.uint32))
-    assert np.array_equal(a.download_tsdf(), b.download_tsdf()), "TSDF"
-    if color:
-        assert np.array_equal(a.download_color(), b.download_color()), "colour volume"
-
-
 @pytest.mark.parametrize("use_graph,color", [(0, False), (2, False), (0, True)])
 def test_tracker_does_not_notice(hsk, use_graph, color):
     """two contexts run the same 30 pipelined frames at 512^3; one renders views in between.  Poses, verdicts, TSDF, colour
@@ -255,7 +195,7 @@ def test_tracker_does_not_notice(hsk, use_graph, color):
 
 def test_tracker_does_not_notice_fuzz(hsk, synth_frames):
     """the same on a stream with garbage and empty frames (test_tracker_fuzz_vs_oracle's, seed 1: lost frames, resets)"""
-    from test_gpu_parity import _random_depth
+    from parity_cases import _random_depth
     rng = np.random.default_rng(2001)
     frames, k = [], 0
     for i in range(14):
@@ -298,7 +238,7 @@ def test_follow_is_the_pose_the_host_would_get(hsk):
         b = trk.render_view(pose=pose, mode=mode, vmap=True, nmap=True, light=(0.2, 0.1, 0.0))
         assert a["n_hit"] == b["n_hit"] > 0.5 * 640 * 480 and a["n_uncolored"] == b["n_uncolored"]
         for key in ("rgb", "depth", "vmap", "nmap"):
-            assert same_bits(a[key], b[key]), (mode, key)
+            assert same_bits_nan(a[key], b[key]), (mode, key)
     # after a tracking loss: the pose hsk_get_pose returns, over the reset volume
     _, ok = trk.process_frame(np.zeros((480, 640), np.uint16))
     assert not ok

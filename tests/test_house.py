@@ -12,7 +12,8 @@ import os
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT
+
 FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "room_corners.json")))
 
 

@@ -4,20 +4,20 @@ for byte on the cases of tests/keytex_cases.py, in both modes; the analytic chec
 projection, the occluder, the hole and the column where two depths meet, the tie, the cameras that must fail --; the empty store;
 hsk_keyframe_wanted; the C layout of the structs; the argument errors that need no device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import keytex_cases as KC
 import keytex_twin as KT
+import kit
 import texture_cases as TC
 import texture_twin as TT
-from test_texture_host import resolved
+from keytex_cases import differing
+from kit import blocked
+from texture_cases import resolved
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (KT.BEST, KT.BLEND)
 
 
@@ -25,9 +25,7 @@ MODES = (KT.BEST, KT.BLEND)
 def harness(tmp_path_factory):
     """hsk_keytex_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program, which is run as a program)"""
-    exe = tmp_path_factory.mktemp("keytex") / "keytex_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "keytex_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("keytex_point", tmp_path_factory.mktemp("keytex"))
     return exe
 
 
@@ -45,14 +43,14 @@ def run_harness(exe, tmp_path, vol, col, size, v, f, kfs, keytex, tex):
                          f32).tobytes())
         o.write(v.tobytes())
         o.write(f.tobytes())
-        o.write(TC.blocked(vol).tobytes())
+        o.write(blocked(vol).tobytes())
         if col is not None:
             o.write(np.ascontiguousarray(col, np.uint8).tobytes())
         for kf in kfs:
             o.write(np.concatenate([kf["pose"][:3, :3].reshape(-1), kf["pose"][:3, 3], kf["intr"]]).astype(f32).tobytes())
             o.write(kf["rgb"].tobytes())
             o.write(kf["depth"].tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     info = [int(x) for x in np.frombuffer(raw, np.uint64, 13)]
     out = dict(info=dict(width=info[0], height=info[1], n_faces_charted=info[2], n_faces_skipped=info[3], n_blocks=info[4:8], n_owned=info[8],
@@ -66,19 +64,6 @@ def run_harness(exe, tmp_path, vol, col, size, v, f, kfs, keytex, tex):
         off += count * np.dtype(dtype).itemsize
     assert off == len(raw)
     return out
-
-
-def differing(got, tw):
-    """the differing bytes of a keyframe bake against the twin's: every output, the charts and both infos"""
-    n = 0
-    for name in ("rgb", "normal_rgb", "mask", "source"):
-        assert got[name].shape == tw[name].shape, (name, got[name].shape, tw[name].shape)
-        n += int((got[name] != tw[name]).sum())
-    n += int((np.ascontiguousarray(got["uv"]).view(np.uint32) != tw["uv"].view(np.uint32)).sum())
-    n += int((np.asarray(got["charts"]).view(np.int32).reshape(-1, 4) != tw["charts"].view(np.int32).reshape(-1, 4)).sum())
-    n += sum(a != b for a, b in zip(TC.info_list(got["info"]), TC.info_list(tw["info"])))
-    n += sum(a != b for a, b in zip(KC.kinfo_list(got["kinfo"]), KC.kinfo_list(tw["kinfo"])))
-    return n
 
 
 def inside_projected(tw):
@@ -262,22 +247,11 @@ def test_keyframe_wanted(hsk):
 
 
 # ---- 4. C layout, Python mirror, errors without a device ---------------------------------------------------------------------------------
-def test_keytex_structs_have_the_c_layout(tmp_path, hsk):
+def test_keytex_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d %d\\n", '
-                   'sizeof(hsk_keytex_params), offsetof(hsk_keytex_params, z_min_m), offsetof(hsk_keytex_params, z_max_m), offsetof(hsk_keytex_params, cos_min), '
-                   'offsetof(hsk_keytex_params, border_px), offsetof(hsk_keytex_params, occlusion_tol_m), offsetof(hsk_keytex_params, blend_floor), '
-                   'offsetof(hsk_keytex_params, fallback_volume), sizeof(hsk_keytex_info), offsetof(hsk_keytex_info, n_keyed), '
-                   'offsetof(hsk_keytex_info, n_pairs_occluded), HSK_TEXEL_KEYFRAME, HSK_KEYTEX_BEST, HSK_KEYTEX_BLEND, HSK_KEYTEX_NONE);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, I = _lib.HskKeytexParams, _lib.HskKeytexInfo
-    assert got == [C.sizeof(P), P.z_min_m.offset, P.z_max_m.offset, P.cos_min.offset, P.border_px.offset, P.occlusion_tol_m.offset, P.blend_floor.offset,
-                   P.fallback_volume.offset, C.sizeof(I), I.n_keyed.offset, I.n_pairs_occluded.offset, hsk.TEXEL_KEYFRAME, hsk.KEYTEX_BEST, hsk.KEYTEX_BLEND,
-                   hsk.KEYTEX_NONE]
-    assert (C.sizeof(P), C.sizeof(I)) == (32, 48) and got[-4:] == [32, 0, 1, 255] == [KT.KEYFRAME, KT.BEST, KT.BLEND, KT.NONE]
+    assert (C.sizeof(P), C.sizeof(I)) == (32, 48) and [hsk.TEXEL_KEYFRAME, hsk.KEYTEX_BEST, hsk.KEYTEX_BLEND, hsk.KEYTEX_NONE] == [
+        _lib.HSK_TEXEL_KEYFRAME, _lib.HSK_KEYTEX_BEST, _lib.HSK_KEYTEX_BLEND, _lib.HSK_KEYTEX_NONE] == [32, 0, 1, 255] == [KT.KEYFRAME, KT.BEST, KT.BLEND, KT.NONE]
     assert tuple(n for n, _ in I._fields_) == hsk.kinfu.KEYTEX_INFO_FIELDS == KT.KINFO_FIELDS
     assert tuple(n for n, _ in P._fields_) == tuple(KT.default_params(0.01))
 

@@ -5,67 +5,24 @@ defaults; the argument errors that need no device; and the properties DESIGN.md 
 accuracy of up and of the walls' direction, floor and ceiling, the hint, what is not found, and hsk_level_config's destination."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
+import kit
 import level_twin as LT
 import np_twin as T
-from test_align_host import same_bits
+from kit import same_bits
+from level_cases import ANGLE_BAR_DEG, jittered, tilted, twin_of
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ANGLE_BAR_DEG = 0.25                  # at that error a 5 m wall strays 22 mm: one cell of a 512-voxel house
-
-_CACHE = {}
-
-
-def tilted(scene, tilt, trunc=0.03):
-    """(volume, points, normals, cell weights, R) of a scene of LT.SCENES under a tilt of LT.TILTS, made once"""
-    key = (scene, tilt, trunc)
-    if key not in _CACHE:
-        dims, size = LT.SCENES[scene]
-        R = LT.TILTS[tilt] if isinstance(tilt, str) else LT.rot(*tilt)
-        _CACHE[key] = LT.scene(dims, size, R, trunc) + (LT.cell_weights(dims, size), R)
-    return _CACHE[key]
-
-
-def twin_of(scene, tilt, **params):
-    key = ("twin", scene, tilt, tuple(sorted(params.items())))
-    if key not in _CACHE:
-        _, ps, ns, w, _ = tilted(scene, tilt)
-        _CACHE[key] = LT.estimate(ps, ns, w, **params)
-    return _CACHE[key]
-
-
-def jittered(n, seed=5):
-    """n points for the stage tests: the tilted scene's cloud repeated with a jitter on points and normals, the edge cases first"""
-    _, ps, ns, _, _ = tilted("80x64x48", "a")
-    eps, ens = LT.edge_cloud()
-    rng = np.random.default_rng(seed)
-    reps = -(-max(n - len(eps), 1) // len(ps))
-    P = np.tile(ps, (reps, 1)) + rng.normal(0, 0.004, (reps * len(ps), 3)).astype(f32)
-    N = np.tile(ns, (reps, 1)) + rng.normal(0, 0.02, (reps * len(ps), 3)).astype(f32)
-    pick = rng.permutation(len(P))[:max(n - len(eps), 0)]
-    return np.concatenate([eps, P[pick]])[:n].astype(f32), np.concatenate([ens, N[pick]])[:n].astype(f32)
 
 
 def upright_words(hsk, up):
     """the 32 words of the hsk_upright a twin's result makes"""
     u = hsk.KinfuTracker._upright_struct(up)
     return np.frombuffer(bytes(u), np.uint32).copy()
-
-
-def assert_same_upright(got, ref, what):
-    for name in ("n_points", "n_invalid", "n_axis", "n_walls", "found"):
-        assert got[name] == ref[name], (what, name, got[name], ref[name])
-    for name in ("level", "box_lo", "box_hi"):
-        assert same_bits(got[name], ref[name]), (what, name, got[name], ref[name])
-    for name in ("floor_m", "ceiling_m"):
-        assert same_bits(f32(got[name]), f32(ref[name])), (what, name, got[name], ref[name])
 
 
 def angles(up, R):
@@ -95,24 +52,9 @@ def test_the_new_symbols_are_bound(hsk):
         assert callable(getattr(hsk.KinfuTracker, name)), name
 
 
-def test_upright_structs_have_the_c_layout(tmp_path, hsk):
+def test_upright_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    fields_p = ("max_tilt_cos", "cone_cos", "wall_sin", "min_fraction", "refits", "flags")
-    fields_u = ("floor_m", "ceiling_m", "box_lo", "box_hi", "n_points", "n_invalid", "n_axis", "n_walls", "found", "pad")
-    args = ["sizeof(hsk_upright_params)"] + [f"offsetof(hsk_upright_params, {f})" for f in fields_p] + ["sizeof(hsk_upright)"] + \
-           [f"offsetof(hsk_upright, {f})" for f in fields_u] + ["(size_t)HSK_UPRIGHT_MAX_POINTS"] + \
-           [f"(size_t)HSK_UPRIGHT_{n}" for n in ("MAX_REFITS", "HIST_BINS", "HEIGHT_BINS", "AXIS_MAX2", "NO_YAW", "UP", "YAW", "FLOOR", "CEILING")]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("' + "%zu " * len(args) + '\\n", ' + ", ".join(args) +
-                   ");return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, U = _lib.HskUprightParams, _lib.HskUpright
-    want = [C.sizeof(P)] + [getattr(P, f).offset for f in fields_p] + [C.sizeof(U)] + [getattr(U, f).offset for f in fields_u] + \
-           [_lib.HSK_UPRIGHT_MAX_POINTS, _lib.HSK_UPRIGHT_MAX_REFITS, _lib.HSK_UPRIGHT_HIST_BINS, _lib.HSK_UPRIGHT_HEIGHT_BINS, _lib.HSK_UPRIGHT_AXIS_MAX2,
-            _lib.HSK_UPRIGHT_NO_YAW, _lib.HSK_UPRIGHT_UP, _lib.HSK_UPRIGHT_YAW, _lib.HSK_UPRIGHT_FLOOR, _lib.HSK_UPRIGHT_CEILING]
-    assert got == want
     assert C.sizeof(P) == 36 and C.sizeof(U) == 128 and P.up_hint.offset == 0 and U.level.offset == 0
     assert (LT.HIST_BINS, LT.H_BINS, LT.UP, LT.YAW, LT.FLOOR, LT.CEILING, LT.NO_YAW) == (1536, 16384, 1, 2, 4, 8, 1)
 
@@ -209,9 +151,7 @@ def test_the_exported_host_steps_equal_the_twin(hsk):
 def harness(tmp_path_factory):
     """the text every lane of the level kernels runs and the host's steps, built for the host with the address and
     undefined-behaviour sanitizers (their runtime linked into the program)"""
-    exe = tmp_path_factory.mktemp("level") / "level_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "level_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("level_point", tmp_path_factory.mktemp("level"))
     return exe
 
 
@@ -221,7 +161,7 @@ def run_harness(hsk, exe, tmp_path, ps, ns, w, **params):
     with open(path, "wb") as f:
         f.write(np.uint32(len(ps)).tobytes() + bytes(p) + np.asarray(w, f32).tobytes())
         f.write(np.ascontiguousarray(np.asarray(ps, f32).reshape(-1, 3).T).tobytes() + np.ascontiguousarray(np.asarray(ns, f32).reshape(-1, 3).T).tobytes())
-    out = subprocess.check_output([str(exe), str(path)], text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    out = kit.run_harness(exe, path, text=True)
     return [line.split() for line in out.strip().splitlines()]
 
 

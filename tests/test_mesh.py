@@ -10,18 +10,7 @@ import struct
 import numpy as np
 import pytest
 
-
-def sphere_volume(n, size, centre, radius, tau, observed=None):
-    """int16 (tsdf, weight) pairs of a solid sphere: negative inside, weight 1 where `observed`"""
-    cell = size / n
-    g = (np.arange(n) + 0.5) * cell
-    z, y, x = np.meshgrid(g, g, g, indexing="ij")
-    d = np.sqrt((x - centre[0]) ** 2 + (y - centre[1]) ** 2 + (z - centre[2]) ** 2) - radius
-    f = np.clip(d / tau, -1, 1)
-    vol = np.zeros((n, n, n, 2), np.int16)
-    vol[..., 0] = np.rint(f * 32767).astype(np.int16)
-    vol[..., 1] = 1 if observed is None else observed.astype(np.int16)
-    return vol
+from mesh_cases import sphere_volume
 
 
 def edge_census(idx):

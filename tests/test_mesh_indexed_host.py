@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 from housescan_amd import _lib, products
-from mesh_twin import mesh_indexed, same_bits
-from test_mesh import sphere_volume
+
+from kit import same_bits
+from mesh_cases import planted_zeros_volume, random_sign_volume, read_ply_indexed, sphere_volume
+from mesh_twin import mesh_indexed
 
 f32 = np.float32
 
@@ -27,31 +29,9 @@ def rough_volume(m, seed=7):
     return vol
 
 
-def random_sign_volume(n, seed=11):
-    """test_mesh's volume of random signs and weights in which every one of the 256 cases occurs (no exact zeros)"""
-    rng = np.random.default_rng(seed)
-    noise = np.zeros((n, n, n, 2), np.int16)
-    noise[..., 0] = rng.integers(1, 32767, (n, n, n)) * rng.choice([-1, 1], (n, n, n))
-    noise[..., 1] = (rng.random((n, n, n)) > 0.02) * rng.integers(1, 100, (n, n, n))
-    return noise
-
-
 def no_zero_sphere(n):
     v = sphere_volume(n, 3.0, np.array([1.4, 1.6, 1.5]), 0.7, 0.12)
     v[..., 0][v[..., 0] == 0] = 1
-    return v
-
-
-def planted_zeros_volume(n, seed=5):
-    """a sphere with exact zeros, 32767s and zero weights planted on and near its surface"""
-    rng = np.random.default_rng(seed)
-    v = sphere_volume(n, 3.0, np.array([1.45, 1.52, 1.57]), 0.8, 0.15)
-    near = np.argwhere(np.abs(v[..., 0]) < 6000)
-    for val, cnt in ((0, 400), (32767, 100)):
-        pick = near[rng.choice(len(near), cnt, replace=False)]
-        v[pick[:, 0], pick[:, 1], pick[:, 2], 0] = val
-    pick = near[rng.choice(len(near), 60, replace=False)]
-    v[pick[:, 0], pick[:, 1], pick[:, 2], 1] = 0
     return v
 
 
@@ -110,24 +90,6 @@ def small_mesh():
     n = np.array([[0, 0, 1], [np.nan, np.nan, np.nan], [0, 0.6, 0.8], [1, 0, 0]], f32)
     c = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255], [10, 20, 30]], np.uint8)
     return v, f, n, c
-
-
-def read_ply_indexed(path):
-    raw = open(path, "rb").read()
-    head, body = raw.split(b"end_header\n", 1)
-    lines = head.decode().split("\n")
-    nv = int([l for l in lines if l.startswith("element vertex")][0].split()[2])
-    nf = int([l for l in lines if l.startswith("element face")][0].split()[2])
-    props = [l.split()[2] for l in lines if l.startswith("property ") and not l.startswith("property list")]
-    dt = np.dtype([(p, "<f4" if p in ("x", "y", "z", "nx", "ny", "nz") else "u1") for p in props])
-    rec = np.frombuffer(body[:nv * dt.itemsize], dt)
-    fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
-    fr = np.frombuffer(body[nv * dt.itemsize:], fdt)
-    assert len(fr) == nf and (fr["n"] == 3).all()
-    v = np.stack([rec["x"], rec["y"], rec["z"]], axis=1) if nv else np.zeros((0, 3), f32)
-    n = np.stack([rec["nx"], rec["ny"], rec["nz"]], axis=1) if "nx" in props else None
-    c = np.stack([rec["red"], rec["green"], rec["blue"]], axis=1) if "red" in props else None
-    return head + b"end_header\n", v, fr["i"].astype(np.int32), n, c
 
 
 @pytest.mark.parametrize("with_n,with_c", [(False, False), (True, False), (False, True), (True, True)])

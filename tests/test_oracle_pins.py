@@ -9,36 +9,21 @@ import numpy as np
 import pytest
 
 import np_twin as T
+from kit import same_bits_nan
+from pins_cases import CX, CY, FX, H, W, small_cfg, small_depth
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kinfu_golden.npz")
-W, H, FX, CX, CY = 160, 120, 131.25, 79.75, 59.75
-
-
-def small_cfg(O, n=32):
-    return O.default_config(n, W=W, H=H, fx=FX, fy=FX, cx=CX, cy=CY)
-
-
-def small_depth(hsk, k):
-    return hsk.synth_depth(hsk.synth_pose(k), W, H, FX, FX, CX, CY)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype.kind == "f":
-        return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.nan_to_num(a).view(np.uint32),
-                                                                          np.nan_to_num(b).view(np.uint32))
-    return np.array_equal(a, b)
 
 
 def test_twin_scale_depth_vmap_nmap_pyrdown(oracle, hsk):
     cfg = small_cfg(oracle)
     d = small_depth(hsk, 5).copy()
     d[10:20, 30:50] = 0
-    assert same_bits(oracle.scale_depth(cfg, d), T.scale_depth(d, FX, FX, CX, CY))
+    assert same_bits_nan(oracle.scale_depth(cfg, d), T.scale_depth(d, FX, FX, CX, CY))
     vm = oracle.vmap(cfg, d)
-    assert same_bits(vm, T.vmap(d, FX, FX, CX, CY))
-    assert same_bits(oracle.nmap(vm), T.nmap(vm))
-    assert same_bits(oracle.pyrdown(d), T.pyrdown(d))
+    assert same_bits_nan(vm, T.vmap(d, FX, FX, CX, CY))
+    assert same_bits_nan(oracle.nmap(vm), T.nmap(vm))
+    assert same_bits_nan(oracle.pyrdown(d), T.pyrdown(d))
 
 
 @pytest.mark.parametrize("n", [24, 40])
@@ -176,15 +161,15 @@ def test_golden_vectors(oracle, hsk):
         poses.append(trk.process(small_depth(hsk, int(k)))[0])
     assert np.array_equal(np.stack(poses).view(np.uint32), g["poses"].view(np.uint32))
     assert np.array_equal(trk.volume()[8:24, 8:24, 8:24], g["tsdf_crop"])
-    assert same_bits(trk.model_map(2, 0)[:, 40:70, 60:100], g["vmap_crop"])
-    assert same_bits(trk.model_map(3, 0)[:, 40:70, 60:100], g["nmap_crop"])
+    assert same_bits_nan(trk.model_map(2, 0)[:, 40:70, 60:100], g["vmap_crop"])
+    assert same_bits_nan(trk.model_map(3, 0)[:, 40:70, 60:100], g["nmap_crop"])
     assert np.array_equal(small_depth(hsk, int(g["frames"][1])), g["depth1"])
     d = small_depth(hsk, 4)
     vm = oracle.vmap(cfg, oracle.bilateral(cfg, d))
     s, _ = oracle.icp_accumulate(cfg, 0, vm, oracle.nmap(vm), trk.model_map(2, 0), trk.model_map(3, 0), poses[-1], poses[-1])
     assert np.array_equal(s.view(np.uint64), g["icp27"].view(np.uint64))
     # vectors added in round 2 (the file is generated by the numpy twin: tests/golden/make_golden.py)
-    assert same_bits(trk.model_map(2, 2), g["vmap2"]) and same_bits(trk.model_map(3, 2), g["nmap2"])
+    assert same_bits_nan(trk.model_map(2, 2), g["vmap2"]) and same_bits_nan(trk.model_map(3, 2), g["nmap2"])
     assert np.array_equal(oracle.bilateral(cfg, small_depth(hsk, int(g["frames"][1]))), g["bilateral1"])
     x6, ok = oracle.icp_solve(g["icp27"])
     assert ok and np.array_equal(x6.view(np.uint32), g["solve6"].view(np.uint32))
@@ -192,7 +177,7 @@ def test_golden_vectors(oracle, hsk):
     _, _, keys, _ = oracle.raycast(cfg, trk.volume(), poses[-1])
     assert np.array_equal(keys[40:70, 60:100], g["keys_crop"])
     pts, total = oracle.extract_cloud(cfg, trk.volume())
-    assert total == int(g["cloud_count"]) and same_bits(pts[:256], g["cloud_head"])
+    assert total == int(g["cloud_count"]) and same_bits_nan(pts[:256], g["cloud_head"])
 
 
 # ---- round 2: every remaining stage has a second, independently written restatement (tests/np_twin.py) ----
@@ -212,7 +197,7 @@ def test_twin_bilateral(oracle, hsk):
     d[rng.random(d.shape) < 0.03] = 0
     d[30:44, 60:90] = 0
     d[0:5, 0:7] = 40000          # beyond the 32767 clamp of the result, at a clipped corner window
-    assert same_bits(oracle.bilateral(cfg, d), T.bilateral(d))
+    assert same_bits_nan(oracle.bilateral(cfg, d), T.bilateral(d))
     ws, wc = hsk.bilateral_tables()
     tws, twc = T.bilateral_tables()
     assert np.array_equal(ws.reshape(13, 13), tws) and np.array_equal(wc, twc)
@@ -227,10 +212,10 @@ def test_twin_resize_and_transform(oracle, hsk):
     pose = hsk.synth_pose(6)
     vo, no = oracle.transform_maps(vm, nm, pose)
     tv, tn = T.transform_maps(vm, nm, pose)
-    assert same_bits(vo, tv) and same_bits(no, tn)
-    assert same_bits(oracle.resize_vmap(vo), T.resize_vmap(vo))
-    assert same_bits(oracle.resize_nmap(no), T.resize_nmap(no))
-    assert same_bits(oracle.resize_nmap(oracle.resize_nmap(no)), T.resize_nmap(T.resize_nmap(no)))
+    assert same_bits_nan(vo, tv) and same_bits_nan(no, tn)
+    assert same_bits_nan(oracle.resize_vmap(vo), T.resize_vmap(vo))
+    assert same_bits_nan(oracle.resize_nmap(no), T.resize_nmap(no))
+    assert same_bits_nan(oracle.resize_nmap(oracle.resize_nmap(no)), T.resize_nmap(T.resize_nmap(no)))
 
 
 def test_twin_sincos_solve_pose_update_gate(oracle, hsk):
@@ -330,7 +315,7 @@ def test_twin_raycast(oracle, hsk, n, slab):
             o = oracle.raycast(cfg, part, pose, zs0=zs0, zo0=zo0, zo1=zo1)
             t = T.raycast(part, (3.0, 3.0, 3.0), 0.03, W, H, FX, FX, CX, CY, pose, Z=n, zs0=zs0, zo0=zo0, zo1=zo1)
         assert np.array_equal(o[2], t[2]), "step keys"
-        assert same_bits(o[0], t[0]) and same_bits(o[1], t[1])
+        assert same_bits_nan(o[0], t[0]) and same_bits_nan(o[1], t[1])
         assert o[3] == t[3] and o[3] > 1000
         assert (o[2] != 0x7FFFFFFF).mean() > (0.2 if slab is None else 0.01)   # a slab ends only the rays that end in it
 
@@ -344,7 +329,7 @@ def test_twin_extract_cloud(oracle, hsk):
         oracle.integrate(cfg, vol, oracle.scale_depth(cfg, d), hsk.synth_pose(k))
     pts, total = oracle.extract_cloud(cfg, vol)
     tp = T.extract_cloud(vol, (3.0, 3.0, 3.0))
-    assert total == len(tp) > 500 and same_bits(pts, tp)
+    assert total == len(tp) > 500 and same_bits_nan(pts, tp)
 
 
 def test_twin_tracker_equals_oracle_tracker(oracle, hsk):
@@ -359,7 +344,7 @@ def test_twin_tracker_equals_oracle_tracker(oracle, hsk):
         assert oko == okt and np.array_equal(po.view(np.uint32), pt.view(np.uint32)), k
     assert np.array_equal(ot.volume(), tt.vol)
     for l in range(3):
-        assert same_bits(ot.model_map(2, l), tt.vmod[l]) and same_bits(ot.model_map(3, l), tt.nmod[l])
+        assert same_bits_nan(ot.model_map(2, l), tt.vmod[l]) and same_bits_nan(ot.model_map(3, l), tt.nmod[l])
     po, oko = ot.process(np.zeros((H, W), np.uint16))
     pt, okt = tt.process(np.zeros((H, W), np.uint16))
     assert not oko and not okt and np.array_equal(po, pt) and not tt.vol.any()
@@ -420,6 +405,6 @@ def test_twin_fuzz_integrate_and_raycast(oracle, hsk, seed):
         o = oracle.raycast(cfg, a, pose)
         t = T.raycast(a, (3.0, 3.0, 3.0), 0.03, W, H, FX, FX, CX, CY, pose)
         assert np.array_equal(o[2], t[2]), "step keys"
-        assert same_bits(o[0], t[0]) and same_bits(o[1], t[1]) and o[3] == t[3]
+        assert same_bits_nan(o[0], t[0]) and same_bits_nan(o[1], t[1]) and o[3] == t[3]
         hits += int((o[2] != 0x7FFFFFFF).sum())
     assert hits > 200

@@ -7,86 +7,22 @@ harness's field on one ragged grid (the two are one relaxation text); hsk_merge_
 defaults; the C layout of the new structs and their Python mirror; the argument errors that need no device.  The scenes and
 constants here are the GPU tests' too."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
 import clearance_twin as CL
+import kit
 import partition_twin as PT
 import reach_twin as RE
-from test_components_host import speckled
-from test_cover_host import carved_volume
-from test_reach_host import (CORNER_DIMS, FREE_WORD, SERPENTINE_DIMS, SOLID_WORD, TILE, WEIGHTS, corridors, serpentine, tile_corner, two_rooms)
-from test_reach_host import run_harness as reach_harness
+from partition_cases import DOOR_THRESHOLD, MIRROR_DIMS, RAGGED, d2_of, mirror_rooms, ragged_case, serpentine_core_d2, twin_partition
+from reach_cases import CORNER_DIMS, SERPENTINE_DIMS, TILE, WEIGHTS, corridors, run_harness as reach_harness, serpentine, tile_corner, two_rooms
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CACHE = {}
-DOOR_THRESHOLD = {(1, 1, 1): 64, (16, 25, 44): 1600}          # the largest D in the door plane of two_rooms(False)
-RAGGED = ((72, 56, 41), (80, 64, 46))
-
-
-def clear_params(weight, scale=16):
-    """the hand-built volumes' clearance parameters: flags 0 and a cap of `scale` times the largest weight"""
-    return dict(weight=tuple(weight), max_d2=scale * max(weight), flags=0)
-
-
-def d2_of(name, vol, weight, scale=16):
-    """the twin's clearance field of a named volume, made once"""
-    key = ("d2", name, tuple(weight), scale)
-    if key not in _CACHE:
-        cp = clear_params(weight, scale)
-        _CACHE[key] = CL.field(vol, cp["weight"], cp["max_d2"], 0)
-    return _CACHE[key]
-
-
-def twin_partition(name, d2, weight, core_d2, min_d2, min_core_voxels, max_cost=RE.MAX_COST):
-    """the twin's partition of a named clearance field, made once per (name, parameters)"""
-    key = ("partition", name, tuple(weight), int(core_d2), int(min_d2), int(min_core_voxels), int(max_cost))
-    if key not in _CACHE:
-        _CACHE[key] = PT.partition(d2, weight, core_d2, min_d2, min_core_voxels, max_cost)
-    return _CACHE[key]
 
 
 # ---- the scenes ----------------------------------------------------------------------------------------------------------------------------
-def ragged(dims):
-    X, Y, Z = dims
-    return np.ascontiguousarray(speckled(carved_volume(), Z)[:Z, :Y, :X])
-
-
-def ragged_case(dims, weight, min_core_voxels):
-    """the speckled carved room cut to dims -> (volume, clearance field, partition parameters as keywords)"""
-    vol = ragged(dims)
-    return vol, d2_of(f"speckled {dims}", vol, weight), dict(core_d2=4 * min(weight), min_d2=min(weight), min_core_voxels=min_core_voxels, max_cost=RE.MAX_COST)
-
-
-MIRROR_DIMS = (67, 16, 12)
-
-
-MIRROR_PAD = 5          # solid planes behind the far wall that make X a multiple of 8, which a context's volume must be
-
-
-def mirror_rooms(pad=0):
-    """odd X, mirror-symmetric about the plane x = 33 OF voxels: two chambers joined by a corridor 4 x 4 voxels wide, which holds
-    no core at core_d2 = 9 min(weight); every passable voxel of the plane is as far from one core as from the other.  `pad` more
-    solid planes behind the far wall change no clearance (flags 0: the border is no obstacle)"""
-    X, Y, Z = MIRROR_DIMS
-    vol = np.zeros((Z, Y, X + pad, 2), np.int16)
-    vol[...] = SOLID_WORD
-    vol[1:Z - 1, 1:Y - 1, 1:25] = FREE_WORD
-    vol[1:Z - 1, 1:Y - 1, X - 25:X - 1] = FREE_WORD
-    vol[4:8, 6:10, 25:X - 25] = FREE_WORD
-    assert np.array_equal(vol[:, :, :X], vol[:, :, :X][:, :, ::-1])
-    return vol
-
-
-def serpentine_core_d2(weight):
-    """a threshold at which only the serpentine's two end chambers -- 10 and 15 voxels deep, the others 13 between two walls --
-    hold a core: 8 voxels from the nearest wall"""
-    return 64 * weight[0]
 
 
 # ---- 1. the door of two rooms --------------------------------------------------------------------------------------------------------------
@@ -225,7 +161,7 @@ def run_harness(exe, tmp_path, d2, weight, core_d2, min_d2, min_core, max_cost, 
         for part in (np.array([X, Y, Z], np.int32), np.array(list(weight) + [core_d2, min_d2, min_core, max_cost, order, radius, len(points)], np.uint32),
                      np.array([x + X * (y + Y * z) for x, y, z in points], np.uint32), np.ascontiguousarray(d2, np.uint32)):
             f.write(np.ascontiguousarray(part).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     counts = dict(zip(("n_cores", "n_kept", "n_passable", "n_rounds", "n_tiles", "n_first"), (int(v) for v in np.frombuffer(raw, np.uint64, 6))))
     if counts["n_kept"] > PT.MAX_ROOMS:
@@ -260,9 +196,7 @@ def test_the_kernels_text_makes_the_twins_partition_on_the_host_in_any_tile_orde
     """hsk_part_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program): the cores by the union-find, rounds of tile relaxations on 64-bit keys, one tile after the other, with the worklist as
     it was filled, reversed and shuffled -- the keys, the roots, the counts and the lookups against the twin, zero differences"""
-    exe = tmp_path / "part_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "part_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("part_point", tmp_path)
     rng = np.random.default_rng(19)
     for name, (d2, weight, core_d2, min_d2, min_core) in host_cases().items():
         p = twin_partition(name, d2, weight, core_d2, min_d2, min_core)
@@ -302,9 +236,7 @@ def test_the_two_harnesses_run_one_relaxation(tmp_path):
     the markers included (a key's G is the reach field's marker)"""
     exes = {}
     for name in ("part_point", "reach_point"):
-        exes[name] = tmp_path / name
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                               "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", name + "_harness.cpp"), "-o", str(exes[name])])
+        exes[name] = kit.build_harness(name, tmp_path)
     dims, weight = (40, 12, 11), (16, 25, 44)
     assert all(t < d < 2 * t for d, t in zip(dims, TILE))
     d2 = np.random.default_rng(23).choice(np.array([0, 1, 3, 50, CL.FAR], np.uint32), dims[::-1], p=[0.25, 0.25, 0.2, 0.15, 0.15])
@@ -356,29 +288,16 @@ def test_default_parameters(hsk):
     hsk._lib.load().hsk_default_partition_params(None, None, None)
 
 
-def test_partition_structs_have_the_c_layout(tmp_path, hsk):
+def test_partition_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
     names = {"hsk_partition_params": (_lib.HskPartitionParams, None), "hsk_room": (_lib.HskRoom, hsk.kinfu.ROOM_DTYPE), "hsk_door": (_lib.HskDoor, hsk.kinfu.DOOR_DTYPE),
              "hsk_partition_stats": (_lib.HskPartitionStats, None)}
-    probes, want = [], []
-    for cname, (cls, dtype) in names.items():
-        probes.append(f"sizeof({cname})")
-        want.append(C.sizeof(cls))
-        for field, _ in cls._fields_:
-            probes.append(f"offsetof({cname}, {field})")
-            want.append(getattr(cls, field).offset)
-            if dtype is not None:
-                assert dtype.fields[field][1] == getattr(cls, field).offset
+    for cls, dtype in names.values():
         if dtype is not None:
+            for field, _ in cls._fields_:
+                assert dtype.fields[field][1] == getattr(cls, field).offset
             assert dtype.itemsize == C.sizeof(cls) and dtype == PT.ROOM_DTYPE or dtype == PT.DOOR_DTYPE
     consts = ["HSK_PARTITION_MAX_ROOMS", "HSK_PARTITION_MAX_RADIUS", "HSK_ROOM_UNASSIGNED", "HSK_ROOM_OUTSIDE", "HSK_ROOM_BLOCKED", "HSK_ROOM_NONE"]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){' +
-                   "".join(f'printf("%llu\\n", (unsigned long long)({e}));' for e in probes + consts) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
-    assert got == want + [getattr(_lib, c) for c in consts]
     assert [C.sizeof(c) for c, _ in names.values()] == [24, 88, 72, 56]
     assert (PT.MAX_ROOMS, PT.MAX_RADIUS, PT.UNASSIGNED, PT.OUTSIDE, PT.BLOCKED, PT.NONE) == tuple(getattr(_lib, c) for c in consts)
     assert (hsk.kinfu.ROOM_UNASSIGNED, hsk.kinfu.ROOM_OUTSIDE, hsk.kinfu.ROOM_BLOCKED, hsk.kinfu.ROOM_NONE) == (PT.UNASSIGNED, PT.OUTSIDE, PT.BLOCKED, PT.NONE)

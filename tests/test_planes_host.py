@@ -5,101 +5,17 @@ the C layout of the new structs and their Python mirror; the argument errors tha
 host detector mixes; write_room_dir with planes found elsewhere."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
+import kit
 import planes_twin as PT
-from test_align_host import same_bits
+from kit import same_bits
+from planes_cases import COS_MIN, DIST_M, assert_scene_bar, odd_cloud, scene_cloud, score_planes_for_tests, twin_scene, twin_wall
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HALF_CELL_M = 0.5 * 3.0 / 80          # half the smallest cell of the 80 x 64 x 48 scene: 18.75 mm
-DIST_M, COS_MIN = 0.02, 0.8660254037844387
-
-_CACHE = {}
-
-
-def scene_cloud():
-    """(volume, points, normals) of the analytic scene at 80 x 64 x 48, made once"""
-    if "scene" not in _CACHE:
-        vol = PT.scene_volume()
-        _CACHE["scene"] = (vol,) + PT.scene_cloud(vol)
-    return _CACHE["scene"]
-
-
-def odd_cloud():
-    """the scene's cloud with the odd points mixed in: NaN and infinite coordinates and normals, a point far away, |x| just
-    either side of 64, a zero normal, a normal that is not a unit vector"""
-    if "odd" not in _CACHE:
-        _, ps, ns = scene_cloud()
-        ps, ns = ps.copy(), ns.copy()
-        below, above = np.nextafter(f32(64), f32(0)), np.nextafter(f32(64), f32(np.inf))
-        ps[5], ps[7, 1], ps[9], ps[11], ps[13, 2], ps[15, 0] = np.nan, np.nan, 1e9, np.inf, -np.inf, -1e30
-        ns[17], ns[19, 2], ns[21, 0], ns[23] = np.nan, np.inf, -np.inf, 0.0
-        ps[25, 0], ps[27, 0], ps[29, 1], ps[31, 2], ps[33, 0], ps[35, 1] = below, above, -below, -above, 64.0, -64.0
-        ns[37] = ns[37] * f32(3.0)
-        ns[39, 1] = 1e30
-        _CACHE["odd"] = (ps, ns)
-    return _CACHE["odd"]
-
-
-def twin_scene():
-    """the twin's detection on the scene (a), made once"""
-    if "twin_scene" not in _CACHE:
-        _, ps, ns = scene_cloud()
-        _CACHE["twin_scene"] = PT.detect(ps, ns)
-    return _CACHE["twin_scene"]
-
-
-def twin_wall():
-    """the thin wall (b) and the twin's detection on it, made once"""
-    if "twin_wall" not in _CACHE:
-        ps, ns, face = PT.thin_wall()
-        _CACHE["twin_wall"] = (ps, ns, face) + PT.detect(ps, ns)
-    return _CACHE["twin_wall"]
-
-
-def score_planes_for_tests(n_planes):
-    """n_planes planes for the scoring tests: the room's faces as the twin found them, then planes of seed points of the odd
-    cloud (some of them invalid: NaN planes), then a NaN plane and an infinite one"""
-    ps, ns = odd_cloud()
-    rec = twin_scene()[0]
-    planes = [r["abcd"] for r in rec]
-    rng = PT.Lcg(11)
-    with np.errstate(all="ignore"):
-        while len(planes) < n_planes:
-            i = rng.next() % 64 if len(planes) % 3 == 0 else rng.next() % len(ps)
-            planes.append(np.append(ns[i], -PT.dot3(*ns[i], *ps[i])).astype(f32))
-    planes = np.array(planes[:n_planes], f32)
-    if n_planes > 2:
-        planes[-1], planes[-2] = np.nan, (np.inf, 0.0, 0.0, 1.0)
-    return planes
-
-
-def assert_scene_bar(rec, what):
-    """(a)'s bar: six planes, each within half the smallest cell of one of the room's faces and within 1 degree of its inward
-    normal, every face once"""
-    faces = PT.room_faces()
-    assert len(rec) == 6, what
-    seen = set()
-    for r in rec:
-        p = r["abcd"].astype(np.float64)
-        assert abs(np.linalg.norm(p[:3]) - 1.0) < 1e-6
-        ang = np.degrees(np.arccos(np.clip(faces[:, :3] @ p[:3], -1.0, 1.0)))
-        i = int(np.argmin(ang))
-        # the plane lies within the bar of the face: the largest distance from it of the face's four corners
-        lo, hi = np.array(AT.ROOM)
-        axis = i // 2
-        at = -faces[i, 3] * faces[i, axis]
-        corners = np.array([[at if c == axis else (lo[c], hi[c])[(k >> (c if c < axis else c - 1)) & 1] for c in range(3)] for k in range(4)])
-        off = np.abs(corners @ p[:3] + p[3]).max()
-        print(f"{what}: plane {r['abcd']} with {r['n_inliers']} points: face {i}, {ang[i]:.4f} degrees, at most {off * 1e3:.3f} mm from it")
-        assert ang[i] <= 1.0 and off <= HALF_CELL_M
-        seen.add(i)
-    assert seen == set(range(6)), what
 
 
 # ---- 1. the kernels' point function, compiled for the host ----------------------------------------------------------------
@@ -107,9 +23,7 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
     """the text every lane of the plane kernels runs, built for the host with the address and undefined-behaviour sanitizers
     (their runtime linked into the program): per plane the inlier count, sum_abs and the ten moments against the twin, zero
     differences; NaN, infinite, far-away points and |x| either side of 64"""
-    exe = tmp_path / "plane_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "plane_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("plane_point", tmp_path)
     ps, ns = odd_cloud()
     n = len(ps)
     planes = score_planes_for_tests(40)
@@ -129,7 +43,7 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
     with open(path, "wb") as f:
         for part in (np.uint32(n), np.uint32(len(planes)), f32(DIST_M), f32(COS_MIN), planes, np.ascontiguousarray(ps.T), np.ascontiguousarray(ns.T), labels):
             f.write(np.ascontiguousarray(part).tobytes())
-    out = subprocess.check_output([str(exe), str(path)], text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    out = kit.run_harness(exe, path, text=True)
     lines = [[int(v) for v in line.split()] for line in out.strip().splitlines()]
     got, got_seeds = lines[:1 + len(planes)], np.array(lines[1 + len(planes):], np.uint32)
     assert got == want, [(g, w) for g, w in zip(got, want) if g != w][:3]
@@ -198,20 +112,9 @@ def test_plane_refit_equals_the_twin_bit_for_bit(hsk):
 
 
 # ---- 3. header, C layout, Python mirror, the errors that need no device -------------------------------------------------------
-def test_plane_structs_have_the_c_layout(tmp_path, hsk):
+def test_plane_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d\\n", '
-                   'sizeof(hsk_plane_params), offsetof(hsk_plane_params, min_fraction), offsetof(hsk_plane_params, max_planes), '
-                   'offsetof(hsk_plane_params, refits), offsetof(hsk_plane_params, seed), sizeof(hsk_plane_record), '
-                   'offsetof(hsk_plane_record, n_inliers), offsetof(hsk_plane_record, sum_abs), (size_t)HSK_PLANE_MAX_POINTS, '
-                   'HSK_PLANE_MAX_PLANES, HSK_PLANE_MAX_HYPOTHESES, HSK_PLANE_MAX_REFITS);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, R = _lib.HskPlaneParams, _lib.HskPlaneRecord
-    assert got == [C.sizeof(P), P.min_fraction.offset, P.max_planes.offset, P.refits.offset, P.seed.offset, C.sizeof(R), R.n_inliers.offset,
-                   R.sum_abs.offset, _lib.HSK_PLANE_MAX_POINTS, _lib.HSK_PLANE_MAX_PLANES, _lib.HSK_PLANE_MAX_HYPOTHESES, _lib.HSK_PLANE_MAX_REFITS]
     assert C.sizeof(P) == 32 and C.sizeof(R) == 32 and hsk.kinfu.PLANE_DTYPE.itemsize == 32 and PT.RECORD_DTYPE == hsk.kinfu.PLANE_DTYPE
 
 

@@ -3,71 +3,20 @@ for the host) against the numpy twin (tests/reloc_twin.py), bit for bit; hsk_ran
 twin; the property DESIGN.md 8g claims for the rule, shown on the twins; the C layout of the new structs and their Python
 mirror; the argument errors that need no device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
-import np_twin as T
+import kit
 import reloc_twin as RT
-from test_align_host import M_TRUE, PERTURBED, TAU, blocked, same_bits, scene
+from align_cases import TAU
+from kit import blocked, same_bits
+from reloc_cases import HALF_CELL_M, ROOM_SIZE, ROOM_TAU, displaced_pair, room_volume, score_cases, thick_wall_volume
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# the room of the relocalisation tests: align_twin's scene at 160 x 128 x 96 over 3 m (three different cells)
-ROOM_DIMS, ROOM_SIZE = (160, 128, 96), (3.0, 3.0, 3.0)
-ROOM_TAU = T.tau_of(ROOM_SIZE, ROOM_DIMS, 0.03)        # 65.6 mm: 2.1 times the largest cell
-HALF_CELL_M = 0.5 * 3.0 / 160                           # half the smallest cell: 9.4 mm
-# (last pose: eye, target; the truth's offset in the last camera's frame: shift, yaw and pitch in degrees)
-DISPLACED = (((2.05, 1.62, 2.13), (1.0, 0.6, 1.2), (0.47, -0.18, 0.34), 33.0, -12.0),
-             ((1.9, 1.5, 0.9), (0.9, 0.7, 1.4), (-0.36, 0.23, -0.45), -37.0, 9.0))
 CAM_L2 = (80, 60, 262.5 / 4, 262.5 / 4, 159.5 / 4, 119.5 / 4)     # level 2 of the 320 x 240 camera of the GPU tests
-
-_CACHE = {}
-
-
-def room_volume():
-    if "room" not in _CACHE:
-        _CACHE["room"] = AT.scene_volume(ROOM_DIMS, ROOM_SIZE, ROOM_TAU)
-    return _CACHE["room"]
-
-
-def displaced_pair(case):
-    eye, target, t, yaw, pitch = DISPLACED[case]
-    last = RT.look_at(eye, target)
-    return last.astype(f32), RT.displaced(last, t, yaw, pitch)
-
-
-def thick_wall_volume():
-    """the 80 x 64 x 48 scene with the four outermost planes in x, which the scene leaves unobserved, observed as solid (-1,
-    weight 1): the scene itself holds no sample F <= -1 (it stops observing a truncation distance behind a surface), a grown
-    volume does"""
-    if "thick" not in _CACHE:
-        vol = scene()[0].copy()
-        assert (vol[:, :, :4, 1] == 0).all()
-        vol[:, :, :4] = (-32767, 1)
-        _CACHE["thick"] = vol
-    return _CACHE["thick"]
-
-
-def score_cases():
-    """(points, {name: pose}) on that volume: the truth, a perturbed pose, one that puts every point outside, one that pushes the
-    cloud half a metre through the walls (points in free space and in unseen voxels) and one that pushes it 0.2 m into the
-    solid wall (points behind a surface)"""
-    _, ps, _ = scene()
-    odd = ps.copy()
-    odd[5], odd[7, 1], odd[9], odd[11], odd[13, 2], odd[15, 0] = np.nan, np.nan, 1e9, np.inf, -np.inf, -1e30
-    away = np.eye(4)
-    away[:3, 3] = (40.0, 0.0, 0.0)
-    push = np.eye(4)
-    push[:3, 3] = (0.5, 0.4, -0.45)
-    wall = np.eye(4)
-    wall[0, 3] = -0.2
-    return odd, {"truth": M_TRUE.astype(f32), "perturbed": PERTURBED, "outside": (away @ M_TRUE).astype(f32), "pushed": (push @ M_TRUE).astype(f32),
-                 "into the wall": (wall @ M_TRUE).astype(f32)}
 
 
 # ---- 1. the kernel's work on one point, compiled for the host ----------------------------------------------------------
@@ -75,9 +24,7 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
     """the text every lane of k_reloc_score runs, built for the host with the address and undefined-behaviour sanitizers (their
     runtime linked into the program): six counts and sum_abs per pose against the twin, zero differences; NaN, infinite and
     far-away points gather inside the volume like any other"""
-    exe = tmp_path / "reloc_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "reloc_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("reloc_point", tmp_path)
     vol = thick_wall_volume()
     ps, cases = score_cases()
     poses = np.stack(list(cases.values()))
@@ -94,7 +41,7 @@ def test_the_kernels_point_function_equals_the_twin_on_the_host(tmp_path):
         for part in (np.array(AT.DST_DIMS, np.int32), np.array(AT.DST_SIZE, f32), np.uint32(len(poses)), np.uint32(len(ps)), poses, blocked(vol),
                      np.ascontiguousarray(ps.T, f32)):
             f.write(np.ascontiguousarray(part).tobytes())
-    out = subprocess.check_output([str(exe), str(path)], text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    out = kit.run_harness(exe, path, text=True)
     got = np.array([[int(v) for v in line.split()] for line in out.strip().splitlines()], np.int64)
     want = np.array([[int(r[c]) for c in RT.CLASSES] + [int(r["sum_abs"])] for r in ref], np.int64)
     assert np.array_equal(got, want), (got, want)
@@ -210,24 +157,9 @@ def test_relocalize_twin_statuses():
 
 
 # ---- 5. header, C layout, Python mirror -----------------------------------------------------------------------------------------
-def test_reloc_structs_have_the_c_layout(tmp_path, hsk):
+def test_reloc_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
-                   '%d %d %d %d %d %d %d\\n", sizeof(hsk_pose_score), offsetof(hsk_pose_score, n_skipped), offsetof(hsk_pose_score, sum_abs), '
-                   'sizeof(hsk_reloc_params), offsetof(hsk_reloc_params, accept_rms_m), offsetof(hsk_reloc_params, align), '
-                   'sizeof(hsk_reloc_stats), offsetof(hsk_reloc_stats, best), offsetof(hsk_reloc_stats, candidate), offsetof(hsk_reloc_stats, score), '
-                   'offsetof(hsk_reloc_stats, align_status), offsetof(hsk_reloc_stats, iterations), offsetof(hsk_reloc_stats, n_used), '
-                   'offsetof(hsk_reloc_stats, rms_m), HSK_LOSS_RESET, HSK_LOSS_HOLD, HSK_RELOC_FOUND, HSK_RELOC_NONE, HSK_RELOC_EMPTY, '
-                   'HSK_RELOC_FINEST, HSK_RELOC_MAX_REFINE);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     S, P, R = _lib.HskPoseScore, _lib.HskRelocParams, _lib.HskRelocStats
-    assert got == [C.sizeof(S), S.n_skipped.offset, S.sum_abs.offset, C.sizeof(P), P.accept_rms_m.offset, P.align.offset, C.sizeof(R), R.best.offset,
-                   R.candidate.offset, R.score.offset, R.align_status.offset, R.iterations.offset, R.n_used.offset, R.rms_m.offset,
-                   _lib.HSK_LOSS_RESET, _lib.HSK_LOSS_HOLD, _lib.HSK_RELOC_FOUND, _lib.HSK_RELOC_NONE, _lib.HSK_RELOC_EMPTY, _lib.HSK_RELOC_FINEST,
-                   _lib.HSK_RELOC_MAX_REFINE]
     assert C.sizeof(S) == 32 and hsk.kinfu.SCORE_DTYPE.itemsize == 32 and RT.SCORE_DTYPE == hsk.kinfu.SCORE_DTYPE
     assert [n for n, _ in S._fields_] == list(RT.CLASSES) + ["sum_abs"]
     assert (_lib.HSK_RELOC_FOUND, _lib.HSK_RELOC_NONE, _lib.HSK_RELOC_EMPTY) == (RT.FOUND, RT.NONE, RT.EMPTY)

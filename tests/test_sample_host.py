@@ -2,19 +2,18 @@
 the mesh, and alignment sample the volume with -- built for the host (tests/sample_harness.cpp) and compared bit for bit with the
 three numpy twins that restate it: np_twin._Grid.trilinear (the raycast), fuse_twin.sample (fusion) and align_twin.probe
 (alignment).  The volume is the alignment tests' scene, 80 x 64 x 48 over 3 m: three different cells, weights 0 present."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_twin as AT
 import fuse_twin as FT
+import kit
 import np_twin as T
-import test_align_host as TA
+from align_cases import M_TRUE, scene
+from kit import blocked
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIMS, SIZE = AT.DST_DIMS, AT.DST_SIZE
 CELL = AT.cells(DIMS, SIZE)
 
@@ -22,8 +21,8 @@ CELL = AT.cells(DIMS, SIZE)
 def points():
     """the point set, [n, 3] binary32: every class the sample treats differently, on every axis"""
     rng = np.random.default_rng(7)
-    vol, ps, ns = TA.scene()
-    M = TA.M_TRUE
+    vol, ps, ns = scene()
+    M = M_TRUE
     surf = (ps.astype(np.float64) @ M[:3, :3].T + M[:3, 3])            # the scene's surfaces, in the volume's coordinates
     dims, cell = np.array(DIMS), np.array([float(c) for c in CELL])
     inner = lambda n: rng.uniform(1.5, dims - 1.5, (n, 3)) * cell      # noqa: E731  (well inside)
@@ -52,7 +51,7 @@ def points():
     return np.concatenate([np.asarray(p, f32) for p in out])
 
 
-def same_bits(a, b):
+def equal_words(a, b):
     """binary32 arrays equal bit for bit, a NaN equal to any NaN"""
     a, b = np.asarray(a, f32), np.asarray(b, f32)
     return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
@@ -62,16 +61,14 @@ def same_bits(a, b):
 def run(tmp_path_factory):
     """(points, the harness's 15 words per point)"""
     tmp = tmp_path_factory.mktemp("sample")
-    exe = tmp / "sample"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "sample_harness.cpp"), "-o", str(exe)])
-    vol = TA.scene()[0]
+    exe = kit.build_harness("sample", tmp)
+    vol = scene()[0]
     p = points()
     with open(tmp / "in.bin", "wb") as f:
-        for part in (np.array(DIMS, np.int32), np.array(SIZE, f32), np.uint32(len(p)), TA.blocked(vol), np.ascontiguousarray(p.T)):
+        for part in (np.array(DIMS, np.int32), np.array(SIZE, f32), np.uint32(len(p)), blocked(vol), np.ascontiguousarray(p.T)):
             f.write(part.tobytes())
     # (a tap outside the volume's array, or undefined behaviour, ends the program with a report and a non-zero status)
-    subprocess.check_call([str(exe), str(tmp / "in.bin"), str(tmp / "out.bin")], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, tmp / "in.bin", tmp / "out.bin")
     out = np.fromfile(tmp / "out.bin", np.int32).reshape(len(p), 15)
     return p, out
 
@@ -80,7 +77,7 @@ def test_the_point_set_holds_every_class(run):
     """counted with the twins' own arithmetic: the containing voxel is fuse_twin's floor, the lower corner follows from its
     clamped voxel and the centre test"""
     p, _ = run
-    vol = TA.scene()[0]
+    vol = scene()[0]
     ok, _, Ws, vox = FT.sample(vol, SIZE, [p[:, i] for i in range(3)])
     assert (ok & (Ws > 0)).sum() > 5000 and (ok & (Ws == 0)).sum() > 500
     for i in range(3):
@@ -104,21 +101,21 @@ def test_the_point_set_holds_every_class(run):
 
 def test_the_sample_equals_the_raycast_twin(run):
     p, out = run
-    vol = TA.scene()[0]
+    vol = scene()[0]
     with np.errstate(all="ignore"):
         ref = T._Grid(vol, SIZE, DIMS[2], 0).trilinear([p[:, i] for i in range(3)])
     got = np.where(out[:, 0] != 0, out[:, 7].view(f32), f32(np.nan))
     assert np.isnan(ref).sum() > 1000 and (~np.isnan(ref)).sum() > 10000
-    assert same_bits(got, ref).all(), np.flatnonzero(~same_bits(got, ref))[:10]
+    assert equal_words(got, ref).all(), np.flatnonzero(~equal_words(got, ref))[:10]
     assert np.array_equal(np.isnan(ref), out[:, 0] == 0)
 
 
 def test_the_sample_equals_the_fusion_twin(run):
     p, out = run
-    vol = TA.scene()[0]
+    vol = scene()[0]
     ok, F, Ws, vox = FT.sample(vol, SIZE, [p[:, i] for i in range(3)])
     assert np.array_equal(ok, out[:, 0] != 0)
-    assert same_bits(out[:, 7].view(f32), F).all()                      # (off the interior too: the clamped cell's blend)
+    assert equal_words(out[:, 7].view(f32), F).all()                      # (off the interior too: the clamped cell's blend)
     assert np.array_equal(out[:, 8], Ws)
     for i in range(3):
         assert np.array_equal(out[:, 1 + i], vox[i]), i
@@ -131,11 +128,11 @@ def test_the_sample_equals_the_fusion_twin(run):
 
 def test_the_sample_equals_the_alignment_twin(run):
     p, out = run
-    vol = TA.scene()[0]
+    vol = scene()[0]
     ok, F, Ws, g = AT.probe(vol, SIZE, [p[:, i] for i in range(3)])
     assert np.array_equal(ok & (Ws > 0), (out[:, 0] != 0) & (out[:, 8] > 0))    # the probe's verdict
     assert np.array_equal(ok, out[:, 0] != 0) and np.array_equal(Ws, out[:, 8])
-    assert same_bits(out[:, 7].view(f32), F).all()
+    assert equal_words(out[:, 7].view(f32), F).all()
     for i in range(3):
-        assert same_bits(out[:, 9 + i].view(f32), g[i]).all(), i
+        assert equal_words(out[:, 9 + i].view(f32), g[i]).all(), i
         assert (np.abs(g[i][ok & (Ws > 0)]) > 0).sum() > 1000, i

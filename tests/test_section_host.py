@@ -10,9 +10,8 @@ import pytest
 
 import section_twin as ST
 import view_twin as VT
-from view_twin import same_bits
+from kit import ROOT, c_values, same_bits_nan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 SIZE, TRUNC = (3.0, 3.0, 3.0), 0.03
 W, H, FX, CX, CY = 160, 120, 131.25, 79.5, 59.5
@@ -41,13 +40,8 @@ def test_symbols_defaults_and_null_checks(hsk):
 def test_section_struct_layout_matches_c(tmp_path, hsk):
     from housescan_amd import _lib
     fields = [n for n, _ in _lib.HskSection._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(){printf("%zu", sizeof(hsk_section));\n'
-                   + "".join('printf(" %%zu", offsetof(hsk_section, %s));\n' % f for f in fields)
-                   + 'printf(" %zu %d %d %d", sizeof(hsk_view), HSK_PROJ_PINHOLE, HSK_PROJ_ORTHO, HSK_MAX_CLIP);printf("\\n");return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    nums = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
+    nums = c_values(tmp_path, ["sizeof(hsk_section)"] + [f"offsetof(hsk_section, {f})" for f in fields] +
+                    ["sizeof(hsk_view)", "HSK_PROJ_PINHOLE", "HSK_PROJ_ORTHO", "HSK_MAX_CLIP"])
     assert nums[0] == C.sizeof(_lib.HskSection)
     assert nums[1:1 + len(fields)] == [getattr(_lib.HskSection, f).offset for f in fields]
     assert nums[1 + len(fields):] == [C.sizeof(_lib.HskView), 0, 1, 4]
@@ -88,7 +82,7 @@ def test_twin_is_pinned_to_the_oracle(hsk, oracle, room_volume):
         ref = VT.shade(vm, nm, pose, mode, light, in_cam, bg, color=col)
         sec = ST.section(W, H, FX, FX, CX, CY, pose, ST.PINHOLE, (), mode, light, in_cam, False, bg)
         got = ST.render(vol, SIZE, TRUNC, sec, color=col)
-        assert same_bits(got["vmap"], vm) and same_bits(got["nmap"], nm), f"frame {k}"
+        assert same_bits_nan(got["vmap"], vm) and same_bits_nan(got["nmap"], nm), f"frame {k}"
         assert np.array_equal(got["rgb"], ref["rgb"]) and np.array_equal(got["depth"], ref["depth"])
         assert (got["n_hit"], got["n_cut"], got["n_uncolored"]) == (ref["n_hit"], 0, ref["n_uncolored"])
 
@@ -245,11 +239,11 @@ def test_section_in_room_against_numpy(hsk):
             sec = house_section(in_cam, directional)
             want = ST.in_room(sec, M)
             got = ST.from_struct(products.section_in_room(ST.to_struct(sec, _lib), M))
-            assert same_bits(got["pose"], want["pose"]), (M, got["pose"], want["pose"])
-            assert same_bits(np.array(got["clip"], f32), np.array(want["clip"], f32))
-            assert same_bits(np.array(got["light"], f32), np.array(want["light"], f32))
+            assert same_bits_nan(got["pose"], want["pose"]), (M, got["pose"], want["pose"])
+            assert same_bits_nan(np.array(got["clip"], f32), np.array(want["clip"], f32))
+            assert same_bits_nan(np.array(got["light"], f32), np.array(want["light"], f32))
             if in_cam:
-                assert same_bits(np.array(got["light"], f32), np.array(sec["light"], f32))
+                assert same_bits_nan(np.array(got["light"], f32), np.array(sec["light"], f32))
             for key in ("width", "height", "fx", "fy", "cx", "cy", "projection", "mode", "light_in_camera", "light_directional",
                         "background", "cut_rgb"):
                 assert got[key] == sec[key], key
@@ -268,7 +262,7 @@ def test_section_in_room_against_numpy(hsk):
     M = rigid(90, (2.6, 0.0, 0.1)).reshape(16)
     mp = M.ctypes.data_as(C.POINTER(C.c_float))
     assert lib.hsk_section_in_room(C.byref(s), mp, C.byref(s)) == 0
-    assert same_bits(ST.from_struct(s)["pose"], ST.in_room(sec, M)["pose"])
+    assert same_bits_nan(ST.from_struct(s)["pose"], ST.in_room(sec, M)["pose"])
     # the three refusals (and NULL pointers)
     s = ST.to_struct(sec, _lib)
     out = _lib.HskSection()

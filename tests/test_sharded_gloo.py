@@ -11,7 +11,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT
+
 N, W, H, FRAMES = 48, 160, 120, 4
 
 

@@ -11,144 +11,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import kit
 import simplify_twin as ST
-from mesh_twin import mesh_indexed, same_bits, same_normals
+from kit import ROOT, same_bits
+from mesh_twin import same_normals
+from simplify_cases import (CLUSTERS, MODES, SMALL_DIMS, SMALL_SIZE, directed_edge_balance, grid, mesh_of, signed_volume, small_cases, sphere_volume, stats_list, twin_of)
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLUSTERS = (2, 4, 8, 16)
-MODES = (ST.QUADRIC, ST.MEAN)
-BOX_DIMS, BOX_SIZE = (72, 40, 24), (2.7, 1.6, 1.2)      # X crosses the indexed mesh's 64-voxel segment; no dim a multiple of 16
-SMALL_DIMS, SMALL_SIZE = (32, 24, 12), (3.0, 3.0, 3.0)  # (anisotropic cells)
-_CACHE = {}
-
-
-def grid(dims):
-    X, Y, Z = dims
-    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
-    return x.astype(np.float64), y.astype(np.float64), z.astype(np.float64)
-
-
-def volume_of(dist_voxels, tau=3.0, weight=3):
-    """a signed distance in voxels (positive: free space) -> [Z, Y, X, 2] int16 (tsdf, weight), every weight non-zero"""
-    t = np.clip(np.rint(dist_voxels / tau * 32767.0), -32767, 32767).astype(np.int16)
-    return np.stack([t, np.full(t.shape, weight, np.int16)], axis=-1)
-
-
-def box_distance(dims, lo, hi):
-    """the free inside of an axis-aligned box room: the distance to the nearest wall, negative in the walls"""
-    x, y, z = grid(dims)
-    return np.minimum.reduce([x - lo[0], hi[0] - x, y - lo[1], hi[1] - y, z - lo[2], hi[2] - z])
-
-
-def box_volume():
-    return volume_of(box_distance(BOX_DIMS, (5.3, 4.7, 3.4), (66.6, 35.2, 20.3)))
-
-
-def sphere_volume():
-    x, y, z = grid((32, 32, 32))
-    return volume_of(np.sqrt((x - 15.3) ** 2 + (y - 16.1) ** 2 + (z - 15.7) ** 2) - 9.4)
-
-
-def two_walls_volume():
-    """free space, one plane of solid voxels at x = 11, free space again: two parallel surfaces one voxel apart"""
-    x, y, z = grid(SMALL_DIMS)
-    t = np.where(x == 11, -6000.0 - 41.0 * y - 13.0 * z, 8000.0 + 37.0 * y + 11.0 * z)
-    return np.stack([t.astype(np.int16), np.full(t.shape, 2, np.int16)], axis=-1)
-
-
-def holes_volume():
-    v = box_volume()
-    rng = np.random.default_rng(1905)
-    v[rng.random(v.shape[:3]) < 0.1, 1] = 0
-    return v
-
-
-def exact_zeros_volume():
-    """stored TSDF exactly 0 on the grid planes x = 12 and x = 20: edges with the ratio exactly 1 (-4000 -> 0) and exactly 0 (0 -> -4000)"""
-    x, _, _ = grid(SMALL_DIMS)
-    t = np.minimum(x - 12.0, 20.0 - x) * 4000.0
-    v = np.stack([t.astype(np.int16), np.full(t.shape, 1, np.int16)], axis=-1)
-    assert (v[..., 0] == 0).sum() == 2 * 24 * 12
-    return v
-
-
-def six_faces_volume():
-    """a tilted plane that meets all six faces of the volume"""
-    x, y, z = grid(SMALL_DIMS)
-    return volume_of((x / 31.0 + y / 23.0 + z / 11.0 - 1.5) * 9.0)
-
-
-def blob_volume():
-    """one solid voxel at (5, 5, 5): the lower corners of its six cut edges are 4 or 5 on every axis -- one cluster at every size"""
-    v = volume_of(np.full(SMALL_DIMS[::-1], 2.0))
-    v[5, 5, 5, 0] = -9000
-    return v
-
-
-def empty_volume():
-    return np.zeros(SMALL_DIMS[::-1] + (2,), np.int16)
-
-
-def box_colour():
-    rng = np.random.default_rng(77)
-    X, Y, Z = BOX_DIMS
-    col = rng.integers(0, 256, (Z, Y, X, 4), dtype=np.uint8)
-    col[..., 3] = np.where(rng.random((Z, Y, X)) < 0.45, 0, 5)
-    col[:, :, :14, 3] = 0                                  # (no colour at all near the wall x = 5.3: uncoloured clusters)
-    return col
-
-
-def small_cases():
-    """{name: (volume, dims, size, colour or None)}: the GPU list's uploaded volumes"""
-    if "cases" not in _CACHE:
-        _CACHE["cases"] = {
-            "box": (box_volume(), BOX_DIMS, BOX_SIZE, None),
-            "sphere": (sphere_volume(), (32, 32, 32), (3.0, 3.0, 3.0), None),
-            "two walls": (two_walls_volume(), SMALL_DIMS, SMALL_SIZE, None),
-            "holes": (holes_volume(), BOX_DIMS, BOX_SIZE, None),
-            "exact zeros": (exact_zeros_volume(), SMALL_DIMS, SMALL_SIZE, None),
-            "six faces": (six_faces_volume(), SMALL_DIMS, SMALL_SIZE, None),
-            "blob": (blob_volume(), SMALL_DIMS, SMALL_SIZE, None),
-            "empty": (empty_volume(), SMALL_DIMS, SMALL_SIZE, None),
-            "box with colour": (box_volume(), BOX_DIMS, BOX_SIZE, box_colour()),
-        }
-    return _CACHE["cases"]
-
-
-def mesh_of(oracle, name):
-    """the indexed mesh of a small case, made once"""
-    if ("mesh", name) not in _CACHE:
-        vol, _, size, col = small_cases()[name]
-        _CACHE[("mesh", name)] = mesh_indexed(vol, *oracle.mc_table(), size=size, col=col, normals=False)
-    return _CACHE[("mesh", name)]
-
-
-def twin_of(oracle, name, c, mode):
-    """the twin's result for a small case, made once and left unchanged"""
-    key = ("twin", name, c, mode)
-    if key not in _CACHE:
-        vol, _, size, col = small_cases()[name]
-        _CACHE[key] = ST.simplify(vol, *oracle.mc_table(), c=c, mode=mode, size=size, col=col, mesh=mesh_of(oracle, name))
-    return _CACHE[key]
-
-
-def directed_edge_balance(faces):
-    """the largest |count(a, b) - count(b, a)| over the directed edges of a face list (0: closed)"""
-    f = np.asarray(faces, np.int64)
-    if not len(f):
-        return 0
-    a = np.concatenate([f[:, 0], f[:, 1], f[:, 2]])
-    b = np.concatenate([f[:, 1], f[:, 2], f[:, 0]])
-    n = int(f.max()) + 1
-    fwd, nf = np.unique(a * n + b, return_counts=True)
-    bwd, nb = np.unique(b * n + a, return_counts=True)
-    return 0 if (np.array_equal(fwd, bwd) and np.array_equal(nf, nb)) else 1 + int(np.setxor1d(fwd, bwd).size)
-
-
-def signed_volume(vertices, faces):
-    v = np.asarray(vertices, np.float64)[np.asarray(faces, np.int64)]
-    return float(np.einsum("ij,ij->i", v[:, 0], np.cross(v[:, 1], v[:, 2])).sum() / 6.0)
 
 
 # ---- 1. the twin pinned by hand -------------------------------------------------------------------------------------------------
@@ -202,7 +71,7 @@ def run_harness(exe, tmp_path, oracle, vol, size, col, c, mode, sv_floor=1e-3):
         f.write(np.ascontiguousarray(words).tobytes())
         if col is not None:
             f.write(np.ascontiguousarray(col, np.uint8).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     n, m = (int(v) for v in np.frombuffer(raw, np.uint64, 2))
     off = 16
@@ -216,17 +85,10 @@ def run_harness(exe, tmp_path, oracle, vol, size, col, c, mode, sv_floor=1e-3):
     return out
 
 
-def stats_list(st):
-    return [st["n_in_vertices"], st["n_in_faces"], st["n_clusters"], st["n_out_vertices"], st["n_out_faces"], st["n_faces_collapsed"]] + st["n_rank"] + \
-        [st["n_clamped"], st["n_uncolored"]]
-
-
 def test_the_kernels_shared_text_equals_the_twin_on_the_host(tmp_path, oracle):
     """hsk_simplify_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program, which is run as a program): every small volume of the GPU list, every cluster size, both modes, zero differences"""
-    exe = tmp_path / "simplify_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "simplify_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("simplify_point", tmp_path)
     for name, (vol, _, size, col) in small_cases().items():
         for c in CLUSTERS:
             for mode in MODES:
@@ -351,20 +213,9 @@ def test_a_closed_surface_stays_closed(oracle):
 
 
 # ---- 5. C layout, Python mirror, errors without a device, the overflow assertion ---------------------------------------------------
-def test_simplify_structs_have_the_c_layout(tmp_path, hsk):
+def test_simplify_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d\\n", '
-                   'sizeof(hsk_simplify_params), offsetof(hsk_simplify_params, mode), offsetof(hsk_simplify_params, sv_floor), '
-                   'sizeof(hsk_simplify_stats), offsetof(hsk_simplify_stats, n_clusters), offsetof(hsk_simplify_stats, n_out_faces), '
-                   'offsetof(hsk_simplify_stats, n_faces_collapsed), offsetof(hsk_simplify_stats, n_rank), offsetof(hsk_simplify_stats, n_clamped), '
-                   'offsetof(hsk_simplify_stats, n_uncolored), HSK_SIMPLIFY_QUADRIC, HSK_SIMPLIFY_MEAN);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, S = _lib.HskSimplifyParams, _lib.HskSimplifyStats
-    assert got == [C.sizeof(P), P.mode.offset, P.sv_floor.offset, C.sizeof(S), S.n_clusters.offset, S.n_out_faces.offset, S.n_faces_collapsed.offset,
-                   S.n_rank.offset, S.n_clamped.offset, S.n_uncolored.offset, _lib.HSK_SIMPLIFY_QUADRIC, _lib.HSK_SIMPLIFY_MEAN]
     assert (C.sizeof(P), C.sizeof(S)) == (12, 96)
     assert (ST.QUADRIC, ST.MEAN) == (hsk.SIMPLIFY_QUADRIC, hsk.SIMPLIFY_MEAN) == (_lib.HSK_SIMPLIFY_QUADRIC, _lib.HSK_SIMPLIFY_MEAN)
     assert tuple(n for n, _ in S._fields_) == hsk.kinfu.SIMPLIFY_STATS_FIELDS

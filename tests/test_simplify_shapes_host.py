@@ -9,8 +9,9 @@ import pytest
 
 import simplify_cases as SC
 import simplify_twin as ST
-from mesh_twin import mesh_indexed, same_bits
-from test_simplify_host import CLUSTERS, MODES
+from kit import same_bits
+from mesh_twin import mesh_indexed
+from simplify_cases import CLUSTERS, MODES
 
 
 def census_of(oracle, name, c):
@@ -83,7 +84,7 @@ def test_the_scanned_wide_volume_leaves_the_first_segment(oracle, synth_frames):
 
 def test_the_census_can_fail(oracle):
     """the counts are not satisfied by anything: the box of tests/test_simplify_host.py, 72 x 40 x 24, meets none of the hall's"""
-    from test_simplify_host import mesh_of, small_cases, twin_of
+    from simplify_cases import mesh_of, small_cases, twin_of
     cs = SC.census(small_cases()["box"][0], mesh_of(oracle, "box"), twin_of(oracle, "box", 2, ST.QUADRIC), 2)
     assert cs["cseg"] == 1 and cs["rows_full"] == cs["rows_gap"] == cs["at_63"] == cs["at_64"] == cs["faces_across"] == 0
     assert cs["rows_1024"] == 0 and not cs["top_partial"] and cs["trip_rows"] == 0

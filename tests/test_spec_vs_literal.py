@@ -14,7 +14,8 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 

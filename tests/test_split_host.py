@@ -3,24 +3,17 @@ numpy twin (tests/split_twin.py) on the volumes the GPU tests use; the twin's ow
 with a box on the floor, against the wall and lifted off it, and the room after their removal; the default
 parameters; the C layout of the new structs and their Python mirror; the refusals that need no device."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import diff_twin as DT
+import kit
 import split_cases as SC
 import split_twin as ST
-from test_align_host import blocked
-from test_diff_host import words_of
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIELDS = ("root", "n_voxels", "sum", "lo", "hi", "contact", "plane_mask", "height_lo", "height_hi")
-
-
-def records_as_dicts(recs):
-    return [{n: (int(c[n]) if np.ndim(c[n]) == 0 else tuple(int(v) for v in c[n])) for n in FIELDS} for c in recs]
+from diff_cases import words_of
+from kit import blocked
+from split_cases import records_as_dicts
 
 
 # ---- 1. the twin's own pins ---------------------------------------------------------------------------------------------------------
@@ -146,7 +139,7 @@ def run_harness(exe, tmp_path, c, rule, roots, mode, halo, fill_weight, color, v
             f.write(np.ascontiguousarray(color).tobytes())
         f.write(np.asarray(voxels, np.int32).tobytes())
         f.write(np.asarray([] if roots is None else roots, np.uint32).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     n, m = X * Y * Z, len(voxels)
     cls = np.frombuffer(raw, np.uint8, n).reshape(Z, Y, X)
@@ -172,9 +165,7 @@ def test_the_kernels_rule_equals_the_twin_on_the_host(tmp_path):
     """hsk_split_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program), splitting and removing sequentially: classes, planes, labels, records in order, the stats, the point query and the
     volume and colour after each removal against the twin, zero differences"""
-    exe = tmp_path / "split_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                           "-static-libasan", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "split_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("split_point", tmp_path)
     keys = [k for k in SC.all_keys() if k[0] != "random" or k[1] in ((72, 56, 40), (80, 64, 41))]
     rng = np.random.default_rng(11)
     for i, key in enumerate(keys):
@@ -244,29 +235,9 @@ def test_split_plane_kinds_on_tilted_normals(hsk):
     assert lib.hsk_split_plane_kinds(pl, 1, u, 0.9, 0.1) == -1 and lib.hsk_split_plane_kinds(pl, 0, u, 0.9, 0.1) == 0
 
 
-def test_split_structs_have_the_c_layout(tmp_path, hsk):
+def test_split_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
-                   '%zu %zu %zu %zu %zu %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\\n", '
-                   'sizeof(hsk_split_plane), offsetof(hsk_split_plane, kind), sizeof(hsk_split_params), offsetof(hsk_split_params, cos_min), '
-                   'offsetof(hsk_split_params, min_voxels), sizeof(hsk_object), offsetof(hsk_object, n_voxels), offsetof(hsk_object, sum), offsetof(hsk_object, lo), '
-                   'offsetof(hsk_object, hi), offsetof(hsk_object, contact), offsetof(hsk_object, plane_mask), offsetof(hsk_object, height_lo), '
-                   'offsetof(hsk_object, height_hi), sizeof(hsk_split_stats), offsetof(hsk_split_stats, n_objects), offsetof(hsk_split_stats, n_edge), '
-                   'offsetof(hsk_split_stats, n_no_normal), offsetof(hsk_split_stats, reused), sizeof(hsk_remove_params), offsetof(hsk_remove_params, fill_weight), '
-                   'sizeof(hsk_remove_stats), offsetof(hsk_remove_stats, n_restored), offsetof(hsk_remove_stats, n_colored), '
-                   'HSK_SPLIT_NONE, HSK_SPLIT_FLOOR, HSK_SPLIT_CEILING, HSK_SPLIT_WALL, HSK_SPLIT_OTHER, HSK_SPLIT_OBJECT, HSK_SPLIT_MINOR, HSK_KIND_FLOOR, '
-                   'HSK_KIND_CEILING, HSK_KIND_WALL, HSK_KIND_OTHER, HSK_REMOVE_ERASE, HSK_REMOVE_RESTORE, HSK_SPLIT_MAX_PLANES, HSK_REMOVE_MAX_OBJECTS);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, S, O, T, R, Q = _lib.HskSplitPlane, _lib.HskSplitParams, _lib.HskObject, _lib.HskSplitStats, _lib.HskRemoveParams, _lib.HskRemoveStats
-    assert got == [C.sizeof(P), P.kind.offset, C.sizeof(S), S.cos_min.offset, S.min_voxels.offset, C.sizeof(O), O.n_voxels.offset, O.sum.offset, O.lo.offset, O.hi.offset,
-                   O.contact.offset, O.plane_mask.offset, O.height_lo.offset, O.height_hi.offset, C.sizeof(T), T.n_objects.offset, T.n_edge.offset, T.n_no_normal.offset,
-                   T.reused.offset, C.sizeof(R), R.fill_weight.offset, C.sizeof(Q), Q.n_restored.offset, Q.n_colored.offset,
-                   _lib.HSK_SPLIT_NONE, _lib.HSK_SPLIT_FLOOR, _lib.HSK_SPLIT_CEILING, _lib.HSK_SPLIT_WALL, _lib.HSK_SPLIT_OTHER, _lib.HSK_SPLIT_OBJECT, _lib.HSK_SPLIT_MINOR,
-                   _lib.HSK_KIND_FLOOR, _lib.HSK_KIND_CEILING, _lib.HSK_KIND_WALL, _lib.HSK_KIND_OTHER, _lib.HSK_REMOVE_ERASE, _lib.HSK_REMOVE_RESTORE,
-                   _lib.HSK_SPLIT_MAX_PLANES, _lib.HSK_REMOVE_MAX_OBJECTS]
     assert (C.sizeof(P), C.sizeof(S), C.sizeof(O), C.sizeof(T), C.sizeof(R), C.sizeof(Q)) == (24, 24, 104, 104, 12, 40)
     K = hsk.kinfu
     assert K.OBJECT_DTYPE == OBJECT_DTYPE and K.OBJECT_DTYPE.itemsize == 104 and [K.OBJECT_DTYPE.fields[n][1] for n, _ in O._fields_] == [getattr(O, n).offset for n, _ in O._fields_]

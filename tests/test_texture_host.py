@@ -6,37 +6,28 @@ writers; the C layout of the structs; the argument errors that need no device.  
 import ctypes as C
 import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import kit
 import simplify_twin as ST
 import texture_cases as TC
 import texture_twin as TT
-from test_simplify_host import twin_of
+from kit import blocked
+from simplify_cases import twin_of
+from texture_cases import check_failed, check_wall, differing, resolved
 
 f32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """hsk_texture_point.h built for the host with the address and undefined-behaviour sanitizers (their runtime linked into the
     program, which is run as a program)"""
-    exe = tmp_path_factory.mktemp("texture") / "texture_point"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-static-libasan",
-                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "texture_point_harness.cpp"), "-o", str(exe)])
+    exe = kit.build_harness("texture_point", tmp_path_factory.mktemp("texture"))
     return exe
-
-
-def resolved(vol, size, texels_per_metre=0.0, atlas_width=0, n_iter=4, f_tol=0.01, max_offset_m=0.0):
-    """the parameters as hsk_bake_texture resolves them: the zeros replaced by the defaults"""
-    Z, Y, X, _ = vol.shape
-    cell = TT.cells((X, Y, Z), size)
-    return (f32(texels_per_metre) if texels_per_metre else f32(1) / min(cell), atlas_width or 1024, n_iter, f32(f_tol),
-            f32(max_offset_m) if max_offset_m else f32(4) * max(cell))
 
 
 def run_harness(exe, tmp_path, vol, col, size, v, f, **params):
@@ -49,10 +40,10 @@ def run_harness(exe, tmp_path, vol, col, size, v, f, **params):
         o.write(np.array(list(size) + [tpm, f_tol, mo], f32).tobytes())
         o.write(v.tobytes())
         o.write(f.tobytes())
-        o.write(TC.blocked(vol).tobytes())
+        o.write(blocked(vol).tobytes())
         if col is not None:
             o.write(np.ascontiguousarray(col, np.uint8).tobytes())
-    subprocess.check_call([str(exe), str(src), str(dst)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    kit.run_harness(exe, src, dst)
     raw = open(dst, "rb").read()
     info = [int(x) for x in np.frombuffer(raw, np.uint64, 13)]
     out = dict(info=dict(width=info[0], height=info[1], n_faces_charted=info[2], n_faces_skipped=info[3], n_blocks=info[4:8], n_owned=info[8],
@@ -67,18 +58,6 @@ def run_harness(exe, tmp_path, vol, col, size, v, f, **params):
         off += count * np.dtype(dtype).itemsize
     assert off == len(raw)
     return out
-
-
-def differing(got, tw, rgb=True):
-    """the differing bytes of a bake against the twin's: every output, the charts and the info"""
-    n = 0
-    for name in ("normal_rgb", "mask") + (("rgb",) if rgb else ()):
-        assert got[name].shape == tw[name].shape, (name, got[name].shape, tw[name].shape)
-        n += int((got[name] != tw[name]).sum())
-    n += int((np.ascontiguousarray(got["uv"]).view(np.uint32) != tw["uv"].view(np.uint32)).sum())
-    n += int((np.asarray(got["charts"]).view(np.int32).reshape(-1, 4) != tw["charts"].view(np.int32).reshape(-1, 4)).sum())
-    n += sum(a != b for a, b in zip(TC.info_list(got["info"]), TC.info_list(tw["info"])))
-    return n
 
 
 def box_meshes(oracle):
@@ -189,17 +168,6 @@ def test_a_mesh_that_needs_too_high_an_atlas_is_refused(hsk):
 
 
 # ---- 3. the analytic wall, and projections that fail ---------------------------------------------------------------------------------
-def check_wall(got):
-    """every texel inside a face is projected, lies within f_tol tau of the wall and has the ramp's colour there within one level:
-    trilinear interpolation of a linear function is exact up to the float rounding and the one rounding to uint8"""
-    inside = (got["mask"] & 3) == 3
-    assert inside.sum() > 1500 and ((got["mask"][inside] & 4) != 0).all()
-    g = got["points"][inside].astype(np.float64) / TC.WALL_CELL - 0.5             # in voxel indices
-    assert np.abs(g[:, 0] - TC.WALL_X).max() <= 0.01 * TC.WALL_TAU_VOXELS
-    want = np.stack([4 * g[:, 1], 8 * g[:, 2], np.full(len(g), 100.0)], axis=1)
-    assert ((got["mask"][inside] & 8) != 0).all() and np.abs(got["rgb"][inside].astype(np.float64) - want).max() <= 1.0
-    # the normal is +x: (255, 128, 128)
-    assert ((got["mask"][inside] & 16) != 0).all() and (got["normal_rgb"][inside] == (255, 128, 128)).all()
 
 
 def test_the_analytic_wall_on_the_host(harness, tmp_path):
@@ -213,20 +181,6 @@ def test_the_analytic_wall_on_the_host(harness, tmp_path):
     # the mesh starts 0.3 voxel off: further than f_tol tau, so the texels moved
     assert 0.3 > 0.01 * TC.WALL_TAU_VOXELS
     assert (np.abs(got["points"][(got["mask"] & 3) == 3][:, 0] - v[0, 0]) > 0.2 * TC.WALL_CELL).all()
-
-
-def check_failed(got, v, colored):
-    """owned texels, none projected, every one at its P0 -- in the mesh's plane -- and, with colour, the ramp there or nothing"""
-    owned = (got["mask"] & 1) != 0
-    assert owned.sum() > 1500 and ((got["mask"][owned] & 4) == 0).all()
-    assert (got["points"][owned][:, 0] == v[0, 0]).all()
-    inside = (got["mask"] & 3) == 3
-    if colored:
-        g = got["points"][inside].astype(np.float64) / TC.WALL_CELL - 0.5
-        want = np.stack([4 * g[:, 1], 8 * g[:, 2], np.full(len(g), 100.0)], axis=1)
-        assert ((got["mask"][inside] & 8) != 0).all() and np.abs(got["rgb"][inside].astype(np.float64) - want).max() <= 1.0
-    else:
-        assert ((got["mask"][owned] & 8) == 0).all() and (got["rgb"] == 0).all()
 
 
 def test_failed_projections_on_the_host(harness, tmp_path):
@@ -339,24 +293,13 @@ def test_textured_ply_files_load(tmp_path, hsk):
 
 
 # ---- 5. C layout, Python mirror, errors without a device ---------------------------------------------------------------------------------
-def test_texture_structs_have_the_c_layout(tmp_path, hsk):
+def test_texture_structs_have_the_c_layout(hsk):
     from housescan_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d %d %d\\n", '
-                   'sizeof(hsk_texture_params), offsetof(hsk_texture_params, atlas_width), offsetof(hsk_texture_params, n_iter), '
-                   'offsetof(hsk_texture_params, f_tol), offsetof(hsk_texture_params, max_offset_m), sizeof(hsk_texture_chart), '
-                   'offsetof(hsk_texture_chart, s), offsetof(hsk_texture_chart, half_rot), sizeof(hsk_texture_info), offsetof(hsk_texture_info, height), '
-                   'offsetof(hsk_texture_info, n_faces_skipped), offsetof(hsk_texture_info, n_blocks), offsetof(hsk_texture_info, n_owned), '
-                   'HSK_TEXEL_OWNED, HSK_TEXEL_INSIDE, HSK_TEXEL_PROJECTED, HSK_TEXEL_COLORED, HSK_TEXEL_NORMAL);return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
     P, Ch, I = _lib.HskTextureParams, _lib.HskTextureChart, _lib.HskTextureInfo
-    assert got == [C.sizeof(P), P.atlas_width.offset, P.n_iter.offset, P.f_tol.offset, P.max_offset_m.offset, C.sizeof(Ch), Ch.s.offset, Ch.half_rot.offset,
-                   C.sizeof(I), I.height.offset, I.n_faces_skipped.offset, I.n_blocks.offset, I.n_owned.offset, hsk.TEXEL_OWNED, hsk.TEXEL_INSIDE,
-                   hsk.TEXEL_PROJECTED, hsk.TEXEL_COLORED, hsk.TEXEL_NORMAL]
     assert (C.sizeof(P), C.sizeof(Ch), C.sizeof(I)) == (20, 16, 104)
-    assert (TT.OWNED, TT.INSIDE, TT.PROJECTED, TT.COLORED, TT.NORMAL) == (1, 2, 4, 8, 16) == tuple(got[-5:])
+    assert (TT.OWNED, TT.INSIDE, TT.PROJECTED, TT.COLORED, TT.NORMAL) == (1, 2, 4, 8, 16) == (
+        hsk.TEXEL_OWNED, hsk.TEXEL_INSIDE, hsk.TEXEL_PROJECTED, hsk.TEXEL_COLORED, hsk.TEXEL_NORMAL) == (
+        _lib.HSK_TEXEL_OWNED, _lib.HSK_TEXEL_INSIDE, _lib.HSK_TEXEL_PROJECTED, _lib.HSK_TEXEL_COLORED, _lib.HSK_TEXEL_NORMAL)
     assert tuple(n for n, _ in I._fields_) == hsk.kinfu.TEXTURE_INFO_FIELDS == TT.INFO_FIELDS
     assert hsk.kinfu.TEXTURE_CHART_DTYPE == TT.CHART_DTYPE and TT.CHART_DTYPE.itemsize == 16
 

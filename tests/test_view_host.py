@@ -3,14 +3,12 @@ numpy restatement of the shading rule (tests/view_twin.py) on volumes the CPU or
 and normal colour have known values."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import view_twin as VT
-from test_oracle_pins import CX, CY, FX, H, W, small_cfg, small_depth
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kit import c_values
+from pins_cases import CX, CY, FX, H, W, small_cfg, small_depth
 
 
 def test_symbols_and_argument_checks(hsk, tmp_path):
@@ -77,12 +75,7 @@ def test_writers_round_trip(hsk, tmp_path):
 def test_view_struct_layout_matches_c(tmp_path, hsk):
     from housescan_amd import _lib
     fields = [n for n, _ in _lib.HskView._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "hskinfu.h"\nint main(){printf("%zu", sizeof(hsk_view));\n'
-                   + "".join('printf(" %%zu", offsetof(hsk_view, %s));\n' % f for f in fields) + 'printf("\\n");return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    nums = list(map(int, subprocess.check_output([str(exe)], text=True).split()))
+    nums = c_values(tmp_path, ["sizeof(hsk_view)"] + [f"offsetof(hsk_view, {f})" for f in fields])
     assert nums[0] == C.sizeof(_lib.HskView)
     assert nums[1:] == [getattr(_lib.HskView, f).offset for f in fields]
 

@@ -4,9 +4,59 @@ tests/test_gpu_texture.py (the kernel): volumes as hsk_download_tsdf hands them 
 import numpy as np
 
 import texture_twin as TT
-from test_simplify_host import BOX_DIMS, BOX_SIZE, grid, small_cases
+from kit import volume_ctx
+from simplify_cases import BOX_DIMS, BOX_SIZE, grid, small_cases
 
 f32 = np.float32
+
+
+def resolved(vol, size, texels_per_metre=0.0, atlas_width=0, n_iter=4, f_tol=0.01, max_offset_m=0.0):
+    """the parameters as hsk_bake_texture resolves them: the zeros replaced by the defaults"""
+    Z, Y, X, _ = vol.shape
+    cell = TT.cells((X, Y, Z), size)
+    return (f32(texels_per_metre) if texels_per_metre else f32(1) / min(cell), atlas_width or 1024, n_iter, f32(f_tol),
+            f32(max_offset_m) if max_offset_m else f32(4) * max(cell))
+
+
+def differing(got, tw, rgb=True):
+    """the differing bytes of a bake against the twin's: every output, the charts and the info"""
+    n = 0
+    for name in ("normal_rgb", "mask") + (("rgb",) if rgb else ()):
+        assert got[name].shape == tw[name].shape, (name, got[name].shape, tw[name].shape)
+        n += int((got[name] != tw[name]).sum())
+    n += int((np.ascontiguousarray(got["uv"]).view(np.uint32) != tw["uv"].view(np.uint32)).sum())
+    n += int((np.asarray(got["charts"]).view(np.int32).reshape(-1, 4) != tw["charts"].view(np.int32).reshape(-1, 4)).sum())
+    n += sum(a != b for a, b in zip(info_list(got["info"]), info_list(tw["info"])))
+    return n
+
+
+def check_wall(got):
+    """every texel inside a face is projected, lies within f_tol tau of the wall and has the ramp's colour there within one level:
+    trilinear interpolation of a linear function is exact up to the float rounding and the one rounding to uint8"""
+    inside = (got["mask"] & 3) == 3
+    assert inside.sum() > 1500 and ((got["mask"][inside] & 4) != 0).all()
+    g = got["points"][inside].astype(np.float64) / WALL_CELL - 0.5             # in voxel indices
+    assert np.abs(g[:, 0] - WALL_X).max() <= 0.01 * WALL_TAU_VOXELS
+    want = np.stack([4 * g[:, 1], 8 * g[:, 2], np.full(len(g), 100.0)], axis=1)
+    assert ((got["mask"][inside] & 8) != 0).all() and np.abs(got["rgb"][inside].astype(np.float64) - want).max() <= 1.0
+    # the normal is +x: (255, 128, 128)
+    assert ((got["mask"][inside] & 16) != 0).all() and (got["normal_rgb"][inside] == (255, 128, 128)).all()
+
+
+def check_failed(got, v, colored):
+    """owned texels, none projected, every one at its P0 -- in the mesh's plane -- and, with colour, the ramp there or nothing"""
+    owned = (got["mask"] & 1) != 0
+    assert owned.sum() > 1500 and ((got["mask"][owned] & 4) == 0).all()
+    assert (got["points"][owned][:, 0] == v[0, 0]).all()
+    inside = (got["mask"] & 3) == 3
+    if colored:
+        g = got["points"][inside].astype(np.float64) / WALL_CELL - 0.5
+        want = np.stack([4 * g[:, 1], 8 * g[:, 2], np.full(len(g), 100.0)], axis=1)
+        assert ((got["mask"][inside] & 8) != 0).all() and np.abs(got["rgb"][inside].astype(np.float64) - want).max() <= 1.0
+    else:
+        assert ((got["mask"][owned] & 8) == 0).all() and (got["rgb"] == 0).all()
+
+
 _CACHE = {}
 
 # ---- the analytic wall: a TSDF exactly linear in x around a wall at voxel coordinate 15.3, a colour ramp ---------------------------
@@ -89,16 +139,6 @@ def box_case():
     return vol, col, size
 
 
-def blocked(vol):
-    """a host volume [Z, Y, X, 2] as the device stores it: 64-B blocks of 4 x-adjacent voxels by 4 planes, the pair in one word"""
-    Z, Y, X, _ = vol.shape
-    out = np.zeros(X * Y * ((Z + 3) & ~3), np.uint32)
-    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
-    idx = ((((z >> 2) * Y + y) * (X // 4) + (x >> 2)) * 16) + (z & 3) * 4 + (x & 3)
-    out[idx.reshape(-1)] = ((vol[..., 0].astype(np.int64) & 0xffff) | ((vol[..., 1].astype(np.int64) & 0xffff) << 16)).reshape(-1)
-    return out
-
-
 def twin_bake(key, vol, col, size, v, f, **params):
     """the twin's bake of a named case, made once and left unchanged"""
     if key not in _CACHE:
@@ -123,3 +163,13 @@ def owner_of_texels(tw):
         assert (sl[mine] == -1).all()                                       # no two faces own one texel
         sl[mine] = i
     return own
+
+
+def loaded(hsk, vol, col, size):
+    Z, Y, X, _ = vol.shape
+    trk = volume_ctx(hsk, (X, Y, Z), size)
+    if col is not None:
+        trk.enable_color()
+        trk.upload_color(col)
+    trk.upload_tsdf(vol)
+    return trk

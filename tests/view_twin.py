@@ -91,11 +91,3 @@ def plane_volume(n=64, cells_in_front=3.5, size=3.0, trunc=0.03):
     vol[..., 0] = np.rint(sd * 32767).astype(np.int16)[:, None, None]
     vol[..., 1] = 1
     return vol
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    if a.dtype.kind == "f":
-        return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.nan_to_num(a).view(np.uint32),
-                                                                          np.nan_to_num(b).view(np.uint32))
-    return np.array_equal(a, b)
