@@ -12,45 +12,14 @@ import pytest
 import fuse_twin as FT
 import section_twin as ST
 import view_twin as VT
-from fuse_cases import HOUSE_DIMS, HOUSE_SIZE, N, PLANE_N, PLANE_TAU, SIZE, _close_scans, general, make_ctx, plane_case, room_scan  # noqa: F401  (the fixture closes the scans)
+from fuse_cases import (HOUSE_DIMS, HOUSE_SIZE, N, PLANE_N, PLANE_TAU, SIZE, _close_scans, assert_fused, assert_nontrivial,  # noqa: F401  (the fixture closes the scans)
+                        empty_like_ctx, general, make_ctx, plane_case, room_scan)
 from kit import same_bits_nan
 from section_cases import SCAN_FRAMES, ortho_cam, room_frames
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 CELL = 3.0 / N
-
-
-def empty_like_ctx(dims, color=True):
-    tsdf = np.zeros((dims[2], dims[1], dims[0], 2), np.int16)
-    return tsdf, (np.zeros((dims[2], dims[1], dims[0], 4), np.uint8) if color else None)
-
-
-def assert_fused(dst, stats, ref_tsdf, ref_color, ref_stats, box, what):
-    """the device against the twin, zero differences"""
-    assert stats["box"] == box, f"{what}: box {stats['box']} != {box}"
-    assert stats["n_fused"] == ref_stats["n_fused"], f"{what}: n_fused {stats['n_fused']} != {ref_stats['n_fused']}"
-    assert stats["n_colored"] == ref_stats["n_colored"], f"{what}: n_colored {stats['n_colored']} != {ref_stats['n_colored']}"
-    got = dst.download_tsdf()
-    bad = np.argwhere((got != ref_tsdf).any(axis=-1))
-    assert len(bad) == 0, (f"{what}: {len(bad)} TSDF pairs differ, first (z, y, x) {bad[:4].tolist()}: "
-                           f"{got[tuple(bad[0])].tolist()} != {ref_tsdf[tuple(bad[0])].tolist()}")
-    if ref_color is not None:
-        gc = dst.download_color()
-        bad = np.argwhere((gc != ref_color).any(axis=-1))
-        assert len(bad) == 0, (f"{what}: {len(bad)} colour voxels differ, first {bad[:4].tolist()}: "
-                               f"{gc[tuple(bad[0])].tolist()} != {ref_color[tuple(bad[0])].tolist()}")
-    assert FT.box_contains(box, ref_stats["box"]), f"{what}: the footprint {box} misses fused voxels {ref_stats['box']}"
-    assert stats["chunks_swept"] <= stats["chunks_total"]
-    assert stats["n_fused"] == 0 or stats["chunks_swept"] > 0, what
-
-
-def assert_nontrivial(ref_tsdf, ref_stats, src_tsdf, what, share=0.05):
-    """the twin's own result: it fused at least 5 % of the source's observed voxels and holds both signs"""
-    observed = int((src_tsdf[..., 1] > 0).sum())
-    assert ref_stats["n_fused"] >= share * observed, f"{what}: the twin fused {ref_stats['n_fused']} of {observed} observed voxels"
-    f = ref_tsdf[..., 0][ref_stats["fused"]]
-    assert (f < 0).any() and (f > 0).any(), f"{what}: the fused TSDF has one sign only"
 
 
 TRANSFORMS = {
