@@ -2,7 +2,7 @@
 // hsk_default_clearance_params, hsk_clearance_d2, hsk_build_clearance, hsk_download_clearance, hsk_clearance_at,
 // hsk_clearance_floor, hsk_release_clearance and the host-only hsk_rank_views_clear.  The field reads the volume as it stands, with
 // NO flush of the deferred weights (as the coverage calls and the components): the rule asks of a weight only whether it is zero
-// and of the TSDF its sign.  It stays on the device (d_clear) while vol_epoch and the 20 device-relevant parameter bytes stand.
+// and of the TSDF its sign.  It stays on the device (clear, a HeldPass) while vol_epoch and the 20 device-relevant parameter bytes stand.
 // Nothing the tracker reads is written; vol_epoch does not move.  The reads of the fields over it (api_reach.hip, api_partition.hip)
 // and the census (api_cover.hip) take from here the box check, the floor map's grid and the point gather (hsk_ctx.h).
 #pragma clang fp contract(off)
@@ -15,15 +15,7 @@
 extern "C" void hsk_default_clearance_params(const hsk_ctx* k, hsk_clearance_params* p) {
   if (!p) return;
   float cell[3];
-  if (k) {
-    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
-  } else {
-    hsk_config c;
-    hsk_default_config(&c, 256);
-    cell[0] = c.vol_size_m[0] / (float)c.vol_x;
-    cell[1] = c.vol_size_m[1] / (float)c.vol_y;
-    cell[2] = c.vol_size_m[2] / (float)c.vol_z;
-  }
+  context_cells(k, cell, nullptr);
   memset(p, 0, sizeof(*p));
   p->flags = HSK_CLEAR_UNKNOWN;
   const float cmin = std::min(cell[0], std::min(cell[1], cell[2]));
@@ -50,6 +42,28 @@ extern "C" uint32_t hsk_clearance_d2(const hsk_clearance_params* p, float metres
   const double q = (double)metres / (double)p->unit_m;
   const double d = std::ceil(q * q);
   return d >= 4294967295.0 ? 0xffffffffu : (uint32_t)d;
+}
+
+void context_cells(const hsk_ctx* k, float cell[3], float* tau) {
+  if (k) {
+    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
+    if (tau) *tau = k->vp.tau;
+    return;
+  }
+  hsk_config c;
+  hsk_default_config(&c, 256);
+  cell[0] = c.vol_size_m[0] / (float)c.vol_x;
+  cell[1] = c.vol_size_m[1] / (float)c.vol_y;
+  cell[2] = c.vol_size_m[2] / (float)c.vol_z;
+  if (tau) *tau = config_tau(&c);
+}
+
+int points_check(hsk_ctx* k, const char* who, const void* xyz, const void* out, size_t n, int radius, int max_radius) {
+  auto bad = [&](const std::string& what) { return fail(k, HSK_ERR_ARG, (who + what).c_str()); };
+  if (n > 0 && (!xyz || !out)) return bad(": null argument");
+  if (n > HSK_CLEAR_MAX_POINTS) return bad(": more than 2^20 points");
+  if (max_radius >= 0 && (radius < 0 || radius > max_radius)) return bad(": radius must lie in 0.." + std::to_string(max_radius));
+  return HSK_OK;
 }
 
 // the parameters a call works with (NULL: the defaults), checked -> the kernels' block
@@ -144,20 +158,17 @@ void clear_key_of(const hsk_clearance_params& p, uint32_t key[5]) {
   key[4] = p.flags;
 }
 
-// the field of the volume as it stands for the checked parameters, in d_clear; *reused: nothing had to be launched
+// the field of the volume as it stands for the checked parameters, in clear's scratch; *reused: nothing had to be launched
 int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, bool* reused) {
   uint32_t key[5];
   clear_key_of(p, key);
-  if (k->d_clear && k->clear_epoch != 0 && k->clear_epoch == k->vol_epoch && memcmp(key, k->clear_key, sizeof(key)) == 0) {
-    *reused = true;
-    return HSK_OK;
-  }
-  *reused = false;
-  k->clear_epoch = 0;
-  int r = ensure_grown(k, &k->d_clear, &k->clear_bytes, clear_layout(k->vp, nullptr, nullptr));
+  *reused = k->clear.stands_for(k, key, sizeof(key));
+  if (*reused) return HSK_OK;
+  k->clear.drop();
+  int r = k->clear.grow(k, clear_layout(k->vp, nullptr, nullptr));
   if (r != HSK_OK) return r;
   ClearBufs b;
-  clear_layout(k->vp, k->d_clear, &b);
+  clear_layout(k->vp, k->clear.buf, &b);
   launch_clear_build(k->stream, k->d_vol, q, b);
   HIPCHK(k, hipGetLastError());
   unsigned long long counts[3];
@@ -166,8 +177,7 @@ int clear_build(hsk_ctx* k, const hsk_clearance_params& p, const ClearGeom& q, b
   HIPCHK(k, hipStreamSynchronize(k->stream));
   HIPCHK(k, hipGetLastError());
   memcpy(k->clear_counts, counts, sizeof(counts));
-  memcpy(k->clear_key, key, sizeof(key));
-  k->clear_epoch = k->vol_epoch;
+  k->clear.stamp(k, key, sizeof(key));
   return HSK_OK;
 }
 
@@ -188,7 +198,7 @@ extern "C" int hsk_build_clearance(hsk_ctx* k, const hsk_clearance_params* param
     st.n_obstacle = k->clear_counts[0];
     st.n_far = k->clear_counts[1];
     st.max_d2_seen = (uint32_t)k->clear_counts[2];
-    st.scratch_bytes = k->clear_bytes;
+    st.scratch_bytes = k->clear.bytes;
     st.reused = reused ? 1 : 0;
     *stats = st;
   }
@@ -210,14 +220,13 @@ extern "C" int hsk_download_clearance(hsk_ctx* k, const hsk_clearance_params* pa
   int r = clear_build(k, p, q, &reused);
   if (r != HSK_OK) return r;
   ClearBufs cb;
-  clear_layout(k->vp, k->d_clear, &cb);
+  clear_layout(k->vp, k->clear.buf, &cb);
   return download_rows(k, cb.field, 4, b, n, d2);
 }
 
 extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, const float* xyz, size_t n, uint32_t* d2) {
   if (!k) return HSK_ERR_ARG;
-  if (n > 0 && (!xyz || !d2)) return fail(k, HSK_ERR_ARG, "hsk_clearance_at: null argument");
-  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_clearance_at: more than 2^20 points");
+  if (int rc = points_check(k, "hsk_clearance_at", xyz, d2, n, 0, -1)) return rc;
   hsk_clearance_params p;
   ClearGeom q;
   if (int rc = clear_check(k, params, "hsk_clearance_at", &p, &q)) return rc;
@@ -228,7 +237,7 @@ extern "C" int hsk_clearance_at(hsk_ctx* k, const hsk_clearance_params* params, 
   int r = clear_build(k, p, q, &reused);
   if (r != HSK_OK) return r;
   ClearBufs cb;
-  clear_layout(k->vp, k->d_clear, &cb);
+  clear_layout(k->vp, k->clear.buf, &cb);
   return gather_points(k, xyz, n, d2, [&](const float* pts, unsigned* out, unsigned char*) { launch_clear_gather(k->stream, cb.field, k->vp, pts, (unsigned)n, out); });
 }
 
@@ -268,15 +277,8 @@ extern "C" int hsk_clearance_floor(hsk_ctx* k, const hsk_clearance_params* param
 
 extern "C" int hsk_release_clearance(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
-  if (k->d_clear) {
-    HIPCHK(k, hipSetDevice(k->cfg.device_id));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipFree(k->d_clear));
-  }
-  k->d_clear = nullptr;
-  k->clear_bytes = 0;
-  k->clear_epoch = 0;
-  return HSK_OK;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  return k->clear.release(k);
 }
 
 extern "C" int hsk_rank_views_clear(const hsk_view_score* s, const uint32_t* eye_d2, uint32_t min_d2, size_t n, uint32_t* order) {

@@ -2,7 +2,7 @@
 // rule): hsk_default_prune_params, hsk_label_components, hsk_download_components, hsk_prune_components.  Labelling reads the
 // volume as it stands, with NO flush of the deferred weights (as the coverage calls, api_cover.hip): the rule asks of a weight
 // only whether it is zero and of the TSDF its sign -- no deferred weight is zero in the volume's own copy, and the TSDF values
-// are current.  The labelling stays on the device (d_comp) with its records on the host (comp_recs) while vol_epoch stands.
+// are current.  The labelling stays on the device (comp, a HeldPass) with its records on the host (comp_recs) while vol_epoch stands.
 // Pruning writes the volume in api_volume.hip's pattern: flush the deferred weights, write, volume_replaced.
 #pragma clang fp contract(off)
 #include <algorithm>
@@ -15,17 +15,7 @@
 extern "C" void hsk_default_prune_params(const hsk_ctx* k, hsk_prune_params* p) {
   if (!p) return;
   float tau, cell[3];
-  if (k) {
-    tau = k->vp.tau;
-    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
-  } else {
-    hsk_config c;
-    hsk_default_config(&c, 256);
-    tau = config_tau(&c);
-    cell[0] = c.vol_size_m[0] / (float)c.vol_x;
-    cell[1] = c.vol_size_m[1] / (float)c.vol_y;
-    cell[2] = c.vol_size_m[2] / (float)c.vol_z;
-  }
+  context_cells(k, cell, &tau);
   memset(p, 0, sizeof(*p));
   // the voxels of a cube of edge 4 tau, in binary64 from the binary32 fields
   const double e = 4.0 * (double)tau;
@@ -44,89 +34,83 @@ int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want) {
   return HSK_OK;
 }
 
-// d_comp_tab for n components: the roots, the records' eight words each, the survivors of a keep_largest prune
-struct CompTab {
-  size_t bytes;
-  unsigned *roots, *table, *keep;
-};
-static CompTab comp_tab(const hsk_ctx* k, size_t n) {
+RegionTab region_tab(const HeldPass& pass, size_t n, size_t extra_bytes) {
   ProductLayout l;
-  char* base = (char*)k->d_comp_tab;
-  CompTab t;
-  const size_t roots_at = l.take(n * 4), table_at = l.take(n * 32), keep_at = l.take(4096 * 4);
+  char* base = (char*)pass.tab;
+  RegionTab t;
+  const size_t roots_at = l.take(n * 4), table_at = l.take(n * 32), extra_at = l.take(extra_bytes);
   t.roots = (unsigned*)(base + roots_at);
   t.table = (unsigned*)(base + table_at);
-  t.keep = (unsigned*)(base + keep_at);
+  t.extra = (unsigned*)(base + extra_at);
   t.bytes = l.bytes;
   return t;
 }
 
-// The labelling of the volume as it stands: the parents in d_comp; with at most 2^24 components their records in comp_recs, in
-// their order, and the labelling kept for later calls.  *n: the components; *reused: nothing had to be launched.
+int region_read(hsk_ctx* k, const CompBufs& b, HeldPass* pass, size_t extra_words, size_t tail_bytes, const char* too_many, const char* no_memory,
+                void* minor_cls, uint64_t min_voxels, const std::function<void(const RegionTab&, unsigned)>& extra, RegionRead* r) {
+  int rc = copy_out(k, &r->n, b.counts + 4, sizeof(r->n));
+  if (rc != HSK_OK) return rc;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  const size_t n = r->n;
+  if (n > HSK_COMPONENT_MAX) return too_many ? fail(k, HSK_ERR_ARG, too_many) : HSK_OK;
+  try {
+    r->roots.resize(n);
+    r->table.resize(n * 8);
+    r->extra.resize(n * extra_words);
+  } catch (const std::bad_alloc&) {
+    return fail(k, HSK_ERR_STATE, no_memory);
+  }
+  if (n == 0) return HSK_OK;
+  const size_t extra_bytes = n * extra_words * 4 + tail_bytes;
+  rc = pass->grow_tab(k, region_tab(*pass, n, extra_bytes).bytes);
+  if (rc != HSK_OK) return rc;
+  const RegionTab t = region_tab(*pass, n, extra_bytes);
+  launch_comp_records(k->stream, k->vp, b, r->n, t.roots, t.table);
+  if (minor_cls) {  // the words of a region below min_voxels keep their class in the weight half and stop being members
+    const unsigned below = min_voxels > 0xffffffffull ? 0xffffffffu : (unsigned)min_voxels;  // (no region has 2^32 voxels)
+    launch_comp_prune(k->stream, minor_cls, nullptr, k->vp, b.parent, t.roots, t.table, r->n, below, t.roots, 0u, true);
+  }
+  if (extra) extra(t, r->n);
+  HIPCHK(k, hipGetLastError());
+  rc = copy_out(k, r->roots.data(), t.roots, n * 4);
+  if (rc == HSK_OK) rc = copy_out(k, r->table.data(), t.table, n * 32);
+  if (rc == HSK_OK && extra_words) rc = copy_out(k, r->extra.data(), t.extra, n * extra_words * 4);
+  if (rc != HSK_OK) return rc;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  return HSK_OK;
+}
+
+// The labelling of the volume as it stands: the parents in comp's scratch; with at most 2^24 components their records in
+// comp_recs, in their order, and the labelling kept for later calls.  *n: the components; *reused: nothing had to be launched.
 static int comp_label(hsk_ctx* k, size_t* n, bool* reused) {
-  if (k->comp_epoch != 0 && k->comp_epoch == k->vol_epoch) {
+  *reused = k->comp.stands(k);
+  if (*reused) {
     *n = k->comp_recs.size();
-    *reused = true;
     return HSK_OK;
   }
-  *reused = false;
-  k->comp_epoch = 0;
-  int r = ensure_grown(k, &k->d_comp, &k->comp_bytes, comp_layout(k->vp, nullptr, nullptr));
+  k->comp.drop();
+  int r = k->comp.grow(k, comp_layout(k->vp, nullptr, nullptr));
   if (r != HSK_OK) return r;
   CompBufs b;
-  comp_layout(k->vp, k->d_comp, &b);
+  comp_layout(k->vp, k->comp.buf, &b);
   launch_comp_label(k->stream, k->d_vol, k->vp, b);
   HIPCHK(k, hipGetLastError());
-  unsigned n_roots = 0;
-  HIPCHK(k, hipMemcpyAsync(&n_roots, b.counts + 4, sizeof(n_roots), hipMemcpyDeviceToHost, k->stream));
-  HIPCHK(k, hipStreamSynchronize(k->stream));
-  *n = n_roots;
-  if ((size_t)n_roots > HSK_COMPONENT_MAX) {  // labelled, but no records: the callers refuse; nothing is kept for a later call
-    k->comp_recs.clear();
-    k->comp_inside = 0;
-    return HSK_OK;
-  }
-  std::vector<unsigned> roots, table;
+  RegionRead rr;
+  k->comp_recs.clear();
+  k->comp_inside = 0;
+  r = region_read(k, b, &k->comp, 0, 4096 * 4, nullptr, "surface components: out of host memory for the records", nullptr, 0, nullptr, &rr);
+  *n = rr.n;
+  if (r != HSK_OK || rr.n > HSK_COMPONENT_MAX) return r;  // (labelled, but no records: the callers refuse; nothing is kept for a later call)
+  const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
   try {
-    k->comp_recs.assign(n_roots, hsk_component{});
-    roots.resize(n_roots);
-    table.resize((size_t)n_roots * 8);
+    comp_region_records(g, rr.roots.data(), rr.table.data(), rr.n, 0, &k->comp_recs, [&](const hsk_component& c, size_t) { k->comp_inside += c.n_voxels; });
   } catch (const std::bad_alloc&) {
     k->comp_recs.clear();
     return fail(k, HSK_ERR_STATE, "surface components: out of host memory for the records");
   }
-  k->comp_inside = 0;
-  if (n_roots > 0) {
-    r = ensure_grown(k, &k->d_comp_tab, &k->comp_tab_bytes, comp_tab(k, n_roots).bytes);
-    if (r != HSK_OK) return r;
-    const CompTab t = comp_tab(k, n_roots);
-    launch_comp_records(k->stream, k->vp, b, n_roots, t.roots, t.table);
-    HIPCHK(k, hipGetLastError());
-    r = copy_out(k, roots.data(), t.roots, (size_t)n_roots * 4);
-    if (r == HSK_OK) r = copy_out(k, table.data(), t.table, (size_t)n_roots * 32);
-    if (r != HSK_OK) return r;
-    const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
-    for (size_t i = 0; i < n_roots; ++i) {
-      hsk_component& c = k->comp_recs[i];
-      unsigned x, y, z;
-      g.xyz(roots[i], x, y, z);
-      c.root[0] = (int32_t)x;
-      c.root[1] = (int32_t)y;
-      c.root[2] = (int32_t)z;
-      const unsigned* t8 = &table[i * 8];
-      c.n_voxels = t8[0];
-      for (int a = 0; a < 3; ++a) {
-        c.lo[a] = (int32_t)t8[1 + a];
-        c.hi[a] = (int32_t)t8[4 + a];
-      }
-      k->comp_inside += t8[0];
-    }
-    std::sort(k->comp_recs.begin(), k->comp_recs.end(), [&](const hsk_component& a, const hsk_component& c) {
-      return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
-                                g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
-    });
-  }
-  k->comp_epoch = k->vol_epoch;
+  k->comp.stamp(k);
   return HSK_OK;
 }
 
@@ -153,10 +137,7 @@ extern "C" int hsk_label_components(hsk_ctx* k, hsk_component* recs, size_t cap,
   st.largest = n > 0 ? k->comp_recs[0].n_voxels : 0;
   st.labels_reused = reused ? 1 : 0;
   if (stats) *stats = st;
-  if (!recs) return HSK_OK;
-  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_label_components: cap is below the number of components");
-  if (n > 0) memcpy(recs, k->comp_recs.data(), n * sizeof(hsk_component));
-  return HSK_OK;
+  return reply_records(k, k->comp_recs, recs, cap, n_components, "hsk_label_components: cap is below the number of components");
 }
 
 extern "C" int hsk_download_components(hsk_ctx* k, uint32_t* labels) {
@@ -173,7 +154,7 @@ extern "C" int hsk_download_components(hsk_ctx* k, uint32_t* labels) {
   r = ensure_product_bytes(k, bytes);
   if (r != HSK_OK) return r;
   CompBufs b;
-  comp_layout(k->vp, k->d_comp, &b);
+  comp_layout(k->vp, k->comp.buf, &b);
   launch_vol_to_linear(k->stream, b.parent, k->vp, 0, k->vp.Z, k->d_out);
   HIPCHK(k, hipGetLastError());
   return copy_out(k, labels, k->d_out, bytes);
@@ -209,9 +190,9 @@ extern "C" int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, 
     if (stats) *stats = st;
     return HSK_OK;
   }
-  const CompTab t = comp_tab(k, n);
+  const RegionTab t = region_tab(k->comp, n, 4096 * 4);  // (extra: the keep slots)
   CompBufs b;
-  comp_layout(k->vp, k->d_comp, &b);
+  comp_layout(k->vp, k->comp.buf, &b);
   unsigned keep[4096];
   if (n_keep > 0) {  // the surviving roots, ascending, handed up
     const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
@@ -220,18 +201,15 @@ extern "C" int hsk_prune_components(hsk_ctx* k, const hsk_prune_params* params, 
       keep[i] = g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]);
     }
     std::sort(keep, keep + n_keep);
-    HIPCHK(k, hipMemcpyAsync(t.keep, keep, n_keep * 4, hipMemcpyHostToDevice, k->stream));
+    HIPCHK(k, hipMemcpyAsync(t.extra, keep, n_keep * 4, hipMemcpyHostToDevice, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));  // (`keep` is this frame's)
   }
-  flush_weights(k);  // the words that stay are to hold their weights
   const unsigned min_voxels = p.min_voxels > 0xffffffffull ? 0xffffffffu : (unsigned)p.min_voxels;  // (no component has 2^32 voxels)
-  launch_comp_prune(k->stream, k->d_vol, k->d_color, k->vp, b.parent, t.roots, t.table, (unsigned)n, min_voxels, t.keep, (unsigned)n_keep,
-                    p.fill == HSK_PRUNE_FREE);
-  HIPCHK(k, hipGetLastError());
-  r = volume_replaced(k);
+  r = commit_volume_write(k, [&] {
+    launch_comp_prune(k->stream, k->d_vol, k->d_color, k->vp, b.parent, t.roots, t.table, (unsigned)n, min_voxels, t.extra, (unsigned)n_keep,
+                      p.fill == HSK_PRUNE_FREE);
+  });
   if (r != HSK_OK) return r;
-  HIPCHK(k, hipStreamSynchronize(k->stream));
-  HIPCHK(k, hipGetLastError());
   if (stats) *stats = st;
   return HSK_OK;
 }

@@ -2,8 +2,8 @@
 // rule): hsk_default_diff_params, hsk_diff_volume, hsk_download_diff, hsk_diff_at, hsk_adopt_diff, hsk_release_diff.  The rule
 // compares weights with min_weight, so both contexts' deferred weights are written back first (as hsk_fuse_volume does; that
 // changes nothing either context returns).  The regions are components.hip's labelling run on the class words, in a scratch of
-// the diff's own (d_diff): hsk_label_components' cached labelling (d_comp, comp_epoch) is neither read nor written.  The diff
-// stays on the device with its records and stats on the host while the three parts of diff_key stand; a call with the same cur
+// the diff's own (diff, a HeldPass): hsk_label_components' cached labelling (comp) is neither read nor written.  The diff
+// stays on the device with its records and stats on the host while ref's volume and its key stand; a call with the same cur
 // and parameters meanwhile is answered from them.  Adopting writes the volume in
 // hsk_prune_components' order: flush the deferred weights, write, volume_replaced.
 #pragma clang fp contract(off)
@@ -31,39 +31,28 @@ extern "C" void hsk_default_diff_params(const hsk_ctx* k, hsk_diff_params* p) {
   p->min_voxels = pp.min_voxels;
 }
 
-// a diff is held for ref's volume as it stands
-static int diff_held_check(hsk_ctx* ref, const char* who) {
-  if (!ref->d_diff || ref->diff_key[0] == 0 || ref->diff_key[0] != ref->vol_epoch)
-    return fail(ref, HSK_ERR_STATE, (std::string(who) + ": no diff is held for the volume as it stands").c_str());
-  return HSK_OK;
-}
+#define DIFF_NOT_HELD ": no diff is held for the volume as it stands"
 
-// d_diff_tab for n regions: the roots, the records' eight words each, the two class counts each
-struct DiffTab {
-  size_t bytes;
-  unsigned *roots, *table, *av;
+// the diff's key: cur's serial and cur's epoch (hsk_adopt_diff compares these two alone), then the zero-padded parameters
+struct DiffKey {
+  uint64_t cur[2];
+  hsk_diff_params p;
 };
-static DiffTab diff_tab(const hsk_ctx* k, size_t n) {
-  ProductLayout l;
-  char* base = (char*)k->d_diff_tab;
-  DiffTab t;
-  const size_t roots_at = l.take(n * 4), table_at = l.take(n * 32), av_at = l.take(n * 8);
-  t.roots = (unsigned*)(base + roots_at);
-  t.table = (unsigned*)(base + table_at);
-  t.av = (unsigned*)(base + av_at);
-  t.bytes = l.bytes;
-  return t;
+static DiffKey diff_key_of(const hsk_ctx* cur, const hsk_diff_params& p) {
+  DiffKey key;
+  memset(&key, 0, sizeof(key));  // (compared as bytes: the padding, if any, is zero on both sides)
+  key.cur[0] = cur->serial;
+  key.cur[1] = cur->vol_epoch;
+  key.p.thresh = p.thresh;
+  key.p.min_weight = p.min_weight;
+  key.p.min_voxels = p.min_voxels;
+  return key;
 }
 
 // hsk_diff_volume's answer from the held records and stats
 static int diff_reply(hsk_ctx* k, hsk_diff_region* recs, size_t cap, size_t* n_regions, hsk_diff_stats* stats) {
-  const size_t n = k->diff_recs.size();
-  *n_regions = n;
   if (stats) *stats = k->diff_stats;
-  if (!recs) return HSK_OK;
-  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: cap is below the number of kept regions");
-  if (n > 0) memcpy(recs, k->diff_recs.data(), n * sizeof(hsk_diff_region));
-  return HSK_OK;
+  return reply_records(k, k->diff_recs, recs, cap, n_regions, "hsk_diff_volume: cap is below the number of kept regions");
 }
 
 extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params* params, hsk_diff_region* recs, size_t cap, size_t* n_regions,
@@ -92,94 +81,44 @@ extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params
   hsk_ctx* k = ref;
   // the diff of an earlier call still fits: both volumes stand, cur is the same context, the parameters are the same.  Nothing is
   // launched; the records and stats are the held ones (what a size query followed by the fill costs once, as the labelling's)
-  const bool held = k->d_diff && k->diff_key[0] != 0 && k->diff_key[0] == k->vol_epoch && k->diff_key[1] == cur->serial && k->diff_key[2] == cur->vol_epoch &&
-                    memcmp(&k->diff_params, &p, sizeof(p)) == 0;
-  if (held) return diff_reply(k, recs, cap, n_regions, stats);
+  const DiffKey key = diff_key_of(cur, p);
+  if (k->diff.stands_for(k, &key, sizeof(key))) return diff_reply(k, recs, cap, n_regions, stats);
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   // cur: read only.  Its deferred weights are written back; everything its stream holds must have ended before ref's stream reads it
   flush_weights(cur);
   HIPCHK(k, hipStreamSynchronize(cur->stream));
   flush_weights(k);
-  k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;  // (the scratch is about to be written: an earlier diff goes)
+  k->diff.drop();  // (the scratch is about to be written: an earlier diff goes)
   k->diff_recs.clear();
-  int r = ensure_grown(k, &k->d_diff, &k->diff_bytes, diff_layout(k->vp, nullptr, nullptr));
+  int r = k->diff.grow(k, diff_layout(k->vp, nullptr, nullptr));
   if (r != HSK_OK) return r;
   DiffBufs b;
-  diff_layout(k->vp, k->d_diff, &b);
+  diff_layout(k->vp, k->diff.buf, &b);
   launch_diff_classify(k->stream, k->d_vol, cur->d_vol, k->vp, b, p.thresh, p.min_weight);
   launch_comp_label(k->stream, b.cls, k->vp, b.comp);
   HIPCHK(k, hipGetLastError());
-  unsigned counts[DIFF_COUNTS], n_roots = 0;
+  unsigned counts[DIFF_COUNTS];
   r = copy_out(k, counts, b.counts, sizeof(counts));
-  if (r == HSK_OK) r = copy_out(k, &n_roots, b.comp.counts + 4, sizeof(n_roots));
   if (r != HSK_OK) return r;
-  HIPCHK(k, hipStreamSynchronize(k->stream));
-  HIPCHK(k, hipGetLastError());
   hsk_diff_stats st;
   memset(&st, 0, sizeof(st));
   for (int c = 0; c < DIFF_CLASSES; ++c) st.n_class[c] = counts[c];
   *n_regions = 0;
-  if ((size_t)n_roots > HSK_COMPONENT_MAX) return fail(k, HSK_ERR_ARG, "hsk_diff_volume: more than 2^24 regions: nothing is held");
-  std::vector<unsigned> roots, table, av;
-  try {
-    roots.resize(n_roots);
-    table.resize((size_t)n_roots * 8);
-    av.resize((size_t)n_roots * 2);
-  } catch (const std::bad_alloc&) {
-    return fail(k, HSK_ERR_STATE, "hsk_diff_volume: out of host memory for the records");
-  }
-  if (n_roots > 0) {
-    r = ensure_grown(k, &k->d_diff_tab, &k->diff_tab_bytes, diff_tab(k, n_roots).bytes);
-    if (r != HSK_OK) return r;
-    const DiffTab t = diff_tab(k, n_roots);
-    launch_comp_records(k->stream, k->vp, b.comp, n_roots, t.roots, t.table);
-    // the MINOR step: the words of a region below min_voxels keep their class in the weight half and stop being members
-    const unsigned min_voxels = p.min_voxels > 0xffffffffull ? 0xffffffffu : (unsigned)p.min_voxels;  // (no region has 2^32 voxels)
-    launch_comp_prune(k->stream, b.cls, nullptr, k->vp, b.comp.parent, t.roots, t.table, n_roots, min_voxels, t.roots, 0u, true);
-    launch_diff_records(k->stream, k->vp, b, n_roots, t.roots, t.av);
-    HIPCHK(k, hipGetLastError());
-    r = copy_out(k, roots.data(), t.roots, (size_t)n_roots * 4);
-    if (r == HSK_OK) r = copy_out(k, table.data(), t.table, (size_t)n_roots * 32);
-    if (r == HSK_OK) r = copy_out(k, av.data(), t.av, (size_t)n_roots * 8);
-    if (r != HSK_OK) return r;
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipGetLastError());
-  }
+  RegionRead rr;
+  r = region_read(k, b.comp, &k->diff, 2, 0, "hsk_diff_volume: more than 2^24 regions: nothing is held", "hsk_diff_volume: out of host memory for the records", b.cls,
+                  p.min_voxels, [&](const RegionTab& t, unsigned n) { launch_diff_records(k->stream, k->vp, b, n, t.roots, t.extra); }, &rr);
+  if (r != HSK_OK) return r;
   const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
   uint64_t kept_a = 0, kept_v = 0;
   try {
-    for (size_t i = 0; i < n_roots; ++i) {
-      const unsigned* t8 = &table[i * 8];
-      if ((uint64_t)t8[0] < p.min_voxels) {
-        st.n_minor_regions += 1;
-        continue;
-      }
-      hsk_diff_region c;
-      memset(&c, 0, sizeof(c));
-      unsigned x, y, z;
-      g.xyz(roots[i], x, y, z);
-      c.root[0] = (int32_t)x;
-      c.root[1] = (int32_t)y;
-      c.root[2] = (int32_t)z;
-      c.n_voxels = t8[0];
-      c.n_appeared = av[2 * i];
-      c.n_vanished = av[2 * i + 1];
-      for (int a = 0; a < 3; ++a) {
-        c.lo[a] = (int32_t)t8[1 + a];
-        c.hi[a] = (int32_t)t8[4 + a];
-      }
-      kept_a += c.n_appeared;
-      kept_v += c.n_vanished;
-      k->diff_recs.push_back(c);
-    }
+    st.n_minor_regions = comp_region_records(g, rr.roots.data(), rr.table.data(), rr.n, p.min_voxels, &k->diff_recs, [&](hsk_diff_region& c, size_t i) {
+      kept_a += c.n_appeared = rr.extra[2 * i];
+      kept_v += c.n_vanished = rr.extra[2 * i + 1];
+    });
   } catch (const std::bad_alloc&) {
     k->diff_recs.clear();
     return fail(k, HSK_ERR_STATE, "hsk_diff_volume: out of host memory for the records");
   }
-  std::sort(k->diff_recs.begin(), k->diff_recs.end(), [&](const hsk_diff_region& a, const hsk_diff_region& c) {
-    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
-                              g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
-  });
   // the final classes: what the kept regions hold stays APPEARED or VANISHED, the rest of CHANGED is MINOR
   st.n_class[DIFF_MINOR] = (st.n_class[DIFF_APPEARED] - kept_a) + (st.n_class[DIFF_VANISHED] - kept_v);
   st.n_class[DIFF_APPEARED] = kept_a;
@@ -187,13 +126,7 @@ extern "C" int hsk_diff_volume(hsk_ctx* ref, hsk_ctx* cur, const hsk_diff_params
   st.n_regions = k->diff_recs.size();
   st.largest = k->diff_recs.empty() ? 0 : k->diff_recs[0].n_voxels;
   k->diff_stats = st;
-  memset(&k->diff_params, 0, sizeof(k->diff_params));  // (compared as bytes: the padding, if any, is zero on both sides)
-  k->diff_params.thresh = p.thresh;
-  k->diff_params.min_weight = p.min_weight;
-  k->diff_params.min_voxels = p.min_voxels;
-  k->diff_key[0] = k->vol_epoch;
-  k->diff_key[1] = cur->serial;
-  k->diff_key[2] = cur->vol_epoch;
+  k->diff.stamp(k, &key, sizeof(key));
   return diff_reply(k, recs, cap, n_regions, stats);
 }
 
@@ -204,14 +137,14 @@ extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* 
   if (int rc = clear_box_check(k, box, "hsk_download_diff", &bx, &n)) return rc;
   if (n > 0 && !cls) return fail(k, HSK_ERR_ARG, "hsk_download_diff: cls is null");
   if (int rc = volume_state_check(k, k, "hsk_download_diff")) return rc;
-  if (int rc = diff_held_check(k, "hsk_download_diff")) return rc;
+  if (int rc = k->diff.require(k, "hsk_download_diff", DIFF_NOT_HELD)) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ProductArrays pa;
   const int a_cls = pa.add(cls, n), a_region = pa.add(region, n * 4);
   if (int r = pa.place(k)) return r;
   DiffBufs b;
-  diff_layout(k->vp, k->d_diff, &b);
+  diff_layout(k->vp, k->diff.buf, &b);
   launch_diff_box(k->stream, k->vp, b, bx.lo, bx.hi, n, pa.dev<unsigned char>(a_cls), pa.dev<unsigned>(a_region));
   HIPCHK(k, hipGetLastError());
   return pa.copy_out(k);
@@ -219,15 +152,13 @@ extern "C" int hsk_download_diff(hsk_ctx* k, const hsk_voxel_box* box, uint8_t* 
 
 extern "C" int hsk_diff_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint32_t* region) {
   if (!k) return HSK_ERR_ARG;
-  if (n > 0 && (!xyz || !cls)) return fail(k, HSK_ERR_ARG, "hsk_diff_at: null argument");
-  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_diff_at: more than 2^20 points");
-  if (radius < 0 || radius > 4) return fail(k, HSK_ERR_ARG, "hsk_diff_at: radius must lie in 0..4");
+  if (int rc = points_check(k, "hsk_diff_at", xyz, cls, n, radius, 4)) return rc;
   if (int rc = volume_state_check(k, k, "hsk_diff_at")) return rc;
-  if (int rc = diff_held_check(k, "hsk_diff_at")) return rc;
+  if (int rc = k->diff.require(k, "hsk_diff_at", DIFF_NOT_HELD)) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   DiffBufs b;
-  diff_layout(k->vp, k->d_diff, &b);
+  diff_layout(k->vp, k->diff.buf, &b);
   return gather_points(
       k, xyz, n, region, [&](const float* pts, unsigned* reg, unsigned char* c) { launch_diff_gather(k->stream, k->vp, b, pts, (unsigned)n, radius, reg, c); }, cls);
 }
@@ -244,14 +175,15 @@ extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params
   if (p.halo < 0 || p.halo > 8) return fail(ref, HSK_ERR_ARG, "hsk_adopt_diff: halo must lie in 0..8");
   for (hsk_ctx* c : {ref, cur})
     if (int rc = volume_state_check(c, ref, "hsk_adopt_diff")) return rc;
-  if (int rc = diff_held_check(ref, "hsk_adopt_diff")) return rc;
-  if (ref->diff_key[1] != cur->serial || ref->diff_key[2] != cur->vol_epoch)
+  if (int rc = ref->diff.require(ref, "hsk_adopt_diff", DIFF_NOT_HELD)) return rc;
+  const uint64_t cur_now[2] = {cur->serial, cur->vol_epoch};
+  if (memcmp(ref->diff.key.data(), cur_now, sizeof(cur_now)) != 0)
     return fail(ref, HSK_ERR_STATE, "hsk_adopt_diff: no diff is held for the volumes as they stand (cur is another context, or its volume has changed)");
   hsk_ctx* k = ref;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   HIPCHK(k, hipStreamSynchronize(cur->stream));
   DiffBufs b;
-  diff_layout(k->vp, k->d_diff, &b);
+  diff_layout(k->vp, k->diff.buf, &b);
   launch_diff_halo(k->stream, cur->d_vol, k->vp, b, p.which, p.halo);
   HIPCHK(k, hipGetLastError());
   unsigned counts[2] = {0, 0};
@@ -265,14 +197,9 @@ extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params
   st.n_adopted = counts[1];
   if (st.n_adopted > 0) {
     st.n_colored = (k->d_color && cur->d_color) ? st.n_adopted : 0;
-    flush_weights(k);  // the words that stay are to hold their weights
-    launch_diff_adopt(k->stream, k->d_vol, cur->d_vol, k->d_color, cur->d_color, k->vp, b);
-    HIPCHK(k, hipGetLastError());
-    k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;  // (the held diff described the volume as it was)
-    r = volume_replaced(k);
+    r = commit_volume_write(k, [&] { launch_diff_adopt(k->stream, k->d_vol, cur->d_vol, k->d_color, cur->d_color, k->vp, b); });
+    k->diff.drop();  // (the held diff described the volume as it was)
     if (r != HSK_OK) return r;
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipGetLastError());
   }  // (else nothing is written, vol_epoch does not move: cached passes and the diff stay valid)
   if (stats) *stats = st;
   return HSK_OK;
@@ -281,14 +208,7 @@ extern "C" int hsk_adopt_diff(hsk_ctx* ref, hsk_ctx* cur, const hsk_adopt_params
 extern "C" int hsk_release_diff(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  for (void** buf : {&k->d_diff, &k->d_diff_tab})
-    if (*buf) {
-      HIPCHK(k, hipStreamSynchronize(k->stream));
-      HIPCHK(k, hipFree(*buf));
-      *buf = nullptr;
-    }
-  k->diff_bytes = k->diff_tab_bytes = 0;
-  k->diff_key[0] = k->diff_key[1] = k->diff_key[2] = 0;
+  const int r = k->diff.release(k);
   k->diff_recs.clear();
-  return HSK_OK;
+  return r;
 }

@@ -2,7 +2,7 @@
 // hsk_default_fill_params, hsk_fill_holes, hsk_download_fill_mask.  The iterations read the volume as it stands, with NO flush of
 // the deferred weights (as the labelling, api_components.hip): the rule asks of a weight only whether it is zero.  The write
 // follows hsk_prune_components' order: the state check, the rounds, then -- only when something will be written -- flush the
-// deferred weights, write, volume_replaced, synchronise.  The mask stays on the device (d_fill) while vol_epoch stands.
+// deferred weights, write, volume_replaced, synchronise.  The mask stays on the device (fill, a HeldPass) while vol_epoch stands.
 #pragma clang fp contract(off)
 #include <algorithm>
 #include <cmath>
@@ -13,15 +13,7 @@
 extern "C" void hsk_default_fill_params(const hsk_ctx* k, hsk_fill_params* p) {
   if (!p) return;
   float cell[3];
-  if (k) {
-    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
-  } else {
-    hsk_config c;
-    hsk_default_config(&c, 256);
-    cell[0] = c.vol_size_m[0] / (float)c.vol_x;
-    cell[1] = c.vol_size_m[1] / (float)c.vol_y;
-    cell[2] = c.vol_size_m[2] / (float)c.vol_z;
-  }
+  context_cells(k, cell, nullptr);
   memset(p, 0, sizeof(*p));
   // the voxels of 15 cm along the finest axis, in binary64 from the binary32 cells: the fronts from a gap's two rims meet
   const double m = (double)std::min(cell[0], std::min(cell[1], cell[2]));
@@ -49,11 +41,11 @@ extern "C" int hsk_fill_holes(hsk_ctx* k, const hsk_fill_params* params, const h
   if (int rc = clear_box_check(k, box, "hsk_fill_holes", &b, &n_box)) return rc;
   if (int rc = volume_state_check(k, k, "hsk_fill_holes")) return rc;  // (prune's refusals: in flight, a slab, more than 2^31 voxels)
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  k->fill_epoch = 0;  // (the scratch is about to be written: the mask of an earlier fill goes)
-  int r = ensure_grown(k, &k->d_fill, &k->fill_bytes, fill_layout(k->vp, nullptr, nullptr));
+  k->fill.drop();  // (the scratch is about to be written: the mask of an earlier fill goes)
+  int r = k->fill.grow(k, fill_layout(k->vp, nullptr, nullptr));
   if (r != HSK_OK) return r;
   FillBufs fb;
-  fill_layout(k->vp, k->d_fill, &fb);
+  fill_layout(k->vp, k->fill.buf, &fb);
   launch_fill_init(k->stream, k->d_vol, k->vp, b.lo, b.hi, fb);
   // every iteration is enqueued: one that has nothing to do costs a launch whose workgroups read a few bytes and leave (fill.hip),
   // and the host learns iterations_run from the iterations' counters without a synchronisation between them
@@ -81,16 +73,11 @@ extern "C" int hsk_fill_holes(hsk_ctx* k, const hsk_fill_params* params, const h
       break;
     }
   if (st.n_written > 0) {
-    flush_weights(k);  // the words that stay are to hold their weights
-    launch_fill_commit(k->stream, k->d_vol, k->vp, fb, fin, p.fill_weight);
-    HIPCHK(k, hipGetLastError());
-    r = volume_replaced(k);
+    r = commit_volume_write(k, [&] { launch_fill_commit(k->stream, k->d_vol, k->vp, fb, fin, p.fill_weight); });
     if (r != HSK_OK) return r;
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipGetLastError());
   }  // (else nothing is written, vol_epoch does not move: cached passes stay valid)
   k->fill_mask = fill_mask_bytes(k->vp, fb, fin);
-  k->fill_epoch = k->vol_epoch;
+  k->fill.stamp(k);
   if (stats) *stats = st;
   return HSK_OK;
 }
@@ -102,8 +89,7 @@ extern "C" int hsk_download_fill_mask(hsk_ctx* k, const hsk_voxel_box* box, uint
   if (int rc = clear_box_check(k, box, "hsk_download_fill_mask", &b, &n)) return rc;
   if (n > 0 && !mask) return fail(k, HSK_ERR_ARG, "hsk_download_fill_mask: mask is null");
   if (int rc = volume_state_check(k, k, "hsk_download_fill_mask")) return rc;
-  if (!k->d_fill || k->fill_epoch == 0 || k->fill_epoch != k->vol_epoch)
-    return fail(k, HSK_ERR_STATE, "hsk_download_fill_mask: no fill is held for the volume as it stands");
+  if (int rc = k->fill.require(k, "hsk_download_fill_mask", ": no fill is held for the volume as it stands")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   return download_rows(k, k->fill_mask, 1, b, n, mask);

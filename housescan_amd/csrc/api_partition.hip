@@ -1,7 +1,7 @@
 // api_partition.hip -- the C ABI's room partition (include/hskinfu.h "Room partition"; DESIGN.md 3.20 the kernels, 8n the rule):
 // hsk_default_partition_params, hsk_build_partition, hsk_partition_doors, hsk_download_partition, hsk_download_partition_cost,
 // hsk_partition_at, hsk_partition_floor, hsk_release_partition, hsk_partition_tiles_relaxed and the host-only hsk_merge_rooms.
-// The partition is built from the clearance field (api_clearance.hip builds or reuses it first) and stays on the device (d_part)
+// The partition is built from the clearance field (api_clearance.hip builds or reuses it first) and stays on the device (part, a HeldPass)
 // while vol_epoch, the 20 device-relevant clearance bytes and the four partition parameters stand.  The host drives it: it reads
 // the number of kept cores and sorts their roots between the labelling and the init, reads the next worklist's length after every
 // round and stops at zero or at HSK_REACH_MAX_ROUNDS (api_reach.hip: relax_rounds), orders the room records and sends the id table back before the door sweep.
@@ -30,15 +30,7 @@ extern "C" void hsk_default_partition_params(const hsk_ctx* k, const hsk_clearan
   else
     hsk_default_clearance_params(k, &c);
   float cell[3];
-  if (k) {
-    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
-  } else {
-    hsk_config cfg;
-    hsk_default_config(&cfg, 256);
-    cell[0] = cfg.vol_size_m[0] / (float)cfg.vol_x;
-    cell[1] = cfg.vol_size_m[1] / (float)cfg.vol_y;
-    cell[2] = cfg.vol_size_m[2] / (float)cfg.vol_z;
-  }
+  context_cells(k, cell, nullptr);
   memset(p, 0, sizeof(*p));
   p->core_d2 = std::max(1u, std::min(hsk_clearance_d2(&c, 0.5f), c.max_d2));  // (half a metre: a stated choice, not a measurement)
   p->min_d2 = 1u;
@@ -157,10 +149,10 @@ static int part_run(hsk_ctx* k, const unsigned* d2, const PartGeom& q, const Par
   }
   // the doors: a dense table over the pairs of rooms, 64 bytes each, scanned on the host in (a, b) order
   const size_t words = (size_t)n_kept * n_kept * PART_DOOR_WORDS;
-  if (int r = ensure_grown(k, &k->d_part_tab, &k->part_tab_bytes, words * 8)) return r;
-  HIPCHK(k, launch_part_doors(k->stream, d2, q, b, n_kept, (unsigned long long*)k->d_part_tab));
+  if (int r = k->part.grow_tab(k, words * 8)) return r;
+  HIPCHK(k, launch_part_doors(k->stream, d2, q, b, n_kept, (unsigned long long*)k->part.tab));
   std::vector<unsigned long long> table(words);
-  if (int r = copy_out(k, table.data(), k->d_part_tab, words * 8)) return r;
+  if (int r = copy_out(k, table.data(), k->part.tab, words * 8)) return r;
   for (unsigned a = 0; a < n_kept; ++a)
     for (unsigned bb = a + 1u; bb < n_kept; ++bb) {
       const unsigned long long* t = &table[((size_t)a * n_kept + bb) * PART_DOOR_WORDS];
@@ -212,51 +204,47 @@ extern "C" int hsk_build_partition(hsk_ctx* k, const hsk_clearance_params* cpara
   key[6] = p.min_d2;
   key[7] = p.min_core_voxels;
   key[8] = p.max_cost;
-  const bool held = k->d_part && k->part_epoch != 0 && k->part_epoch == k->vol_epoch && memcmp(key, k->part_key, sizeof(key)) == 0;
+  const bool held = k->part.stands_for(k, key, sizeof(key));
   if (!held) {
     HIPCHK(k, hipSetDevice(k->cfg.device_id));
-    k->part_epoch = 0;
+    k->part.drop();
     bool clear_reused = false;
     int r = clear_build(k, cp, cq, &clear_reused);
     if (r != HSK_OK) return r;
     PartGeom q;
     part_geom(cq.X, cq.Y, cq.Z, cq.w, p.core_d2, p.min_d2, p.min_core_voxels, p.max_cost, &q);
-    r = ensure_grown(k, &k->d_part, &k->part_bytes, part_layout(q, nullptr, nullptr));
+    r = k->part.grow(k, part_layout(q, nullptr, nullptr));
     if (r != HSK_OK) return r;
     PartBufs b;
-    part_layout(q, k->d_part, &b);
+    part_layout(q, k->part.buf, &b);
     ClearBufs cb;
-    clear_layout(k->vp, k->d_clear, &cb);
+    clear_layout(k->vp, k->clear.buf, &cb);
     PartResult res;
     r = part_run(k, cb.field, q, b, &res);
     if (r != HSK_OK) return r;
     if (res.too_many) {
-      if (stats) part_fill_stats(stats, res, k->part_bytes + k->part_tab_bytes, false);
+      if (stats) part_fill_stats(stats, res, k->part.bytes + k->part.tab_bytes, false);
       return fail(k, HSK_ERR_ARG, "hsk_build_partition: more than HSK_PARTITION_MAX_ROOMS cores are kept (raise core_d2 or min_core_voxels)");
     }
     memcpy(k->part_counts, res.counts, sizeof(res.counts));
-    memcpy(k->part_key, key, sizeof(key));
     k->part_recs.swap(res.recs);
     k->part_doors.swap(res.doors);
     k->part_q = q;
     k->part_rounds = res.rounds;
     k->part_tiles = res.tiles;
     k->part_first = res.first;
-    k->part_epoch = k->vol_epoch;
+    k->part.stamp(k, key, sizeof(key));
   }
-  const size_t n = k->part_recs.size();
-  if (recs && cap < n) {
-    *n_rooms = n;
-    return fail(k, HSK_ERR_ARG, "hsk_build_partition: cap is smaller than the number of rooms (*n_rooms: the count)");
-  }
-  if (recs && n) memcpy(recs, k->part_recs.data(), n * sizeof(hsk_room));
-  if (n_rooms) *n_rooms = n;
+  size_t n_unasked;  // (recs null and n_rooms null: a call for the stats alone)
+  if (int rc = reply_records(k, k->part_recs, recs, cap, n_rooms ? n_rooms : &n_unasked,
+                             "hsk_build_partition: cap is smaller than the number of rooms (*n_rooms: the count)"))
+    return rc;
   if (stats) {
     PartResult res;
     memcpy(res.counts, k->part_counts, sizeof(res.counts));
     res.rounds = k->part_rounds;
     res.doors.resize(k->part_doors.size());
-    part_fill_stats(stats, res, k->part_bytes + k->part_tab_bytes, held);
+    part_fill_stats(stats, res, k->part.bytes + k->part.tab_bytes, held);
   }
   return HSK_OK;
 }
@@ -264,23 +252,14 @@ extern "C" int hsk_build_partition(hsk_ctx* k, const hsk_clearance_params* cpara
 // the reads: a partition must be held
 static int part_held(hsk_ctx* k, const char* who) {
   if (int rc = volume_state_check(k, k, who)) return rc;
-  if (!(k->d_part && k->part_epoch != 0 && k->part_epoch == k->vol_epoch))
-    return fail(k, HSK_ERR_STATE, (std::string(who) + ": no partition of the volume as it stands is held (hsk_build_partition makes one)").c_str());
-  return HSK_OK;
+  return k->part.require(k, who, ": no partition of the volume as it stands is held (hsk_build_partition makes one)");
 }
 
 extern "C" int hsk_partition_doors(hsk_ctx* k, hsk_door* doors, size_t cap, size_t* n_doors) {
   if (!k) return HSK_ERR_ARG;
   if (!n_doors) return fail(k, HSK_ERR_ARG, "hsk_partition_doors: n_doors is null");
   if (int rc = part_held(k, "hsk_partition_doors")) return rc;
-  const size_t n = k->part_doors.size();
-  if (doors && cap < n) {
-    *n_doors = n;
-    return fail(k, HSK_ERR_ARG, "hsk_partition_doors: cap is smaller than the number of doors (*n_doors: the count)");
-  }
-  if (doors && n) memcpy(doors, k->part_doors.data(), n * sizeof(hsk_door));
-  *n_doors = n;
-  return HSK_OK;
+  return reply_records(k, k->part_doors, doors, cap, n_doors, "hsk_partition_doors: cap is smaller than the number of doors (*n_doors: the count)");
 }
 
 static int part_download(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* out, bool cost, const char* who) {
@@ -292,7 +271,7 @@ static int part_download(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* out, bo
   if (int rc = part_held(k, who)) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   PartBufs pb;
-  part_layout(k->part_q, k->d_part, &pb);
+  part_layout(k->part_q, k->part.buf, &pb);
   if (n == 0) return HSK_OK;
   int r = ensure_product_bytes(k, n * 4);
   if (r != HSK_OK) return r;
@@ -311,14 +290,13 @@ extern "C" int hsk_download_partition_cost(hsk_ctx* k, const hsk_voxel_box* box,
 
 extern "C" int hsk_partition_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint32_t* ids) {
   if (!k) return HSK_ERR_ARG;
-  if (n > 0 && (!xyz || !ids)) return fail(k, HSK_ERR_ARG, "hsk_partition_at: null argument");
-  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_partition_at: more than 2^20 points");
-  if (radius < 0 || radius > HSK_PARTITION_MAX_RADIUS) return fail(k, HSK_ERR_ARG, "hsk_partition_at: radius must lie in 0..4");
+  static_assert(HSK_PARTITION_MAX_RADIUS == 4, "the radius refusal names 4");
+  if (int rc = points_check(k, "hsk_partition_at", xyz, ids, n, radius, HSK_PARTITION_MAX_RADIUS)) return rc;
   if (int rc = part_held(k, "hsk_partition_at")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   PartBufs pb;
-  part_layout(k->part_q, k->d_part, &pb);
+  part_layout(k->part_q, k->part.buf, &pb);
   return gather_points(k, xyz, n, ids, [&](const float* pts, unsigned* out, unsigned char*) {
     launch_part_gather(k->stream, k->part_q, pb, (unsigned)k->part_recs.size(), k->vp, pts, (unsigned)n, radius, out);
   });
@@ -375,26 +353,17 @@ extern "C" int hsk_partition_floor(hsk_ctx* k, const hsk_clearance_params* cpara
   if (doors && !res.doors.empty()) memcpy(doors, res.doors.data(), res.doors.size() * sizeof(hsk_door));
   if (n_rooms) *n_rooms = res.recs.size();
   if (n_doors) *n_doors = res.doors.size();
-  if (stats) part_fill_stats(stats, res, lay.bytes + k->part_tab_bytes, false);
+  if (stats) part_fill_stats(stats, res, lay.bytes + k->part.tab_bytes, false);
   return HSK_OK;
 }
 
 extern "C" int hsk_release_partition(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
-  if (k->d_part || k->d_part_tab) {
-    HIPCHK(k, hipSetDevice(k->cfg.device_id));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    if (k->d_part) HIPCHK(k, hipFree(k->d_part));
-    k->d_part = nullptr;
-    if (k->d_part_tab) HIPCHK(k, hipFree(k->d_part_tab));
-    k->d_part_tab = nullptr;
-  }
-  k->part_bytes = 0;
-  k->part_tab_bytes = 0;
-  k->part_epoch = 0;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  const int r = k->part.release(k);
   k->part_recs.clear();
   k->part_doors.clear();
-  return HSK_OK;
+  return r;
 }
 
 extern "C" int hsk_partition_tiles_relaxed(const hsk_ctx* k, uint64_t* tiles_relaxed, uint64_t* first_tiles, uint64_t* tiles) {

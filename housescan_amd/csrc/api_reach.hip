@@ -1,7 +1,7 @@
 // api_reach.hip -- the C ABI's reach field (include/hskinfu.h "Reach field"; DESIGN.md 3.19 the kernels, 8m the rule):
 // hsk_default_reach_params, hsk_build_reach, hsk_download_reach, hsk_reach_at, hsk_reach_path, hsk_reach_floor, hsk_release_reach,
 // hsk_reach_tiles_relaxed and the host-only hsk_rank_views_reach and hsk_reach_metres.  The field is built from the clearance field
-// (api_clearance.hip builds or reuses it first) and stays on the device (d_reach) while vol_epoch, the 20 device-relevant
+// (api_clearance.hip builds or reuses it first) and stays on the device (reach, a HeldPass) while vol_epoch, the 20 device-relevant
 // clearance bytes, min_d2, max_cost and the seeds' voxels stand.  The host drives the rounds: it reads the next worklist's length
 // after every round and stops at zero, or at HSK_REACH_MAX_ROUNDS (relax_rounds, which api_partition.hip drives its rounds with
 // too).  Nothing the tracker reads is written; vol_epoch does not move.
@@ -126,63 +126,61 @@ extern "C" int hsk_build_reach(hsk_ctx* k, const hsk_clearance_params* cparams, 
   if (int rc = clear_check(k, cparams, "hsk_build_reach", &cp, &cq)) return rc;
   if (int rc = reach_check(k, cp, params, seeds_xyz, n_seeds, "hsk_build_reach", &p)) return rc;
   if (int rc = volume_state_check(k, k, "hsk_build_reach")) return rc;
-  // the seeds' voxels: a point outside the grid, or with a NaN, is dropped here; one on a voxel that is not passable on the device
+  // the key: the clearance key, min_d2, max_cost, then the seeds' voxels -- a point outside the grid, or with a NaN, is dropped
+  // here; one on a voxel that is not passable on the device
   const SampleVol sv = hsk_sample_vol(k->vp);
-  std::vector<uint32_t> vox;
-  vox.reserve(n_seeds);
+  std::vector<uint32_t> key(7);
+  key.reserve(7 + n_seeds);
+  clear_key_of(cp, key.data());
+  key[5] = p.min_d2;
+  key[6] = p.max_cost;
   for (size_t i = 0; i < n_seeds; ++i) {
     unsigned x, y, z;
     bool inside;
     clear_point_voxel(sv, seeds_xyz[3 * i], seeds_xyz[3 * i + 1], seeds_xyz[3 * i + 2], x, y, z, inside);
-    if (inside) vox.push_back((uint32_t)(((size_t)z * (unsigned)sv.Y + y) * (unsigned)sv.X + x));
+    if (inside) key.push_back((uint32_t)(((size_t)z * (unsigned)sv.Y + y) * (unsigned)sv.X + x));
   }
-  uint32_t key[7];
-  clear_key_of(cp, key);
-  key[5] = p.min_d2;
-  key[6] = p.max_cost;
-  const bool held = k->d_reach && k->reach_epoch != 0 && k->reach_epoch == k->vol_epoch && memcmp(key, k->reach_key, sizeof(key)) == 0 && vox == k->reach_seeds;
+  const uint32_t* vox = key.data() + 7;
+  const size_t n_vox = key.size() - 7;
+  const bool held = k->reach.stands_for(k, key.data(), key.size() * 4);
   if (!held) {
     HIPCHK(k, hipSetDevice(k->cfg.device_id));
-    k->reach_epoch = 0;
+    k->reach.drop();
     bool clear_reused = false;
     int r = clear_build(k, cp, cq, &clear_reused);
     if (r != HSK_OK) return r;
     ReachGeom q;
     reach_geom(cq.X, cq.Y, cq.Z, cq.w, p.min_d2, p.max_cost, &q);
-    r = ensure_grown(k, &k->d_reach, &k->reach_bytes, reach_layout(q, nullptr, nullptr));
+    r = k->reach.grow(k, reach_layout(q, nullptr, nullptr));
     if (r != HSK_OK) return r;
     ReachBufs b;
-    reach_layout(q, k->d_reach, &b);
+    reach_layout(q, k->reach.buf, &b);
     ClearBufs cb;
-    clear_layout(k->vp, k->d_clear, &cb);
-    if (!vox.empty()) {
-      r = ensure_product_bytes(k, vox.size() * 4);
+    clear_layout(k->vp, k->clear.buf, &cb);
+    if (n_vox) {
+      r = ensure_product_bytes(k, n_vox * 4);
       if (r != HSK_OK) return r;
-      HIPCHK(k, hipMemcpyAsync(k->d_out, vox.data(), vox.size() * 4, hipMemcpyHostToDevice, k->stream));
+      HIPCHK(k, hipMemcpyAsync(k->d_out, vox, n_vox * 4, hipMemcpyHostToDevice, k->stream));
     }
     unsigned long long counts[4];
     uint32_t rounds = 0;
     unsigned long long tiles = 0;
-    r = reach_run(k, cb.field, q, b, (const unsigned*)k->d_out, (unsigned)vox.size(), counts, &rounds, &tiles);
+    r = reach_run(k, cb.field, q, b, (const unsigned*)k->d_out, (unsigned)n_vox, counts, &rounds, &tiles);
     if (r != HSK_OK) return r;
     memcpy(k->reach_counts, counts, sizeof(counts));
-    memcpy(k->reach_key, key, sizeof(key));
-    k->reach_seeds = vox;
     k->reach_q = q;
     k->reach_rounds = rounds;
     k->reach_tiles = tiles;
-    k->reach_epoch = k->vol_epoch;
+    k->reach.stamp(k, key.data(), key.size() * 4);
   }
-  if (stats) reach_fill_stats(stats, k->reach_counts, k->reach_bytes, held ? 0u : k->reach_rounds, held);
+  if (stats) reach_fill_stats(stats, k->reach_counts, k->reach.bytes, held ? 0u : k->reach_rounds, held);
   return HSK_OK;
 }
 
 // the reads: a field must be held
 static int reach_held(hsk_ctx* k, const char* who) {
   if (int rc = volume_state_check(k, k, who)) return rc;
-  if (!(k->d_reach && k->reach_epoch != 0 && k->reach_epoch == k->vol_epoch))
-    return fail(k, HSK_ERR_STATE, (std::string(who) + ": no reach field of the volume as it stands is held (hsk_build_reach makes one)").c_str());
-  return HSK_OK;
+  return k->reach.require(k, who, ": no reach field of the volume as it stands is held (hsk_build_reach makes one)");
 }
 
 extern "C" int hsk_download_reach(hsk_ctx* k, const hsk_voxel_box* box, uint32_t* g) {
@@ -194,19 +192,18 @@ extern "C" int hsk_download_reach(hsk_ctx* k, const hsk_voxel_box* box, uint32_t
   if (int rc = reach_held(k, "hsk_download_reach")) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ReachBufs rb;
-  reach_layout(k->reach_q, k->d_reach, &rb);
+  reach_layout(k->reach_q, k->reach.buf, &rb);
   return download_rows(k, rb.field, 4, b, n, g);
 }
 
 extern "C" int hsk_reach_at(hsk_ctx* k, const float* xyz, size_t n, uint32_t* g) {
   if (!k) return HSK_ERR_ARG;
-  if (n > 0 && (!xyz || !g)) return fail(k, HSK_ERR_ARG, "hsk_reach_at: null argument");
-  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_reach_at: more than 2^20 points");
+  if (int rc = points_check(k, "hsk_reach_at", xyz, g, n, 0, -1)) return rc;
   if (int rc = reach_held(k, "hsk_reach_at")) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ReachBufs rb;
-  reach_layout(k->reach_q, k->d_reach, &rb);
+  reach_layout(k->reach_q, k->reach.buf, &rb);
   // (the clearance field's gather: OUTSIDE is the same word)
   return gather_points(k, xyz, n, g, [&](const float* pts, unsigned* out, unsigned char*) { launch_clear_gather(k->stream, rb.field, k->vp, pts, (unsigned)n, out); });
 }
@@ -225,7 +222,7 @@ extern "C" int hsk_reach_path(hsk_ctx* k, const float goal_xyz[3], int32_t* voxe
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   const ReachGeom& q = k->reach_q;
   ReachBufs rb;
-  reach_layout(q, k->d_reach, &rb);
+  reach_layout(q, k->reach.buf, &rb);
   const unsigned goal = (unsigned)(((size_t)z * q.Y + y) * q.X + x);
   // the walk writes at most `room` voxels and counts them all: a first pass with room for most paths, a second one for a longer path
   unsigned long long res[2] = {0, 0};
@@ -317,16 +314,8 @@ extern "C" int hsk_reach_floor(hsk_ctx* k, const hsk_clearance_params* cparams, 
 
 extern "C" int hsk_release_reach(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
-  if (k->d_reach) {
-    HIPCHK(k, hipSetDevice(k->cfg.device_id));
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipFree(k->d_reach));
-  }
-  k->d_reach = nullptr;
-  k->reach_bytes = 0;
-  k->reach_epoch = 0;
-  k->reach_seeds.clear();
-  return HSK_OK;
+  HIPCHK(k, hipSetDevice(k->cfg.device_id));
+  return k->reach.release(k);
 }
 
 extern "C" int hsk_reach_tiles_relaxed(const hsk_ctx* k, uint64_t* tiles_relaxed, uint64_t* tiles) {

@@ -454,12 +454,9 @@ extern "C" int hsk_extract_mesh_indexed(hsk_ctx* k, float* vertices, float* norm
   int r = ensure_cube_table(k);
   if (r != HSK_OK) return r;
   MeshIndexBufs mb;
-  if (!k->d_mi) {
-    const size_t bytes = mesh_index_layout(k->vp, nullptr, nullptr);
-    HIPCHK(k, hipMalloc(&k->d_mi, bytes));
-    k->mi_bytes = bytes;
-  }
-  (void)mesh_index_layout(k->vp, k->d_mi, &mb);
+  r = k->mi.grow(k, mesh_index_layout(k->vp, nullptr, nullptr));
+  if (r != HSK_OK) return r;
+  (void)mesh_index_layout(k->vp, k->mi.buf, &mb);
   r = product_counts(k, 4, mb.totals, [&]() {
     launch_mesh_index_count(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, k->d_rowoff, mb, k->d_flags);
   });

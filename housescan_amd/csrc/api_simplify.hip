@@ -68,24 +68,21 @@ extern "C" int hsk_extract_mesh_simplified(hsk_ctx* k, const hsk_simplify_params
   st.n_in_vertices = nv_in;
   st.n_in_faces = nf_in;
   MeshIndexBufs mb;
-  (void)mesh_index_layout(k->vp, k->d_mi, &mb);
+  (void)mesh_index_layout(k->vp, k->mi.buf, &mb);
   const int s = simp_shift(p.cluster_voxels);
-  const size_t fixed = simp_layout(k->vp, s, nullptr, nullptr);
-  if (k->simp_bytes < fixed) k->simp_epoch = 0;  // (the buffer is made again: what it held is gone)
-  r = ensure_grown(k, &k->d_simp, &k->simp_bytes, fixed);
+  r = k->simp.grow(k, simp_layout(k->vp, s, nullptr, nullptr));
   if (r != HSK_OK) return r;
   SimpBufs sb;
-  (void)simp_layout(k->vp, s, k->d_simp, &sb);
+  (void)simp_layout(k->vp, s, k->simp.buf, &sb);
   // the clustering's own count pass: found in place when the last call counted this volume at this cluster size (the indexed
   // mesh's pass it stands on is a function of the volume alone, so vol_epoch covers it whoever made it again meanwhile)
-  if (!(k->simp_epoch == k->vol_epoch && k->simp_shift == s)) {
-    k->simp_epoch = 0;
+  if (!k->simp.stands_for(k, &s, sizeof(s))) {
+    k->simp.drop();
     launch_simp_count(k->stream, k->d_vol, k->vp, k->d_cube_tab, k->d_rowcnt, mb, sb);
     HIPCHK(k, hipGetLastError());
     r = read_u64(k, k->simp_totals, sb.totals, 3);
     if (r != HSK_OK) return r;
-    k->simp_epoch = k->vol_epoch;
-    k->simp_shift = s;
+    k->simp.stamp(k, &s, sizeof(s));
   }
   const unsigned long long* totals = k->simp_totals;
   const size_t nf = (size_t)totals[0], nv = (size_t)totals[1];
@@ -103,14 +100,14 @@ extern "C" int hsk_extract_mesh_simplified(hsk_ctx* k, const hsk_simplify_params
   // what is proportional to the output: the clusters' numbers, then their sums
   ProductLayout scratch;
   const size_t list_at = scratch.take(nv * 4), sums_at = scratch.take(nv * SIMP_REC * 8);
-  r = ensure_grown(k, &k->d_simp_out, &k->simp_out_bytes, scratch.bytes + (scratch.bytes >> 2));
+  r = k->simp.grow_tab(k, scratch.bytes + (scratch.bytes >> 2));
   if (r != HSK_OK) return r;
   ProductArrays out;  // (an array that is not asked for takes no space)
   const int a_xyz = out.add(vertices, nv * 12), a_nrm = out.add(normals, nv * 12), a_rgb = out.add(rgb, nv * 3), a_fc = out.add(faces, nf * 12);
   r = out.place(k);
   if (r != HSK_OK) return r;
   launch_simp_write(k->stream, k->d_vol, rgb ? k->d_color : nullptr, k->vp, k->d_cube_tab, k->d_rowcnt, mb, sb, (unsigned)nv,
-                    (unsigned*)((char*)k->d_simp_out + list_at), (long long*)((char*)k->d_simp_out + sums_at), p.mode, (double)p.sv_floor,
+                    (unsigned*)((char*)k->simp.tab + list_at), (long long*)((char*)k->simp.tab + sums_at), p.mode, (double)p.sv_floor,
                     out.dev<float>(a_xyz), out.dev<float>(a_nrm), out.dev<unsigned char>(a_rgb), out.dev<int>(a_fc));
   HIPCHK(k, hipGetLastError());
   r = out.copy_out(k);

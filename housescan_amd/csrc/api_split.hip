@@ -2,7 +2,7 @@
 // hsk_default_split_params, hsk_default_remove_params, hsk_split_plane_kinds, hsk_split_scene, hsk_download_split, hsk_split_at,
 // hsk_remove_objects, hsk_release_split.  The rule asks of a weight only whether it is zero, so the split reads the volume as it
 // stands, with NO flush of the deferred weights (as the labelling, api_components.hip).  The objects are components.hip's labelling
-// run on the class words, in a scratch of the split's own (d_split): hsk_label_components' cached labelling (d_comp, comp_epoch) is
+// run on the class words, in a scratch of the split's own (split, a HeldPass): hsk_label_components' cached labelling (comp) is
 // neither read nor written.  The split stays on the device with its records and stats on the host while the volume, the planes and
 // the parameters stand; a call with the same planes and parameters meanwhile is answered from them.  Removing writes the volume in
 // hsk_prune_components' order: flush the deferred weights, write, volume_replaced.
@@ -25,27 +25,12 @@ static_assert(sizeof(hsk_split_plane) == 24 && sizeof(hsk_split_params) == 24 &&
               "the split structs");
 static_assert(sizeof(SplitPlaneQ) == 48 && sizeof(SplitSelected) == 40, "the split's device tables");
 
-// the context's truncation distance and cells, or hsk_default_config(256)'s
-static void split_geometry(const hsk_ctx* k, float* tau, float cell[3]) {
-  if (k) {
-    *tau = k->vp.tau;
-    for (int i = 0; i < 3; ++i) cell[i] = k->vp.cell[i];
-    return;
-  }
-  hsk_config c;
-  hsk_default_config(&c, 256);
-  *tau = config_tau(&c);
-  cell[0] = c.vol_size_m[0] / (float)c.vol_x;
-  cell[1] = c.vol_size_m[1] / (float)c.vol_y;
-  cell[2] = c.vol_size_m[2] / (float)c.vol_z;
-}
-
 extern "C" void hsk_default_split_params(const hsk_ctx* k, hsk_split_params* p) {
   if (!p) return;
   hsk_prune_params pp;
   hsk_default_prune_params(k, &pp);
   float tau, cell[3];
-  split_geometry(k, &tau, cell);
+  context_cells(k, cell, &tau);
   memset(p, 0, sizeof(*p));
   p->dist_m = 0.04f;
   p->back_m = tau + 0.04f;
@@ -56,7 +41,7 @@ extern "C" void hsk_default_split_params(const hsk_ctx* k, hsk_split_params* p) 
 extern "C" void hsk_default_remove_params(const hsk_ctx* k, hsk_remove_params* p) {
   if (!p) return;
   float tau, cell[3];
-  split_geometry(k, &tau, cell);
+  context_cells(k, cell, &tau);
   const float c_min = std::min(cell[0], std::min(cell[1], cell[2]));
   const double h = std::ceil((double)tau / (double)c_min) + 1.0;
   p->mode = HSK_REMOVE_RESTORE;
@@ -111,42 +96,25 @@ static void split_rule_of(const hsk_ctx* k, const hsk_split_params& p, const hsk
   }
 }
 
-// a split is held for the volume as it stands
-static int split_held_check(hsk_ctx* k, const char* who) {
-  if (!k->d_split || k->split_epoch == 0 || k->split_epoch != k->vol_epoch)
-    return fail(k, HSK_ERR_STATE, (std::string(who) + ": no split is held for the volume as it stands").c_str());
-  return HSK_OK;
-}
+#define SPLIT_NOT_HELD ": no split is held for the volume as it stands"
 
-// d_split_tab for n objects: the roots, the labelling's records (eight words each), the split's (SPLIT_REC_WORDS each)
-struct SplitTab {
-  size_t bytes;
-  unsigned *roots, *table, *rec;
+// the split's key: the zero-padded parameters, then the planes asked for, zero-padded too (compared as bytes)
+struct SplitKey {
+  hsk_split_params p;
+  hsk_split_plane planes[HSK_SPLIT_MAX_PLANES];
 };
-static SplitTab split_tab(const hsk_ctx* k, size_t n) {
-  ProductLayout l;
-  char* base = (char*)k->d_split_tab;
-  SplitTab t;
-  const size_t roots_at = l.take(n * 4), table_at = l.take(n * 32), rec_at = l.take(n * SPLIT_REC_WORDS * 4);
-  t.roots = (unsigned*)(base + roots_at);
-  t.table = (unsigned*)(base + table_at);
-  t.rec = (unsigned*)(base + rec_at);
-  t.bytes = l.bytes;
-  return t;
-}
+static_assert(offsetof(SplitKey, planes) == sizeof(hsk_split_params), "the planes follow the parameters");
+static size_t split_key_bytes(size_t n_planes) { return sizeof(hsk_split_params) + n_planes * sizeof(hsk_split_plane); }
+// ... and the planes a held key was made for
+static size_t split_key_planes(const HeldPass& pass) { return (pass.key.size() - sizeof(hsk_split_params)) / sizeof(hsk_split_plane); }
 
 // hsk_split_scene's answer from the held records and stats
 static int split_reply(hsk_ctx* k, hsk_object* recs, size_t cap, size_t* n_objects, hsk_split_stats* stats, bool reused) {
-  const size_t n = k->split_recs.size();
-  *n_objects = n;
   if (stats) {
     *stats = k->split_stats;
     stats->reused = reused ? 1u : 0u;
   }
-  if (!recs) return HSK_OK;
-  if (cap < n) return fail(k, HSK_ERR_ARG, "hsk_split_scene: cap is below the number of kept objects");
-  if (n > 0) memcpy(recs, k->split_recs.data(), n * sizeof(hsk_object));
-  return HSK_OK;
+  return reply_records(k, k->split_recs, recs, cap, n_objects, "hsk_split_scene: cap is below the number of kept objects");
 }
 
 extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t n_planes, const hsk_split_params* params, hsk_object* recs, size_t cap,
@@ -154,7 +122,9 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
   if (!k) return HSK_ERR_ARG;
   if (!n_objects || (n_planes > 0 && !planes)) return fail(k, HSK_ERR_ARG, "hsk_split_scene: null argument");
   if (n_planes > HSK_SPLIT_MAX_PLANES) return fail(k, HSK_ERR_ARG, "hsk_split_scene: more than 64 planes");
-  hsk_split_params p;
+  SplitKey key;
+  memset(&key, 0, sizeof(key));  // (compared as bytes: the padding is zero on both sides)
+  hsk_split_params& p = key.p;
   hsk_default_split_params(k, &p);  // (zeroes the whole struct first)
   if (params) {
     p.dist_m = params->dist_m;
@@ -166,8 +136,7 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
   if (!(p.back_m > 0.0f && p.back_m <= 2.0f)) return fail(k, HSK_ERR_ARG, "hsk_split_scene: back_m must lie in (0, 2]");
   if (!(p.cos_min >= 0.0f && p.cos_min <= 1.0f)) return fail(k, HSK_ERR_ARG, "hsk_split_scene: cos_min must lie in [0, 1]");
   if (p.min_voxels < 1) return fail(k, HSK_ERR_ARG, "hsk_split_scene: min_voxels must be at least 1");
-  hsk_split_plane pl[HSK_SPLIT_MAX_PLANES];
-  memset(pl, 0, sizeof(pl));  // (compared as bytes: the padding is zero on both sides)
+  hsk_split_plane* pl = key.planes;
   for (size_t i = 0; i < n_planes; ++i) {
     const float* a = planes[i].abcd;
     const double len = std::sqrt(((double)a[0] * (double)a[0] + (double)a[1] * (double)a[1]) + (double)a[2] * (double)a[2]);
@@ -181,17 +150,15 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
   }
   if (int rc = volume_state_check(k, k, "hsk_split_scene")) return rc;
   // the split of an earlier call still fits: the volume stands, the planes and the parameters are the same.  Nothing is launched
-  const bool held = k->d_split && k->split_epoch != 0 && k->split_epoch == k->vol_epoch && k->split_planes.size() == n_planes &&
-                    (n_planes == 0 || memcmp(k->split_planes.data(), pl, n_planes * sizeof(hsk_split_plane)) == 0) &&
-                    memcmp(&k->split_params, &p, sizeof(p)) == 0;
+  const bool held = k->split.stands_for(k, &key, split_key_bytes(n_planes));
   if (held) return split_reply(k, recs, cap, n_objects, stats, true);
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  k->split_epoch = 0;  // (the scratch is about to be written: an earlier split goes)
+  k->split.drop();  // (the scratch is about to be written: an earlier split goes)
   k->split_recs.clear();
-  int r = ensure_grown(k, &k->d_split, &k->split_bytes, split_layout(k->vp, nullptr, nullptr));
+  int r = k->split.grow(k, split_layout(k->vp, nullptr, nullptr));
   if (r != HSK_OK) return r;
   SplitBufs b;
-  split_layout(k->vp, k->d_split, &b);
+  split_layout(k->vp, k->split.buf, &b);
   SplitRule rule;
   SplitPlaneQ q[HSK_SPLIT_MAX_PLANES];
   split_rule_of(k, p, pl, n_planes, &rule, q);
@@ -202,12 +169,9 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
   launch_split_classify(k->stream, k->d_vol, k->vp, b, rule);
   launch_comp_label(k->stream, b.cls, k->vp, b.comp);
   HIPCHK(k, hipGetLastError());
-  unsigned counts[SPLIT_COUNTS], n_roots = 0;
+  unsigned counts[SPLIT_COUNTS];
   r = copy_out(k, counts, b.counts, sizeof(counts));
-  if (r == HSK_OK) r = copy_out(k, &n_roots, b.comp.counts + 4, sizeof(n_roots));
   if (r != HSK_OK) return r;
-  HIPCHK(k, hipStreamSynchronize(k->stream));
-  HIPCHK(k, hipGetLastError());
   hsk_split_stats st;
   memset(&st, 0, sizeof(st));
   uint64_t classed = 0;
@@ -219,56 +183,17 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
   st.n_edge = counts[6];
   st.n_no_normal = counts[7];
   *n_objects = 0;
-  if ((size_t)n_roots > HSK_COMPONENT_MAX) return fail(k, HSK_ERR_ARG, "hsk_split_scene: more than 2^24 objects: nothing is held");
-  std::vector<unsigned> roots, table, rec;
-  try {
-    roots.resize(n_roots);
-    table.resize((size_t)n_roots * 8);
-    rec.resize((size_t)n_roots * SPLIT_REC_WORDS);
-    k->split_planes.assign(pl, pl + n_planes);
-  } catch (const std::bad_alloc&) {
-    return fail(k, HSK_ERR_STATE, "hsk_split_scene: out of host memory for the records");
-  }
-  if (n_roots > 0) {
-    r = ensure_grown(k, &k->d_split_tab, &k->split_tab_bytes, split_tab(k, n_roots).bytes);
-    if (r != HSK_OK) return r;
-    const SplitTab t = split_tab(k, n_roots);
-    launch_comp_records(k->stream, k->vp, b.comp, n_roots, t.roots, t.table);
-    // the MINOR step: the words of an object below min_voxels keep their class in the weight half and stop being members
-    const unsigned min_voxels = p.min_voxels > 0xffffffffull ? 0xffffffffu : (unsigned)p.min_voxels;  // (no object has 2^32 voxels)
-    launch_comp_prune(k->stream, b.cls, nullptr, k->vp, b.comp.parent, t.roots, t.table, n_roots, min_voxels, t.roots, 0u, true);
-    launch_split_records(k->stream, k->vp, b, n_roots, t.roots, t.rec, rule.floor_plane);
-    HIPCHK(k, hipGetLastError());
-    r = copy_out(k, roots.data(), t.roots, (size_t)n_roots * 4);
-    if (r == HSK_OK) r = copy_out(k, table.data(), t.table, (size_t)n_roots * 32);
-    if (r == HSK_OK) r = copy_out(k, rec.data(), t.rec, (size_t)n_roots * SPLIT_REC_WORDS * 4);
-    if (r != HSK_OK) return r;
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipGetLastError());
-  }
+  RegionRead rr;
+  r = region_read(k, b.comp, &k->split, SPLIT_REC_WORDS, 0, "hsk_split_scene: more than 2^24 objects: nothing is held",
+                  "hsk_split_scene: out of host memory for the records", b.cls, p.min_voxels,
+                  [&](const RegionTab& t, unsigned n) { launch_split_records(k->stream, k->vp, b, n, t.roots, t.extra, rule.floor_plane); }, &rr);
+  if (r != HSK_OK) return r;
   const CompGrid g{(unsigned)k->vp.X, (unsigned)k->vp.Y, (unsigned)k->vp.Z};
   uint64_t kept = 0;
   try {
-    for (size_t i = 0; i < n_roots; ++i) {
-      const unsigned* t8 = &table[i * 8];
-      if ((uint64_t)t8[0] < p.min_voxels) {
-        st.n_minor_objects += 1;
-        continue;
-      }
-      hsk_object c;
-      memset(&c, 0, sizeof(c));
-      unsigned x, y, z;
-      g.xyz(roots[i], x, y, z);
-      c.root[0] = (int32_t)x;
-      c.root[1] = (int32_t)y;
-      c.root[2] = (int32_t)z;
-      c.n_voxels = t8[0];
-      const unsigned* t16 = &rec[i * SPLIT_REC_WORDS];
-      for (int a = 0; a < 3; ++a) {
-        c.lo[a] = (int32_t)t8[1 + a];
-        c.hi[a] = (int32_t)t8[4 + a];
-        c.sum[a] = (uint64_t)t16[2 * a] | ((uint64_t)t16[2 * a + 1] << 32);
-      }
+    st.n_minor_objects = comp_region_records(g, rr.roots.data(), rr.table.data(), rr.n, p.min_voxels, &k->split_recs, [&](hsk_object& c, size_t i) {
+      const unsigned* t16 = &rr.extra[i * SPLIT_REC_WORDS];
+      for (int a = 0; a < 3; ++a) c.sum[a] = (uint64_t)t16[2 * a] | ((uint64_t)t16[2 * a + 1] << 32);
       for (int a = 0; a < 4; ++a) c.contact[a] = t16[SPLIT_REC_CONTACT + a];
       c.plane_mask = (uint64_t)t16[SPLIT_REC_MASK] | ((uint64_t)t16[SPLIT_REC_MASK + 1] << 32);
       if (rule.floor_plane >= 0) {
@@ -276,24 +201,18 @@ extern "C" int hsk_split_scene(hsk_ctx* k, const hsk_split_plane* planes, size_t
         c.height_hi = (int32_t)(t16[SPLIT_REC_HHI] ^ 0x80000000u);
       }
       kept += c.n_voxels;
-      k->split_recs.push_back(c);
-    }
+    });
   } catch (const std::bad_alloc&) {
     k->split_recs.clear();
     return fail(k, HSK_ERR_STATE, "hsk_split_scene: out of host memory for the records");
   }
-  std::sort(k->split_recs.begin(), k->split_recs.end(), [&](const hsk_object& a, const hsk_object& c) {
-    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
-                              g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
-  });
   // the final classes: what the kept objects hold stays OBJECT, the rest is MINOR
   st.n_class[SPLIT_MINOR] = st.n_class[SPLIT_OBJECT] - kept;
   st.n_class[SPLIT_OBJECT] = kept;
   st.n_objects = k->split_recs.size();
   st.largest = k->split_recs.empty() ? 0 : k->split_recs[0].n_voxels;
   k->split_stats = st;
-  k->split_params = p;  // (zeroed before it was filled: the padding is zero)
-  k->split_epoch = k->vol_epoch;
+  k->split.stamp(k, &key, split_key_bytes(n_planes));
   return split_reply(k, recs, cap, n_objects, stats, false);
 }
 
@@ -304,14 +223,14 @@ extern "C" int hsk_download_split(hsk_ctx* k, const hsk_voxel_box* box, uint8_t*
   if (int rc = clear_box_check(k, box, "hsk_download_split", &bx, &n)) return rc;
   if (n > 0 && !cls) return fail(k, HSK_ERR_ARG, "hsk_download_split: cls is null");
   if (int rc = volume_state_check(k, k, "hsk_download_split")) return rc;
-  if (int rc = split_held_check(k, "hsk_download_split")) return rc;
+  if (int rc = k->split.require(k, "hsk_download_split", SPLIT_NOT_HELD)) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ProductArrays pa;
   const int a_cls = pa.add(cls, n), a_plane = pa.add(plane, n), a_object = pa.add(object, n * 4);
   if (int r = pa.place(k)) return r;
   SplitBufs b;
-  split_layout(k->vp, k->d_split, &b);
+  split_layout(k->vp, k->split.buf, &b);
   launch_split_box(k->stream, k->vp, b, bx.lo, bx.hi, n, pa.dev<unsigned char>(a_cls), pa.dev<unsigned char>(a_plane), pa.dev<unsigned>(a_object));
   HIPCHK(k, hipGetLastError());
   return pa.copy_out(k);
@@ -319,18 +238,16 @@ extern "C" int hsk_download_split(hsk_ctx* k, const hsk_voxel_box* box, uint8_t*
 
 extern "C" int hsk_split_at(hsk_ctx* k, const float* xyz, size_t n, int radius, uint8_t* cls, uint8_t* plane, uint32_t* object) {
   if (!k) return HSK_ERR_ARG;
-  if (n > 0 && (!xyz || !cls)) return fail(k, HSK_ERR_ARG, "hsk_split_at: null argument");
-  if (n > HSK_CLEAR_MAX_POINTS) return fail(k, HSK_ERR_ARG, "hsk_split_at: more than 2^20 points");
-  if (radius < 0 || radius > 4) return fail(k, HSK_ERR_ARG, "hsk_split_at: radius must lie in 0..4");
+  if (int rc = points_check(k, "hsk_split_at", xyz, cls, n, radius, 4)) return rc;
   if (int rc = volume_state_check(k, k, "hsk_split_at")) return rc;
-  if (int rc = split_held_check(k, "hsk_split_at")) return rc;
+  if (int rc = k->split.require(k, "hsk_split_at", SPLIT_NOT_HELD)) return rc;
   if (n == 0) return HSK_OK;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   ProductArrays pa;  // (the points first: kept for the gather, not handed back)
   const int a_pts = pa.add(nullptr, n * 12, true), a_cls = pa.add(cls, n), a_plane = pa.add(plane, n), a_object = pa.add(object, n * 4);
   if (int r = pa.place(k)) return r;
   SplitBufs b;
-  split_layout(k->vp, k->d_split, &b);
+  split_layout(k->vp, k->split.buf, &b);
   HIPCHK(k, hipMemcpyAsync(pa.dev<float>(a_pts), xyz, n * 12, hipMemcpyHostToDevice, k->stream));
   launch_split_gather(k->stream, k->vp, b, pa.dev<float>(a_pts), (unsigned)n, radius, pa.dev<unsigned char>(a_cls), pa.dev<unsigned char>(a_plane),
                       pa.dev<unsigned>(a_object));
@@ -348,7 +265,7 @@ extern "C" int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, c
   if (p.fill_weight < 1 || p.fill_weight > 128) return fail(k, HSK_ERR_ARG, "hsk_remove_objects: fill_weight must lie in 1..128");
   if (roots && n > HSK_REMOVE_MAX_OBJECTS) return fail(k, HSK_ERR_ARG, "hsk_remove_objects: more than 256 roots");
   if (int rc = volume_state_check(k, k, "hsk_remove_objects")) return rc;
-  if (int rc = split_held_check(k, "hsk_remove_objects")) return rc;
+  if (int rc = k->split.require(k, "hsk_remove_objects", SPLIT_NOT_HELD)) return rc;
   if (!roots && k->split_recs.size() > HSK_REMOVE_MAX_OBJECTS)
     return fail(k, HSK_ERR_ARG, "hsk_remove_objects: more than 256 kept objects: name the roots");
   // the selected records, each once
@@ -399,10 +316,12 @@ extern "C" int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, c
   }
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   SplitBufs b;
-  split_layout(k->vp, k->d_split, &b);
+  split_layout(k->vp, k->split.buf, &b);
   SplitRule rule;
   SplitPlaneQ q[HSK_SPLIT_MAX_PLANES];
-  split_rule_of(k, k->split_params, k->split_planes.data(), k->split_planes.size(), &rule, q);  // (the table on the device is the held split's)
+  SplitKey held;  // (the table on the device is the held split's)
+  memcpy(&held, k->split.key.data(), k->split.key.size());
+  split_rule_of(k, held.p, held.planes, split_key_planes(k->split), &rule, q);
   HIPCHK(k, hipMemcpyAsync(b.sel, sel, n_sel * sizeof(SplitSelected), hipMemcpyHostToDevice, k->stream));
   HIPCHK(k, hipStreamSynchronize(k->stream));  // (`sel` is this frame's)
   launch_split_halo(k->stream, k->d_vol, k->vp, b, n_sel, uni_lo, uni_hi, rule, p.mode, p.halo, p.fill_weight);
@@ -417,14 +336,9 @@ extern "C" int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, c
   st.n_restored = counts[2];
   if (st.n_written > 0) {
     st.n_colored = k->d_color ? st.n_written : 0;
-    flush_weights(k);  // the words that stay are to hold their weights
-    launch_split_restore(k->stream, k->d_vol, k->d_color, k->vp, b, n_sel, uni_lo, uni_hi, rule, p.mode, p.fill_weight);
-    HIPCHK(k, hipGetLastError());
-    k->split_epoch = 0;  // (the held split described the volume as it was)
-    r = volume_replaced(k);
+    r = commit_volume_write(k, [&] { launch_split_restore(k->stream, k->d_vol, k->d_color, k->vp, b, n_sel, uni_lo, uni_hi, rule, p.mode, p.fill_weight); });
+    k->split.drop();  // (the held split described the volume as it was)
     if (r != HSK_OK) return r;
-    HIPCHK(k, hipStreamSynchronize(k->stream));
-    HIPCHK(k, hipGetLastError());
   }  // (else nothing is written, vol_epoch does not move: cached passes and the split stay valid)
   if (stats) *stats = st;
   return HSK_OK;
@@ -433,15 +347,7 @@ extern "C" int hsk_remove_objects(hsk_ctx* k, const uint32_t* roots, size_t n, c
 extern "C" int hsk_release_split(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
-  for (void** buf : {&k->d_split, &k->d_split_tab})
-    if (*buf) {
-      HIPCHK(k, hipStreamSynchronize(k->stream));
-      HIPCHK(k, hipFree(*buf));
-      *buf = nullptr;
-    }
-  k->split_bytes = k->split_tab_bytes = 0;
-  k->split_epoch = 0;
+  const int r = k->split.release(k);
   k->split_recs.clear();
-  k->split_planes.clear();
-  return HSK_OK;
+  return r;
 }

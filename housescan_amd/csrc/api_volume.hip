@@ -31,6 +31,17 @@ int volume_replaced(hsk_ctx* k) {
   return HSK_OK;
 }
 
+int commit_volume_write(hsk_ctx* k, const std::function<void()>& launch) {
+  flush_weights(k);
+  launch();
+  HIPCHK(k, hipGetLastError());
+  const int r = volume_replaced(k);
+  if (r != HSK_OK) return r;
+  HIPCHK(k, hipStreamSynchronize(k->stream));
+  HIPCHK(k, hipGetLastError());
+  return HSK_OK;
+}
+
 extern "C" int hsk_flush_weights(hsk_ctx* k) {
   if (!k) return HSK_ERR_ARG;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
@@ -65,7 +76,7 @@ extern "C" int hsk_upload_color(hsk_ctx* k, const uint8_t* rgbw) {
   if (int rc = require_color(k)) return rc;
   HIPCHK(k, hipSetDevice(k->cfg.device_id));
   HIPCHK(k, hipMemcpyAsync(k->d_color, rgbw, k->color_bytes, hipMemcpyHostToDevice, k->stream));
-  k->pk_epoch = 0;  // (the volume image's pass is void)
+  k->pack.drop();  // (the volume image's pass is void)
   HIPCHK(k, hipStreamSynchronize(k->stream));
   return HSK_OK;
 }
@@ -140,7 +151,7 @@ extern "C" int hsk_fuse_volume(hsk_ctx* dst, hsk_ctx* src, const float src_to_ds
 // ------------------------------------------------------------------------------------------------------
 // volume files (include/hskinfu.h "Volume files")
 // ------------------------------------------------------------------------------------------------------
-// the pack scratch, carved out of d_pack: counters (8 words for the TSDF, 8 for the colour), the class tables (zero-padded to
+// the pack scratch, carved out of pack's buffer: counters (8 words for the TSDF, 8 for the colour), the class tables (zero-padded to
 // the image's table length), the size / offset tables, the scan's block sums
 struct PackBufs {
   size_t n_bricks, table_bytes, bytes;
@@ -153,7 +164,7 @@ static PackBufs pack_bufs(const hsk_ctx* k) {
   b.n_bricks = pack_bricks(k->vp);
   b.table_bytes = (size_t)hskv_table_bytes(b.n_bricks);
   ProductLayout l;
-  char* base = (char*)k->d_pack;
+  char* base = (char*)k->pack.buf;
   b.counts = (unsigned*)(base + l.take(64));
   b.cls_t = (unsigned char*)(base + l.take(b.table_bytes));
   b.cls_c = (unsigned char*)(base + l.take(b.table_bytes));
@@ -164,16 +175,15 @@ static PackBufs pack_bufs(const hsk_ctx* k) {
   return b;
 }
 static int ensure_pack(hsk_ctx* k) {
-  if (k->d_pack) return HSK_OK;
+  if (k->pack.buf) return HSK_OK;
   const size_t bytes = pack_bufs(k).bytes;
-  HIPCHK(k, hipMalloc(&k->d_pack, bytes));
-  const hipError_t e = hipMemsetAsync(k->d_pack, 0, bytes, k->stream);  // (the tables' padding stays zero from here on)
+  const int r = k->pack.grow(k, bytes);
+  if (r != HSK_OK) return r;
+  const hipError_t e = hipMemsetAsync(k->pack.buf, 0, bytes, k->stream);  // (the tables' padding stays zero from here on)
   if (e != hipSuccess) {
-    (void)hipFree(k->d_pack);
-    k->d_pack = nullptr;
+    (void)k->pack.release(k);
     HIPCHK(k, e);
   }
-  k->pk_epoch = 0;
   return HSK_OK;
 }
 // the state every call of this section needs: a context that stores its whole volume, with no frame in flight
@@ -219,9 +229,9 @@ extern "C" int hsk_pack_volume(hsk_ctx* k, void* buf, size_t cap_bytes, size_t* 
   if (r != HSK_OK) return r;
   const PackBufs pb = pack_bufs(k);
   const bool colour = k->d_color != nullptr;
-  const bool reused = k->pk_epoch == k->vol_epoch && k->pk_color == colour;
+  const bool reused = k->pack.stands_for(k, &colour, sizeof(colour));
   if (!reused) {
-    k->pk_epoch = 0;
+    k->pack.drop();
     launch_pack_classify(k->stream, k->d_vol, k->vp, pb.cls_t, pb.off_t);
     launch_pack_scan(k->stream, pb.off_t, pb.n_bricks, pb.bsum, pb.counts);
     if (colour) {
@@ -231,8 +241,7 @@ extern "C" int hsk_pack_volume(hsk_ctx* k, void* buf, size_t cap_bytes, size_t* 
     HIPCHK(k, hipGetLastError());
     HIPCHK(k, hipMemcpyAsync(k->pk_counts, pb.counts, 64, hipMemcpyDeviceToHost, k->stream));
     HIPCHK(k, hipStreamSynchronize(k->stream));
-    k->pk_epoch = k->vol_epoch;
-    k->pk_color = colour;
+    k->pack.stamp(k, &colour, sizeof(colour));
   }
   hsk_volume_info f;
   r = pack_fill_info(k, &f);
@@ -296,7 +305,7 @@ extern "C" int hsk_unpack_volume(hsk_ctx* k, const void* buf, size_t n_bytes) {
   const size_t payload_t = (size_t)f.tsdf_payload_bytes, payload_c = colour ? (size_t)f.color_payload_bytes : 0;
   r = ensure_product_bytes(k, payload_t + payload_c + 512);
   if (r != HSK_OK) return r;
-  k->pk_epoch = 0;  // the pack tables are about to hold the image's classes
+  k->pack.drop();  // the pack tables are about to hold the image's classes
   const unsigned char* src = (const unsigned char*)buf;
   // a host range into device memory, in pieces through the pinned pair; `turn` counts the pieces of this call
   int turn = 0;

@@ -3,7 +3,8 @@
 // and `unite` over an array of parents.  Plain C++ with no HIP type in it: the atomic minimum and the load are a template
 // argument, so tests/comp_point_harness.cpp compiles the same text for the host with a plain minimum and labels a volume
 // sequentially, and tests/test_components_host.py compares it with the numpy twin (tests/components_twin.py).  The kernels' two
-// sets of atomic operations stand beside the sequential ones, for the device compiler alone.
+// sets of atomic operations stand beside the sequential ones, for the device compiler alone.  Last comes the host's half of the
+// records (comp_region_records): the library and the harnesses of the labelling, the diff and the split all run that one text.
 //
 // THE INVARIANT every loop below rests on: parent[v] <= v, always, for every v that is a member.  An entry starts as v, and is
 // only ever lowered (an atomic minimum with a smaller member of the same component).  So a walk v -> parent[v] -> ... is
@@ -11,6 +12,10 @@
 // meanwhile.  No thread ever waits for another.
 #pragma once
 #include <stddef.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "hsk_sample.h"
 #if defined(__HIPCC__)
@@ -128,4 +133,37 @@ HSK_HD unsigned comp_search(const unsigned* roots, unsigned n, unsigned root) {
 // the order of the records: more voxels first, ties to the smaller root
 HSK_HD bool comp_record_before(unsigned long long n_a, unsigned root_a, unsigned long long n_b, unsigned root_b) {
   return n_a != n_b ? n_a > n_b : root_a < root_b;
+}
+
+// The ABI's records of n labelled regions (host only; hsk_component, hsk_diff_region and hsk_object all have root, n_voxels, lo
+// and hi), from the ascending roots and the table's eight words a region (count, lo[3], hi[3], one unused): a zeroed record with
+// those four members for every region of at least min_voxels, handed to extra(record, the region's index) for what else it
+// holds, then all of them in comp_record_before's order.  Returns the regions below min_voxels.
+template <class Rec, class Extra>
+size_t comp_region_records(const CompGrid& g, const unsigned* roots, const unsigned* table, size_t n, unsigned long long min_voxels, std::vector<Rec>* recs,
+                           Extra extra) {
+  size_t n_below = 0;
+  recs->clear();
+  for (size_t i = 0; i < n; ++i) {
+    const unsigned* t8 = table + i * 8;
+    if ((unsigned long long)t8[0] < min_voxels) {
+      n_below += 1;
+      continue;
+    }
+    Rec c;
+    memset(&c, 0, sizeof(c));
+    unsigned p[3];
+    g.xyz(roots[i], p[0], p[1], p[2]);
+    c.n_voxels = t8[0];
+    for (int a = 0; a < 3; ++a) {
+      c.root[a] = (int)p[a];
+      c.lo[a] = (int)t8[1 + a];
+      c.hi[a] = (int)t8[4 + a];
+    }
+    extra(c, i);
+    recs->push_back(c);
+  }
+  auto lin_of = [&](const Rec& c) { return g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]); };
+  std::sort(recs->begin(), recs->end(), [&](const Rec& a, const Rec& c) { return comp_record_before(a.n_voxels, lin_of(a), c.n_voxels, lin_of(c)); });
+  return n_below;
 }

@@ -35,6 +35,29 @@ inline uint64_t next_ctx_serial() {
   return n.fetch_add(1) + 1;
 }
 
+// A pass over the whole volume whose result stays on the device while the volume stands: the scratch, an optional second
+// table buffer that only grows, the vol_epoch it was made at (0: nothing is held; vol_epoch starts at 1) and the key it was made
+// for, as bytes.  A build drops what is held before it writes the scratch and stamps it once the result has been read back; an
+// error in between leaves nothing held.  (The bodies follow HIPCHK, below.)
+struct hsk_ctx;
+struct HeldPass {
+  void* buf = nullptr;
+  size_t bytes = 0;
+  void* tab = nullptr;
+  size_t tab_bytes = 0;
+  uint64_t epoch = 0;
+  std::vector<unsigned char> key;
+  inline bool stands(const hsk_ctx* k) const;
+  bool stands_for(const hsk_ctx* k, const void* kp, size_t n) const { return stands(k) && key.size() == n && (n == 0 || memcmp(key.data(), kp, n) == 0); }
+  void drop() { epoch = 0; }
+  inline int grow(hsk_ctx* k, size_t want);      // a scratch that has to be made again drops what it held
+  inline int grow_tab(hsk_ctx* k, size_t want);  // (the table is filled and read back within one call: nothing held lives in it)
+  inline void stamp(const hsk_ctx* k, const void* kp = nullptr, size_t n = 0);
+  inline int release(hsk_ctx* k);  // frees both buffers behind what the stream still holds
+  // HSK_ERR_STATE "<who><what>" unless it stands
+  inline int require(hsk_ctx* k, const char* who, const char* what) const;
+};
+
 struct hsk_ctx {
   hsk_config cfg;
   uint64_t serial = next_ctx_serial();
@@ -145,10 +168,26 @@ struct hsk_ctx {
   int color_max_w = 0;
   bool group_slab = false;  // a slab of a group (hsk_group_create*): no colour
   float color_band = 0.0f;
-  // the indexed mesh's scratch (hsk_extract_mesh_indexed: edge bits, per-row tables; extract.hip mesh_index_layout), made on
-  // first use; its counts belong to ro_kind 4
-  void* d_mi = nullptr;
-  size_t mi_bytes = 0;
+  // the passes held over the volume, each with its scratch (HeldPass; hsk_destroy frees them through `passes`):
+  // mi: the indexed mesh's scratch (extract.hip mesh_index_layout), made on first use; only a buffer -- its counts are ro_kind 4's
+  // pack: the volume image's class and offset pass (pack.hip: 64 B of counters, the two class tables, the two size / offset
+  //   tables, the scan's block sums), keyed by the colour flag; pk_counts its counters
+  // comp: the labelling (components.hip comp_layout: counters, row tables, one parent per volume word); tab = the roots
+  //   ascending, eight words per component, the survivors of a keep_largest prune (region_tab)
+  // fill: the last fill's scratch (fill.hip fill_layout), its mask at fill_mask
+  // diff: diff_layout's counters, class words, byte volumes and labelling scratch; tab = the regions' roots, records and class
+  //   counts.  Key: cur's serial and cur's vol_epoch (two uint64: hsk_adopt_diff reads them back), then the zero-padded parameters
+  // split: split_layout's scratch; tab = the objects' roots and records.  Key: the zero-padded parameters, then the planes
+  //   (hsk_remove_objects reads both back)
+  // clear: clear_layout's counters, field and intermediates.  Key: the 20 device-relevant parameter bytes (clear_key_of)
+  // reach: reach_layout's counters, field, tile flags and worklists.  Key: the clearance key, min_d2, max_cost, then the seed
+  //   voxels (those inside the grid, in the caller's order)
+  // part: part_layout's scratch; tab = the dense door table of the last build or floor call.  Key: the clearance key and the four
+  //   partition parameters
+  // simp: the simplified mesh's count pass (simp_layout of the cluster size asked for); tab = what is proportional to the output,
+  //   per output vertex its cluster's number and its 20 sums (164 B).  Key: the shift
+  HeldPass mi, pack, comp, fill, diff, split, clear, reach, part, simp;
+  HeldPass* const passes[10] = {&mi, &pack, &comp, &fill, &diff, &split, &clear, &reach, &part, &simp};
   // scene views (hsk_render_view), made on first use: the free camera's block and the counter slots in device memory, and their
   // pinned host side (the camera on its way in, the counts on their way out)
   void* d_view = nullptr;
@@ -157,10 +196,6 @@ struct hsk_ctx {
   // brick table (fuse.hip)
   void* d_fuse = nullptr;
   size_t fuse_bytes = 0;
-  // volume images (hsk_pack_volume / hsk_unpack_volume), made on first use: 64 B of counters, the two class tables, the two
-  // size / offset tables and the scan's block sums (pack.hip); what the tables hold is the class and offset pass of the
-  // volume at pk_epoch (0: nothing), with or without colour, and pk_counts its counters
-  void* d_pack = nullptr;
   // the scratch of every call that works on a cloud (align_scratch -> CloudScratch), made on first use and only grown: the
   // alignment's accumulators (align.hip: HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what the call carves for
   // itself -- RelocScratch (api_reloc.hip), PlaneScratch (api_planes.hip) or LevelScratch (api_level.hip); h_align: the
@@ -168,106 +203,39 @@ struct hsk_ctx {
   void* d_align = nullptr;
   size_t align_bytes = 0;
   unsigned long long* h_align = nullptr;
-  uint64_t pk_epoch = 0;
-  bool pk_color = false;
-  unsigned pk_counts[16] = {};
-  // surface components (hsk_label_components; components.hip), made on first use and only grown:
-  // d_comp = 64 B of counters, the rows' root counts / offsets and their scan's block sums, then one parent per volume word
-  // (comp_layout); d_comp_tab = the roots in ascending order, then eight words per component (count, lo, hi), then the
-  // survivors of a keep_largest prune.  What they hold is the labelling of the volume at comp_epoch (0: nothing), and
-  // comp_recs its records in their order
-  void* d_comp = nullptr;
-  size_t comp_bytes = 0;
-  void* d_comp_tab = nullptr;
-  size_t comp_tab_bytes = 0;
-  uint64_t comp_epoch = 0;
+  unsigned pk_counts[16] = {};  // the counters of the volume image's pass (pack)
+  // surface components (hsk_label_components): comp_recs the records of what `comp` holds, in their order
   uint64_t comp_inside = 0;  // the voxels of all components
   std::vector<hsk_component> comp_recs;
-  // hole filling (hsk_fill_holes; fill.hip), made by the first call that fills and only grown: d_fill = fill_layout's counters,
-  // tile bytes and two state buffers.  What it holds is the mask of the last fill, at fill_mask, valid while vol_epoch is
-  // fill_epoch (0: nothing)
-  void* d_fill = nullptr;
-  size_t fill_bytes = 0;
-  uint64_t fill_epoch = 0;
+  // hole filling (hsk_fill_holes): where in fill's scratch the last fill's mask lies
   const unsigned char* fill_mask = nullptr;
-  // volume differencing (hsk_diff_volume; diff.hip), made by the first call that diffs and freed by hsk_release_diff: d_diff =
-  // diff_layout's counters, class words, byte volumes and labelling scratch; d_diff_tab = the regions' roots, records and class
-  // counts (grown only).  What they hold is the diff of this volume at diff_key[0] against the context with the serial diff_key[1]
-  // at its epoch diff_key[2] (all 0: nothing); diff_recs the kept regions' records in their order, diff_stats
-  // the call's stats, diff_params its parameters: hsk_diff_volume answers a call with the same cur and parameters from them
-  void* d_diff = nullptr;
-  size_t diff_bytes = 0;
-  void* d_diff_tab = nullptr;
-  size_t diff_tab_bytes = 0;
-  uint64_t diff_key[3] = {0, 0, 0};
+  // volume differencing (hsk_diff_volume): diff_recs the kept regions' records in their order, diff_stats the call's stats --
+  // hsk_diff_volume answers a call with the same cur and parameters from them
   std::vector<hsk_diff_region> diff_recs;
   hsk_diff_stats diff_stats = {};
-  hsk_diff_params diff_params = {};
-  // the scene split (hsk_split_scene; split.hip), made by the first call that splits and freed by hsk_release_split: d_split =
-  // split_layout's counters, tables, class words, byte volumes and labelling scratch; d_split_tab = the objects' roots and records
-  // (grown only).  What they hold is the split of this volume at split_epoch (0: nothing) for the planes split_planes and the
-  // parameters split_params, compared as bytes; split_recs the kept objects' records in their order, split_stats the call's stats:
+  // the scene split (hsk_split_scene): split_recs the kept objects' records in their order, split_stats the call's stats --
   // hsk_split_scene answers a call with the same planes and parameters from them
-  void* d_split = nullptr;
-  size_t split_bytes = 0;
-  void* d_split_tab = nullptr;
-  size_t split_tab_bytes = 0;
-  uint64_t split_epoch = 0;
-  std::vector<hsk_split_plane> split_planes;
-  hsk_split_params split_params = {};
   std::vector<hsk_object> split_recs;
   hsk_split_stats split_stats = {};
-  // the clearance field (hsk_build_clearance; clearance.hip), made by the first call that builds and freed by
-  // hsk_release_clearance: d_clear = clear_layout's counters, field and intermediates.  What it holds is the field of the volume
-  // at clear_epoch (0: nothing) for the 20 device-relevant parameter bytes in clear_key, and clear_counts its counters
-  void* d_clear = nullptr;
-  size_t clear_bytes = 0;
-  uint64_t clear_epoch = 0;
-  uint32_t clear_key[5] = {};
+  // the clearance field (hsk_build_clearance): its counters
   unsigned long long clear_counts[3] = {0, 0, 0};
-  // the reach field (hsk_build_reach; reach.hip), made by the first build and freed by hsk_release_reach: d_reach = reach_layout's
-  // counters, field, tile flags and worklists.  What it holds is the field of the volume at reach_epoch (0: nothing) for the
-  // clearance key, min_d2 and max_cost in reach_key and the seed voxels in reach_seeds (the seeds inside the grid, in the caller's
-  // order); reach_q its geometry and costs (the path trace's), reach_counts its counters, reach_rounds its rounds
-  void* d_reach = nullptr;
-  size_t reach_bytes = 0;
-  uint64_t reach_epoch = 0;
-  uint32_t reach_key[7] = {};
-  std::vector<uint32_t> reach_seeds;
+  // the reach field (hsk_build_reach): reach_q its geometry and costs (the path trace's), reach_counts its counters,
+  // reach_rounds its rounds
   ReachGeom reach_q = {};
   unsigned long long reach_counts[4] = {0, 0, 0, 0};
   uint32_t reach_rounds = 0;
   unsigned long long reach_tiles = 0;  // the tiles relaxed over all rounds of the last hsk_build_reach that built (hsk_reach_tiles_relaxed)
-  // the room partition (hsk_build_partition; partition.hip), made by the first build and freed by hsk_release_partition: d_part =
-  // part_layout's counters, keys, parents, tile flags, worklists and tables; d_part_tab = the dense door table of the last build
-  // or floor call (grown only).  What d_part holds is the partition of the volume at part_epoch (0: nothing) for the clearance key
-  // and the four partition parameters in part_key; part_q its geometry, part_recs and part_doors its records in their order,
+  // the room partition (hsk_build_partition): part_q its geometry, part_recs and part_doors its records in their order,
   // part_counts = passable, cores, kept cores, assigned
-  void* d_part = nullptr;
-  size_t part_bytes = 0;
-  void* d_part_tab = nullptr;
-  size_t part_tab_bytes = 0;
-  uint64_t part_epoch = 0;
-  uint32_t part_key[9] = {};
   PartGeom part_q = {};
   std::vector<hsk_room> part_recs;
   std::vector<hsk_door> part_doors;
   unsigned long long part_counts[4] = {0, 0, 0, 0};
   uint32_t part_rounds = 0;
   unsigned long long part_tiles = 0, part_first = 0;  // of the last build that built: tiles relaxed over all rounds, tiles of the first worklist
-  // the simplified mesh (hsk_extract_mesh_simplified; simplify.hip), made on first use and only grown: d_simp = the fixed scratch
-  // of the cluster size asked for (simp_layout: a byte per cluster of the grid, the cluster rows' and the cube rows' tables);
-  // d_simp_out = what is proportional to the output -- per output vertex its cluster's number and its 20 sums (164 B)
-  // ... and what d_simp holds: the count pass (the cube rows' surviving faces, the cluster bytes and rows, their scans) of the
-  // volume at simp_epoch (0: nothing) for clusters of 2^simp_shift voxels, and simp_totals its faces, vertices and clusters --
-  // a size query followed by the fill counts once, as the other products do
-  void* d_simp = nullptr;
-  size_t simp_bytes = 0;
-  uint64_t simp_epoch = 0;
-  int simp_shift = 0;
+  // the simplified mesh (hsk_extract_mesh_simplified): simp_totals the faces, vertices and clusters of simp's count pass -- a
+  // size query followed by the fill counts once, as the other products do
   unsigned long long simp_totals[3] = {0, 0, 0};
-  void* d_simp_out = nullptr;
-  size_t simp_out_bytes = 0;
   // the keyframe store (hsk_enable_keyframes; hsk_keytex_point.h: KeyStore), one allocation made there and freed by
   // hsk_release_keyframes: key_cap slots of key_slot_bytes(key_w, key_h), key_n of them taken; key_rec = the host's copy of the
   // taken slots' records, 16 floats each (hsk_get_keyframe).  Nothing the tracker reads; hsk_reset leaves it alone
@@ -348,9 +316,69 @@ int align_run(hsk_ctx* k, const hsk_align_params& p, const float* d_soa, size_t 
 int check_poses(hsk_ctx* k, const float* poses, size_t n_poses, const char* who);
 // ---- api_components.hip ----
 int ensure_grown(hsk_ctx* k, void** buf, size_t* have, size_t want);  // a device buffer of at least `want` bytes, its content not kept
+inline bool HeldPass::stands(const hsk_ctx* k) const { return buf && epoch == k->vol_epoch; }
+inline int HeldPass::grow(hsk_ctx* k, size_t want) {
+  if (bytes < want) drop();
+  return ensure_grown(k, &buf, &bytes, want);
+}
+inline int HeldPass::grow_tab(hsk_ctx* k, size_t want) { return ensure_grown(k, &tab, &tab_bytes, want); }
+inline void HeldPass::stamp(const hsk_ctx* k, const void* kp, size_t n) {
+  key.assign((const unsigned char*)kp, (const unsigned char*)kp + n);
+  epoch = k->vol_epoch;
+}
+inline int HeldPass::release(hsk_ctx* k) {
+  if (buf || tab) HIPCHK(k, hipStreamSynchronize(k->stream));
+  for (void** b : {&buf, &tab})
+    if (*b) {
+      HIPCHK(k, hipFree(*b));
+      *b = nullptr;
+    }
+  bytes = tab_bytes = 0;
+  drop();
+  return HSK_OK;
+}
+inline int HeldPass::require(hsk_ctx* k, const char* who, const char* what) const {
+  return stands(k) ? HSK_OK : fail(k, HSK_ERR_STATE, (std::string(who) + what).c_str());
+}
+// The host's half of "labelled regions -> records" for a labelling in b (launch_comp_label has run): the root count is read and
+// more than 2^24 refused with `too_many` (null: no refusal -- r->n says it, nothing else is done); the host vectors are sized
+// (`no_memory` when they cannot be); pass's table is grown to roots, eight words a region, extra_words more a region and
+// tail_bytes behind them (region_tab); launch_comp_records runs, then -- minor_cls not null -- the MINOR step on those class words
+// (the regions below min_voxels stop being members), then -- extra not null -- the caller's record kernel, which writes the extra
+// words; roots, table and extra words come back, and the stream has drained.  hsk_comp_point.h's comp_region_records turns them
+// into the ABI's records.
+struct RegionTab {
+  size_t bytes;
+  unsigned *roots, *table, *extra;
+};
+RegionTab region_tab(const HeldPass& pass, size_t n, size_t extra_bytes);
+struct RegionRead {
+  unsigned n = 0;
+  std::vector<unsigned> roots, table, extra;
+};
+int region_read(hsk_ctx* k, const CompBufs& b, HeldPass* pass, size_t extra_words, size_t tail_bytes, const char* too_many, const char* no_memory,
+                void* minor_cls, uint64_t min_voxels, const std::function<void(const RegionTab&, unsigned)>& extra, RegionRead* r);
+// The tail of a call that writes the volume: the deferred weights are written back (the words that stay are to hold theirs), `launch`
+// writes, volume_replaced follows it, and the stream drains.  The caller drops its own held pass.
+int commit_volume_write(hsk_ctx* k, const std::function<void()>& launch);
+// the held records into the caller's array, or their count: *n_out is the count; recs null: that is all; cap below it: `message`
+template <class T>
+int reply_records(hsk_ctx* k, const std::vector<T>& held, T* recs, size_t cap, size_t* n_out, const char* message) {
+  *n_out = held.size();
+  if (!recs) return HSK_OK;
+  if (cap < held.size()) return fail(k, HSK_ERR_ARG, message);
+  if (!held.empty()) memcpy(recs, held.data(), held.size() * sizeof(T));
+  return HSK_OK;
+}
+// ---- api_clearance.hip ----
+// the cells and the truncation distance of this context, or (k null) of hsk_default_config(256)
+void context_cells(const hsk_ctx* k, float cell[3], float* tau);
+// the arguments of an _at call, or HSK_ERR_ARG: "<who>: null argument" (n > 0 points without xyz or out), "<who>: more than 2^20
+// points", "<who>: radius must lie in 0..<max_radius>" (max_radius negative: the call takes no radius)
+int points_check(hsk_ctx* k, const char* who, const void* xyz, const void* out, size_t n, int radius, int max_radius);
 // ---- api_clearance.hip ----
 // the parameters a clearance call works with (NULL: the defaults), checked -> the kernels' block; the field of the volume as it
-// stands, in d_clear (*reused: nothing had to be launched)
+// stands, in clear's scratch (*reused: nothing had to be launched)
 int clear_check(hsk_ctx* k, const hsk_clearance_params* params, const char* who, hsk_clearance_params* p, ClearGeom* q);
 // the state a pass over a whole volume needs of k, reported in `errs`: require_whole_volume's and require_idle's refusals, and a
 // volume lin can number (HSK_ERR_ARG: "<who>: the volume has more than 2^31 voxels")

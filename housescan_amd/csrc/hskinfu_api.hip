@@ -149,24 +149,13 @@ static void free_all(hsk_ctx* k) {
   F(k->d_out);
   F(k->d_color);
   F(k->d_has_color);
-  F(k->d_mi);
   F(k->d_view);
   F(k->d_fuse);
-  F(k->d_pack);
   F(k->d_align);
-  F(k->d_comp);
-  F(k->d_comp_tab);
-  F(k->d_fill);
-  F(k->d_diff);
-  F(k->d_diff_tab);
-  F(k->d_split);
-  F(k->d_split_tab);
-  F(k->d_clear);
-  F(k->d_reach);
-  F(k->d_part);
-  F(k->d_part_tab);
-  F(k->d_simp);
-  F(k->d_simp_out);
+  for (HeldPass* p : k->passes) {
+    F(p->buf);
+    F(p->tab);
+  }
   F(k->d_key);
   if (k->h_align) (void)hipHostFree(k->h_align);
   if (k->h_view) (void)hipHostFree(k->h_view);
@@ -1288,7 +1277,7 @@ extern "C" int hsk_integrate_color(hsk_ctx* k, const uint16_t* depth, const uint
   k->rgb_src = nullptr;
   HIPCHK(k, e);
   enqueue_color(k);
-  k->pk_epoch = 0;  // (the colour changed without the TSDF: the volume image's pass is void)
+  k->pack.drop();  // (the colour changed without the TSDF: the volume image's pass is void)
   HIPCHK(k, hipStreamSynchronize(k->stream));
   HIPCHK(k, hipGetLastError());
   return HSK_OK;

@@ -37,32 +37,25 @@ int main(int argc, char** argv) {
     labels[l] = parent[g.at(l)] == COMP_NONE ? COMP_NONE : comp_find<CompPlainOps>(parent.data(), g, l);
     if (labels[l] == l) roots.push_back(l);  // (ascending)
   }
-  std::vector<hsk_component> recs(roots.size());
-  for (size_t i = 0; i < roots.size(); ++i) {
-    unsigned x, y, z;
-    g.xyz(roots[i], x, y, z);
-    hsk_component c = {};
-    c.root[0] = (int)x, c.root[1] = (int)y, c.root[2] = (int)z;
-    for (int a = 0; a < 3; ++a) c.lo[a] = 0x7fffffff;
-    recs[i] = c;
-  }
+  // the device's table, eight words a root (count, lo, hi); the records and their order are the library's own text
+  std::vector<unsigned> table(roots.size() * 8, 0u);
+  for (size_t i = 0; i < roots.size(); ++i)
+    for (int a = 0; a < 3; ++a) table[i * 8 + 1 + a] = 0x7fffffffu;
   for (unsigned l = 0; l < labels.size(); ++l) {
     if (labels[l] == COMP_NONE) continue;
     const unsigned at = comp_search(roots.data(), (unsigned)roots.size(), labels[l]);
     if (at >= roots.size()) return 3;
     unsigned p[3];
     g.xyz(l, p[0], p[1], p[2]);
-    hsk_component& c = recs[at];
-    c.n_voxels += 1;
+    unsigned* t8 = &table[(size_t)at * 8];
+    t8[0] += 1;
     for (int a = 0; a < 3; ++a) {
-      c.lo[a] = std::min(c.lo[a], (int)p[a]);
-      c.hi[a] = std::max(c.hi[a], (int)p[a] + 1);
+      t8[1 + a] = std::min(t8[1 + a], p[a]);
+      t8[4 + a] = std::max(t8[4 + a], p[a] + 1);
     }
   }
-  std::sort(recs.begin(), recs.end(), [&](const hsk_component& a, const hsk_component& b) {
-    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), b.n_voxels,
-                              g.lin((unsigned)b.root[0], (unsigned)b.root[1], (unsigned)b.root[2]));
-  });
+  std::vector<hsk_component> recs;
+  comp_region_records(g, roots.data(), table.data(), roots.size(), 0, &recs, [](hsk_component&, size_t) {});
   HarnessOut o(argv[2]);
   const unsigned n = (unsigned)recs.size();
   o.put(labels), o.put(&n, 1), o.put(recs);

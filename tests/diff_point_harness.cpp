@@ -84,17 +84,14 @@ int main(int argc, char** argv) {
         }
       }
   // the MINOR step: prune's FREE fill on the class words of the regions below min_voxels
-  unsigned long long n_kept = 0, n_minor = 0;
+  // (the records, the cut at min_voxels and their order are the library's own text)
   std::vector<hsk_diff_region> recs;
-  for (unsigned r : roots) {
-    if (all[r].n_voxels >= min_voxels) recs.push_back(all[r]);
-    else n_minor += 1;
-  }
-  n_kept = recs.size();
-  std::sort(recs.begin(), recs.end(), [&](const hsk_diff_region& a, const hsk_diff_region& c) {
-    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
-                              g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
+  const std::vector<unsigned> table = region_table(all, roots);
+  const unsigned long long n_minor = comp_region_records(g, roots.data(), table.data(), roots.size(), min_voxels, &recs, [&](hsk_diff_region& c, size_t i) {
+    c.n_appeared = all[roots[i]].n_appeared;
+    c.n_vanished = all[roots[i]].n_vanished;
   });
+  const unsigned long long n_kept = recs.size();
   std::vector<unsigned char> cls(n);
   std::vector<unsigned> region(n);
   for (unsigned z = 0; z < Z; ++z)

@@ -29,6 +29,21 @@ struct HarnessIn {
 // (exactly the volume's words, as the device allocates them: an access past them is the sanitizer's to find)
 inline size_t volume_words(size_t X, size_t Y, size_t Z) { return X * Y * ((Z + 3) & ~(size_t)3); }
 
+// the device's table of labelled regions -- eight words a root: count, lo[3], hi[3], one unused -- from records indexed by root
+template <class Rec>
+std::vector<unsigned> region_table(const std::vector<Rec>& by_root, const std::vector<unsigned>& roots) {
+  std::vector<unsigned> table(roots.size() * 8, 0u);
+  for (size_t i = 0; i < roots.size(); ++i) {
+    const Rec& c = by_root[roots[i]];
+    table[i * 8] = (unsigned)c.n_voxels;
+    for (int a = 0; a < 3; ++a) {
+      table[i * 8 + 1 + a] = (unsigned)c.lo[a];
+      table[i * 8 + 4 + a] = (unsigned)c.hi[a];
+    }
+  }
+  return table;
+}
+
 struct HarnessOut {
   FILE* o;
   bool ok;

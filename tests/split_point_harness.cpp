@@ -145,15 +145,16 @@ int main(int argc, char** argv) {
           first[parent[a]] = 0;
         }
       }
-  unsigned long long n_minor = 0;
+  // (the records, the cut at min_voxels and their order are the library's own text)
   std::vector<hsk_object> recs;
-  for (unsigned r : roots) {
-    if (all[r].n_voxels >= min_voxels) recs.push_back(all[r]);
-    else n_minor += 1;
-  }
-  std::sort(recs.begin(), recs.end(), [&](const hsk_object& a, const hsk_object& c) {
-    return comp_record_before(a.n_voxels, g.lin((unsigned)a.root[0], (unsigned)a.root[1], (unsigned)a.root[2]), c.n_voxels,
-                              g.lin((unsigned)c.root[0], (unsigned)c.root[1], (unsigned)c.root[2]));
+  const std::vector<unsigned> table = region_table(all, roots);
+  const unsigned long long n_minor = comp_region_records(g, roots.data(), table.data(), roots.size(), min_voxels, &recs, [&](hsk_object& c, size_t i) {
+    const hsk_object& o = all[roots[i]];
+    memcpy(c.sum, o.sum, sizeof(c.sum));
+    memcpy(c.contact, o.contact, sizeof(c.contact));
+    c.plane_mask = o.plane_mask;
+    c.height_lo = o.height_lo;
+    c.height_hi = o.height_hi;
   });
   std::vector<unsigned char> cls(n), pln(n);
   std::vector<unsigned> label(n);

@@ -278,6 +278,22 @@ def test_two_call_protocol_and_the_cached_pass(hsk):
         trk.close()
 
 
+def test_enabling_colour_voids_the_cached_pass(hsk):
+    """the pass is held for the volume AND the colour flag: colour enabled behind a pass, with no volume change, runs it again,
+    and the image then carries the colour section"""
+    trk = make_ctx(hsk, (64, 32, 20), color=False)
+    try:
+        assert trk.pack_volume_info()["pass_reused"] == 0 and trk.pack_volume_info()["pass_reused"] == 1
+        plain = trk.pack_volume()
+        with_color(trk)
+        assert trk.pack_volume_info()["pass_reused"] == 0 and trk.pack_volume_info()["pass_reused"] == 1
+        img = trk.pack_volume()
+        assert_same_image(img, twin_image(hsk, trk), "colour enabled behind a pass")
+        assert PT.info(plain)["flags"] == 0 and PT.info(img)["flags"] == 1 and len(img) > len(plain)
+    finally:
+        trk.close()
+
+
 # ---- 6. files --------------------------------------------------------------------------------------------------------
 def test_files(hsk, tmp_path):
     src, tsdf, col = room_scan(hsk, 0)
