@@ -7,81 +7,13 @@ volume that it reaches the path it is there for.  Also hsk_create's refusal of a
 import numpy as np
 import pytest
 
-import align_twin as AT
 import brick_twin as BT
 import mesh_twin as MT
 from kit import assert_same_bits
 from np_twin import _Grid
+from view_shape_cases import BRICK_CASES as CASES, along_x, look, scene_fill
 
 pytestmark = pytest.mark.gpu
-
-EYE = np.eye(3, dtype=np.float32)
-CYC = np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0]], np.float32)    # volume x <- world z, volume y <- world x, volume z <- world y
-TAU_SCENE = 0.1                                                   # the truncation of the uploaded scene, in the scene's own units
-
-
-def look(eye, at, down=(0.0, 0.0, 1.0)):
-    """camera-to-volume pose: at `eye` (metres), its z axis towards `at`, its y axis (image rows downwards) as near `down` as
-    that allows"""
-    eye, at = np.asarray(eye, np.float64), np.asarray(at, np.float64)
-    z = (at - eye) / np.linalg.norm(at - eye)
-    d = np.asarray(down, np.float64)
-    if abs(d @ z) > 0.95:
-        d = np.array([0.0, 1.0, 0.0]) if abs(z[1]) < 0.9 else np.array([1.0, 0.0, 0.0])
-    x = np.cross(d, z)
-    x /= np.linalg.norm(x)
-    P = np.eye(4, dtype=np.float32)
-    P[:3, :3] = np.stack([x, np.cross(z, x), z], axis=1).astype(np.float32)
-    P[:3, 3] = eye.astype(np.float32)
-    return P
-
-
-def along_x(eye):
-    """a camera that looks exactly along +x (its central rays run the length of a brick row); image rows downwards = +z"""
-    return look(eye, np.asarray(eye, np.float64) + [1.0, 0.0, 0.0])
-
-
-# dims (X, Y, Z) and size in metres (the three cells within a factor of three of one another);
-# scene: the uploaded filling -- align_twin's room with a box in it, evaluated at shift + scale * 3 * (p / size) per axis;
-# world: the integrated filling -- the synthetic stream's frames, the volume placed in its world by a rotation and an origin;
-# poses: three raycasts per filling (outside looking in, inside, along +x), in the volume's metres.
-CASES = {
-    # 41 bricks a row: the rows whose first bit is bit 24..31 of a word take their last bricks from a third word
-    "328x40x44": dict(
-        dims=(328, 40, 44), size=(3.0, 1.08, 1.18), omp=False, full=True,
-        scene=dict(scale=(1.0, 1.0, 1.0), shift=(0.0, 0.0, 0.5)),
-        world=dict(rot=CYC, origin=(0.7, 1.2, 0.0), frames=(0, 10, 20)),
-        poses=dict(upload=[look((1.5, 0.54, -0.4), (1.5, 0.54, 1.0), (0, 1, 0)), look((0.6, 0.4, 0.2), (2.4, 0.7, 0.7)), along_x((0.5, 0.54, 0.4))],
-                   integrate=[look((2.2, -0.25, 0.59), (2.8, 0.45, 0.59)), look((2.1, 0.5, 0.6), (2.8, 0.6, 0.5)), along_x((1.0, 0.54, 0.59))])),
-    # exactly 64 bricks a row: the mask is used untrimmed, brick 63 is its top bit
-    "512x64x52": dict(
-        dims=(512, 64, 52), size=(3.0, 1.1, 0.9), omp=False, full=True,
-        scene=dict(scale=(1.0, 1.0, 1.0), shift=(-0.28, 0.0, 0.5)),
-        world=dict(rot=CYC, origin=(0.7, 1.3, -0.17), frames=(0, 10, 20)),
-        poses=dict(upload=[look((1.5, 0.55, -0.4), (1.5, 0.55, 1.0), (0, 1, 0)), look((0.9, 0.4, 0.2), (2.6, 0.7, 0.5)), along_x((0.8, 0.55, 0.3))],
-                   integrate=[look((2.4, -0.3, 0.45), (2.97, 0.5, 0.45)), look((2.2, 0.5, 0.45), (2.97, 0.6, 0.4)), along_x((1.2, 0.55, 0.45))])),
-    # 66 bricks a row: no row mask, every segment is swept
-    "528x16x20": dict(
-        dims=(528, 16, 20), size=(3.0, 0.27, 0.34), omp=False, full=True,
-        scene=dict(scale=(1.0, 1.0, 1.0), shift=(-0.25, 0.0, 0.5)),
-        world=dict(rot=EYE, origin=(-0.15, 0.9, 2.6), frames=(0, 10, 20)),
-        poses=dict(upload=[look((1.5, 0.135, -0.3), (1.5, 0.135, 0.3), (0, 1, 0)), look((1.0, 0.1, 0.05), (1.5, 0.16, 0.2)), along_x((0.9, 0.135, 0.12))],
-                   integrate=[look((1.5, 0.135, -0.6), (1.5, 0.135, 0.2), (0, 1, 0)), look((1.0, 0.135, 0.03), (1.6, 0.135, 0.2)), along_x((0.4, 0.135, 0.16))])),
-    # 1156 words: the march stages more than four quads a lane, the super-brick words start behind word 1024
-    "264x264x264": dict(
-        dims=(264, 264, 264), size=(3.0, 3.0, 3.0), omp=True, full=False,
-        scene=dict(scale=(1.0, 1.0, 0.7653), shift=(0.0, 0.0, 0.5148)),
-        world=dict(rot=EYE, origin=(0.0, 0.0, 0.0), frames=(0, 10)),
-        poses=dict(upload=[look((1.5, 1.5, -0.4), (1.5, 1.5, 1.5), (0, 1, 0)), look((0.6, 1.6, 0.5), (2.4, 1.4, 2.6), (0, 1, 0)), along_x((0.5, 1.5, 1.5))],
-                   integrate=[look((1.5, 1.5, -0.3), (1.5, 1.5, 1.5), (0, 1, 0)), look((1.2, 1.2, 1.0), (2.0, 2.2, 2.8), (0, 1, 0)), along_x((0.5, 1.9, 1.8))])),
-    # 1089 super-bricks: more than the 1024 super bits, so no super bit is written and the march never crosses wave-wide
-    "1048x1048x12": dict(
-        dims=(1048, 1048, 12), size=(3.0, 3.0, 0.103), omp=True, full=False,
-        scene=dict(scale=(1.0, 1.0, 0.1), shift=(0.0, -0.3, 2.5)),
-        world=dict(rot=EYE, origin=(0.0, -0.2, 2.75), frames=(0, 10)),
-        poses=dict(upload=[look((1.5, 1.6, -0.5), (1.5, 1.6, 0.05), (0, 1, 0)), look((1.0, 1.2, 0.01), (1.6, 1.5, 0.0515), (0, 0, 1)), along_x((1.0, 2.0, 0.02))],
-                   integrate=[look((1.4, 1.4, -0.5), (1.4, 1.4, 0.05), (0, 1, 0)), look((0.9, 1.0, 0.01), (1.5, 1.3, 0.05), (0, 0, 1)), along_x((0.6, 1.3, 0.02))])),
-}
 
 
 def configs(hsk, oracle, dims, size, omp=False, **over):
@@ -89,21 +21,6 @@ def configs(hsk, oracle, dims, size, omp=False, **over):
     cfg_h = hsk.default_config(X, vol_y=Y, vol_z=Z, own_z1=Z, vol_size_m=size, **over)
     cfg_o = oracle.default_config(X, omp=omp, vol=dims, size=size)
     return cfg_h, cfg_o
-
-
-def scene_fill(dims, size, scale, shift):
-    """align_twin.scene_volume's quantisation of align_twin's scene, stretched and shifted per axis, a few planes at a time"""
-    X, Y, Z = dims
-    ax = [shift[k] + scale[k] * 3.0 * (np.arange(dims[k]) + 0.5) / dims[k] for k in range(3)]
-    vol = np.zeros((Z, Y, X, 2), np.int16)
-    step = max(1, 1500000 // (X * Y))
-    for z0 in range(0, Z, step):
-        zz, yy, xx = np.meshgrid(ax[2][z0:z0 + step], ax[1], ax[0], indexing="ij")
-        d = AT.scene_distance(np.stack([xx, yy, zz], -1))
-        seen = d > -TAU_SCENE
-        vol[z0:z0 + step, ..., 0] = np.where(seen, np.trunc(np.clip(d / TAU_SCENE, -1.0, 1.0) * 32767.0), 0).astype(np.int16)
-        vol[z0:z0 + step, ..., 1] = seen
-    return vol
 
 
 def world_pose(world, pose):

@@ -14,6 +14,7 @@ import view_twin as VT
 from kit import same_bits_nan
 from section_cases import SCAN_FRAMES, SIDE, SPAN, ortho_cam, room_frames
 from view_cases import RAGGED, SENSOR, assert_trackers_equal, frames_of, moved, scan
+from view_shape_cases import assert_section
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -106,19 +107,6 @@ def twin_and_gpu(trk, tsdf, color, fields):
     from housescan_amd import _lib
     got = trk.render_section(ST.to_struct(sec, _lib), vmap=True, nmap=True)
     return sec, ref, got
-
-
-def assert_section(got, ref, what):
-    """every pixel of every output and the three counts, zero differences"""
-    for key in ("n_hit", "n_cut", "n_uncolored"):
-        assert got[key] == ref[key], f"{what}: {key} {got[key]} != {ref[key]}"
-    assert same_bits_nan(got["vmap"], ref["vmap"]), f"{what}: vmap ({(np.isnan(got['vmap'][0]) != np.isnan(ref['vmap'][0])).sum()} hit pixels differ)"
-    assert same_bits_nan(got["nmap"], ref["nmap"]), f"{what}: nmap"
-    bad = np.argwhere(got["depth"] != ref["depth"])
-    assert len(bad) == 0, f"{what}: {len(bad)} depth pixels differ, first {bad[:4].tolist()}"
-    bad = np.argwhere((got["rgb"] != ref["rgb"]).any(axis=2))
-    assert len(bad) == 0, (f"{what}: {len(bad)} rgb pixels differ, first {bad[:4].tolist()}: "
-                           f"{got['rgb'][tuple(bad[0])].tolist()} != {ref['rgb'][tuple(bad[0])].tolist()}")
 
 
 def shares(ref):

@@ -10,6 +10,7 @@ import pytest
 import view_twin as VT
 from kit import same_bits_nan
 from view_cases import RAGGED, SENSOR, assert_trackers_equal, frames_of, moved, rot_y, scan
+from view_shape_cases import MODES, assert_view, check_camera
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -17,54 +18,12 @@ WIDE = dict(width=800, height=600, fx=400.0, fy=400.0, cx=399.5, cy=299.5)
 FULLHD = dict(width=1920, height=1080, fx=1000.0, fy=1000.0, cx=959.5, cy=539.5)
 FREE = dict(width=1280, height=960, fx=1050.0, fy=1050.0, cx=639.5, cy=479.5)
 ONE = dict(width=1, height=1, fx=525.0, fy=525.0, cx=0.0, cy=0.0)
-MODES = (VT.LAMBERT, VT.NORMALS, VT.COLOR, VT.COLOR_LIT)
 
 
 def reference(oracle, dims, tsdf, color, cam, pose, mode, light, light_in_camera, background):
     cfg = VT.view_config(oracle, dims, cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"])
     vm, nm = VT.geometry(oracle, cfg, tsdf, pose)
     return vm, nm, VT.shade(vm, nm, pose, mode, light, light_in_camera, background, color=color)
-
-
-def assert_view(got, vm, nm, ref, what):
-    """every pixel of every output, zero differences"""
-    assert got["n_hit"] == ref["n_hit"], f"{what}: n_hit {got['n_hit']} != {ref['n_hit']}"
-    assert got["n_uncolored"] == ref["n_uncolored"], f"{what}: n_uncolored {got['n_uncolored']} != {ref['n_uncolored']}"
-    if "vmap" in got:
-        assert same_bits_nan(got["vmap"], vm), f"{what}: vmap"
-    if "nmap" in got:
-        assert same_bits_nan(got["nmap"], nm), f"{what}: nmap"
-    bad = np.argwhere(got["depth"] != ref["depth"])
-    assert len(bad) == 0, f"{what}: {len(bad)} depth pixels differ, first {bad[:4].tolist()}"
-    bad = np.argwhere((got["rgb"] != ref["rgb"]).any(axis=2))
-    assert len(bad) == 0, (f"{what}: {len(bad)} rgb pixels differ, first {bad[:4].tolist()}: "
-                           f"{got['rgb'][tuple(bad[0])].tolist()} != {ref['rgb'][tuple(bad[0])].tolist()}")
-
-
-def check_camera(trk, oracle, dims, tsdf, color, cam, pose, what, degenerate=False, modes=MODES):
-    """one camera: the geometry once (with the first mode), then every mode with the light in camera and in world coordinates"""
-    cfg = VT.view_config(oracle, dims, cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"])
-    vm, nm = VT.geometry(oracle, cfg, tsdf, pose)
-    hit = ~np.isnan(vm[0])
-    if not degenerate:   # the condition on the inputs: a test cannot pass on an empty (or a full) picture
-        assert hit.mean() >= 0.20, f"{what}: the reference has only {hit.mean():.3f} hit pixels"
-        assert (~hit).mean() >= 0.02, f"{what}: the reference has only {(~hit).mean():.3f} background pixels"
-    first = True
-    for mode in modes:
-        if mode in (VT.COLOR, VT.COLOR_LIT) and color is None:
-            continue
-        for light, in_cam in (((0.1, -0.2, 0.05), True), ((1.4, 0.3, 0.2), False)):
-            bg = (10 + mode, 200, 33)
-            ref = VT.shade(vm, nm, pose, mode, light, in_cam, bg, color=color)
-            if mode in (VT.COLOR, VT.COLOR_LIT) and not degenerate:
-                assert ref["n_uncolored"] <= 0.05 * ref["n_hit"], f"{what}: {ref['n_uncolored']} of {ref['n_hit']} hits uncoloured"
-            got = trk.render_view(pose=pose, mode=mode, light=light, light_in_camera=int(in_cam), background=bg, vmap=first,
-                                  nmap=first, **cam)
-            assert_view(got, vm, nm, ref, f"{what} mode {mode} light_in_camera {in_cam}")
-            first = False
-            if mode in (VT.NORMALS, VT.COLOR):
-                break   # (no light in these modes)
-    return hit
 
 
 def turned_away(pose):
