@@ -243,6 +243,29 @@ class HskViewScore(C.Structure):
     ]
 
 
+HSK_SPLAT_DISC, HSK_SPLAT_SURFEL = 0, 1
+HSK_SPLAT_MAX_POINTS, HSK_SPLAT_MAX_POSES = 1 << 24, 65536
+
+
+class HskSplatParams(C.Structure):
+    """Mirror of `hsk_splat_params` (include/hskinfu.h): 28 bytes; a 0 in a field means its default."""
+
+    _fields_ = [
+        ("mode", C.c_int),
+        ("point_size_m", C.c_float), ("cover", C.c_float), ("min_half_px", C.c_float), ("max_half_px", C.c_float),
+        ("near_m", C.c_float), ("far_m", C.c_float),
+    ]
+
+
+class HskSplatStats(C.Structure):
+    """Mirror of `hsk_splat_stats` (include/hskinfu.h): 24 bytes."""
+
+    _fields_ = [
+        ("n_invalid", C.c_uint32), ("n_clipped", C.c_uint32), ("n_backfacing", C.c_uint32), ("n_outside", C.c_uint32),
+        ("n_splatted", C.c_uint32), ("n_pixels", C.c_uint32),
+    ]
+
+
 HSK_COMPONENT_NONE = 0xFFFFFFFF
 HSK_COMPONENT_MAX = 1 << 24
 HSK_PRUNE_UNSEEN, HSK_PRUNE_FREE = 0, 1
@@ -643,6 +666,9 @@ SYMBOLS = {
     "hsk_score_views": (C.c_int, [_P, C.POINTER(HskProbe), _P, C.c_size_t, C.POINTER(HskViewScore)]),
     "hsk_render_coverage": (C.c_int, [_P, C.POINTER(HskProbe), _F, _P, _P, _P, C.POINTER(HskViewScore)]),
     "hsk_rank_views": (C.c_int, [C.POINTER(HskViewScore), C.c_size_t, C.POINTER(C.c_uint32)]),
+    "hsk_default_splat_params": (None, [_P, C.POINTER(HskSplatParams)]),
+    "hsk_splat_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _F, C.POINTER(HskSplatParams), _P, C.POINTER(HskSplatStats)]),
+    "hsk_import_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskSplatParams), C.POINTER(HskSplatStats)]),
     "hsk_default_prune_params": (None, [_P, C.POINTER(HskPruneParams)]),
     "hsk_label_components": (C.c_int, [_P, C.POINTER(HskComponent), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskComponentStats)]),
     "hsk_download_components": (C.c_int, [_P, _P]),

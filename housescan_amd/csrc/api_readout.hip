@@ -340,6 +340,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) HIPCHK(k, (hipError_t)level_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)texture_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)keytex_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)splat_warm());
   return r;
 }
 

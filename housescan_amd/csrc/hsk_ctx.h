@@ -198,7 +198,8 @@ struct hsk_ctx {
   size_t fuse_bytes = 0;
   // the scratch of every call that works on a cloud (align_scratch -> CloudScratch), made on first use and only grown: the
   // alignment's accumulators (align.hip: HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what the call carves for
-  // itself -- RelocScratch (api_reloc.hip), PlaneScratch (api_planes.hip) or LevelScratch (api_level.hip); h_align: the
+  // itself -- RelocScratch (api_reloc.hip), PlaneScratch (api_planes.hip), LevelScratch (api_level.hip) or SplatScratch
+  // (api_splat.hip: the z-buffer, a frame, the views' counters); h_align: the
   // accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;
@@ -277,6 +278,7 @@ void leave_slab_bookkeeping(hsk_ctx* k);
 int set_pose_internal(hsk_ctx* k, const float pose[16]);
 void enqueue_raycast_and_resize(hsk_ctx* k, int* keys, bool report = false);
 int preprocess_frame(hsk_ctx* k, const uint16_t* depth, int w, int h);  // hsk_preprocess behind its argument checks
+void enqueue_integrate_staged(hsk_ctx* k);  // the scaled depth and the integrate of the frame in B().d_raw, at the device state's pose
 void hsk_mark_group_slab(hsk_ctx* k);  // hsk_group_create* marks the contexts it makes as slabs, whatever planes they own
 // the state a call needs, or its refusal (HSK_ERR_STATE): no frame in flight; colour enabled; a context that stores its whole
 // volume ("<who>: not for a slab (<sentence>)").  `errs` takes the message: hsk_fuse_volume asks of its source, too, and reports

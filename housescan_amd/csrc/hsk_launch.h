@@ -539,3 +539,18 @@ void launch_bake_keytex(hipStream_t s, const void* vol, const unsigned* colv, co
                         const KeyArgs& ka, const unsigned* tiles, const TexBlock* blocks, const int* faces, const float* vertices,
                         unsigned char* rgb, unsigned char* nrm, unsigned char* mask, unsigned char* source, unsigned long long* counts);
 int keytex_warm();    // loads keytex.hip's code object (hsk_prepare_readout); a hipError_t
+
+// cloud import (splat.hip): the n points of a cloud in the alignment scratch's planes (the normals' three only
+// with_normals) offered to a view's z-buffer by hsk_splat_point.h's rule -- zbuf: cam.w x cam.h words, all ones before the first
+// offer; counts: SPLAT_COUNT_WORDS words of the view, zeroed by the caller: the points by SPLAT_* class, then the pixels that got
+// a depth.  resolve: the z-buffer as the 16-bit frame (all ones -> 0), counted, and all ones again.  pose: the view's pose into
+// the tracker state, lost cleared (hsk_set_pose's effect).  Nothing is launched for n == 0.
+#define SPLAT_COUNT_WORDS 8
+struct SplatCam;
+struct SplatPose;
+struct SplatArgs;
+void launch_splat_points(hipStream_t s, const float* soa, unsigned n, unsigned pitch, bool with_normals, const SplatCam& cam, const SplatPose& pose,
+                         const SplatArgs& args, unsigned* zbuf, unsigned* counts);
+void launch_splat_resolve(hipStream_t s, unsigned* zbuf, unsigned n_pixels, unsigned short* frame, unsigned* counts);
+void launch_splat_pose(hipStream_t s, TrackState* st, const SplatPose& pose);
+int splat_warm();     // loads splat.hip's code object (hsk_prepare_readout); a hipError_t

@@ -512,6 +512,12 @@ static void enqueue_integrate(hsk_ctx* k, const IcpFinal* fin = nullptr, bool re
                    k->d_uni, report_early ? &ring : nullptr);
 }
 
+// hsk_integrate behind its pose and its upload, for a frame that is already in the set's d_raw (api_splat.hip: hsk_import_cloud)
+void enqueue_integrate_staged(hsk_ctx* k) {
+  enqueue_scaled_depth(k);
+  enqueue_integrate(k);
+}
+
 // colour (hsk_enable_color): right behind the frame's integrate -- its pose is final there (the integrate's first kernel does
 // the last solve) -- and before its raycast, whose report into the ring says the buffer set's inputs (the colour image with
 // them) are consumed.  Nothing is launched while colour is off.

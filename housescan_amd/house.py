@@ -155,6 +155,14 @@ def read_pcd_xyz(path):
     return out
 
 
+def import_room(directory, trk, poses, **params):
+    """a room directory's cloud_bin.pcd (read_pcd_xyz) fused into the tracker's volume as a sensor at each of the poses [m, 4, 4]
+    would have seen it (KinfuTracker.import_cloud; the keywords are its splat parameters -- point_size_m is the cloud's leaf
+    size) -> (the per-view stats, the cloud [n, 3])"""
+    xyz = read_pcd_xyz(os.path.join(os.fspath(directory), "cloud_bin.pcd"))
+    return trk.import_cloud(xyz, poses, **params), xyz
+
+
 def write_ply_points(path, xyz):
     pts = _f32(xyz).reshape(-1, 3)
     _ck0(_lib.load().hsh_write_ply_points(os.fsencode(path), pts.ctypes.data, len(pts)), "hsh_write_ply_points")

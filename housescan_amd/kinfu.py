@@ -149,6 +149,19 @@ def default_probe(tracker=None, **fields):
     return _params(_PROBE, tracker, None, fields)
 
 
+SPLAT_DISC, SPLAT_SURFEL = 0, 1
+SPLAT_FIELDS = ("mode", "point_size_m", "cover", "min_half_px", "max_half_px", "near_m", "far_m")
+SPLAT_STATS_DTYPE = np.dtype(_lib.HskSplatStats)
+_SPLAT = (_lib.HskSplatParams, "hsk_default_splat_params", SPLAT_FIELDS, "splat parameters have no field")
+
+
+def default_splat_params(tracker=None, **fields):
+    """the parameters of splat_cloud and import_cloud (hsk_default_splat_params): mode SPLAT_DISC, point_size_m the tracker's
+    largest cell (without a tracker 3 / 512) -- a property of the cloud: set it to the cloud's leaf size --, cover 1.5, min_half_px
+    0.5, max_half_px 8, near_m 0.1, far_m 8; the keywords override its fields -> an `_lib.HskSplatParams`"""
+    return _params(_SPLAT, tracker, None, fields)
+
+
 COMPONENT_DTYPE = np.dtype(_lib.HskComponent)
 COMPONENT_NONE = 0xFFFFFFFF
 PRUNE_UNSEEN, PRUNE_FREE = 0, 1
@@ -1050,6 +1063,38 @@ class KinfuTracker:
         self._ck(self.lib.hsk_render_coverage(self.h, C.byref(p), _fp(m), *(out[key].ctypes.data if key in out else None for key, _, _ in shapes),
                                               sc.ctypes.data_as(C.POINTER(_lib.HskViewScore))))
         out["score"] = sc[0]
+        return out
+
+    # ---- cloud import -------------------------------------------------------------------------------------
+    @staticmethod
+    def _cloud(xyz, normals):
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if nrm is not None and len(nrm) != len(pts):
+            raise ValueError("normals must be [n, 3] like xyz")
+        return pts, nrm, (pts.ctypes.data if len(pts) else None), (nrm.ctypes.data if nrm is not None and len(nrm) else None)
+
+    def splat_cloud(self, xyz, pose, normals=None, params=None, **fields):
+        """the cloud xyz [n, 3] (world coordinates; normals [n, 3] or None) as the depth image of this tracker's camera at pose [4, 4]
+        (hsk_splat_cloud): a z-buffered point splat, the smallest depth a pixel; params: an HskSplatParams (default:
+        default_splat_params(self)), the keywords override its fields -> (depth (h, w) uint16, stats dict).  Read-only"""
+        p = _params(_SPLAT, self, params, fields)
+        pts, nrm, px, pn = self._cloud(xyz, normals)
+        m = np.ascontiguousarray(pose, np.float32).reshape(16)
+        depth, st = np.zeros((self.cfg.height, self.cfg.width), np.uint16), _lib.HskSplatStats()
+        self._ck(self.lib.hsk_splat_cloud(self.h, px, pn, len(pts), _fp(m), C.byref(p), depth.ctypes.data, C.byref(st)))
+        return depth, _stats_dict(st)
+
+    def import_cloud(self, xyz, poses, normals=None, params=None, **fields):
+        """the cloud fused into the volume as a sensor at each of the poses [m, 4, 4] would have seen it, in their order
+        (hsk_import_cloud): per view splat_cloud's image through integrate, on the device; leaves the pose at the last view --
+        resume_scan(that pose) tracks a live sensor on -> a structured array [m] with SPLAT_STATS_DTYPE"""
+        p = _params(_SPLAT, self, params, fields)
+        pts, nrm, px, pn = self._cloud(xyz, normals)
+        ps = self._poses(poses)
+        out = np.zeros(len(ps), SPLAT_STATS_DTYPE)
+        self._ck(self.lib.hsk_import_cloud(self.h, px, pn, len(pts), ps.ctypes.data if len(ps) else None, len(ps), C.byref(p),
+                                           out.ctypes.data_as(C.POINTER(_lib.HskSplatStats)) if len(ps) else None))
         return out
 
     # ---- surface components ----------------------------------------------------------------------------

@@ -1007,6 +1007,69 @@ int hsk_render_coverage(hsk_ctx* k, const hsk_probe* probe, const float pose[16]
  * whose eye_state is not HSK_EYE_FREE -- viewpoints nobody can stand in -- behind all others, in the same order among themselves */
 int hsk_rank_views(const hsk_view_score* s, size_t n, uint32_t* order);
 
+/* ---- Cloud import: a point cloud rendered into the depth images of virtual cameras and fused like a sensor's frames (DESIGN.md
+ * 3.27 the kernels, 8u the rule; tests/splat_twin.py restates the rule in numpy).  The way INTO the volume chain for data that
+ * are no depth stream: a room directory's cloud_bin.pcd (hsh_read_pcd_xyz), another scanner's cloud, this library's own
+ * exports once their volume is gone.  xyz alone suffices, and free space is carved as a sensor carves it -- so clearance, reach,
+ * partition and coverage, which take never-observed space for an obstacle, work on the result.  The host loop: hsk_pose_lattice
+ * (centre, 0, 0, step_rad, n_rot) for a fan of views from one standpoint -> hsk_import_cloud -> hsk_coverage_census,
+ * hsk_score_views, hsk_rank_views for where the next virtual camera should stand -> hsk_import_cloud again.
+ *   The camera is the context's own (width, height, fx, fy, cx, cy); pose is camera -> world, rigid.  Per point p:
+ *   1. a coordinate that is not finite: skipped (n_invalid)
+ *   2. p_c = R^T (p - t), z = p_c.z; z outside [near_m, far_m]: skipped (n_clipped)
+ *   3. HSK_SPLAT_SURFEL, the point's normal n finite and not zero: n . p_c >= 0 faces away -- skipped (n_backfacing); this is what
+ *      keeps the far face of a thin wall out of a view.  Any other normal makes the point a DISC point
+ *   4. the footprint: the integer pixels u0 - ru <= u <= u0 + ru, v0 - rv <= v <= v0 + rv inside the image, (u0, v0) = (fx x / z +
+ *      cx, fy y / z + cy), ru = fx half_m / z and rv = fy half_m / z each clamped to [min_half_px, max_half_px], half_m = 0.5
+ *      point_size_m cover.  No pixel: skipped (n_outside); min_half_px >= 0.5, so a point inside the image owns at least one
+ *   5. every pixel of the footprint is offered a depth in millimetres, rounded as hsk_render_view's depth image rounds and kept to
+ *      1..65535 -- DISC: the point's z; SURFEL: the depth at which the pixel's ray ((u - cx) / fx, (v - cy) / fy, 1) meets the
+ *      point's tangent plane, clamped to z +- 2 half_m (n_splatted counts the points that reach this step)
+ *   A pixel's value is the smallest depth offered to it, 0 if none was: the image does not depend on the order of the points.
+ *   point_size_m is a property of the CLOUD -- the leaf size of a downsampled cloud, the spacing of neighbouring points of one
+ * surface --, not of the camera or the volume; its default, the context's largest cell, is right for a cloud this library
+ * extracted from such a volume.  cover must be >= sqrt(2) for a regular grid of that spacing in any in-plane rotation to be
+ * watertight under square footprints (default 1.5).
+ *   Colour is out of scope: neither an rgb field of the cloud nor a winner-index image is taken. */
+#define HSK_SPLAT_DISC 0
+#define HSK_SPLAT_SURFEL 1
+#define HSK_SPLAT_MAX_POINTS ((size_t)1 << 24)
+#define HSK_SPLAT_MAX_POSES ((size_t)65536)
+typedef struct hsk_splat_params {   /* a 0 in a field means its default */
+  int mode;               /* HSK_SPLAT_DISC (default), HSK_SPLAT_SURFEL (needs normals)                                        */
+  float point_size_m;     /* finite, > 0; default: the context's largest cell (without a context 3 / 512)                      */
+  float cover;            /* finite, >= 1; default 1.5                                                                         */
+  float min_half_px;      /* >= 0.5; default 0.5                                                                               */
+  float max_half_px;      /* min_half_px .. 64; default 8                                                                      */
+  float near_m, far_m;    /* 0 < near_m <= far_m <= 65.535; defaults 0.1 and 8                                                 */
+} hsk_splat_params;       /* 28 bytes */
+typedef struct hsk_splat_stats {
+  uint32_t n_invalid, n_clipped, n_backfacing, n_outside, n_splatted;   /* the points by what became of them: they sum to n     */
+  uint32_t n_pixels;      /* the pixels of the image that are not 0                                                            */
+} hsk_splat_stats;        /* 24 bytes */
+/* the defaults as values (k NULL: point_size_m = 3 / 512) */
+void hsk_default_splat_params(const hsk_ctx* k /* may be NULL */, hsk_splat_params* p);
+/* One view: the cloud (n <= 2^24 packed xyz triples; normals likewise or NULL: DISC only) as the depth image of the context's camera
+ * at `pose`.  Writes nothing of the context but scratch -- pose, volume (the deferred weights are not even flushed), model maps and
+ * image buffers stay bit for bit -- and is legal between submit and wait of pipelined frames.  n = 0: HSK_OK, the image all 0.
+ * The cloud goes up once per call; nothing is allocated on a later call of the same size.
+ * HSK_ERR_ARG (outputs untouched): a NULL context, pose or depth_out; xyz NULL with n > 0; n > 2^24; SURFEL without normals; a
+ * parameter that is not finite or outside its range; a pose hsk_invert_rigid refuses.  HSK_ERR_STATE: a slab of a group, or any
+ * context that stores part of its volume. */
+int hsk_splat_cloud(hsk_ctx* k, const float* xyz, const float* normals /* NULL: DISC only */, size_t n, const float pose[16],
+                    const hsk_splat_params* params /* NULL: the defaults */, uint16_t* depth_out /* width * height of the context */,
+                    hsk_splat_stats* stats /* may be NULL */);
+/* Defined by composition, bit for bit: for j ascending, hsk_integrate(k, hsk_splat_cloud's image of poses[j], width, height,
+ * poses[j]).  The cloud goes up once, the frames never leave the device, the host waits once at the end, and the views' counters
+ * come back in one copy.  Leaves the pose at poses[n_poses - 1], as the composition does; follow with hsk_resume_scan(k, that pose)
+ * to track a live sensor on in the imported volume.  n_poses = 0: HSK_OK and nothing changes; n = 0: the views are empty frames,
+ * which change no voxel.
+ * HSK_ERR_ARG (context and per_view untouched): hsk_splat_cloud's cases; poses NULL with n_poses > 0; n_poses > 65536; a pose
+ * hsk_invert_rigid refuses (the message names its index).  HSK_ERR_STATE: frames in flight; a slab of a group, or any context that
+ * stores part of its volume. */
+int hsk_import_cloud(hsk_ctx* k, const float* xyz, const float* normals /* NULL: DISC only */, size_t n, const float* poses /* 16 per view */,
+                     size_t n_poses, const hsk_splat_params* params, hsk_splat_stats* per_view /* n_poses of them, may be NULL */);
+
 /* ---- Surface components: the volume's pieces, labelled on the device, and the call that erases the small ones (DESIGN.md 3.16
  * the kernels, 8j the rule; tests/components_twin.py restates the rule in numpy).  All integers.  A voxel is INSIDE when it was
  * observed (weight != 0) with a NEGATIVE TSDF -- the voxels that can be the negative end of a zero crossing, so everything the
