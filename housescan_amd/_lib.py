@@ -266,6 +266,29 @@ class HskSplatStats(C.Structure):
     ]
 
 
+HSK_NORMAL_OK, HSK_NORMAL_INVALID, HSK_NORMAL_SPARSE, HSK_NORMAL_CROWDED, HSK_NORMAL_DEGENERATE = range(5)
+HSK_NORMAL_MAX_POINTS, HSK_NORMAL_MAX_VIEWPOINTS = 1 << 24, 256
+
+
+class HskNormalParams(C.Structure):
+    """Mirror of `hsk_normal_params` (include/hskinfu.h): 24 bytes; a 0 in a field means its default."""
+
+    _fields_ = [
+        ("radius_m", C.c_float), ("min_neighbours", C.c_uint32), ("max_neighbours", C.c_uint32), ("line_rel", C.c_float),
+        ("flags", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
+class HskNormalStats(C.Structure):
+    """Mirror of `hsk_normal_stats` (include/hskinfu.h): 32 bytes."""
+
+    _fields_ = [
+        ("n_ok", C.c_uint32), ("n_invalid", C.c_uint32), ("n_sparse", C.c_uint32), ("n_crowded", C.c_uint32), ("n_degenerate", C.c_uint32),
+        ("n_cells", C.c_uint32),
+        ("n_pairs", C.c_uint64),
+    ]
+
+
 HSK_COMPONENT_NONE = 0xFFFFFFFF
 HSK_COMPONENT_MAX = 1 << 24
 HSK_PRUNE_UNSEEN, HSK_PRUNE_FREE = 0, 1
@@ -669,6 +692,9 @@ SYMBOLS = {
     "hsk_default_splat_params": (None, [_P, C.POINTER(HskSplatParams)]),
     "hsk_splat_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _F, C.POINTER(HskSplatParams), _P, C.POINTER(HskSplatStats)]),
     "hsk_import_cloud": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskSplatParams), C.POINTER(HskSplatStats)]),
+    "hsk_default_normal_params": (None, [_P, C.POINTER(HskNormalParams)]),
+    "hsk_estimate_normals": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.POINTER(HskNormalParams), _P, _P, _P, _P, C.POINTER(HskNormalStats)]),
+    "hsk_normal_solve": (C.c_int, [C.POINTER(C.c_int64), _F, _P, C.c_size_t, C.c_float, _F, _F, _I]),
     "hsk_default_prune_params": (None, [_P, C.POINTER(HskPruneParams)]),
     "hsk_label_components": (C.c_int, [_P, C.POINTER(HskComponent), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(HskComponentStats)]),
     "hsk_download_components": (C.c_int, [_P, _P]),

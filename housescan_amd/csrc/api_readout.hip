@@ -341,6 +341,7 @@ extern "C" int hsk_prepare_readout(hsk_ctx* k, size_t product_bytes) {
   if (r == HSK_OK) HIPCHK(k, (hipError_t)texture_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)keytex_warm());
   if (r == HSK_OK) HIPCHK(k, (hipError_t)splat_warm());
+  if (r == HSK_OK) HIPCHK(k, (hipError_t)normals_warm());
   return r;
 }
 

@@ -199,7 +199,8 @@ struct hsk_ctx {
   // the scratch of every call that works on a cloud (align_scratch -> CloudScratch), made on first use and only grown: the
   // alignment's accumulators (align.hip: HSK_ALIGN_ACC_WORDS words), then the cloud's six planes, then what the call carves for
   // itself -- RelocScratch (api_reloc.hip), PlaneScratch (api_planes.hip), LevelScratch (api_level.hip) or SplatScratch
-  // (api_splat.hip: the z-buffer, a frame, the views' counters); h_align: the
+  // (api_splat.hip: the z-buffer, a frame, the views' counters) or NormalScratch (api_normals.hip: the cell table, the points in
+  // cell order, the outputs); h_align: the
   // accumulators' pinned host side
   void* d_align = nullptr;
   size_t align_bytes = 0;

@@ -554,3 +554,41 @@ void launch_splat_points(hipStream_t s, const float* soa, unsigned n, unsigned p
 void launch_splat_resolve(hipStream_t s, unsigned* zbuf, unsigned n_pixels, unsigned short* frame, unsigned* counts);
 void launch_splat_pose(hipStream_t s, TrackState* st, const SplatPose& pose);
 int splat_warm();     // loads splat.hip's code object (hsk_prepare_readout); a hipError_t
+
+// cloud normals (normals.hip): a fixed-radius neighbour search over the n <= 2^24 points of a cloud in the
+// alignment scratch's planes (the positions' three), and hsk_normal_point.h's solve at every point.
+// NormalIndex: the cell table -- mask + 1 slots, a power of two and at least 2 n; keys all ones, counts, cursor and words zeroed by
+// the caller -- and the points in cell order: sq, three planes `pitch` ints apart (the cloud's pitch) of q, and sidx, their
+// original indices.  words: [0 .. 4] the points by NORMAL_* class, [5] the sum of the reported neighbour counts, then
+#define NORMAL_W_CELLS 6   // the occupied cells
+#define NORMAL_W_ERROR 7   // not 0: a probe ran out of its bound, or a range left the cloud -- the call fails
+#define NORMAL_W_VALID 8   // the valid points (the scan's total)
+#define NORMAL_WORDS 16
+struct NormalIndex {
+  unsigned long long* keys;
+  unsigned* counts;
+  unsigned long long* off;  // hsk_scan_scratch_entries(mask + 1) entries: a cell's first place in cell order
+  unsigned* cursor;
+  unsigned* slot;           // n: a point's slot in the table, all ones for an invalid point
+  int* sq;
+  unsigned* sidx;
+  unsigned long long* words;
+  unsigned mask;
+};
+struct NormalArgs {
+  unsigned min_neighbours, max_neighbours, n_viewpoints;
+  float line_rel;
+};
+// the call's outputs on the device: normals 3 n floats (packed triples), the others n each
+struct NormalOut {
+  float* normals;
+  float* curvature;
+  unsigned* neighbours;
+  unsigned char* cls;
+};
+// index: the table, the scan, the points in cell order -- and the invalid points' outputs.  gather: every valid point's sums,
+// solve and outputs.  viewpoints: 3 floats each on the device, args.n_viewpoints of them.  Nothing is launched for n == 0.
+void launch_normal_index(hipStream_t s, const float* soa, unsigned n, unsigned pitch, int r_q, const NormalIndex& ix, const NormalOut& out);
+void launch_normal_gather(hipStream_t s, const float* soa, unsigned n, unsigned pitch, int r_q, const NormalArgs& args, const float* viewpoints,
+                          const NormalIndex& ix, const NormalOut& out);
+int normals_warm();   // loads normals.hip's code object (hsk_prepare_readout); a hipError_t

@@ -162,6 +162,37 @@ def default_splat_params(tracker=None, **fields):
     return _params(_SPLAT, tracker, None, fields)
 
 
+NORMAL_OK, NORMAL_INVALID, NORMAL_SPARSE, NORMAL_CROWDED, NORMAL_DEGENERATE = range(5)
+NORMAL_FIELDS = ("radius_m", "min_neighbours", "max_neighbours", "line_rel")
+_NORMAL = (_lib.HskNormalParams, "hsk_default_normal_params", NORMAL_FIELDS, "normal parameters have no field")
+
+
+def default_normal_params(tracker=None, **fields):
+    """the parameters of estimate_normals (hsk_default_normal_params): radius_m 3 x the tracker's largest cell, kept to 1 / 1024 ..
+    0.25 (without a tracker 9 / 512), min_neighbours 8, max_neighbours 4096, line_rel 1e-3; the keywords override its fields -> an
+    `_lib.HskNormalParams`"""
+    return _params(_NORMAL, tracker, None, fields)
+
+
+def _viewpoints(viewpoints):
+    vp = np.zeros((0, 3), np.float32) if viewpoints is None else np.ascontiguousarray(viewpoints, np.float32).reshape(-1, 3)
+    return vp, (vp.ctypes.data if len(vp) else None)
+
+
+def normal_solve(sums10, point, viewpoints=None, line_rel=1e-3):
+    """one point's normal from its neighbours' ten integer sums (hsk_normal_solve; host only, the device solve's mirror): sums10 = m,
+    S_x S_y S_z, S_xx S_xy S_xz S_yy S_yz S_zz of q_j - q_p with q = rint(coordinate * 4096); point [3] and viewpoints [v, 3] in metres
+    -> (normal [3] float32, curvature float32, class: NORMAL_OK or NORMAL_DEGENERATE)"""
+    s = np.ascontiguousarray(sums10, np.int64).reshape(10)
+    pt = np.ascontiguousarray(point, np.float32).reshape(3)
+    vp, pv = _viewpoints(viewpoints)
+    nrm, curv, cls = np.zeros(3, np.float32), np.zeros(1, np.float32), C.c_int()
+    if _lib.load().hsk_normal_solve(s.ctypes.data_as(C.POINTER(C.c_int64)), _fp(pt), pv, len(vp), float(line_rel), _fp(nrm), _fp(curv), C.byref(cls)) != 0:
+        raise KinfuError("normal_solve: invalid arguments (m outside 1..2^20, a sum out of range, more than 256 viewpoints, a value that "
+                         "is not finite or a line_rel outside (0, 1])")
+    return nrm, curv[0], cls.value
+
+
 COMPONENT_DTYPE = np.dtype(_lib.HskComponent)
 COMPONENT_NONE = 0xFFFFFFFF
 PRUNE_UNSEEN, PRUNE_FREE = 0, 1
@@ -1096,6 +1127,23 @@ class KinfuTracker:
         self._ck(self.lib.hsk_import_cloud(self.h, px, pn, len(pts), ps.ctypes.data if len(ps) else None, len(ps), C.byref(p),
                                            out.ctypes.data_as(C.POINTER(_lib.HskSplatStats)) if len(ps) else None))
         return out
+
+    # ---- cloud normals ------------------------------------------------------------------------------------
+    def estimate_normals(self, xyz, viewpoints=None, params=None, **fields):
+        """oriented normals and curvature of the cloud xyz [n, 3], which has none (hsk_estimate_normals): a fixed-radius
+        neighbourhood, integer sums, a binary64 solve, each normal turned to the nearest of viewpoints [v, 3] (None: its largest
+        component positive); params: an HskNormalParams (default: default_normal_params(self)), the keywords override its fields
+        -> (normals [n, 3] float32, curvature [n] float32, neighbours [n] uint32, classes [n] uint8 of NORMAL_*, stats dict).
+        Read-only"""
+        p = _params(_NORMAL, self, params, fields)
+        pts = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        vp, pv = _viewpoints(viewpoints)
+        n = len(pts)
+        nrm, curv = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        cnt, cls, st = np.zeros(n, np.uint32), np.zeros(n, np.uint8), _lib.HskNormalStats()
+        self._ck(self.lib.hsk_estimate_normals(self.h, pts.ctypes.data if n else None, n, pv, len(vp), C.byref(p), nrm.ctypes.data,
+                                               curv.ctypes.data, cnt.ctypes.data, cls.ctypes.data, C.byref(st)))
+        return nrm, curv, cnt, cls, _stats_dict(st)
 
     # ---- surface components ----------------------------------------------------------------------------
     def label_components(self):

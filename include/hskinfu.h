@@ -1070,6 +1070,65 @@ int hsk_splat_cloud(hsk_ctx* k, const float* xyz, const float* normals /* NULL: 
 int hsk_import_cloud(hsk_ctx* k, const float* xyz, const float* normals /* NULL: DISC only */, size_t n, const float* poses /* 16 per view */,
                      size_t n_poses, const hsk_splat_params* params, hsk_splat_stats* per_view /* n_poses of them, may be NULL */);
 
+/* ---- Cloud normals: oriented normals and curvature of a cloud that has none, on the device (DESIGN.md 3.28 the kernels, 8v the
+ * rule; tests/normals_twin.py restates the rule in numpy).  What a room directory's cloud_bin.pcd or another scanner's cloud needs
+ * before HSK_SPLAT_SURFEL, hsk_detect_planes_oriented, hsk_estimate_upright_oriented and hsk_align_cloud can take it.  A fixed-radius
+ * neighbourhood on the 1 / 4096 m grid of the plane moments, integer sums, a binary64 solve: the result is the same bits whatever
+ * the launch shape, and permuting the cloud permutes the outputs and changes no bit.  Per point p:
+ *   1. a coordinate that is not finite or beyond +-64 m: HSK_NORMAL_INVALID.  q = rint(4096 coordinate)
+ *   2. its neighbours: every valid point j with |q_j - q_p|^2 <= r_q^2 in integers, r_q = rint(4096 radius_m) -- the boundary, the
+ *      point itself and every duplicate included.  m of them
+ *   3. m < min_neighbours: HSK_NORMAL_SPARSE; m > max_neighbours: HSK_NORMAL_CROWDED, reported as max_neighbours + 1 -- the cost of a
+ *      call is the sum of m, and a dense cloud wants hsk_voxel_downsample or a smaller radius first
+ *   4. the covariance m S_ab - S_a S_b of the neighbours' q - q_p, exact in 64 bits; its eigenvalues e0 <= e1 <= e2 by eight cyclic
+ *      Jacobi sweeps in binary64.  Not e1 > line_rel e2: HSK_NORMAL_DEGENERATE (a collinear or coincident neighbourhood)
+ *   5. the normal: the eigenvector of e0 at length 1, turned towards the nearest of the viewpoints (the lowest index on a tie; one
+ *      standpoint per room makes each face of a shared wall turn to its own room); without viewpoints, or when the viewpoint lies
+ *      in the tangent plane, so that its component of largest magnitude is positive (the lowest index on a tie)
+ *   6. curvature = max(e0, 0) / (e0 + e1 + e2), the surface variation: 0 on a plane, at most 1 / 3
+ * Every class but HSK_NORMAL_OK has the normal (0, 0, 0) and the curvature 0; INVALID has the neighbour count 0.
+ *   Out of scope: colour, k-nearest neighbourhoods (a cap on WHICH neighbours count would depend on their order), normals
+ * propagated without a standpoint, outlier filters (threshold neighbours_out). */
+#define HSK_NORMAL_OK 0
+#define HSK_NORMAL_INVALID 1
+#define HSK_NORMAL_SPARSE 2
+#define HSK_NORMAL_CROWDED 3
+#define HSK_NORMAL_DEGENERATE 4
+#define HSK_NORMAL_MAX_POINTS ((size_t)1 << 24)
+#define HSK_NORMAL_MAX_VIEWPOINTS 256
+typedef struct hsk_normal_params {   /* a 0 in a field means its default */
+  float radius_m;           /* 1 / 1024 .. 0.25; default: 3 x the context's largest cell, clamped to that range (no context: 9 / 512) */
+  uint32_t min_neighbours;  /* >= 3; default 8                                                                                  */
+  uint32_t max_neighbours;  /* min_neighbours .. 2^20; default 4096                                                             */
+  float line_rel;           /* finite, 0 < line_rel <= 1; default 1e-3                                                          */
+  uint32_t flags;           /* 0                                                                                                */
+  uint32_t pad;
+} hsk_normal_params;        /* 24 bytes */
+typedef struct hsk_normal_stats {
+  uint32_t n_ok, n_invalid, n_sparse, n_crowded, n_degenerate;   /* the points by class: they sum to n                          */
+  uint32_t n_cells;         /* the occupied cells of the search grid (edge r_q)                                                 */
+  uint64_t n_pairs;         /* the sum of the reported neighbour counts: the work done                                          */
+} hsk_normal_stats;         /* 32 bytes */
+/* the defaults as values (k NULL: radius_m = 9 / 512) -- stated choices, not measurements */
+void hsk_default_normal_params(const hsk_ctx* k /* may be NULL */, hsk_normal_params* p);
+/* The normals of the cloud (n <= 2^24 packed xyz triples), synchronous; any idle context will do, its volume is not read.  Writes
+ * nothing of the context but scratch: pose, volume, deferred weights, model maps and image buffers stay bit for bit.  The cloud goes
+ * up once; nothing is allocated on a later call of the same size.  n = 0: HSK_OK, zero stats.  With CROWDED points the call still
+ * returns HSK_OK, and hsk_last_error says how many and what to do.
+ * HSK_ERR_ARG (outputs untouched): a NULL context or normals_out; xyz NULL with n > 0; n > 2^24; viewpoints NULL with n_viewpoints > 0;
+ * n_viewpoints > 256; a viewpoint that is not finite; a parameter that is not finite or outside its range; flags != 0.
+ * HSK_ERR_STATE: frames in flight; a slab of a group, or any context that stores part of its volume. */
+int hsk_estimate_normals(hsk_ctx* k, const float* xyz, size_t n, const float* viewpoints /* 3 each, may be NULL */, size_t n_viewpoints,
+                         const hsk_normal_params* params /* NULL: the defaults */, float* normals_out /* 3 n */,
+                         float* curvature_out /* n, may be NULL */, uint32_t* neighbours_out /* n, may be NULL */,
+                         uint8_t* class_out /* n, may be NULL */, hsk_normal_stats* stats /* may be NULL */);
+/* host only: one point's solve from its ten sums -- m, S_x S_y S_z, S_xx S_xy S_xz S_yy S_yz S_zz of the neighbours' q - q_p -- as the
+ * device does it (steps 4 to 6): *class_out HSK_NORMAL_OK or HSK_NORMAL_DEGENERATE.  HSK_ERR_ARG: a NULL pointer, m outside 1 .. 2^20,
+ * a sum beyond what m neighbours within 1024 grid steps can make, viewpoints NULL with n_viewpoints > 0, n_viewpoints > 256, a
+ * point or viewpoint that is not finite, a line_rel outside (0, 1]. */
+int hsk_normal_solve(const int64_t sums10[10], const float point[3], const float* viewpoints, size_t n_viewpoints, float line_rel,
+                     float normal_out[3], float* curvature_out, int* class_out);
+
 /* ---- Surface components: the volume's pieces, labelled on the device, and the call that erases the small ones (DESIGN.md 3.16
  * the kernels, 8j the rule; tests/components_twin.py restates the rule in numpy).  All integers.  A voxel is INSIDE when it was
  * observed (weight != 0) with a NEGATIVE TSDF -- the voxels that can be the negative end of a zero crossing, so everything the
